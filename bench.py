@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fwd+bwd Mpixels/s of the tri renderer at 1920x1080, 500k triangles (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5] [--dump-outputs DIR]
 
 (--config C3 is the tet renderer's step -- render_tets + render_tets_backward on the Kuhn lattice of BASELINE configs[2] --
 with its own roofline / cpu_baseline objects; the default and the headline metric are C4.)
@@ -57,7 +57,43 @@ def parse():
                     help="N > 1: tile-row bands of all views, or (view, band) pairs (auto: the latter when B > 1 and N %% B == 0)")
     ap.add_argument("--emulate-rank", default=None, metavar="R/N",
                     help="one process, no collective: time rank R's tile-row band of an N-rank run (for rocprofv3 traces of the per-rank work)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): color, depth "
+                         "(tet: and active) and grad_<input> of one rank rendering the whole frame; of a rank of a sharded or "
+                         "emulated run, the gradients of its all-reduce payload only.  At most 64 MB in all (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(dirpath: str, arrays, seed: int = 0):
+    """Writes every tensor of `arrays` (name -> tensor, any device) as dirpath/<name>.npy, float32 (float64 kept), and
+    returns {name: {"shape", "sample"}} for the result line.  Within DUMP_BUDGET_BYTES they are written whole; beyond it
+    the smallest arrays are kept whole and each larger one becomes a fixed sample, the same from run to run: the values at
+    the flat indices np.unique(np.random.default_rng(seed).integers(0, numel, k)), in index order ("sample" = k, None when
+    whole).  Between two runs of the same build the images are bit-identical; the gradients are sums whose order varies from
+    run to run and agree to float32 rounding."""
+    os.makedirs(dirpath, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BUDGET_BYTES - 256 * len(items)  # .npy headers
+    info = {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t if t.dtype in (th.float32, th.float64) else t.float()
+        n, esize = t.numel(), t.element_size()
+        k = min(n, left // (len(items) - i) // esize)
+        flat = t.reshape(-1)
+        sample = None
+        if k < n:
+            idx = np.unique(np.random.default_rng(seed).integers(0, n, k))
+            flat = flat[th.from_numpy(idx).to(flat.device)]
+            sample = int(k)
+        arr = flat.cpu().numpy() if sample is not None else flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+        left -= arr.nbytes
+        info[name] = {"shape": list(t.shape), "sample": sample}
+    return info
 
 
 def launch_ranks(n: int, argv, script=None, timeout_s: float = 3000.0) -> int:
@@ -120,6 +156,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     backend = os.environ.get("DMR_DIST_BACKEND", "nccl")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # no launcher around us: become one.  Nothing above has initialised the GPU (device_count() does not).
@@ -329,6 +367,22 @@ def main():
         collect()
         host_sync = "per call (default): the asynchronous steps overflowed their buffers and were discarded"
         o, g, dt, _ = timed(False)
+    # --dump-outputs: what the last timed step returned, before any later step reuses a buffer (`flat` is every step's)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        th.cuda.synchronize()
+        if world == 1 and not emu:
+            outs = dict(zip(("color", "depth", "active") if tet else ("color", "depth"), o[1:4] if tet else o[1:3]))
+            outs.update(("grad_" + k, t) for k, t in zip(GRADS, g))
+        else:  # a rank's images hold its own rows only: the all-reduced (emulated: this rank's) gradient payload
+            shapes = ((P, 3), (F,)) if tet else ((P, 3), (P, 3), (F,), (B, P), (B, F))
+            outs, at = {}, 0
+            for k, shp in zip(GRADS, shapes):
+                n = int(np.prod(shp))
+                outs["grad_" + k] = flat[at:at + n].view(shp)
+                at += n
+        dumped = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, outs)}
+        del outs
     if world > 1:
         tt = th.tensor([dt], dtype=th.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -633,6 +687,8 @@ def main():
         if tet:
             line["config"]["tets"] = int(d["tets"].shape[0])
         line.update(parity)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,8 +1,9 @@
 """Oracle-backed stand-in for `_C` on CPU tensors (TEST INFRASTRUCTURE ONLY).
 
 Same four functions and tuple arities as dmesh_renderer_amd._C / the reference ext.cpp:6-11, computed
-by the CPU oracle.  Used (a) to run the REFERENCE Python wrapper (read-only, /root/reference) over a
-`_C` in this GPU-less container and (b) to exercise dmesh_renderer_amd.sharding with the gloo backend.
+by the CPU oracle.  Used (a) to run our wrapper, and the REFERENCE Python wrapper when its golden fixtures are
+generated (tests/golden/gen_wrapper_fixtures.py), over a `_C` without a GPU and (b) to exercise
+dmesh_renderer_amd.sharding with the gloo backend.
 The product never imports this module.
 """
 from __future__ import annotations

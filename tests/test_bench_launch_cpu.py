@@ -61,3 +61,30 @@ def test_too_few_devices_is_an_error():
     env = dict(_clean_env(), DMR_DIST_BACKEND="nccl")
     r = _run(["--gpus", "2"], env=env)
     assert r.returncode != 0 and "HIP devices" in r.stderr
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files within the byte budget, small arrays whole, larger ones the same seeded sample
+    run after run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64_000)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"color": torch.rand(2, 3, 60, 70, generator=g), "active": torch.rand(2, 60, 70, generator=g) > 0.5,
+              "grad_faces_opacity": torch.randn(500, generator=g)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["active.npy", "color.npy", "grad_faces_opacity.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64_000
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert info["grad_faces_opacity"]["sample"] is None
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "grad_faces_opacity.npy"), arrays["grad_faces_opacity"].numpy())
+    k = info["color"]["sample"]
+    assert k is not None and 0 < k < arrays["color"].numel() and info["color"]["shape"] == [2, 3, 60, 70]
+    idx = np.unique(np.random.default_rng(0).integers(0, arrays["color"].numel(), k))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "color.npy"), arrays["color"].reshape(-1).numpy()[idx])

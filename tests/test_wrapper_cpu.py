@@ -1,13 +1,13 @@
 """Host-side mirror of the reference interface, checked on CPU with the oracle-backed `_C` stand-in:
   * our wrapper (dmesh_renderer_amd) routes arguments / gradients like the reference wrapper,
-  * when /root/reference is present (this container only), the REFERENCE wrapper itself is run over the
-    same stand-in and must agree exactly -- that is the drop-in proof for the Python boundary,
-  * both must reproduce the committed golden fixtures (tests/golden/wrapper_*.npz, generated by
-    tests/golden/gen_wrapper_fixtures.py from the reference wrapper).
+  * the REFERENCE wrapper's own run over the same stand-in is stored in tests/golden (outputs and gradients in
+    wrapper_*.npz, the argument descriptors of each of its `_C` calls in wrapper_calls.json, all written by
+    tests/golden/gen_wrapper_fixtures.py from a reference checkout): ours must agree with it exactly -- that is
+    the drop-in proof for the Python boundary,
+  * ours must reproduce the golden fixtures.
 """
+import json
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -18,7 +18,6 @@ from dmesh_renderer_amd import scenes
 from util import upstream_grads
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
 
 
 @pytest.fixture()
@@ -30,33 +29,17 @@ def ours(monkeypatch, oracle):
     return dmr
 
 
-def _reference_module():
-    """The reference wrapper, built from its audited SOURCE TEXT: the file is read, compiled and executed into a fresh
-    module object here -- the import machinery is never pointed at the reference tree (no sys.path entry), so its
-    __pycache__ bytecode is never executed and nothing is written there.  `dmesh_renderer._C` (the unbuilt CUDA
-    extension) is the oracle stand-in."""
-    path = os.path.join(REF, "dmesh_renderer", "__init__.py")
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present (GPU box)")
-    saved = {k: sys.modules.pop(k) for k in [k for k in sys.modules if k == "dmesh_renderer" or k.startswith("dmesh_renderer.")]}
-    dont_write = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True
-    try:
-        with open(path, "r") as f:
-            src = f.read()
-        mod = types.ModuleType("dmesh_renderer")
-        mod.__file__ = path
-        mod.__package__ = "dmesh_renderer"
-        mod.__path__ = []  # a package with nothing to find: `from . import _C` resolves through sys.modules only
-        sys.modules["dmesh_renderer"] = mod
-        sys.modules["dmesh_renderer._C"] = oracle_C
-        exec(compile(src, path, "exec", dont_inherit=True), mod.__dict__)
-        return mod
-    finally:
-        sys.dont_write_bytecode = dont_write
-        for k in [k for k in sys.modules if k == "dmesh_renderer" or k.startswith("dmesh_renderer.")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+def jsonable(calls):
+    """oracle_C.calls as stored in tests/golden/wrapper_calls.json (tuples become lists)."""
+    return json.loads(json.dumps(calls))
+
+
+def _reference_run(kind):
+    """What the reference wrapper returned and passed to `_C` on the scene of `kind` (tests/golden/gen_wrapper_fixtures.py)."""
+    g = np.load(os.path.join(GOLD, f"wrapper_{kind}.npz"))
+    with open(os.path.join(GOLD, "wrapper_calls.json")) as f:
+        calls = json.load(f)[kind]
+    return {k: th.from_numpy(g[k]) for k in g.files}, calls
 
 
 def _tri_run(mod, d, H, W):
@@ -113,27 +96,23 @@ def test_tet_call_protocol(ours):
 
 
 def test_tri_matches_reference_wrapper(ours):
-    ref = _reference_module()
-    d = _tri_scene()
-    oc, od, og = _tri_run(ours, d, TRI["H"], TRI["W"])
-    ours_calls = list(oracle_C.calls); oracle_C.calls.clear()
-    rc, rd, rg = _tri_run(ref, d, TRI["H"], TRI["W"])
-    assert th.equal(oc, rc) and th.equal(od, rd)
+    ref, ref_calls = _reference_run("tri")
+    oc, od, og = _tri_run(ours, _tri_scene(), TRI["H"], TRI["W"])
+    assert th.equal(oc, ref["color"]) and th.equal(od, ref["depth"])
+    assert sorted("grad_" + k for k in og) == sorted(k for k in ref if k.startswith("grad_"))
     for k in og:
-        assert th.equal(og[k], rg[k]), k
-    assert ours_calls == oracle_C.calls  # identical argument descriptors (order, dtype, shape, stride)
+        assert th.equal(og[k], ref["grad_" + k]), k
+    assert jsonable(oracle_C.calls) == ref_calls  # identical argument descriptors (order, dtype, shape, stride)
 
 
 def test_tet_matches_reference_wrapper(ours):
-    ref = _reference_module()
-    d = _tet_scene()
-    oc, od, oa, og = _tet_run(ours, d, TET["H"], TET["W"])
-    ours_calls = list(oracle_C.calls); oracle_C.calls.clear()
-    rc, rd, ra, rg = _tet_run(ref, d, TET["H"], TET["W"])
-    assert th.equal(oc, rc) and th.equal(od, rd) and th.equal(oa, ra)
+    ref, ref_calls = _reference_run("tet")
+    oc, od, oa, og = _tet_run(ours, _tet_scene(), TET["H"], TET["W"])
+    assert th.equal(oc, ref["color"]) and th.equal(od, ref["depth"]) and th.equal(oa, ref["active"])
+    assert sorted("grad_" + k for k in og) == sorted(k for k in ref if k.startswith("grad_"))
     for k in og:
-        assert th.equal(og[k], rg[k]), k
-    assert ours_calls == oracle_C.calls
+        assert th.equal(og[k], ref["grad_" + k]), k
+    assert jsonable(oracle_C.calls) == ref_calls
 
 
 def test_golden_fixtures(ours):
