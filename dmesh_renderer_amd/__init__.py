@@ -95,11 +95,12 @@ class _TriFn(th.autograd.Function):
 
 
 class _TetFn(th.autograd.Function):
-    """Gradients flow to verts_color and faces_opacity only (reference :407-422)."""
+    """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
+    faces_intense (beyond the reference)."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows):
+                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, full_grads=False):
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         topo = (tets, face_tets, tet_faces)
@@ -110,7 +111,7 @@ class _TetFn(th.autograd.Function):
             print("\nAn error occured in forward.")
             raise
         color, depth, active = out[0], out[1], out[2] > 0.5  # bool mask, reference :333
-        ctx.settings, ctx.rows = settings, rows
+        ctx.settings, ctx.rows, ctx.full_grads = settings, rows, full_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
         ctx.mark_non_differentiable(active)
         return color, depth, active
@@ -119,13 +120,18 @@ class _TetFn(th.autograd.Function):
     def backward(ctx, grad_color, grad_depth, _grad_active):
         saved = ctx.saved_tensors
         inputs, scratch = saved[:13], saved[13:17]
+        g_verts = g_fintense = None
         try:
-            g_vcolor, g_fopacity = _C.render_tets_backward(ctx.settings.bg, *inputs, grad_color, grad_depth,
-                                                           *scratch, rows=ctx.rows)
+            if ctx.full_grads:  # (the keyword is only passed when set: the default call is the reference's)
+                g_verts, g_vcolor, g_fopacity, g_fintense = _C.render_tets_backward(
+                    ctx.settings.bg, *inputs, grad_color, grad_depth, *scratch, rows=ctx.rows, full_grads=True)
+            else:
+                g_vcolor, g_fopacity = _C.render_tets_backward(ctx.settings.bg, *inputs, grad_color, grad_depth,
+                                                               *scratch, rows=ctx.rows)
         except Exception:
             print("\nAn error occured in backward.\n")
             raise
-        return (None, None, g_vcolor, g_fopacity) + (None,) * 9
+        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 6
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
@@ -136,10 +142,11 @@ def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0)):
-    """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices."""
+               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False):
+    """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads: see
+    TetRenderer."""
     return _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth,
-                        faces_intense, tets, face_tets, tet_faces, render_settings, tuple(rows))
+                        faces_intense, tets, face_tets, tet_faces, render_settings, tuple(rows), bool(full_grads))
 
 
 class TriRenderer(th.nn.Module):
@@ -166,14 +173,21 @@ class TetRenderer(th.nn.Module):
     faces are composited in exact depth order; gradients reach verts_color and faces_opacity only
     (reference README.md:4).
 
+    full_grads=True (beyond the reference, which has no such gradients): gradients also reach verts and
+    faces_intense.  On the forward's march each composited face enters through the ray's hit (t, u, v) on it: u, v
+    set its interpolated colour, t the hit point and so its ndc depth; the march itself (which faces, in which order)
+    and the opacities are constants of the gradient.  verts_depth (not read by this renderer) and the matrices get
+    none.  Costs a slower backward; the forward is the same.
+
     forward(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
             tets [T,4], face_tets [F,2] (-1 = none), tet_faces [T,4])
         -> color [B,3,H,W], depth [B,1,H,W], active bool [B,H,W]
     """
 
-    def __init__(self, render_settings: TetRenderSettings):
+    def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False):
         super().__init__()
         self.render_settings = render_settings
+        self.full_grads = bool(full_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
@@ -181,4 +195,5 @@ class TetRenderer(th.nn.Module):
         return render_tet(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
                           mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
                           verts_depth.to(**f32), faces_intense.to(**f32),
-                          tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings)
+                          tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
+                          full_grads=self.full_grads)

@@ -613,6 +613,14 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     Dims d;
     if (check_scene(s, true, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* full = nullptr;  // DMR_FLAG_TET_FULL_GRADS: [dL_dverts 3P | dL_dfintense BF], requested from the caller
+    if ((s->flags & DMR_FLAG_TET_FULL_GRADS) && 3 * (int64_t)s->P + (int64_t)d.BF > 0) {
+        if (!alloc) return fail("null argument");
+        const int64_t n = 3 * (int64_t)s->P + (int64_t)d.BF;
+        full = static_cast<float*>(alloc(ctx, DMR_BUF_TET_GRADS, (size_t)n * sizeof(float)));
+        if (!full) return fail("allocation of the tet gradient buffer failed");
+        dmr::launch_tet_zero_grads(full, 3 * (int64_t)s->P, full + 3 * (int64_t)s->P, (int64_t)d.BF, st);
+    }
     dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
     if (s->P == 0 || s->F == 0) return 0;
     if (!image_buf || !face_buf) return fail("null scratch buffer");
@@ -631,7 +639,8 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         auto it = g_size_cache.find(size_key(s, true, d));
         if (it != g_size_cache.end()) host_seq_steps = it->second.seq_steps;
     }
-    dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, img, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st);
+    dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, img, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
+                             full, full ? full + 3 * (int64_t)s->P : nullptr);
     DMR_HIP(hipGetLastError());
     return 0;
 }

@@ -182,6 +182,6 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
 // host_seq_steps (pinned, may be null): receives seq->max_steps, the next forward's capacity estimate.
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st);
+                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts = nullptr, float* dL_dfintense = nullptr);
 
 }  // namespace dmr

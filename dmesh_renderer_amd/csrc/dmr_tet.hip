@@ -528,14 +528,27 @@ k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ ou
 constexpr int TET_TBL = DMR_TET_TBL;     // slots (a multiple of 16)
 constexpr int TET_PROBES = 8;
 
+// Full gradients (DMR_FLAG_TET_FULL_GRADS, beyond the reference): the kernels below are instantiated a second time with
+// 20 values per (pixel, face) instead of 10 -- the 9 vertex-colour values, the opacity, then dL/d(the three vertex
+// positions) and dL/d(faces_intense[b, face]).  Their table has fewer slots: 384 x 20 f64 cells + keys = 61.5 KiB, two
+// workgroups per CU (the full re-marching kernel's 192 VGPRs allow two as well; the full sequence kernel has 147);
+// 512 slots would be 82 KiB, one.
+#ifndef DMR_TET_TBL_FULL
+#define DMR_TET_TBL_FULL 384
+#endif
+constexpr int TET_TBL_FULL = DMR_TET_TBL_FULL;  // (a multiple of 8: the full flush covers 8 slots per pass)
+constexpr int tet_nv(bool full) { return full ? 20 : 10; }
+constexpr int tet_tbl(bool full) { return full ? TET_TBL_FULL : TET_TBL; }
+
+template <int NS>
 struct TetAccum {
-    int* key; double (*val)[TET_TBL];
+    int* key; double (*val)[NS];
     __device__ __forceinline__ int find(int face) const {
-        uint32_t slot = __umulhi((uint32_t)face * 2654435761u, (uint32_t)TET_TBL);
+        uint32_t slot = __umulhi((uint32_t)face * 2654435761u, (uint32_t)NS);
         for (int i = 0; i < TET_PROBES; i++) {
             const int prev = atomicCAS(&key[slot], -1, face);
             if (prev == -1 || prev == face) return (int)slot;
-            slot = slot + 1u == (uint32_t)TET_TBL ? 0u : slot + 1u;
+            slot = slot + 1u == (uint32_t)NS ? 0u : slot + 1u;
         }
         return -1;
     }
@@ -569,6 +582,21 @@ __device__ __forceinline__ float ndc_depth(F3 pt, const float* __restrict__ mv, 
     const float cw = pr[3] * vx + pr[7] * vy + pr[11] * vz + pr[15];
     return cz * rcp(clamp_w(cw));
 }
+// d(ndc_depth(o + t d))/dt: cz and cw are affine in t; where clamp_w clamps cw, only cz's term is left
+__device__ __forceinline__ float ndc_depth_dt(F3 pt, F3 d, const float* __restrict__ mv, const float* __restrict__ pr) {
+    const float vx = mv[0] * pt.x + mv[4] * pt.y + mv[8] * pt.z + mv[12];
+    const float vy = mv[1] * pt.x + mv[5] * pt.y + mv[9] * pt.z + mv[13];
+    const float vz = mv[2] * pt.x + mv[6] * pt.y + mv[10] * pt.z + mv[14];
+    const float cz = pr[2] * vx + pr[6] * vy + pr[10] * vz + pr[14];
+    const float cw = pr[3] * vx + pr[7] * vy + pr[11] * vz + pr[15];
+    const float dx = mv[0] * d.x + mv[4] * d.y + mv[8] * d.z;
+    const float dy = mv[1] * d.x + mv[5] * d.y + mv[9] * d.z;
+    const float dz = mv[2] * d.x + mv[6] * d.y + mv[10] * d.z;
+    const float dcz = pr[2] * dx + pr[6] * dy + pr[10] * dz;
+    const float dcw = pr[3] * dx + pr[7] * dy + pr[11] * dz;
+    const float cwc = clamp_w(cw), inv = rcp(cwc);
+    return cwc == cw ? (dcz - cz * inv * dcw) * inv : dcz * inv;
+}
 }  // namespace tfast
 #pragma clang fp contract(off)
 
@@ -579,16 +607,40 @@ struct TetBwdPixel {
     float dpc0, dpc1, dpc2, dpd, bg_dot, bd_dot, final_prev_T, final_T, prev_log_T;
     float last_alpha, lc0, lc1, lc2, ar0, ar1, ar2, last_depth, ard;
     bool first_iter;
-    // -> g[0..8] = dL/d(vertex colours of the face), g[9] = dL/d(opacity); v0..v2: the face's vertices
+    // -> g[0..8] = dL/d(vertex colours of the face), g[9] = dL/d(opacity); v0..v2: the face's vertices.
+    // FULL: also g[10..18] = dL/d(vertex positions p0, p1, p2) and g[19] = dL/d(faces_intense[b, face]) (see full_grads).
+    template <bool FULL = false>
     __device__ __forceinline__ void face_grad(const TetParams& p, int b, int face, V3 ro, V3 rd, const float* __restrict__ mv,
-                                              const float* __restrict__ pr, float rt, float iu, float iv, float (&g)[10],
+                                              const float* __restrict__ pr, float rt, float iu, float iv, float (&g)[tet_nv(FULL)],
                                               int& v0, int& v1, int& v2) {
         const float4* cq = reinterpret_cast<const float4*>(p.colrec + face);
-        face_grad(ro, rd, mv, pr, rt, iu, iv, cq[0], cq[1], cq[2], cq[3], p.faces_intense[(int64_t)b * p.F + face], g, v0, v1, v2);
+        float4 f0 = {}, f1 = {}, f2 = {};
+        if constexpr (FULL) {  // the face's vertices
+            const float4* fq = reinterpret_cast<const float4*>(p.facerec + face);
+            f0 = fq[0]; f1 = fq[1]; f2 = fq[2];
+        }
+        face_grad<FULL>(ro, rd, mv, pr, rt, iu, iv, cq[0], cq[1], cq[2], cq[3], p.faces_intense[(int64_t)b * p.F + face], g, v0, v1, v2,
+                        f0, f1, f2);
     }
+    // The chain rule from the face's hit (t, u, v) to its vertices and intensity, given this step's weight w = prev_T * opacity.
+    // o + t d = (1-u-v) p0 + u p1 + v p2, differentiated implicitly: with E1 = p1 - p0, E2 = p2 - p0, P = d x E2,
+    // den = P . E1, dL/dp_k = b_k lambda, lambda = -(g_t (E1 x E2) + g_u P + g_v (E1 x d)) / den, b = (1-u-v, u, v).
+    // g_u, g_v: dL/du, dL/dv through the interpolated colour; g_t: dL/dt through the hit point's ndc depth.  The ray depends
+    // on the camera only, and opacities / transmittance do not depend on the positions.
+    template <class Vec>
+    __device__ __forceinline__ static void full_grads(Vec d, Vec E1, Vec E2, Vec P, float inv_den, float g_t, float g_u, float g_v,
+                                                      float i0, float i1, float i2, float g_int, float* __restrict__ g) {
+        const Vec lam = (-inv_den) * ((g_t * cross(E1, E2)) + (g_u * P) + (g_v * cross(E1, d)));
+        g[0] = i0 * lam.x; g[1] = i0 * lam.y; g[2] = i0 * lam.z;
+        g[3] = i1 * lam.x; g[4] = i1 * lam.y; g[5] = i1 * lam.z;
+        g[6] = i2 * lam.x; g[7] = i2 * lam.y; g[8] = i2 * lam.z;
+        g[9] = g_int;
+    }
+    template <bool FULL = false>
     __device__ __forceinline__ void face_grad(V3 ro, V3 rd, const float* __restrict__ mv, const float* __restrict__ pr, float rt,
                                               float iu, float iv, float4 cq0, float4 cq1, float4 cq2, float4 cq3, float intense,
-                                              float (&g)[10], int& v0, int& v1, int& v2) {
+                                              float (&g)[tet_nv(FULL)], int& v0, int& v1, int& v2,
+                                              float4 f0 = {}, float4 f1 = {}, float4 f2 = {}) {
         const V3 c0 = {cq0.x, cq0.y, cq0.z}, c1 = {cq0.w, cq1.x, cq1.y}, c2 = {cq1.z, cq1.w, cq2.x};
         v0 = __float_as_int(cq2.y); v1 = __float_as_int(cq2.z); v2 = __float_as_int(cq2.w);
         const float i0 = 1.0f - iu - iv, i1 = iu, i2 = iv;
@@ -625,11 +677,26 @@ struct TetBwdPixel {
         g[3] = i1 * dc0 * intense; g[4] = i1 * dc1 * intense; g[5] = i1 * dc2 * intense;
         g[6] = i2 * dc0 * intense; g[7] = i2 * dc1 * intense; g[8] = i2 * dc2 * intense;
         g[9] = dop;
+        if constexpr (FULL) {
+            const V3 craw = (i0 * c0) + (i1 * c1) + (i2 * c2);  // the interpolated colour before the intensity
+            const float w = opacity * prev_T;
+            const V3 dc = {dc0, dc1, dc2};  // dL/dcolour of the pixel * w
+            const float g_u = intense * dot(dc, c1 - c0), g_v = intense * dot(dc, c2 - c0);
+            const V3 md = {mv[0] * rd.x + mv[4] * rd.y + mv[8] * rd.z, mv[1] * rd.x + mv[5] * rd.y + mv[9] * rd.z,
+                           mv[2] * rd.x + mv[6] * rd.y + mv[10] * rd.z};  // d(view point)/dt
+            const float dcz = pr[2] * md.x + pr[6] * md.y + pr[10] * md.z, dcw = pr[3] * md.x + pr[7] * md.y + pr[11] * md.z;
+            const float dz_dt = (clamp_w(pn.w) == pn.w ? dcz - pdepth * dcw : dcz) * pw;
+            const V3 p0 = {f0.x, f0.y, f0.z}, E1 = V3{f0.w, f1.x, f1.y} - p0, E2 = V3{f1.z, f1.w, f2.x} - p0;
+            const V3 P = cross(rd, E2);
+            full_grads(rd, E1, E2, P, 1.0f / dot(P, E1), w * dpd * dz_dt, g_u, g_v, i0, i1, i2, w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z),
+                       g + 10);
+        }
     }
     // the same with tfast's arithmetic, from the face's records (k_tet_backward_seq)
+    template <bool FULL = false>
     __device__ __forceinline__ void face_grad_fast(V3 ro, V3 rd, const float* __restrict__ mv, const float* __restrict__ pr,
                                                    float4 f0, float4 f1, float4 f2, float4 cq0, float4 cq1, float4 cq2, float4 cq3,
-                                                   float intense, float (&g)[10], int& v0, int& v1, int& v2) {
+                                                   float intense, float (&g)[tet_nv(FULL)], int& v0, int& v1, int& v2) {
 #pragma clang fp contract(fast)
         using namespace tfast;
         const F3 o = {ro.x, ro.y, ro.z}, d = {rd.x, rd.y, rd.z};
@@ -660,6 +727,15 @@ struct TetBwdPixel {
         g[3] = i1 * dc0; g[4] = i1 * dc1; g[5] = i1 * dc2;
         g[6] = i2 * dc0; g[7] = i2 * dc1; g[8] = i2 * dc2;
         g[9] = dop;
+        if constexpr (FULL) {
+            const F3 p0 = {f0.x, f0.y, f0.z}, E1 = F3{f0.w, f1.x, f1.y} - p0, E2 = F3{f1.z, f1.w, f2.x} - p0;
+            const F3 P = cross(d, E2);
+            const F3 craw = (i0 * c0) + (i1 * c1) + (i2 * c2);
+            const F3 dc = {dc0, dc1, dc2};  // dL/dcolour of the pixel * w * intensity
+            const float w = opacity * prev_T;
+            full_grads(d, E1, E2, P, rcp(dot(P, E1)), w * dpd * ndc_depth_dt(o + (rt * d), d, mv, pr), dot(dc, c1 - c0),
+                       dot(dc, c2 - c0), i0, i1, i2, w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z), g + 10);
+        }
     }
 };
 
@@ -676,15 +752,21 @@ struct TetBwdPixel {
 // step were these merges).  Non-finite values never get here (tet_accumulate takes such lanes out first): 0 * inf would
 // leak NaN into the partner's face.
 #define DMR_TET_FMAC(N, DPP) "v_fmac_f32_dpp %[g" #N "], %[g" #N "], %[m] " DPP "\n\t"
-#define DMR_TET_MERGE(DPP)                                                                                              \
+// ten values g[0..9] of the array G (the full kernels merge their second ten, G = g + 10, with a block of their own)
+#define DMR_TET_MERGE10(DPP, G)                                                                                         \
     asm volatile("s_nop 1\n\t"                                                                                          \
                  DMR_TET_FMAC(0, DPP) DMR_TET_FMAC(1, DPP) DMR_TET_FMAC(2, DPP) DMR_TET_FMAC(3, DPP) DMR_TET_FMAC(4, DPP)  \
                  DMR_TET_FMAC(5, DPP) DMR_TET_FMAC(6, DPP) DMR_TET_FMAC(7, DPP) DMR_TET_FMAC(8, DPP) DMR_TET_FMAC(9, DPP)  \
-                 : [g0] "+v"(g[0]), [g1] "+v"(g[1]), [g2] "+v"(g[2]), [g3] "+v"(g[3]), [g4] "+v"(g[4]),                  \
-                   [g5] "+v"(g[5]), [g6] "+v"(g[6]), [g7] "+v"(g[7]), [g8] "+v"(g[8]), [g9] "+v"(g[9])                   \
+                 : [g0] "+v"(G[0]), [g1] "+v"(G[1]), [g2] "+v"(G[2]), [g3] "+v"(G[3]), [g4] "+v"(G[4]),                  \
+                   [g5] "+v"(G[5]), [g6] "+v"(G[6]), [g7] "+v"(G[7]), [g8] "+v"(G[8]), [g9] "+v"(G[9])                   \
                  : [m] "v"(m))
-template <int LEVEL>
-__device__ __forceinline__ void tet_merge_level(int lane, int& key, float (&g)[10]) {
+#define DMR_TET_MERGE(DPP)                                      \
+    do {                                                        \
+        DMR_TET_MERGE10(DPP, g);                                \
+        if constexpr (NV > 10) DMR_TET_MERGE10(DPP, (g + 10));  \
+    } while (0)
+template <int LEVEL, int NV>
+__device__ __forceinline__ void tet_merge_level(int lane, int& key, float (&g)[NV]) {
     constexpr int offset = 1 << LEVEL;
     constexpr int FROM_UPPER = LEVEL == 0 ? 0xB1 : (LEVEL == 1 ? 0x4E : (LEVEL == 2 ? 0x104 : 0x108));  // quad_perm ^1, ^2; row_shl:4, :8
     constexpr int FROM_LOWER = LEVEL == 0 ? 0xB1 : (LEVEL == 1 ? 0x4E : (LEVEL == 2 ? 0x114 : 0x118));  // ... row_shr:4, :8
@@ -700,8 +782,10 @@ __device__ __forceinline__ void tet_merge_level(int lane, int& key, float (&g)[1
     if (retire) key = -1;  // its values went to the partner (what it still holds is finite and is taken by nobody: its key says so)
 }
 
-__device__ __forceinline__ void tet_direct_atomics(const float (&g)[10], int face, int v0, int v1, int v2, float* __restrict__ dL_dvcolor,
-                                                   float* __restrict__ dL_dfopacity) {
+template <bool FULL = false>
+__device__ __forceinline__ void tet_direct_atomics(const float (&g)[tet_nv(FULL)], int face, int v0, int v1, int v2, float* __restrict__ dL_dvcolor,
+                                                   float* __restrict__ dL_dfopacity, float* __restrict__ dL_dverts = nullptr,
+                                                   float* __restrict__ dL_dfint_b = nullptr) {
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         atomicAdd(&dL_dvcolor[3 * v0 + c], g[c]);
@@ -709,21 +793,33 @@ __device__ __forceinline__ void tet_direct_atomics(const float (&g)[10], int fac
         atomicAdd(&dL_dvcolor[3 * v2 + c], g[6 + c]);
     }
     atomicAdd(&dL_dfopacity[face], g[9]);
+    if constexpr (FULL) {  // dL_dfint_b: the intensity row of this workgroup's view
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            atomicAdd(&dL_dverts[3 * v0 + c], g[10 + c]);
+            atomicAdd(&dL_dverts[3 * v1 + c], g[13 + c]);
+            atomicAdd(&dL_dverts[3 * v2 + c], g[16 + c]);
+        }
+        atomicAdd(&dL_dfint_b[face], g[19]);
+    }
 }
 
-__device__ __forceinline__ void tet_accumulate(const TetParams& p, const TetAccum& acc, double (*s_val)[TET_TBL], int lane, bool act,
-                                               int face, float (&g)[10], int v0, int v1, int v2, float* __restrict__ dL_dvcolor,
-                                               float* __restrict__ dL_dfopacity) {
-    if (act) {  // a lane with a non-finite value adds its ten values the reference's way and takes no part in the merges
+template <bool FULL = false>
+__device__ __forceinline__ void tet_accumulate(const TetParams& p, const TetAccum<tet_tbl(FULL)>& acc, double (*s_val)[tet_tbl(FULL)], int lane,
+                                               bool act, int face, float (&g)[tet_nv(FULL)], int v0, int v1, int v2,
+                                               float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity,
+                                               float* __restrict__ dL_dverts = nullptr, float* __restrict__ dL_dfint_b = nullptr) {
+    constexpr int NV = tet_nv(FULL);
+    if (act) {  // a lane with a non-finite value adds its values the reference's way and takes no part in the merges
         float chk = 0.f;
 #pragma unroll
-        for (int c = 0; c < 10; c++) chk = fmaf(g[c], 0.f, chk);
-        if (!(chk == 0.f)) { tet_direct_atomics(g, face, v0, v1, v2, dL_dvcolor, dL_dfopacity); act = false; }
+        for (int c = 0; c < NV; c++) chk = fmaf(g[c], 0.f, chk);
+        if (!(chk == 0.f)) { tet_direct_atomics<FULL>(g, face, v0, v1, v2, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b); act = false; }
     }
     int key = act ? face : -1;  // -1: nothing (left) in this lane
     if (!act) {
 #pragma unroll
-        for (int c = 0; c < 10; c++) g[c] = 0.f;
+        for (int c = 0; c < NV; c++) g[c] = 0.f;
     }
     tet_merge_level<0>(lane, key, g);
     tet_merge_level<1>(lane, key, g);
@@ -734,23 +830,40 @@ __device__ __forceinline__ void tet_accumulate(const TetParams& p, const TetAccu
     const int slot = (DMR_DBG(p, 2048) && (face & 1)) ? -1 : acc.find(face);
     if (slot >= 0) {
 #pragma unroll
-        for (int c = 0; c < 10; c++) atomicAdd(&s_val[c][slot], (double)g[c]);
+        for (int c = 0; c < NV; c++) atomicAdd(&s_val[c][slot], (double)g[c]);
     } else {
-        tet_direct_atomics(g, face, v0, v1, v2, dL_dvcolor, dL_dfopacity);
+        tet_direct_atomics<FULL>(g, face, v0, v1, v2, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
     }
 }
 
-// flush of the tile's table: 16 lanes per slot (10 used): lanes 0-8 -> the three vertex-colour rows, lane 9 -> opacity
-__device__ __forceinline__ void tet_flush(const TetParams& p, const int* s_key, double (*s_val)[TET_TBL], int tid,
-                                          float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity) {
-    const int sub = tid & 15;
-    for (int s0 = 0; s0 < TET_TBL; s0 += 16) {
-        const int slot = s0 + (tid >> 4);
-        const int face = s_key[slot];
-        if (face < 0 || sub > 9) continue;
-        const float v = (float)s_val[sub][slot];
-        if (sub < 9) atomicAdd(&dL_dvcolor[3 * p.faces[3 * face + sub / 3] + sub % 3], v);
-        else atomicAdd(&dL_dfopacity[face], v);
+// flush of the tile's table: 16 lanes per slot (10 used): lanes 0-8 -> the three vertex-colour rows, lane 9 -> opacity;
+// FULL: 32 lanes per slot (20 used), lanes 10-18 -> the three vertex-position rows, lane 19 -> the view's intensity row
+template <bool FULL = false>
+__device__ __forceinline__ void tet_flush(const TetParams& p, const int* s_key, double (*s_val)[tet_tbl(FULL)], int tid,
+                                          float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity,
+                                          float* __restrict__ dL_dverts = nullptr, float* __restrict__ dL_dfint_b = nullptr) {
+    if constexpr (!FULL) {
+        const int sub = tid & 15;
+        for (int s0 = 0; s0 < TET_TBL; s0 += 16) {
+            const int slot = s0 + (tid >> 4);
+            const int face = s_key[slot];
+            if (face < 0 || sub > 9) continue;
+            const float v = (float)s_val[sub][slot];
+            if (sub < 9) atomicAdd(&dL_dvcolor[3 * p.faces[3 * face + sub / 3] + sub % 3], v);
+            else atomicAdd(&dL_dfopacity[face], v);
+        }
+    } else {
+        const int sub = tid & 31;
+        for (int s0 = 0; s0 < TET_TBL_FULL; s0 += 8) {
+            const int slot = s0 + (tid >> 5);
+            const int face = s_key[slot];
+            if (face < 0 || sub > 19) continue;
+            const float v = (float)s_val[sub][slot];
+            if (sub < 9) atomicAdd(&dL_dvcolor[3 * p.faces[3 * face + sub / 3] + sub % 3], v);
+            else if (sub == 9) atomicAdd(&dL_dfopacity[face], v);
+            else if (sub < 19) atomicAdd(&dL_dverts[3 * p.faces[3 * face + (sub - 10) / 3] + (sub - 10) % 3], v);
+            else atomicAdd(&dL_dfint_b[face], v);
+        }
     }
 }
 
@@ -788,27 +901,38 @@ __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px,
 // (Launched with a few workgroups per CU that loop over the band's tiles, not one per tile: when it is the idle one of the
 // two launches -- every call but the first of a view configuration -- 2 500 workgroups that only find that out cost 6.7 us
 // at C3, 768 cost under 2.)
+// Full: no type (the default), or float*, float* -- dL_dverts [P,3] and dL_dfintense [B,F] of the full gradients
+// (DMR_FLAG_TET_FULL_GRADS), which this instantiation accumulates as well (the default one's code is unchanged by them).
+template <class... Full>
 __global__ void __launch_bounds__(256)
 k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
-               float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity) {
+               float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, Full... full) {
+    constexpr bool FULL = sizeof...(Full) != 0;
+    constexpr int NV = tet_nv(FULL), NS = tet_tbl(FULL);
     {
         const uint32_t cap = p.img.seq->cap_steps;
         if (cap != 0u && p.img.seq->max_steps <= cap && !DMR_DBG(p, 8192)) return;  // uniform: k_tet_backward_seq does this call's work
     }
-    __shared__ int s_key[TET_TBL];
-    __shared__ double s_val[10][TET_TBL];
+    __shared__ int s_key[NS];
+    __shared__ double s_val[NV][NS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const TetAccum acc{s_key, s_val};
+    const TetAccum<NS> acc{s_key, s_val};
     const int ntiles = p.gx * rows * p.B;
     for (int ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {   // tiles of the band [r0, r0 + rows), all views
         __syncthreads();  // (the previous tile's flush has read the table)
-        for (int i = tid; i < TET_TBL; i += 256) {
+        for (int i = tid; i < NS; i += 256) {
             s_key[i] = -1;
 #pragma unroll
-            for (int c = 0; c < 10; c++) s_val[c][i] = 0.0;
+            for (int c = 0; c < NV; c++) s_val[c][i] = 0.0;
         }
         __syncthreads();
         const int tx = ti % p.gx, ty = (ti / p.gx) % rows + p.r0, b = ti / (p.gx * rows);
+        float* dL_dverts = nullptr;
+        float* dL_dfint_b = nullptr;  // the intensity row of the tile's view
+        if constexpr (FULL) {
+            float* const out[] = {full...};
+            dL_dverts = out[0]; dL_dfint_b = out[1] + (int64_t)b * p.F;
+        }
         const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
         TetBwdPixel st;
         V3 ro = {0, 0, 0}, rd = {0, 0, 0};
@@ -835,23 +959,25 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
         }
         while (!__all(done)) {  // the wave's lanes stay together: tet_accumulate merges lanes that hold the same face
             const bool act = !done;
-            float g[10];
+            float g[NV];
             int v0 = 0, v1 = 0, v2 = 0;
             const int face = curr_face;
             if (act) {
-                st.face_grad(p, b, curr_face, ro, rd, mv, pr, curr_rt, curr_iu, curr_iv, g, v0, v1, v2);
+                st.face_grad<FULL>(p, b, curr_face, ro, rd, mv, pr, curr_rt, curr_iu, curr_iv, g, v0, v1, v2);
                 if (curr_face == first_face) done = true;
                 if (!done) {
                     if (curr_tet == -1) done = true;
                     else if (!march_step<false>(p, ro, rd, curr_face, curr_tet, curr_slot, curr_rt, curr_iu, curr_iv, curr_dn)) done = true;
                 }
             }
-            tet_accumulate(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity);
+            tet_accumulate<FULL>(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
         }
         __syncthreads();
-        tet_flush(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity);
+        tet_flush<FULL>(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
     }
 }
+
+
 
 // The backward on the forward's march sequence (dmr_kernels.hpp): a wave walks its rows from the back, step s of all its
 // pixels in the same iteration (a pixel joins at its own last step), one contiguous kilobyte per four steps.  Per step and
@@ -859,25 +985,35 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
 // picked, here with contracted arithmetic (tfast: nothing is decided by it) -- instead of the tet record, three candidate
 // records, three tests and the orientation logic.  Stops where the reference stops: behind first_face, or behind an entry
 // whose bit 31 says the reverse march would find two candidates there.
+// Full: as k_tet_backward's
+template <class... Full>
 __global__ void __launch_bounds__(256, DMR_TET_BWD_WAVES)
 k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
-                   float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, uint32_t* __restrict__ host_seq_steps) {
+                   float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, uint32_t* __restrict__ host_seq_steps, Full... full) {
+    constexpr bool FULL = sizeof...(Full) != 0;
+    constexpr int NV = tet_nv(FULL), NS = tet_tbl(FULL);
     const uint32_t seq_cap = p.img.seq->cap_steps, longest = p.img.seq->max_steps;
     if (host_seq_steps && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
         *host_seq_steps = longest;  // pinned: the next forward's capacity estimate (whichever kernel does the work)
     if (seq_cap == 0u || longest > seq_cap || DMR_DBG(p, 8192)) return;  // uniform: no complete sequence, k_tet_backward re-marches
-    __shared__ int s_key[TET_TBL];
-    __shared__ double s_val[10][TET_TBL];
+    __shared__ int s_key[NS];
+    __shared__ double s_val[NV][NS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < TET_TBL; i += 256) {
+    for (int i = tid; i < NS; i += 256) {
         s_key[i] = -1;
 #pragma unroll
-        for (int c = 0; c < 10; c++) s_val[c][i] = 0.0;
+        for (int c = 0; c < NV; c++) s_val[c][i] = 0.0;
     }
     __syncthreads();
-    const TetAccum acc{s_key, s_val};
+    const TetAccum<NS> acc{s_key, s_val};
 
     const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
+    float* dL_dverts = nullptr;
+    float* dL_dfint_b = nullptr;  // a workgroup is one tile of one view: the view's intensity row
+    if constexpr (FULL) {
+        float* const out[] = {full...};
+        dL_dverts = out[0]; dL_dfint_b = out[1] + (int64_t)b * p.F;
+    }
     const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
     TetBwdPixel st;
     V3 ro = {0, 0, 0}, rd = {0, 0, 0};
@@ -931,13 +1067,14 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
             load_recs(done ? 0xffffffffu : e_nxt, nxt);             // in flight during step s
             const bool act = !done && e_cur != 0xffffffffu;
             const int face = (int)(e_cur & 0x7fffffffu);
-            float g[10];
+            float g[NV];
             int v0 = 0, v1 = 0, v2 = 0;
             if (act) {  // (t, u, v) of the ray on this face, then the face's gradient
-                st.face_grad_fast(ro, rd, mv, pr, cur.f0, cur.f1, cur.f2, cur.c0, cur.c1, cur.c2, cur.c3, cur.intense, g, v0, v1, v2);
+                st.face_grad_fast<FULL>(ro, rd, mv, pr, cur.f0, cur.f1, cur.f2, cur.c0, cur.c1, cur.c2, cur.c3, cur.intense, g, v0, v1, v2);
                 if (face == first_face || (e_cur & 0x80000000u)) done = true;
             }
-            tet_accumulate(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity);
+            if constexpr (FULL) tet_accumulate<true>(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
+            else tet_accumulate(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity);  // (captures nothing more)
             e_cur = e_nxt;
             return __all(done);
         };
@@ -947,8 +1084,10 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
         }
     }
     __syncthreads();
-    tet_flush(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity);
+    tet_flush<FULL>(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
 }
+
+
 
 static TetParams make_params(const dmr_scene& s, int gx, int gy, int r0, TetImageState img) {
     TetParams p;
@@ -1016,13 +1155,20 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
 
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st) {
+                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense) {
     if (r1 <= r0) return;
     TetParams p = make_params(s, gx, gy, r0, img);
     StageScope t(DMR_STAGE_TET_BACKWARD, st);
-    k_tet_backward_seq<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps);
     const int ntiles = gx * (r1 - r0) * s.B;
-    k_tet_backward<<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity);
+    if (!dL_dverts) {
+        k_tet_backward_seq<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps);
+        k_tet_backward<><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity);
+    } else {
+        k_tet_backward_seq<float*, float*><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity,
+                                                                             host_seq_steps, dL_dverts, dL_dfintense);
+        k_tet_backward<float*, float*><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor,
+                                                                                         dL_dfopacity, dL_dverts, dL_dfintense);
+    }
 }
 
 }  // namespace dmr

@@ -18,6 +18,8 @@
 //   fill_outside=True        render_tris: zero the pixels outside the band (False: leave them uninitialised)
 //   flat_out=None            backward: one caller-owned fp32 buffer receiving the gradients back to back (the payload
 //                            of the one all-reduce in sharding.py); the returned tensors are views into it
+//   full_grads=False         render_tets_backward: also dL_dverts and dL_dfaces_intense (DMR_FLAG_TET_FULL_GRADS, beyond
+//                            the reference) -> (dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dfaces_intense)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -171,7 +173,8 @@ c10::Device hip_device_of(const at::Tensor& verts) {
 // (render.cu:18-24,91-100), plus the backward's transient workspace
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, 5> buf;
+    std::array<at::Tensor, 6> buf;
+    at::Tensor tet_grads;  // where DMR_BUF_TET_GRADS is served from (an output, not scratch), if defined
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -179,7 +182,11 @@ struct Scratch {
 };
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
-    if (which < 0 || which >= 5) return nullptr;
+    if (which < 0 || which >= 6) return nullptr;
+    if (which == DMR_BUF_TET_GRADS) {  // the caller's gradient tensor, which the library fills
+        const at::Tensor& t = s->tet_grads;
+        return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
+    }
     try {
         s->buf[which] = at::empty({(int64_t)std::max<size_t>(nbytes, 1)}, at::TensorOptions().dtype(at::kByte).device(s->dev));
         return s->buf[which].data_ptr();
@@ -343,9 +350,12 @@ TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, con
                           call.scratch.get(DMR_BUF_BINNING), call.scratch.get(DMR_BUF_IMAGE));
 }
 
-// -> (dL_dverts_color [P,3], dL_dfaces_opacity [F])
+// -> (dL_dverts_color [P,3], dL_dfaces_opacity [F]), or with full_grads
+//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F])
 using TetBwdOut = std::tuple<at::Tensor, at::Tensor>;
-TetBwdOut render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+using TetBwdFullOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+template <bool FULL>
+std::conditional_t<FULL, TetBwdFullOut, TetBwdOut> tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                                const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets,
@@ -359,23 +369,55 @@ TetBwdOut render_tets_backward(const at::Tensor& background, const at::Tensor& v
     Call call(dev, background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth,
               faces_intense, H, W, &tets, &face_tets, &tet_faces, 0, rows);
     const at::Tensor gc = f32(grad_color, "grad_color"), gd = f32(grad_depth, "grad_depth");
-    const int64_t P = call.sc.P, F = call.sc.F;
-    at::Tensor g_vcolor, g_fop;
+    const int64_t P = call.sc.P, F = call.sc.F, B = call.sc.B;
+    // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from this tensor.  With flat_out
+    // the layout is [dL_dverts_color 3P | dL_dfaces_opacity F | dL_dverts 3P | dL_dfaces_intense BF]: the default layout
+    // followed by that buffer, so one all-reduce still carries everything.
+    const int64_t n = 3 * P + F + (FULL ? 3 * P + B * F : 0);
+    at::Tensor g_vcolor, g_fop, g_full;
     if (!flat_out.has_value()) {
         g_vcolor = at::empty({P, 3}, f32_on(dev)); g_fop = at::empty({F}, f32_on(dev));
+        if (FULL) g_full = at::empty({3 * P + B * F}, f32_on(dev));
     } else {
         const at::Tensor& fo = *flat_out;
-        if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != 3 * P + F)
-            err("flat_out must be a contiguous float32 tensor of " + std::to_string(3 * P + F) + " elements on " + dev.str());
+        if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != n)
+            err("flat_out must be a contiguous float32 tensor of " + std::to_string(n) + " elements on " + dev.str());
         const at::Tensor flat = fo.view({-1});
         g_vcolor = flat.narrow(0, 0, 3 * P).view({P, 3}); g_fop = flat.narrow(0, 3 * P, F);
+        if (FULL) g_full = flat.narrow(0, 3 * P + F, 3 * P + B * F);
+    }
+    if (FULL) {
+        call.scratch.tet_grads = g_full;
+        call.sc.flags |= DMR_FLAG_TET_FULL_GRADS;
     }
     const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     if (g_abi.tet_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), mptr<const void>(pb), mptr<const void>(fb),
                            mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g_vcolor), mptr<float>(g_fop), &alloc_cb,
                            &call.scratch, call.stream()))
         raise_lib();
-    return TetBwdOut(g_vcolor, g_fop);
+    if constexpr (FULL)
+        return TetBwdFullOut(g_full.narrow(0, 0, 3 * P).view({P, 3}), g_vcolor, g_fop, g_full.narrow(0, 3 * P, B * F).view({B, F}));
+    else
+        return TetBwdOut(g_vcolor, g_fop);
+}
+
+// the binding: without full_grads exactly the reference's function (render.cu:338-412)
+py::object render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
+                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
+                                const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets,
+                                const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
+                                const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
+                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                                bool full_grads) {
+    auto run = [&](auto full) {
+        py::gil_scoped_release nogil;
+        return tets_backward<decltype(full)::value>(background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats,
+                                                    inv_proj_mats, verts_depth, faces_intense, tets, face_tets, tet_faces, grad_color,
+                                                    grad_depth, pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out);
+    };
+    if (full_grads) return py::cast(run(std::true_type{}));
+    return py::cast(run(std::false_type{}));
 }
 
 // ---- extensions -----------------------------------------------------------------------------------------------------
@@ -457,7 +499,7 @@ PYBIND11_MODULE(_C, m) {
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
           py::arg("grad_color"), py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"),
-          py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::call_guard<py::gil_scoped_release>());
+          py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("full_grads") = false);
     m.def("invert_mats", &invert_mats);
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));

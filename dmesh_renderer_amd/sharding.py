@@ -420,7 +420,7 @@ class ShardedTriRenderer(th.nn.Module):
 class _ShardedTetFn(th.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, group, bands, impl):
+                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, group, bands, impl, full_grads=False):
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         topo = (tets, face_tets, tet_faces)
@@ -430,7 +430,7 @@ class _ShardedTetFn(th.autograd.Function):
         if bands is not None and _world(group) > 1:
             color, depth, active = gather_bands((color, depth, active), bands, dist.get_rank(group), group)
         active = active > 0.5  # bool mask, reference __init__.py:333
-        ctx.settings, ctx.rows, ctx.group, ctx.impl = settings, rows, group, impl
+        ctx.settings, ctx.rows, ctx.group, ctx.impl, ctx.full_grads = settings, rows, group, impl, full_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
         ctx.mark_non_differentiable(active)
         return color, depth, active
@@ -439,29 +439,40 @@ class _ShardedTetFn(th.autograd.Function):
     def backward(ctx, grad_color, grad_depth, _grad_active):
         saved = ctx.saved_tensors
         verts, faces = saved[0], saved[1]
-        P, F = verts.size(0), faces.size(0)
+        P, F, B = verts.size(0), faces.size(0), saved[4].size(0)
+        full = {"full_grads": True} if ctx.full_grads else {}  # (the keyword only when set: the default call is unchanged)
+        g_verts = g_fintense = None
         if getattr(ctx.impl, "SUPPORTS_FLAT_OUT", False):
-            flat = th.empty(3 * P + F, dtype=th.float32, device=verts.device)  # [dL_dverts_color 3P | dL_dfaces_opacity F]
-            g_vcolor, g_fopacity = ctx.impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth,
-                                                                 *saved[13:17], rows=ctx.rows, flat_out=flat)
+            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F]
+            n = 3 * P + F + (3 * P + B * F if ctx.full_grads else 0)
+            flat = th.empty(n, dtype=th.float32, device=verts.device)
+            g = ctx.impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth,
+                                              *saved[13:17], rows=ctx.rows, flat_out=flat, **full)
             if _world(ctx.group) > 1:
                 dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
         else:
             g = ctx.impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth, *saved[13:17],
-                                              rows=ctx.rows)
-            g_vcolor, g_fopacity = allreduce_grads(g, ctx.group)
-        return (None, None, g_vcolor, g_fopacity) + (None,) * 12
+                                              rows=ctx.rows, **full)
+            g = allreduce_grads(g, ctx.group)
+        if ctx.full_grads:
+            g_verts, g_vcolor, g_fopacity, g_fintense = g
+        else:
+            g_vcolor, g_fopacity = g
+        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 9
 
 
 class ShardedTetRenderer(th.nn.Module):
     """TetRenderer whose image is sharded by tile-row bands across the ranks of `group` ("the tet path
     shards identically"): every rank bins with rects clipped to its band, finds first hits and marches the rays of
-    its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F].
+    its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F]
+    (full_grads: followed by [dL_dverts 3P | dL_dfaces_intense B*F], see TetRenderer).
     Same call signature and outputs as TetRenderer (color, depth, active bool)."""
 
-    def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None):
+    def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
+                 full_grads: bool = False):
         super().__init__()
         self.render_settings = render_settings
+        self.full_grads = bool(full_grads)
         self.group = group
         self.assemble = assemble
         if impl is None:
@@ -491,4 +502,4 @@ class ShardedTetRenderer(th.nn.Module):
                                    mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
                                    verts_depth.to(**f32), faces_intense.to(**f32),
                                    tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32),
-                                   self.render_settings, rows, self.group, bands, self.impl)
+                                   self.render_settings, rows, self.group, bands, self.impl, self.full_grads)

@@ -39,7 +39,8 @@ extern "C" {
  * binningBuffer / imageBuffer (rasterizer.h:14-17): opaque byte buffers that the
  * caller owns, returns from forward and passes back to backward.  DMR_BUF_WORK is a
  * transient workspace of the backward calls (packed gradient accumulators). */
-enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE = 3, DMR_BUF_WORK = 4 };
+enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE = 3, DMR_BUF_WORK = 4,
+       DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -49,7 +50,8 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * entries, not 4 GiB for its tiles; the reference's binning buffer scales with R only) -- plus, tet only, the forward's march sequence for
  * the backward: 4 bytes per tile pixel (256 Nt of them) and step of capacity, capacity = the longest march of the previous
  * call with the same view configuration * 1.25 + 4 steps (0 in the first such call), the whole capped at 16 GiB;
- * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record. */
+ * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS only)
+ * 4 (3P + BF), exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -105,6 +107,9 @@ typedef struct dmr_scene {
  *     step with a default (waiting) call, which refreshes the estimate.  Needs one earlier default call with the same
  *     view configuration (the warm-up before a capture), else it fails. */
 #define DMR_FLAG_ASYNC 1
+/* dmr_tet_backward also computes dL/dverts and dL/dfaces_intense (beyond the reference, whose tet renderer has no such
+ * gradients); see dmr_tet_backward.  Ignored by every other call. */
+#define DMR_FLAG_TET_FULL_GRADS 2
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -133,7 +138,14 @@ int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float
 int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, float* out_active,
                     dmr_alloc_fn alloc, void* alloc_ctx, void* stream, int* num_rendered);
 
-/* dL_dvcolor [P,3], dL_dfopacity [F], fully overwritten. */
+/* dL_dvcolor [P,3], dL_dfopacity [F], fully overwritten.
+ * With DMR_FLAG_TET_FULL_GRADS in scene->flags, the call also requests buffer DMR_BUF_TET_GRADS through `alloc`, once, of
+ * 4 (3P + BF) bytes, and fully overwrites it with [dL_dverts [P,3] | dL_dfintense [B,F]] (fp32): the gradients of the
+ * vertex positions and face intensities along the forward's march (each marched face enters through its hit (t, u, v):
+ * u, v set the interpolated colour, t the hit point's ndc depth; opacities and transmittance do not depend on the
+ * positions).  The buffer is caller-owned like the others; no host wait is added (DMR_FLAG_ASYNC and stream capture work
+ * as without the flag).  verts_depth and the matrices get no gradient (the tet renderer does not read verts_depth).
+ * Without the flag the call is exactly as before and requests no buffer. */
 int dmr_tet_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,

@@ -6,6 +6,7 @@ from dmesh_renderer_amd import _C, scenes
 
 ap = argparse.ArgumentParser(); ap.add_argument("--m", type=int, default=16); ap.add_argument("--size", type=int, default=800)
 ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--full-grads", action="store_true", help="backward with dL/dverts and dL/dfaces_intense (TetRenderer(full_grads=True))")
 a = ap.parse_args()
 dev = th.device("cuda:0"); H = W = a.size
 d = scenes.kuhn_tets(a.m, 1, H, W)
@@ -13,7 +14,7 @@ args = scenes.c_args(d, dev, tet=True)
 gc, gd = scenes.upstream_grads(1, H, W); gc, gd = gc.to(dev), gd.to(dev)
 def step():
     o = _C.render_tets(*args, H, W, 0)
-    g = _C.render_tets_backward(*args, gc, gd, *o[3:7])
+    g = _C.render_tets_backward(*args, gc, gd, *o[3:7], **({"full_grads": True} if a.full_grads else {}))
     return o, g
 for _ in range(3): step()
 _C.profile_enable(0xFFFFFFFF); th.cuda.synchronize(); t0 = time.perf_counter()
