@@ -122,6 +122,28 @@ size_t carve_binning(void* b, size_t R, size_t mask_tiles, size_t seq_tiles, siz
 
 struct Dims { int gx, gy, r0, r1, ntiles; size_t BP, BF, npix; };
 
+// The four scratch buffers of a call (null buffers: sizes only, null pointers).  The binning buffer as the backward passes and
+// dmr_export see it: its lists of R entries (run_forward carves the forward's, with its capacity, itself).
+struct Scratch { PointState ps; FaceState fs; ImageState is; BinningState bs; size_t point_bytes, face_bytes, image_bytes; };
+Scratch carve_scratch(const dmr_scene* s, bool tet, const Dims& d, const void* pb, const void* fb, const void* ib,
+                      const void* bb = nullptr, size_t R = 0) {
+    Scratch c;
+    c.point_bytes = carve_point(const_cast<void*>(pb), d.BP, c.ps);
+    c.face_bytes = carve_face(const_cast<void*>(fb), d.BF, (size_t)s->F, (size_t)s->T, tet, c.fs);
+    c.image_bytes = carve_image(const_cast<void*>(ib), (size_t)s->B, (size_t)d.ntiles, d.npix, tet, c.is);
+    carve_binning(const_cast<void*>(bb), R, 0, 0, 0, c.bs);
+    return c;
+}
+dmr::TriImageState tri_image(const Scratch& c) {
+    const ImageState& is = c.is;
+    return {is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.mask_offset};
+}
+dmr::TetImageState tet_image(const Scratch& c) {
+    const ImageState& is = c.is;
+    return {is.final_T, is.final_prev_T, is.n_contrib, is.first_face, is.first_tet, is.last_face, is.last_tet, is.is_active,
+            c.fs.facerec, c.fs.colrec, c.fs.tetrec, is.seed, is.seq, c.bs.base};
+}
+
 // The scene as every kernel behind k_project_verts sees it: matrices in contract layout, read from the image buffer.
 dmr_scene canonical(const dmr_scene* s, const float* mats) {
     dmr_scene c = *s;
@@ -150,26 +172,24 @@ int check_scene(const dmr_scene* s, bool tet, Dims& d) {
     return 0;
 }
 
-// Pinned (coherent, device-visible) landing pad the kernels write the sizes to -- forward: the 8-byte word at byte 0,
-// backward: the one at byte 8, each host_size_word(sequence number, size) (dmr_kernels.hpp) -- one per host thread and
-// device.  The host POLLS the word until it carries the call's sequence number: an event recorded between two kernels costs the
-// device 2-7 us (profiles/r03/dead_ends.md), a default call had two of them per step.
+// 64 zeroed bytes of pinned (coherent, device-visible) host memory for words the kernels store into; null: failed
+void* pinned_words() {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) return nullptr;
+    memset(p, 0, 64);
+    return p;
+}
+
+// Pinned landing pad the kernels write the sizes to -- forward: the 8-byte word at byte 0, backward: the one at byte 8, each
+// host_size_word(sequence number, size) (dmr_kernels.hpp) -- one per host thread and device.  The host POLLS the word until it
+// carries the call's sequence number: an event recorded between two kernels costs the device 2-7 us
+// (profiles/r03/dead_ends.md), a default call had two of them per step.
 struct SizeRead {
     void* slot = nullptr; uint32_t seq = 0;
     volatile unsigned long long* word(int which) const { return reinterpret_cast<volatile unsigned long long*>(slot) + which; }
     uint32_t next_seq() { seq = (seq + 1u) & 0xffffffu; if (seq == 0u) seq = 1u; return seq; }
 };
-SizeRead* size_read() {
-    thread_local std::map<int, SizeRead> per_device;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    SizeRead& sr = per_device[dev];
-    if (!sr.slot) {
-        if (hipHostMalloc(&sr.slot, 64, hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) { sr.slot = nullptr; return nullptr; }
-        memset(sr.slot, 0, 64);
-    }
-    return &sr;
-}
+thread_local std::map<int, SizeRead> g_size_read;  // per device
 // Waits until *w carries `seq`; returns the size in it.  Spins on the pinned word; if it does not arrive within ~50 ms the
 // stream is synchronised instead (a kernel error then surfaces as a HIP error, and a completed stream has written the word).
 int wait_size(volatile unsigned long long* w, uint32_t seq, hipStream_t st, unsigned long long* size) {
@@ -199,13 +219,14 @@ uint32_t* overflow_word(int dev, bool create) {
     auto it = g_overflow.find(dev);
     if (it != g_overflow.end()) return it->second;
     if (!create) return nullptr;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) return nullptr;
-    *reinterpret_cast<volatile uint32_t*>(p) = 0u;
+    void* p = pinned_words();
+    if (!p) return nullptr;
     return g_overflow[dev] = reinterpret_cast<uint32_t*>(p);
 }
 
-bool stream_is_capturing(hipStream_t st) {
+// DMR_FLAG_ASYNC, or a stream being captured into a HIP graph: the call must not wait for the device
+bool is_async(const dmr_scene* s, hipStream_t st) {
+    if (s->flags & DMR_FLAG_ASYNC) return true;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
     return cs != hipStreamCaptureStatusNone;
@@ -254,63 +275,106 @@ double lookup_estimate(const SizeKey& key, double SizeGuess::* field) {
 }
 uint64_t padded(uint64_t n) { return n + n / 4 + 4096; }
 
-// Stages shared by both renderers up to the sorted per-tile lists, then `render` (the renderer's own
-// kernels, which only need the binning state).  See "Speculative sizing" above for the control flow.
-int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc, void* ctx, hipStream_t st,
-                PointState& ps, FaceState& fs, ImageState& is, int* num_rendered,
-                const std::function<void(const BinningState&)>& render) {
-    PointState tp; FaceState tf; ImageState ti;
-    void* pb = alloc(ctx, DMR_BUF_POINT, carve_point(nullptr, d.BP, tp));
-    void* fb = alloc(ctx, DMR_BUF_FACE, carve_face(nullptr, d.BF, (size_t)s->F, (size_t)s->T, tet, tf));
-    void* ib = alloc(ctx, DMR_BUF_IMAGE, carve_image(nullptr, (size_t)s->B, (size_t)d.ntiles, d.npix, tet, ti));
-    if (!pb || !fb || !ib) return fail("scratch allocation failed");
-    carve_point(pb, d.BP, ps);
-    carve_face(fb, d.BF, (size_t)s->F, (size_t)s->T, tet, fs);
-    carve_image(ib, (size_t)s->B, (size_t)d.ntiles, d.npix, tet, is);
-    const bool async = (s->flags & DMR_FLAG_ASYNC) != 0 || stream_is_capturing(st);
+// tet: the key's SizeGuess::seq_steps word (created by a default forward: create; null: none) and, if asked for, the room for
+// the next forward's march sequence: the longest march + 25 %, a multiple of 4, within a memory budget (0: no march reported
+// yet, that call's backward re-marches).
+uint32_t* march_estimate(const SizeKey& key, const Dims& d, bool create, size_t* seq_steps = nullptr) {
+    std::lock_guard<std::mutex> lk(g_size_mu);
+    SizeGuess& g = g_size_cache[key];
+    if (!g.seq_steps && create && !(g.seq_steps = reinterpret_cast<uint32_t*>(pinned_words()))) (void)hipGetLastError();
+    if (seq_steps) {
+        const uint64_t longest = g.seq_steps ? *reinterpret_cast<volatile uint32_t*>(g.seq_steps) : 0u;
+        const uint64_t budget = 16ull << 30;  // bytes: beyond it the longest rays do not fit and such a call re-marches
+        const uint64_t per4 = dmr::tet_seq_bytes((size_t)d.ntiles, 4);
+        *seq_steps = longest ? (size_t)(std::min<uint64_t>((longest + longest / 4 + 4 + 3) / 4, std::max<uint64_t>(budget / std::max<uint64_t>(per4, 1), 1)) * 4) : 0;
+    }
+    return g.seq_steps;
+}
+
+// Where the kernel that computes a size publishes it ({host word, sequence number, overflow word} of the scans and
+// dmr::HitRegions): a default call's pinned word; an asynchronous call's overflow word, raised above `capacity`; or NOWHERE
+// (a redo: the size is known, and a late store could land in the word after a later call, on another stream, took it over).
+struct SizeOut { unsigned long long* host; uint32_t seq; uint32_t* overflow; uint32_t capacity; };
+const SizeOut NOWHERE{nullptr, 0u, nullptr, 0xffffffffu};
+
+// One speculatively sized buffer: its estimate, its largest size (the clamp of a guess; an exact size above it is the error
+// too_large), its word in SizeRead, the error of an asynchronous call without an estimate.
+struct Sizing { double SizeGuess::* estimate; uint64_t limit; int word; const char* too_large; const char* no_estimate; };
+
+// The speculative sizing above, for both buffers.  first(guess, out): the stages that can be enqueued before the size is
+// known, `guess` the capacity (0: no estimate), `out` where the size goes; then(size, redo): the stages that need the exact
+// size (redo: they ran with a guess too small).  *size: the exact size, or an asynchronous call's capacity.
+template <class First, class Then>
+int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_t st, uint64_t* size, First first, Then then) {
     int dev = 0;
     DMR_HIP(hipGetDevice(&dev));
     uint32_t* overflow = overflow_word(dev, !async);
+    uint64_t guess = 0;
+    {
+        std::lock_guard<std::mutex> lk(g_size_mu);
+        const double per_face = lookup_estimate(key, z.estimate);
+        if (per_face > 0.0) guess = std::min<uint64_t>(padded((uint64_t)(per_face * (double)BF)), z.limit);
+    }
+    if (async) {  // no host wait at all: capacity from the estimate, overflow checked on the device
+        if (!guess || !overflow) return fail(z.no_estimate);
+        if (first(guess, SizeOut{nullptr, 0u, overflow, (uint32_t)guess})) return 1;
+        *size = guess;  // an upper bound the backward accepts in R's place
+        DMR_HIP(hipGetLastError());
+        return 0;
+    }
+    SizeRead& sr = g_size_read[dev];
+    if (!sr.slot && !(sr.slot = pinned_words())) return fail("hipHostMalloc failed");
+    const uint32_t seq = sr.next_seq();
+    if (first(guess, SizeOut{const_cast<unsigned long long*>(sr.word(z.word)), seq, nullptr, 0xffffffffu})) return 1;
+    unsigned long long n = 0;
+    if (wait_size(sr.word(z.word), seq, st, &n)) return 1;  // the call's one host wait (rasterizer_impl.cu:287-292)
+    if (n > z.limit) return fail(z.too_large);
+    *size = n;
+    if (!guess) {
+        if (then(n, false)) return 1;
+    } else if (n > guess) {  // the guess was too small: redo the affected stages with the exact size
+        g_redo_count.fetch_add(1, std::memory_order_relaxed);
+        DMR_HIP(hipStreamSynchronize(st));
+        if (then(n, true)) return 1;
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_size_mu);
+        g_size_cache[key].*z.estimate = (double)std::max<uint64_t>(n, 1) / (double)std::max<size_t>(BF, 1);
+    }
+    DMR_HIP(hipGetLastError());
+    return 0;
+}
 
-    // host_R: pinned slot the scan also stores R into (null: not needed).  Not on a redo pass: R is known by then, and
-    // a late store could land in the slot after this call has returned and a later call (another stream) reuses it.
-    auto front = [&](unsigned long long* host_R, uint32_t host_seq, uint64_t capacity, uint32_t* ovf) -> int {
+// Stages shared by both renderers up to the sorted per-tile lists, then `render` (the renderer's own kernels, which only need
+// the scratch buffers, the binning buffer included).
+int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc, void* ctx, hipStream_t st, int* num_rendered,
+                const std::function<void(const Scratch&)>& render) {
+    const Scratch need = carve_scratch(s, tet, d, nullptr, nullptr, nullptr);
+    void* pb = alloc(ctx, DMR_BUF_POINT, need.point_bytes);
+    void* fb = alloc(ctx, DMR_BUF_FACE, need.face_bytes);
+    void* ib = alloc(ctx, DMR_BUF_IMAGE, need.image_bytes);
+    if (!pb || !fb || !ib) return fail("scratch allocation failed");
+    Scratch c = carve_scratch(s, tet, d, pb, fb, ib);
+    const PointState& ps = c.ps; const FaceState& fs = c.fs; const ImageState& is = c.is;
+    const bool async = is_async(s, st);
+    const SizeKey key = size_key(s, tet, d);
+    size_t seq_steps = 0;
+    if (tet) march_estimate(key, d, !async, &seq_steps);
+
+    auto front = [&](SizeOut out) {
         // (tile_count | tile_hits | tile_bound are contiguous: zeroed by k_project_verts, a slice per block)
         dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st);
         dmr::launch_setup_faces(*s, tet, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.rect, fs.key_depth, fs.max_depth,
                                 fs.tiles_touched, is.tile_count, st);
-        dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, host_R, host_seq, is.tile_order,
-                               is.scan_tmp, (uint32_t)std::min<uint64_t>(capacity, 0xffffffffu), ovf, st);
-        return 0;
+        dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, out.host, out.seq, is.tile_order,
+                               is.scan_tmp, out.capacity, out.overflow, st);
     };
-    // tet: room for the forward's march sequence = the longest march the last backward that has run reported, + 25 % (0: none
-    // yet -- this call's backward re-marches), within a memory budget.  The pinned word is created by the first default call
-    // of the view configuration.
-    size_t seq_steps = 0;
-    if (tet) {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        SizeGuess& g = g_size_cache[size_key(s, tet, d)];
-        if (!g.seq_steps && !async) {
-            void* w = nullptr;
-            if (hipHostMalloc(&w, 64, hipHostMallocCoherent | hipHostMallocPortable) == hipSuccess) {
-                g.seq_steps = reinterpret_cast<uint32_t*>(w);
-                *reinterpret_cast<volatile uint32_t*>(g.seq_steps) = 0u;
-            } else (void)hipGetLastError();
-        }
-        if (g.seq_steps) {
-            const uint64_t longest = *reinterpret_cast<volatile uint32_t*>(g.seq_steps);
-            if (longest) {
-                const uint64_t budget = 16ull << 30;  // bytes: beyond it the longest rays do not fit and such a call re-marches
-                const uint64_t per4 = dmr::tet_seq_bytes((size_t)d.ntiles, 4);
-                seq_steps = (size_t)(std::min<uint64_t>((longest + longest / 4 + 4 + 3) / 4, std::max<uint64_t>(budget / std::max<uint64_t>(per4, 1), 1)) * 4);
-            }
-        }
-    }
     auto rest = [&](uint64_t capacity) -> int {
-        BinningState tb, bs;
+        BinningState tb;
         const size_t mask_tiles = tet ? 0 : (size_t)d.ntiles;
         void* bb = alloc(ctx, DMR_BUF_BINNING, carve_binning(nullptr, (size_t)capacity, mask_tiles, (size_t)d.ntiles, seq_steps, tb));
         if (!bb && (capacity > 0 || seq_steps > 0)) return fail("binning allocation failed");
+        BinningState& bs = c.bs;
         carve_binning(bb, (size_t)capacity, mask_tiles, (size_t)d.ntiles, seq_steps, bs);
 
         if (capacity > 0) {
@@ -320,49 +384,20 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
             if (d.ntiles > dmr::SCAN_SINGLE_MAX)
                 dmr::launch_sort_tiles(d.ntiles, is.tile_offset, is.tile_order, bs.keys, bs.face_list, bs.capacity, st);
         }
-        render(bs);
+        render(c);
         return 0;
     };
 
-    const SizeKey key = size_key(s, tet, d);
-    uint64_t guess = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        const double per_face = lookup_estimate(key, &SizeGuess::rendered_per_face);
-        if (per_face > 0.0) guess = std::min<uint64_t>(padded((uint64_t)(per_face * (double)d.BF)), 0x7fffffffu);
-    }
-    if (async) {  // no host wait at all: capacity from the estimate, overflow checked on the device
-        if (!guess || !overflow)
-            return fail("asynchronous / captured call without a size estimate: run one default (waiting) call with the same "
-                        "view configuration first");
-        if (front(nullptr, 0u, guess, overflow) || rest(guess)) return 1;
-        *num_rendered = (int)guess;  // the capacity: an upper bound the backward accepts in R's place
-        DMR_HIP(hipGetLastError());
-        return 0;
-    }
-    SizeRead* sr = size_read();
-    if (!sr) return fail("hipHostMalloc failed");
-    const uint32_t seq = sr->next_seq();
-    if (front(const_cast<unsigned long long*>(sr->word(0)), seq, ~0ull, nullptr)) return 1;
-    if (guess && rest(guess)) return 1;
-    unsigned long long R64 = 0;
-    if (wait_size(sr->word(0), seq, st, &R64)) return 1;  // the forward's one host wait (rasterizer_impl.cu:287-292)
-    if (R64 > 0x7fffffffull) return fail("num_rendered overflows 31 bits");
-    const int R = (int)R64;
-    *num_rendered = R;
-    if (!guess) {
-        if (rest((uint64_t)R)) return 1;
-    } else if ((uint64_t)R > guess) {  // the guess was too small: redo binning + render with the exact size
-        g_redo_count.fetch_add(1, std::memory_order_relaxed);
-        DMR_HIP(hipStreamSynchronize(st));
-        if (front(nullptr, 0u, ~0ull, nullptr) || rest((uint64_t)R)) return 1;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        g_size_cache[key].rendered_per_face = (double)std::max(R, 1) / (double)std::max<size_t>(d.BF, 1);
-    }
-    DMR_HIP(hipGetLastError());
-    return 0;
+    const Sizing list_entries{&SizeGuess::rendered_per_face, 0x7fffffffu, 0, "num_rendered overflows 31 bits",
+                              "asynchronous / captured call without a size estimate: run one default (waiting) call with the same "
+                              "view configuration first"};
+    uint64_t R = 0;
+    // a redo enqueues the front again too: the scatter pass has used up the tile cursors
+    const int rc = sized(list_entries, key, d.BF, async, st, &R,
+                         [&](uint64_t guess, SizeOut out) { front(out); return guess ? rest(guess) : 0; },
+                         [&](uint64_t exact, bool redo) { if (redo) front(NOWHERE); return rest(exact); });
+    *num_rendered = (int)R;
+    return rc;
 }
 
 // ---- per-stage timing ---------------------------------------------------------------------------
@@ -456,15 +491,13 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
     *num_rendered = 0;
     if (s->P == 0 || s->F == 0) return 0;  // render.cu:105 (and Q16: F == 0)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PointState ps; FaceState fs; ImageState is;
-    auto render = [&](const BinningState& bs) {
-        dmr::TriImageState img{is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.mask_offset};
-        const dmr_scene sc = canonical(s, is.mats);
-        dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, ps.vproj, is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : bs.keys,
-                                bs.face_list, bs.capacity, img, out_color,
+    auto render = [&](const Scratch& c) {
+        const dmr_scene sc = canonical(s, c.is.mats);
+        dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, c.is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys,
+                                c.bs.face_list, c.bs.capacity, tri_image(c), out_color,
                                 out_depth, st);
     };
-    return run_forward(s, false, d, alloc, ctx, st, ps, fs, is, num_rendered, render);
+    return run_forward(s, false, d, alloc, ctx, st, num_rendered, render);
 }
 
 int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL_ddepth, int num_rendered,
@@ -494,18 +527,11 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         return 0;
     }
     if (!point_buf || !face_buf || !binning_buf || !image_buf || !alloc) return fail("null scratch buffer");
-    PointState ps; FaceState fs; ImageState is; BinningState bs;
-    carve_point(const_cast<void*>(point_buf), d.BP, ps);
-    carve_face(const_cast<void*>(face_buf), d.BF, (size_t)s->F, (size_t)s->T, false, fs);
-    carve_image(const_cast<void*>(image_buf), (size_t)s->B, (size_t)d.ntiles, d.npix, false, is);
-    carve_binning(const_cast<void*>(binning_buf), (size_t)num_rendered, 0, 0, 0, bs);
+    const Scratch c = carve_scratch(s, false, d, point_buf, face_buf, image_buf, binning_buf, (size_t)num_rendered);
+    const ImageState& is = c.is;
 
     // The forward counted the blended (pixel, face) pairs per tile and in total; the total sizes the record
     // buffer (the backward's one 8-byte host read; speculative sizing as in the forward).
-    const bool async = (s->flags & DMR_FLAG_ASYNC) != 0 || stream_is_capturing(st);
-    int dev = 0;
-    DMR_HIP(hipGetDevice(&dev));
-    uint32_t* overflow = overflow_word(dev, !async);
     const size_t vbytes = up(sizeof(float) * dmr::VROW * d.BP), fbytes = up(sizeof(float) * dmr::FROW * d.BF);
     const size_t pbytes = up(sizeof(float4) * 2 * (size_t)d.ntiles * dmr::TILE_PIX);  // per tile: its 256 pixels' (ray, upstream gradient) records
     // regions: see dmr::HitRegions -- null hit_offset: launch_scan_hits has laid the record regions out
@@ -517,7 +543,7 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         float* frow = reinterpret_cast<float*>(work + vbytes);
         float4* pixrec = reinterpret_cast<float4*>(work + vbytes + fbytes);
         dmr::HitRecord* hits = reinterpret_cast<dmr::HitRecord*>(work + vbytes + fbytes + pbytes);
-        dmr::TriImageState img{is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.mask_offset};
+        const dmr::TriImageState img = tri_image(c);
         const dmr_scene sc = canonical(s, is.mats);
         // (Splitting the tiles into bands whose hit-parallel kernel runs on a second stream while the next band's
         // per-pixel kernel computes -- atomic unit and SIMDs busy at the same time -- was measured and lost: 0.56 ms
@@ -525,65 +551,30 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         // k_tri_backward_pix also zeroes the packed accumulators (every block a slice).  (Handing out the tiles'
         // record regions from an atomic cursor: the 2.9 k returning same-address atomics stall their waves, in order
         // with every younger load -- 17 us.)
-        dmr::launch_tri_backward_pix(sc, d.gx, d.gy, d.r0, d.r1, ps.vproj, is.tile_offset, bs.face_list, img,
+        dmr::launch_tri_backward_pix(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, is.tile_offset, c.bs.face_list, img,
                                      dL_dcolor, dL_ddepth, pixrec, hits, (uint32_t)capacity,
                                      reinterpret_cast<float*>(work), (vbytes + fbytes) / sizeof(float), regions, st);
-        dmr::launch_tri_backward_hits(sc, d.gx, d.gy, ps.vproj, bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st);
+        dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
         return 0;
     };
     const dmr::HitRegions scanned{nullptr, nullptr, nullptr, nullptr, 0u};
+    auto self_laid = [&](SizeOut out) { return dmr::HitRegions{is.hit_offset, is.hit_total, out.host, out.overflow, out.seq}; };
     // With a size estimate and few enough tiles the per-pixel kernel lays the regions out itself: no scan launch.
     const bool self_regions = d.ntiles <= dmr::SCAN_SINGLE_MAX;
-    const SizeKey key = size_key(s, false, d);
-    uint64_t guess = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        const double per_face = lookup_estimate(key, &SizeGuess::hits_per_face);
-        if (per_face > 0.0) guess = std::min<uint64_t>(padded((uint64_t)(per_face * (double)d.BF)), 0xfffffffeull);
-    }
-    if (async) {  // no host wait: see run_forward
-        if (!guess || !overflow)
-            return fail("asynchronous / captured call without a size estimate: run one default (waiting) backward with the "
-                        "same view configuration first");
-        if (self_regions) {
-            if (rest(guess, dmr::HitRegions{is.hit_offset, is.hit_total, nullptr, overflow, 0u})) return 1;
-        } else {
-            dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.hit_offset, is.tile_used, is.hit_total, nullptr, 0u, is.scan_tmp, (uint32_t)guess, overflow, st);
-            if (rest(guess, scanned)) return 1;
-        }
-        DMR_HIP(hipGetLastError());
-        return 0;
-    }
-    SizeRead* sr = size_read();
-    if (!sr) return fail("hipHostMalloc failed");
-    unsigned long long* host_total = const_cast<unsigned long long*>(sr->word(1));
-    const uint32_t seq = sr->next_seq();
-    if (guess && self_regions) {
-        // everything is enqueued with the estimate; the total arrives behind the per-pixel kernel
-        if (rest(guess, dmr::HitRegions{is.hit_offset, is.hit_total, host_total, nullptr, seq})) return 1;
-    } else {
-        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.hit_offset, is.tile_used, is.hit_total, host_total, seq, is.scan_tmp, 0xffffffffu, nullptr, st);
-        if (guess && rest(guess, scanned)) return 1;
-    }
-    unsigned long long nhits = 0;
-    if (wait_size(sr->word(1), seq, st, &nhits)) return 1;
-    if (nhits >= 0xffffffffull) return fail("more than 2^32 blended (pixel, face) pairs");
-    if (!guess) {
-        if (rest(nhits, scanned)) return 1;
-    } else if (nhits > guess) {  // (the redo pass does not store into the pinned slot: a later call may own it by then)
-        g_redo_count.fetch_add(1, std::memory_order_relaxed);
-        DMR_HIP(hipStreamSynchronize(st));
-        if (self_regions) {
-            if (rest(nhits, dmr::HitRegions{is.hit_offset, is.hit_total, nullptr, nullptr, 0u})) return 1;
-        } else if (rest(nhits, scanned)) return 1;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        g_size_cache[key].hits_per_face = (double)std::max<uint64_t>(nhits, 1) / (double)std::max<size_t>(d.BF, 1);
-    }
-    DMR_HIP(hipGetLastError());
-    return 0;
+    auto first = [&](uint64_t guess, SizeOut out) -> int {
+        if (guess && self_regions) return rest(guess, self_laid(out));
+        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.hit_offset, is.tile_used, is.hit_total, out.host, out.seq,
+                              is.scan_tmp, out.capacity, out.overflow, st);
+        return guess ? rest(guess, scanned) : 0;
+    };
+    const Sizing hit_records{&SizeGuess::hits_per_face, 0xfffffffeu, 1, "more than 2^32 blended (pixel, face) pairs",
+                             "asynchronous / captured call without a size estimate: run one default (waiting) backward with the "
+                             "same view configuration first"};
+    uint64_t nhits = 0;
+    // a redo re-runs the record passes only: the scan's regions still stand
+    return sized(hit_records, size_key(s, false, d), d.BF, is_async(s, st), st, &nhits, first,
+                 [&](uint64_t exact, bool redo) { return rest(exact, redo && self_regions ? self_laid(NOWHERE) : scanned); });
 }
 
 int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, float* out_active, dmr_alloc_fn alloc,
@@ -593,18 +584,15 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
     if (!alloc || !num_rendered || !out_color || !out_depth || !out_active) return fail("null argument");
     *num_rendered = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PointState ps; FaceState fs; ImageState is;
-    auto render = [&](const BinningState& bs) {
-        dmr::TetImageState img{is.final_T, is.final_prev_T, is.n_contrib, is.first_face, is.first_tet,
-                               is.last_face, is.last_tet, is.is_active, fs.facerec, fs.colrec, fs.tetrec, is.seed,
-                               is.seq, bs.base};
-        const dmr_scene sc = canonical(s, is.mats);
-        dmr::launch_tet_prep(sc, img, bs.seq_steps, bs.seq_offset, st);
-        dmr::launch_tet_first_intersect(sc, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.max_depth, is.tile_offset,
-                                        d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : bs.keys, bs.face_list, bs.capacity, img, st);
+    auto render = [&](const Scratch& c) {
+        const dmr::TetImageState img = tet_image(c);
+        const dmr_scene sc = canonical(s, c.is.mats);
+        dmr::launch_tet_prep(sc, img, c.bs.seq_steps, c.bs.seq_offset, st);
+        dmr::launch_tet_first_intersect(sc, d.gx, d.gy, d.r0, d.r1, c.fs.key_depth, c.fs.max_depth, c.is.tile_offset,
+                                        d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys, c.bs.face_list, c.bs.capacity, img, st);
         dmr::launch_tet_forward(sc, d.gx, d.gy, d.r0, d.r1, img, out_color, out_depth, out_active, st);
     };
-    return run_forward(s, true, d, alloc, ctx, st, ps, fs, is, num_rendered, render);
+    return run_forward(s, true, d, alloc, ctx, st, num_rendered, render);
 }
 
 int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL_ddepth, const void* point_buf,
@@ -624,22 +612,12 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
     if (s->P == 0 || s->F == 0) return 0;
     if (!image_buf || !face_buf) return fail("null scratch buffer");
-    ImageState is; FaceState fs;
-    carve_image(const_cast<void*>(image_buf), (size_t)s->B, (size_t)d.ntiles, d.npix, true, is);
-    carve_face(const_cast<void*>(face_buf), d.BF, (size_t)s->F, (size_t)s->T, true, fs);
     // binning_buf: the forward's march sequence lives there (where and how much of it: is.seq, on the device); a null
     // buffer is fine when the forward ran without one (its descriptor then says cap = 0 and the backward re-marches)
-    dmr::TetImageState img{is.final_T, is.final_prev_T, is.n_contrib, is.first_face, is.first_tet,
-                           is.last_face, is.last_tet, is.is_active, fs.facerec, fs.colrec, fs.tetrec, is.seed,
-                           is.seq, reinterpret_cast<char*>(const_cast<void*>(binning_buf))};
-    const dmr_scene sc = canonical(s, is.mats);
-    uint32_t* host_seq_steps = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_size_mu);
-        auto it = g_size_cache.find(size_key(s, true, d));
-        if (it != g_size_cache.end()) host_seq_steps = it->second.seq_steps;
-    }
-    dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, img, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
+    const Scratch c = carve_scratch(s, true, d, point_buf, face_buf, image_buf, binning_buf);
+    const dmr_scene sc = canonical(s, c.is.mats);
+    uint32_t* host_seq_steps = march_estimate(size_key(s, true, d), d, false);
+    dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
                              full, full ? full + 3 * (int64_t)s->P : nullptr);
     DMR_HIP(hipGetLastError());
     return 0;
@@ -707,11 +685,8 @@ int64_t dmr_export(const dmr_scene* s, int is_tet, int num_rendered, const char*
     Dims d;
     if (!name || check_scene(s, is_tet != 0, d)) return -1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PointState ps; FaceState fs; ImageState is; BinningState bs;
-    carve_point(const_cast<void*>(point_buf), d.BP, ps);
-    carve_face(const_cast<void*>(face_buf), d.BF, (size_t)s->F, (size_t)s->T, is_tet != 0, fs);
-    carve_image(const_cast<void*>(image_buf), (size_t)s->B, (size_t)d.ntiles, d.npix, is_tet != 0, is);
-    carve_binning(const_cast<void*>(binning_buf), (size_t)std::max(0, num_rendered), 0, 0, 0, bs);
+    const Scratch c = carve_scratch(s, is_tet != 0, d, point_buf, face_buf, image_buf, binning_buf, (size_t)std::max(0, num_rendered));
+    const FaceState& fs = c.fs; const ImageState& is = c.is;
     const std::string n(name);
     auto plain = [&](const void* src, size_t bytes) -> int64_t {
         if (dst && src && bytes) {
@@ -726,7 +701,7 @@ int64_t dmr_export(const dmr_scene* s, int is_tet, int num_rendered, const char*
         const size_t bytes = d.BP * (n == "image" ? 8 : 4);
         if (dst && d.BP && (size_t)cap >= bytes)
             k_export_vproj<<<dim3((unsigned)((d.BP + 255) / 256)), dim3(256), 0, st>>>(
-                ps.vproj, (int64_t)d.BP, n == "image" ? 0 : 1, reinterpret_cast<float*>(dst));
+                c.ps.vproj, (int64_t)d.BP, n == "image" ? 0 : 1, reinterpret_cast<float*>(dst));
         return (int64_t)bytes;
     }
     if (n == "ranges") {
@@ -739,7 +714,7 @@ int64_t dmr_export(const dmr_scene* s, int is_tet, int num_rendered, const char*
     if (n == "key_depth") return plain(fs.key_depth, d.BF * 4);
     if (n == "max_depth") return is_tet ? plain(fs.max_depth, d.BF * 4) : -1;
     if (n == "tiles_touched") return plain(fs.tiles_touched, d.BF * 4);
-    if (n == "face_list") return plain(bs.face_list, (size_t)std::max(0, num_rendered) * 4);
+    if (n == "face_list") return plain(c.bs.face_list, (size_t)std::max(0, num_rendered) * 4);
     if (n == "final_T") return plain(is.final_T, d.npix * 4);
     if (n == "final_prev_T") return plain(is.final_prev_T, d.npix * 4);
     if (n == "n_contrib") return plain(is.n_contrib, d.npix * 4);
