@@ -59,13 +59,27 @@ def _with_inverses(mv_mats: th.Tensor, proj_mats: th.Tensor) -> Tuple[th.Tensor,
     return mv_mats, proj_mats, th.inverse(mv_mats), th.inverse(proj_mats)
 
 
+def _through_inverse(y: th.Tensor, g: th.Tensor) -> th.Tensor:
+    """dL/dX from g = dL/dY for Y = X^-1 ([B,4,4] each): -Y^T g Y^T."""
+    yt = y.transpose(1, 2)
+    return -th.matmul(th.matmul(yt, g), yt)
+
+
+def _tri_grad_keywords(exact_grads: bool, camera_grads: bool) -> dict:
+    """The keywords of _C.render_tris_backward for the tri gradient options: none by default (the reference's call)."""
+    if camera_grads:
+        return {"camera_grads": True}
+    return {"exact_grads": True} if exact_grads else {}
+
+
 class _TriFn(th.autograd.Function):
     """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense,
-    settings, rows.  Gradients flow to verts, verts_color, faces_opacity, verts_depth, faces_intense."""
+    settings, rows[, exact_grads, camera_grads].  Gradients flow to verts, verts_color, faces_opacity, verts_depth,
+    faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer)."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows):
+                settings: TriRenderSettings, rows, exact_grads=False, camera_grads=False):
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         try:
@@ -77,6 +91,7 @@ class _TriFn(th.autograd.Function):
             raise
         num_rendered, color, depth = out[0], out[1], out[2]
         ctx.settings, ctx.rows, ctx.num_rendered = settings, rows, num_rendered
+        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *out[3:7])
         return color, depth
 
@@ -84,14 +99,20 @@ class _TriFn(th.autograd.Function):
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
         inputs, scratch = saved[:10], saved[10:14]
+        # the matrices' gradients only when asked for: otherwise the exact variant, which skips the per-pixel ray sums
+        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
         try:
             g = _C.render_tris_backward(ctx.settings.bg, *inputs, grad_color, grad_depth, ctx.num_rendered,
-                                        *scratch, rows=ctx.rows)
+                                        *scratch, rows=ctx.rows, **_tri_grad_keywords(ctx.exact_grads, camera))
         except Exception:
             print("\nAn error occured in backward.\n")
             raise
-        g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g
-        return g_verts, None, g_vcolor, g_fopacity, None, None, g_vdepth, g_fintense, None, None
+        g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g[:5]
+        g_mv = g_proj = None
+        if camera:  # dL/d(inverse) -> dL/d(matrix); saved[6:8] are the inverses the forward used
+            g_mv = _through_inverse(saved[6], g[5]) if ctx.needs_input_grad[4] else None
+            g_proj = _through_inverse(saved[7], g[6]) if ctx.needs_input_grad[5] else None
+        return g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense, None, None, None, None
 
 
 class _TetFn(th.autograd.Function):
@@ -135,10 +156,12 @@ class _TetFn(th.autograd.Function):
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               render_settings: TriRenderSettings, rows=(0, 0)):
-    """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices."""
+               render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False):
+    """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices.  exact_grads,
+    camera_grads: see TriRenderer."""
+    opts = (bool(exact_grads), bool(camera_grads)) if exact_grads or camera_grads else ()
     return _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth,
-                        faces_intense, render_settings, tuple(rows))
+                        faces_intense, render_settings, tuple(rows), *opts)
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
@@ -153,19 +176,33 @@ class TriRenderer(th.nn.Module):
     """Renderer for (semi-transparent) triangles: depth-sorted front-to-back compositing of every
     triangle of a tile; no exact per-pixel depth test (reference README.md:3).
 
+    exact_grads=True (beyond the reference): verts receive the true derivative of color and depth.  Each blended
+    (pixel, face) pair enters through the Moeller-Trumbore (u, v) of the pixel's ray on the face, and that (u, v) is
+    differentiated exactly.  The reference's gradient, the default, differentiates t where it means v.
+    Coverage, list order and the clamp region of (u, v) are constants of the gradient, as for every gradient here.
+    The other gradients are the default's, summed in another order.
+
+    camera_grads=True (implies exact_grads): mv_mats and proj_mats receive gradients too, through every pixel's ray
+    (its origin and direction come from the inverse matrices).  The depth output reads verts_depth, not the
+    matrices: a caller who computes verts_depth from the camera gets that part through their own autograd.
+
+    Both options cost a slower backward; the forward is the same.
+
     forward(verts [P,3], faces [F,3], verts_color [P,3], faces_opacity [F],
             mv_mats [B,4,4], proj_mats [B,4,4], verts_depth [B,P], faces_intense [B,F])
         -> color [B,3,H,W], depth [B,1,H,W]
     """
 
-    def __init__(self, render_settings: TriRenderSettings):
+    def __init__(self, render_settings: TriRenderSettings, exact_grads: bool = False, camera_grads: bool = False):
         super().__init__()
         self.render_settings = render_settings
+        self.exact_grads = bool(exact_grads)
+        self.camera_grads = bool(camera_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
         return render_tri(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
                           mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
-                          self.render_settings)
+                          self.render_settings, exact_grads=self.exact_grads, camera_grads=self.camera_grads)
 
 
 class TetRenderer(th.nn.Module):

@@ -507,9 +507,20 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     Dims d;
     if (check_scene(s, false, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // DMR_FLAG_TRI_EXACT_GRADS / DMR_FLAG_TRI_CAMERA_GRADS: which k_tri_backward_hits; with camera gradients the caller's
+    // [B][dL/dinv_mv 16 | dL/dinv_proj 16] buffer, requested once
+    const bool camera = (s->flags & DMR_FLAG_TRI_CAMERA_GRADS) != 0;
+    const int grads = camera ? dmr::TRI_GRAD_CAMERA : ((s->flags & DMR_FLAG_TRI_EXACT_GRADS) ? dmr::TRI_GRAD_EXACT : dmr::TRI_GRAD_REF);
+    float* cam_out = nullptr;
+    if (camera && s->B > 0) {
+        if (!alloc) return fail("null argument");
+        cam_out = static_cast<float*>(alloc(ctx, DMR_BUF_TRI_CAMERA_GRADS, 128 * (size_t)s->B));
+        if (!cam_out) return fail("allocation of the tri camera gradient buffer failed");
+    }
     // Nothing to back-propagate: no geometry (render.cu:173), nothing on screen, or an empty tile-row band (a rank without
     // rows; the asynchronous forward of such a band returns its capacity as num_rendered, hence the band test of its own).
     if (s->P == 0 || s->F == 0 || num_rendered <= 0 || d.r1 <= d.r0) {
+        if (cam_out) DMR_HIP(hipMemsetAsync(cam_out, 0, 128 * (size_t)s->B, st));
         if (s->P > 0) {
             DMR_HIP(hipMemsetAsync(dL_dverts, 0, sizeof(float) * 3 * (size_t)s->P, st));
             DMR_HIP(hipMemsetAsync(dL_dvcolor, 0, sizeof(float) * 3 * (size_t)s->P, st));
@@ -534,15 +545,17 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     // buffer (the backward's one 8-byte host read; speculative sizing as in the forward).
     const size_t vbytes = up(sizeof(float) * dmr::VROW * d.BP), fbytes = up(sizeof(float) * dmr::FROW * d.BF);
     const size_t pbytes = up(sizeof(float4) * 2 * (size_t)d.ntiles * dmr::TILE_PIX);  // per tile: its 256 pixels' (ray, upstream gradient) records
+    const size_t cbytes = camera ? up(sizeof(float) * 32 * (size_t)d.ntiles) : 0;  // camera gradients: every tile's partial
     // regions: see dmr::HitRegions -- null hit_offset: launch_scan_hits has laid the record regions out
     auto rest = [&](uint64_t capacity, dmr::HitRegions regions) -> int {
         const size_t hbytes = up(sizeof(dmr::HitRecord) * (size_t)capacity);
-        char* work = reinterpret_cast<char*>(alloc(ctx, DMR_BUF_WORK, vbytes + fbytes + pbytes + hbytes));
+        char* work = reinterpret_cast<char*>(alloc(ctx, DMR_BUF_WORK, vbytes + fbytes + cbytes + pbytes + hbytes));
         if (!work) return fail("workspace allocation failed");
         float* vrow = reinterpret_cast<float*>(work);
         float* frow = reinterpret_cast<float*>(work + vbytes);
-        float4* pixrec = reinterpret_cast<float4*>(work + vbytes + fbytes);
-        dmr::HitRecord* hits = reinterpret_cast<dmr::HitRecord*>(work + vbytes + fbytes + pbytes);
+        float* cam_part = reinterpret_cast<float*>(work + vbytes + fbytes);  // (zeroed with the accumulators)
+        float4* pixrec = reinterpret_cast<float4*>(work + vbytes + fbytes + cbytes);
+        dmr::HitRecord* hits = reinterpret_cast<dmr::HitRecord*>(work + vbytes + fbytes + cbytes + pbytes);
         const dmr::TriImageState img = tri_image(c);
         const dmr_scene sc = canonical(s, is.mats);
         // (Splitting the tiles into bands whose hit-parallel kernel runs on a second stream while the next band's
@@ -553,9 +566,11 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         // with every younger load -- 17 us.)
         dmr::launch_tri_backward_pix(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, is.tile_offset, c.bs.face_list, img,
                                      dL_dcolor, dL_ddepth, pixrec, hits, (uint32_t)capacity,
-                                     reinterpret_cast<float*>(work), (vbytes + fbytes) / sizeof(float), regions, st);
-        dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st);
+                                     reinterpret_cast<float*>(work), (vbytes + fbytes + cbytes) / sizeof(float), regions, st);
+        dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st,
+                                      grads, camera ? cam_part : nullptr);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
+        if (camera) dmr::launch_tri_camera_reduce(s->B, d.gx * d.gy, cam_part, cam_out, st);
         return 0;
     };
     const dmr::HitRegions scanned{nullptr, nullptr, nullptr, nullptr, 0u};

@@ -128,10 +128,17 @@ void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1,
                              const uint32_t* tile_offset, const uint32_t* face_list, TriImageState img,
                              const float* dL_dcolor, const float* dL_ddepth, float4* pixrec, HitRecord* hits,
                              uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st);
-// one workgroup per tile (longest list first) over the tile's img.tile_used records
+// one workgroup per tile (longest list first) over the tile's img.tile_used records.
+// grads: the vertex-position gradient the kernel forms -- TRI_GRAD_REF the reference's ray_tri_intersection_grad (Q11),
+// TRI_GRAD_EXACT the exact derivative of each pair's (u, v), TRI_GRAD_CAMERA that and the ray's: every tile of the call
+// then stores its 32-float part of [dL/dinv_mv 16 | dL/dinv_proj 16] (contract layout) at cam_part + 32 * tile (tiles
+// that blend nothing keep what is there: the zeros of k_tri_backward_pix, which clears cam_part with the accumulators)
+enum { TRI_GRAD_REF = 0, TRI_GRAD_EXACT = 1, TRI_GRAD_CAMERA = 2 };
 void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* vproj, const uint32_t* face_list, TriImageState img,
                               const float4* pixrec, const HitRecord* hits, uint32_t capacity, float* vrow, float* frow,
-                              hipStream_t st);
+                              hipStream_t st, int grads = TRI_GRAD_REF, float* cam_part = nullptr);
+// sums the B * tiles partials of the camera variant per view: out [B][32]
+void launch_tri_camera_reduce(int B, int tiles, const float* cam_part, float* out, hipStream_t st);
 void launch_tri_unpack(const dmr_scene& s, const float* vrow, const float* frow, float* dL_dverts,
                        float* dL_dvcolor, float* dL_dfopacity, float* dL_dvdepth, float* dL_dfintense,
                        hipStream_t st);

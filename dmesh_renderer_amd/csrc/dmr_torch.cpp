@@ -20,6 +20,9 @@
 //                            of the one all-reduce in sharding.py); the returned tensors are views into it
 //   full_grads=False         render_tets_backward: also dL_dverts and dL_dfaces_intense (DMR_FLAG_TET_FULL_GRADS, beyond
 //                            the reference) -> (dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dfaces_intense)
+//   exact_grads=False        render_tris_backward: dL_dverts is the exact derivative of the image (DMR_FLAG_TRI_EXACT_GRADS)
+//   camera_grads=False       render_tris_backward: also dL_dinv_mv_mats, dL_dinv_proj_mats [B,4,4] (DMR_FLAG_TRI_CAMERA_GRADS,
+//                            implies exact_grads) -> the five gradients, then those two
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -173,8 +176,9 @@ c10::Device hip_device_of(const at::Tensor& verts) {
 // (render.cu:18-24,91-100), plus the backward's transient workspace
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, 6> buf;
+    std::array<at::Tensor, 7> buf;
     at::Tensor tet_grads;  // where DMR_BUF_TET_GRADS is served from (an output, not scratch), if defined
+    at::Tensor tri_cam;    // where DMR_BUF_TRI_CAMERA_GRADS is served from (an output), if defined
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -182,9 +186,9 @@ struct Scratch {
 };
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
-    if (which < 0 || which >= 6) return nullptr;
-    if (which == DMR_BUF_TET_GRADS) {  // the caller's gradient tensor, which the library fills
-        const at::Tensor& t = s->tet_grads;
+    if (which < 0 || which >= 7) return nullptr;
+    if (which == DMR_BUF_TET_GRADS || which == DMR_BUF_TRI_CAMERA_GRADS) {  // the caller's gradient tensor, which the library fills
+        const at::Tensor& t = which == DMR_BUF_TET_GRADS ? s->tet_grads : s->tri_cam;
         return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
     }
     try {
@@ -272,14 +276,20 @@ TriFwdOut render_tris(const at::Tensor& background, const at::Tensor& verts, con
                           call.scratch.get(DMR_BUF_BINNING), call.scratch.get(DMR_BUF_IMAGE));
 }
 
-// -> (dL_dverts [P,3], dL_dvcolor [P,3], dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F])
+// -> (dL_dverts [P,3], dL_dvcolor [P,3], dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F]), with camera grads
+//    followed by (dL_dinv_mv_mats [B,4,4], dL_dinv_proj_mats [B,4,4]): element [b,i,j] is the gradient of the inverse
+//    tensor's [b,i,j] as the call received it (the library's contract layout m[4*col+row] read as a row-major [4,4] is
+//    the transpose of the matrix it means, which is how such a tensor holds it)
 using TriBwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-TriBwdOut render_tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+using TriBwdCamOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+template <bool CAM>
+std::conditional_t<CAM, TriBwdCamOut, TriBwdOut> tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                                const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
                                int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out) {
+                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                               bool exact_grads) {
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
     if (dL_dout_color.dim() != 4) err("dL_dout_color must have dimensions (B, 3, H, W)");
@@ -289,14 +299,17 @@ TriBwdOut render_tris_backward(const at::Tensor& background, const at::Tensor& v
     const at::Tensor gc = f32(dL_dout_color, "dL_dout_color");  // may arrive non-contiguous / expanded (render.cu:197-198)
     const at::Tensor gd = f32(dL_dout_depth, "dL_dout_depth");
     const int64_t B = call.sc.B, P = call.sc.P, F = call.sc.F;
-    at::Tensor g_verts, g_vcolor, g_fop, g_vdepth, g_fint;
+    at::Tensor g_verts, g_vcolor, g_fop, g_vdepth, g_fint, g_cam;
+    // camera grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16] is DMR_BUF_TRI_CAMERA_GRADS, served by alloc_cb from g_cam; with
+    // flat_out it follows the default layout ([3P | 3P | F | BP | BF | 32B]), so one all-reduce still carries everything
     if (!flat_out.has_value()) {
         const auto opt = f32_on(dev);
         g_verts = at::empty({P, 3}, opt); g_vcolor = at::empty({P, NUM_CHANNELS}, opt); g_fop = at::empty({F}, opt);
         g_vdepth = at::empty({B, P}, opt); g_fint = at::empty({B, F}, opt);
+        if (CAM) g_cam = at::empty({B, 32}, opt);
     } else {
         const at::Tensor& fo = *flat_out;
-        const int64_t total = 6 * P + F + B * (P + F);
+        const int64_t total = 6 * P + F + B * (P + F) + (CAM ? 32 * B : 0);
         if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != total)
             err("flat_out must be a contiguous float32 tensor of " + std::to_string(total) + " elements on " + dev.str());
         const at::Tensor flat = fo.view({-1});
@@ -305,14 +318,42 @@ TriBwdOut render_tris_backward(const at::Tensor& background, const at::Tensor& v
         g_vcolor = flat.narrow(0, o, 3 * P).view({P, NUM_CHANNELS}); o += 3 * P;
         g_fop = flat.narrow(0, o, F); o += F;
         g_vdepth = flat.narrow(0, o, B * P).view({B, P}); o += B * P;
-        g_fint = flat.narrow(0, o, B * F).view({B, F});
+        g_fint = flat.narrow(0, o, B * F).view({B, F}); o += B * F;
+        if (CAM) g_cam = flat.narrow(0, o, 32 * B).view({B, 32});
     }
+    if (CAM) {
+        call.scratch.tri_cam = g_cam;
+        call.sc.flags |= DMR_FLAG_TRI_CAMERA_GRADS;
+    }
+    if (exact_grads) call.sc.flags |= DMR_FLAG_TRI_EXACT_GRADS;
     const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     if (g_abi.tri_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), (int)R, mptr<const void>(pb), mptr<const void>(fb),
                            mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g_verts), mptr<float>(g_vcolor), mptr<float>(g_fop),
                            mptr<float>(g_vdepth), mptr<float>(g_fint), &alloc_cb, &call.scratch, call.stream()))
         raise_lib();
-    return TriBwdOut(g_verts, g_vcolor, g_fop, g_vdepth, g_fint);
+    if constexpr (CAM)
+        return TriBwdCamOut(g_verts, g_vcolor, g_fop, g_vdepth, g_fint, g_cam.view({B, 2, 4, 4}).select(1, 0),
+                            g_cam.view({B, 2, 4, 4}).select(1, 1));
+    else
+        return TriBwdOut(g_verts, g_vcolor, g_fop, g_vdepth, g_fint);
+}
+
+// the binding: without the two keywords exactly the reference's function (render.cu:134-208)
+py::object render_tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
+                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
+                                const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
+                                int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
+                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                                bool exact_grads, bool camera_grads) {
+    auto run = [&](auto cam) {
+        py::gil_scoped_release nogil;
+        return tris_backward<decltype(cam)::value>(background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats,
+                                                   inv_proj_mats, verts_depth, faces_intense, dL_dout_color, dL_dout_depth, R, pointBuffer,
+                                                   faceBuffer, binningBuffer, imageBuffer, rows, flat_out, exact_grads || camera_grads);
+    };
+    if (camera_grads) return py::cast(run(std::true_type{}));
+    return py::cast(run(std::false_type{}));
 }
 
 void check_tets(const at::Tensor& faces, const at::Tensor& tets, const at::Tensor& face_tets, const at::Tensor& tet_faces) {
@@ -489,7 +530,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"),
           py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"),
-          py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::call_guard<py::gil_scoped_release>());
+          py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("exact_grads") = false,
+          py::arg("camera_grads") = false);
     m.def("render_tets", &render_tets, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),

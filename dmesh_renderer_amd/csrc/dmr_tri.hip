@@ -26,6 +26,7 @@
 // LDS table, packed atomics).  DESIGN.md section 5 has the measurements behind every step.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "dmr_kernels.hpp"
 #include "dmr_sort.hpp"
@@ -464,6 +465,23 @@ __device__ __forceinline__ void seg_scan_level(int k, float (&g)[NSCAN]) {
     else if (CTRL == DPP_ROW_SHR + 4) DMR_SEG_LEVEL("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0");
     else DMR_SEG_LEVEL("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0");
 }
+// The exact-gradient variants of k_tri_backward_hits carry two sums more (the y, z of a third ray moment): the same level
+// over both sets, one key comparison.
+#define DMR_SEG_EXTRA(DPP) asm volatile("s_nop 1\n\t" DMR_SEG1(0, DPP) DMR_SEG1(1, DPP) : [g0] "+v"(e[0]), [g1] "+v"(e[1]) : [m] "v"(m))
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void seg_scan_level(int k, float (&g)[NSCAN], float (&e)[2]) {
+    const int ko = dpp_i<CTRL, ROW_MASK>((int)0x80000000, k);
+    const float m = (ko == k) ? 1.0f : 0.0f;
+    if (CTRL == DPP_ROW_SHR + 1) {
+        DMR_SEG_LEVEL("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"); DMR_SEG_EXTRA("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0");
+    } else if (CTRL == DPP_ROW_SHR + 2) {
+        DMR_SEG_LEVEL("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0"); DMR_SEG_EXTRA("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0");
+    } else if (CTRL == DPP_ROW_SHR + 4) {
+        DMR_SEG_LEVEL("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0"); DMR_SEG_EXTRA("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0");
+    } else {
+        DMR_SEG_LEVEL("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0"); DMR_SEG_EXTRA("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0");
+    }
+}
 
 // ---------------------------------------------------------------------------
 // backward, kernel 1 of 2: k_tri_backward_pix -- the per-pixel sequential part.
@@ -876,6 +894,11 @@ struct HitsLds {
     double vval[VTAB][7];   // dx dy dz dr dg db ddepth of row (view, vertex)
     uint32_t frow_stage[4][64][3];  // per wave: {face row id, dopacity, dintense} of the round's segment tails (see the loop)
 };
+// ... and in the camera variant the tile's per-pixel dL/d(ray direction) and the epilogue's per-wave sums (3.4 KB more)
+struct HitsLdsCam : HitsLds {
+    float dray[TILE_PIX][3];
+    float red[4][24];
+};
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -887,7 +910,9 @@ __device__ __forceinline__ void wave_lds_sync() {
 // moves pair by pair and keeps the row's parity), so the flush -- consecutive slots in consecutive lane groups of one
 // instruction -- sends both out in one memory-side request whenever a tile holds both (neighbouring vertex ids are
 // neighbouring vertices in most meshes; nothing is lost when they are not): 106.6 -> 102.6 us at C4.
-template <int SLOTS>
+// (TAG: one instantiation of these helpers per variant of k_tri_backward_hits.  When three kernels share one, the inliner
+// takes it in a different state and the default kernel's instructions change with the variants compiled beside it.)
+template <int SLOTS, int TAG = 0>
 __device__ __forceinline__ uint32_t tab_home(uint32_t rid) {  // the slot pair a row hashes to
     constexpr int PAIRS = SLOTS / 2;
     constexpr bool POW2 = (PAIRS & (PAIRS - 1)) == 0;
@@ -896,7 +921,7 @@ __device__ __forceinline__ uint32_t tab_home(uint32_t rid) {  // the slot pair a
     return POW2 ? ((h >> 8) & (uint32_t)(PAIRS - 1)) : __umulhi(h, (uint32_t)PAIRS);
 }
 // probes `probes` slot pairs from `pair` on; -1: no slot (the row goes out with direct atomics)
-template <int SLOTS>
+template <int SLOTS, int TAG = 0>
 __device__ __forceinline__ int tab_probe(uint32_t* __restrict__ key, uint32_t rid, uint32_t pair, int probes) {
     constexpr int PAIRS = SLOTS / 2;
     constexpr bool POW2 = (PAIRS & (PAIRS - 1)) == 0;
@@ -914,13 +939,13 @@ __device__ __forceinline__ int tab_find(uint32_t* __restrict__ key, uint32_t rid
 }
 // The three rows of a list entry: their first probes are in flight together (three LDS round trips one after the other
 // were a sizeable part of what a segment tail costs); only a row whose home slot is taken by another row probes on.
-template <int SLOTS>
+template <int SLOTS, int TAG = 0>
 __device__ __forceinline__ void tab_find3(uint32_t* __restrict__ key, const uint32_t (&rid)[3], int (&slot)[3]) {
     constexpr int PAIRS = SLOTS / 2;
     constexpr bool POW2 = (PAIRS & (PAIRS - 1)) == 0;
     uint32_t home[3], prev[3];
 #pragma unroll
-    for (int w = 0; w < 3; w++) home[w] = tab_home<SLOTS>(rid[w]);
+    for (int w = 0; w < 3; w++) home[w] = tab_home<SLOTS, TAG>(rid[w]);
 #pragma unroll
     for (int w = 0; w < 3; w++) prev[w] = atomicCAS(&key[2u * home[w] + (rid[w] & 1u)], TAB_EMPTY, rid[w]);
 #pragma unroll
@@ -928,7 +953,7 @@ __device__ __forceinline__ void tab_find3(uint32_t* __restrict__ key, const uint
         if (prev[w] == TAB_EMPTY || prev[w] == rid[w]) slot[w] = (int)(2u * home[w] + (rid[w] & 1u));
         else {
             const uint32_t next = POW2 ? ((home[w] + 1u) & (uint32_t)(PAIRS - 1)) : (home[w] + 1u == (uint32_t)PAIRS ? 0u : home[w] + 1u);
-            slot[w] = tab_probe<SLOTS>(key, rid[w], next, TAB_PROBES - 1);
+            slot[w] = tab_probe<SLOTS, TAG>(key, rid[w], next, TAB_PROBES - 1);
         }
     }
 }
@@ -938,12 +963,20 @@ __device__ __forceinline__ void tab_find3(uint32_t* __restrict__ key, const uint
 // sums the 21 components of its (up to) HIT_GROUP pairs in registers, and only then enters the segmented scan: one scan,
 // one tail hand-off per group instead of per record (the scan was 92 half-rate DPP instructions of ~600 per 64 records),
 // and HIT_GROUP independent pixel gathers in flight per lane.
+//
+// GV (TRI_GRAD_*, dmr_kernels.hpp) selects the vertex-position gradient.  TRI_GRAD_REF is the reference's
+// ray_tri_intersection_grad (Q11: its "dv" is dt's).  TRI_GRAD_EXACT differentiates each pair's Moeller-Trumbore (u, v)
+// exactly; TRI_GRAD_CAMERA does so with respect to the ray as well and leaves the tile's part of dL/dinv_mv, dL/dinv_proj
+// (32 floats, contract layout) in cam_part[tile] (its one argument in Cam).
 #ifndef DMR_HITS_WAVES
 #define DMR_HITS_WAVES 1
 #endif
+template <int GV, class... Cam>
 __global__ void __launch_bounds__(256, DMR_HITS_WAVES)
 k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRecord* __restrict__ hits, uint32_t capacity,
-                    float* __restrict__ vrow, float* __restrict__ frow) {
+                    float* __restrict__ vrow, float* __restrict__ frow, Cam... cam_part) {
+    constexpr bool EXACT = GV != TRI_GRAD_REF, CAM = GV == TRI_GRAD_CAMERA;
+    static_assert(CAM == (sizeof...(Cam) == 1), "the camera variant, and only it, takes the partials' buffer");
     const int tile = (int)p.tile_order[blockIdx.x];
     uint32_t nrec = p.tile_used[tile];
     if (nrec == 0u) return;  // uniform: nothing blended in this tile (or outside this shard's band)
@@ -953,7 +986,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     const uint32_t ngroups = nrec / (uint32_t)HIT_GROUP;
     const int b = tile / (p.gx * p.gy);
 
-    __shared__ HitsLds L;
+    __shared__ std::conditional_t<CAM, HitsLdsCam, HitsLds> L;
     const int tid = threadIdx.x, lane = tid & 63;
     DMR_STAMP_RT(p, 2, 0);
     DMR_STAMP(p, 2, 0u, 8);
@@ -985,6 +1018,11 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     L.pix[tid] = px0;
     L.pix[tid + 256] = px1;
 #endif
+    fm::F3 camT = {0.f, 0.f, 0.f};  // camera variant: this lane's part of dL/d(ray origin) = sum of dL/dT
+    if constexpr (CAM) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) L.dray[tid][c] = 0.f;
+    }
     __syncthreads();
     DMR_STAMP(p, 2, 0u, 9);
     for (uint32_t g0 = 0; g0 < ngroups; g0 += 256u) {
@@ -999,6 +1037,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         float g[NSCAN];
 #pragma unroll
         for (int c = 0; c < NSCAN; c++) g[c] = 0.f;
+        float ex[2] = {0.f, 0.f};  // exact variants: the y, z of the moment A_v (its x is g[6]; see the loop)
         if (valid) {  // key and row ids: a group of skipped pairs at the end of its run still carries the run's sums to the tables
             face = (int)raw[0].x; v0 = (int)raw[1].x; v1 = (int)raw[2].x; v2 = (int)raw[3].x;
             k = face;  // a face occurs once per tile: as good a segment key as the list entry
@@ -1077,19 +1116,37 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
                     const float dL_di1 = cc1.x * dii0 + cc1.y * dii1 + cc1.z * dii2 + fd1 * did;
                     const float dL_di2 = cc2.x * dii0 + cc2.y * dii1 + cc2.z * dii2 + fd2 * did;
                     const float f1 = dL_di1 - dL_di0, f2 = dL_di2 - dL_di0;
-                    const float rdiu = f1 * duc_du + f2 * dvc_du, rdiv = f1 * duc_dv + f2 * dvc_dv;
-                    const float rinv = 1.0f / (denom * denom);
-                    const float w0 = nu, w1 = denom;
-                    const V3 du_dE1 = (-1.0f * xP * w0) * rinv;
-                    const V3 du_dE2 = (dmr::cross(xT, xd) * w1 - w0 * dmr::cross(xE1, xd)) * rinv;
-                    const V3 du_dT = (xP * w1) * rinv;
-                    const V3 dv_dE1 = ((xE2T * w1) - (w2 * xP)) * rinv;
-                    const V3 dv_dE2 = ((xQ * w1) - (w2 * dmr::cross(xE1, xd))) * rinv;
-                    const V3 dv_dT = xE12 * w1 * rinv;
-                    const V3 du_dp0 = -du_dE1 - du_dE2 - du_dT, dv_dp0 = -dv_dE1 - dv_dE2 - dv_dT;
-                    const V3 dp0 = rdiu * du_dp0 + rdiv * dv_dp0;
-                    const V3 dp1 = rdiu * du_dE1 + rdiv * dv_dE1;
-                    const V3 dp2 = rdiu * du_dE2 + rdiv * dv_dE2;
+                    V3 dp0, dp1, dp2;
+                    if constexpr (!EXACT) {
+                        const float rdiu = f1 * duc_du + f2 * dvc_du, rdiv = f1 * duc_dv + f2 * dvc_dv;
+                        const float rinv = 1.0f / (denom * denom);
+                        const float w0 = nu, w1 = denom;
+                        const V3 du_dE1 = (-1.0f * xP * w0) * rinv;
+                        const V3 du_dE2 = (dmr::cross(xT, xd) * w1 - w0 * dmr::cross(xE1, xd)) * rinv;
+                        const V3 du_dT = (xP * w1) * rinv;
+                        const V3 dv_dE1 = ((xE2T * w1) - (w2 * xP)) * rinv;
+                        const V3 dv_dE2 = ((xQ * w1) - (w2 * dmr::cross(xE1, xd))) * rinv;
+                        const V3 dv_dT = xE12 * w1 * rinv;
+                        const V3 du_dp0 = -du_dE1 - du_dE2 - du_dT, dv_dp0 = -dv_dE1 - dv_dE2 - dv_dT;
+                        dp0 = rdiu * du_dp0 + rdiv * dv_dp0;
+                        dp1 = rdiu * du_dE1 + rdiv * dv_dE1;
+                        dp2 = rdiu * du_dE2 + rdiv * dv_dE2;
+                    } else {
+                        // the exact derivative of (u, v) = ((d x E2) . T, (T x E1) . d) / ((d x E2) . E1), pair by pair:
+                        // the formulas the moments below sum, with this pair's d
+                        const float su = dL_diu * inv_denom, sv = dL_div * inv_denom;
+                        const float sb = (su * nu + sv * dmr::dot(xQ, xd)) * inv_denom;
+                        const V3 dT = su * xP + sv * dmr::cross(xE1, xd);
+                        dp1 = sv * dmr::cross(xd, xT) - sb * xP;
+                        dp2 = su * dmr::cross(xT, xd) - sb * dmr::cross(xE1, xd);
+                        dp0 = -(dT + dp1 + dp2);
+                        if constexpr (CAM) {
+                            const V3 gd = su * xE2T + sv * xQ + sb * xE12;  // dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)
+                            float* dr = L.dray[raw[q].y & 255u];
+                            atomicAdd(dr, gd.x); atomicAdd(dr + 1, gd.y); atomicAdd(dr + 2, gd.z);
+                            camT = camT + fm::F3{dT.x, dT.y, dT.z};
+                        }
+                    }
                     float h[NACC];
                     h[0] = dp0.x; h[1] = dp0.y; h[2] = dp0.z;
                     h[3] = dp1.x; h[4] = dp1.y; h[5] = dp1.z;
@@ -1119,11 +1176,31 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
                     // S3 = sum s3 (w2 = Q . E2 is the reference's "v" numerator, Q11).  So a pair adds 7 multiply-adds here
                     // and the six cross products are taken once per list entry, at the segment tails after the scan -- not
                     // ~150 instructions per pair.  Rounding: (s d) x E2 and s (d x E2) lose the same bits.
-                    const float s2 = dL_diu * inv_denom, s3 = dL_div * inv_denom;
-                    const float sb = (s2 * nu + s3 * w2) * inv_denom;
-                    g[0] += sb * xd.x; g[1] += sb * xd.y; g[2] += sb * xd.z;
-                    g[3] += s2 * xd.x; g[4] += s2 * xd.y; g[5] += s2 * xd.z;
-                    g[6] += s3;
+                    //
+                    // The exact derivative (EXACT) is linear in d the same way.  With su = dL/du / denom, sv = dL/dv / denom,
+                    // sb = (su nu + sv nv) / denom (nv = Q . d, v's own numerator):
+                    //   dL/dT = su (d x E2) + sv (E1 x d),  dL/dE1 = sv (d x T) - sb (d x E2),  dL/dE2 = su (T x d) - sb (E1 x d)
+                    // so nine moments B = sum sb d, A_u = sum su d, A_v = sum sv d replace the seven (g[6] and ex hold A_v).
+                    // The camera variant also adds the pair's dL/dd = su (E2 x T) + sv Q - sb (E2 x E1) to its pixel.
+                    if constexpr (!EXACT) {
+                        const float s2 = dL_diu * inv_denom, s3 = dL_div * inv_denom;
+                        const float sb = (s2 * nu + s3 * w2) * inv_denom;
+                        g[0] += sb * xd.x; g[1] += sb * xd.y; g[2] += sb * xd.z;
+                        g[3] += s2 * xd.x; g[4] += s2 * xd.y; g[5] += s2 * xd.z;
+                        g[6] += s3;
+                    } else {
+                        const float su = dL_diu * inv_denom, sv = dL_div * inv_denom;
+                        const float sb = (su * nu + sv * dmr::dot(xQ, xd)) * inv_denom;
+                        g[0] += sb * xd.x; g[1] += sb * xd.y; g[2] += sb * xd.z;
+                        g[3] += su * xd.x; g[4] += su * xd.y; g[5] += su * xd.z;
+                        g[6] += sv * xd.x; ex[0] += sv * xd.y; ex[1] += sv * xd.z;
+                        if constexpr (CAM) {
+                            float* dr = L.dray[raw[q].y & 255u];
+                            atomicAdd(dr, su * xE2T.x + sv * xQ.x + sb * xE12.x);
+                            atomicAdd(dr + 1, su * xE2T.y + sv * xQ.y + sb * xE12.y);
+                            atomicAdd(dr + 2, su * xE2T.z + sv * xQ.z + sb * xE12.z);
+                        }
+                    }
                     g[7] += i0 * dii0; g[8] += i0 * dii1; g[9] += i0 * dii2;
                     g[10] += i1 * dii0; g[11] += i1 * dii1; g[12] += i1 * dii2;
                     g[13] += i2 * dii0; g[14] += i2 * dii1; g[15] += i2 * dii2;
@@ -1136,10 +1213,17 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         // The scan stops at the 16-lane DPP rows: the table takes partial sums just as well, so an entry that crosses a
         // row boundary simply contributes one more partial.
         DMR_STAMP(p, 2, g0 / 256u, 2);
-        seg_scan_level<DPP_ROW_SHR + 1, 0xF>(k, g);
-        seg_scan_level<DPP_ROW_SHR + 2, 0xF>(k, g);
-        seg_scan_level<DPP_ROW_SHR + 4, 0xF>(k, g);
-        seg_scan_level<DPP_ROW_SHR + 8, 0xF>(k, g);
+        if constexpr (!EXACT) {
+            seg_scan_level<DPP_ROW_SHR + 1, 0xF>(k, g);
+            seg_scan_level<DPP_ROW_SHR + 2, 0xF>(k, g);
+            seg_scan_level<DPP_ROW_SHR + 4, 0xF>(k, g);
+            seg_scan_level<DPP_ROW_SHR + 8, 0xF>(k, g);
+        } else {
+            seg_scan_level<DPP_ROW_SHR + 1, 0xF>(k, g, ex);
+            seg_scan_level<DPP_ROW_SHR + 2, 0xF>(k, g, ex);
+            seg_scan_level<DPP_ROW_SHR + 4, 0xF>(k, g, ex);
+            seg_scan_level<DPP_ROW_SHR + 8, 0xF>(k, g, ex);
+        }
 
         // segment tails hold the totals: the ray moments become the three vertex-position gradients (see above)
         DMR_STAMP(p, 2, g0 / 256u, 3);
@@ -1151,10 +1235,21 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
             const F3 mB = {g[0], g[1], g[2]}, mA = {g[3], g[4], g[5]};
             const F3 fT = {xT.x, xT.y, xT.z}, fE1 = {xE1.x, xE1.y, xE1.z}, fE2 = {xE2.x, xE2.y, xE2.z};
             const F3 fQ = {xQ.x, xQ.y, xQ.z}, fE12 = {xE12.x, xE12.y, xE12.z}, fE2T = {xE2T.x, xE2T.y, xE2T.z};
-            dp1 = g[6] * fE2T - cross(mB, fE2);
-            dp2 = cross(fT, mA) - cross(fE1, mB) + g[6] * fQ;
-            const F3 dT = cross(mA, fE2) + g[6] * fE12;
-            dp0 = -(dp1 + dp2 + dT);
+            if constexpr (!EXACT) {
+                dp1 = g[6] * fE2T - cross(mB, fE2);
+                dp2 = cross(fT, mA) - cross(fE1, mB) + g[6] * fQ;
+                const F3 dT = cross(mA, fE2) + g[6] * fE12;
+                dp0 = -(dp1 + dp2 + dT);
+            } else {
+                const F3 mV = {g[6], ex[0], ex[1]};  // A_v (mA is A_u)
+                dp1 = cross(mV, fT) - cross(mB, fE2);
+                dp2 = cross(fT, mA) - cross(fE1, mB);
+                const F3 dT = cross(mA, fE2) + cross(fE1, mV);
+                dp0 = -(dp1 + dp2 + dT);
+                if constexpr (CAM) {
+                    if (tail) camT = camT + dT;
+                }
+            }
         }
         // The face rows (opacity, intensity: two adjacent floats) of the round's tails go out first.  A tail lane sending its two
         // values itself is two memory-side requests (two instructions): 4.6 us of this kernel at C4.  So the tails are compacted
@@ -1186,7 +1281,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
             const uint32_t rid[3] = {(uint32_t)b * (uint32_t)p.P + (uint32_t)v0, (uint32_t)b * (uint32_t)p.P + (uint32_t)v1,
                                      (uint32_t)b * (uint32_t)p.P + (uint32_t)v2};
             int slot[3];
-            tab_find3<VTAB>(L.vkey, rid, slot);
+            tab_find3<VTAB, GV>(L.vkey, rid, slot);
 #pragma unroll
             for (int w = 0; w < 3; w++) {
                 // (ablation build, DMR_ABLATE bit 2048, tests only: odd rows are refused their slot, which exercises the direct-atomic fallback)
@@ -1206,6 +1301,53 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     DMR_STAMP(p, 2, 0u, 5);
     __syncthreads();
     DMR_STAMP(p, 2, 0u, 6);
+    if constexpr (CAM) {
+        // Thread t owns pixel t of the tile: its dL/dd goes through d = w / (|w| + 1e-7), w = inv_mv (pv, 1) - o,
+        // pv = inv_proj (ndc, -1, 1) (pixel_ray) to the view's two inverse matrices.  c[3 col + row]: dL/dinv_mv rows 0-2
+        // (col 3 = dL/do, from the tails), c[12 + 3 col + row]: dL/dinv_proj rows 0-2; the w rows get nothing.
+        float c[24];
+#pragma unroll
+        for (int i = 0; i < 24; i++) c[i] = 0.f;
+        const int px = (tile % p.gx) * TILE + (tid & 15), py = ((tile / p.gx) % p.gy) * TILE + (tid >> 4);
+        if (px < p.W && py < p.H) {
+            const float* im = p.inv_mv + 16 * b; const float* ip = p.inv_proj + 16 * b;
+            const float ndc[4] = {pix2ndc(px + 0.5f, p.W), pix2ndc(py + 0.5f, p.H), -1.0f, 1.0f};
+            const V4 pv = xform4x4({ndc[0], ndc[1], ndc[2]}, ip);
+            const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
+            const V3 w = V3{pw.x, pw.y, pw.z} - view_o;
+            const float n = sqrtf(dmr::dot(w, w)), len = n + 0.0000001f;
+            const float gd[3] = {L.dray[tid][0], L.dray[tid][1], L.dray[tid][2]};
+            // dL/dw = g / len - w (w . g) / (n len^2)
+            const float k = n > 0.f ? (w.x * gd[0] + w.y * gd[1] + w.z * gd[2]) / (n * len * len) : 0.f;
+            const float dw[3] = {gd[0] / len - k * w.x, gd[1] / len - k * w.y, gd[2] / len - k * w.z};
+            const float pvv[3] = {pv.x, pv.y, pv.z};
+#pragma unroll
+            for (int col = 0; col < 3; col++)
+#pragma unroll
+                for (int row = 0; row < 3; row++) c[3 * col + row] = dw[row] * pvv[col];
+#pragma unroll
+            for (int row = 0; row < 3; row++) {  // (R^T dL/dw)_row, R = inv_mv's upper 3x3
+                const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];
+#pragma unroll
+                for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
+            }
+        }
+        c[9] += camT.x; c[10] += camT.y; c[11] += camT.z;
+#pragma unroll
+        for (int i = 0; i < 24; i++)
+#pragma unroll
+            for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 24; i++) L.red[tid >> 6][i] = c[i];
+        }
+        __syncthreads();
+        if (tid < 32) {  // entry tid of the tile's partial, m[4 col + row] of inv_mv (tid < 16) / inv_proj
+            const int row = tid & 3, col = (tid >> 2) & 3, i = 12 * (tid >> 4) + 3 * col + row;
+            const float v = row == 3 ? 0.f : L.red[0][i] + L.red[1][i] + L.red[2][i] + L.red[3][i];
+            ((cam_part + (int64_t)tile * 32 + tid), ...)[0] = v;
+        }
+    }
     if (DMR_DBG(p, 1024)) return;
     // (eight slots per lane are read before the first atomic goes out: the LDS latencies overlap instead of adding up)
     constexpr int FLUSH_BATCH = VTAB % 256 == 0 ? 8 : (VTAB % 128 == 0 ? 4 : 2);
@@ -1306,7 +1448,7 @@ void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1,
 
 void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* vproj, const uint32_t* face_list, TriImageState img,
                               const float4* pixrec, const HitRecord* hits, uint32_t capacity, float* vrow, float* frow,
-                              hipStream_t st) {
+                              hipStream_t st, int grads, float* cam_part) {
     if (capacity == 0) return;
     TriParams p = make_params(s, gx, gy, 0, 0, vproj, nullptr, face_list, img);
     StageScope t(DMR_STAGE_TRI_BACKWARD_HITS, st);
@@ -1314,7 +1456,55 @@ void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* 
 #ifdef DMR_ABLATION
     if (DMR_DBG(p, 131072)) nblocks = std::min(nblocks, 3072u);  // timing experiment, as above
 #endif
-    k_tri_backward_hits<<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow);
+    if (grads == TRI_GRAD_CAMERA)
+        k_tri_backward_hits<TRI_GRAD_CAMERA, float*><<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow, cam_part);
+    else if (grads == TRI_GRAD_EXACT)
+        k_tri_backward_hits<TRI_GRAD_EXACT><<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow);
+    else
+        k_tri_backward_hits<TRI_GRAD_REF><<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow);
+}
+
+// the tiles' camera partials [B * tiles][32] -> out [B][32], one workgroup per view, in a fixed order.  Thread t sums
+// float4 q = t % 8 of every 128th tile from t / 8 on, four tiles' loads in flight at a time (one dependent load after the
+// other was 242 us at C4's 8 160 tiles), then a tree over the 128 rows in LDS.
+__global__ void __launch_bounds__(1024)
+k_tri_camera_reduce(int tiles, const float* __restrict__ cam_part, float* __restrict__ out) {
+    __shared__ float4 s[128][8];
+    const int b = blockIdx.x, q = threadIdx.x & 7, j = threadIdx.x >> 3;
+    const float4* src = reinterpret_cast<const float4*>(cam_part + (int64_t)b * tiles * 32) + q;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    int t = j;
+    for (; t + 3 * 128 < tiles; t += 4 * 128) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[u] = src[(int64_t)(t + u * 128) * 8];
+#pragma unroll
+        for (int u = 0; u < 4; u++) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
+    }
+    for (; t < tiles; t += 128) {
+        const float4 v = src[(int64_t)t * 8];
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    s[j][q] = a;
+    __syncthreads();
+    for (int h = 64; h > 0; h >>= 1) {
+        if (j < h) {
+            const float4 o = s[j + h][q];
+            a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+            s[j][q] = a;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 32) {  // (out may be any float of a flat gradient buffer: dword stores)
+        const float4 v = s[0][threadIdx.x >> 2];
+        const int c = threadIdx.x & 3;
+        out[32 * b + threadIdx.x] = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
+    }
+}
+
+void launch_tri_camera_reduce(int B, int tiles, const float* cam_part, float* out, hipStream_t st) {
+    if (B == 0) return;
+    k_tri_camera_reduce<<<dim3((unsigned)B), dim3(1024), 0, st>>>(tiles, cam_part, out);
 }
 
 void launch_tri_unpack(const dmr_scene& s, const float* vrow, const float* frow, float* dL_dverts,

@@ -40,7 +40,7 @@ import numpy as np
 import torch as th
 import torch.distributed as dist
 
-from . import TetRenderSettings, TriRenderSettings, _with_inverses
+from . import TetRenderSettings, TriRenderSettings, _through_inverse, _tri_grad_keywords, _with_inverses
 
 TILE = 16
 
@@ -252,7 +252,7 @@ class _ShardedTriViewFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, segs, group, parts, impl):
+                settings: TriRenderSettings, segs, group, parts, impl, exact_grads=False, camera_grads=False):
         B = mv_mats.size(0)
         geom = (verts, faces, verts_color, faces_opacity)
         H, W = settings.image_height, settings.image_width
@@ -277,38 +277,52 @@ class _ShardedTriViewFn(th.autograd.Function):
                 color[v, :, y0:y1] = c[0, :, y0:y1]
                 depth[v, ..., y0:y1, :] = z[0, ..., y0:y1, :]
         ctx.settings, ctx.segs, ctx.group, ctx.impl, ctx.nums, ctx.B = settings, tuple(segs), group, impl, nums, B
-        ctx.save_for_backward(*geom, *saved)
+        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
+        ctx.save_for_backward(*geom, *saved, *((mv_mats, proj_mats) if camera_grads else ()))
         return color, depth
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
-        geom, per = saved[:4], saved[4:]
+        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        geom, per = saved[:4], saved[4:4 + 10 * len(ctx.segs)]
         verts, faces = geom[0], geom[1]
         P, F, B = verts.size(0), faces.size(0), ctx.B
         gy = tile_rows(ctx.settings.image_height)
-        # the all-views flat layout [3P | 3P | F | B*P | B*F]: this rank fills the shared part and its views' rows of the per-view parts
-        flat = th.zeros(6 * P + F + B * (P + F), dtype=th.float32, device=verts.device)
+        # the all-views flat layout [3P | 3P | F | B*P | B*F] (camera grads: then [B][dL/dinv_mv 16 | dL/dinv_proj 16]):
+        # this rank fills the shared part and its views' rows of the per-view parts
+        oc = 6 * P + F + B * (P + F)
+        flat = th.zeros(oc + (32 * B if camera else 0), dtype=th.float32, device=verts.device)
         o = 6 * P + F
+        kw = _tri_grad_keywords(ctx.exact_grads, camera)
         for i, (v, r0, r1) in enumerate(ctx.segs):
             s = per[10 * i:10 * i + 10]  # mv, proj, their inverses, verts_depth, faces_intense, four scratch buffers
             g = ctx.impl.render_tris_backward(ctx.settings.bg, *geom, *s[:6], grad_color[v:v + 1].contiguous(),
                                               grad_depth[v:v + 1].contiguous(), ctx.nums[i], *s[6:10],
-                                              rows=(r0, r1) if r1 > r0 else (gy, gy))
+                                              rows=(r0, r1) if r1 > r0 else (gy, gy), **kw)
             flat[:3 * P] += g[0].reshape(-1); flat[3 * P:6 * P] += g[1].reshape(-1); flat[6 * P:o] += g[2].reshape(-1)
             flat[o + v * P:o + (v + 1) * P] += g[3].reshape(-1)
             flat[o + B * P + v * F:o + B * P + (v + 1) * F] += g[4].reshape(-1)
+            if camera:  # the segment's B = 1 rows land in its view's slot
+                flat[oc + 32 * v:oc + 32 * v + 16] += g[5].reshape(-1)
+                flat[oc + 32 * v + 16:oc + 32 * (v + 1)] += g[6].reshape(-1)
         if dist.is_initialized() and dist.get_world_size(ctx.group) > 1:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
         g_verts, g_vcolor, g_fopacity = flat[:3 * P].view(P, 3), flat[3 * P:6 * P].view(P, 3), flat[6 * P:o]
-        g_vdepth, g_fintense = flat[o:o + B * P].view(B, P), flat[o + B * P:].view(B, F)
-        return (g_verts, None, g_vcolor, g_fopacity, None, None, g_vdepth, g_fintense) + (None,) * 5
+        g_vdepth, g_fintense = flat[o:o + B * P].view(B, P), flat[o + B * P:oc].view(B, F)
+        g_mv = g_proj = None
+        if camera:  # every view's inverses (a rank holds only its segments'), then dL/d(inverse) -> dL/d(matrix)
+            inv = _with_inverses(saved[-2], saved[-1])[2:]
+            cam = flat[oc:].view(B, 2, 4, 4)
+            g_mv = _through_inverse(inv[0], cam[:, 0]) if ctx.needs_input_grad[4] else None
+            g_proj = _through_inverse(inv[1], cam[:, 1]) if ctx.needs_input_grad[5] else None
+        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense) + (None,) * 7
 
 
 class _ShardedTriFn(th.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, group, bands, impl):
+                settings: TriRenderSettings, rows, group, bands, impl, exact_grads=False, camera_grads=False):
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         out = impl.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
@@ -317,42 +331,53 @@ class _ShardedTriFn(th.autograd.Function):
         if bands is not None and _world(group) > 1:  # assemble: one all-gather of the bands
             color, depth = gather_bands((color, depth), bands, dist.get_rank(group), group)
         ctx.settings, ctx.rows, ctx.group, ctx.impl, ctx.num_rendered = settings, rows, group, impl, out[0]
+        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *out[3:7])
         return color, depth
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
+        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        kw = _tri_grad_keywords(ctx.exact_grads, camera)  # (no keyword by default: the reference's call)
         if getattr(ctx.impl, "SUPPORTS_FLAT_OUT", False):
-            # the five gradients land back to back in one buffer: the all-reduce payload, no concatenation
+            # the gradients land back to back in one buffer: the all-reduce payload, no concatenation
             verts, faces, mv = saved[0], saved[1], saved[4]
             P, F, B = verts.size(0), faces.size(0), mv.size(0)
-            flat = th.empty(6 * P + F + B * (P + F), dtype=th.float32, device=verts.device)
+            flat = th.empty(6 * P + F + B * (P + F) + (32 * B if camera else 0), dtype=th.float32, device=verts.device)
             g = ctx.impl.render_tris_backward(ctx.settings.bg, *saved[:10], grad_color, grad_depth, ctx.num_rendered,
-                                              *saved[10:14], rows=ctx.rows, flat_out=flat)
+                                              *saved[10:14], rows=ctx.rows, flat_out=flat, **kw)
             if dist.is_initialized() and dist.get_world_size(ctx.group) > 1:
                 dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
-            g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g
         else:
             g = ctx.impl.render_tris_backward(ctx.settings.bg, *saved[:10], grad_color, grad_depth, ctx.num_rendered,
-                                              *saved[10:14], rows=ctx.rows)
-            g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = allreduce_grads(g, ctx.group)
-        return (g_verts, None, g_vcolor, g_fopacity, None, None, g_vdepth, g_fintense) + (None,) * 5
+                                              *saved[10:14], rows=ctx.rows, **kw)
+            g = allreduce_grads(g, ctx.group)
+        g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g[:5]
+        g_mv = g_proj = None
+        if camera:  # dL/d(inverse) -> dL/d(matrix); saved[6:8] are the inverses the forward used
+            g_mv = _through_inverse(saved[6], g[5]) if ctx.needs_input_grad[4] else None
+            g_proj = _through_inverse(saved[7], g[6]) if ctx.needs_input_grad[5] else None
+        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense) + (None,) * 7
 
 
 class ShardedTriRenderer(th.nn.Module):
     """TriRenderer whose image is sharded across the ranks of `group`: by tile-row bands of all views ("bands") or, with
     several views, by (view, band) pairs ("view_bands"; see the module docstring).
 
-    Same call signature as TriRenderer.  Every rank must pass identical inputs; every rank gets the
-    full summed gradients.  The bands may be refreshed at any time with `set_row_work` (e.g. every few
+    Same call signature as TriRenderer, and the same exact_grads / camera_grads options (with camera_grads the flat
+    all-reduce payload gains [B][dL/dinv_mv 16 | dL/dinv_proj 16]).  Every rank must pass identical inputs; every rank
+    gets the full summed gradients.  The bands may be refreshed at any time with `set_row_work` (e.g. every few
     iterations from `row_work_from_ranges` / `view_row_work_from_ranges`)."""
 
-    def __init__(self, render_settings: TriRenderSettings, group=None, assemble: bool = True, impl=None, partition: str = "auto"):
+    def __init__(self, render_settings: TriRenderSettings, group=None, assemble: bool = True, impl=None, partition: str = "auto",
+                 exact_grads: bool = False, camera_grads: bool = False):
         super().__init__()
         if partition not in ("auto", "bands", "view_bands"):
             raise ValueError("partition must be 'auto', 'bands' or 'view_bands'")
         self.render_settings = render_settings
+        self.exact_grads = bool(exact_grads)
+        self.camera_grads = bool(camera_grads)
         self.group = group
         self.assemble = assemble
         self.partition = partition
@@ -409,12 +434,15 @@ class ShardedTriRenderer(th.nn.Module):
             return _ShardedTriViewFn.apply(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
                                            mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
                                            self.render_settings, tuple(parts[self.rank]), self.group,
-                                           tuple(tuple(p) for p in parts) if self.assemble else None, self.impl)
+                                           tuple(tuple(p) for p in parts) if self.assemble else None, self.impl, *self._grad_opts())
         rows = self.rows if self.world > 1 else (0, 0)
         bands = tuple(self.bands) if self.assemble and self.world > 1 else None
         return _ShardedTriFn.apply(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
                                    mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
-                                   self.render_settings, rows, self.group, bands, self.impl)
+                                   self.render_settings, rows, self.group, bands, self.impl, *self._grad_opts())
+
+    def _grad_opts(self) -> tuple:
+        return (self.exact_grads, self.camera_grads) if self.exact_grads or self.camera_grads else ()
 
 
 class _ShardedTetFn(th.autograd.Function):

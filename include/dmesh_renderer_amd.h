@@ -40,7 +40,8 @@ extern "C" {
  * caller owns, returns from forward and passes back to backward.  DMR_BUF_WORK is a
  * transient workspace of the backward calls (packed gradient accumulators). */
 enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE = 3, DMR_BUF_WORK = 4,
-       DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */ };
+       DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */,
+       DMR_BUF_TRI_CAMERA_GRADS = 6 /* dmr_tri_backward with DMR_FLAG_TRI_CAMERA_GRADS: an OUTPUT, see there */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -50,7 +51,8 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * entries, not 4 GiB for its tiles; the reference's binning buffer scales with R only) -- plus, tet only, the forward's march sequence for
  * the backward: 4 bytes per tile pixel (256 Nt of them) and step of capacity, capacity = the longest march of the previous
  * call with the same view configuration * 1.25 + 4 steps (0 in the first such call), the whole capped at 16 GiB;
- * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS only)
+ * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record (+ 128 Nt with DMR_FLAG_TRI_CAMERA_GRADS); tri camera grads
+ * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS only)
  * 4 (3P + BF), exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
@@ -110,6 +112,12 @@ typedef struct dmr_scene {
 /* dmr_tet_backward also computes dL/dverts and dL/dfaces_intense (beyond the reference, whose tet renderer has no such
  * gradients); see dmr_tet_backward.  Ignored by every other call. */
 #define DMR_FLAG_TET_FULL_GRADS 2
+/* dmr_tri_backward writes the exact derivative of the image into dL_dverts instead of the reference's (whose "dv/dp" is
+ * dt/dp); see dmr_tri_backward.  Ignored by every other call. */
+#define DMR_FLAG_TRI_EXACT_GRADS 4
+/* dmr_tri_backward also computes the gradients of the inverse matrices (implies DMR_FLAG_TRI_EXACT_GRADS); see there.
+ * Ignored by every other call. */
+#define DMR_FLAG_TRI_CAMERA_GRADS 8
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -125,7 +133,16 @@ int dmr_tri_forward(const dmr_scene* scene, float* out_color, float* out_depth,
                     dmr_alloc_fn alloc, void* alloc_ctx, void* stream, int* num_rendered);
 
 /* Gradient outputs are fully overwritten: dL_dverts [P,3], dL_dvcolor [P,3],
- * dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F]. */
+ * dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F].
+ * With DMR_FLAG_TRI_EXACT_GRADS in scene->flags, dL_dverts is the exact derivative of colour and depth through each blended
+ * pair's Moeller-Trumbore (u, v) (coverage, list order and the clamp region held fixed, as for every gradient here); the
+ * other four outputs are the same sums in another order.  With DMR_FLAG_TRI_CAMERA_GRADS the call also requests buffer
+ * DMR_BUF_TRI_CAMERA_GRADS through `alloc`, once, of 128 B bytes, and fully overwrites it with fp32
+ * [B][dL/dinv_mv 16 | dL/dinv_proj 16] in the contract layout m[4*col+row] whatever mats_transposed says: the gradients of
+ * the inverse matrices through every pixel's ray (origin = inv_mv's translation column, direction
+ * normalize(inv_mv (inv_proj (ndc, -1, 1)).xyz - origin) with no w divide); their w rows are 0.  dL_dvdepth does not
+ * involve the matrices.  No host wait is added (DMR_FLAG_ASYNC and stream capture work as without the flags).  Without
+ * the flags the call is exactly as before and requests no buffer beyond the work space. */
 int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      int num_rendered, const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,
