@@ -7,12 +7,13 @@ with identical argument order, dtypes, shapes, outputs and gradient routing.  Th
 lives in libdmesh_renderer_hip.so (hand-written gfx950 kernels) behind `_C`.
 
 Conventions kept from the reference: the Modules receive ROW-major [B,4,4] matrices and
-pass transposed views down (:219-220, :476-477); the autograd Functions invert those
+pass transposed views down (:219-220, :476-477); _TriFn / _TetFn invert those
 (:62-63, :298-299); the tri Module only casts `faces`, the tet Module casts everything (Q23).
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Tuple
+import math
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch as th
 
@@ -65,74 +66,122 @@ def _through_inverse(y: th.Tensor, g: th.Tensor) -> th.Tensor:
     return -th.matmul(th.matmul(yt, g), yt)
 
 
-def _tri_grad_keywords(exact_grads: bool, camera_grads: bool) -> dict:
-    """The keywords of _C.render_tris_backward for the tri gradient options: none by default (the reference's call)."""
-    if camera_grads:
-        return {"camera_grads": True}
-    return {"exact_grads": True} if exact_grads else {}
+def _trailing(*args) -> tuple:
+    """The optional trailing arguments of _TriFn / _TetFn.apply without the unset ones at the end: every argument of
+    apply costs host time on each call, and the default call passes none."""
+    n = len(args)
+    while n and not args[n - 1]:
+        n -= 1
+    return args[:n]
+
+
+def _tri_forward(impl, settings: TriRenderSettings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows):
+    """One render_tris call -> (num_rendered, color, depth, what its backward needs after geom: the matrices, their
+    inverses, verts_depth, faces_intense and the four scratch buffers)."""
+    cams = _with_inverses(mv_mats, proj_mats)
+    try:
+        out = impl.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
+                               settings.image_height, settings.image_width, rows=rows)
+    except Exception as ex:
+        print("\nAn error occured in forward.")
+        print(ex)
+        raise
+    return out[0], out[1], out[2], (*cams, verts_depth, faces_intense, *out[3:7])
+
+
+def _tri_backward(impl, settings: TriRenderSettings, geom, saved, grad_color, grad_depth, num_rendered, rows, kw):
+    """One render_tris_backward call for a _tri_forward."""
+    try:
+        return impl.render_tris_backward(settings.bg, *geom, *saved[:6], grad_color, grad_depth, num_rendered, *saved[6:],
+                                         rows=rows, **kw)
+    except Exception:
+        print("\nAn error occured in backward.\n")
+        raise
+
+
+def _tri_grad_options(ctx) -> Tuple[bool, dict]:
+    """(camera, keywords of render_tris_backward).  The matrices' gradients are computed only when asked for and a matrix
+    needs one: otherwise the exact variant, which skips the per-pixel ray sums.  No keyword by default: the reference's
+    call.  (A fresh dict: the caller may add flat_out.)"""
+    if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
+        return True, {"camera_grads": True}
+    return False, ({"exact_grads": True} if ctx.exact_grads else {})
+
+
+def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj) -> Tuple[Optional[th.Tensor], Optional[th.Tensor]]:
+    """dL/d(inverse) -> dL/d(matrix) for the matrices (inputs 4 and 5) that need a gradient."""
+    return (_through_inverse(inv_mv, g_inv_mv) if ctx.needs_input_grad[4] else None,
+            _through_inverse(inv_proj, g_inv_proj) if ctx.needs_input_grad[5] else None)
+
+
+def _tri_flat(P: int, F: int, B: int, camera: bool, device, alloc=th.empty) -> Tuple[th.Tensor, List[th.Tensor]]:
+    """The flat tri gradient buffer [3P | 3P | F | B*P | B*F], with camera grads followed by [B][dL/dinv_mv 16 |
+    dL/dinv_proj 16] (what render_tris_backward(flat_out=) fills), and its pieces as views shaped like the gradients."""
+    shapes = [(P, 3), (P, 3), (F,), (B, P), (B, F)] + ([(B, 2, 4, 4)] if camera else [])
+    sizes = [math.prod(s) for s in shapes]
+    flat = alloc(sum(sizes), dtype=th.float32, device=device)
+    return flat, [p.view(s) for p, s in zip(flat.split(sizes), shapes)]
 
 
 class _TriFn(th.autograd.Function):
-    """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense,
-    settings, rows[, exact_grads, camera_grads].  Gradients flow to verts, verts_color, faces_opacity, verts_depth,
-    faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer)."""
+    """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense, settings, rows, shard,
+    exact_grads, camera_grads (the last three only when set: see _trailing).  Gradients flow to verts, verts_color,
+    faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  shard: None
+    on one device (the kernels are then `_C` as it is at call time: tests swap it); from a sharded Module
+    (sharding._Shard) its kernels, the band images to assemble and the gradients' all-reduce."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, exact_grads=False, camera_grads=False):
-        cams = _with_inverses(mv_mats, proj_mats)
+                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False):
+        impl = _C if shard is None else shard.impl
         geom = (verts, faces, verts_color, faces_opacity)
-        try:
-            out = _C.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
-                                 settings.image_height, settings.image_width, rows=rows)
-        except Exception as ex:
-            print("\nAn error occured in forward.")
-            print(ex)
-            raise
-        num_rendered, color, depth = out[0], out[1], out[2]
-        ctx.settings, ctx.rows, ctx.num_rendered = settings, rows, num_rendered
+        num_rendered, color, depth, saved = _tri_forward(impl, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense,
+                                                         rows)
+        if shard is not None:
+            color, depth = shard.gather((color, depth))
+        ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
         ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
-        ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *out[3:7])
+        ctx.save_for_backward(*geom, *saved)
         return color, depth
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
-        inputs, scratch = saved[:10], saved[10:14]
-        # the matrices' gradients only when asked for: otherwise the exact variant, which skips the per-pixel ray sums
-        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
-        try:
-            g = _C.render_tris_backward(ctx.settings.bg, *inputs, grad_color, grad_depth, ctx.num_rendered,
-                                        *scratch, rows=ctx.rows, **_tri_grad_keywords(ctx.exact_grads, camera))
-        except Exception:
-            print("\nAn error occured in backward.\n")
-            raise
-        g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g[:5]
-        g_mv = g_proj = None
-        if camera:  # dL/d(inverse) -> dL/d(matrix); saved[6:8] are the inverses the forward used
-            g_mv = _through_inverse(saved[6], g[5]) if ctx.needs_input_grad[4] else None
-            g_proj = _through_inverse(saved[7], g[6]) if ctx.needs_input_grad[5] else None
-        return g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense, None, None, None, None
+        geom, saved = saved[:4], saved[4:]
+        camera, kw = _tri_grad_options(ctx)
+        shard, flat = ctx.shard, None
+        impl = _C if shard is None else shard.impl
+        if shard is not None and shard.flat_out:  # the gradients land back to back in the all-reduce payload
+            flat = kw["flat_out"] = _tri_flat(geom[0].size(0), geom[1].size(0), saved[0].size(0), camera, geom[0].device)[0]
+        g = _tri_backward(impl, ctx.settings, geom, saved, grad_color, grad_depth, ctx.num_rendered, ctx.rows, kw)
+        if shard is not None:
+            g = shard.reduce(g, flat)
+        g_mv, g_proj = _camera_grads(ctx, saved[2], saved[3], g[5], g[6]) if camera else (None, None)
+        return g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4], None, None, None, None, None
 
 
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
-    faces_intense (beyond the reference)."""
+    faces_intense (beyond the reference).  shard: as for _TriFn."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, full_grads=False):
+                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False):
+        impl = _C if shard is None else shard.impl
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         topo = (tets, face_tets, tet_faces)
         try:
-            out = _C.render_tets(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo,
-                                 settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows)
+            out = impl.render_tets(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo,
+                                   settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows)
         except Exception:
             print("\nAn error occured in forward.")
             raise
-        color, depth, active = out[0], out[1], out[2] > 0.5  # bool mask, reference :333
-        ctx.settings, ctx.rows, ctx.full_grads = settings, rows, full_grads
+        color, depth, active = out[0], out[1], out[2]
+        if shard is not None:
+            color, depth, active = shard.gather((color, depth, active))
+        active = active > 0.5  # bool mask, reference :333
+        ctx.settings, ctx.rows, ctx.shard, ctx.full_grads = settings, rows, shard, full_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
         ctx.mark_non_differentiable(active)
         return color, depth, active
@@ -140,36 +189,40 @@ class _TetFn(th.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_depth, _grad_active):
         saved = ctx.saved_tensors
-        inputs, scratch = saved[:13], saved[13:17]
-        g_verts = g_fintense = None
+        kw = {"full_grads": True} if ctx.full_grads else {}  # (the keyword only when set: the default call is the reference's)
+        shard, flat = ctx.shard, None
+        impl = _C if shard is None else shard.impl
+        if shard is not None and shard.flat_out:
+            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F]
+            P, F, B = saved[0].size(0), saved[1].size(0), saved[4].size(0)
+            flat = kw["flat_out"] = th.empty(3 * P + F + (3 * P + B * F if ctx.full_grads else 0), dtype=th.float32,
+                                             device=saved[0].device)
         try:
-            if ctx.full_grads:  # (the keyword is only passed when set: the default call is the reference's)
-                g_verts, g_vcolor, g_fopacity, g_fintense = _C.render_tets_backward(
-                    ctx.settings.bg, *inputs, grad_color, grad_depth, *scratch, rows=ctx.rows, full_grads=True)
-            else:
-                g_vcolor, g_fopacity = _C.render_tets_backward(ctx.settings.bg, *inputs, grad_color, grad_depth,
-                                                               *scratch, rows=ctx.rows)
+            g = impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth, *saved[13:17],
+                                          rows=ctx.rows, **kw)
         except Exception:
             print("\nAn error occured in backward.\n")
             raise
-        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 6
+        if shard is not None:
+            g = shard.reduce(g, flat)
+        g_verts, g_vcolor, g_fopacity, g_fintense = g if ctx.full_grads else (None, *g, None)
+        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 7
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False):
     """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices.  exact_grads,
     camera_grads: see TriRenderer."""
-    opts = (bool(exact_grads), bool(camera_grads)) if exact_grads or camera_grads else ()
-    return _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth,
-                        faces_intense, render_settings, tuple(rows), *opts)
+    return _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
+                        render_settings, tuple(rows), *_trailing(None, bool(exact_grads), bool(camera_grads)))
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False):
     """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads: see
     TetRenderer."""
-    return _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth,
-                        faces_intense, tets, face_tets, tet_faces, render_settings, tuple(rows), bool(full_grads))
+    return _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
+                        tets, face_tets, tet_faces, render_settings, tuple(rows), *_trailing(None, bool(full_grads)))
 
 
 class TriRenderer(th.nn.Module):
@@ -200,9 +253,17 @@ class TriRenderer(th.nn.Module):
         self.camera_grads = bool(camera_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
-        return render_tri(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
-                          mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
-                          self.render_settings, exact_grads=self.exact_grads, camera_grads=self.camera_grads)
+        return self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
+                            mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense)
+
+    def _render(self, *inputs):
+        """_TriFn on the normalised inputs (faces int32, the matrices transposed); ShardedTriRenderer adds a partition."""
+        rows, shard = self._shard()
+        return _TriFn.apply(*inputs, self.render_settings, rows, *_trailing(shard, self.exact_grads, self.camera_grads))
+
+    def _shard(self):
+        """(rows, shard) of the Functions: all rows on one device (the sharded Modules return their band)."""
+        return (0, 0), None
 
 
 class TetRenderer(th.nn.Module):
@@ -229,8 +290,11 @@ class TetRenderer(th.nn.Module):
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
         f32, i32 = dict(dtype=th.float32), dict(dtype=th.int32)
-        return render_tet(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
-                          mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
-                          verts_depth.to(**f32), faces_intense.to(**f32),
-                          tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
-                          full_grads=self.full_grads)
+        rows, shard = self._shard()
+        return _TetFn.apply(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
+                            mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
+                            verts_depth.to(**f32), faces_intense.to(**f32),
+                            tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
+                            rows, *_trailing(shard, self.full_grads))
+
+    _shard = TriRenderer._shard  # (rows, shard) of one device

@@ -92,9 +92,11 @@ void load_abi() {
     }
     g_abi.path = path;
     g_abi.handle = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (!g_abi.handle)
-        throw std::runtime_error(path + " cannot be loaded (" + std::string(dlerror() ? dlerror() : "?") +
+    if (!g_abi.handle) {
+        const char* why = dlerror();  // (a second call would return NULL: the message is consumed by the first)
+        throw std::runtime_error(path + " cannot be loaded (" + std::string(why ? why : "?") +
                                  "): the HIP library is not built (run `python -m dmesh_renderer_amd.build`); there is no CPU fallback");
+    }
     bind(g_abi.tri_forward, "dmr_tri_forward"); bind(g_abi.tri_backward, "dmr_tri_backward");
     bind(g_abi.tet_forward, "dmr_tet_forward"); bind(g_abi.tet_backward, "dmr_tet_backward");
     bind(g_abi.invert_mats, "dmr_invert_mats"); bind(g_abi.export_item, "dmr_export");
@@ -276,20 +278,43 @@ TriFwdOut render_tris(const at::Tensor& background, const at::Tensor& verts, con
                           call.scratch.get(DMR_BUF_BINNING), call.scratch.get(DMR_BUF_IMAGE));
 }
 
+// The gradient outputs of a backward, one piece per shape: each allocated, or carved in order out of flat_out, the
+// caller's buffer (the payload of the one all-reduce in sharding.py), which must hold exactly all of them.
+std::vector<at::Tensor> grad_outputs(c10::Device dev, const std::optional<at::Tensor>& flat_out,
+                                     const std::vector<std::vector<int64_t>>& shapes) {
+    std::vector<at::Tensor> out;
+    if (!flat_out.has_value()) {
+        for (const auto& s : shapes) out.push_back(at::empty(s, f32_on(dev)));
+        return out;
+    }
+    int64_t total = 0;
+    for (const auto& s : shapes) total += c10::multiply_integers(s);
+    const at::Tensor& fo = *flat_out;
+    if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != total)
+        err("flat_out must be a contiguous float32 tensor of " + std::to_string(total) + " elements on " + dev.str());
+    const at::Tensor flat = fo.view({-1});
+    int64_t o = 0;
+    for (const auto& s : shapes) {
+        const int64_t n = c10::multiply_integers(s);
+        out.push_back(flat.narrow(0, o, n).view(s));
+        o += n;
+    }
+    return out;
+}
+
 // -> (dL_dverts [P,3], dL_dvcolor [P,3], dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F]), with camera grads
 //    followed by (dL_dinv_mv_mats [B,4,4], dL_dinv_proj_mats [B,4,4]): element [b,i,j] is the gradient of the inverse
 //    tensor's [b,i,j] as the call received it (the library's contract layout m[4*col+row] read as a row-major [4,4] is
-//    the transpose of the matrix it means, which is how such a tensor holds it)
-using TriBwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-using TriBwdCamOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-template <bool CAM>
-std::conditional_t<CAM, TriBwdCamOut, TriBwdOut> tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+//    the transpose of the matrix it means, which is how such a tensor holds it).
+// The binding: without the two keywords exactly the reference's function (render.cu:134-208).
+py::tuple render_tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                                const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
                                int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool exact_grads) {
+                               bool exact_grads, bool camera_grads) {
+    std::optional<py::gil_scoped_release> nogil(std::in_place);  // (the default call waits for the size read-back)
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
     if (dL_dout_color.dim() != 4) err("dL_dout_color must have dimensions (B, 3, H, W)");
@@ -299,61 +324,28 @@ std::conditional_t<CAM, TriBwdCamOut, TriBwdOut> tris_backward(const at::Tensor&
     const at::Tensor gc = f32(dL_dout_color, "dL_dout_color");  // may arrive non-contiguous / expanded (render.cu:197-198)
     const at::Tensor gd = f32(dL_dout_depth, "dL_dout_depth");
     const int64_t B = call.sc.B, P = call.sc.P, F = call.sc.F;
-    at::Tensor g_verts, g_vcolor, g_fop, g_vdepth, g_fint, g_cam;
-    // camera grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16] is DMR_BUF_TRI_CAMERA_GRADS, served by alloc_cb from g_cam; with
+    // camera grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16] is DMR_BUF_TRI_CAMERA_GRADS, served by alloc_cb from g[5]; with
     // flat_out it follows the default layout ([3P | 3P | F | BP | BF | 32B]), so one all-reduce still carries everything
-    if (!flat_out.has_value()) {
-        const auto opt = f32_on(dev);
-        g_verts = at::empty({P, 3}, opt); g_vcolor = at::empty({P, NUM_CHANNELS}, opt); g_fop = at::empty({F}, opt);
-        g_vdepth = at::empty({B, P}, opt); g_fint = at::empty({B, F}, opt);
-        if (CAM) g_cam = at::empty({B, 32}, opt);
-    } else {
-        const at::Tensor& fo = *flat_out;
-        const int64_t total = 6 * P + F + B * (P + F) + (CAM ? 32 * B : 0);
-        if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != total)
-            err("flat_out must be a contiguous float32 tensor of " + std::to_string(total) + " elements on " + dev.str());
-        const at::Tensor flat = fo.view({-1});
-        int64_t o = 0;
-        g_verts = flat.narrow(0, o, 3 * P).view({P, 3}); o += 3 * P;
-        g_vcolor = flat.narrow(0, o, 3 * P).view({P, NUM_CHANNELS}); o += 3 * P;
-        g_fop = flat.narrow(0, o, F); o += F;
-        g_vdepth = flat.narrow(0, o, B * P).view({B, P}); o += B * P;
-        g_fint = flat.narrow(0, o, B * F).view({B, F}); o += B * F;
-        if (CAM) g_cam = flat.narrow(0, o, 32 * B).view({B, 32});
-    }
-    if (CAM) {
-        call.scratch.tri_cam = g_cam;
+    std::vector<std::vector<int64_t>> shapes = {{P, 3}, {P, NUM_CHANNELS}, {F}, {B, P}, {B, F}};
+    if (camera_grads) shapes.push_back({B, 32});
+    std::vector<at::Tensor> g = grad_outputs(dev, flat_out, shapes);
+    if (camera_grads) {
+        call.scratch.tri_cam = g[5];
         call.sc.flags |= DMR_FLAG_TRI_CAMERA_GRADS;
     }
-    if (exact_grads) call.sc.flags |= DMR_FLAG_TRI_EXACT_GRADS;
+    if (exact_grads || camera_grads) call.sc.flags |= DMR_FLAG_TRI_EXACT_GRADS;
     const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     if (g_abi.tri_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), (int)R, mptr<const void>(pb), mptr<const void>(fb),
-                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g_verts), mptr<float>(g_vcolor), mptr<float>(g_fop),
-                           mptr<float>(g_vdepth), mptr<float>(g_fint), &alloc_cb, &call.scratch, call.stream()))
+                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g[0]), mptr<float>(g[1]), mptr<float>(g[2]),
+                           mptr<float>(g[3]), mptr<float>(g[4]), &alloc_cb, &call.scratch, call.stream()))
         raise_lib();
-    if constexpr (CAM)
-        return TriBwdCamOut(g_verts, g_vcolor, g_fop, g_vdepth, g_fint, g_cam.view({B, 2, 4, 4}).select(1, 0),
-                            g_cam.view({B, 2, 4, 4}).select(1, 1));
-    else
-        return TriBwdOut(g_verts, g_vcolor, g_fop, g_vdepth, g_fint);
-}
-
-// the binding: without the two keywords exactly the reference's function (render.cu:134-208)
-py::object render_tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                                const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
-                                int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                                bool exact_grads, bool camera_grads) {
-    auto run = [&](auto cam) {
-        py::gil_scoped_release nogil;
-        return tris_backward<decltype(cam)::value>(background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats,
-                                                   inv_proj_mats, verts_depth, faces_intense, dL_dout_color, dL_dout_depth, R, pointBuffer,
-                                                   faceBuffer, binningBuffer, imageBuffer, rows, flat_out, exact_grads || camera_grads);
-    };
-    if (camera_grads) return py::cast(run(std::true_type{}));
-    return py::cast(run(std::false_type{}));
+    if (camera_grads) {
+        const at::Tensor cam = g[5].view({B, 2, 4, 4});
+        g[5] = cam.select(1, 0);
+        g.push_back(cam.select(1, 1));
+    }
+    nogil.reset();
+    return py::tuple(py::cast(g));
 }
 
 void check_tets(const at::Tensor& faces, const at::Tensor& tets, const at::Tensor& face_tets, const at::Tensor& tet_faces) {
@@ -392,17 +384,17 @@ TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, con
 }
 
 // -> (dL_dverts_color [P,3], dL_dfaces_opacity [F]), or with full_grads
-//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F])
-using TetBwdOut = std::tuple<at::Tensor, at::Tensor>;
-using TetBwdFullOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-template <bool FULL>
-std::conditional_t<FULL, TetBwdFullOut, TetBwdOut> tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
+//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F]).
+// The binding: without full_grads exactly the reference's function (render.cu:338-412).
+py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                                const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets,
                                const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
                                const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out) {
+                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                               bool full_grads) {
+    std::optional<py::gil_scoped_release> nogil(std::in_place);
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
     if (grad_color.dim() != 4) err("grad_color must have dimensions (B, 3, H, W)");
@@ -411,54 +403,24 @@ std::conditional_t<FULL, TetBwdFullOut, TetBwdOut> tets_backward(const at::Tenso
               faces_intense, H, W, &tets, &face_tets, &tet_faces, 0, rows);
     const at::Tensor gc = f32(grad_color, "grad_color"), gd = f32(grad_depth, "grad_depth");
     const int64_t P = call.sc.P, F = call.sc.F, B = call.sc.B;
-    // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from this tensor.  With flat_out
+    // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from g[2].  With flat_out
     // the layout is [dL_dverts_color 3P | dL_dfaces_opacity F | dL_dverts 3P | dL_dfaces_intense BF]: the default layout
     // followed by that buffer, so one all-reduce still carries everything.
-    const int64_t n = 3 * P + F + (FULL ? 3 * P + B * F : 0);
-    at::Tensor g_vcolor, g_fop, g_full;
-    if (!flat_out.has_value()) {
-        g_vcolor = at::empty({P, 3}, f32_on(dev)); g_fop = at::empty({F}, f32_on(dev));
-        if (FULL) g_full = at::empty({3 * P + B * F}, f32_on(dev));
-    } else {
-        const at::Tensor& fo = *flat_out;
-        if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != n)
-            err("flat_out must be a contiguous float32 tensor of " + std::to_string(n) + " elements on " + dev.str());
-        const at::Tensor flat = fo.view({-1});
-        g_vcolor = flat.narrow(0, 0, 3 * P).view({P, 3}); g_fop = flat.narrow(0, 3 * P, F);
-        if (FULL) g_full = flat.narrow(0, 3 * P + F, 3 * P + B * F);
-    }
-    if (FULL) {
-        call.scratch.tet_grads = g_full;
+    std::vector<std::vector<int64_t>> shapes = {{P, 3}, {F}};
+    if (full_grads) shapes.push_back({3 * P + B * F});
+    std::vector<at::Tensor> g = grad_outputs(dev, flat_out, shapes);
+    if (full_grads) {
+        call.scratch.tet_grads = g[2];
         call.sc.flags |= DMR_FLAG_TET_FULL_GRADS;
     }
     const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     if (g_abi.tet_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), mptr<const void>(pb), mptr<const void>(fb),
-                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g_vcolor), mptr<float>(g_fop), &alloc_cb,
+                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g[0]), mptr<float>(g[1]), &alloc_cb,
                            &call.scratch, call.stream()))
         raise_lib();
-    if constexpr (FULL)
-        return TetBwdFullOut(g_full.narrow(0, 0, 3 * P).view({P, 3}), g_vcolor, g_fop, g_full.narrow(0, 3 * P, B * F).view({B, F}));
-    else
-        return TetBwdOut(g_vcolor, g_fop);
-}
-
-// the binding: without full_grads exactly the reference's function (render.cu:338-412)
-py::object render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                                const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets,
-                                const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
-                                const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                                bool full_grads) {
-    auto run = [&](auto full) {
-        py::gil_scoped_release nogil;
-        return tets_backward<decltype(full)::value>(background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats,
-                                                    inv_proj_mats, verts_depth, faces_intense, tets, face_tets, tet_faces, grad_color,
-                                                    grad_depth, pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out);
-    };
-    if (full_grads) return py::cast(run(std::true_type{}));
-    return py::cast(run(std::false_type{}));
+    if (full_grads) g = {g[2].narrow(0, 0, 3 * P).view({P, 3}), g[0], g[1], g[2].narrow(0, 3 * P, B * F).view({B, F})};
+    nogil.reset();
+    return py::tuple(py::cast(g));
 }
 
 // ---- extensions -----------------------------------------------------------------------------------------------------

@@ -34,13 +34,14 @@ an oracle-backed stand-in to exercise this file's logic on CPU with the gloo bac
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch as th
 import torch.distributed as dist
 
-from . import TetRenderSettings, TriRenderSettings, _through_inverse, _tri_grad_keywords, _with_inverses
+from . import (TetRenderer, TetRenderSettings, TriRenderer, TriRenderSettings, _camera_grads, _tri_backward, _tri_flat,
+               _tri_forward, _tri_grad_options, _with_inverses)
 
 TILE = 16
 
@@ -247,6 +248,38 @@ def gather_view_bands(images: Sequence[Sequence[th.Tensor]], B: int, parts: Sequ
     return [o if im.dim() == 4 else o.squeeze(1) for o, im in zip(outs, images[0])]
 
 
+def _band_rows(band, gy: int) -> Tuple[int, int]:
+    """`rows=` of a call for a band of tile rows; an empty band becomes (gy, gy): (0, 0) would mean "all rows" to the C ABI."""
+    r0, r1 = band
+    return (gy, gy) if r1 <= r0 else (int(r0), int(r1))
+
+
+class _Shard(NamedTuple):
+    """The `shard` argument of _TriFn / _TetFn from a sharded Module: the kernels, the group, and the bands to assemble
+    the images from (None: every rank keeps its own band)."""
+    impl: object
+    group: object
+    bands: Optional[tuple]
+
+    @property
+    def flat_out(self) -> bool:
+        """impl's backward writes the gradients into one caller-owned buffer, the all-reduce payload."""
+        return getattr(self.impl, "SUPPORTS_FLAT_OUT", False)
+
+    def gather(self, images):
+        if self.bands is None or _world(self.group) <= 1:
+            return images
+        return gather_bands(images, self.bands, dist.get_rank(self.group), self.group)
+
+    def reduce(self, grads, flat: Optional[th.Tensor]):
+        """The gradients summed over the ranks with ONE all-reduce: of `flat` if the backward wrote them there."""
+        if flat is None:
+            return allreduce_grads(grads, self.group)
+        if _world(self.group) > 1:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+        return grads
+
+
 class _ShardedTriViewFn(th.autograd.Function):
     """The "view_bands" partition: this rank renders its segments (view, row_begin, row_end), one B = 1 call each."""
 
@@ -259,14 +292,14 @@ class _ShardedTriViewFn(th.autograd.Function):
         gy = tile_rows(H)
         if not segs:  # a rank without rows still joins the collectives: an empty band of view 0
             segs = ((0, gy, gy),)
+        rows = [_band_rows((r0, r1), gy) for _, r0, r1 in segs]
         saved, nums, outs = [], [], []
-        for v, r0, r1 in segs:
-            cams = _with_inverses(mv_mats[v:v + 1], proj_mats[v:v + 1])
-            vdepth, fintense = verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous()
-            out = impl.render_tris(settings.bg, *geom, *cams, vdepth, fintense, H, W, rows=(r0, r1) if r1 > r0 else (gy, gy))
-            outs.append((out[1], out[2]))
-            nums.append(out[0])
-            saved += [*cams, vdepth, fintense, *out[3:7]]
+        for (v, _, _), r in zip(segs, rows):
+            num, color, depth, s = _tri_forward(impl, settings, geom, mv_mats[v:v + 1], proj_mats[v:v + 1],
+                                                verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous(), r)
+            outs.append((color, depth))
+            nums.append(num)
+            saved += s
         if parts is not None and _world(group) > 1:  # assemble: one all-gather of every rank's rows
             color, depth = gather_view_bands(outs, B, parts, dist.get_rank(group), group)
         else:  # this rank's rows of its views, in place in full-size images
@@ -276,7 +309,7 @@ class _ShardedTriViewFn(th.autograd.Function):
                 y0, y1 = min(H, TILE * r0), min(H, TILE * r1)
                 color[v, :, y0:y1] = c[0, :, y0:y1]
                 depth[v, ..., y0:y1, :] = z[0, ..., y0:y1, :]
-        ctx.settings, ctx.segs, ctx.group, ctx.impl, ctx.nums, ctx.B = settings, tuple(segs), group, impl, nums, B
+        ctx.settings, ctx.segs, ctx.rows, ctx.group, ctx.impl, ctx.nums = settings, tuple(segs), rows, group, impl, nums
         ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
         ctx.save_for_backward(*geom, *saved, *((mv_mats, proj_mats) if camera_grads else ()))
         return color, depth
@@ -284,84 +317,57 @@ class _ShardedTriViewFn(th.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
-        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
-        geom, per = saved[:4], saved[4:4 + 10 * len(ctx.segs)]
-        verts, faces = geom[0], geom[1]
-        P, F, B = verts.size(0), faces.size(0), ctx.B
-        gy = tile_rows(ctx.settings.image_height)
-        # the all-views flat layout [3P | 3P | F | B*P | B*F] (camera grads: then [B][dL/dinv_mv 16 | dL/dinv_proj 16]):
-        # this rank fills the shared part and its views' rows of the per-view parts
-        oc = 6 * P + F + B * (P + F)
-        flat = th.zeros(oc + (32 * B if camera else 0), dtype=th.float32, device=verts.device)
-        o = 6 * P + F
-        kw = _tri_grad_keywords(ctx.exact_grads, camera)
-        for i, (v, r0, r1) in enumerate(ctx.segs):
-            s = per[10 * i:10 * i + 10]  # mv, proj, their inverses, verts_depth, faces_intense, four scratch buffers
-            g = ctx.impl.render_tris_backward(ctx.settings.bg, *geom, *s[:6], grad_color[v:v + 1].contiguous(),
-                                              grad_depth[v:v + 1].contiguous(), ctx.nums[i], *s[6:10],
-                                              rows=(r0, r1) if r1 > r0 else (gy, gy), **kw)
-            flat[:3 * P] += g[0].reshape(-1); flat[3 * P:6 * P] += g[1].reshape(-1); flat[6 * P:o] += g[2].reshape(-1)
-            flat[o + v * P:o + (v + 1) * P] += g[3].reshape(-1)
-            flat[o + B * P + v * F:o + B * P + (v + 1) * F] += g[4].reshape(-1)
+        camera, kw = _tri_grad_options(ctx)
+        geom = saved[:4]
+        B = grad_color.size(0)
+        # the all-views flat layout: this rank fills the shared part and its views' rows of the per-view parts
+        flat, g = _tri_flat(geom[0].size(0), geom[1].size(0), B, camera, geom[0].device, th.zeros)
+        for i, ((v, _, _), rows) in enumerate(zip(ctx.segs, ctx.rows)):
+            s = saved[4 + 10 * i:14 + 10 * i]  # mv, proj, their inverses, verts_depth, faces_intense, four scratch buffers
+            gs = _tri_backward(ctx.impl, ctx.settings, geom, s, grad_color[v:v + 1].contiguous(),
+                               grad_depth[v:v + 1].contiguous(), ctx.nums[i], rows, kw)
+            for k in range(3):
+                g[k] += gs[k]
+            g[3][v] += gs[3][0]
+            g[4][v] += gs[4][0]
             if camera:  # the segment's B = 1 rows land in its view's slot
-                flat[oc + 32 * v:oc + 32 * v + 16] += g[5].reshape(-1)
-                flat[oc + 32 * v + 16:oc + 32 * (v + 1)] += g[6].reshape(-1)
-        if dist.is_initialized() and dist.get_world_size(ctx.group) > 1:
+                g[5][v, 0] += gs[5][0]
+                g[5][v, 1] += gs[6][0]
+        if _world(ctx.group) > 1:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
-        g_verts, g_vcolor, g_fopacity = flat[:3 * P].view(P, 3), flat[3 * P:6 * P].view(P, 3), flat[6 * P:o]
-        g_vdepth, g_fintense = flat[o:o + B * P].view(B, P), flat[o + B * P:oc].view(B, F)
         g_mv = g_proj = None
-        if camera:  # every view's inverses (a rank holds only its segments'), then dL/d(inverse) -> dL/d(matrix)
-            inv = _with_inverses(saved[-2], saved[-1])[2:]
-            cam = flat[oc:].view(B, 2, 4, 4)
-            g_mv = _through_inverse(inv[0], cam[:, 0]) if ctx.needs_input_grad[4] else None
-            g_proj = _through_inverse(inv[1], cam[:, 1]) if ctx.needs_input_grad[5] else None
-        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense) + (None,) * 7
+        if camera:  # every view's inverses (a rank holds only its segments')
+            g_mv, g_proj = _camera_grads(ctx, *_with_inverses(saved[-2], saved[-1])[2:], g[5][:, 0], g[5][:, 1])
+        return (g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4]) + (None,) * 7
 
 
-class _ShardedTriFn(th.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, group, bands, impl, exact_grads=False, camera_grads=False):
-        cams = _with_inverses(mv_mats, proj_mats)
-        geom = (verts, faces, verts_color, faces_opacity)
-        out = impl.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
-                               settings.image_height, settings.image_width, rows=rows)
-        color, depth = out[1], out[2]
-        if bands is not None and _world(group) > 1:  # assemble: one all-gather of the bands
-            color, depth = gather_bands((color, depth), bands, dist.get_rank(group), group)
-        ctx.settings, ctx.rows, ctx.group, ctx.impl, ctx.num_rendered = settings, rows, group, impl, out[0]
-        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
-        ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *out[3:7])
-        return color, depth
+class _Banded:
+    """The tile-row bands of a sharded Module, one per rank of `group`, and the `shard` argument of its Functions."""
 
-    @staticmethod
-    def backward(ctx, grad_color, grad_depth):
-        saved = ctx.saved_tensors
-        camera = ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
-        kw = _tri_grad_keywords(ctx.exact_grads, camera)  # (no keyword by default: the reference's call)
-        if getattr(ctx.impl, "SUPPORTS_FLAT_OUT", False):
-            # the gradients land back to back in one buffer: the all-reduce payload, no concatenation
-            verts, faces, mv = saved[0], saved[1], saved[4]
-            P, F, B = verts.size(0), faces.size(0), mv.size(0)
-            flat = th.empty(6 * P + F + B * (P + F) + (32 * B if camera else 0), dtype=th.float32, device=verts.device)
-            g = ctx.impl.render_tris_backward(ctx.settings.bg, *saved[:10], grad_color, grad_depth, ctx.num_rendered,
-                                              *saved[10:14], rows=ctx.rows, flat_out=flat, **kw)
-            if dist.is_initialized() and dist.get_world_size(ctx.group) > 1:
-                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
-        else:
-            g = ctx.impl.render_tris_backward(ctx.settings.bg, *saved[:10], grad_color, grad_depth, ctx.num_rendered,
-                                              *saved[10:14], rows=ctx.rows, **kw)
-            g = allreduce_grads(g, ctx.group)
-        g_verts, g_vcolor, g_fopacity, g_vdepth, g_fintense = g[:5]
-        g_mv = g_proj = None
-        if camera:  # dL/d(inverse) -> dL/d(matrix); saved[6:8] are the inverses the forward used
-            g_mv = _through_inverse(saved[6], g[5]) if ctx.needs_input_grad[4] else None
-            g_proj = _through_inverse(saved[7], g[6]) if ctx.needs_input_grad[5] else None
-        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, g_vdepth, g_fintense) + (None,) * 7
+    def __init__(self, render_settings, group, assemble: bool, impl, **grad_opts):
+        super().__init__(render_settings, **grad_opts)
+        self.group = group
+        self.assemble = assemble
+        if impl is None:
+            from . import _C as impl  # the HIP extension; fails loudly if it is not built
+        self.impl = impl
+        self.world = _world(group)
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.bands = equal_bands(tile_rows(render_settings.image_height), self.world)
+
+    def set_row_work(self, row_work: Sequence[float]) -> None:
+        self.bands = balanced_bands(row_work, self.world)
+
+    @property
+    def rows(self) -> Tuple[int, int]:
+        return _band_rows(self.bands[self.rank], tile_rows(self.render_settings.image_height))
+
+    def _shard(self):
+        rows = self.rows if self.world > 1 else (0, 0)
+        return rows, _Shard(self.impl, self.group, tuple(self.bands) if self.assemble and self.world > 1 else None)
 
 
-class ShardedTriRenderer(th.nn.Module):
+class ShardedTriRenderer(_Banded, TriRenderer):
     """TriRenderer whose image is sharded across the ranks of `group`: by tile-row bands of all views ("bands") or, with
     several views, by (view, band) pairs ("view_bands"; see the module docstring).
 
@@ -372,21 +378,10 @@ class ShardedTriRenderer(th.nn.Module):
 
     def __init__(self, render_settings: TriRenderSettings, group=None, assemble: bool = True, impl=None, partition: str = "auto",
                  exact_grads: bool = False, camera_grads: bool = False):
-        super().__init__()
         if partition not in ("auto", "bands", "view_bands"):
             raise ValueError("partition must be 'auto', 'bands' or 'view_bands'")
-        self.render_settings = render_settings
-        self.exact_grads = bool(exact_grads)
-        self.camera_grads = bool(camera_grads)
-        self.group = group
-        self.assemble = assemble
+        super().__init__(render_settings, group, assemble, impl, exact_grads=exact_grads, camera_grads=camera_grads)
         self.partition = partition
-        if impl is None:
-            from . import _C as impl  # the HIP extension; fails loudly if it is not built
-        self.impl = impl
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.bands = equal_bands(tile_rows(render_settings.image_height), self.world)
         self.view_work = None   # "view_bands": [B, rows] work of the (view, tile row) sequence; None: every row counts the same
         self.segment_cost_per_face = SEGMENT_COST_PER_FACE  # (SEGMENT_COST_PER_FACE_WITH_PAIRS when the row work counts blended pairs)
         self._parts_key, self._parts = None, None
@@ -400,7 +395,7 @@ class ShardedTriRenderer(th.nn.Module):
         if w.ndim == 2:
             self.view_work, self._parts_key = w.copy(), None
             w = w.sum(axis=0)
-        self.bands = balanced_bands(w, self.world)
+        super().set_row_work(w)
 
     def _use_view_bands(self, B: int) -> bool:
         return self.world > 1 and B > 1 and self.partition != "bands"
@@ -417,79 +412,17 @@ class ShardedTriRenderer(th.nn.Module):
             self._parts_key = key
         return self._parts
 
-    @staticmethod
-    def _rows(band, gy) -> Tuple[int, int]:
-        r0, r1 = band
-        return (gy, gy) if r1 <= r0 else (int(r0), int(r1))  # an empty band; (0, 0) would mean "all rows" to the C ABI
-
-    @property
-    def rows(self) -> Tuple[int, int]:
-        return self._rows(self.bands[self.rank], tile_rows(self.render_settings.image_height))
-
-    def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
-        B = mv_mats.size(0)
-        gy = tile_rows(self.render_settings.image_height)
-        if self._use_view_bands(B):
-            parts = self.view_parts(B, faces.size(0))
-            return _ShardedTriViewFn.apply(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
-                                           mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
-                                           self.render_settings, tuple(parts[self.rank]), self.group,
-                                           tuple(tuple(p) for p in parts) if self.assemble else None, self.impl, *self._grad_opts())
-        rows = self.rows if self.world > 1 else (0, 0)
-        bands = tuple(self.bands) if self.assemble and self.world > 1 else None
-        return _ShardedTriFn.apply(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
-                                   mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense,
-                                   self.render_settings, rows, self.group, bands, self.impl, *self._grad_opts())
-
-    def _grad_opts(self) -> tuple:
-        return (self.exact_grads, self.camera_grads) if self.exact_grads or self.camera_grads else ()
+    def _render(self, *inputs):
+        B, F = inputs[4].size(0), inputs[1].size(0)  # mv_mats, faces
+        if not self._use_view_bands(B):
+            return super()._render(*inputs)
+        parts = self.view_parts(B, F)
+        return _ShardedTriViewFn.apply(*inputs, self.render_settings, tuple(parts[self.rank]), self.group,
+                                       tuple(tuple(p) for p in parts) if self.assemble else None, self.impl,
+                                       self.exact_grads, self.camera_grads)
 
 
-class _ShardedTetFn(th.autograd.Function):
-    @staticmethod
-    def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, group, bands, impl, full_grads=False):
-        cams = _with_inverses(mv_mats, proj_mats)
-        geom = (verts, faces, verts_color, faces_opacity)
-        topo = (tets, face_tets, tet_faces)
-        out = impl.render_tets(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo,
-                               settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows)
-        color, depth, active = out[0], out[1], out[2]
-        if bands is not None and _world(group) > 1:
-            color, depth, active = gather_bands((color, depth, active), bands, dist.get_rank(group), group)
-        active = active > 0.5  # bool mask, reference __init__.py:333
-        ctx.settings, ctx.rows, ctx.group, ctx.impl, ctx.full_grads = settings, rows, group, impl, full_grads
-        ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
-        ctx.mark_non_differentiable(active)
-        return color, depth, active
-
-    @staticmethod
-    def backward(ctx, grad_color, grad_depth, _grad_active):
-        saved = ctx.saved_tensors
-        verts, faces = saved[0], saved[1]
-        P, F, B = verts.size(0), faces.size(0), saved[4].size(0)
-        full = {"full_grads": True} if ctx.full_grads else {}  # (the keyword only when set: the default call is unchanged)
-        g_verts = g_fintense = None
-        if getattr(ctx.impl, "SUPPORTS_FLAT_OUT", False):
-            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F]
-            n = 3 * P + F + (3 * P + B * F if ctx.full_grads else 0)
-            flat = th.empty(n, dtype=th.float32, device=verts.device)
-            g = ctx.impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth,
-                                              *saved[13:17], rows=ctx.rows, flat_out=flat, **full)
-            if _world(ctx.group) > 1:
-                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
-        else:
-            g = ctx.impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth, *saved[13:17],
-                                              rows=ctx.rows, **full)
-            g = allreduce_grads(g, ctx.group)
-        if ctx.full_grads:
-            g_verts, g_vcolor, g_fopacity, g_fintense = g
-        else:
-            g_vcolor, g_fopacity = g
-        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 9
-
-
-class ShardedTetRenderer(th.nn.Module):
+class ShardedTetRenderer(_Banded, TetRenderer):
     """TetRenderer whose image is sharded by tile-row bands across the ranks of `group` ("the tet path
     shards identically"): every rank bins with rects clipped to its band, finds first hits and marches the rays of
     its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F]
@@ -498,36 +431,4 @@ class ShardedTetRenderer(th.nn.Module):
 
     def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
                  full_grads: bool = False):
-        super().__init__()
-        self.render_settings = render_settings
-        self.full_grads = bool(full_grads)
-        self.group = group
-        self.assemble = assemble
-        if impl is None:
-            from . import _C as impl  # the HIP extension; fails loudly if it is not built
-        self.impl = impl
-        self.world = _world(group)
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.bands = equal_bands(tile_rows(render_settings.image_height), self.world)
-
-    def set_row_work(self, row_work: Sequence[float]) -> None:
-        self.bands = balanced_bands(row_work, self.world)
-
-    @property
-    def rows(self) -> Tuple[int, int]:
-        r0, r1 = self.bands[self.rank]
-        if r1 <= r0:
-            gy = tile_rows(self.render_settings.image_height)
-            return (gy, gy)
-        return (int(r0), int(r1))
-
-    def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces):
-        f32, i32 = dict(dtype=th.float32), dict(dtype=th.int32)
-        rows = self.rows if self.world > 1 else (0, 0)
-        bands = tuple(self.bands) if self.assemble and self.world > 1 else None
-        return _ShardedTetFn.apply(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
-                                   mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
-                                   verts_depth.to(**f32), faces_intense.to(**f32),
-                                   tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32),
-                                   self.render_settings, rows, self.group, bands, self.impl, self.full_grads)
+        super().__init__(render_settings, group, assemble, impl, full_grads=full_grads)

@@ -102,3 +102,17 @@ def test_product_library_has_no_ablation_switch():
         for m in re.finditer(r"getenv", src):
             before = src[:m.start()]
             assert before.rfind("#ifdef DMR_ABLATION") > before.rfind("#endif"), f"{f}: getenv outside DMR_ABLATION"
+
+
+def test_missing_library_reports_the_loader_error(tmp_path):
+    """A HIP library that cannot be loaded makes the import fail with the dynamic loader's own message."""
+    import subprocess
+    import sys
+    missing = str(tmp_path / "missing" / "libdmesh_renderer_hip.so")
+    env = dict(os.environ, DMR_LIBRARY=missing)
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "try:\n    import dmesh_renderer_amd._C\nexcept ImportError as e:\n    print('ImportError:', e)" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.startswith("ImportError:"), r.stdout
+    assert f"cannot be loaded ({missing}: " in r.stdout and "_M_construct" not in r.stdout, r.stdout
