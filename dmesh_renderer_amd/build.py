@@ -107,7 +107,6 @@ def build(force: bool = False, verbose: bool = False, ablation: bool = False) ->
            "-Wall", "-Wno-unused-function", "-Wl,-rpath,/opt/rocm/lib", "-o", lib + ".tmp"]
     if ablation:
         cmd.append("-DDMR_ABLATION")
-    cmd += os.environ.get("DMR_HIPCC_FLAGS", "").split()  # tuning experiments only
     cmd += [os.path.join(CSRC, s) for s in SOURCES]
     if verbose:
         print(" ".join(cmd), flush=True)

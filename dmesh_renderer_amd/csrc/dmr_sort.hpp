@@ -14,10 +14,7 @@
 namespace dmr {
 
 constexpr int SORT_LDS_KEYS = 2048;  // 16 KiB of keys + 8 KiB of ranks
-#ifndef DMR_SORT_SEG
-#define DMR_SORT_SEG 128
-#endif
-constexpr int SORT_SEG = DMR_SORT_SEG;  // keys per rank-sorted segment (two per lane)
+constexpr int SORT_SEG = 128;  // keys per rank-sorted segment (two per lane)
 constexpr int SORT_LDS_BYTES = SORT_LDS_KEYS * (int)(sizeof(uint64_t) + sizeof(uint32_t));
 
 template <class Ptr>
@@ -55,9 +52,6 @@ __device__ __forceinline__ void bitonic_pass(Ptr a, uint32_t n, uint32_t npow2, 
 __device__ __forceinline__ void sort_tile(uint32_t begin, uint32_t n, uint64_t* __restrict__ keys, uint32_t* __restrict__ face_list,
                                           uint64_t* __restrict__ s_keys, uint32_t* __restrict__ s_rank, uint32_t tid) {
     const uint32_t wave = tid >> 6, lane = tid & 63;
-#ifndef DMR_SORT_BUCKETS
-#define DMR_SORT_BUCKETS 1
-#endif
     // BUCKETS FIRST (round 3).  The rank sort below compares every key with the 128 keys of its segment and then searches every
     // other segment: ~400 VALU instructions per key, a fifth of k_tri_forward's instructions in a kernel whose VALUs are busy 97 %
     // of the time.  Keys that are cut into SORT_NB order-preserving buckets first -- by the bits of
@@ -68,15 +62,9 @@ __device__ __forceinline__ void sort_tile(uint32_t begin, uint32_t n, uint64_t* 
     // A tile whose fullest bucket holds more than SORT_BUCKET_MAX keys (depths bunched in a few buckets) is sorted as before.
     // k_tri_forward 77.0 -> 73.2 us at C4 on the same box; 64 / 128 / 256 buckets and a limit of 64 / 96 / 160 within 1 us of
     // each other (profiles/r03/variants_sort_buckets_c4.txt).
-#ifndef DMR_SORT_NB_LOG2
-#define DMR_SORT_NB_LOG2 6
-#endif
-#ifndef DMR_SORT_BUCKET_MAX
-#define DMR_SORT_BUCKET_MAX 96
-#endif
-    constexpr uint32_t SORT_NB_LOG2 = DMR_SORT_NB_LOG2, SORT_NB = 1u << SORT_NB_LOG2, SORT_BUCKET_MAX = DMR_SORT_BUCKET_MAX;
+    constexpr uint32_t SORT_NB_LOG2 = 6, SORT_NB = 1u << SORT_NB_LOG2, SORT_BUCKET_MAX = 96;
     static_assert(SORT_NB >= 64 && SORT_NB <= 512, "a wave scans the bucket sizes, SORT_NB / 64 per lane");
-    if (DMR_SORT_BUCKETS && n <= SORT_LDS_KEYS && n > 64u) {
+    if (n <= SORT_LDS_KEYS && n > 64u) {
         uint32_t* const s_cnt = s_rank;            // [SORT_NB] bucket sizes, then claim cursors are not needed again
         uint32_t* const s_base = s_rank + SORT_NB; // [SORT_NB] exclusive scan
         uint32_t* const s_misc = s_rank + 2 * SORT_NB;  // [0] min depth bits, [1] max depth bits, [2] fullest bucket

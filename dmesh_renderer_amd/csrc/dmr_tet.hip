@@ -21,20 +21,12 @@ namespace dmr {
 
 constexpr int FI_CHUNK = 256;
 
-#ifndef DMR_TET_FI_HOIST
-#define DMR_TET_FI_HOIST 1
-#endif
-#if DMR_TET_FI_HOIST
 // A staged face of the first-hit search with everything of ray_tri_hit (cuda_renderer/auxiliary.h:265-296) that does not depend
 // on the ray's direction -- the origin is the same for all pixels of a view: T = o - p0, E1, E2, Q = T x E1, Q . E2 (the
 // numerator of t) -- computed once per staged face with the reference's arithmetic instead of once per (pixel, face): 23 of a
 // test's ~68 instructions in a kernel whose VALUs are busy 91 % of the time (profiles/r03/valu_mix_c3.txt).
 struct alignas(16) HitRec { float T[3], E1[3], E2[3], Q[3]; float qe2, min_depth, max_depth; int face; };
 static_assert(sizeof(HitRec) == 64, "HitRec");
-#else
-struct alignas(16) HitRec { float p0[3], p1[3], p2[3]; float min_depth, max_depth; int face; };
-static_assert(sizeof(HitRec) == 48, "HitRec");
-#endif
 
 struct alignas(16) TetFaceRec { float p0[3], p1[3], p2[3], n[3]; int ft0, ft1; float opacity; int pad; };
 static_assert(sizeof(TetFaceRec) == 64, "TetFaceRec");
@@ -43,25 +35,18 @@ struct alignas(16) TetColRec { float c0[3], c1[3], c2[3]; int v0, v1, v2; float 
 static_assert(sizeof(TetColRec) == 64, "TetColRec");
 
 // Per tet: everything a march step needs of it, in ONE 224-byte record -- its four faces (id | slot of the face in the tet
-// behind it << 29 | orientation flip << 31), the tets behind them (-1: none) and, per face, the three vertices and the unit
-// normal before orientation (round 3: the vertex p0 and the edge vectors p1 - p0, p2 - p0).  A step used to be tet record -> three face records: two dependent levels of gathers; the march
-// now carries the slot its current face has in its current tet, so the step's eleven loads go out together, one level.
+// behind it << 29 | orientation flip << 31), the tets behind them (-1: none) and, per face, the vertex p0, the edge vectors
+// p1 - p0, p2 - p0 and the unit normal before orientation.  A step used to be tet record -> three face records: two dependent
+// levels of gathers; the march now carries the slot its current face has in its current tet, so the step's eleven loads go
+// out together, one level.
 struct alignas(16) TetBlock { int face[4]; int nbr[4]; float geo[4][12]; };
 static_assert(sizeof(TetBlock) == 224, "TetBlock");
-#ifndef DMR_TET_DUP_BIT
-#define DMR_TET_DUP_BIT 1
-#endif
-#if DMR_TET_DUP_BIT
 constexpr int TET_FACE_MASK = 0x0fffffff;  // (check_scene: F < 2^28)
 // bit 28 of a face entry: the same face id sits in another slot of this tet as well (malformed tet_faces).  The march carries
 // the slot of its current face, so the reference's "exactly one of the tet's four faces is the current one" (`cnt != 3`,
 // forward.cu:716-722) is: the slot's entry is the current face and has no duplicate -- one compare per step instead of four
 // masks, four compares and a count, all of the 4.5-cycle kind in a kernel whose VALUs are busy all the time.
 constexpr int TET_FACE_DUP = 0x10000000;
-#else
-constexpr int TET_FACE_MASK = 0x1fffffff;  // (check_scene: F < 2^29)
-constexpr int TET_FACE_DUP = 0;
-#endif
 
 struct TetParams {
     int B, P, F, W, H, gx, gy, r0;
@@ -158,19 +143,11 @@ k_tet_prep_tets(int T, int F, const float* __restrict__ verts, const int* __rest
         }
         r.face[i] = f; r.nbr[i] = nbr;
         r.geo[i][0] = p0.x; r.geo[i][1] = p0.y; r.geo[i][2] = p0.z;
-#ifndef DMR_TET_EDGES
-#define DMR_TET_EDGES 1
-#endif
-#if DMR_TET_EDGES
         // (the edge vectors, not the vertices: ray_tri_hit's p1 - p0 and p2 - p0, taken here once per tet and face -- the march
         // is VALU-bound, profiles/r03/valu_mix_c3.txt, and these were 18 of a step's ~420 instructions)
         const V3 E1 = p1 - p0, E2 = p2 - p0;
         r.geo[i][3] = E1.x; r.geo[i][4] = E1.y; r.geo[i][5] = E1.z;
         r.geo[i][6] = E2.x; r.geo[i][7] = E2.y; r.geo[i][8] = E2.z;
-#else
-        r.geo[i][3] = p1.x; r.geo[i][4] = p1.y; r.geo[i][5] = p1.z;
-        r.geo[i][6] = p2.x; r.geo[i][7] = p2.y; r.geo[i][8] = p2.z;
-#endif
         r.geo[i][9] = n.x; r.geo[i][10] = n.y; r.geo[i][11] = n.z;
     }
     tetrec[t] = r;
@@ -251,7 +228,6 @@ k_tet_first_intersect(TetParams p, const float* __restrict__ key_depth, const fl
             const V3 c = load_v3(p.verts, p.faces[3 * face + 1]);
             const V3 e = load_v3(p.verts, p.faces[3 * face + 2]);
             HitRec& r = s_rec[tid];
-#if DMR_TET_FI_HOIST
             const V3 hT = view_o - a, hE1 = c - a, hE2 = e - a;
             const V3 hQ = cross(hT, hE1);
             r.T[0] = hT.x; r.T[1] = hT.y; r.T[2] = hT.z;
@@ -259,11 +235,6 @@ k_tet_first_intersect(TetParams p, const float* __restrict__ key_depth, const fl
             r.E2[0] = hE2.x; r.E2[1] = hE2.y; r.E2[2] = hE2.z;
             r.Q[0] = hQ.x; r.Q[1] = hQ.y; r.Q[2] = hQ.z;
             r.qe2 = dot(hQ, hE2);
-#else
-            r.p0[0] = a.x; r.p0[1] = a.y; r.p0[2] = a.z;
-            r.p1[0] = c.x; r.p1[1] = c.y; r.p1[2] = c.z;
-            r.p2[0] = e.x; r.p2[1] = e.y; r.p2[2] = e.z;
-#endif
             r.min_depth = key_depth[(int64_t)b * p.F + face];
             r.max_depth = max_depth[(int64_t)b * p.F + face];
             r.face = face;
@@ -273,7 +244,6 @@ k_tet_first_intersect(TetParams p, const float* __restrict__ key_depth, const fl
             const HitRec& r = s_rec[j];
             if (min_T >= 0.0f && r.min_depth > min_T_max_depth) { done = true; continue; }
             V3 tuv;
-#if DMR_TET_FI_HOIST
             {
                 const V3 E1 = {r.E1[0], r.E1[1], r.E1[2]}, E2 = {r.E2[0], r.E2[1], r.E2[2]};
                 const V3 P = cross(rd, E2);
@@ -285,11 +255,6 @@ k_tet_first_intersect(TetParams p, const float* __restrict__ key_depth, const fl
                 tuv.z = dot({r.Q[0], r.Q[1], r.Q[2]}, rd) * inv_denom;
                 if (!(tuv.x >= 0.0f && tuv.y >= 0.0f && tuv.z >= 0.0f && tuv.y + tuv.z <= 1.0f)) continue;
             }
-#else
-            if (!ray_tri_hit(ro, rd, {r.p0[0], r.p0[1], r.p0[2]}, {r.p1[0], r.p1[1], r.p1[2]},
-                             {r.p2[0], r.p2[1], r.p2[2]}, tuv))
-                continue;
-#endif
             if (min_T < 0.0f || tuv.x < min_T) { min_T = tuv.x; min_T_max_depth = r.max_depth; ff = r.face; }
         }
     }
@@ -343,16 +308,9 @@ __device__ __forceinline__ bool march_step(const TetParams& p, V3 ro, V3 rd, int
     const float4 a0 = g0[0], a1 = g0[1], a2 = g0[2];
     const float4 b0 = g1[0], b1 = g1[1], b2 = g1[2];
     const float4 c0 = g2[0], c1 = g2[1], c2 = g2[2];
-#if DMR_TET_DUP_BIT
     const int cur_e = s1 ? tr.x : (s2 ? tr.y : (s3 ? tr.z : tr.w));  // the entry of the slot the march carries
     if ((cur_e & (TET_FACE_MASK | TET_FACE_DUP)) != curr_face) return false;  // the reference's `cnt != 3` (see TET_FACE_DUP)
     const bool cur_flip = cur_e < 0;
-#else
-    const int t0 = tr.x & TET_FACE_MASK, t1 = tr.y & TET_FACE_MASK, t2 = tr.z & TET_FACE_MASK, t3 = tr.w & TET_FACE_MASK;
-    const bool m0 = t0 == curr_face, m1 = t1 == curr_face, m2 = t2 == curr_face, m3 = t3 == curr_face;
-    if ((int)m0 + (int)m1 + (int)m2 + (int)m3 != 1) return false;  // the reference's `cnt != 3` (then the slot is the match's)
-    const bool cur_flip = (m0 ? tr.x : (m1 ? tr.y : (m2 ? tr.z : tr.w))) < 0;
-#endif
     const int r0e = s1 ? tr.y : tr.x, r1e = s2 ? tr.z : tr.y, r2e = s3 ? tr.w : tr.z;
     const int nb0 = s1 ? nb.y : nb.x, nb1 = s2 ? nb.z : nb.y, nb2 = s3 ? nb.w : nb.z;
     bool ok = true;
@@ -363,16 +321,12 @@ __device__ __forceinline__ bool march_step(const TetParams& p, V3 ro, V3 rd, int
     float nrt = 0, niu = 0, niv = 0;
     float ndn = 0.f;
     bool amb = false;
-    // q0..q2: p0, p1, p2, unit normal of the candidate; e: its header entry; behind: the tet on its other side
+    // q0..q2: p0, p1 - p0, p2 - p0, unit normal of the candidate; e: its header entry; behind: the tet on its other side
     // (a face id outside [0, F) -- malformed tet_faces -- never hits)
     auto test = [&](float4 q0, float4 q1, float4 q2, int e, int behind) {
         const int of = e & TET_FACE_MASK;
         V3 tuv;
-#if DMR_TET_EDGES
         const bool hit = ray_tri_hit_edges(ro, rd, {q0.x, q0.y, q0.z}, {q0.w, q1.x, q1.y}, {q1.z, q1.w, q2.x}, tuv) && (unsigned)of < (unsigned)p.F;
-#else
-        const bool hit = ray_tri_hit(ro, rd, {q0.x, q0.y, q0.z}, {q0.w, q1.x, q1.y}, {q1.z, q1.w, q2.x}, tuv) && (unsigned)of < (unsigned)p.F;
-#endif
         const V3 n = {q2.y, q2.z, q2.w};
         const float dn0 = dot(n, rd);
         const float dn = e < 0 ? -dn0 : dn0;
@@ -402,10 +356,8 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {  // all 64 lanes 
     return v;
 }
 
-#ifndef DMR_TET_FWD_WAVES
-#define DMR_TET_FWD_WAVES 4
-#endif
-__global__ void __launch_bounds__(256, DMR_TET_FWD_WAVES)
+constexpr int TET_FWD_WAVES = 4;
+__global__ void __launch_bounds__(256, TET_FWD_WAVES)
 k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_active) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
@@ -465,12 +417,9 @@ k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ ou
         C = C + tmp_T * opacity * col;
         const V3 pt = ro + (rd * curr_rt);
         const V4 pn = xform4x4(xform4x3(pt, mv), pr);
-#ifndef DMR_TET_FWD_RCP
-#define DMR_TET_FWD_RCP 1
-#endif
         // (the hit point's depth decides nothing: 1-ulp reciprocal instead of the IEEE division's ten instructions -- the march is
         // VALU-bound; out_depth moves by ~1e-7 of its value, the tolerance is 1e-5)
-        const float pw = DMR_TET_FWD_RCP ? __builtin_amdgcn_rcpf(clamp_w(pn.w)) : 1.0f / clamp_w(pn.w);
+        const float pw = __builtin_amdgcn_rcpf(clamp_w(pn.w));
         D += tmp_T * opacity * (pn.z * pw);
         prev_log_T = log_T;
         if (opacity < 1.0f) log_T += cq3.y;  // logf(1 - opacity), per face (TetColRec)
@@ -519,13 +468,7 @@ k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ ou
 // precision: ds_add_f32 retires one lane per ~3 cycles per CU, ds_add_f64 ten times that
 // (scripts/micro/lds_atomics.hip: 194 vs 20 cycles per conflict-free wave instruction), and this kernel was
 // bound by exactly those adds (10 per marched face and pixel).
-#ifndef DMR_TET_TBL
-#define DMR_TET_TBL 512
-#endif
-#ifndef DMR_TET_BWD_WAVES
-#define DMR_TET_BWD_WAVES 1
-#endif
-constexpr int TET_TBL = DMR_TET_TBL;     // slots (a multiple of 16)
+constexpr int TET_TBL = 512;     // slots (a multiple of 16)
 constexpr int TET_PROBES = 8;
 
 // Full gradients (DMR_FLAG_TET_FULL_GRADS, beyond the reference): the kernels below are instantiated a second time with
@@ -533,10 +476,7 @@ constexpr int TET_PROBES = 8;
 // positions) and dL/d(faces_intense[b, face]).  Their table has fewer slots: 384 x 20 f64 cells + keys = 61.5 KiB, two
 // workgroups per CU (the full re-marching kernel's 192 VGPRs allow two as well; the full sequence kernel has 147);
 // 512 slots would be 82 KiB, one.
-#ifndef DMR_TET_TBL_FULL
-#define DMR_TET_TBL_FULL 384
-#endif
-constexpr int TET_TBL_FULL = DMR_TET_TBL_FULL;  // (a multiple of 8: the full flush covers 8 slots per pass)
+constexpr int TET_TBL_FULL = 384;  // (a multiple of 8: the full flush covers 8 slots per pass)
 constexpr int tet_nv(bool full) { return full ? 20 : 10; }
 constexpr int tet_tbl(bool full) { return full ? TET_TBL_FULL : TET_TBL; }
 
@@ -986,8 +926,9 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
 // records, three tests and the orientation logic.  Stops where the reference stops: behind first_face, or behind an entry
 // whose bit 31 says the reverse march would find two candidates there.
 // Full: as k_tet_backward's
+constexpr int TET_BWD_WAVES = 1;
 template <class... Full>
-__global__ void __launch_bounds__(256, DMR_TET_BWD_WAVES)
+__global__ void __launch_bounds__(256, TET_BWD_WAVES)
 k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                    float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, uint32_t* __restrict__ host_seq_steps, Full... full) {
     constexpr bool FULL = sizeof...(Full) != 0;

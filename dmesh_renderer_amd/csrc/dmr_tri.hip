@@ -8,7 +8,7 @@
 // consumed in 128-face chunks staged through LDS (waves 0-1 build the coverage records, waves 2-3 the shading
 // records).  Per chunk:
 //
-//   A. coverage  -- face-parallel: 256 / CHUNK threads rasterise one staged face each over the rows of its
+//   A. coverage  -- face-parallel: two threads rasterise one staged face each over the rows of its
 //      tile-local pixel box, stepping the three fixed-point edge functions incrementally, and OR the face's bit
 //      into the covered pixels' mask words in LDS (ds_or_b32 runs at full rate).  All the per-face work of the
 //      reference's in_tri (float->fixed conversion, winding swap, edge deltas, top-left bias) was done once when
@@ -32,12 +32,6 @@
 #include "dmr_sort.hpp"
 
 namespace dmr {
-
-constexpr int FWD_CHUNK = 128;
-#ifndef DMR_BWD_CHUNK
-#define DMR_BWD_CHUNK 128
-#endif
-constexpr int BWD_CHUNK = DMR_BWD_CHUNK;
 
 // Phase stamps (ablation build only, DMR_ABLATE bit 4096; scripts/phase_times.py reads them): lane 0 of every wave of the
 // first PH_BLOCKS workgroups (= the longest tile lists, tile_order) writes s_memtime at the phase boundaries of its first
@@ -192,13 +186,12 @@ __device__ __forceinline__ void stage_shade_attr(const TriParams& p, int b, cons
     sh.intense = f.intense;
 }
 
-// thread tid stages face (tid mod CHUNK) of the chunk: its coverage record if tid < CHUNK, else its shading record
-template <int CHUNK>
+// thread tid stages face (tid mod MASK_CHUNK) of the chunk: its coverage record if tid < MASK_CHUNK, else its shading record
 __device__ __forceinline__ void stage_chunk(const TriParams& p, int b, const FaceIds& ids, int n, int tid, int x0, int y0,
                                             V3 ray_o, CovRec* __restrict__ s_cov, ShadeRec* __restrict__ s_shade) {
-    static_assert(CHUNK == 128, "256 threads = 128 coverage + 128 shading records");
-    const int j = tid & (CHUNK - 1);
-    if (tid < CHUNK) {
+    static_assert(MASK_CHUNK == 128, "256 threads = 128 coverage + 128 shading records");
+    const int j = tid & (MASK_CHUNK - 1);
+    if (tid < MASK_CHUNK) {
         if (j < n) stage_cov(p, b, ids, x0, y0, s_cov[j]);
         else stage_null(s_cov[j]);
     } else if (j < n) {
@@ -207,17 +200,16 @@ __device__ __forceinline__ void stage_chunk(const TriParams& p, int b, const Fac
 }
 
 
-// Phase A, face-parallel.  256 / CHUNK threads rasterise one staged face each (interleaved rows of its pixel
+// Phase A, face-parallel.  256 / MASK_CHUNK threads rasterise one staged face each (interleaved rows of its pixel
 // box): the three fixed-point edge functions are stepped incrementally (+bx per pixel) and every covered
 // pixel centre gets the face's bit OR-ed into that pixel's mask word in LDS.  ds_or_b32 runs at full rate on
 // gfx950 (scripts/micro/lds_atomics.hip), so a 6x6-pixel triangle costs ~150 lane-instructions instead of
 // the ~1900 lane-slots of testing all 256 pixels of the tile against it (the earlier pixel-parallel
 // versions: every wave reading every record was LDS-issue bound, 157 of 232 us at C4; one wave per
 // 32-face block for all four quadrants with quadrant culling, 45-65 us).
-template <int CHUNK>
 __device__ __forceinline__ void rasterize_faces(const CovRec* __restrict__ cov, int n, int tid,
-                                                uint32_t (*__restrict__ pm)[CHUNK / 32]) {
-    constexpr int TPF = 256 / CHUNK;  // threads per face
+                                                uint32_t (*__restrict__ pm)[MASK_CHUNK / 32]) {
+    constexpr int TPF = 256 / MASK_CHUNK;  // threads per face
     const int j = tid / TPF, sub = tid % TPF;
     if (j >= n) return;
     const CovRec& c = cov[j];
@@ -241,12 +233,7 @@ __device__ __forceinline__ void rasterize_faces(const CovRec* __restrict__ cov, 
 // (launch_bounds(256, 6): six waves per SIMD is what the kernel's 77 registers and 24.6 KB of LDS give; (256, 4) compiles to the
 // same speed -- 76.5-77.3 against 76.9-77.7 us at C4 on one box, profiles/r03/variants_launch_bounds_c4.txt --, (256, 7) = 72
 // registers: 86.9)
-#ifndef DMR_FWD_WAVES
-#define DMR_FWD_WAVES 6
-#endif
-#ifndef DMR_PIX_WAVES
-#define DMR_PIX_WAVES 6
-#endif
+constexpr int FWD_WAVES = 6;
 // The workgroup first SORTS its tile's list (dmr_sort.hpp; the LDS of the sort is the LDS of the compositing loop): as a
 // kernel of its own the sort took 22-24 us at C4, nearly all of it the serial chain of the longest tile on an otherwise
 // idle chip (an eighth of the tiles took 19 us, profiles/r02/shard_kernel_sums_c4.json); here that chain runs beside the
@@ -254,12 +241,12 @@ __device__ __forceinline__ void rasterize_faces(const CovRec* __restrict__ cov, 
 // are visible to it behind a barrier) and for the backward.
 // (SORT == false: the lists were sorted by k_sort_tiles.  Frames of many tiles keep the chip busy in either kernel and the
 // separate sort is the cheaper one there -- C5, 262 144 tiles: 0.39 + 2.01 ms against 2.48 ms fused; dmr_api.hip decides.)
-template <int CHUNK, bool SORT>
-__global__ void __launch_bounds__(256, DMR_FWD_WAVES)
+template <bool SORT>
+__global__ void __launch_bounds__(256, FWD_WAVES)
 k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ out_depth) {
-    constexpr int WORDS = CHUNK / 32;
+    constexpr int WORDS = MASK_CHUNK / 32;
     static_assert(WORDS == 4, "one 32-face block per wave");
-    constexpr int COV_BYTES = CHUNK * (int)sizeof(CovRec), SHADE_BYTES = CHUNK * (int)sizeof(ShadeRec);
+    constexpr int COV_BYTES = MASK_CHUNK * (int)sizeof(CovRec), SHADE_BYTES = MASK_CHUNK * (int)sizeof(ShadeRec);
     constexpr int FWD_BYTES = COV_BYTES + SHADE_BYTES + TILE_PIX * WORDS * (int)sizeof(uint32_t);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[FWD_BYTES > SORT_LDS_BYTES ? FWD_BYTES : SORT_LDS_BYTES];
     CovRec* const s_cov = reinterpret_cast<CovRec*>(s_mem);
@@ -313,30 +300,29 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     uint32_t last_contributor = 0, n_hits = 0, n_skipped = 0;
     bool done = !inside;
 
-    // staging pipeline (threads < CHUNK): ids of the current chunk, face id of the next one
-    const int sj = tid & (CHUNK - 1);  // the chunk face this thread stages (see stage_chunk)
+    // staging pipeline (threads < MASK_CHUNK): ids of the current chunk, face id of the next one
+    const int sj = tid & (MASK_CHUNK - 1);  // the chunk face this thread stages (see stage_chunk)
     FaceIds ids = load_face_ids(p, b, begin + sj < end ? (int)p.face_list[begin + sj] : -1);
-    int face_next = begin + CHUNK + sj < end ? (int)p.face_list[begin + CHUNK + sj] : -1;
+    int face_next = begin + MASK_CHUNK + sj < end ? (int)p.face_list[begin + MASK_CHUNK + sj] : -1;
 
     DMR_STAMP_RT(p, 0, 0);
-    static_assert(CHUNK == MASK_CHUNK, "one mask slot per chunk");
     const ChunkMasks masks = chunk_masks(p, blockIdx.x, begin);
     AllDone all_done;
     all_done.init(s_live);
-    for (uint32_t base = begin; base < end; base += CHUNK) {
-        const uint32_t ph = (base - begin) / CHUNK;  // (phase stamps, ablation build)
+    for (uint32_t base = begin; base < end; base += MASK_CHUNK) {
+        const uint32_t ph = (base - begin) / MASK_CHUNK;  // (phase stamps, ablation build)
         DMR_STAMP(p, 0, ph, 0);
         if (all_done.barrier(done)) break;  // also fences LDS reuse
         DMR_STAMP(p, 0, ph, 1);
-        const int n = (int)min((uint32_t)CHUNK, end - base);
-        if (!DMR_DBG(p, 64)) stage_chunk<CHUNK>(p, b, ids, n, tid, tx * TILE, ty * TILE, view_o, s_cov, s_shade);
+        const int n = (int)min((uint32_t)MASK_CHUNK, end - base);
+        if (!DMR_DBG(p, 64)) stage_chunk(p, b, ids, n, tid, tx * TILE, ty * TILE, view_o, s_cov, s_shade);
         ids = load_face_ids(p, b, face_next);  // in flight while this chunk is composited
-        face_next = base + 2 * CHUNK + sj < end ? (int)p.face_list[base + 2 * CHUNK + sj] : -1;
+        face_next = base + 2 * MASK_CHUNK + sj < end ? (int)p.face_list[base + 2 * MASK_CHUNK + sj] : -1;
         *reinterpret_cast<uint4*>(&s_pm[tid][0]) = make_uint4(0u, 0u, 0u, 0u);
         DMR_STAMP(p, 0, ph, 2);
         __syncthreads();
         DMR_STAMP(p, 0, ph, 3);
-        if (!DMR_DBG(p, 16)) rasterize_faces<CHUNK>(s_cov, n, tid, s_pm);  // A
+        if (!DMR_DBG(p, 16)) rasterize_faces(s_cov, n, tid, s_pm);  // A
         DMR_STAMP(p, 0, ph, 4);
         __syncthreads();
         DMR_STAMP(p, 0, ph, 5);
@@ -516,20 +502,19 @@ constexpr uint32_t HIT_SKIPPED = 0x80000000u;
 // here (HitRegions, dmr_kernels.hpp) -- tested at run time in that instantiation: with the test folded away the register
 // allocator spills 16 bytes at the kernel's 80-register cap (k_tri_backward_pix 89 -> 91-93 us at C4), as it is it does not;
 // the scanned instantiation without the other path's code is 3 % faster at C5 (2.66 -> 2.58 ms).
+constexpr int PIX_WAVES = 6;
 template <bool SCANNED>
-__global__ void __launch_bounds__(256, DMR_PIX_WAVES)
+__global__ void __launch_bounds__(256, PIX_WAVES)
 k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                    float4* __restrict__ pixrec, HitRecord* __restrict__ hits, uint32_t capacity,
                    float* __restrict__ work, uint32_t work_floats, HitRegions regions) {
-    constexpr int CHUNK = BWD_CHUNK;
-    constexpr int WORDS = CHUNK / 32;
-    static_assert(CHUNK == 128, "one wave scans the face counters, two per lane; 256 threads stage 128 + 128 records");
-    static_assert(CHUNK == MASK_CHUNK, "the forward's chunks: one mask slot each");
-    __shared__ ShadeRec s_shade[CHUNK];
-    __shared__ uint32_t s_fcnt[CHUNK];              // blended pixels per face of the chunk (zero between chunks)
-    __shared__ uint32_t s_fcur[CHUNK];              // exclusive scan of the padded s_fcnt, then the claim cursor per face
-    __shared__ uint32_t s_fpad[CHUNK];              // first pad slot of the face's run | number of pad slots << 28
-    __shared__ int s_ids[CHUNK][HIT_GROUP];         // face id and its three vertex ids: word q rides in record q of every group
+    constexpr int WORDS = MASK_CHUNK / 32;
+    static_assert(MASK_CHUNK == 128, "one wave scans the face counters, two per lane; 256 threads stage 128 + 128 records");
+    __shared__ ShadeRec s_shade[MASK_CHUNK];
+    __shared__ uint32_t s_fcnt[MASK_CHUNK];         // blended pixels per face of the chunk (zero between chunks)
+    __shared__ uint32_t s_fcur[MASK_CHUNK];         // exclusive scan of the padded s_fcnt, then the claim cursor per face
+    __shared__ uint32_t s_fpad[MASK_CHUNK];         // first pad slot of the face's run | number of pad slots << 28
+    __shared__ int s_ids[MASK_CHUNK][HIT_GROUP];    // face id and its three vertex ids: word q rides in record q of every group
     __shared__ uint32_t s_max_last, s_chunk_hits;
     __shared__ unsigned long long s_before[4];
 
@@ -633,7 +618,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     const float bd_dot = 0.f + (float)(1.0 * (double)dpd);
 
     if (tid == 0) s_max_last = 0;
-    if (tid < CHUNK) s_fcnt[tid] = 0u;
+    if (tid < MASK_CHUNK) s_fcnt[tid] = 0u;
     __syncthreads();
     if (last_contributor) atomicMax(&s_max_last, last_contributor);
     if (self) {
@@ -667,13 +652,14 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     float last_alpha = 0, lc0 = 0, lc1 = 0, lc2 = 0, last_depth = 0;
     const uint32_t pixel = (uint32_t)pl;  // records carry the tile-local pixel
 
-    const uint32_t nchunks = (total + CHUNK - 1) / CHUNK;
-    // Chunks are the forward's (list positions [c * CHUNK, (c + 1) * CHUNK), cut at `total`), walked from the back;
-    // thread t stages position lo + (t mod CHUNK): threads < CHUNK the geometry half of its record, the others the attributes.
-    const int sj = tid & (CHUNK - 1);
+    const uint32_t nchunks = (total + MASK_CHUNK - 1) / MASK_CHUNK;
+    // Chunks are the forward's (list positions [c * MASK_CHUNK, (c + 1) * MASK_CHUNK), cut at `total`), walked from the back;
+    // thread t stages position lo + (t mod MASK_CHUNK): threads < MASK_CHUNK the geometry half of its record, the others the
+    // attributes.
+    const int sj = tid & (MASK_CHUNK - 1);
     auto chunk_face = [&](uint32_t ci) -> int {
         if (ci >= nchunks) return -1;
-        const uint32_t lo = (nchunks - 1u - ci) * CHUNK, hi = min(total, lo + (uint32_t)CHUNK);
+        const uint32_t lo = (nchunks - 1u - ci) * MASK_CHUNK, hi = min(total, lo + (uint32_t)MASK_CHUNK);
         return lo + (uint32_t)sj < hi ? (int)p.face_list[begin + lo + sj] : -1;
     };
     const ChunkMasks masks = chunk_masks(p, blockIdx.x, begin);
@@ -682,7 +668,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     DMR_STAMP_RT(p, 1, 0);
     for (uint32_t ci = 0; ci < nchunks; ci++) {
         const uint32_t fc = nchunks - 1u - ci;  // the forward's chunk index
-        const uint32_t lo = fc * CHUNK, hi = min(total, lo + (uint32_t)CHUNK);  // chunk = list positions [lo, hi)
+        const uint32_t lo = fc * MASK_CHUNK, hi = min(total, lo + (uint32_t)MASK_CHUNK);  // chunk = list positions [lo, hi)
         const int n = (int)(hi - lo);
         DMR_STAMP(p, 1, ci, 0);
         // ---- A: this pixel's coverage bits of the chunk, as the forward's rasterisation left them (requested before the
@@ -690,7 +676,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
         uint4 mm = masks.at(fc)[pl];
         __syncthreads();  // previous chunk is done with the LDS records and cursors
         DMR_STAMP(p, 1, ci, 1);
-        if (tid < CHUNK) {
+        if (tid < MASK_CHUNK) {
             if (sj < n) stage_shade_geom(p, ids, view_o, s_shade[sj]);
             *reinterpret_cast<int4*>(&s_ids[tid][0]) = make_int4(ids.face, ids.v0, ids.v1, ids.v2);
         } else if (sj < n) {
@@ -700,7 +686,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
         face_next = chunk_face(ci + 2);
         uint32_t m[WORDS] = {mm.x, mm.y, mm.z, mm.w};
         {
-            const int lim = last_contributor > lo ? (int)min(last_contributor - lo, (uint32_t)CHUNK) : 0;
+            const int lim = last_contributor > lo ? (int)min(last_contributor - lo, (uint32_t)MASK_CHUNK) : 0;
 #pragma unroll
             for (int w = 0; w < WORDS; w++) {
                 const int keep = lim - 32 * w;  // bits of word w below the bound
@@ -726,7 +712,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
             // A face's records form ONE run padded to a multiple of HIT_GROUP (the hit-parallel kernel takes HIT_GROUP
             // records of one list entry per lane, so its segmented scan runs once per group instead of once per record);
             // the pad slots are filled here with records that contribute nothing.
-            constexpr int PER = CHUNK / 64;
+            constexpr int PER = MASK_CHUNK / 64;
             uint32_t c[PER], cp[PER]; uint32_t sum = 0;
 #pragma unroll
             for (int i = 0; i < PER; i++) {
@@ -843,9 +829,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
 // and the reference's own sums are unordered float atomics.  F3 is this block's vector type (the V3 helpers of
 // dmr_device.hpp were compiled under -ffp-contract=off and keep that when inlined).  The forward and everything
 // that decides an index stay exact.
-#ifndef DMR_HITS_NOCONTRACT
 #pragma clang fp contract(fast)
-#endif
 namespace fm {
 struct F3 { float x, y, z; };
 __device__ __forceinline__ F3 operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -857,13 +841,7 @@ __device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y,
 __device__ __forceinline__ F3 load3(const float* __restrict__ a, int id) { return {a[3 * id], a[3 * id + 1], a[3 * id + 2]}; }
 }  // namespace fm
 
-#ifndef DMR_VTAB
-#define DMR_VTAB 640
-#endif
-#ifndef DMR_HITS_UNROLL
-#define DMR_HITS_UNROLL 1
-#endif
-constexpr int VTAB = DMR_VTAB;   // vertex-row slots per workgroup
+constexpr int VTAB = 640;   // vertex-row slots per workgroup
 constexpr int TAB_PROBES = 16;
 constexpr uint32_t TAB_EMPTY = 0xffffffffu;
 
@@ -883,13 +861,8 @@ constexpr uint32_t TAB_EMPTY = 0xffffffffu;
 // What the atomics cost at C4 (timing builds without them, round 2): the table's flush 23 us (0.53 M requests), the
 // face rows 11 us (0.9 M) of the kernel's 106; staging the tails through LDS so that every lane takes one row (the
 // earlier layout) cost 5 us more than letting the tail lanes add their three rows from registers.
-#ifndef DMR_HITS_PIX_LDS
-#define DMR_HITS_PIX_LDS 1
-#endif
 struct HitsLds {
-#if DMR_HITS_PIX_LDS
     float4 pix[2 * TILE_PIX];   // the tile's pixels: (ray direction, dL/ddepth), (dL/dcolor, -)
-#endif
     uint32_t vkey[VTAB];
     double vval[VTAB][7];   // dx dy dz dr dg db ddepth of row (view, vertex)
     uint32_t frow_stage[4][64][3];  // per wave: {face row id, dopacity, dintense} of the round's segment tails (see the loop)
@@ -968,11 +941,9 @@ __device__ __forceinline__ void tab_find3(uint32_t* __restrict__ key, const uint
 // ray_tri_intersection_grad (Q11: its "dv" is dt's).  TRI_GRAD_EXACT differentiates each pair's Moeller-Trumbore (u, v)
 // exactly; TRI_GRAD_CAMERA does so with respect to the ray as well and leaves the tile's part of dL/dinv_mv, dL/dinv_proj
 // (32 floats, contract layout) in cam_part[tile] (its one argument in Cam).
-#ifndef DMR_HITS_WAVES
-#define DMR_HITS_WAVES 1
-#endif
+constexpr int HITS_WAVES = 1;
 template <int GV, class... Cam>
-__global__ void __launch_bounds__(256, DMR_HITS_WAVES)
+__global__ void __launch_bounds__(256, HITS_WAVES)
 k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRecord* __restrict__ hits, uint32_t capacity,
                     float* __restrict__ vrow, float* __restrict__ frow, Cam... cam_part) {
     constexpr bool EXACT = GV != TRI_GRAD_REF, CAM = GV == TRI_GRAD_CAMERA;
@@ -1006,18 +977,14 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     // costs one memory latency, not one after the other (phase stamps: 5.1 k cycles of a tile's ~55 k were set-up)
     uint4 raw[HIT_GROUP], nxt[HIT_GROUP];
     load_group((uint32_t)tid, nxt);
-#if DMR_HITS_PIX_LDS
     const float4 px0 = pixrec[2 * (int64_t)tile * TILE_PIX + tid], px1 = pixrec[2 * (int64_t)tile * TILE_PIX + 256 + tid];
-#endif
     for (int i = tid; i < VTAB; i += 256) {
         L.vkey[i] = TAB_EMPTY;
 #pragma unroll
         for (int c = 0; c < 7; c++) L.vval[i][c] = 0.0;
     }
-#if DMR_HITS_PIX_LDS
     L.pix[tid] = px0;
     L.pix[tid + 256] = px1;
-#endif
     fm::F3 camT = {0.f, 0.f, 0.f};  // camera variant: this lane's part of dL/d(ray origin) = sum of dL/dT
     if constexpr (CAM) {
 #pragma unroll
@@ -1069,12 +1036,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
 #pragma unroll
             for (int q = 0; q < HIT_GROUP; q++) {
                 if (raw[q].y & HIT_SKIPPED) continue;  // pad, or a pair the forward skipped (denom == 0)
-#if DMR_HITS_PIX_LDS
                 const float4 pr0 = L.pix[2 * (raw[q].y & 255u)], pr1 = L.pix[2 * (raw[q].y & 255u) + 1];
-#else
-                const float4* tp = pixrec + 2 * ((int64_t)tile * TILE_PIX + (raw[q].y & 255u));
-                const float4 pr0 = tp[0], pr1 = tp[1];
-#endif
                 const float hT = __uint_as_float(raw[q].z), hdLda = __uint_as_float(raw[q].w);
                 // forward quantities of this (pixel, face) pair (backward.cu:206-243).  Exact arithmetic (the V3 helpers
                 // are not contracted): the clamp region `code` selects a piecewise-constant Jacobian, so (u, v) must land
@@ -1425,8 +1387,8 @@ void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, cons
     p.list_capacity = capacity;
     StageScope t(DMR_STAGE_TRI_FORWARD, st);
     const dim3 grid((unsigned)(s.B * gx * gy)), block(256);
-    if (keys) k_tri_forward<FWD_CHUNK, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
-    else k_tri_forward<FWD_CHUNK, false><<<grid, block, 0, st>>>(p, out_color, out_depth);
+    if (keys) k_tri_forward<true><<<grid, block, 0, st>>>(p, out_color, out_depth);
+    else k_tri_forward<false><<<grid, block, 0, st>>>(p, out_color, out_depth);
 }
 
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
