@@ -108,10 +108,24 @@ def _tri_grad_options(ctx) -> Tuple[bool, dict]:
     return False, ({"exact_grads": True} if ctx.exact_grads else {})
 
 
-def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj) -> Tuple[Optional[th.Tensor], Optional[th.Tensor]]:
-    """dL/d(inverse) -> dL/d(matrix) for the matrices (inputs 4 and 5) that need a gradient."""
-    return (_through_inverse(inv_mv, g_inv_mv) if ctx.needs_input_grad[4] else None,
-            _through_inverse(inv_proj, g_inv_proj) if ctx.needs_input_grad[5] else None)
+def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj, g_mv=None,
+                  g_proj=None) -> Tuple[Optional[th.Tensor], Optional[th.Tensor]]:
+    """dL/d(inverse) -> dL/d(matrix) for the matrices (inputs 4 and 5) that need a gradient, plus the direct terms g_mv,
+    g_proj of a renderer that also reads the matrices themselves (the tet renderer's depth)."""
+    def one(i, inv, g_inv, direct):
+        if not ctx.needs_input_grad[i]:
+            return None
+        g = _through_inverse(inv, g_inv)
+        return g if direct is None else direct + g
+    return one(4, inv_mv, g_inv_mv, g_mv), one(5, inv_proj, g_inv_proj, g_proj)
+
+
+def _tet_grad_options(ctx) -> Tuple[bool, dict]:
+    """(camera, keywords of render_tets_backward), decided as _tri_grad_options does: the camera variant only when asked
+    for and a matrix needs a gradient, else the full one, else no keyword (the reference's call)."""
+    if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
+        return True, {"camera_grads": True}
+    return False, ({"full_grads": True} if ctx.full_grads else {})
 
 
 def _tri_flat(P: int, F: int, B: int, camera: bool, device, alloc=th.empty) -> Tuple[th.Tensor, List[th.Tensor]]:
@@ -162,11 +176,11 @@ class _TriFn(th.autograd.Function):
 
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
-    faces_intense (beyond the reference).  shard: as for _TriFn."""
+    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard: as for _TriFn."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False):
+                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False):
         impl = _C if shard is None else shard.impl
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
@@ -181,7 +195,8 @@ class _TetFn(th.autograd.Function):
         if shard is not None:
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
-        ctx.settings, ctx.rows, ctx.shard, ctx.full_grads = settings, rows, shard, full_grads
+        ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
+        ctx.full_grads, ctx.camera_grads = full_grads or camera_grads, camera_grads
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
         ctx.mark_non_differentiable(active)
         return color, depth, active
@@ -189,14 +204,15 @@ class _TetFn(th.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_depth, _grad_active):
         saved = ctx.saved_tensors
-        kw = {"full_grads": True} if ctx.full_grads else {}  # (the keyword only when set: the default call is the reference's)
+        camera, kw = _tet_grad_options(ctx)
         shard, flat = ctx.shard, None
         impl = _C if shard is None else shard.impl
         if shard is not None and shard.flat_out:
-            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F]
+            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F],
+            # with camera_grads then by [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16]
             P, F, B = saved[0].size(0), saved[1].size(0), saved[4].size(0)
-            flat = kw["flat_out"] = th.empty(3 * P + F + (3 * P + B * F if ctx.full_grads else 0), dtype=th.float32,
-                                             device=saved[0].device)
+            flat = kw["flat_out"] = th.empty(3 * P + F + (3 * P + B * F if ctx.full_grads else 0) + (64 * B if camera else 0),
+                                             dtype=th.float32, device=saved[0].device)
         try:
             g = impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth, *saved[13:17],
                                           rows=ctx.rows, **kw)
@@ -205,8 +221,9 @@ class _TetFn(th.autograd.Function):
             raise
         if shard is not None:
             g = shard.reduce(g, flat)
-        g_verts, g_vcolor, g_fopacity, g_fintense = g if ctx.full_grads else (None, *g, None)
-        return (g_verts, None, g_vcolor, g_fopacity, None, None, None, g_fintense) + (None,) * 7
+        g_verts, g_vcolor, g_fopacity, g_fintense = g[:4] if ctx.full_grads else (None, *g, None)
+        g_mv, g_proj = _camera_grads(ctx, saved[6], saved[7], *g[4:8]) if camera else (None, None)
+        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, None, g_fintense) + (None,) * 8
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
@@ -218,11 +235,12 @@ def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False):
-    """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads: see
-    TetRenderer."""
+               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False, camera_grads=False):
+    """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads,
+    camera_grads: see TetRenderer."""
     return _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                        tets, face_tets, tet_faces, render_settings, tuple(rows), *_trailing(None, bool(full_grads)))
+                        tets, face_tets, tet_faces, render_settings, tuple(rows),
+                        *_trailing(None, bool(full_grads), bool(camera_grads)))
 
 
 class TriRenderer(th.nn.Module):
@@ -274,18 +292,24 @@ class TetRenderer(th.nn.Module):
     full_grads=True (beyond the reference, which has no such gradients): gradients also reach verts and
     faces_intense.  On the forward's march each composited face enters through the ray's hit (t, u, v) on it: u, v
     set its interpolated colour, t the hit point and so its ndc depth; the march itself (which faces, in which order)
-    and the opacities are constants of the gradient.  verts_depth (not read by this renderer) and the matrices get
-    none.  Costs a slower backward; the forward is the same.
+    and the opacities are constants of the gradient.  verts_depth (not read by this renderer) gets none.
+
+    camera_grads=True (implies full_grads): mv_mats and proj_mats receive gradients too.  Every pixel's ray (origin
+    and direction from the inverse matrices) moves each composited face's hit, and the depth output reads the
+    matrices directly through each hit point's ndc depth.  The seeded jitter of the ray is a constant of the gradient.
+
+    Both options cost a slower backward; the forward is the same.
 
     forward(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
             tets [T,4], face_tets [F,2] (-1 = none), tet_faces [T,4])
         -> color [B,3,H,W], depth [B,1,H,W], active bool [B,H,W]
     """
 
-    def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False):
+    def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False):
         super().__init__()
         self.render_settings = render_settings
         self.full_grads = bool(full_grads)
+        self.camera_grads = bool(camera_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
@@ -295,6 +319,6 @@ class TetRenderer(th.nn.Module):
                             mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
                             verts_depth.to(**f32), faces_intense.to(**f32),
                             tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
-                            rows, *_trailing(shard, self.full_grads))
+                            rows, *_trailing(shard, self.full_grads, self.camera_grads))
 
     _shard = TriRenderer._shard  # (rows, shard) of one device

@@ -570,7 +570,7 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st,
                                       grads, camera ? cam_part : nullptr);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
-        if (camera) dmr::launch_tri_camera_reduce(s->B, d.gx * d.gy, cam_part, cam_out, st);
+        if (camera) dmr::launch_camera_reduce(s->B, d.gx * d.gy, 32, cam_part, cam_out, st);
         return 0;
     };
     const dmr::HitRegions scanned{nullptr, nullptr, nullptr, nullptr, 0u};
@@ -616,8 +616,17 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     Dims d;
     if (check_scene(s, true, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // DMR_FLAG_TET_CAMERA_GRADS (implies the full gradients): the caller's [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 |
+    // dL/dproj 16] buffer, requested once, summed from per-tile partials in the work space
+    const bool camera = (s->flags & DMR_FLAG_TET_CAMERA_GRADS) != 0;
+    float* cam_out = nullptr;
+    if (camera && s->B > 0) {
+        if (!alloc) return fail("null argument");
+        cam_out = static_cast<float*>(alloc(ctx, DMR_BUF_TET_CAMERA_GRADS, 256 * (size_t)s->B));
+        if (!cam_out) return fail("allocation of the tet camera gradient buffer failed");
+    }
     float* full = nullptr;  // DMR_FLAG_TET_FULL_GRADS: [dL_dverts 3P | dL_dfintense BF], requested from the caller
-    if ((s->flags & DMR_FLAG_TET_FULL_GRADS) && 3 * (int64_t)s->P + (int64_t)d.BF > 0) {
+    if ((s->flags & (DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS)) && 3 * (int64_t)s->P + (int64_t)d.BF > 0) {
         if (!alloc) return fail("null argument");
         const int64_t n = 3 * (int64_t)s->P + (int64_t)d.BF;
         full = static_cast<float*>(alloc(ctx, DMR_BUF_TET_GRADS, (size_t)n * sizeof(float)));
@@ -625,15 +634,28 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         dmr::launch_tet_zero_grads(full, 3 * (int64_t)s->P, full + 3 * (int64_t)s->P, (int64_t)d.BF, st);
     }
     dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
+    // the camera gradients of a call with nothing to back-propagate (no geometry, or an empty tile-row band: a rank without
+    // rows) are zeros
+    const int band_tiles = d.gx * (d.r1 - d.r0);  // per view
+    if (cam_out && (s->P == 0 || s->F == 0 || band_tiles == 0)) {
+        DMR_HIP(hipMemsetAsync(cam_out, 0, 256 * (size_t)s->B, st));
+        cam_out = nullptr;
+    }
     if (s->P == 0 || s->F == 0) return 0;
     if (!image_buf || !face_buf) return fail("null scratch buffer");
+    float* cam_part = nullptr;  // every tile's partial (launch_tet_backward)
+    if (cam_out) {
+        cam_part = static_cast<float*>(alloc(ctx, DMR_BUF_WORK, 256 * (size_t)band_tiles * (size_t)s->B));
+        if (!cam_part) return fail("workspace allocation failed");
+    }
     // binning_buf: the forward's march sequence lives there (where and how much of it: is.seq, on the device); a null
     // buffer is fine when the forward ran without one (its descriptor then says cap = 0 and the backward re-marches)
     const Scratch c = carve_scratch(s, true, d, point_buf, face_buf, image_buf, binning_buf);
     const dmr_scene sc = canonical(s, c.is.mats);
     uint32_t* host_seq_steps = march_estimate(size_key(s, true, d), d, false);
     dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
-                             full, full ? full + 3 * (int64_t)s->P : nullptr);
+                             full, full ? full + 3 * (int64_t)s->P : nullptr, cam_part);
+    if (cam_out) dmr::launch_camera_reduce(s->B, band_tiles, 64, cam_part, cam_out, st);
     DMR_HIP(hipGetLastError());
     return 0;
 }

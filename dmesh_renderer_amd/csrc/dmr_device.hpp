@@ -157,6 +157,20 @@ __device__ __forceinline__ void pixel_ray(const float* __restrict__ inv_mv, cons
     d = d / len;
 }
 
+// The ndc (x, y) pixel_ray<TET> sends a pixel's ray through (the same arithmetic; the camera gradients of the tet renderer
+// recompute the ray's parts with it).  A separate copy: pixel_ray calling it moves operands in the kernels that inline it.
+template <bool TET>
+__device__ __forceinline__ V2 pixel_ndc(int px, int py, int W, int H, int seed, uint64_t idx) {
+    V2 pixf = {px + 0.5f, py + 0.5f};
+    if (TET && seed > 0) {
+        uint32_t r0, r1;
+        philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)seed, r0, r1);
+        pixf.x = (float)px - 0.5f + (0.5f * uniform_01(r0));
+        pixf.y = (float)py - 0.5f + (0.5f * uniform_01(r1));
+    }
+    return {pix2ndc(pixf.x, W), pix2ndc(pixf.y, H)};
+}
+
 // auxiliary.h:335-372
 __device__ __forceinline__ void clamp_bary_uv(float u, float v, float& u_c, float& v_c, int& code) {
     if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f) { u_c = u; v_c = v; code = 0; }

@@ -137,8 +137,9 @@ enum { TRI_GRAD_REF = 0, TRI_GRAD_EXACT = 1, TRI_GRAD_CAMERA = 2 };
 void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* vproj, const uint32_t* face_list, TriImageState img,
                               const float4* pixrec, const HitRecord* hits, uint32_t capacity, float* vrow, float* frow,
                               hipStream_t st, int grads = TRI_GRAD_REF, float* cam_part = nullptr);
-// sums the B * tiles partials of the camera variant per view: out [B][32]
-void launch_tri_camera_reduce(int B, int tiles, const float* cam_part, float* out, hipStream_t st);
+// sums the B * tiles partials of a camera variant per view, in a fixed order: out [B][width]; width 32 (the tri
+// renderer's, see launch_tri_backward_hits) or 64 (the tet renderer's, see launch_tet_backward)
+void launch_camera_reduce(int B, int tiles, int width, const float* cam_part, float* out, hipStream_t st);
 void launch_tri_unpack(const dmr_scene& s, const float* vrow, const float* frow, float* dL_dverts,
                        float* dL_dvcolor, float* dL_dfopacity, float* dL_dvdepth, float* dL_dfintense,
                        hipStream_t st);
@@ -187,8 +188,12 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
 // Two launches, of which the device runs one: k_tet_backward_seq when the forward's march sequence is complete
 // (seq->max_steps <= seq->cap_steps != 0), else the re-marching k_tet_backward; the other one returns at once.  No host read.
 // host_seq_steps (pinned, may be null): receives seq->max_steps, the next forward's capacity estimate.
+// dL_dverts, dL_dfintense: the full gradients (null: the default kernels).  cam_part (needs them): the camera variant,
+// which also stores every tile's 64-float partial [dL/dinv_mv | dL/dinv_proj | dL/dmv | dL/dproj] (contract layout) at
+// cam_part + 64 * ((view * (r1 - r0) + row - r0) * gx + column) -- launch_camera_reduce's input with tiles = gx (r1 - r0).
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts = nullptr, float* dL_dfintense = nullptr);
+                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts = nullptr, float* dL_dfintense = nullptr,
+                         float* cam_part = nullptr);
 
 }  // namespace dmr

@@ -537,7 +537,41 @@ __device__ __forceinline__ float ndc_depth_dt(F3 pt, F3 d, const float* __restri
     const float cwc = clamp_w(cw), inv = rcp(cwc);
     return cwc == cw ? (dcz - cz * inv * dcw) * inv : dcz * inv;
 }
+// (clip z, clip w) of a world point, with ndc_depth's arithmetic (the compiler computes them once for both)
+__device__ __forceinline__ void clip_zw(F3 pt, const float* __restrict__ mv, const float* __restrict__ pr, float& cz, float& cw) {
+    const float vx = mv[0] * pt.x + mv[4] * pt.y + mv[8] * pt.z + mv[12];
+    const float vy = mv[1] * pt.x + mv[5] * pt.y + mv[9] * pt.z + mv[13];
+    const float vz = mv[2] * pt.x + mv[6] * pt.y + mv[10] * pt.z + mv[14];
+    cz = pr[2] * vx + pr[6] * vy + pr[10] * vz + pr[14];
+    cw = pr[3] * vx + pr[7] * vy + pr[11] * vz + pr[15];
+}
 }  // namespace tfast
+
+// Camera gradients (DMR_FLAG_TET_CAMERA_GRADS, beyond the reference): what one pixel's reverse walk sums in registers.  Per
+// marched face, with lambda of TetBwdPixel::full_grads, G = w dL/d(depth) and (kz, kw) = G d(ndc depth)/d(clip z, clip w) at
+// the hit point pt = o + t d (kw = 0 where clamp_w clamps):
+//   - the hit: moving o by delta is moving the three vertices by -delta, so the hit's part is dL/do = -lambda, dL/dd = -t lambda;
+//   - the depth's explicit dependence on pt (t held): G grad(ndc depth)(pt) = mv3^T (kz proj row z + kw proj row w);
+//   - mu = -lambda + that; go = sum mu, gd = sum t mu;
+//   - the direct dependence of the depth on mv and proj: sum kz (pt, 1) = sz (o, 1) + szt (d, 0) (o and d are the pixel's), so
+//     four sums carry it: sz = sum kz, szt = sum kz t, sw = sum kw, swt = sum kw t.
+struct TetCamPix {
+    float go[3], gd[3], sz, szt, sw, swt;
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int c = 0; c < 3; c++) go[c] = gd[c] = 0.f;
+        sz = szt = sw = swt = 0.f;
+    }
+    template <class Vec>
+    __device__ __forceinline__ void add(Vec lam, float t, float kz, float kw, const float* __restrict__ mv, const float* __restrict__ pr) {
+        const float ax = kz * pr[2] + kw * pr[3], ay = kz * pr[6] + kw * pr[7], az = kz * pr[10] + kw * pr[11];  // dL/d(view point)
+        const float mu[3] = {mv[0] * ax + mv[1] * ay + mv[2] * az - lam.x, mv[4] * ax + mv[5] * ay + mv[6] * az - lam.y,
+                             mv[8] * ax + mv[9] * ay + mv[10] * az - lam.z};
+#pragma unroll
+        for (int c = 0; c < 3; c++) { go[c] += mu[c]; gd[c] += t * mu[c]; }
+        sz += kz; szt += kz * t; sw += kw; swt += kw * t;
+    }
+};
 #pragma clang fp contract(off)
 
 // One pixel's state of the reverse walk and the gradient of one marched face (cuda_renderer/backward.cu:236-360),
@@ -549,38 +583,41 @@ struct TetBwdPixel {
     bool first_iter;
     // -> g[0..8] = dL/d(vertex colours of the face), g[9] = dL/d(opacity); v0..v2: the face's vertices.
     // FULL: also g[10..18] = dL/d(vertex positions p0, p1, p2) and g[19] = dL/d(faces_intense[b, face]) (see full_grads).
-    template <bool FULL = false>
+    // CAM (needs FULL): also adds the face's camera terms to *cam (TetCamPix).
+    template <bool FULL = false, bool CAM = false>
     __device__ __forceinline__ void face_grad(const TetParams& p, int b, int face, V3 ro, V3 rd, const float* __restrict__ mv,
                                               const float* __restrict__ pr, float rt, float iu, float iv, float (&g)[tet_nv(FULL)],
-                                              int& v0, int& v1, int& v2) {
+                                              int& v0, int& v1, int& v2, TetCamPix* cam = nullptr) {
         const float4* cq = reinterpret_cast<const float4*>(p.colrec + face);
         float4 f0 = {}, f1 = {}, f2 = {};
         if constexpr (FULL) {  // the face's vertices
             const float4* fq = reinterpret_cast<const float4*>(p.facerec + face);
             f0 = fq[0]; f1 = fq[1]; f2 = fq[2];
         }
-        face_grad<FULL>(ro, rd, mv, pr, rt, iu, iv, cq[0], cq[1], cq[2], cq[3], p.faces_intense[(int64_t)b * p.F + face], g, v0, v1, v2,
-                        f0, f1, f2);
+        face_grad<FULL, CAM>(ro, rd, mv, pr, rt, iu, iv, cq[0], cq[1], cq[2], cq[3], p.faces_intense[(int64_t)b * p.F + face], g, v0, v1,
+                             v2, f0, f1, f2, cam);
     }
     // The chain rule from the face's hit (t, u, v) to its vertices and intensity, given this step's weight w = prev_T * opacity.
     // o + t d = (1-u-v) p0 + u p1 + v p2, differentiated implicitly: with E1 = p1 - p0, E2 = p2 - p0, P = d x E2,
     // den = P . E1, dL/dp_k = b_k lambda, lambda = -(g_t (E1 x E2) + g_u P + g_v (E1 x d)) / den, b = (1-u-v, u, v).
     // g_u, g_v: dL/du, dL/dv through the interpolated colour; g_t: dL/dt through the hit point's ndc depth.  The ray depends
     // on the camera only, and opacities / transmittance do not depend on the positions.
+    // Returns lambda (the camera variant needs it: see TetCamPix).
     template <class Vec>
-    __device__ __forceinline__ static void full_grads(Vec d, Vec E1, Vec E2, Vec P, float inv_den, float g_t, float g_u, float g_v,
-                                                      float i0, float i1, float i2, float g_int, float* __restrict__ g) {
+    __device__ __forceinline__ static Vec full_grads(Vec d, Vec E1, Vec E2, Vec P, float inv_den, float g_t, float g_u, float g_v,
+                                                     float i0, float i1, float i2, float g_int, float* __restrict__ g) {
         const Vec lam = (-inv_den) * ((g_t * cross(E1, E2)) + (g_u * P) + (g_v * cross(E1, d)));
         g[0] = i0 * lam.x; g[1] = i0 * lam.y; g[2] = i0 * lam.z;
         g[3] = i1 * lam.x; g[4] = i1 * lam.y; g[5] = i1 * lam.z;
         g[6] = i2 * lam.x; g[7] = i2 * lam.y; g[8] = i2 * lam.z;
         g[9] = g_int;
+        return lam;
     }
-    template <bool FULL = false>
+    template <bool FULL = false, bool CAM = false>
     __device__ __forceinline__ void face_grad(V3 ro, V3 rd, const float* __restrict__ mv, const float* __restrict__ pr, float rt,
                                               float iu, float iv, float4 cq0, float4 cq1, float4 cq2, float4 cq3, float intense,
                                               float (&g)[tet_nv(FULL)], int& v0, int& v1, int& v2,
-                                              float4 f0 = {}, float4 f1 = {}, float4 f2 = {}) {
+                                              float4 f0 = {}, float4 f1 = {}, float4 f2 = {}, TetCamPix* cam = nullptr) {
         const V3 c0 = {cq0.x, cq0.y, cq0.z}, c1 = {cq0.w, cq1.x, cq1.y}, c2 = {cq1.z, cq1.w, cq2.x};
         v0 = __float_as_int(cq2.y); v1 = __float_as_int(cq2.z); v2 = __float_as_int(cq2.w);
         const float i0 = 1.0f - iu - iv, i1 = iu, i2 = iv;
@@ -628,15 +665,20 @@ struct TetBwdPixel {
             const float dz_dt = (clamp_w(pn.w) == pn.w ? dcz - pdepth * dcw : dcz) * pw;
             const V3 p0 = {f0.x, f0.y, f0.z}, E1 = V3{f0.w, f1.x, f1.y} - p0, E2 = V3{f1.z, f1.w, f2.x} - p0;
             const V3 P = cross(rd, E2);
-            full_grads(rd, E1, E2, P, 1.0f / dot(P, E1), w * dpd * dz_dt, g_u, g_v, i0, i1, i2, w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z),
-                       g + 10);
+            [[maybe_unused]] const V3 lam = full_grads(rd, E1, E2, P, 1.0f / dot(P, E1), w * dpd * dz_dt, g_u, g_v, i0, i1, i2,
+                                                       w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z), g + 10);
+            if constexpr (CAM) {
+                const float kz = w * dpd * pw;
+                cam->add(lam, rt, kz, clamp_w(pn.w) == pn.w ? -kz * pdepth : 0.f, mv, pr);
+            }
         }
     }
     // the same with tfast's arithmetic, from the face's records (k_tet_backward_seq)
-    template <bool FULL = false>
+    template <bool FULL = false, bool CAM = false>
     __device__ __forceinline__ void face_grad_fast(V3 ro, V3 rd, const float* __restrict__ mv, const float* __restrict__ pr,
                                                    float4 f0, float4 f1, float4 f2, float4 cq0, float4 cq1, float4 cq2, float4 cq3,
-                                                   float intense, float (&g)[tet_nv(FULL)], int& v0, int& v1, int& v2) {
+                                                   float intense, float (&g)[tet_nv(FULL)], int& v0, int& v1, int& v2,
+                                                   TetCamPix* cam = nullptr) {
 #pragma clang fp contract(fast)
         using namespace tfast;
         const F3 o = {ro.x, ro.y, ro.z}, d = {rd.x, rd.y, rd.z};
@@ -673,8 +715,15 @@ struct TetBwdPixel {
             const F3 craw = (i0 * c0) + (i1 * c1) + (i2 * c2);
             const F3 dc = {dc0, dc1, dc2};  // dL/dcolour of the pixel * w * intensity
             const float w = opacity * prev_T;
-            full_grads(d, E1, E2, P, rcp(dot(P, E1)), w * dpd * ndc_depth_dt(o + (rt * d), d, mv, pr), dot(dc, c1 - c0),
-                       dot(dc, c2 - c0), i0, i1, i2, w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z), g + 10);
+            [[maybe_unused]] const F3 lam = full_grads(d, E1, E2, P, rcp(dot(P, E1)), w * dpd * ndc_depth_dt(o + (rt * d), d, mv, pr),
+                                                       dot(dc, c1 - c0), dot(dc, c2 - c0), i0, i1, i2,
+                                                       w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z), g + 10);
+            if constexpr (CAM) {
+                float cz, cw;
+                clip_zw(o + (rt * d), mv, pr, cz, cw);
+                const float cwc = clamp_w(cw), inv = rcp(cwc), kz = w * dpd * inv;
+                cam->add(lam, rt, kz, cwc == cw ? -kz * cz * inv : 0.f, mv, pr);
+            }
         }
     }
 };
@@ -807,6 +856,77 @@ __device__ __forceinline__ void tet_flush(const TetParams& p, const int* s_key, 
     }
 }
 
+// The camera variant's end of a tile (all 256 threads, after tet_flush: `red` is 128 floats of the table's LDS).  A pixel
+// maps its sums (TetCamPix) through its ray, pixel_ray<true>: o = inv_mv's translation column, d = w / max(|w|, 1e-4),
+// w = inv_mv (pv.xyz, 1) - o, pv = inv_proj (ndc, -1, 1), the seeded jitter a constant.  That gives 24 values of
+// dL/dinv_mv, dL/dinv_proj (their w rows get nothing; inv_mv's translation column is dL/do alone, it cancels in w), and 8
+// of the direct depth term: sz, sw, szt d, swt d.  The workgroup sums them in a fixed order and threads 0-63 store the
+// tile's partial [dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16] (contract layout) at `part`: with
+// A_z = sum kz (pt, 1) = (sz o + sum szt d, sz) and A_w likewise,
+//   dL/dmv[row < 3][col] = proj[2][row] A_z[col] + proj[3][row] A_w[col],  dL/dproj[2][col] = (mv A_z)[col], [3] from A_w.
+__device__ __forceinline__ void tet_camera_tile(const TetParams& p, int b, int px, int py, bool work, const TetCamPix& cam, int tid,
+                                                float* red, float* __restrict__ part) {
+    const float* im = p.inv_mv + 16 * b;
+    float c[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++) c[i] = 0.f;
+    if (work) {
+        const float* ip = p.inv_proj + 16 * b;
+        const V2 nd = pixel_ndc<true>(px, py, p.W, p.H, *p.seed, (uint64_t)((int64_t)b * p.H * p.W + (int64_t)p.W * py + px));
+        const float ndc[4] = {nd.x, nd.y, -1.0f, 1.0f};
+        const V4 pv = xform4x4({nd.x, nd.y, -1.0f}, ip);
+        const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
+        const V3 w = V3{pw.x, pw.y, pw.z} - V3{im[12], im[13], im[14]};
+        const float n = sqrtf(dot(w, w)), len = fmaxf(n, 0.0001f);
+        // dL/dw = gd / len - w (w . gd) / n^3 where the length is not clamped
+        const float k = n > 0.0001f ? (w.x * cam.gd[0] + w.y * cam.gd[1] + w.z * cam.gd[2]) / (n * n * n) : 0.f;
+        const float dw[3] = {cam.gd[0] / len - k * w.x, cam.gd[1] / len - k * w.y, cam.gd[2] / len - k * w.z};
+        const float pvv[3] = {pv.x, pv.y, pv.z}, d[3] = {w.x / len, w.y / len, w.z / len};
+#pragma unroll
+        for (int row = 0; row < 3; row++) {
+#pragma unroll
+            for (int col = 0; col < 3; col++) c[3 * col + row] = dw[row] * pvv[col];
+            c[9 + row] = cam.go[row];
+            const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];  // (R^T dL/dw)_row
+#pragma unroll
+            for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
+            c[26 + row] = cam.szt * d[row];
+            c[29 + row] = cam.swt * d[row];
+        }
+        c[24] = cam.sz; c[25] = cam.sw;
+    }
+#pragma unroll
+    for (int i = 0; i < 32; i++)
+#pragma unroll
+        for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
+    __syncthreads();  // (the flush has read the table)
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 32; i++) red[32 * (tid >> 6) + i] = c[i];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        auto tot = [&](int i) { return red[i] + red[32 + i] + red[64 + i] + red[96 + i]; };
+        auto A = [&](int zw, int k) {  // A_z (zw = 0), A_w (zw = 1)
+            const float sum = tot(24 + zw);
+            return k == 3 ? sum : sum * im[12 + k] + tot(26 + 3 * zw + k);
+        };
+        const float* mv = p.mv + 16 * b;
+        const float* pr = p.proj + 16 * b;
+        const int row = tid & 3, col = (tid >> 2) & 3;
+        float v = 0.f;
+        if (tid < 32) {  // dL/dinv_mv, dL/dinv_proj
+            if (row < 3) v = tot(12 * (tid >> 4) + 3 * col + row);
+        } else if (tid < 48) {  // dL/dmv
+            if (row < 3) v = pr[4 * row + 2] * A(0, col) + pr[4 * row + 3] * A(1, col);
+        } else if (row >= 2) {  // dL/dproj, rows z and w
+            const int zw = row - 2;
+            v = col == 3 ? A(zw, 3) : mv[col] * A(zw, 0) + mv[4 + col] * A(zw, 1) + mv[8 + col] * A(zw, 2) + mv[12 + col] * A(zw, 3);
+        }
+        part[tid] = v;
+    }
+}
+
 // what a pixel's reverse walk starts from; false: the pixel has no gradient (outside, inactive, nothing marched)
 __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px, int py, const float* __restrict__ dL_dcolor,
                                               const float* __restrict__ dL_ddepth, TetBwdPixel& st, V3& ro, V3& rd,
@@ -842,12 +962,14 @@ __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px,
 // two launches -- every call but the first of a view configuration -- 2 500 workgroups that only find that out cost 6.7 us
 // at C3, 768 cost under 2.)
 // Full: no type (the default), or float*, float* -- dL_dverts [P,3] and dL_dfintense [B,F] of the full gradients
-// (DMR_FLAG_TET_FULL_GRADS), which this instantiation accumulates as well (the default one's code is unchanged by them).
+// (DMR_FLAG_TET_FULL_GRADS), which this instantiation accumulates as well (the default one's code is unchanged by them),
+// or float*, float*, float* -- those and the camera variant's per-tile partials [tiles][64] (DMR_FLAG_TET_CAMERA_GRADS,
+// tet_camera_tile; tile = (view * rows + row - r0) * gx + column, every tile of the band written).
 template <class... Full>
 __global__ void __launch_bounds__(256)
 k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, Full... full) {
-    constexpr bool FULL = sizeof...(Full) != 0;
+    constexpr bool FULL = sizeof...(Full) != 0, CAM = sizeof...(Full) == 3;
     constexpr int NV = tet_nv(FULL), NS = tet_tbl(FULL);
     {
         const uint32_t cap = p.img.seq->cap_steps;
@@ -869,15 +991,20 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
         const int tx = ti % p.gx, ty = (ti / p.gx) % rows + p.r0, b = ti / (p.gx * rows);
         float* dL_dverts = nullptr;
         float* dL_dfint_b = nullptr;  // the intensity row of the tile's view
+        [[maybe_unused]] float* cam_part = nullptr;
         if constexpr (FULL) {
             float* const out[] = {full...};
             dL_dverts = out[0]; dL_dfint_b = out[1] + (int64_t)b * p.F;
+            if constexpr (CAM) cam_part = out[2] + 64 * (int64_t)ti;
         }
         const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
         TetBwdPixel st;
         V3 ro = {0, 0, 0}, rd = {0, 0, 0};
         int first_face = -1, last_face = -1;
         bool done = !tet_bwd_begin(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
+        [[maybe_unused]] const bool work = !done;
+        [[maybe_unused]] TetCamPix cam;
+        if constexpr (CAM) cam.clear();
         const float* mv = p.mv + 16 * b;
         const float* pr = p.proj + 16 * b;
         int curr_face = last_face, curr_tet = -1, curr_slot = 0;
@@ -903,7 +1030,8 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
             int v0 = 0, v1 = 0, v2 = 0;
             const int face = curr_face;
             if (act) {
-                st.face_grad<FULL>(p, b, curr_face, ro, rd, mv, pr, curr_rt, curr_iu, curr_iv, g, v0, v1, v2);
+                if constexpr (CAM) st.face_grad<true, true>(p, b, curr_face, ro, rd, mv, pr, curr_rt, curr_iu, curr_iv, g, v0, v1, v2, &cam);
+                else st.face_grad<FULL>(p, b, curr_face, ro, rd, mv, pr, curr_rt, curr_iu, curr_iv, g, v0, v1, v2);
                 if (curr_face == first_face) done = true;
                 if (!done) {
                     if (curr_tet == -1) done = true;
@@ -914,6 +1042,7 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
         }
         __syncthreads();
         tet_flush<FULL>(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
+        if constexpr (CAM) tet_camera_tile(p, b, px, py, work, cam, tid, reinterpret_cast<float*>(&s_val[0][0]), cam_part);
     }
 }
 
@@ -931,7 +1060,7 @@ template <class... Full>
 __global__ void __launch_bounds__(256, TET_BWD_WAVES)
 k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                    float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, uint32_t* __restrict__ host_seq_steps, Full... full) {
-    constexpr bool FULL = sizeof...(Full) != 0;
+    constexpr bool FULL = sizeof...(Full) != 0, CAM = sizeof...(Full) == 3;
     constexpr int NV = tet_nv(FULL), NS = tet_tbl(FULL);
     const uint32_t seq_cap = p.img.seq->cap_steps, longest = p.img.seq->max_steps;
     if (host_seq_steps && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
@@ -951,15 +1080,19 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
     const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
     float* dL_dverts = nullptr;
     float* dL_dfint_b = nullptr;  // a workgroup is one tile of one view: the view's intensity row
+    [[maybe_unused]] float* cam_part = nullptr;
     if constexpr (FULL) {
         float* const out[] = {full...};
         dL_dverts = out[0]; dL_dfint_b = out[1] + (int64_t)b * p.F;
+        if constexpr (CAM) cam_part = out[2] + 64 * (((int64_t)b * gridDim.y + blockIdx.y) * p.gx + tx);
     }
     const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
     TetBwdPixel st;
     V3 ro = {0, 0, 0}, rd = {0, 0, 0};
     int first_face = -1, last_face = -1;
     const bool work = tet_bwd_begin(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
+    [[maybe_unused]] TetCamPix cam;
+    if constexpr (CAM) cam.clear();
     const uint32_t n = work ? min(p.img.n_contrib[(int64_t)b * p.H * p.W + (int64_t)p.W * py + px], seq_cap) : 0u;
     const uint32_t smax = wave_max_u32(n);  // the wave's first step from the back
     const uint4* const seq_row = reinterpret_cast<const uint4*>(p.img.binning + p.img.seq->offset) +
@@ -1011,7 +1144,10 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
             float g[NV];
             int v0 = 0, v1 = 0, v2 = 0;
             if (act) {  // (t, u, v) of the ray on this face, then the face's gradient
-                st.face_grad_fast<FULL>(ro, rd, mv, pr, cur.f0, cur.f1, cur.f2, cur.c0, cur.c1, cur.c2, cur.c3, cur.intense, g, v0, v1, v2);
+                if constexpr (CAM)
+                    st.face_grad_fast<true, true>(ro, rd, mv, pr, cur.f0, cur.f1, cur.f2, cur.c0, cur.c1, cur.c2, cur.c3, cur.intense, g, v0, v1,
+                                                  v2, &cam);
+                else st.face_grad_fast<FULL>(ro, rd, mv, pr, cur.f0, cur.f1, cur.f2, cur.c0, cur.c1, cur.c2, cur.c3, cur.intense, g, v0, v1, v2);
                 if (face == first_face || (e_cur & 0x80000000u)) done = true;
             }
             if constexpr (FULL) tet_accumulate<true>(p, acc, s_val, lane, act, face, g, v0, v1, v2, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
@@ -1026,6 +1162,7 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
     }
     __syncthreads();
     tet_flush<FULL>(p, s_key, s_val, tid, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfint_b);
+    if constexpr (CAM) tet_camera_tile(p, b, px, py, work, cam, tid, reinterpret_cast<float*>(&s_val[0][0]), cam_part);
 }
 
 
@@ -1096,12 +1233,17 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
 
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense) {
+                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense, float* cam_part) {
     if (r1 <= r0) return;
     TetParams p = make_params(s, gx, gy, r0, img);
     StageScope t(DMR_STAGE_TET_BACKWARD, st);
     const int ntiles = gx * (r1 - r0) * s.B;
-    if (!dL_dverts) {
+    if (cam_part) {
+        k_tet_backward_seq<float*, float*, float*><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(
+            p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, dL_dverts, dL_dfintense, cam_part);
+        k_tet_backward<float*, float*, float*><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(
+            p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfintense, cam_part);
+    } else if (!dL_dverts) {
         k_tet_backward_seq<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps);
         k_tet_backward<><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity);
     } else {

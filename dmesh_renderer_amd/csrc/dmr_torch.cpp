@@ -23,6 +23,8 @@
 //   exact_grads=False        render_tris_backward: dL_dverts is the exact derivative of the image (DMR_FLAG_TRI_EXACT_GRADS)
 //   camera_grads=False       render_tris_backward: also dL_dinv_mv_mats, dL_dinv_proj_mats [B,4,4] (DMR_FLAG_TRI_CAMERA_GRADS,
 //                            implies exact_grads) -> the five gradients, then those two
+//                            render_tets_backward: also dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats
+//                            [B,4,4] (DMR_FLAG_TET_CAMERA_GRADS, implies full_grads) -> the four full gradients, then those
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -181,6 +183,7 @@ struct Scratch {
     std::array<at::Tensor, 7> buf;
     at::Tensor tet_grads;  // where DMR_BUF_TET_GRADS is served from (an output, not scratch), if defined
     at::Tensor tri_cam;    // where DMR_BUF_TRI_CAMERA_GRADS is served from (an output), if defined
+    at::Tensor tet_cam;    // where DMR_BUF_TET_CAMERA_GRADS is served from (an output), if defined
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -188,9 +191,10 @@ struct Scratch {
 };
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
-    if (which < 0 || which >= 7) return nullptr;
-    if (which == DMR_BUF_TET_GRADS || which == DMR_BUF_TRI_CAMERA_GRADS) {  // the caller's gradient tensor, which the library fills
-        const at::Tensor& t = which == DMR_BUF_TET_GRADS ? s->tet_grads : s->tri_cam;
+    if (which < 0 || which > DMR_BUF_TET_CAMERA_GRADS) return nullptr;
+    if (which == DMR_BUF_TET_GRADS || which == DMR_BUF_TRI_CAMERA_GRADS || which == DMR_BUF_TET_CAMERA_GRADS) {
+        // the caller's gradient tensor, which the library fills
+        const at::Tensor& t = which == DMR_BUF_TET_GRADS ? s->tet_grads : (which == DMR_BUF_TRI_CAMERA_GRADS ? s->tri_cam : s->tet_cam);
         return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
     }
     try {
@@ -384,8 +388,10 @@ TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, con
 }
 
 // -> (dL_dverts_color [P,3], dL_dfaces_opacity [F]), or with full_grads
-//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F]).
-// The binding: without full_grads exactly the reference's function (render.cu:338-412).
+//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F]), with camera_grads followed by
+//    (dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats) [B,4,4], each of the matrix tensor as the call
+//    received it (as render_tris_backward's).
+// The binding: without full_grads and camera_grads exactly the reference's function (render.cu:338-412).
 py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                                const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                                const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
@@ -393,7 +399,7 @@ py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& v
                                const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
                                const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool full_grads) {
+                               bool full_grads, bool camera_grads) {
     std::optional<py::gil_scoped_release> nogil(std::in_place);
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
@@ -406,19 +412,34 @@ py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& v
     // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from g[2].  With flat_out
     // the layout is [dL_dverts_color 3P | dL_dfaces_opacity F | dL_dverts 3P | dL_dfaces_intense BF]: the default layout
     // followed by that buffer, so one all-reduce still carries everything.
+    // camera_grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16] is DMR_BUF_TET_CAMERA_GRADS, served from
+    // g[3]; with flat_out it follows the full layout.
+    full_grads = full_grads || camera_grads;
     std::vector<std::vector<int64_t>> shapes = {{P, 3}, {F}};
     if (full_grads) shapes.push_back({3 * P + B * F});
+    if (camera_grads) shapes.push_back({B, 64});
     std::vector<at::Tensor> g = grad_outputs(dev, flat_out, shapes);
     if (full_grads) {
         call.scratch.tet_grads = g[2];
         call.sc.flags |= DMR_FLAG_TET_FULL_GRADS;
+    }
+    if (camera_grads) {
+        call.scratch.tet_cam = g[3];
+        call.sc.flags |= DMR_FLAG_TET_CAMERA_GRADS;
     }
     const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
     if (g_abi.tet_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), mptr<const void>(pb), mptr<const void>(fb),
                            mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g[0]), mptr<float>(g[1]), &alloc_cb,
                            &call.scratch, call.stream()))
         raise_lib();
-    if (full_grads) g = {g[2].narrow(0, 0, 3 * P).view({P, 3}), g[0], g[1], g[2].narrow(0, 3 * P, B * F).view({B, F})};
+    if (full_grads) {
+        std::vector<at::Tensor> r = {g[2].narrow(0, 0, 3 * P).view({P, 3}), g[0], g[1], g[2].narrow(0, 3 * P, B * F).view({B, F})};
+        if (camera_grads) {
+            const at::Tensor cam = g[3].view({B, 4, 4, 4});
+            for (int k = 0; k < 4; k++) r.push_back(cam.select(1, k));
+        }
+        g = std::move(r);
+    }
     nogil.reset();
     return py::tuple(py::cast(g));
 }
@@ -503,7 +524,8 @@ PYBIND11_MODULE(_C, m) {
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
           py::arg("grad_color"), py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"),
-          py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("full_grads") = false);
+          py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("full_grads") = false,
+          py::arg("camera_grads") = false);
     m.def("invert_mats", &invert_mats);
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));

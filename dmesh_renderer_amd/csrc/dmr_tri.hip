@@ -1426,30 +1426,33 @@ void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* 
         k_tri_backward_hits<TRI_GRAD_REF><<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow);
 }
 
-// the tiles' camera partials [B * tiles][32] -> out [B][32], one workgroup per view, in a fixed order.  Thread t sums
-// float4 q = t % 8 of every 128th tile from t / 8 on, four tiles' loads in flight at a time (one dependent load after the
-// other was 242 us at C4's 8 160 tiles), then a tree over the 128 rows in LDS.
+// the tiles' camera partials [B * tiles][N] -> out [B][N], one workgroup per view, in a fixed order.  With Q = N / 4 float4
+// per partial and ROWS = 1024 / Q, thread t sums float4 q = t % Q of every ROWS-th tile from t / Q on, four tiles' loads in
+// flight at a time (one dependent load after the other was 242 us at C4's 8 160 tiles), then a tree over the ROWS rows in
+// LDS.  N = 32: the tri renderer's partials (128 rows of 8), N = 64: the tet renderer's (64 rows of 16).
+template <int N>
 __global__ void __launch_bounds__(1024)
 k_tri_camera_reduce(int tiles, const float* __restrict__ cam_part, float* __restrict__ out) {
-    __shared__ float4 s[128][8];
-    const int b = blockIdx.x, q = threadIdx.x & 7, j = threadIdx.x >> 3;
-    const float4* src = reinterpret_cast<const float4*>(cam_part + (int64_t)b * tiles * 32) + q;
+    constexpr int Q = N / 4, ROWS = 1024 / Q;
+    __shared__ float4 s[ROWS][Q];
+    const int b = blockIdx.x, q = threadIdx.x % Q, j = threadIdx.x / Q;
+    const float4* src = reinterpret_cast<const float4*>(cam_part + (int64_t)b * tiles * N) + q;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     int t = j;
-    for (; t + 3 * 128 < tiles; t += 4 * 128) {
+    for (; t + 3 * ROWS < tiles; t += 4 * ROWS) {
         float4 v[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) v[u] = src[(int64_t)(t + u * 128) * 8];
+        for (int u = 0; u < 4; u++) v[u] = src[(int64_t)(t + u * ROWS) * Q];
 #pragma unroll
         for (int u = 0; u < 4; u++) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
     }
-    for (; t < tiles; t += 128) {
-        const float4 v = src[(int64_t)t * 8];
+    for (; t < tiles; t += ROWS) {
+        const float4 v = src[(int64_t)t * Q];
         a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
     }
     s[j][q] = a;
     __syncthreads();
-    for (int h = 64; h > 0; h >>= 1) {
+    for (int h = ROWS / 2; h > 0; h >>= 1) {
         if (j < h) {
             const float4 o = s[j + h][q];
             a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
@@ -1457,16 +1460,17 @@ k_tri_camera_reduce(int tiles, const float* __restrict__ cam_part, float* __rest
         }
         __syncthreads();
     }
-    if (threadIdx.x < 32) {  // (out may be any float of a flat gradient buffer: dword stores)
+    if (threadIdx.x < N) {  // (out may be any float of a flat gradient buffer: dword stores)
         const float4 v = s[0][threadIdx.x >> 2];
         const int c = threadIdx.x & 3;
-        out[32 * b + threadIdx.x] = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
+        out[N * b + threadIdx.x] = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
     }
 }
 
-void launch_tri_camera_reduce(int B, int tiles, const float* cam_part, float* out, hipStream_t st) {
+void launch_camera_reduce(int B, int tiles, int width, const float* cam_part, float* out, hipStream_t st) {
     if (B == 0) return;
-    k_tri_camera_reduce<<<dim3((unsigned)B), dim3(1024), 0, st>>>(tiles, cam_part, out);
+    if (width == 64) k_tri_camera_reduce<64><<<dim3((unsigned)B), dim3(1024), 0, st>>>(tiles, cam_part, out);
+    else k_tri_camera_reduce<32><<<dim3((unsigned)B), dim3(1024), 0, st>>>(tiles, cam_part, out);
 }
 
 void launch_tri_unpack(const dmr_scene& s, const float* vrow, const float* frow, float* dL_dverts,

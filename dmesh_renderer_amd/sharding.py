@@ -426,9 +426,10 @@ class ShardedTetRenderer(_Banded, TetRenderer):
     """TetRenderer whose image is sharded by tile-row bands across the ranks of `group` ("the tet path
     shards identically"): every rank bins with rects clipped to its band, finds first hits and marches the rays of
     its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F]
-    (full_grads: followed by [dL_dverts 3P | dL_dfaces_intense B*F], see TetRenderer).
+    (full_grads: followed by [dL_dverts 3P | dL_dfaces_intense B*F], camera_grads: then by the 64 B matrix gradients,
+    see TetRenderer).
     Same call signature and outputs as TetRenderer (color, depth, active bool)."""
 
     def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
-                 full_grads: bool = False):
-        super().__init__(render_settings, group, assemble, impl, full_grads=full_grads)
+                 full_grads: bool = False, camera_grads: bool = False):
+        super().__init__(render_settings, group, assemble, impl, full_grads=full_grads, camera_grads=camera_grads)

@@ -41,7 +41,8 @@ extern "C" {
  * transient workspace of the backward calls (packed gradient accumulators). */
 enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE = 3, DMR_BUF_WORK = 4,
        DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */,
-       DMR_BUF_TRI_CAMERA_GRADS = 6 /* dmr_tri_backward with DMR_FLAG_TRI_CAMERA_GRADS: an OUTPUT, see there */ };
+       DMR_BUF_TRI_CAMERA_GRADS = 6 /* dmr_tri_backward with DMR_FLAG_TRI_CAMERA_GRADS: an OUTPUT, see there */,
+       DMR_BUF_TET_CAMERA_GRADS = 7 /* dmr_tet_backward with DMR_FLAG_TET_CAMERA_GRADS: an OUTPUT, see there */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -52,8 +53,9 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * the backward: 4 bytes per tile pixel (256 Nt of them) and step of capacity, capacity = the longest march of the previous
  * call with the same view configuration * 1.25 + 4 steps (0 in the first such call), the whole capped at 16 GiB;
  * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record (+ 128 Nt with DMR_FLAG_TRI_CAMERA_GRADS); tri camera grads
- * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS only)
- * 4 (3P + BF), exactly. */
+ * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS or
+ * DMR_FLAG_TET_CAMERA_GRADS only) 4 (3P + BF), exactly; work (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 per tile of
+ * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -118,6 +120,9 @@ typedef struct dmr_scene {
 /* dmr_tri_backward also computes the gradients of the inverse matrices (implies DMR_FLAG_TRI_EXACT_GRADS); see there.
  * Ignored by every other call. */
 #define DMR_FLAG_TRI_CAMERA_GRADS 8
+/* dmr_tet_backward also computes the gradients of the four matrices (implies DMR_FLAG_TET_FULL_GRADS); see there.
+ * Ignored by every other call. */
+#define DMR_FLAG_TET_CAMERA_GRADS 16
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -161,8 +166,14 @@ int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, 
  * vertex positions and face intensities along the forward's march (each marched face enters through its hit (t, u, v):
  * u, v set the interpolated colour, t the hit point's ndc depth; opacities and transmittance do not depend on the
  * positions).  The buffer is caller-owned like the others; no host wait is added (DMR_FLAG_ASYNC and stream capture work
- * as without the flag).  verts_depth and the matrices get no gradient (the tet renderer does not read verts_depth).
- * Without the flag the call is exactly as before and requests no buffer. */
+ * as without the flag).  verts_depth gets no gradient (the tet renderer does not read it).
+ * With DMR_FLAG_TET_CAMERA_GRADS (implies DMR_FLAG_TET_FULL_GRADS) the call also requests buffer DMR_BUF_TET_CAMERA_GRADS
+ * through `alloc`, once, of 256 B bytes, and fully overwrites it with fp32 [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 |
+ * dL/dproj 16] in the contract layout m[4*col+row] whatever mats_transposed says.  The inverse matrices enter through every
+ * pixel's ray (origin = inv_mv's translation column, direction normalize(inv_mv (inv_proj (ndc, -1, 1)).xyz - origin) with
+ * no w divide and the length clamped to 1e-4, the seeded jitter held fixed); mv and proj through the ndc depth of each
+ * marched face's hit point (rows 0-2 of mv, rows 2-3 of proj).  The w rows of the inverses get 0.  Per-tile partials go to
+ * a DMR_BUF_WORK request.  No host wait is added.  Without the flags the call is exactly as before and requests no buffer. */
 int dmr_tet_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,

@@ -7,14 +7,16 @@ from dmesh_renderer_amd import _C, scenes
 ap = argparse.ArgumentParser(); ap.add_argument("--m", type=int, default=16); ap.add_argument("--size", type=int, default=800)
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--full-grads", action="store_true", help="backward with dL/dverts and dL/dfaces_intense (TetRenderer(full_grads=True))")
+ap.add_argument("--camera-grads", action="store_true", help="backward with those and the matrices' (TetRenderer(camera_grads=True))")
 a = ap.parse_args()
+kw = {"camera_grads": True} if a.camera_grads else ({"full_grads": True} if a.full_grads else {})
 dev = th.device("cuda:0"); H = W = a.size
 d = scenes.kuhn_tets(a.m, 1, H, W)
 args = scenes.c_args(d, dev, tet=True)
 gc, gd = scenes.upstream_grads(1, H, W); gc, gd = gc.to(dev), gd.to(dev)
 def step():
     o = _C.render_tets(*args, H, W, 0)
-    g = _C.render_tets_backward(*args, gc, gd, *o[3:7], **({"full_grads": True} if a.full_grads else {}))
+    g = _C.render_tets_backward(*args, gc, gd, *o[3:7], **kw)
     return o, g
 for _ in range(3): step()
 _C.profile_enable(0xFFFFFFFF); th.cuda.synchronize(); t0 = time.perf_counter()
