@@ -841,13 +841,14 @@ __device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y,
 __device__ __forceinline__ F3 load3(const float* __restrict__ a, int id) { return {a[3 * id], a[3 * id + 1], a[3 * id + 2]}; }
 }  // namespace fm
 
-constexpr int VTAB = 640;   // vertex-row slots per workgroup
+constexpr int VTAB = 560;   // vertex-row slots per workgroup
 constexpr int TAB_PROBES = 16;
 constexpr uint32_t TAB_EMPTY = 0xffffffffu;
 
-// Workgroup-level aggregation of the vertex gradient rows (LDS: 640 slots, 38 KB; with the tile's pixel records 46 KB: three
-// workgroups per CU.  C4's busiest tiles touch ~500 rows: 512 slots left them with probe sequences at load factor ~1 --
-// k_tri_backward_hits 101.4 us with 512 slots, 95.6-98.2 with 576 / 640 / 704, 117 with 768 = two workgroups per CU).
+// Workgroup-level aggregation of the vertex gradient rows (LDS: 560 slots, 32.8 KB; with the tile's pixels at 28 bytes each
+// 39.8 KB: four workgroups per CU, as the kernel's 128 registers allow.  C4's busiest tiles touch ~500 rows: 512 slots left
+// them with probe sequences at load factor ~1 -- k_tri_backward_hits 101.4 us with 512 slots, 95.6-98.2 with 576 / 640 / 704
+// at three workgroups per CU, 117 with 768 = two; the 640 slots of rounds 2-3 and a 3-KB face-row stage were 48.5 KB).
 // Global float atomics execute at the memory side at ~20 G 64-byte requests/s chip-wide whatever they carry
 // (MI355X_MICROARCH.md, "Global float atomics"): with one request per (segment, row) -- 3 vertex rows + 1 face row
 // per list entry -- this kernel was bound by exactly that (0.195 ms with the atomics, 0.110 ms without, 0.195 ms
@@ -862,11 +863,12 @@ constexpr uint32_t TAB_EMPTY = 0xffffffffu;
 // face rows 11 us (0.9 M) of the kernel's 106; staging the tails through LDS so that every lane takes one row (the
 // earlier layout) cost 5 us more than letting the tail lanes add their three rows from registers.
 struct HitsLds {
-    float4 pix[2 * TILE_PIX];   // the tile's pixels: (ray direction, dL/ddepth), (dL/dcolor, -)
-    uint32_t vkey[VTAB];
     double vval[VTAB][7];   // dx dy dz dr dg db ddepth of row (view, vertex)
-    uint32_t frow_stage[4][64][3];  // per wave: {face row id, dopacity, dintense} of the round's segment tails (see the loop)
+    float4 pixd[TILE_PIX];  // the tile's pixels: (ray direction, dL/ddepth) ...
+    float pixc[TILE_PIX][3];  // ... and dL/dcolor: 28 bytes a pixel (pixrec's unused eighth float is not staged)
+    uint32_t vkey[VTAB];
 };
+static_assert(sizeof(HitsLds) <= 160 * 1024 / 4, "four workgroups per CU share its 160 KB of LDS");
 // ... and in the camera variant the tile's per-pixel dL/d(ray direction) and the epilogue's per-wave sums (3.4 KB more)
 struct HitsLdsCam : HitsLds {
     float dray[TILE_PIX][3];
@@ -941,9 +943,12 @@ __device__ __forceinline__ void tab_find3(uint32_t* __restrict__ key, const uint
 // ray_tri_intersection_grad (Q11: its "dv" is dt's).  TRI_GRAD_EXACT differentiates each pair's Moeller-Trumbore (u, v)
 // exactly; TRI_GRAD_CAMERA does so with respect to the ray as well and leaves the tile's part of dL/dinv_mv, dL/dinv_proj
 // (32 floats, contract layout) in cam_part[tile] (its one argument in Cam).
-constexpr int HITS_WAVES = 1;
+// Four workgroups per CU (the start of a tile -- ids -> face and vertex gathers -- is latency nothing else on the SIMD hid at
+// three): 128 registers and no scratch for the default and exact variants.  The camera variant's per-pixel dL/d(ray
+// direction) takes its LDS past a quarter of the CU's: three, as before.
+constexpr int HITS_WAVES = 4;
 template <int GV, class... Cam>
-__global__ void __launch_bounds__(256, HITS_WAVES)
+__global__ void __launch_bounds__(256, GV == TRI_GRAD_CAMERA ? 3 : HITS_WAVES)
 k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRecord* __restrict__ hits, uint32_t capacity,
                     float* __restrict__ vrow, float* __restrict__ frow, Cam... cam_part) {
     constexpr bool EXACT = GV != TRI_GRAD_REF, CAM = GV == TRI_GRAD_CAMERA;
@@ -965,26 +970,31 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
 
     // record q of a lane's group: the wave's 64 lanes read one contiguous kilobyte (dmr_kernels.hpp, HIT_BLOCK).
     // The four `id` words of a group are the face and its three vertices (k_tri_backward_pix), so the vertex data can
-    // be gathered as soon as the records are here: two dependent memory levels per round instead of four
-    // (record -> list entry -> face -> vertices) -- and the records of round r + 1 are loaded while round r computes.
-    auto load_group = [&](uint32_t gi, uint4 (&r)[HIT_GROUP]) {
-        const bool in = gi < ngroups;
-        const uint4* src = reinterpret_cast<const uint4*>(hits + rec0 + (uint64_t)((in && !DMR_DBG(p, 65536) ? gi : 0u) / 64u) * HIT_BLOCK + (uint32_t)lane);
-#pragma unroll
-        for (int q = 0; q < HIT_GROUP; q++) r[q] = in ? src[64 * q] : make_uint4(0u, HIT_SKIPPED, 0u, 0u);
+    // be gathered as soon as the ids are here: two dependent memory levels per round instead of four
+    // (record -> list entry -> face -> vertices) -- and the ids of round r + 1 are loaded while round r computes.  The other
+    // three words of a record (pixel, T, dL/dalpha) are requested when their round starts, together with the face's gathers,
+    // which wait for as long (the ids' loads have brought their lines in).  Prefetching whole records held 12 registers more
+    // across the round: 146, three workgroups per CU.
+    auto group_src = [&](uint32_t gi) {
+        return hits + rec0 + (uint64_t)((gi < ngroups && !DMR_DBG(p, 65536) ? gi : 0u) / 64u) * HIT_BLOCK + (uint32_t)lane;
     };
-    // the first round's records and the tile's pixels are requested before the table is cleared: the workgroup's set-up
+    auto load_ids = [&](uint32_t gi, uint32_t (&id)[HIT_GROUP]) {
+        const HitRecord* src = group_src(gi);
+#pragma unroll
+        for (int q = 0; q < HIT_GROUP; q++) id[q] = gi < ngroups ? src[64 * q].id : 0u;
+    };
+    // the first round's ids and the tile's pixels are requested before the table is cleared: the workgroup's set-up
     // costs one memory latency, not one after the other (phase stamps: 5.1 k cycles of a tile's ~55 k were set-up)
-    uint4 raw[HIT_GROUP], nxt[HIT_GROUP];
-    load_group((uint32_t)tid, nxt);
-    const float4 px0 = pixrec[2 * (int64_t)tile * TILE_PIX + tid], px1 = pixrec[2 * (int64_t)tile * TILE_PIX + 256 + tid];
+    uint32_t nid[HIT_GROUP];
+    load_ids((uint32_t)tid, nid);
+    const float4 px0 = pixrec[2 * ((int64_t)tile * TILE_PIX + tid)], px1 = pixrec[2 * ((int64_t)tile * TILE_PIX + tid) + 1];
     for (int i = tid; i < VTAB; i += 256) {
         L.vkey[i] = TAB_EMPTY;
 #pragma unroll
         for (int c = 0; c < 7; c++) L.vval[i][c] = 0.0;
     }
-    L.pix[tid] = px0;
-    L.pix[tid + 256] = px1;
+    L.pixd[tid] = px0;
+    L.pixc[tid][0] = px1.x; L.pixc[tid][1] = px1.y; L.pixc[tid][2] = px1.z;
     fm::F3 camT = {0.f, 0.f, 0.f};  // camera variant: this lane's part of dL/d(ray origin) = sum of dL/dT
     if constexpr (CAM) {
 #pragma unroll
@@ -996,9 +1006,17 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         const uint32_t gi = g0 + (uint32_t)tid;
         const bool valid = gi < ngroups;   // lanes past the end: no group, unique keys
         DMR_STAMP(p, 2, g0 / 256u, 0);
+        uint4 raw[HIT_GROUP];  // this round's records (past the end: skipped pairs)
+        {
+            const HitRecord* src = group_src(gi);
 #pragma unroll
-        for (int q = 0; q < HIT_GROUP; q++) raw[q] = nxt[q];
-        load_group(gi + 256u, nxt);  // in flight while this round computes (past the end: nothing is loaded)
+            for (int q = 0; q < HIT_GROUP; q++) {
+                const HitRecord* h = src + 64 * q;
+                raw[q] = valid ? make_uint4(nid[q], h->pixel, __float_as_uint(h->T), __float_as_uint(h->dL_dalpha))
+                               : make_uint4(0u, HIT_SKIPPED, 0u, 0u);
+            }
+        }
+        load_ids(gi + 256u, nid);  // in flight while this round computes (past the end: nothing is loaded)
         int k = -1 - lane;  // invalid lanes: unique keys
         int v0 = 0, v1 = 0, v2 = 0, face = 0;
         float g[NSCAN];
@@ -1023,7 +1041,9 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
             xT = view_o - xp0; xE1 = xp1 - xp0; xE2 = xp2 - xp0;
             xQ = dmr::cross(xT, xE1);
             w2 = dmr::dot(xQ, xE2);
-            xE12 = dmr::cross(xE1, xE2); xE2T = dmr::cross(xE2, xT);
+            // E1 x E2 and E2 x T: carried across the pairs by the camera variant only, the others take them where they are
+            // needed (the same function of the same vectors): six registers of the four workgroups per CU
+            if constexpr (CAM) { xE12 = dmr::cross(xE1, xE2); xE2T = dmr::cross(xE2, xT); }
             // i0 = 1 - uc - vc, i1 = uc, i2 = vc: what multiplies uc and vc in the interpolated colour / depth
             const F3 dc10 = cc1 - cc0, dc20 = cc2 - cc0;
             const float dd10 = fd1 - fd0, dd20 = fd2 - fd0;
@@ -1036,7 +1056,8 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
 #pragma unroll
             for (int q = 0; q < HIT_GROUP; q++) {
                 if (raw[q].y & HIT_SKIPPED) continue;  // pad, or a pair the forward skipped (denom == 0)
-                const float4 pr0 = L.pix[2 * (raw[q].y & 255u)], pr1 = L.pix[2 * (raw[q].y & 255u) + 1];
+                const float4 pr0 = L.pixd[raw[q].y & 255u];
+                const float* pr1 = L.pixc[raw[q].y & 255u];
                 const float hT = __uint_as_float(raw[q].z), hdLda = __uint_as_float(raw[q].w);
                 // forward quantities of this (pixel, face) pair (backward.cu:206-243).  Exact arithmetic (the V3 helpers
                 // are not contracted): the clamp region `code` selects a piecewise-constant Jacobian, so (u, v) must land
@@ -1054,7 +1075,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
                 const float i0 = 1 - iuc - ivc, i1 = iuc, i2 = ivc;
                 // dL/dcolor and dL/ddepth of the pair (backward.cu:254-275), the face intensity folded in once
                 const float aT = alpha * hT;
-                const float dic0 = pr1.x * aT, dic1 = pr1.y * aT, dic2 = pr1.z * aT, did = pr0.w * aT;
+                const float dic0 = pr1[0] * aT, dic1 = pr1[1] * aT, dic2 = pr1[2] * aT, did = pr0.w * aT;
                 const float dii0 = dic0 * intense, dii1 = dic1 * intense, dii2 = dic2 * intense;
                 // dL/d(uc), dL/d(vc) (backward.cu:313-330: dL/d(weights), then i1 - i0 and i2 - i0) and dL/dintensity
                 const float e1 = dc10.x * dii0 + dc10.y * dii1 + dc10.z * dii2 + dd10 * did;
@@ -1086,9 +1107,9 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
                         const V3 du_dE1 = (-1.0f * xP * w0) * rinv;
                         const V3 du_dE2 = (dmr::cross(xT, xd) * w1 - w0 * dmr::cross(xE1, xd)) * rinv;
                         const V3 du_dT = (xP * w1) * rinv;
-                        const V3 dv_dE1 = ((xE2T * w1) - (w2 * xP)) * rinv;
+                        const V3 dv_dE1 = ((dmr::cross(xE2, xT) * w1) - (w2 * xP)) * rinv;
                         const V3 dv_dE2 = ((xQ * w1) - (w2 * dmr::cross(xE1, xd))) * rinv;
-                        const V3 dv_dT = xE12 * w1 * rinv;
+                        const V3 dv_dT = dmr::cross(xE1, xE2) * w1 * rinv;
                         const V3 du_dp0 = -du_dE1 - du_dE2 - du_dT, dv_dp0 = -dv_dE1 - dv_dE2 - dv_dT;
                         dp0 = rdiu * du_dp0 + rdiv * dv_dp0;
                         dp1 = rdiu * du_dE1 + rdiv * dv_dE1;
@@ -1196,8 +1217,10 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
             using namespace fm;
             const F3 mB = {g[0], g[1], g[2]}, mA = {g[3], g[4], g[5]};
             const F3 fT = {xT.x, xT.y, xT.z}, fE1 = {xE1.x, xE1.y, xE1.z}, fE2 = {xE2.x, xE2.y, xE2.z};
-            const F3 fQ = {xQ.x, xQ.y, xQ.z}, fE12 = {xE12.x, xE12.y, xE12.z}, fE2T = {xE2T.x, xE2T.y, xE2T.z};
+            const F3 fQ = {xQ.x, xQ.y, xQ.z};
             if constexpr (!EXACT) {
+                const V3 xE12 = dmr::cross(xE1, xE2), xE2T = dmr::cross(xE2, xT);
+                const F3 fE12 = {xE12.x, xE12.y, xE12.z}, fE2T = {xE2T.x, xE2T.y, xE2T.z};
                 dp1 = g[6] * fE2T - cross(mB, fE2);
                 dp2 = cross(fT, mA) - cross(fE1, mB) + g[6] * fQ;
                 const F3 dT = cross(mA, fE2) + g[6] * fE12;
@@ -1215,25 +1238,30 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         }
         // The face rows (opacity, intensity: two adjacent floats) of the round's tails go out first.  A tail lane sending its two
         // values itself is two memory-side requests (two instructions): 4.6 us of this kernel at C4.  So the tails are compacted
-        // through 12 bytes of wave-private LDS each and lanes 2r / 2r + 1 send the two floats of tail r in ONE instruction -- one
-        // 8-byte request per tail (up to 32 tails per instruction).
+        // and lanes 2r / 2r + 1 send the two floats of tail r in ONE instruction -- one 8-byte request per tail (up to 32 tails
+        // per instruction).  The compaction is two lane permutations, no LDS memory (it was a 3-KB stage, the difference between
+        // three and four workgroups per CU): tail r sends its lane number to lane r (ds_permute; the other lanes fill the lanes
+        // behind the tails, so every lane receives exactly one), then lane 2r / 2r + 1 pulls from tail r's lane (ds_bpermute).
         {
             const bool ft = tail && !DMR_DBG(p, 512);
             const uint64_t tmask = __ballot(ft);
             const int ntail = __popcll(tmask);
-            if (ft) {
-                uint32_t* st = L.frow_stage[tid >> 6][__popcll(tmask & ((1ull << lane) - 1ull))];
-                st[0] = (uint32_t)b * (uint32_t)p.F + (uint32_t)face; st[1] = __float_as_uint(g[19]); st[2] = __float_as_uint(g[20]);
-            }
-            wave_lds_sync();
-            for (int t0 = 0; t0 < ntail; t0 += 32) {
-                const int t = t0 + (lane >> 1);
-                if (t < ntail) {
-                    const uint32_t* st = L.frow_stage[tid >> 6][t];
-                    atomicAdd(&frow[(int64_t)st[0] * FROW + (lane & 1)], __uint_as_float(st[1 + (lane & 1)]));
+            if (ntail > 0) {  // uniform
+                // (tails in lanes below this one: v_mbcnt, not a popcount of a lane mask the compiler would hoist out of the loop
+                // and keep in four registers)
+                const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+                const int dst = ft ? below : ntail + (lane - below);
+                const int src = __builtin_amdgcn_ds_permute(dst << 2, lane);  // lane r < ntail: the lane of tail r
+                const int fid = b * p.F + face;
+                for (int t0 = 0; t0 < ntail; t0 += 32) {
+                    const int t = t0 + (lane >> 1);  // < 64
+                    const int s = __builtin_amdgcn_ds_bpermute(t << 2, src) << 2;
+                    const int row = __builtin_amdgcn_ds_bpermute(s, fid);
+                    const int dop = __builtin_amdgcn_ds_bpermute(s, __float_as_int(g[19]));
+                    const int din = __builtin_amdgcn_ds_bpermute(s, __float_as_int(g[20]));
+                    if (t < ntail) atomicAdd(&frow[(int64_t)(uint32_t)row * FROW + (lane & 1)], __int_as_float((lane & 1) ? din : dop));
                 }
             }
-            wave_lds_sync();  // (the stage may be refilled by the next round)
         }
         // a tail lane adds its entry's three vertex rows into the table, from its registers
         if (tail && !DMR_DBG(p, 512)) {
@@ -1312,16 +1340,16 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     }
     if (DMR_DBG(p, 1024)) return;
     // (eight slots per lane are read before the first atomic goes out: the LDS latencies overlap instead of adding up)
-    constexpr int FLUSH_BATCH = VTAB % 256 == 0 ? 8 : (VTAB % 128 == 0 ? 4 : 2);
-    static_assert(VTAB % (32 * FLUSH_BATCH) == 0, "table size");
+    // (slots past the table's end, in the last batch, read as empty)
+    constexpr int FLUSH_BATCH = 8;
     const int comp = tid & 7;
     for (int s0 = 0; s0 < VTAB; s0 += 32 * FLUSH_BATCH) {
         uint32_t rid[FLUSH_BATCH]; float val[FLUSH_BATCH];
 #pragma unroll
         for (int i = 0; i < FLUSH_BATCH; i++) {
             const int slot = s0 + 32 * i + (tid >> 3);
-            rid[i] = L.vkey[slot];
-            val[i] = (float)L.vval[slot][comp < 7 ? comp : 0];
+            rid[i] = slot < VTAB ? L.vkey[slot] : TAB_EMPTY;
+            val[i] = slot < VTAB ? (float)L.vval[slot][comp < 7 ? comp : 0] : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < FLUSH_BATCH; i++)
