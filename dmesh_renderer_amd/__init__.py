@@ -75,13 +75,24 @@ def _trailing(*args) -> tuple:
     return args[:n]
 
 
-def _tri_forward(impl, settings: TriRenderSettings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows):
+def _alpha_kw(alpha) -> dict:
+    """The `alpha` keyword of the four `_C` functions; no keyword by default: the reference's call."""
+    return {"alpha": True} if alpha else {}
+
+
+def _split_alpha(out):
+    """(color, depth | alpha [B,2,H,W], ...) of a Function called with alpha -> (color, depth, ..., alpha [B,1,H,W]).  Slices
+    of one tensor: autograd assembles the two-channel upstream gradient (zeros for a channel the loss does not use)."""
+    return (out[0], out[1][:, :1], *out[2:], out[1][:, 1:])
+
+
+def _tri_forward(impl, settings: TriRenderSettings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows, alpha=False):
     """One render_tris call -> (num_rendered, color, depth, what its backward needs after geom: the matrices, their
-    inverses, verts_depth, faces_intense and the four scratch buffers)."""
+    inverses, verts_depth, faces_intense and the four scratch buffers).  alpha: depth is [B,2,H,W], depth | alpha."""
     cams = _with_inverses(mv_mats, proj_mats)
     try:
         out = impl.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
-                               settings.image_height, settings.image_width, rows=rows)
+                               settings.image_height, settings.image_width, rows=rows, **_alpha_kw(alpha))
     except Exception as ex:
         print("\nAn error occured in forward.")
         print(ex)
@@ -102,10 +113,10 @@ def _tri_backward(impl, settings: TriRenderSettings, geom, saved, grad_color, gr
 def _tri_grad_options(ctx) -> Tuple[bool, dict]:
     """(camera, keywords of render_tris_backward).  The matrices' gradients are computed only when asked for and a matrix
     needs one: otherwise the exact variant, which skips the per-pixel ray sums.  No keyword by default: the reference's
-    call.  (A fresh dict: the caller may add flat_out.)"""
+    call.  (A fresh dict: the caller may add flat_out.)  With ctx.alpha also alpha=True: grad_depth is [B,2,H,W]."""
     if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
-        return True, {"camera_grads": True}
-    return False, ({"exact_grads": True} if ctx.exact_grads else {})
+        return True, {"camera_grads": True, **_alpha_kw(ctx.alpha)}
+    return False, {**({"exact_grads": True} if ctx.exact_grads else {}), **_alpha_kw(ctx.alpha)}
 
 
 def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj, g_mv=None,
@@ -124,8 +135,8 @@ def _tet_grad_options(ctx) -> Tuple[bool, dict]:
     """(camera, keywords of render_tets_backward), decided as _tri_grad_options does: the camera variant only when asked
     for and a matrix needs a gradient, else the full one, else no keyword (the reference's call)."""
     if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
-        return True, {"camera_grads": True}
-    return False, ({"full_grads": True} if ctx.full_grads else {})
+        return True, {"camera_grads": True, **_alpha_kw(ctx.alpha)}
+    return False, {**({"full_grads": True} if ctx.full_grads else {}), **_alpha_kw(ctx.alpha)}
 
 
 def _tri_flat(P: int, F: int, B: int, camera: bool, device, alloc=th.empty) -> Tuple[th.Tensor, List[th.Tensor]]:
@@ -139,22 +150,23 @@ def _tri_flat(P: int, F: int, B: int, camera: bool, device, alloc=th.empty) -> T
 
 class _TriFn(th.autograd.Function):
     """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense, settings, rows, shard,
-    exact_grads, camera_grads (the last three only when set: see _trailing).  Gradients flow to verts, verts_color,
-    faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  shard: None
+    exact_grads, camera_grads, alpha (the last four only when set: see _trailing).  Gradients flow to verts, verts_color,
+    faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  alpha: the
+    second output is [B,2,H,W], depth | alpha (the caller slices it: _split_alpha), and so is its gradient.  shard: None
     on one device (the kernels are then `_C` as it is at call time: tests swap it); from a sharded Module
     (sharding._Shard) its kernels, the band images to assemble and the gradients' all-reduce."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False):
+                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False):
         impl = _C if shard is None else shard.impl
         geom = (verts, faces, verts_color, faces_opacity)
         num_rendered, color, depth, saved = _tri_forward(impl, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense,
-                                                         rows)
+                                                         rows, alpha)
         if shard is not None:
             color, depth = shard.gather((color, depth))
         ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
-        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
+        ctx.exact_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved)
         return color, depth
 
@@ -171,23 +183,25 @@ class _TriFn(th.autograd.Function):
         if shard is not None:
             g = shard.reduce(g, flat)
         g_mv, g_proj = _camera_grads(ctx, saved[2], saved[3], g[5], g[6]) if camera else (None, None)
-        return g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4], None, None, None, None, None
+        return g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4], None, None, None, None, None, None
 
 
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
-    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard: as for _TriFn."""
+    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha: as for _TriFn."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False):
+                tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False,
+                alpha=False):
         impl = _C if shard is None else shard.impl
         cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
         topo = (tets, face_tets, tet_faces)
         try:
             out = impl.render_tets(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo,
-                                   settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows)
+                                   settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows,
+                                   **_alpha_kw(alpha))
         except Exception:
             print("\nAn error occured in forward.")
             raise
@@ -196,7 +210,7 @@ class _TetFn(th.autograd.Function):
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
         ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
-        ctx.full_grads, ctx.camera_grads = full_grads or camera_grads, camera_grads
+        ctx.full_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
         ctx.mark_non_differentiable(active)
         return color, depth, active
@@ -223,24 +237,27 @@ class _TetFn(th.autograd.Function):
             g = shard.reduce(g, flat)
         g_verts, g_vcolor, g_fopacity, g_fintense = g[:4] if ctx.full_grads else (None, *g, None)
         g_mv, g_proj = _camera_grads(ctx, saved[6], saved[7], *g[4:8]) if camera else (None, None)
-        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, None, g_fintense) + (None,) * 8
+        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, None, g_fintense) + (None,) * 9
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False):
+               render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False, return_alpha=False):
     """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices.  exact_grads,
-    camera_grads: see TriRenderer."""
-    return _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                        render_settings, tuple(rows), *_trailing(None, bool(exact_grads), bool(camera_grads)))
+    camera_grads, return_alpha: see TriRenderer."""
+    out = _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
+                       render_settings, tuple(rows), *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha)))
+    return _split_alpha(out) if return_alpha else out
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False, camera_grads=False):
+               tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False, camera_grads=False,
+               return_alpha=False):
     """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads,
-    camera_grads: see TetRenderer."""
-    return _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                        tets, face_tets, tet_faces, render_settings, tuple(rows),
-                        *_trailing(None, bool(full_grads), bool(camera_grads)))
+    camera_grads, return_alpha: see TetRenderer."""
+    out = _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
+                       tets, face_tets, tet_faces, render_settings, tuple(rows),
+                       *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha)))
+    return _split_alpha(out) if return_alpha else out
 
 
 class TriRenderer(th.nn.Module):
@@ -259,25 +276,35 @@ class TriRenderer(th.nn.Module):
 
     Both options cost a slower backward; the forward is the same.
 
+    return_alpha=True (beyond the reference): a third image, alpha [B,1,H,W] = 1 - T, the accumulated opacity (coverage)
+    of the pixel, T being the transmittance the renderer multiplies into the background: color == C + (1 - alpha) * bg.
+    0 where nothing was blended and outside a rendered row band.  Its gradient reaches faces_opacity only
+    (d alpha / d opacity_i = T / (1 - opacity_i) for every blended face) and combines with the options above: a mask
+    loss, or a per-pixel background composited in torch -- render with bg = 0, then color + (1 - alpha) * bg_image.
+
     forward(verts [P,3], faces [F,3], verts_color [P,3], faces_opacity [F],
             mv_mats [B,4,4], proj_mats [B,4,4], verts_depth [B,P], faces_intense [B,F])
-        -> color [B,3,H,W], depth [B,1,H,W]
+        -> color [B,3,H,W], depth [B,1,H,W] (, alpha [B,1,H,W] with return_alpha)
     """
 
-    def __init__(self, render_settings: TriRenderSettings, exact_grads: bool = False, camera_grads: bool = False):
+    def __init__(self, render_settings: TriRenderSettings, exact_grads: bool = False, camera_grads: bool = False,
+                 return_alpha: bool = False):
         super().__init__()
         self.render_settings = render_settings
         self.exact_grads = bool(exact_grads)
         self.camera_grads = bool(camera_grads)
+        self.return_alpha = bool(return_alpha)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
-        return self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
-                            mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense)
+        out = self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
+                           mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense)
+        return _split_alpha(out) if self.return_alpha else out
 
     def _render(self, *inputs):
         """_TriFn on the normalised inputs (faces int32, the matrices transposed); ShardedTriRenderer adds a partition."""
         rows, shard = self._shard()
-        return _TriFn.apply(*inputs, self.render_settings, rows, *_trailing(shard, self.exact_grads, self.camera_grads))
+        return _TriFn.apply(*inputs, self.render_settings, rows,
+                            *_trailing(shard, self.exact_grads, self.camera_grads, self.return_alpha))
 
     def _shard(self):
         """(rows, shard) of the Functions: all rows on one device (the sharded Modules return their band)."""
@@ -300,25 +327,31 @@ class TetRenderer(th.nn.Module):
 
     Both options cost a slower backward; the forward is the same.
 
+    return_alpha=True (beyond the reference): a fourth output, alpha [B,1,H,W] = 1 - T as TriRenderer's; 0 where the
+    march fails (active == False: the colour there is the bare background).  Its gradient reaches faces_opacity only.
+
     forward(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
             tets [T,4], face_tets [F,2] (-1 = none), tet_faces [T,4])
-        -> color [B,3,H,W], depth [B,1,H,W], active bool [B,H,W]
+        -> color [B,3,H,W], depth [B,1,H,W], active bool [B,H,W] (, alpha [B,1,H,W] with return_alpha)
     """
 
-    def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False):
+    def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False,
+                 return_alpha: bool = False):
         super().__init__()
         self.render_settings = render_settings
         self.full_grads = bool(full_grads)
         self.camera_grads = bool(camera_grads)
+        self.return_alpha = bool(return_alpha)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
         f32, i32 = dict(dtype=th.float32), dict(dtype=th.int32)
         rows, shard = self._shard()
-        return _TetFn.apply(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
-                            mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
-                            verts_depth.to(**f32), faces_intense.to(**f32),
-                            tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
-                            rows, *_trailing(shard, self.full_grads, self.camera_grads))
+        out = _TetFn.apply(verts.to(**f32), faces.to(**i32), verts_color.to(**f32), faces_opacity.to(**f32),
+                           mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
+                           verts_depth.to(**f32), faces_intense.to(**f32),
+                           tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
+                           rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha))
+        return _split_alpha(out) if self.return_alpha else out
 
     _shard = TriRenderer._shard  # (rows, shard) of one device

@@ -495,7 +495,7 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
         const dmr_scene sc = canonical(s, c.is.mats);
         dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, c.is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys,
                                 c.bs.face_list, c.bs.capacity, tri_image(c), out_color,
-                                out_depth, st);
+                                out_depth, st, (s->flags & DMR_FLAG_ALPHA) != 0);
     };
     return run_forward(s, false, d, alloc, ctx, st, num_rendered, render);
 }
@@ -566,7 +566,8 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         // with every younger load -- 17 us.)
         dmr::launch_tri_backward_pix(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, is.tile_offset, c.bs.face_list, img,
                                      dL_dcolor, dL_ddepth, pixrec, hits, (uint32_t)capacity,
-                                     reinterpret_cast<float*>(work), (vbytes + fbytes + cbytes) / sizeof(float), regions, st);
+                                     reinterpret_cast<float*>(work), (vbytes + fbytes + cbytes) / sizeof(float), regions, st,
+                                     (s->flags & DMR_FLAG_ALPHA) != 0);  // (dL_ddepth [B,2,H,W]: its alpha channel reaches dL_dfopacity)
         dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st,
                                       grads, camera ? cam_part : nullptr);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
@@ -605,7 +606,7 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
         dmr::launch_tet_prep(sc, img, c.bs.seq_steps, c.bs.seq_offset, st);
         dmr::launch_tet_first_intersect(sc, d.gx, d.gy, d.r0, d.r1, c.fs.key_depth, c.fs.max_depth, c.is.tile_offset,
                                         d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys, c.bs.face_list, c.bs.capacity, img, st);
-        dmr::launch_tet_forward(sc, d.gx, d.gy, d.r0, d.r1, img, out_color, out_depth, out_active, st);
+        dmr::launch_tet_forward(sc, d.gx, d.gy, d.r0, d.r1, img, out_color, out_depth, out_active, st, (s->flags & DMR_FLAG_ALPHA) != 0);
     };
     return run_forward(s, true, d, alloc, ctx, st, num_rendered, render);
 }
@@ -654,7 +655,7 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     const dmr_scene sc = canonical(s, c.is.mats);
     uint32_t* host_seq_steps = march_estimate(size_key(s, true, d), d, false);
     dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
-                             full, full ? full + 3 * (int64_t)s->P : nullptr, cam_part);
+                             full, full ? full + 3 * (int64_t)s->P : nullptr, cam_part, (s->flags & DMR_FLAG_ALPHA) != 0);
     if (cam_out) dmr::launch_camera_reduce(s->B, band_tiles, 64, cam_part, cam_out, st);
     DMR_HIP(hipGetLastError());
     return 0;

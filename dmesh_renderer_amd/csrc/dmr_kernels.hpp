@@ -103,11 +103,14 @@ inline size_t mask_slots(size_t list_capacity, size_t ntiles) { return mask_firs
 // consumed one per lane by k_tri_backward_hits.
 // (A 32-byte record carrying face and vertex ids was tried: kernel 2 did not get faster, kernel 1 got 9 % slower.)
 struct alignas(16) HitRecord { uint32_t id; uint32_t pixel; float T; float dL_dalpha; };  // id: word (slot mod HIT_GROUP) of {face, v0, v1, v2}; pixel: tile-local
+// alpha (DMR_FLAG_ALPHA, every launcher that takes it): the depth image -- out_depth, dL_ddepth -- has two channels, [B,2,H,W]:
+// channel 0 the depth, channel 1 the accumulated opacity alpha = 1 - T_final (0 where a tet pixel's march fails) / its
+// upstream gradient, which reaches dL_dfopacity only.  A compile-time variant of the kernels; the default ones are unchanged.
 // keys: the unsorted (depth_bits << 32 | face) list entries of the scatter pass: every tile's workgroup sorts its own list
 // (dmr_sort.hpp) into face_list before compositing it, no launch_sort_tiles; null: face_list is sorted already
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
-                        float* out_color, float* out_depth, hipStream_t st);
+                        float* out_color, float* out_depth, hipStream_t st, bool alpha = false);
 // host_*: pinned host memory the kernel also writes its total to (no separate device->host copy)
 // hit_offset: every tile's region of the record buffer, sized by the bound h + (HIT_GROUP - 1) * min(list length, h) of
 // its h blended pairs (tile_hits); tile_used is cleared (the per-pixel kernel fills it)
@@ -127,7 +130,8 @@ struct HitRegions {
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                              const uint32_t* tile_offset, const uint32_t* face_list, TriImageState img,
                              const float* dL_dcolor, const float* dL_ddepth, float4* pixrec, HitRecord* hits,
-                             uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st);
+                             uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st,
+                             bool alpha = false);
 // one workgroup per tile (longest list first) over the tile's img.tile_used records.
 // grads: the vertex-position gradient the kernel forms -- TRI_GRAD_REF the reference's ray_tri_intersection_grad (Q11),
 // TRI_GRAD_EXACT the exact derivative of each pair's (u, v), TRI_GRAD_CAMERA that and the ray's: every tile of the call
@@ -183,7 +187,7 @@ void launch_tet_first_intersect(const dmr_scene& s, int gx, int gy, int r0, int 
                                 const float* max_depth, const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list,
                                 uint32_t capacity, TetImageState img, hipStream_t st);
 void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
-                        float* out_color, float* out_depth, float* out_active, hipStream_t st);
+                        float* out_color, float* out_depth, float* out_active, hipStream_t st, bool alpha = false);
 void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopacity, int64_t n_fopacity, hipStream_t st);
 // Two launches, of which the device runs one: k_tet_backward_seq when the forward's march sequence is complete
 // (seq->max_steps <= seq->cap_steps != 0), else the re-marching k_tet_backward; the other one returns at once.  No host read.
@@ -194,6 +198,6 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
                          uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts = nullptr, float* dL_dfintense = nullptr,
-                         float* cam_part = nullptr);
+                         float* cam_part = nullptr, bool alpha = false);
 
 }  // namespace dmr

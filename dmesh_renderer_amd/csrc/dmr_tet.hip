@@ -356,7 +356,10 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {  // all 64 lanes 
     return v;
 }
 
+// ALPHA (DMR_FLAG_ALPHA): out_depth is [B,2,H,W] -- channel 0 the depth, channel 1 the accumulated opacity 1 - T of the T the
+// pixel's colour multiplies into the background, 0 where the march fails: one more 4-byte store per pixel.
 constexpr int TET_FWD_WAVES = 4;
+template <bool ALPHA = false>
 __global__ void __launch_bounds__(256, TET_FWD_WAVES)
 k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_active) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -448,13 +451,23 @@ k_tet_forward(TetParams p, float* __restrict__ out_color, float* __restrict__ ou
         out_color[((int64_t)b * 3 + 0) * HW + pix_id] = C.x + fT * p.bg[0];
         out_color[((int64_t)b * 3 + 1) * HW + pix_id] = C.y + fT * p.bg[1];
         out_color[((int64_t)b * 3 + 2) * HW + pix_id] = C.z + fT * p.bg[2];
-        out_depth[bpix] = D + fT * 1.0f;
+        if constexpr (ALPHA) {
+            out_depth[((int64_t)b * 2 + 0) * HW + pix_id] = D + fT * 1.0f;
+            out_depth[((int64_t)b * 2 + 1) * HW + pix_id] = 1.0f - fT;
+        } else {
+            out_depth[bpix] = D + fT * 1.0f;
+        }
         out_active[bpix] = 1.0f;
     } else {
         out_color[((int64_t)b * 3 + 0) * HW + pix_id] = p.bg[0];
         out_color[((int64_t)b * 3 + 1) * HW + pix_id] = p.bg[1];
         out_color[((int64_t)b * 3 + 2) * HW + pix_id] = p.bg[2];
-        out_depth[bpix] = 1.0f;
+        if constexpr (ALPHA) {
+            out_depth[((int64_t)b * 2 + 0) * HW + pix_id] = 1.0f;
+            out_depth[((int64_t)b * 2 + 1) * HW + pix_id] = 0.0f;
+        } else {
+            out_depth[bpix] = 1.0f;
+        }
         out_active[bpix] = 0.0f;
     }
 }
@@ -928,6 +941,10 @@ __device__ __forceinline__ void tet_camera_tile(const TetParams& p, int b, int p
 }
 
 // what a pixel's reverse walk starts from; false: the pixel has no gradient (outside, inactive, nothing marched)
+// ALPHA (DMR_FLAG_ALPHA): dL_ddepth is [B,2,H,W], channel 1 the upstream gradient g_a of alpha = 1 - T_final.  d alpha / d opacity_i
+// = T_final / (1 - opacity_i) is minus the factor of the background terms, so -g_a joins bd_dot, which enters face_grad /
+// face_grad_fast through that tail term only: one more 4-byte load per pixel, the walk itself is the same code.
+template <bool ALPHA>
 __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px, int py, const float* __restrict__ dL_dcolor,
                                               const float* __restrict__ dL_ddepth, TetBwdPixel& st, V3& ro, V3& rd,
                                               int& first_face, int& last_face) {
@@ -944,11 +961,13 @@ __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px,
     st.dpc0 = dL_dcolor[((int64_t)b * 3 + 0) * HW + pix_id];
     st.dpc1 = dL_dcolor[((int64_t)b * 3 + 1) * HW + pix_id];
     st.dpc2 = dL_dcolor[((int64_t)b * 3 + 2) * HW + pix_id];
-    st.dpd = dL_ddepth[bpix];
+    if constexpr (ALPHA) st.dpd = dL_ddepth[((int64_t)b * 2 + 0) * HW + pix_id];
+    else st.dpd = dL_ddepth[bpix];
     float bg_dot = 0.f;
     bg_dot += p.bg[0] * st.dpc0; bg_dot += p.bg[1] * st.dpc1; bg_dot += p.bg[2] * st.dpc2;
     st.bg_dot = bg_dot;
     st.bd_dot = 0.f + (float)(1.0 * (double)st.dpd);
+    if constexpr (ALPHA) st.bd_dot = st.bd_dot - dL_ddepth[((int64_t)b * 2 + 1) * HW + pix_id];
     st.last_alpha = 0.f; st.lc0 = st.lc1 = st.lc2 = 0.f; st.ar0 = st.ar1 = st.ar2 = 0.f; st.last_depth = 0.f; st.ard = 0.f;
     st.first_iter = true;
     pixel_ray<true>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd, *p.seed, (uint64_t)bpix);
@@ -965,7 +984,8 @@ __device__ __forceinline__ bool tet_bwd_begin(const TetParams& p, int b, int px,
 // (DMR_FLAG_TET_FULL_GRADS), which this instantiation accumulates as well (the default one's code is unchanged by them),
 // or float*, float*, float* -- those and the camera variant's per-tile partials [tiles][64] (DMR_FLAG_TET_CAMERA_GRADS,
 // tet_camera_tile; tile = (view * rows + row - r0) * gx + column, every tile of the band written).
-template <class... Full>
+// ALPHA: see tet_bwd_begin.
+template <bool ALPHA, class... Full>
 __global__ void __launch_bounds__(256)
 k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, Full... full) {
@@ -1001,7 +1021,7 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
         TetBwdPixel st;
         V3 ro = {0, 0, 0}, rd = {0, 0, 0};
         int first_face = -1, last_face = -1;
-        bool done = !tet_bwd_begin(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
+        bool done = !tet_bwd_begin<ALPHA>(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
         [[maybe_unused]] const bool work = !done;
         [[maybe_unused]] TetCamPix cam;
         if constexpr (CAM) cam.clear();
@@ -1054,9 +1074,9 @@ k_tet_backward(TetParams p, int rows, const float* __restrict__ dL_dcolor, const
 // picked, here with contracted arithmetic (tfast: nothing is decided by it) -- instead of the tet record, three candidate
 // records, three tests and the orientation logic.  Stops where the reference stops: behind first_face, or behind an entry
 // whose bit 31 says the reverse march would find two candidates there.
-// Full: as k_tet_backward's
+// Full, ALPHA: as k_tet_backward's
 constexpr int TET_BWD_WAVES = 1;
-template <class... Full>
+template <bool ALPHA, class... Full>
 __global__ void __launch_bounds__(256, TET_BWD_WAVES)
 k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                    float* __restrict__ dL_dvcolor, float* __restrict__ dL_dfopacity, uint32_t* __restrict__ host_seq_steps, Full... full) {
@@ -1090,7 +1110,7 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
     TetBwdPixel st;
     V3 ro = {0, 0, 0}, rd = {0, 0, 0};
     int first_face = -1, last_face = -1;
-    const bool work = tet_bwd_begin(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
+    const bool work = tet_bwd_begin<ALPHA>(p, b, px, py, dL_dcolor, dL_ddepth, st, ro, rd, first_face, last_face);
     [[maybe_unused]] TetCamPix cam;
     if constexpr (CAM) cam.clear();
     const uint32_t n = work ? min(p.img.n_contrib[(int64_t)b * p.H * p.W + (int64_t)p.W * py + px], seq_cap) : 0u;
@@ -1211,11 +1231,12 @@ void launch_tet_first_intersect(const dmr_scene& s, int gx, int gy, int r0, int 
 }
 
 void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
-                        float* out_color, float* out_depth, float* out_active, hipStream_t st) {
+                        float* out_color, float* out_depth, float* out_active, hipStream_t st, bool alpha) {
     if (r1 <= r0) return;
     TetParams p = make_params(s, gx, gy, r0, img);
     StageScope t(DMR_STAGE_TET_FORWARD, st);
-    k_tet_forward<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
+    if (alpha) k_tet_forward<true><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
+    else k_tet_forward<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
 }
 
 // both gradient tensors zeroed by one launch (two hipMemsetAsync are three fill kernels of ~4.6 us each)
@@ -1231,26 +1252,33 @@ void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopac
     if (n > 0) k_tet_zero_grads<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(dL_dvcolor, n_vcolor, dL_dfopacity, n_fopacity);
 }
 
+// the two launches of launch_tet_backward for one variant (full...: nothing, or dL_dverts, dL_dfintense[, cam_part])
+template <bool ALPHA, class... Full>
+static void tet_backward_pair(const TetParams& p, int gx, int rows, int B, const float* dL_dcolor, const float* dL_ddepth,
+                              float* dL_dvcolor, float* dL_dfopacity, uint32_t* host_seq_steps, hipStream_t st, Full... full) {
+    const int ntiles = gx * rows * B;
+    k_tet_backward_seq<ALPHA, Full...><<<dim3(gx, rows, B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity,
+                                                                               host_seq_steps, full...);
+    k_tet_backward<ALPHA, Full...><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, rows, dL_dcolor, dL_ddepth, dL_dvcolor,
+                                                                                               dL_dfopacity, full...);
+}
+
 void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense, float* cam_part) {
+                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense, float* cam_part, bool alpha) {
     if (r1 <= r0) return;
     TetParams p = make_params(s, gx, gy, r0, img);
     StageScope t(DMR_STAGE_TET_BACKWARD, st);
-    const int ntiles = gx * (r1 - r0) * s.B;
+    const int rows = r1 - r0;
     if (cam_part) {
-        k_tet_backward_seq<float*, float*, float*><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(
-            p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, dL_dverts, dL_dfintense, cam_part);
-        k_tet_backward<float*, float*, float*><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(
-            p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, dL_dverts, dL_dfintense, cam_part);
+        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense, cam_part);
+        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense, cam_part);
     } else if (!dL_dverts) {
-        k_tet_backward_seq<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps);
-        k_tet_backward<><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity);
+        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st);
+        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st);
     } else {
-        k_tet_backward_seq<float*, float*><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity,
-                                                                             host_seq_steps, dL_dverts, dL_dfintense);
-        k_tet_backward<float*, float*><<<dim3((unsigned)std::min(ntiles, 768)), dim3(256), 0, st>>>(p, r1 - r0, dL_dcolor, dL_ddepth, dL_dvcolor,
-                                                                                         dL_dfopacity, dL_dverts, dL_dfintense);
+        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
+        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
     }
 }
 

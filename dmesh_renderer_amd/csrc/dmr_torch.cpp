@@ -255,14 +255,22 @@ template <class T> T* mptr(const at::Tensor& t) { return t.numel() ? reinterpret
 
 at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at::kFloat).device(dev); }
 
+// alpha=True (DMR_FLAG_ALPHA): the depth image carries a second channel, the accumulated opacity -- [B,2,H,W], depth | alpha
+void check_depth_alpha_grad(const at::Tensor& g, int64_t B, int64_t H, int64_t W, const char* name) {
+    if (g.dim() != 4 || g.size(0) != B || g.size(1) != 2 || g.size(2) != H || g.size(3) != W)
+        err(std::string(name) + " must have dimensions (B, 2, H, W) with alpha=True (channel 0 the depth's gradient, channel 1 "
+            "alpha's): (" + std::to_string(B) + ", 2, " + std::to_string(H) + ", " + std::to_string(W) + ") here");
+}
+
 // ---- the four functions of ext.cpp:6-11 -----------------------------------------------------------------------------
 // -> (num_rendered:int, color [B,3,H,W], depth [B,1,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
+//    alpha=True: the depth slot is [B,2,H,W], channel 1 the accumulated opacity alpha = 1 - T_final
 using TriFwdOut = std::tuple<int64_t, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
 TriFwdOut render_tris(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
                       const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                       const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                       const at::Tensor& faces_intense, int64_t image_height, int64_t image_width, std::pair<int, int> rows,
-                      bool fill_outside) {
+                      bool fill_outside, bool alpha) {
     check_common(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense, false);
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
@@ -274,7 +282,9 @@ TriFwdOut render_tris(const at::Tensor& background, const at::Tensor& verts, con
     const auto opt = f32_on(dev);
     at::Tensor color = full ? at::empty({call.sc.B, NUM_CHANNELS, image_height, image_width}, opt)
                             : at::zeros({call.sc.B, NUM_CHANNELS, image_height, image_width}, opt);
-    at::Tensor depth = full ? at::empty({call.sc.B, 1, image_height, image_width}, opt) : at::zeros({call.sc.B, 1, image_height, image_width}, opt);
+    const int64_t dch = alpha ? 2 : 1;
+    at::Tensor depth = full ? at::empty({call.sc.B, dch, image_height, image_width}, opt) : at::zeros({call.sc.B, dch, image_height, image_width}, opt);
+    if (alpha) call.sc.flags |= DMR_FLAG_ALPHA;
     int rendered = 0;
     // (the bindings release the GIL around this whole function: the default call waits for the size read-back)
     if (g_abi.tri_forward(&call.sc, mptr<float>(color), mptr<float>(depth), &alloc_cb, &call.scratch, call.stream(), &rendered)) raise_lib();
@@ -317,7 +327,7 @@ py::tuple render_tris_backward(const at::Tensor& background, const at::Tensor& v
                                const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
                                int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool exact_grads, bool camera_grads) {
+                               bool exact_grads, bool camera_grads, bool alpha) {
     std::optional<py::gil_scoped_release> nogil(std::in_place);  // (the default call waits for the size read-back)
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
@@ -328,6 +338,10 @@ py::tuple render_tris_backward(const at::Tensor& background, const at::Tensor& v
     const at::Tensor gc = f32(dL_dout_color, "dL_dout_color");  // may arrive non-contiguous / expanded (render.cu:197-198)
     const at::Tensor gd = f32(dL_dout_depth, "dL_dout_depth");
     const int64_t B = call.sc.B, P = call.sc.P, F = call.sc.F;
+    if (alpha) {
+        check_depth_alpha_grad(gd, B, H, W, "dL_dout_depth");
+        call.sc.flags |= DMR_FLAG_ALPHA;
+    }
     // camera grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16] is DMR_BUF_TRI_CAMERA_GRADS, served by alloc_cb from g[5]; with
     // flat_out it follows the default layout ([3P | 3P | F | BP | BF | 32B]), so one all-reduce still carries everything
     std::vector<std::vector<int64_t>> shapes = {{P, 3}, {P, NUM_CHANNELS}, {F}, {B, P}, {B, F}};
@@ -365,7 +379,7 @@ TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, con
                       const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
                       const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
                       const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets, const at::Tensor& tet_faces,
-                      int64_t image_height, int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows) {
+                      int64_t image_height, int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows, bool alpha) {
     check_common(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense, true);
     check_tets(faces, tets, face_tets, tet_faces);
     const c10::Device dev = hip_device_of(verts);
@@ -378,7 +392,8 @@ TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, con
     const auto opt = f32_on(dev);
     auto img = [&](at::IntArrayRef shape) { return full ? at::empty(shape, opt) : at::zeros(shape, opt); };
     at::Tensor color = img({call.sc.B, NUM_CHANNELS, image_height, image_width});
-    at::Tensor depth = img({call.sc.B, 1, image_height, image_width});
+    at::Tensor depth = img({call.sc.B, alpha ? 2 : 1, image_height, image_width});  // alpha=True: depth | alpha
+    if (alpha) call.sc.flags |= DMR_FLAG_ALPHA;
     at::Tensor active = img({call.sc.B, image_height, image_width});
     int rendered = 0;
     if (g_abi.tet_forward(&call.sc, mptr<float>(color), mptr<float>(depth), mptr<float>(active), &alloc_cb, &call.scratch, call.stream(), &rendered))
@@ -399,7 +414,7 @@ py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& v
                                const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
                                const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
                                const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool full_grads, bool camera_grads) {
+                               bool full_grads, bool camera_grads, bool alpha) {
     std::optional<py::gil_scoped_release> nogil(std::in_place);
     const c10::Device dev = hip_device_of(verts);
     c10::DeviceGuard guard(dev);
@@ -409,6 +424,10 @@ py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& v
               faces_intense, H, W, &tets, &face_tets, &tet_faces, 0, rows);
     const at::Tensor gc = f32(grad_color, "grad_color"), gd = f32(grad_depth, "grad_depth");
     const int64_t P = call.sc.P, F = call.sc.F, B = call.sc.B;
+    if (alpha) {
+        check_depth_alpha_grad(gd, B, H, W, "grad_depth");
+        call.sc.flags |= DMR_FLAG_ALPHA;
+    }
     // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from g[2].  With flat_out
     // the layout is [dL_dverts_color 3P | dL_dfaces_opacity F | dL_dverts 3P | dL_dfaces_intense BF]: the default layout
     // followed by that buffer, so one all-reduce still carries everything.
@@ -508,24 +527,25 @@ PYBIND11_MODULE(_C, m) {
     m.def("render_tris", &render_tris, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("image_height"), py::arg("image_width"),
-          py::arg("rows") = no_rows, py::arg("fill_outside") = true, py::call_guard<py::gil_scoped_release>());
+          py::arg("rows") = no_rows, py::arg("fill_outside") = true, py::kw_only(), py::arg("alpha") = false,
+          py::call_guard<py::gil_scoped_release>());
     m.def("render_tris_backward", &render_tris_backward, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"),
           py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"),
           py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("exact_grads") = false,
-          py::arg("camera_grads") = false);
+          py::arg("camera_grads") = false, py::arg("alpha") = false);
     m.def("render_tets", &render_tets, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
           py::arg("image_height"), py::arg("image_width"), py::arg("ray_random_seed"), py::arg("rows") = no_rows,
-          py::call_guard<py::gil_scoped_release>());
+          py::kw_only(), py::arg("alpha") = false, py::call_guard<py::gil_scoped_release>());
     m.def("render_tets_backward", &render_tets_backward, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
           py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
           py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
           py::arg("grad_color"), py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"),
           py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("full_grads") = false,
-          py::arg("camera_grads") = false);
+          py::arg("camera_grads") = false, py::arg("alpha") = false);
     m.def("invert_mats", &invert_mats);
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));

@@ -241,7 +241,9 @@ constexpr int FWD_WAVES = 6;
 // are visible to it behind a barrier) and for the backward.
 // (SORT == false: the lists were sorted by k_sort_tiles.  Frames of many tiles keep the chip busy in either kernel and the
 // separate sort is the cheaper one there -- C5, 262 144 tiles: 0.39 + 2.01 ms against 2.48 ms fused; dmr_api.hip decides.)
-template <bool SORT>
+// ALPHA (DMR_FLAG_ALPHA): out_depth is [B,2,H,W] -- channel 0 the depth, channel 1 the accumulated opacity 1 - T of the T the
+// pixel ends with (the value multiplied into the background): one more 4-byte store per pixel, nothing else changes.
+template <bool SORT, bool ALPHA = false>
 __global__ void __launch_bounds__(256, FWD_WAVES)
 k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ out_depth) {
     constexpr int WORDS = MASK_CHUNK / 32;
@@ -281,7 +283,12 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
             out_color[((int64_t)b * 3 + 0) * HW + pix_id] = 0.f + 1.0f * p.bg[0];
             out_color[((int64_t)b * 3 + 1) * HW + pix_id] = 0.f + 1.0f * p.bg[1];
             out_color[((int64_t)b * 3 + 2) * HW + pix_id] = 0.f + 1.0f * p.bg[2];
-            out_depth[bpix] = 0.f + 1.0f * 1.0f;
+            if constexpr (ALPHA) {
+                out_depth[((int64_t)b * 2 + 0) * HW + pix_id] = 0.f + 1.0f * 1.0f;
+                out_depth[((int64_t)b * 2 + 1) * HW + pix_id] = 0.f;
+            } else {
+                out_depth[bpix] = 0.f + 1.0f * 1.0f;
+            }
         }
         return;  // uniform
     }
@@ -400,7 +407,12 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
         out_color[((int64_t)b * 3 + 0) * HW + pix_id] = C0 + T * p.bg[0];
         out_color[((int64_t)b * 3 + 1) * HW + pix_id] = C1 + T * p.bg[1];
         out_color[((int64_t)b * 3 + 2) * HW + pix_id] = C2 + T * p.bg[2];
-        out_depth[bpix] = D + T * 1.0f;
+        if constexpr (ALPHA) {
+            out_depth[((int64_t)b * 2 + 0) * HW + pix_id] = D + T * 1.0f;
+            out_depth[((int64_t)b * 2 + 1) * HW + pix_id] = 1.0f - T;
+        } else {
+            out_depth[bpix] = D + T * 1.0f;
+        }
     }
 }
 
@@ -502,8 +514,11 @@ constexpr uint32_t HIT_SKIPPED = 0x80000000u;
 // here (HitRegions, dmr_kernels.hpp) -- tested at run time in that instantiation: with the test folded away the register
 // allocator spills 16 bytes at the kernel's 80-register cap (k_tri_backward_pix 89 -> 91-93 us at C4), as it is it does not;
 // the scanned instantiation without the other path's code is 3 % faster at C5 (2.66 -> 2.58 ms).
+// ALPHA (DMR_FLAG_ALPHA): dL_ddepth is [B,2,H,W], channel 1 the upstream gradient g_a of alpha = 1 - T_final.  d alpha / d opacity_i
+// = T_final / (1 - opacity_i) is minus the factor of the background terms, so -g_a joins bd_dot (which only enters that tail
+// term): one more 4-byte load per pixel, no register more in the loop; only this variant's summation order differs.
 constexpr int PIX_WAVES = 6;
-template <bool SCANNED>
+template <bool SCANNED, bool ALPHA = false>
 __global__ void __launch_bounds__(256, PIX_WAVES)
 k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                    float4* __restrict__ pixrec, HitRecord* __restrict__ hits, uint32_t capacity,
@@ -599,11 +614,17 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     const float prev_T_final = inside ? p.final_prev_T[bpix] : 0.f;
     const uint32_t last_contributor = inside ? p.n_contrib[bpix] : 0u;
     float dpc0 = 0, dpc1 = 0, dpc2 = 0, dpd = 0;
+    [[maybe_unused]] float dpa = 0;
     if (inside) {
         dpc0 = dL_dcolor[((int64_t)b * 3 + 0) * HW + pix_id];
         dpc1 = dL_dcolor[((int64_t)b * 3 + 1) * HW + pix_id];
         dpc2 = dL_dcolor[((int64_t)b * 3 + 2) * HW + pix_id];
-        dpd = dL_ddepth[bpix];
+        if constexpr (ALPHA) {
+            dpd = dL_ddepth[((int64_t)b * 2 + 0) * HW + pix_id];
+            dpa = dL_ddepth[((int64_t)b * 2 + 1) * HW + pix_id];
+        } else {
+            dpd = dL_ddepth[bpix];
+        }
     }
     // what kernel 2 needs of a pixel: ray direction and upstream gradient.  Tile-major (the tile's 256 pixels are 8 KB in a
     // row): kernel 2's workgroup stages them in LDS with coalesced loads instead of two 16-byte gathers per pair.
@@ -615,7 +636,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     // backward.cu:293-298 (loop invariant there)
     float bg_dot = 0.f;
     bg_dot += p.bg[0] * dpc0; bg_dot += p.bg[1] * dpc1; bg_dot += p.bg[2] * dpc2;
-    const float bd_dot = 0.f + (float)(1.0 * (double)dpd);
+    const float bd_dot = ALPHA ? (0.f + (float)(1.0 * (double)dpd)) - dpa : 0.f + (float)(1.0 * (double)dpd);
 
     if (tid == 0) s_max_last = 0;
     if (tid < MASK_CHUNK) s_fcnt[tid] = 0u;
@@ -1408,21 +1429,24 @@ static TriParams make_params(const dmr_scene& s, int gx, int gy, int r0, int r1,
 
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
-                        float* out_color, float* out_depth, hipStream_t st) {
+                        float* out_color, float* out_depth, hipStream_t st, bool alpha) {
     if (r1 <= r0) return;
     TriParams p = make_params(s, gx, gy, r0, r1, vproj, tile_offset, face_list, img);
     p.keys = reinterpret_cast<unsigned long long*>(keys);
     p.list_capacity = capacity;
     StageScope t(DMR_STAGE_TRI_FORWARD, st);
     const dim3 grid((unsigned)(s.B * gx * gy)), block(256);
-    if (keys) k_tri_forward<true><<<grid, block, 0, st>>>(p, out_color, out_depth);
+    if (alpha) {  // out_depth [B,2,H,W]: depth | alpha
+        if (keys) k_tri_forward<true, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
+        else k_tri_forward<false, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
+    } else if (keys) k_tri_forward<true><<<grid, block, 0, st>>>(p, out_color, out_depth);
     else k_tri_forward<false><<<grid, block, 0, st>>>(p, out_color, out_depth);
 }
 
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                              const uint32_t* tile_offset, const uint32_t* face_list, TriImageState img,
                              const float* dL_dcolor, const float* dL_ddepth, float4* pixrec, HitRecord* hits,
-                             uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st) {
+                             uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st, bool alpha) {
     // (an empty band never gets here: dmr_tri_backward zeroes the gradients itself -- this kernel is also what zeroes `work`)
     TriParams p = make_params(s, gx, gy, r0, r1, vproj, tile_offset, face_list, img);
     StageScope t(DMR_STAGE_TRI_BACKWARD, st);
@@ -1430,7 +1454,12 @@ void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1,
 #ifdef DMR_ABLATION
     if (DMR_DBG(p, 131072)) grid.x = std::min(grid.x, 3072u);  // timing experiment (results invalid): only the busiest tiles' workgroups
 #endif
-    if (regions.hit_offset)
+    if (alpha) {  // dL_ddepth [B,2,H,W]: dL/ddepth | dL/dalpha
+        if (regions.hit_offset)
+            k_tri_backward_pix<false, true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
+        else
+            k_tri_backward_pix<true, true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
+    } else if (regions.hit_offset)
         k_tri_backward_pix<false><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
     else
         k_tri_backward_pix<true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);

@@ -281,11 +281,12 @@ class _Shard(NamedTuple):
 
 
 class _ShardedTriViewFn(th.autograd.Function):
-    """The "view_bands" partition: this rank renders its segments (view, row_begin, row_end), one B = 1 call each."""
+    """The "view_bands" partition: this rank renders its segments (view, row_begin, row_end), one B = 1 call each.
+    alpha: as _TriFn's (the depth image and its gradient are [B,2,H,W], depth | alpha; the gathers carry any channel count)."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, segs, group, parts, impl, exact_grads=False, camera_grads=False):
+                settings: TriRenderSettings, segs, group, parts, impl, exact_grads=False, camera_grads=False, alpha=False):
         B = mv_mats.size(0)
         geom = (verts, faces, verts_color, faces_opacity)
         H, W = settings.image_height, settings.image_width
@@ -296,7 +297,7 @@ class _ShardedTriViewFn(th.autograd.Function):
         saved, nums, outs = [], [], []
         for (v, _, _), r in zip(segs, rows):
             num, color, depth, s = _tri_forward(impl, settings, geom, mv_mats[v:v + 1], proj_mats[v:v + 1],
-                                                verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous(), r)
+                                                verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous(), r, alpha)
             outs.append((color, depth))
             nums.append(num)
             saved += s
@@ -310,7 +311,7 @@ class _ShardedTriViewFn(th.autograd.Function):
                 color[v, :, y0:y1] = c[0, :, y0:y1]
                 depth[v, ..., y0:y1, :] = z[0, ..., y0:y1, :]
         ctx.settings, ctx.segs, ctx.rows, ctx.group, ctx.impl, ctx.nums = settings, tuple(segs), rows, group, impl, nums
-        ctx.exact_grads, ctx.camera_grads = exact_grads or camera_grads, camera_grads
+        ctx.exact_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved, *((mv_mats, proj_mats) if camera_grads else ()))
         return color, depth
 
@@ -338,7 +339,7 @@ class _ShardedTriViewFn(th.autograd.Function):
         g_mv = g_proj = None
         if camera:  # every view's inverses (a rank holds only its segments')
             g_mv, g_proj = _camera_grads(ctx, *_with_inverses(saved[-2], saved[-1])[2:], g[5][:, 0], g[5][:, 1])
-        return (g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4]) + (None,) * 7
+        return (g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4]) + (None,) * 8
 
 
 class _Banded:
@@ -371,16 +372,18 @@ class ShardedTriRenderer(_Banded, TriRenderer):
     """TriRenderer whose image is sharded across the ranks of `group`: by tile-row bands of all views ("bands") or, with
     several views, by (view, band) pairs ("view_bands"; see the module docstring).
 
-    Same call signature as TriRenderer, and the same exact_grads / camera_grads options (with camera_grads the flat
-    all-reduce payload gains [B][dL/dinv_mv 16 | dL/dinv_proj 16]).  Every rank must pass identical inputs; every rank
+    Same call signature as TriRenderer, and the same exact_grads / camera_grads / return_alpha options (with camera_grads
+    the flat all-reduce payload gains [B][dL/dinv_mv 16 | dL/dinv_proj 16]; return_alpha adds no gradient tensor: alpha
+    travels as a second channel of the depth image).  Every rank must pass identical inputs; every rank
     gets the full summed gradients.  The bands may be refreshed at any time with `set_row_work` (e.g. every few
     iterations from `row_work_from_ranges` / `view_row_work_from_ranges`)."""
 
     def __init__(self, render_settings: TriRenderSettings, group=None, assemble: bool = True, impl=None, partition: str = "auto",
-                 exact_grads: bool = False, camera_grads: bool = False):
+                 exact_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False):
         if partition not in ("auto", "bands", "view_bands"):
             raise ValueError("partition must be 'auto', 'bands' or 'view_bands'")
-        super().__init__(render_settings, group, assemble, impl, exact_grads=exact_grads, camera_grads=camera_grads)
+        super().__init__(render_settings, group, assemble, impl, exact_grads=exact_grads, camera_grads=camera_grads,
+                         return_alpha=return_alpha)
         self.partition = partition
         self.view_work = None   # "view_bands": [B, rows] work of the (view, tile row) sequence; None: every row counts the same
         self.segment_cost_per_face = SEGMENT_COST_PER_FACE  # (SEGMENT_COST_PER_FACE_WITH_PAIRS when the row work counts blended pairs)
@@ -419,7 +422,7 @@ class ShardedTriRenderer(_Banded, TriRenderer):
         parts = self.view_parts(B, F)
         return _ShardedTriViewFn.apply(*inputs, self.render_settings, tuple(parts[self.rank]), self.group,
                                        tuple(tuple(p) for p in parts) if self.assemble else None, self.impl,
-                                       self.exact_grads, self.camera_grads)
+                                       self.exact_grads, self.camera_grads, self.return_alpha)
 
 
 class ShardedTetRenderer(_Banded, TetRenderer):
@@ -428,8 +431,9 @@ class ShardedTetRenderer(_Banded, TetRenderer):
     its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F]
     (full_grads: followed by [dL_dverts 3P | dL_dfaces_intense B*F], camera_grads: then by the 64 B matrix gradients,
     see TetRenderer).
-    Same call signature and outputs as TetRenderer (color, depth, active bool)."""
+    Same call signature and outputs as TetRenderer (color, depth, active bool; with return_alpha also alpha)."""
 
     def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
-                 full_grads: bool = False, camera_grads: bool = False):
-        super().__init__(render_settings, group, assemble, impl, full_grads=full_grads, camera_grads=camera_grads)
+                 full_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False):
+        super().__init__(render_settings, group, assemble, impl, full_grads=full_grads, camera_grads=camera_grads,
+                         return_alpha=return_alpha)

@@ -123,6 +123,16 @@ typedef struct dmr_scene {
 /* dmr_tet_backward also computes the gradients of the four matrices (implies DMR_FLAG_TET_FULL_GRADS); see there.
  * Ignored by every other call. */
 #define DMR_FLAG_TET_CAMERA_GRADS 16
+/* All four calls: the depth image has a second channel, the accumulated opacity (coverage) alpha = 1 - T_final, T_final the
+ * transmittance the call multiplies into the background (color == C + (1 - alpha) * background per pixel).  out_depth and
+ * dL_ddepth are then [B,2,H,W]: channel 0 the depth as without the flag, channel 1 alpha / its upstream gradient.  alpha is 0
+ * where nothing was blended, where a tet pixel's march fails (out_active == 0) and, like the other images, untouched outside
+ * the rendered tile rows (the caller zero-initialises).  d alpha / d opacity_i = T_final / (1 - opacity_i) for every blended
+ * face i of the pixel (prev_T_final for a face of opacity 1, as for the background terms); alpha depends on nothing else, so
+ * the upstream gradient reaches dL_dfopacity only, whatever other gradient flags are set.  No new buffer, no host wait
+ * (DMR_FLAG_ASYNC and stream capture work as before); colour and depth are bit for bit those of a call without the flag.
+ * Forward and backward of a step must agree on the flag only in the shapes they pass: the scratch buffers are the same. */
+#define DMR_FLAG_ALPHA 32
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -131,7 +141,7 @@ int dmr_overflowed(int device, int reset);
  * kept per view configuration and power-of-two bucket of B * F). */
 uint64_t dmr_redo_count(void);
 
-/* out_color [B,3,H,W], out_depth [B,1,H,W]: every pixel of the rendered tile rows is written; the caller
+/* out_color [B,3,H,W], out_depth [B,1,H,W] ([B,2,H,W] with DMR_FLAG_ALPHA: depth | alpha): every pixel of the rendered tile rows is written; the caller
  * zero-initialises them (render.cu:88-89) when a band leaves rows untouched or when P == 0 / F == 0
  * (nothing is launched, render.cu:105).  *num_rendered receives R = sum of tiles touched. */
 int dmr_tri_forward(const dmr_scene* scene, float* out_color, float* out_depth,
@@ -147,7 +157,8 @@ int dmr_tri_forward(const dmr_scene* scene, float* out_color, float* out_depth,
  * the inverse matrices through every pixel's ray (origin = inv_mv's translation column, direction
  * normalize(inv_mv (inv_proj (ndc, -1, 1)).xyz - origin) with no w divide); their w rows are 0.  dL_dvdepth does not
  * involve the matrices.  No host wait is added (DMR_FLAG_ASYNC and stream capture work as without the flags).  Without
- * the flags the call is exactly as before and requests no buffer beyond the work space. */
+ * the flags the call is exactly as before and requests no buffer beyond the work space.
+ * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term. */
 int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      int num_rendered, const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,
@@ -156,7 +167,8 @@ int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float
                      dmr_alloc_fn alloc, void* alloc_ctx, void* stream);
 
 /* out_active [B,H,W]: 1.0 where the ray marched to a valid end, else 0.0.  Like the tri forward, every pixel of the
- * rendered tile rows of all three outputs is written (background / 1 / 0 where the march fails). */
+ * rendered tile rows of all three outputs is written (background / 1 / 0 where the march fails).  With DMR_FLAG_ALPHA
+ * out_depth is [B,2,H,W] (depth | alpha; alpha 0 where the march fails). */
 int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, float* out_active,
                     dmr_alloc_fn alloc, void* alloc_ctx, void* stream, int* num_rendered);
 
@@ -173,7 +185,8 @@ int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, 
  * pixel's ray (origin = inv_mv's translation column, direction normalize(inv_mv (inv_proj (ndc, -1, 1)).xyz - origin) with
  * no w divide and the length clamped to 1e-4, the seeded jitter held fixed); mv and proj through the ndc depth of each
  * marched face's hit point (rows 0-2 of mv, rows 2-3 of proj).  The w rows of the inverses get 0.  Per-tile partials go to
- * a DMR_BUF_WORK request.  No host wait is added.  Without the flags the call is exactly as before and requests no buffer. */
+ * a DMR_BUF_WORK request.  No host wait is added.  Without the flags the call is exactly as before and requests no buffer.
+ * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term. */
 int dmr_tet_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,
