@@ -13,6 +13,7 @@ pass transposed views down (:219-220, :476-477); _TriFn / _TetFn invert those
 from __future__ import annotations
 
 import math
+from operator import itemgetter
 from typing import List, NamedTuple, Optional, Tuple
 
 import torch as th
@@ -86,37 +87,85 @@ def _split_alpha(out):
     return (out[0], out[1][:, :1], *out[2:], out[1][:, 1:])
 
 
-def _tri_forward(impl, settings: TriRenderSettings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows, alpha=False):
-    """One render_tris call -> (num_rendered, color, depth, what its backward needs after geom: the matrices, their
-    inverses, verts_depth, faces_intense and the four scratch buffers).  alpha: depth is [B,2,H,W], depth | alpha."""
+def _impl(shard):
+    """The kernels of a Function: `_C` as it is at call time on one device (tests swap it), a sharded Module's otherwise."""
+    return _C if shard is None else shard.impl
+
+
+def _forward(render, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows, alpha=False, topo=()):
+    """One render_tris / render_tets (with topo) call -> (its three results: num_rendered, color, depth / color, depth,
+    active; what its backward needs after geom: the matrices, their inverses, verts_depth, faces_intense, topo and the four
+    scratch buffers).  alpha: depth is [B,2,H,W], depth | alpha."""
     cams = _with_inverses(mv_mats, proj_mats)
-    try:
-        out = impl.render_tris(settings.bg, *geom, *cams, verts_depth, faces_intense,
-                               settings.image_height, settings.image_width, rows=rows, **_alpha_kw(alpha))
+    try:  # (settings[3:]: the tet settings' ray_random_seed)
+        out = render(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo, settings.image_height, settings.image_width,
+                     *settings[3:], rows=rows, **_alpha_kw(alpha))
     except Exception as ex:
         print("\nAn error occured in forward.")
-        print(ex)
+        if not topo:  # (as the reference: its tri wrapper prints the exception, its tet wrapper does not)
+            print(ex)
         raise
-    return out[0], out[1], out[2], (*cams, verts_depth, faces_intense, *out[3:7])
+    return out[:3], (*cams, verts_depth, faces_intense, *topo, *out[3:7])
 
 
-def _tri_backward(impl, settings: TriRenderSettings, geom, saved, grad_color, grad_depth, num_rendered, rows, kw):
-    """One render_tris_backward call for a _tri_forward."""
+def _one_backward(render_backward, settings, geom, saved, upstream, rows, kw):
+    """One render_tris_backward / render_tets_backward call for a _forward: upstream = (grad_color, grad_depth) and, tri,
+    num_rendered."""
     try:
-        return impl.render_tris_backward(settings.bg, *geom, *saved[:6], grad_color, grad_depth, num_rendered, *saved[6:],
-                                         rows=rows, **kw)
+        return render_backward(settings.bg, *geom, *saved[:-4], *upstream, *saved[-4:], rows=rows, **kw)
     except Exception:
         print("\nAn error occured in backward.\n")
         raise
 
 
-def _tri_grad_options(ctx) -> Tuple[bool, dict]:
-    """(camera, keywords of render_tris_backward).  The matrices' gradients are computed only when asked for and a matrix
-    needs one: otherwise the exact variant, which skips the per-pixel ray sums.  No keyword by default: the reference's
-    call.  (A fresh dict: the caller may add flat_out.)  With ctx.alpha also alpha=True: grad_depth is [B,2,H,W]."""
+class _GradSet:
+    """The gradient set of one renderer, stated once for _TriFn, _TetFn and sharding._ShardedTriViewFn.  (GradTable in
+    csrc/dmr_torch.cpp states the same for `_C`; the two meet in flat_out, whose size the binding checks.)  A backward has a
+    level: 0 the reference's gradients, 1 exact_grads (tri) / full_grads (tet), 2 camera_grads, which implies level 1.
+    backward: its name in `_C`; level_kw: its keyword of level 1.
+    shapes: (P, F, B) -> the shapes of the pieces of the flat buffer (what flat_out= receives, the payload of the one all-reduce),
+    in its order; the last is the camera piece, [B, n, 4, 4]: n matrix gradients per view.
+    order: per level, the pieces it holds but the camera one (level 2 only) in the order of the backward's tuple; the camera
+    piece's n [B,4,4] slices follow.
+    inputs: per piece but the camera one, the argument of apply it is the gradient of (the camera piece reaches arguments 4 and
+    5, mv_mats and proj_mats, through _camera_grads).
+    pick: per level, (*that tuple's gradients, dL/dmv, dL/dproj, None) -> the gradients of apply's eight tensors."""
+
+    def __init__(self, backward: str, level_kw: str, shapes, inputs, order):
+        self.backward, self.level_kw, self.shapes, self.order, self.pick = backward, level_kw, shapes, order, []
+        for o in order:
+            at = [len(o) + 2] * 8  # None
+            at[4], at[5] = len(o), len(o) + 1
+            for k, piece in enumerate(o):
+                at[inputs[piece]] = k
+            self.pick.append(itemgetter(*at))
+
+
+# [3P | 3P | F | BP | BF], with camera grads followed by [B][dL/dinv_mv 16 | dL/dinv_proj 16]
+_TRI_GRADS = _GradSet("render_tris_backward", "exact_grads", lambda P, F, B: ((P, 3), (P, 3), (F,), (B, P), (B, F), (B, 2, 4, 4)),
+                      inputs=(0, 2, 3, 6, 7), order=((0, 1, 2, 3, 4),) * 3)
+# [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense BF], with camera
+# grads then by [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16]
+_TET_GRADS = _GradSet("render_tets_backward", "full_grads", lambda P, F, B: ((P, 3), (F,), (P, 3), (B, F), (B, 4, 4, 4)),
+                      inputs=(2, 3, 0, 7), order=((0, 1), (2, 0, 1, 3), (2, 0, 1, 3)))
+
+
+def _grad_options(ctx, gs: _GradSet) -> Tuple[int, dict]:
+    """(level, keywords of the backward).  The matrices' gradients are computed only when asked for and a matrix needs one:
+    otherwise level 1, which skips the per-pixel ray sums.  No keyword by default: the reference's call.  (A fresh dict: the
+    caller may add flat_out.)  With ctx.alpha also alpha=True: grad_depth is [B,2,H,W]."""
     if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
-        return True, {"camera_grads": True, **_alpha_kw(ctx.alpha)}
-    return False, {**({"exact_grads": True} if ctx.exact_grads else {}), **_alpha_kw(ctx.alpha)}
+        return 2, {"camera_grads": True, **_alpha_kw(ctx.alpha)}
+    return int(ctx.more_grads), {**({gs.level_kw: True} if ctx.more_grads else {}), **_alpha_kw(ctx.alpha)}
+
+
+def _flat(gs: _GradSet, level: int, P: int, F: int, B: int, device, alloc=th.empty) -> Tuple[th.Tensor, List[th.Tensor]]:
+    """The flat gradient buffer of a backward (what flat_out= fills) and its pieces as views of their shapes."""
+    shapes = gs.shapes(P, F, B)
+    shapes = shapes[:len(gs.order[level])] + shapes[-1:] * (level == 2)
+    sizes = [math.prod(s) for s in shapes]
+    flat = alloc(sum(sizes), dtype=th.float32, device=device)
+    return flat, [p.view(s) for p, s in zip(flat.split(sizes), shapes)]
 
 
 def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj, g_mv=None,
@@ -131,21 +180,26 @@ def _camera_grads(ctx, inv_mv, inv_proj, g_inv_mv, g_inv_proj, g_mv=None,
     return one(4, inv_mv, g_inv_mv, g_mv), one(5, inv_proj, g_inv_proj, g_proj)
 
 
-def _tet_grad_options(ctx) -> Tuple[bool, dict]:
-    """(camera, keywords of render_tets_backward), decided as _tri_grad_options does: the camera variant only when asked
-    for and a matrix needs a gradient, else the full one, else no keyword (the reference's call)."""
-    if ctx.camera_grads and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
-        return True, {"camera_grads": True, **_alpha_kw(ctx.alpha)}
-    return False, {**({"full_grads": True} if ctx.full_grads else {}), **_alpha_kw(ctx.alpha)}
+def _input_grads(ctx, gs: _GradSet, level: int, g, inv_mv, inv_proj) -> tuple:
+    """A backward's tuple `g` -> the gradients of apply's eight tensors (None where there is none)."""
+    k = len(gs.order[level])
+    mats = _camera_grads(ctx, inv_mv, inv_proj, *g[k:]) if level == 2 else (None, None)
+    return gs.pick[level]((*g[:k], *mats, None))
 
 
-def _tri_flat(P: int, F: int, B: int, camera: bool, device, alloc=th.empty) -> Tuple[th.Tensor, List[th.Tensor]]:
-    """The flat tri gradient buffer [3P | 3P | F | B*P | B*F], with camera grads followed by [B][dL/dinv_mv 16 |
-    dL/dinv_proj 16] (what render_tris_backward(flat_out=) fills), and its pieces as views shaped like the gradients."""
-    shapes = [(P, 3), (P, 3), (F,), (B, P), (B, F)] + ([(B, 2, 4, 4)] if camera else [])
-    sizes = [math.prod(s) for s in shapes]
-    flat = alloc(sum(sizes), dtype=th.float32, device=device)
-    return flat, [p.view(s) for p, s in zip(flat.split(sizes), shapes)]
+def _backward(ctx, gs: _GradSet, *upstream) -> tuple:
+    """The backward of _TriFn / _TetFn: one _one_backward at ctx's level, the all-reduce of a sharded Module, the gradients of
+    apply's eight tensors."""
+    saved = ctx.saved_tensors
+    geom, saved = saved[:4], saved[4:]
+    level, kw = _grad_options(ctx, gs)
+    shard, flat = ctx.shard, None
+    if shard is not None and shard.flat_out:  # the gradients land back to back in the all-reduce payload
+        flat = kw["flat_out"] = _flat(gs, level, geom[0].size(0), geom[1].size(0), saved[0].size(0), geom[0].device)[0]
+    g = _one_backward(getattr(_impl(shard), gs.backward), ctx.settings, geom, saved, upstream, ctx.rows, kw)
+    if shard is not None:
+        g = shard.reduce(g, flat)
+    return _input_grads(ctx, gs, level, g, saved[2], saved[3])
 
 
 class _TriFn(th.autograd.Function):
@@ -153,37 +207,25 @@ class _TriFn(th.autograd.Function):
     exact_grads, camera_grads, alpha (the last four only when set: see _trailing).  Gradients flow to verts, verts_color,
     faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  alpha: the
     second output is [B,2,H,W], depth | alpha (the caller slices it: _split_alpha), and so is its gradient.  shard: None
-    on one device (the kernels are then `_C` as it is at call time: tests swap it); from a sharded Module
-    (sharding._Shard) its kernels, the band images to assemble and the gradients' all-reduce."""
+    on one device; from a sharded Module (sharding._Shard) its kernels, the band images to assemble and the gradients'
+    all-reduce."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False):
-        impl = _C if shard is None else shard.impl
         geom = (verts, faces, verts_color, faces_opacity)
-        num_rendered, color, depth, saved = _tri_forward(impl, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense,
-                                                         rows, alpha)
+        (num_rendered, color, depth), saved = _forward(_impl(shard).render_tris, settings, geom, mv_mats, proj_mats, verts_depth,
+                                                       faces_intense, rows, alpha)
         if shard is not None:
             color, depth = shard.gather((color, depth))
         ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
-        ctx.exact_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
+        ctx.more_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved)
         return color, depth
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
-        saved = ctx.saved_tensors
-        geom, saved = saved[:4], saved[4:]
-        camera, kw = _tri_grad_options(ctx)
-        shard, flat = ctx.shard, None
-        impl = _C if shard is None else shard.impl
-        if shard is not None and shard.flat_out:  # the gradients land back to back in the all-reduce payload
-            flat = kw["flat_out"] = _tri_flat(geom[0].size(0), geom[1].size(0), saved[0].size(0), camera, geom[0].device)[0]
-        g = _tri_backward(impl, ctx.settings, geom, saved, grad_color, grad_depth, ctx.num_rendered, ctx.rows, kw)
-        if shard is not None:
-            g = shard.reduce(g, flat)
-        g_mv, g_proj = _camera_grads(ctx, saved[2], saved[3], g[5], g[6]) if camera else (None, None)
-        return g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4], None, None, None, None, None, None
+        return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered) + (None,) * 6
 
 
 class _TetFn(th.autograd.Function):
@@ -194,50 +236,21 @@ class _TetFn(th.autograd.Function):
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False,
                 alpha=False):
-        impl = _C if shard is None else shard.impl
-        cams = _with_inverses(mv_mats, proj_mats)
         geom = (verts, faces, verts_color, faces_opacity)
-        topo = (tets, face_tets, tet_faces)
-        try:
-            out = impl.render_tets(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo,
-                                   settings.image_height, settings.image_width, settings.ray_random_seed, rows=rows,
-                                   **_alpha_kw(alpha))
-        except Exception:
-            print("\nAn error occured in forward.")
-            raise
-        color, depth, active = out[0], out[1], out[2]
+        (color, depth, active), saved = _forward(_impl(shard).render_tets, settings, geom, mv_mats, proj_mats, verts_depth,
+                                                 faces_intense, rows, alpha, (tets, face_tets, tet_faces))
         if shard is not None:
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
         ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
-        ctx.full_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads, camera_grads, alpha
-        ctx.save_for_backward(*geom, *cams, verts_depth, faces_intense, *topo, *out[3:7])
+        ctx.more_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads, camera_grads, alpha
+        ctx.save_for_backward(*geom, *saved)
         ctx.mark_non_differentiable(active)
         return color, depth, active
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth, _grad_active):
-        saved = ctx.saved_tensors
-        camera, kw = _tet_grad_options(ctx)
-        shard, flat = ctx.shard, None
-        impl = _C if shard is None else shard.impl
-        if shard is not None and shard.flat_out:
-            # [dL_dverts_color 3P | dL_dfaces_opacity F], with full_grads followed by [dL_dverts 3P | dL_dfaces_intense B*F],
-            # with camera_grads then by [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16]
-            P, F, B = saved[0].size(0), saved[1].size(0), saved[4].size(0)
-            flat = kw["flat_out"] = th.empty(3 * P + F + (3 * P + B * F if ctx.full_grads else 0) + (64 * B if camera else 0),
-                                             dtype=th.float32, device=saved[0].device)
-        try:
-            g = impl.render_tets_backward(ctx.settings.bg, *saved[:13], grad_color, grad_depth, *saved[13:17],
-                                          rows=ctx.rows, **kw)
-        except Exception:
-            print("\nAn error occured in backward.\n")
-            raise
-        if shard is not None:
-            g = shard.reduce(g, flat)
-        g_verts, g_vcolor, g_fopacity, g_fintense = g[:4] if ctx.full_grads else (None, *g, None)
-        g_mv, g_proj = _camera_grads(ctx, saved[6], saved[7], *g[4:8]) if camera else (None, None)
-        return (g_verts, None, g_vcolor, g_fopacity, g_mv, g_proj, None, g_fintense) + (None,) * 9
+        return _backward(ctx, _TET_GRADS, grad_color, grad_depth) + (None,) * 9
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,

@@ -32,6 +32,19 @@ int fail(const std::string& m) { g_err = m; return 1; }
         if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+// An output the caller provides through `alloc` (the DMR_BUF_* ids beyond the work space), requested once; not at all when
+// bytes == 0 (flag not set, or an empty output).  idle: nothing to back-propagate: zeroed here, and *out stays null.
+int caller_output(dmr_alloc_fn alloc, void* ctx, int which, size_t bytes, const char* what, bool idle, hipStream_t st, float** out) {
+    *out = nullptr;
+    if (bytes == 0) return 0;
+    if (!alloc) return fail("null argument");
+    float* p = static_cast<float*>(alloc(ctx, which, bytes));
+    if (!p) return fail(std::string("allocation of the ") + what + " buffer failed");
+    if (idle) DMR_HIP(hipMemsetAsync(p, 0, bytes, st));
+    else *out = p;
+    return 0;
+}
+
 constexpr size_t ALIGN = 256;
 inline size_t up(size_t n) { return (n + ALIGN - 1) & ~(ALIGN - 1); }
 
@@ -511,16 +524,12 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     // [B][dL/dinv_mv 16 | dL/dinv_proj 16] buffer, requested once
     const bool camera = (s->flags & DMR_FLAG_TRI_CAMERA_GRADS) != 0;
     const int grads = camera ? dmr::TRI_GRAD_CAMERA : ((s->flags & DMR_FLAG_TRI_EXACT_GRADS) ? dmr::TRI_GRAD_EXACT : dmr::TRI_GRAD_REF);
-    float* cam_out = nullptr;
-    if (camera && s->B > 0) {
-        if (!alloc) return fail("null argument");
-        cam_out = static_cast<float*>(alloc(ctx, DMR_BUF_TRI_CAMERA_GRADS, 128 * (size_t)s->B));
-        if (!cam_out) return fail("allocation of the tri camera gradient buffer failed");
-    }
     // Nothing to back-propagate: no geometry (render.cu:173), nothing on screen, or an empty tile-row band (a rank without
     // rows; the asynchronous forward of such a band returns its capacity as num_rendered, hence the band test of its own).
-    if (s->P == 0 || s->F == 0 || num_rendered <= 0 || d.r1 <= d.r0) {
-        if (cam_out) DMR_HIP(hipMemsetAsync(cam_out, 0, 128 * (size_t)s->B, st));
+    const bool idle = s->P == 0 || s->F == 0 || num_rendered <= 0 || d.r1 <= d.r0;
+    float* cam_out = nullptr;
+    if (caller_output(alloc, ctx, DMR_BUF_TRI_CAMERA_GRADS, camera ? 128 * (size_t)s->B : 0, "tri camera gradient", idle, st, &cam_out)) return 1;
+    if (idle) {
         if (s->P > 0) {
             DMR_HIP(hipMemsetAsync(dL_dverts, 0, sizeof(float) * 3 * (size_t)s->P, st));
             DMR_HIP(hipMemsetAsync(dL_dvcolor, 0, sizeof(float) * 3 * (size_t)s->P, st));
@@ -620,28 +629,19 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     // DMR_FLAG_TET_CAMERA_GRADS (implies the full gradients): the caller's [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 |
     // dL/dproj 16] buffer, requested once, summed from per-tile partials in the work space
     const bool camera = (s->flags & DMR_FLAG_TET_CAMERA_GRADS) != 0;
-    float* cam_out = nullptr;
-    if (camera && s->B > 0) {
-        if (!alloc) return fail("null argument");
-        cam_out = static_cast<float*>(alloc(ctx, DMR_BUF_TET_CAMERA_GRADS, 256 * (size_t)s->B));
-        if (!cam_out) return fail("allocation of the tet camera gradient buffer failed");
-    }
-    float* full = nullptr;  // DMR_FLAG_TET_FULL_GRADS: [dL_dverts 3P | dL_dfintense BF], requested from the caller
-    if ((s->flags & (DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS)) && 3 * (int64_t)s->P + (int64_t)d.BF > 0) {
-        if (!alloc) return fail("null argument");
-        const int64_t n = 3 * (int64_t)s->P + (int64_t)d.BF;
-        full = static_cast<float*>(alloc(ctx, DMR_BUF_TET_GRADS, (size_t)n * sizeof(float)));
-        if (!full) return fail("allocation of the tet gradient buffer failed");
-        dmr::launch_tet_zero_grads(full, 3 * (int64_t)s->P, full + 3 * (int64_t)s->P, (int64_t)d.BF, st);
-    }
-    dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
     // the camera gradients of a call with nothing to back-propagate (no geometry, or an empty tile-row band: a rank without
     // rows) are zeros
     const int band_tiles = d.gx * (d.r1 - d.r0);  // per view
-    if (cam_out && (s->P == 0 || s->F == 0 || band_tiles == 0)) {
-        DMR_HIP(hipMemsetAsync(cam_out, 0, 256 * (size_t)s->B, st));
-        cam_out = nullptr;
-    }
+    float* cam_out = nullptr;
+    if (caller_output(alloc, ctx, DMR_BUF_TET_CAMERA_GRADS, camera ? 256 * (size_t)s->B : 0, "tet camera gradient",
+                      s->P == 0 || s->F == 0 || band_tiles == 0, st, &cam_out))
+        return 1;
+    float* full = nullptr;  // DMR_FLAG_TET_FULL_GRADS: [dL_dverts 3P | dL_dfintense BF], zeroed by the launch that follows
+    const bool full_grads = (s->flags & (DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS)) != 0;
+    if (caller_output(alloc, ctx, DMR_BUF_TET_GRADS, full_grads ? sizeof(float) * (3 * (size_t)s->P + d.BF) : 0, "tet gradient", false, st, &full))
+        return 1;
+    if (full) dmr::launch_tet_zero_grads(full, 3 * (int64_t)s->P, full + 3 * (int64_t)s->P, (int64_t)d.BF, st);
+    dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
     if (s->P == 0 || s->F == 0) return 0;
     if (!image_buf || !face_buf) return fail("null scratch buffer");
     float* cam_part = nullptr;  // every tile's partial (launch_tet_backward)

@@ -135,9 +135,16 @@ std::pair<at::Tensor, int> mat(const at::Tensor& t, const char* name) {
     return {t.contiguous(), 0};
 }
 
-void check_common(const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                  const at::Tensor& faces_opacity, const at::Tensor& mv, const at::Tensor& proj, const at::Tensor& inv_mv,
-                  const at::Tensor& inv_proj, const at::Tensor& verts_depth, const at::Tensor& faces_intense, bool tet) {
+using In = const at::Tensor&;
+
+// The tensors every render_* function starts with (and the tet renderer's three more, else null).
+struct Inputs {
+    In background, verts, faces, verts_color, faces_opacity, mv, proj, inv_mv, inv_proj, verts_depth, faces_intense;
+    const at::Tensor *tets = nullptr, *face_tets = nullptr, *tet_faces = nullptr;
+};
+
+void check_common(const Inputs& in, bool tet) {
+    const auto& [bg, verts, faces, verts_color, faces_opacity, mv, proj, inv_mv, inv_proj, verts_depth, faces_intense, tets, face_tets, tet_faces] = in;
     // messages: render.cu:49-79 (tri) and :237-267 (tet)
     if (verts.dim() != 2 || verts.size(1) != 3) err("verts must have dimensions (num_points, 3)");
     if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
@@ -167,6 +174,11 @@ void check_common(const at::Tensor& verts, const at::Tensor& faces, const at::Te
     for (auto& m : batched)
         if (m.first->size(0) != B)  // the reference would read out of bounds here
             err(std::string(m.second) + " must have the batch size of mv_mats (" + std::to_string(B) + ")");
+    if (!tet) return;
+    // render.cu:269-277
+    if (tets->dim() != 2 || tets->size(1) != 4) err("tets must have dimensions (num_tets, 4)");
+    if (face_tets->dim() != 2 || face_tets->size(0) != faces.size(0) || face_tets->size(1) != 2) err("face_tets must have dimensions (num_faces, 2)");
+    if (tet_faces->dim() != 2 || tet_faces->size(0) != tets->size(0) || tet_faces->size(1) != 4) err("tet_faces must have dimensions (num_tets, 4)");
 }
 
 c10::Device hip_device_of(const at::Tensor& verts) {
@@ -176,14 +188,14 @@ c10::Device hip_device_of(const at::Tensor& verts) {
     return verts.device();
 }
 
-// the caller-owned scratch buffers of one call: the C equivalent of the reference's four resizeFunctional lambdas
-// (render.cu:18-24,91-100), plus the backward's transient workspace
+at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at::kFloat).device(dev); }
+
+// the caller-owned buffers of one call, by DMR_BUF_* id.  Up to DMR_BUF_WORK scratch, allocated on request: the C equivalent of
+// the reference's four resizeFunctional lambdas (render.cu:18-24,91-100), plus the backward's transient workspace.  Beyond it
+// the gradient outputs the library asks for (GradTable::from): tensors the backward has put here for the library to fill.
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, 7> buf;
-    at::Tensor tet_grads;  // where DMR_BUF_TET_GRADS is served from (an output, not scratch), if defined
-    at::Tensor tri_cam;    // where DMR_BUF_TRI_CAMERA_GRADS is served from (an output), if defined
-    at::Tensor tet_cam;    // where DMR_BUF_TET_CAMERA_GRADS is served from (an output), if defined
+    std::array<at::Tensor, DMR_BUF_TET_CAMERA_GRADS + 1> buf;
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -191,10 +203,9 @@ struct Scratch {
 };
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
-    if (which < 0 || which > DMR_BUF_TET_CAMERA_GRADS) return nullptr;
-    if (which == DMR_BUF_TET_GRADS || which == DMR_BUF_TRI_CAMERA_GRADS || which == DMR_BUF_TET_CAMERA_GRADS) {
-        // the caller's gradient tensor, which the library fills
-        const at::Tensor& t = which == DMR_BUF_TET_GRADS ? s->tet_grads : (which == DMR_BUF_TRI_CAMERA_GRADS ? s->tri_cam : s->tet_cam);
+    if (which < 0 || which >= (int)s->buf.size()) return nullptr;
+    if (which > DMR_BUF_WORK) {  // the caller's gradient tensor, which the library fills
+        const at::Tensor& t = s->buf[which];
         return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
     }
     try {
@@ -215,11 +226,8 @@ struct Call {
     template <class T>
     const T* ptr(const at::Tensor& t) { keep.push_back(t); return t.numel() ? reinterpret_cast<const T*>(t.data_ptr()) : nullptr; }
 
-    Call(c10::Device dev_, const at::Tensor& bg, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-         const at::Tensor& faces_opacity, const at::Tensor& mv, const at::Tensor& proj, const at::Tensor& inv_mv,
-         const at::Tensor& inv_proj, const at::Tensor& verts_depth, const at::Tensor& faces_intense, int64_t H, int64_t W,
-         const at::Tensor* tets, const at::Tensor* face_tets, const at::Tensor* tet_faces, int64_t seed, std::pair<int, int> rows)
-        : dev(dev_), scratch(dev_) {
+    Call(c10::Device dev_, const Inputs& in, int64_t H, int64_t W, int64_t seed, std::pair<int, int> rows) : dev(dev_), scratch(dev_) {
+        const auto& [bg, verts, faces, verts_color, faces_opacity, mv, proj, inv_mv, inv_proj, verts_depth, faces_intense, tets, face_tets, tet_faces] = in;
         keep.reserve(16);
         auto m0 = mat(mv, "mv_mats"), m1 = mat(proj, "proj_mats"), m2 = mat(inv_mv, "inv_mv_mats"), m3 = mat(inv_proj, "inv_proj_mats");
         if (bg.numel() < NUM_CHANNELS) err("background must have 3 channels");
@@ -253,214 +261,198 @@ struct Call {
 
 template <class T> T* mptr(const at::Tensor& t) { return t.numel() ? reinterpret_cast<T*>(t.data_ptr()) : nullptr; }
 
-at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at::kFloat).device(dev); }
-
-// alpha=True (DMR_FLAG_ALPHA): the depth image carries a second channel, the accumulated opacity -- [B,2,H,W], depth | alpha
-void check_depth_alpha_grad(const at::Tensor& g, int64_t B, int64_t H, int64_t W, const char* name) {
-    if (g.dim() != 4 || g.size(0) != B || g.size(1) != 2 || g.size(2) != H || g.size(3) != W)
-        err(std::string(name) + " must have dimensions (B, 2, H, W) with alpha=True (channel 0 the depth's gradient, channel 1 "
-            "alpha's): (" + std::to_string(B) + ", 2, " + std::to_string(H) + ", " + std::to_string(W) + ") here");
-}
-
 // ---- the four functions of ext.cpp:6-11 -----------------------------------------------------------------------------
-// -> (num_rendered:int, color [B,3,H,W], depth [B,1,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
-//    alpha=True: the depth slot is [B,2,H,W], channel 1 the accumulated opacity alpha = 1 - T_final
+// What the two forwards share: the call, color [B,3,H,W] and depth [B,1,H,W] -- with alpha=True (DMR_FLAG_ALPHA) [B,2,H,W],
+// depth | alpha, channel 1 the accumulated opacity alpha = 1 - T_final -- and the return of the four scratch buffers.
+struct Forward {
+    c10::Device dev;
+    c10::DeviceGuard guard;
+    Call call;
+    // the kernels write every pixel of the rendered rows (tet: the background where the march fails); zero-fill (render.cu:88-89,
+    // :287-290) is only needed when nothing is launched (P == 0 / F == 0, render.cu:105) or when a band leaves rows untouched
+    bool written;
+    at::Tensor color, depth;
+
+    Forward(const Inputs& in, int64_t H, int64_t W, int64_t seed, std::pair<int, int> rows, bool fill_outside, bool alpha)
+        : dev(hip_device_of(in.verts)), guard(dev), call(dev, in, H, W, seed, rows),
+          written(((rows.first == 0 && rows.second == 0) || !fill_outside) && call.sc.P > 0 && call.sc.F > 0),
+          color(image({call.sc.B, NUM_CHANNELS, H, W})), depth(image({call.sc.B, alpha ? 2 : 1, H, W})) {
+        if (alpha) call.sc.flags |= DMR_FLAG_ALPHA;
+    }
+    at::Tensor image(at::IntArrayRef shape) const { return written ? at::empty(shape, f32_on(dev)) : at::zeros(shape, f32_on(dev)); }
+    template <class... Out>  // -> (out..., pointBuffer, faceBuffer, binningBuffer, imgBuffer)
+    auto result(Out... out) const {
+        return std::make_tuple(out..., call.scratch.get(DMR_BUF_POINT), call.scratch.get(DMR_BUF_FACE), call.scratch.get(DMR_BUF_BINNING),
+                               call.scratch.get(DMR_BUF_IMAGE));
+    }
+};
+
+// -> (num_rendered:int, color, depth, pointBuffer, faceBuffer, binningBuffer, imgBuffer)
 using TriFwdOut = std::tuple<int64_t, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-TriFwdOut render_tris(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                      const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                      const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                      const at::Tensor& faces_intense, int64_t image_height, int64_t image_width, std::pair<int, int> rows,
+TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
+                      In inv_proj_mats, In verts_depth, In faces_intense, int64_t image_height, int64_t image_width, std::pair<int, int> rows,
                       bool fill_outside, bool alpha) {
-    check_common(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense, false);
-    const c10::Device dev = hip_device_of(verts);
-    c10::DeviceGuard guard(dev);
-    Call call(dev, background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth,
-              faces_intense, image_height, image_width, nullptr, nullptr, nullptr, 0, rows);
-    // the kernels write every pixel of the rendered rows; zero-fill (render.cu:88-89) is only needed when nothing is
-    // launched (P == 0 / F == 0, render.cu:105) or when a band leaves rows untouched
-    const bool full = ((rows.first == 0 && rows.second == 0) || !fill_outside) && call.sc.P > 0 && call.sc.F > 0;
-    const auto opt = f32_on(dev);
-    at::Tensor color = full ? at::empty({call.sc.B, NUM_CHANNELS, image_height, image_width}, opt)
-                            : at::zeros({call.sc.B, NUM_CHANNELS, image_height, image_width}, opt);
-    const int64_t dch = alpha ? 2 : 1;
-    at::Tensor depth = full ? at::empty({call.sc.B, dch, image_height, image_width}, opt) : at::zeros({call.sc.B, dch, image_height, image_width}, opt);
-    if (alpha) call.sc.flags |= DMR_FLAG_ALPHA;
+    const Inputs in{background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense};
+    check_common(in, false);
+    Forward f(in, image_height, image_width, 0, rows, fill_outside, alpha);
     int rendered = 0;
     // (the bindings release the GIL around this whole function: the default call waits for the size read-back)
-    if (g_abi.tri_forward(&call.sc, mptr<float>(color), mptr<float>(depth), &alloc_cb, &call.scratch, call.stream(), &rendered)) raise_lib();
-    return TriFwdOut((int64_t)rendered, color, depth, call.scratch.get(DMR_BUF_POINT), call.scratch.get(DMR_BUF_FACE),
-                          call.scratch.get(DMR_BUF_BINNING), call.scratch.get(DMR_BUF_IMAGE));
+    if (g_abi.tri_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), &alloc_cb, &f.call.scratch, f.call.stream(), &rendered)) raise_lib();
+    return f.result((int64_t)rendered, f.color, f.depth);
 }
 
-// The gradient outputs of a backward, one piece per shape: each allocated, or carved in order out of flat_out, the
-// caller's buffer (the payload of the one all-reduce in sharding.py), which must hold exactly all of them.
-std::vector<at::Tensor> grad_outputs(c10::Device dev, const std::optional<at::Tensor>& flat_out,
-                                     const std::vector<std::vector<int64_t>>& shapes) {
-    std::vector<at::Tensor> out;
-    if (!flat_out.has_value()) {
-        for (const auto& s : shapes) out.push_back(at::empty(s, f32_on(dev)));
-        return out;
-    }
-    int64_t total = 0;
-    for (const auto& s : shapes) total += c10::multiply_integers(s);
-    const at::Tensor& fo = *flat_out;
-    if (fo.scalar_type() != at::kFloat || fo.device() != dev || !fo.is_contiguous() || fo.numel() != total)
-        err("flat_out must be a contiguous float32 tensor of " + std::to_string(total) + " elements on " + dev.str());
-    const at::Tensor flat = fo.view({-1});
-    int64_t o = 0;
-    for (const auto& s : shapes) {
-        const int64_t n = c10::multiply_integers(s);
-        out.push_back(flat.narrow(0, o, n).view(s));
-        o += n;
-    }
-    return out;
-}
-
-// -> (dL_dverts [P,3], dL_dvcolor [P,3], dL_dfopacity [F], dL_dvdepth [B,P], dL_dfintense [B,F]), with camera grads
-//    followed by (dL_dinv_mv_mats [B,4,4], dL_dinv_proj_mats [B,4,4]): element [b,i,j] is the gradient of the inverse
-//    tensor's [b,i,j] as the call received it (the library's contract layout m[4*col+row] read as a row-major [4,4] is
-//    the transpose of the matrix it means, which is how such a tensor holds it).
-// The binding: without the two keywords exactly the reference's function (render.cu:134-208).
-py::tuple render_tris_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                               const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                               const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                               const at::Tensor& faces_intense, const at::Tensor& dL_dout_color, const at::Tensor& dL_dout_depth,
-                               int64_t R, const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool exact_grads, bool camera_grads, bool alpha) {
-    std::optional<py::gil_scoped_release> nogil(std::in_place);  // (the default call waits for the size read-back)
-    const c10::Device dev = hip_device_of(verts);
-    c10::DeviceGuard guard(dev);
-    if (dL_dout_color.dim() != 4) err("dL_dout_color must have dimensions (B, 3, H, W)");
-    const int64_t H = dL_dout_color.size(2), W = dL_dout_color.size(3);  // render.cu:163-164
-    Call call(dev, background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth,
-              faces_intense, H, W, nullptr, nullptr, nullptr, 0, rows);
-    const at::Tensor gc = f32(dL_dout_color, "dL_dout_color");  // may arrive non-contiguous / expanded (render.cu:197-198)
-    const at::Tensor gd = f32(dL_dout_depth, "dL_dout_depth");
-    const int64_t B = call.sc.B, P = call.sc.P, F = call.sc.F;
-    if (alpha) {
-        check_depth_alpha_grad(gd, B, H, W, "dL_dout_depth");
-        call.sc.flags |= DMR_FLAG_ALPHA;
-    }
-    // camera grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16] is DMR_BUF_TRI_CAMERA_GRADS, served by alloc_cb from g[5]; with
-    // flat_out it follows the default layout ([3P | 3P | F | BP | BF | 32B]), so one all-reduce still carries everything
-    std::vector<std::vector<int64_t>> shapes = {{P, 3}, {P, NUM_CHANNELS}, {F}, {B, P}, {B, F}};
-    if (camera_grads) shapes.push_back({B, 32});
-    std::vector<at::Tensor> g = grad_outputs(dev, flat_out, shapes);
-    if (camera_grads) {
-        call.scratch.tri_cam = g[5];
-        call.sc.flags |= DMR_FLAG_TRI_CAMERA_GRADS;
-    }
-    if (exact_grads || camera_grads) call.sc.flags |= DMR_FLAG_TRI_EXACT_GRADS;
-    const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
-    if (g_abi.tri_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), (int)R, mptr<const void>(pb), mptr<const void>(fb),
-                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g[0]), mptr<float>(g[1]), mptr<float>(g[2]),
-                           mptr<float>(g[3]), mptr<float>(g[4]), &alloc_cb, &call.scratch, call.stream()))
-        raise_lib();
-    if (camera_grads) {
-        const at::Tensor cam = g[5].view({B, 2, 4, 4});
-        g[5] = cam.select(1, 0);
-        g.push_back(cam.select(1, 1));
-    }
-    nogil.reset();
-    return py::tuple(py::cast(g));
-}
-
-void check_tets(const at::Tensor& faces, const at::Tensor& tets, const at::Tensor& face_tets, const at::Tensor& tet_faces) {
-    // render.cu:269-277
-    if (tets.dim() != 2 || tets.size(1) != 4) err("tets must have dimensions (num_tets, 4)");
-    if (face_tets.dim() != 2 || face_tets.size(0) != faces.size(0) || face_tets.size(1) != 2) err("face_tets must have dimensions (num_faces, 2)");
-    if (tet_faces.dim() != 2 || tet_faces.size(0) != tets.size(0) || tet_faces.size(1) != 4) err("tet_faces must have dimensions (num_tets, 4)");
-}
-
-// -> (color [B,3,H,W], depth [B,1,H,W], active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
+// -> (color, depth, active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
 using TetFwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-TetFwdOut render_tets(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                      const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                      const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                      const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets, const at::Tensor& tet_faces,
-                      int64_t image_height, int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows, bool alpha) {
-    check_common(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense, true);
-    check_tets(faces, tets, face_tets, tet_faces);
-    const c10::Device dev = hip_device_of(verts);
-    c10::DeviceGuard guard(dev);
-    Call call(dev, background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth,
-              faces_intense, image_height, image_width, &tets, &face_tets, &tet_faces, ray_random_seed, rows);
-    // k_tet_forward writes every pixel of the rendered rows (background where the march fails); zero-fill
-    // (render.cu:287-290) is only needed when a band leaves rows untouched or nothing is launched
-    const bool full = rows.first == 0 && rows.second == 0 && call.sc.P > 0 && call.sc.F > 0;
-    const auto opt = f32_on(dev);
-    auto img = [&](at::IntArrayRef shape) { return full ? at::empty(shape, opt) : at::zeros(shape, opt); };
-    at::Tensor color = img({call.sc.B, NUM_CHANNELS, image_height, image_width});
-    at::Tensor depth = img({call.sc.B, alpha ? 2 : 1, image_height, image_width});  // alpha=True: depth | alpha
-    if (alpha) call.sc.flags |= DMR_FLAG_ALPHA;
-    at::Tensor active = img({call.sc.B, image_height, image_width});
+TetFwdOut render_tets(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
+                      In inv_proj_mats, In verts_depth, In faces_intense, In tets, In face_tets, In tet_faces, int64_t image_height,
+                      int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows, bool alpha) {
+    const Inputs in{background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense,
+                    &tets, &face_tets, &tet_faces};
+    check_common(in, true);
+    Forward f(in, image_height, image_width, ray_random_seed, rows, true, alpha);
+    const at::Tensor active = f.image({f.call.sc.B, image_height, image_width});
     int rendered = 0;
-    if (g_abi.tet_forward(&call.sc, mptr<float>(color), mptr<float>(depth), mptr<float>(active), &alloc_cb, &call.scratch, call.stream(), &rendered))
+    if (g_abi.tet_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), mptr<float>(active), &alloc_cb, &f.call.scratch, f.call.stream(),
+                          &rendered))
         raise_lib();
-    return TetFwdOut(color, depth, active, call.scratch.get(DMR_BUF_POINT), call.scratch.get(DMR_BUF_FACE),
-                          call.scratch.get(DMR_BUF_BINNING), call.scratch.get(DMR_BUF_IMAGE));
+    return f.result(f.color, f.depth, active);
 }
 
-// -> (dL_dverts_color [P,3], dL_dfaces_opacity [F]), or with full_grads
-//    (dL_dverts [P,3], dL_dverts_color [P,3], dL_dfaces_opacity [F], dL_dfaces_intense [B,F]), with camera_grads followed by
-//    (dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats) [B,4,4], each of the matrix tensor as the call
-//    received it (as render_tris_backward's).
-// The binding: without full_grads and camera_grads exactly the reference's function (render.cu:338-412).
-py::tuple render_tets_backward(const at::Tensor& background, const at::Tensor& verts, const at::Tensor& faces, const at::Tensor& verts_color,
-                               const at::Tensor& faces_opacity, const at::Tensor& mv_mats, const at::Tensor& proj_mats,
-                               const at::Tensor& inv_mv_mats, const at::Tensor& inv_proj_mats, const at::Tensor& verts_depth,
-                               const at::Tensor& faces_intense, const at::Tensor& tets, const at::Tensor& face_tets,
-                               const at::Tensor& tet_faces, const at::Tensor& grad_color, const at::Tensor& grad_depth,
-                               const at::Tensor& pointBuffer, const at::Tensor& faceBuffer, const at::Tensor& binningBuffer,
-                               const at::Tensor& imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool full_grads, bool camera_grads, bool alpha) {
-    std::optional<py::gil_scoped_release> nogil(std::in_place);
-    const c10::Device dev = hip_device_of(verts);
+// ---- the gradient set of a backward, stated once ------------------------------------------------------------------------
+// Level 0: the reference's gradients; 1: exact_grads (tri) / full_grads (tet); 2: camera_grads, which implies level 1.
+// `shape`: the pieces of the flat layout, in its order -- what flat_out holds back to back (the payload of the one all-reduce
+// in sharding.py, which states the same table: _TRI_GRADS / _TET_GRADS) and what is allocated otherwise.  `from`: where the
+// library gets a piece's pointer: ARG, the next gradient argument of the C call, or the DMR_BUF_* id of the output it requests
+// through alloc (alloc_cb serves it from Scratch::buf; consecutive pieces of one id are one buffer).  `tuple`: the pieces in
+// the order of the returned tuple; a [B, n, 4, 4] piece -- n matrix gradients per view in the library's contract layout
+// m[4*col+row] -- stands for its n [B,4,4] slices: element [b,i,j] is the gradient of the matrix tensor's [b,i,j] as the call
+// received it (the contract layout read as a row-major [4,4] is the transpose of the matrix it means, which is how such a
+// tensor holds it).  `flags`: the level's DMR_FLAG_* bits.
+constexpr int ARG = -1;
+using Shape = c10::SmallVector<int64_t, 4>;
+struct GradTable {
+    c10::SmallVector<Shape, 6> shape;
+    c10::SmallVector<int, 6> from, tuple;
+    int flags;
+    void add(Shape s, int buf) { tuple.push_back((int)shape.size()); shape.push_back(std::move(s)); from.push_back(buf); }
+};
+
+// -> (dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense), camera: then (dL_dinv_mv_mats, dL_dinv_proj_mats).
+// Level 0 is exactly the reference's function (render.cu:134-208).
+GradTable tri_grads(int level, int64_t P, int64_t F, int64_t B) {
+    static const int flags[3] = {0, DMR_FLAG_TRI_EXACT_GRADS, DMR_FLAG_TRI_EXACT_GRADS | DMR_FLAG_TRI_CAMERA_GRADS};
+    GradTable t{{{P, 3}, {P, NUM_CHANNELS}, {F}, {B, P}, {B, F}}, {ARG, ARG, ARG, ARG, ARG}, {0, 1, 2, 3, 4}, flags[level]};
+    if (level == 2) t.add({B, 2, 4, 4}, DMR_BUF_TRI_CAMERA_GRADS);
+    return t;
+}
+
+// -> (dL_dverts_color, dL_dfaces_opacity); full: (dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dfaces_intense); camera: then
+// (dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats).  Level 0 is exactly the reference's function (render.cu:338-412).
+GradTable tet_grads(int level, int64_t P, int64_t F, int64_t B) {
+    static const int flags[3] = {0, DMR_FLAG_TET_FULL_GRADS, DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS};
+    GradTable t{{{P, 3}, {F}}, {ARG, ARG}, {0, 1}, flags[level]};
+    if (level >= 1) {
+        t.add({P, 3}, DMR_BUF_TET_GRADS);  // [dL_dverts 3P | dL_dfaces_intense BF]: one buffer
+        t.add({B, F}, DMR_BUF_TET_GRADS);
+        t.tuple = {2, 0, 1, 3};
+    }
+    if (level == 2) t.add({B, 4, 4, 4}, DMR_BUF_TET_CAMERA_GRADS);
+    return t;
+}
+
+// The pieces of `t` as tensors: each run (a piece, or the pieces of one buffer) allocated, or carved in order out of flat_out,
+// the caller's buffer, which must hold exactly all of them.  A run the library requests is left where alloc_cb finds it.
+std::vector<at::Tensor> grad_outputs(Call& call, const std::optional<at::Tensor>& flat_out, const GradTable& t) {
+    const size_t n = t.shape.size();
+    c10::SmallVector<int64_t, 6> numel;
+    int64_t total = 0;
+    for (const Shape& s : t.shape) total += numel.emplace_back(c10::multiply_integers(s));
+    at::Tensor flat;
+    if (flat_out.has_value()) {
+        const at::Tensor& fo = *flat_out;
+        if (fo.scalar_type() != at::kFloat || fo.device() != call.dev || !fo.is_contiguous() || fo.numel() != total)
+            err("flat_out must be a contiguous float32 tensor of " + std::to_string(total) + " elements on " + call.dev.str());
+        flat = fo.view({-1});
+    }
+    std::vector<at::Tensor> g(n);
+    int64_t o = 0;
+    for (size_t i = 0, j; i < n; i = j) {
+        int64_t len = numel[i];
+        for (j = i + 1; j < n && t.from[i] != ARG && t.from[j] == t.from[i]; j++) len += numel[j];
+        const bool one = j == i + 1;
+        const at::Tensor run = flat.defined() ? flat.narrow(0, o, len) : at::empty(one ? at::IntArrayRef(t.shape[i]) : at::IntArrayRef(len), f32_on(call.dev));
+        if (t.from[i] != ARG) call.scratch.buf[t.from[i]] = run;
+        for (int64_t k = 0; i < j; k += numel[i++]) {
+            const at::Tensor piece = one ? run : run.narrow(0, k, numel[i]);
+            g[i] = piece.sizes() == at::IntArrayRef(t.shape[i]) ? piece : piece.view(t.shape[i]);
+        }
+        o += len;
+    }
+    return g;
+}
+
+// The body of the two backwards: `launch(call, dL_dcolor, dL_ddepth, the four scratch buffers, the ARG pieces)` is the C call.
+template <class Launch>
+py::tuple backward(const Inputs& in, In grad_color, In grad_depth, const char* color_name, const char* depth_name, In pointBuffer, In faceBuffer,
+                   In binningBuffer, In imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                   GradTable (*table)(int, int64_t, int64_t, int64_t), int level, bool alpha, Launch launch) {
+    std::optional<py::gil_scoped_release> nogil(std::in_place);  // (the default call waits for the size read-back)
+    const c10::Device dev = hip_device_of(in.verts);
     c10::DeviceGuard guard(dev);
-    if (grad_color.dim() != 4) err("grad_color must have dimensions (B, 3, H, W)");
-    const int64_t H = grad_color.size(2), W = grad_color.size(3);  // render.cu:371-372
-    Call call(dev, background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth,
-              faces_intense, H, W, &tets, &face_tets, &tet_faces, 0, rows);
-    const at::Tensor gc = f32(grad_color, "grad_color"), gd = f32(grad_depth, "grad_depth");
-    const int64_t P = call.sc.P, F = call.sc.F, B = call.sc.B;
-    if (alpha) {
-        check_depth_alpha_grad(gd, B, H, W, "grad_depth");
+    if (grad_color.dim() != 4) err(std::string(color_name) + " must have dimensions (B, 3, H, W)");
+    const int64_t H = grad_color.size(2), W = grad_color.size(3);  // render.cu:163-164, :371-372
+    Call call(dev, in, H, W, 0, rows);
+    const at::Tensor gc = f32(grad_color, color_name);  // may arrive non-contiguous / expanded (render.cu:197-198)
+    const at::Tensor gd = f32(grad_depth, depth_name);
+    if (alpha) {  // [B,2,H,W], depth | alpha
+        if (gd.dim() != 4 || gd.size(0) != call.sc.B || gd.size(1) != 2 || gd.size(2) != H || gd.size(3) != W)
+            err(std::string(depth_name) + " must have dimensions (B, 2, H, W) with alpha=True (channel 0 the depth's gradient, channel 1 "
+                "alpha's): (" + std::to_string(call.sc.B) + ", 2, " + std::to_string(H) + ", " + std::to_string(W) + ") here");
         call.sc.flags |= DMR_FLAG_ALPHA;
     }
-    // full_grads: [dL_dverts 3P | dL_dfintense BF] is DMR_BUF_TET_GRADS, served by alloc_cb from g[2].  With flat_out
-    // the layout is [dL_dverts_color 3P | dL_dfaces_opacity F | dL_dverts 3P | dL_dfaces_intense BF]: the default layout
-    // followed by that buffer, so one all-reduce still carries everything.
-    // camera_grads: [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 | dL/dproj 16] is DMR_BUF_TET_CAMERA_GRADS, served from
-    // g[3]; with flat_out it follows the full layout.
-    full_grads = full_grads || camera_grads;
-    std::vector<std::vector<int64_t>> shapes = {{P, 3}, {F}};
-    if (full_grads) shapes.push_back({3 * P + B * F});
-    if (camera_grads) shapes.push_back({B, 64});
-    std::vector<at::Tensor> g = grad_outputs(dev, flat_out, shapes);
-    if (full_grads) {
-        call.scratch.tet_grads = g[2];
-        call.sc.flags |= DMR_FLAG_TET_FULL_GRADS;
-    }
-    if (camera_grads) {
-        call.scratch.tet_cam = g[3];
-        call.sc.flags |= DMR_FLAG_TET_CAMERA_GRADS;
-    }
-    const at::Tensor pb = pointBuffer.contiguous(), fb = faceBuffer.contiguous(), bb = binningBuffer.contiguous(), ib = imageBuffer.contiguous();
-    if (g_abi.tet_backward(&call.sc, mptr<const float>(gc), mptr<const float>(gd), mptr<const void>(pb), mptr<const void>(fb),
-                           mptr<const void>(bb), mptr<const void>(ib), mptr<float>(g[0]), mptr<float>(g[1]), &alloc_cb,
-                           &call.scratch, call.stream()))
-        raise_lib();
-    if (full_grads) {
-        std::vector<at::Tensor> r = {g[2].narrow(0, 0, 3 * P).view({P, 3}), g[0], g[1], g[2].narrow(0, 3 * P, B * F).view({B, F})};
-        if (camera_grads) {
-            const at::Tensor cam = g[3].view({B, 4, 4, 4});
-            for (int k = 0; k < 4; k++) r.push_back(cam.select(1, k));
-        }
-        g = std::move(r);
+    const GradTable t = table(level, call.sc.P, call.sc.F, call.sc.B);
+    call.sc.flags |= t.flags;
+    const std::vector<at::Tensor> g = grad_outputs(call, flat_out, t);
+    float* args[5];
+    for (size_t i = 0, a = 0; i < g.size(); i++)
+        if (t.from[i] == ARG) args[a++] = mptr<float>(g[i]);
+    const at::Tensor buf[4] = {pointBuffer.contiguous(), faceBuffer.contiguous(), binningBuffer.contiguous(), imageBuffer.contiguous()};
+    const void* bufs[4] = {mptr<const void>(buf[0]), mptr<const void>(buf[1]), mptr<const void>(buf[2]), mptr<const void>(buf[3])};
+    if (launch(call, mptr<const float>(gc), mptr<const float>(gd), bufs, args)) raise_lib();
+    std::vector<at::Tensor> out;
+    for (int i : t.tuple) {
+        if (t.shape[i].size() != 4) out.push_back(g[i]);
+        else for (int64_t k = 0; k < t.shape[i][1]; k++) out.push_back(g[i].select(1, k));
     }
     nogil.reset();
-    return py::tuple(py::cast(g));
+    return py::tuple(py::cast(out));
+}
+
+// tri_grads' tuple; the keywords select its level
+py::tuple render_tris_backward(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
+                               In inv_proj_mats, In verts_depth, In faces_intense, In dL_dout_color, In dL_dout_depth, int64_t R, In pointBuffer,
+                               In faceBuffer, In binningBuffer, In imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
+                               bool exact_grads, bool camera_grads, bool alpha) {
+    return backward({background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense},
+                    dL_dout_color, dL_dout_depth, "dL_dout_color", "dL_dout_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out,
+                    &tri_grads, camera_grads ? 2 : exact_grads, alpha,
+                    [R](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                        return g_abi.tri_backward(&c.sc, gc, gd, (int)R, b[0], b[1], b[2], b[3], g[0], g[1], g[2], g[3], g[4], &alloc_cb, &c.scratch,
+                                                  c.stream());
+                    });
+}
+
+// tet_grads' tuple; the keywords select its level
+py::tuple render_tets_backward(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
+                               In inv_proj_mats, In verts_depth, In faces_intense, In tets, In face_tets, In tet_faces, In grad_color, In grad_depth,
+                               In pointBuffer, In faceBuffer, In binningBuffer, In imageBuffer, std::pair<int, int> rows,
+                               const std::optional<at::Tensor>& flat_out, bool full_grads, bool camera_grads, bool alpha) {
+    return backward({background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense,
+                     &tets, &face_tets, &tet_faces},
+                    grad_color, grad_depth, "grad_color", "grad_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out, &tet_grads,
+                    camera_grads ? 2 : full_grads, alpha, [](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                        return g_abi.tet_backward(&c.sc, gc, gd, b[0], b[1], b[2], b[3], g[0], g[1], &alloc_cb, &c.scratch, c.stream());
+                    });
 }
 
 // ---- extensions -----------------------------------------------------------------------------------------------------
@@ -496,8 +488,8 @@ at::Tensor export_item(const std::string& name, const py::sequence& call_args, b
     if (a.size() < (is_tet ? 14u : 11u)) err("export: call_args must hold the leading tensors of render_*");
     const c10::Device dev = hip_device_of(a[1]);
     c10::DeviceGuard guard(dev);
-    Call call(dev, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], H, W, is_tet ? &a[11] : nullptr,
-              is_tet ? &a[12] : nullptr, is_tet ? &a[13] : nullptr, 0, {0, 0});
+    Call call(dev, {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], is_tet ? &a[11] : nullptr, is_tet ? &a[12] : nullptr,
+                    is_tet ? &a[13] : nullptr}, H, W, 0, {0, 0});
     std::vector<at::Tensor> b;
     for (const auto& h : buffers) b.push_back(h.cast<at::Tensor>().contiguous());
     if (b.size() != 4) err("export: buffers must be the four scratch tensors");
@@ -523,29 +515,23 @@ py::tuple profile_collect() {
 PYBIND11_MODULE(_C, m) {
     load_abi();  // import fails loudly when the HIP library is missing or mismatched
     m.doc() = "dmesh_renderer_amd._C: the reference's four-function binding surface (ext.cpp:6-11) over libdmesh_renderer_hip.so";
-    const auto no_rows = std::pair<int, int>(0, 0);
-    m.def("render_tris", &render_tris, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
-          py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
-          py::arg("verts_depth"), py::arg("faces_intense"), py::arg("image_height"), py::arg("image_width"),
-          py::arg("rows") = no_rows, py::arg("fill_outside") = true, py::kw_only(), py::arg("alpha") = false,
-          py::call_guard<py::gil_scoped_release>());
-    m.def("render_tris_backward", &render_tris_backward, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
-          py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
-          py::arg("verts_depth"), py::arg("faces_intense"), py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"),
-          py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"),
-          py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("exact_grads") = false,
-          py::arg("camera_grads") = false, py::arg("alpha") = false);
-    m.def("render_tets", &render_tets, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
-          py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
-          py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
-          py::arg("image_height"), py::arg("image_width"), py::arg("ray_random_seed"), py::arg("rows") = no_rows,
-          py::kw_only(), py::arg("alpha") = false, py::call_guard<py::gil_scoped_release>());
-    m.def("render_tets_backward", &render_tets_backward, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"),
-          py::arg("faces_opacity"), py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"),
-          py::arg("verts_depth"), py::arg("faces_intense"), py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"),
-          py::arg("grad_color"), py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"),
-          py::arg("imageBuffer"), py::arg("rows") = no_rows, py::arg("flat_out") = py::none(), py::kw_only(), py::arg("full_grads") = false,
-          py::arg("camera_grads") = false, py::arg("alpha") = false);
+    const auto rows = py::arg("rows") = std::pair<int, int>(0, 0), alpha = py::arg("alpha") = false;
+    const auto flat_out = py::arg("flat_out") = py::none(), camera_grads = py::arg("camera_grads") = false;
+    const auto def = [&m](const char* name, auto fn, const auto&... more) {  // the arguments every render_* function starts with
+        m.def(name, fn, py::arg("background"), py::arg("verts"), py::arg("faces"), py::arg("verts_color"), py::arg("faces_opacity"),
+              py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"), py::arg("verts_depth"),
+              py::arg("faces_intense"), more...);
+    };
+    def("render_tris", &render_tris, py::arg("image_height"), py::arg("image_width"), rows, py::arg("fill_outside") = true, py::kw_only(), alpha,
+        py::call_guard<py::gil_scoped_release>());
+    def("render_tris_backward", &render_tris_backward, py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"), py::arg("pointBuffer"),
+        py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out, py::kw_only(), py::arg("exact_grads") = false,
+        camera_grads, alpha);
+    def("render_tets", &render_tets, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("image_height"), py::arg("image_width"),
+        py::arg("ray_random_seed"), rows, py::kw_only(), alpha, py::call_guard<py::gil_scoped_release>());
+    def("render_tets_backward", &render_tets_backward, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("grad_color"),
+        py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out,
+        py::kw_only(), py::arg("full_grads") = false, camera_grads, alpha);
     m.def("invert_mats", &invert_mats);
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));

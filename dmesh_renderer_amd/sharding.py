@@ -40,8 +40,8 @@ import numpy as np
 import torch as th
 import torch.distributed as dist
 
-from . import (TetRenderer, TetRenderSettings, TriRenderer, TriRenderSettings, _camera_grads, _tri_backward, _tri_flat,
-               _tri_forward, _tri_grad_options, _with_inverses)
+from . import (_TRI_GRADS, TetRenderer, TetRenderSettings, TriRenderer, TriRenderSettings, _flat, _forward, _grad_options, _input_grads,
+               _one_backward, _with_inverses)
 
 TILE = 16
 
@@ -296,8 +296,8 @@ class _ShardedTriViewFn(th.autograd.Function):
         rows = [_band_rows((r0, r1), gy) for _, r0, r1 in segs]
         saved, nums, outs = [], [], []
         for (v, _, _), r in zip(segs, rows):
-            num, color, depth, s = _tri_forward(impl, settings, geom, mv_mats[v:v + 1], proj_mats[v:v + 1],
-                                                verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous(), r, alpha)
+            (num, color, depth), s = _forward(impl.render_tris, settings, geom, mv_mats[v:v + 1], proj_mats[v:v + 1],
+                                              verts_depth[v:v + 1].contiguous(), faces_intense[v:v + 1].contiguous(), r, alpha)
             outs.append((color, depth))
             nums.append(num)
             saved += s
@@ -311,35 +311,32 @@ class _ShardedTriViewFn(th.autograd.Function):
                 color[v, :, y0:y1] = c[0, :, y0:y1]
                 depth[v, ..., y0:y1, :] = z[0, ..., y0:y1, :]
         ctx.settings, ctx.segs, ctx.rows, ctx.group, ctx.impl, ctx.nums = settings, tuple(segs), rows, group, impl, nums
-        ctx.exact_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
+        ctx.more_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved, *((mv_mats, proj_mats) if camera_grads else ()))
         return color, depth
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth):
         saved = ctx.saved_tensors
-        camera, kw = _tri_grad_options(ctx)
+        level, kw = _grad_options(ctx, _TRI_GRADS)
         geom = saved[:4]
         B = grad_color.size(0)
-        # the all-views flat layout: this rank fills the shared part and its views' rows of the per-view parts
-        flat, g = _tri_flat(geom[0].size(0), geom[1].size(0), B, camera, geom[0].device, th.zeros)
+        # the all-views flat layout: this rank fills the shared pieces and its views' rows of the per-view pieces
+        flat, g = _flat(_TRI_GRADS, level, geom[0].size(0), geom[1].size(0), B, geom[0].device, th.zeros)
         for i, ((v, _, _), rows) in enumerate(zip(ctx.segs, ctx.rows)):
             s = saved[4 + 10 * i:14 + 10 * i]  # mv, proj, their inverses, verts_depth, faces_intense, four scratch buffers
-            gs = _tri_backward(ctx.impl, ctx.settings, geom, s, grad_color[v:v + 1].contiguous(),
-                               grad_depth[v:v + 1].contiguous(), ctx.nums[i], rows, kw)
-            for k in range(3):
-                g[k] += gs[k]
-            g[3][v] += gs[3][0]
-            g[4][v] += gs[4][0]
-            if camera:  # the segment's B = 1 rows land in its view's slot
-                g[5][v, 0] += gs[5][0]
-                g[5][v, 1] += gs[6][0]
+            gs = _one_backward(ctx.impl.render_tris_backward, ctx.settings, geom, s,
+                               (grad_color[v:v + 1].contiguous(), grad_depth[v:v + 1].contiguous(), ctx.nums[i]), rows, kw)
+            if level == 2:  # the camera piece of the segment's B = 1 call
+                gs = (*gs[:5], th.stack(gs[5:], 1))
+            for piece, seg in zip(g, gs):  # a per-view piece: the segment's row lands in its view's slot
+                (piece if piece.shape == seg.shape else piece[v:v + 1]).add_(seg)
         if _world(ctx.group) > 1:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=ctx.group)
-        g_mv = g_proj = None
-        if camera:  # every view's inverses (a rank holds only its segments')
-            g_mv, g_proj = _camera_grads(ctx, *_with_inverses(saved[-2], saved[-1])[2:], g[5][:, 0], g[5][:, 1])
-        return (g[0], None, g[1], g[2], g_mv, g_proj, g[3], g[4]) + (None,) * 8
+        inverses = (None, None)
+        if level == 2:  # the camera piece as the backward's tuple has it; every view's inverses (a rank holds only its segments')
+            g, inverses = [*g[:5], *g[5].unbind(1)], _with_inverses(saved[-2], saved[-1])[2:]
+        return _input_grads(ctx, _TRI_GRADS, level, g, *inverses) + (None,) * 8
 
 
 class _Banded:

@@ -9,6 +9,7 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
+from standins import _FakeC
 from tet_camera_grad_ref import TetCameraGradRef
 from util import rel_err, upstream_grads
 
@@ -58,27 +59,6 @@ def test_model_matrix_grads_match_central_differences(oracle, case):
         fd = ref.finite_differences(k, gc, gd)
         assert np.abs(g[k]).max() > 1e-3, k
         assert rel_err(g[k], fd) <= 1e-6, (k, rel_err(g[k], fd))
-
-
-class _FakeC:
-    """Records the render_tets_backward calls; returns recognisable gradients."""
-
-    def __init__(self):
-        self.calls = []
-
-    def render_tets(self, bg, verts, faces, vcol, fop, mv, proj, imv, iproj, vdepth, fint, tets, ft, tf, H, W, seed, rows=(0, 0)):
-        B = mv.shape[0]
-        z = th.zeros(1)
-        return th.zeros(B, 3, H, W), th.zeros(B, 1, H, W), th.ones(B, H, W), z, z, z, z
-
-    def render_tets_backward(self, *args, **kw):
-        self.calls.append((len(args), dict(kw)))
-        verts, faces, mv, fint = args[1], args[2], args[5], args[10]
-        P, F, B = verts.shape[0], faces.shape[0], mv.shape[0]
-        g = (th.full((P, 3), 1.0), th.full((P, 3), 2.0), th.full((F,), 3.0), th.full(tuple(fint.shape), 4.0))
-        if kw.get("camera_grads"):
-            return g + (th.zeros(B, 4, 4), th.zeros(B, 4, 4), th.full((B, 4, 4), 5.0), th.full((B, 4, 4), 6.0))
-        return g if kw.get("full_grads") else g[1:3]
 
 
 def _run(r, d, needs_mats=True):

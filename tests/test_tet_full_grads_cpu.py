@@ -10,6 +10,7 @@ import torch as th
 
 import capi_ctypes
 from dmesh_renderer_amd import scenes
+from standins import _FakeC
 from tet_grad_ref import TetGradRef
 from util import rel_err, upstream_grads
 
@@ -56,25 +57,6 @@ def test_reference_model_matches_oracle(oracle, case):
         e = rel_err(g[k].astype(np.float32), og[k])
         assert e <= (2e-3 if (case, k) == ("opaque", "faces_opacity") else 1e-4), (k, e)
     assert np.abs(g["verts"]).max() > 0 and np.abs(g["faces_intense"]).max() > 0
-
-
-class _FakeC:
-    """Records the render_tets_backward calls; returns recognisable gradients."""
-
-    def __init__(self):
-        self.calls = []
-
-    def render_tets(self, bg, verts, faces, vcol, fop, mv, proj, imv, iproj, vdepth, fint, tets, ft, tf, H, W, seed, rows=(0, 0)):
-        B = mv.shape[0]
-        z = th.zeros(1)
-        return th.zeros(B, 3, H, W), th.zeros(B, 1, H, W), th.ones(B, H, W), z, z, z, z
-
-    def render_tets_backward(self, *args, **kw):
-        self.calls.append((len(args), dict(kw)))
-        verts, faces, fint = args[1], args[2], args[10]
-        P, F = verts.shape[0], faces.shape[0]
-        g = (th.full((P, 3), 1.0), th.full((P, 3), 2.0), th.full((F,), 3.0), th.full(tuple(fint.shape), 4.0))
-        return g if kw.get("full_grads") else g[1:3]
 
 
 @pytest.mark.parametrize("full", [False, True])

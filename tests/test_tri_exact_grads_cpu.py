@@ -8,6 +8,7 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
+from standins import _StandIn
 from tri_grad_ref import TriGradRef
 from util import rel_err, upstream_grads
 
@@ -58,25 +59,6 @@ def test_model_default_gradients_match_oracle(oracle, pinned):
         assert rel_err(og[k], g[k]) <= 1e-4, k
     # the reference's dL_dverts is not the derivative: the model must disagree with it
     assert rel_err(og["verts"], g["verts"]) > 1e-2
-
-
-class _StandIn:
-    """`_C` stand-in: fixed outputs, records the keywords of render_tris_backward, returns given inverse gradients."""
-
-    def __init__(self, B, P, F, H, W, g_inv):
-        self.B, self.P, self.F, self.H, self.W, self.g_inv = B, P, F, H, W, g_inv
-        self.kw = []
-
-    def render_tris(self, bg, verts, faces, vc, fo, mv, proj, imv, iproj, vd, fi, H, W, rows=(0, 0)):
-        e = th.zeros(1, dtype=th.uint8)
-        return 1, th.zeros(self.B, 3, H, W, dtype=verts.dtype), th.zeros(self.B, 1, H, W, dtype=verts.dtype), e, e, e, e
-
-    def render_tris_backward(self, *args, rows=(0, 0), **kw):
-        self.kw.append(kw)
-        B, P, F = self.B, self.P, self.F
-        z = lambda *s: th.zeros(*s, dtype=th.float64)
-        g = (z(P, 3), z(P, 3), z(F), z(B, P), z(B, F))
-        return g + tuple(self.g_inv) if kw.get("camera_grads") else g
 
 
 @pytest.mark.parametrize("opts", [{}, {"exact_grads": True}, {"camera_grads": True}, {"exact_grads": True, "camera_grads": True}])
