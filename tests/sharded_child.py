@@ -1,85 +1,127 @@
-"""Child of tests/test_sharded_gpu.py: one rank of a 2-rank (gloo) run of ShardedTriRenderer on one GPU.
-Every rank also renders the full image alone and compares."""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+"""Child of harness.run_ranks: `sharded_child.py <case>` is one rank of a 2-rank (gloo) run of the sharded Modules on one
+GPU.  Every rank also renders the full image alone and compares: the images bit for bit, the gradients to GRAD_TOL.
+--list prints the case names."""
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
+
 import numpy as np
 import torch as th
 import torch.distributed as dist
+
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import scenes, sharding
+from harness import module_step
 
-dist.init_process_group(backend="gloo")
-rank, world = dist.get_rank(), dist.get_world_size()
-dev = th.device("cuda:0")
-th.cuda.set_device(dev)
-B, H, W = 2, 200, 328
-d = scenes.layered_sheets(3, 14, B, H, W, seed=9)
-t = {k: v.to(dev) for k, v in d.items()}
-gc, gd = scenes.upstream_grads(B, H, W)
-gc, gd = gc.to(dev), gd.to(dev)
-names = ("verts", "verts_color", "faces_opacity", "verts_depth", "faces_intense")
-settings = dmr.TriRenderSettings(H, W, t["bg"])
+DEV = th.device("cuda:0")
+GRAD_TOL = 1e-5
+TRI_NAMES = ("verts", "verts_color", "faces_opacity", "verts_depth", "faces_intense")
 
 
-def run(renderer):
-    leaves = {k: t[k].clone().requires_grad_(True) for k in names}
-    color, depth = renderer(leaves["verts"], t["faces"], leaves["verts_color"], leaves["faces_opacity"], t["mv_mats"],
-                            t["proj_mats"], leaves["verts_depth"], leaves["faces_intense"])
-    th.autograd.backward([color, depth], [gc, gd])
-    return color.detach(), depth.detach(), [leaves[k].grad for k in names]
+def compare(full, sharded, names, tol, what):
+    """(images, gradients) of module_step, unsharded and sharded; `tol` is a bound or a function of the gradient's name."""
+    for a, b in zip(sharded[0], full[0]):
+        assert th.equal(a, b), (what, "image differs")
+    for k in names:
+        e = scenes.rel_err(sharded[1][k].cpu().numpy(), full[1][k].cpu().numpy())
+        assert e <= (tol(k) if callable(tol) else tol), (what, k, e)
 
 
-full = run(dmr.TriRenderer(settings))
-for partition in ("bands", "view_bands"):   # bands of both views per rank / (view, band) segments (B = 2 views, 2 ranks)
-    for assemble in (True, False):
-        sh = sharding.ShardedTriRenderer(settings, assemble=assemble, partition=partition)
-        assert sh.world == world == 2 and sh.rows != (0, 0)
-        if partition == "view_bands":  # the second view costs twice the first: rank 0 renders view 0 and the top of view 1
-            gy = sharding.tile_rows(H)
-            sh.set_row_work(np.stack([np.ones(gy), 2.0 * np.ones(gy)]))
-            sh.segment_cost_per_face = 0.0
-            parts = sh.view_parts(B, t["faces"].shape[0])
-            assert [len(p) for p in parts] == [2, 1], parts
-        c, z, g = run(sh)
-        if assemble:
-            assert th.equal(c, full[0]) and th.equal(z, full[1]), "assembled image differs"
-        elif partition == "bands":
-            r0, r1 = sh.rows
-            assert th.equal(c[:, :, 16 * r0:16 * r1], full[0][:, :, 16 * r0:16 * r1]), "band rows differ"
-        else:
-            for v, r0, r1 in parts[rank]:
-                assert th.equal(c[v, :, 16 * r0:16 * r1], full[0][v, :, 16 * r0:16 * r1]), "this rank's segment differs"
-        for a, b, k in zip(g, full[2], names):
-            e = scenes.rel_err(a.cpu().numpy(), b.cpu().numpy())
-            assert e <= scenes.sum_order_tol(k), (partition, k, e)
-
-# the tet renderer, same sharding (ShardedTetRenderer: bands, one all-gather of the images, ONE all-reduce over [3P | F])
-Ht = Wt = 160
-dt = scenes.kuhn_tets(5, B, Ht, Wt, seed=3)
-tt = {k: v.to(dev) for k, v in dt.items()}
-gct, gdt = scenes.upstream_grads(B, Ht, Wt)
-gct, gdt = gct.to(dev), gdt.to(dev)
-tsettings = dmr.TetRenderSettings(Ht, Wt, tt["bg"], 0)
+def on_device(d, B, H, W, alpha=False):
+    """The scene and the upstream gradients (g_c, g_d[, g_a]) on the device, and the renderer's settings."""
+    t = {k: v.to(DEV) for k, v in d.items()}
+    up = list(scenes.upstream_grads(B, H, W))
+    if alpha:
+        up.append(th.randn(B, 1, H, W, generator=th.Generator().manual_seed(5)))
+    settings = dmr.TetRenderSettings(H, W, t["bg"], 0) if "tets" in t else dmr.TriRenderSettings(H, W, t["bg"])
+    return t, [x.to(DEV) for x in up], settings
 
 
-def run_tet(renderer):
-    vc = tt["verts_color"].clone().requires_grad_(True); fo = tt["faces_opacity"].clone().requires_grad_(True)
-    color, depth, active = renderer(tt["verts"], tt["faces"], vc, fo, tt["mv_mats"], tt["proj_mats"], tt["verts_depth"],
-                                    tt["faces_intense"], tt["tets"], tt["face_tets"], tt["tet_faces"])
-    th.autograd.backward([color, depth], [gct, gdt])
-    return color.detach(), depth.detach(), active, [vc.grad, fo.grad]
+def sharded_vs_full(d, B, H, W, names, **kw):
+    """The scene `d` through the Module alone and through the assembling sharded Module (tri: both partitions), both
+    made with the keywords `kw`, compared -> the unsharded outputs."""
+    tet = "tets" in d
+    t, up, settings = on_device(d, B, H, W, alpha=kw.get("return_alpha", False))
+    full = module_step((dmr.TetRenderer if tet else dmr.TriRenderer)(settings, **kw), t, names, up)
+    for part in ({},) if tet else ({"partition": "bands"}, {"partition": "view_bands"}):
+        sh = (sharding.ShardedTetRenderer if tet else sharding.ShardedTriRenderer)(settings, assemble=True, **part, **kw)
+        assert sh.world == dist.get_world_size() == 2 and (not tet or sh.rows != (0, 0))
+        compare(full, module_step(sh, t, names, up), names, GRAD_TOL, (part, kw))
+    return full[0]
 
 
-tfull = run_tet(dmr.TetRenderer(tsettings))
-assert bool(tfull[2].any())
-sht = sharding.ShardedTetRenderer(tsettings, assemble=True)
-assert sht.world == 2 and sht.rows != (0, 0)
-c, z, a, g = run_tet(sht)
-assert th.equal(c, tfull[0]) and th.equal(z, tfull[1]) and th.equal(a, tfull[2]), "assembled tet image differs"
-for x, y, k in zip(g, tfull[3], ("verts_color", "faces_opacity")):
-    e = scenes.rel_err(x.cpu().numpy(), y.cpu().numpy())
-    assert e <= 1e-5, (k, e)
-dist.barrier()
-if rank == 0:
-    print("sharded ok")
-dist.destroy_process_group()
+def base():
+    """ShardedTriRenderer, assembled or not: bands of both views per rank / (view, band) segments (B = 2 views, 2 ranks);
+    then ShardedTetRenderer (bands, one all-gather of the images, ONE all-reduce over [3P | F])."""
+    rank = dist.get_rank()
+    B, H, W = 2, 200, 328
+    t, up, settings = on_device(scenes.layered_sheets(3, 14, B, H, W, seed=9), B, H, W)
+    full = module_step(dmr.TriRenderer(settings), t, TRI_NAMES, up)
+    for partition in ("bands", "view_bands"):
+        for assemble in (True, False):
+            sh = sharding.ShardedTriRenderer(settings, assemble=assemble, partition=partition)
+            assert sh.world == dist.get_world_size() == 2 and sh.rows != (0, 0)
+            if partition == "view_bands":  # the second view costs twice the first: rank 0 renders view 0 and the top of view 1
+                gy = sharding.tile_rows(H)
+                sh.set_row_work(np.stack([np.ones(gy), 2.0 * np.ones(gy)]))
+                sh.segment_cost_per_face = 0.0
+                parts = sh.view_parts(B, t["faces"].shape[0])
+                assert [len(p) for p in parts] == [2, 1], parts
+            if assemble:
+                mine = lambda im: im
+            elif partition == "bands":       # this rank's band rows of the colour image
+                r0, r1 = sh.rows
+                mine = lambda im: [im[0][:, :, 16 * r0:16 * r1]]
+            else:                            # this rank's segments of it
+                mine = lambda im: [im[0][v, :, 16 * r0:16 * r1] for v, r0, r1 in parts[rank]]
+            im, g = module_step(sh, t, TRI_NAMES, up)
+            compare((mine(full[0]), full[1]), (mine(im), g), TRI_NAMES, scenes.sum_order_tol, (partition, assemble))
+    out = sharded_vs_full(scenes.kuhn_tets(5, B, 160, 160, seed=3), B, 160, 160, ("verts_color", "faces_opacity"))
+    assert bool(out[2].any())
+
+
+def full_grads():
+    sharded_vs_full(scenes.kuhn_tets(5, 2, 160, 160, seed=3), 2, 160, 160,
+                    ("verts", "verts_color", "faces_opacity", "faces_intense"), full_grads=True)
+
+
+def exact_grads():
+    sharded_vs_full(scenes.layered_sheets(3, 9, 2, 96, 160, seed=4), 2, 96, 160,
+                    ("verts", "verts_color", "faces_opacity", "mv_mats", "proj_mats", "verts_depth", "faces_intense"), camera_grads=True)
+
+
+def camera_grads_tet():
+    sharded_vs_full(scenes.kuhn_tets(5, 2, 160, 176, seed=3), 2, 160, 176,
+                    ("verts", "verts_color", "faces_opacity", "mv_mats", "proj_mats", "faces_intense"), camera_grads=True)
+
+
+def alpha():
+    B, H, W = 2, 96, 176
+    out = sharded_vs_full(scenes.layered_sheets(3, 9, B, H, W, seed=4), B, H, W, TRI_NAMES, return_alpha=True)
+    assert float(out[2].max()) > 0.3
+    out = sharded_vs_full(scenes.kuhn_tets(4, B, H, W, seed=3), B, H, W, ("verts_color", "faces_opacity"), return_alpha=True)
+    assert float(out[3].max()) > 0.05
+
+
+CASES = {  # name: (the case, the line rank 0 prints when every rank got through it)
+    "base": (base, "sharded ok"),
+    "full_grads": (full_grads, "sharded full grads ok"),
+    "exact_grads": (exact_grads, "sharded exact grads ok"),
+    "camera_grads_tet": (camera_grads_tet, "sharded camera grads ok"),
+    "alpha": (alpha, "sharded alpha ok"),
+}
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["--list"]:
+        print(" ".join(CASES))
+        sys.exit(0)
+    run, ok_line = CASES[sys.argv[1]]
+    dist.init_process_group(backend="gloo")
+    th.cuda.set_device(DEV)
+    run()
+    dist.barrier()
+    if dist.get_rank() == 0:
+        print(ok_line)
+    dist.destroy_process_group()

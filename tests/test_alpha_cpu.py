@@ -7,8 +7,6 @@ import inspect
 import json
 import os
 import re
-import socket
-import sys
 
 import numpy as np
 import pytest
@@ -19,6 +17,7 @@ import torch.multiprocessing as mp
 import alpha_ref
 import oracle_C
 from dmesh_renderer_amd import scenes
+from harness import free_port
 from util import rel_err, upstream_grads
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -195,10 +194,6 @@ def test_default_modules_make_the_calls_they_made(ours):
 
 
 # ---- gloo, world size 2, both partitions -----------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _sharded_scene():
     H, W, B = 88, 72, 2
     return scenes.layered_sheets(3, 7, B, H, W, seed=1), scenes.kuhn_tets(3, B, H, W, seed=2), B, H, W
@@ -219,9 +214,6 @@ def _run_tet(r, d, gc, gd, ga):
 
 
 def _worker(rank, world, port, out_dir):
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ["OMP_NUM_THREADS"] = "2"
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -250,7 +242,7 @@ def _worker(rank, world, port, out_dir):
 def test_two_rank_sharded_alpha_equals_single_rank(tmp_path, ours):
     """ShardedTriRenderer (both partitions) and ShardedTetRenderer with return_alpha=True on two gloo ranks: every rank
     ends with the images and gradients of the single-rank Module."""
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
     tri, tet, B, H, W = _sharded_scene()
     gc, gd = upstream_grads(B, H, W)
     ga = _alpha_upstream(B, H, W)

@@ -8,31 +8,22 @@ Bounds (the project's own): alpha 1e-5 absolute; gradients rel_err <= 1e-4; colo
 call without the flag; every gradient but faces_opacity within 1e-5 of the call without alpha.  Every case prints what it
 measured (pytest -s); the figures taken on the MI355X are quoted in the README.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch as th
 
 import alpha_ref
 from dmesh_renderer_amd import scenes
+from grad_cases import TRI_CASES, seq_state
+from harness import capture_replay, module_step, replay, run_ranks
 from util import c_args, rel_err, upstream_grads
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 FWD_TOL = 1e-5
 GRAD_TOL = 1e-4
 SAME_TOL = 1e-5
 
-TRI_CASES = {
-    # name: (L, n, B, H, W, rows) -- the cases of tests/test_tri_exact_grads_gpu.py
-    "one_view": (3, 9, 1, 96, 128, (0, 0)),
-    "two_views_ragged": (3, 8, 2, 88, 152, (0, 0)),
-    "band": (3, 9, 2, 96, 128, (1, 4)),
-}
 TET_CASES = {
     # name: (m, B, H, W, rows)
     "kuhn": (3, 2, 64, 96, (0, 0)),
@@ -130,11 +121,6 @@ def test_tri_alpha_scanned_path(oracle, hip_device):
     _check_tri(oracle, hip_device, d, B, H, W, (0, 0), "scanned", options=False)
 
 
-def _seq_state(_C, args, bufs, H, W):
-    longest, cap = _C.export("tet_seq", args, True, 0, bufs, H, W, th.int32).cpu().numpy().view(np.uint32)[:2]
-    return int(longest), int(cap)
-
-
 @pytest.mark.parametrize("case", list(TET_CASES))
 def test_tet_alpha_matches_oracle(oracle, hip_device, case):
     """Call 0 is the first of its view configuration (no march sequence: the re-marching k_tet_backward), call 1 runs
@@ -160,7 +146,7 @@ def test_tet_alpha_matches_oracle(oracle, hip_device, case):
         outa = _C.render_tets(*args, H, W, 0, rows=rows, alpha=True)
         gra = _np(_C.render_tets_backward(*args, gcd, gdad, *outa[3:7], rows=rows, alpha=True))
         th.cuda.synchronize()
-        longest, cap = _seq_state(_C, args, outa[3:7], H, W)
+        longest, cap = seq_state(_C, args, outa[3:7], H, W)
         assert (cap == 0) if call == 0 else (0 < longest <= cap), (call, longest, cap)
         gin = _np(_C.render_tets_backward(*args, th.zeros_like(gcd), g_inactive, *outa[3:7], rows=rows, alpha=True))
         gopt = {kw: _np(_C.render_tets_backward(*args, gcd, gdad, *outa[3:7], rows=rows, alpha=True, **{kw: True}))
@@ -236,17 +222,14 @@ def test_modules_through_autograd(oracle, hip_device):
     _, _, oactive, ost = oracle.tet_forward(sc)
     gc, gd, ga, gcd, _, gdd = _upstream(B, H, W, (0, 0), dev)
     t = {k: v.to(dev) for k, v in d.items()}
-    vc, fo = t["verts_color"].clone().requires_grad_(True), t["faces_opacity"].clone().requires_grad_(True)
-    color, depth, active, alpha = dmr.TetRenderer(dmr.TetRenderSettings(H, W, t["bg"], 0), return_alpha=True)(
-        t["verts"], t["faces"], vc, fo, t["mv_mats"], t["proj_mats"], t["verts_depth"], t["faces_intense"], t["tets"], t["face_tets"],
-        t["tet_faces"])
+    (color, depth, active, alpha), g = module_step(dmr.TetRenderer(dmr.TetRenderSettings(H, W, t["bg"], 0), return_alpha=True), t,
+                                                   ("verts_color", "faces_opacity"), [gcd, gdd, ga.to(dev)])
     assert active.dtype == th.bool and tuple(alpha.shape) == (B, 1, H, W)
-    assert np.abs(alpha.detach().cpu().numpy() - alpha_ref.expected_alpha(sc, ost, True, active=oactive)).max() <= FWD_TOL
-    th.autograd.backward([color, depth, alpha], [gcd, gdd, ga.to(dev)])
+    assert np.abs(alpha.cpu().numpy() - alpha_ref.expected_alpha(sc, ost, True, active=oactive)).max() <= FWD_TOL
     og = oracle.tet_backward(sc, ost, gc.numpy(), gd.numpy())
-    e = rel_err(fo.grad.cpu().numpy(), og["faces_opacity"] + alpha_ref.alpha_opacity_grad(sc, ga.numpy(), True))
+    e = rel_err(g["faces_opacity"].cpu().numpy(), og["faces_opacity"] + alpha_ref.alpha_opacity_grad(sc, ga.numpy(), True))
     print(f"tet Module, loss on all: dL_dfaces_opacity {e:.2e}")
-    assert e <= GRAD_TOL and rel_err(vc.grad.cpu().numpy(), og["verts_color"]) <= GRAD_TOL
+    assert e <= GRAD_TOL and rel_err(g["verts_color"].cpu().numpy(), og["verts_color"]) <= GRAD_TOL
 
 
 def test_binding_checks_the_two_channel_gradient(hip_device):
@@ -273,20 +256,8 @@ def test_alpha_step_replays_as_graph(hip_device):
         out = _C.render_tris(*args, H, W, alpha=True)
         return (out[1], out[2]) + tuple(_C.render_tris_backward(*args, gcd, gdad, out[0], *out[3:7], alpha=True))
 
-    s = th.cuda.Stream()
-    s.wait_stream(th.cuda.current_stream())
-    with th.cuda.stream(s):
-        for _ in range(2):  # the size estimates the capture needs
-            eager = [x.clone() for x in step()]
-    th.cuda.current_stream().wait_stream(s)
-    th.cuda.synchronize()
-    _C.overflowed()
-    g = th.cuda.CUDAGraph()
-    with th.cuda.graph(g):
-        captured = step()
-    g.replay()
-    th.cuda.synchronize()
-    assert not _C.overflowed()
+    graph, captured, eager = capture_replay(step)
+    replay(graph)
     assert float(eager[1][:, 1].max()) > 0.3
     for a, b_ in zip(captured, eager):
         assert rel_err(a.cpu().numpy(), b_.cpu().numpy()) <= SAME_TOL
@@ -294,8 +265,4 @@ def test_alpha_step_replays_as_graph(hip_device):
 
 def test_two_ranks_alpha_match_single_rank(hip_device):
     """Sharded Modules with return_alpha=True, two ranks (gloo, one GPU), against the single-device Modules."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", os.path.join(HERE, "sharded_alpha_child.py")]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
-    assert r.returncode == 0 and "sharded alpha ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    run_ranks("alpha", "sharded alpha ok")

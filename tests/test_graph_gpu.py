@@ -13,6 +13,7 @@ import torch as th
 
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import scenes
+from harness import capture_replay, replay
 from util import c_args, rel_err, upstream_grads
 
 pytestmark = pytest.mark.gpu
@@ -46,19 +47,11 @@ def test_tri_step_replays_as_one_graph(hip_device, oracle):
         th.autograd.backward([color, depth], [gcd, gdd])
         return color, depth
 
-    # warm-up on a side stream: default (waiting) calls, which also leave the size estimates the captured calls need
-    s = th.cuda.Stream()
-    s.wait_stream(th.cuda.current_stream())
-    with th.cuda.stream(s):
-        for _ in range(2):
-            step()
-    th.cuda.current_stream().wait_stream(s)
-    for v in leaves.values():
-        v.grad = None
-    dmr._C.overflowed()  # clear
-    g = th.cuda.CUDAGraph()
-    with th.cuda.graph(g):
-        color, depth = step()
+    def reset():
+        for v in leaves.values():
+            v.grad = None
+
+    g, (color, depth), _ = capture_replay(step, reset=reset)
     gen = th.Generator().manual_seed(11)
     for it in range(3):
         d2 = dict(d)
@@ -68,9 +61,7 @@ def test_tri_step_replays_as_one_graph(hip_device, oracle):
         with th.no_grad():
             for k in ("verts", "verts_color", "faces_opacity"):
                 leaves[k].copy_(d2[k].to(dev))
-        g.replay()
-        th.cuda.synchronize()
-        assert not dmr._C.overflowed(), "the replayed scene outgrew the captured capacity"
+        replay(g)
         oc, od, og = _oracle_tri(oracle, d2, H, W, gc, gd)
         assert np.abs(color.detach().cpu().numpy() - oc).max() <= FWD_TOL and np.abs(depth.detach().cpu().numpy() - od).max() <= FWD_TOL, it
         for k in TRI_NAMES:
@@ -95,17 +86,10 @@ def test_tet_step_replays_as_one_graph(hip_device, oracle):
         th.autograd.backward([color, depth], [gcd, gdd])
         return color, depth, active
 
-    s = th.cuda.Stream()
-    s.wait_stream(th.cuda.current_stream())
-    with th.cuda.stream(s):
-        for _ in range(2):
-            step()
-    th.cuda.current_stream().wait_stream(s)
-    vc.grad = None; fo.grad = None
-    dmr._C.overflowed()
-    g = th.cuda.CUDAGraph()
-    with th.cuda.graph(g):
-        color, depth, active = step()
+    def reset():
+        vc.grad = None; fo.grad = None
+
+    g, (color, depth, active), _ = capture_replay(step, reset=reset)
     gen = th.Generator().manual_seed(5)
     for it in range(3):
         d2 = dict(d)
@@ -113,9 +97,7 @@ def test_tet_step_replays_as_one_graph(hip_device, oracle):
         d2["faces_opacity"] = th.rand(d["faces_opacity"].shape, generator=gen) * 0.3 + 0.02
         with th.no_grad():
             vc.copy_(d2["verts_color"].to(dev)); fo.copy_(d2["faces_opacity"].to(dev))
-        g.replay()
-        th.cuda.synchronize()
-        assert not dmr._C.overflowed()
+        replay(g)
         sc = oracle.scene_from_module_inputs(d2, H, W)
         oc, od, oa, ost = oracle.tet_forward(sc)
         og = oracle.tet_backward(sc, ost, gc.numpy(), gd.numpy())
@@ -229,22 +211,16 @@ def test_capture_on_an_empty_band(hip_device):
     gc, gd = upstream_grads(B, H, W)
     gcd, gdd = gc.to(dev), gd.to(dev)
     rows = (gy, gy)
-    s = th.cuda.Stream()
-    s.wait_stream(th.cuda.current_stream())
-    with th.cuda.stream(s):
-        o = _C.render_tris(*args, H, W, rows=rows)   # warm-up, default calls
-        assert o[0] == 0
-        _C.render_tris_backward(*args, gcd, gdd, o[0], *o[3:7], rows=rows)
-    th.cuda.current_stream().wait_stream(s)
-    _C.overflowed()
-    g = th.cuda.CUDAGraph()
-    with th.cuda.graph(g):
+    rendered = []
+
+    def step():
         o = _C.render_tris(*args, H, W, rows=rows)
-        grads = _C.render_tris_backward(*args, gcd, gdd, o[0], *o[3:7], rows=rows)
-    for _ in range(2):
-        g.replay()
-    th.cuda.synchronize()
-    assert not _C.overflowed()
+        rendered.append(o[0])
+        return _C.render_tris_backward(*args, gcd, gdd, o[0], *o[3:7], rows=rows)
+
+    g, grads, _ = capture_replay(step, warmup=1)
+    assert rendered[0] == 0  # the warm-up: a default call
+    replay(g, times=2)
     assert all(float(t.abs().sum()) == 0.0 for t in grads)
 
 

@@ -2,8 +2,6 @@
 stand-in.  Checks the sharding logic itself: band split, band rendering, image assembly and the
 single flattened gradient all-reduce give every rank the same result as one unsharded render."""
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
@@ -11,18 +9,10 @@ import torch as th
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+from harness import free_port
 
 
 def _worker(rank, world, port, out_dir):
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ["OMP_NUM_THREADS"] = "2"
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -52,8 +42,7 @@ def _worker(rank, world, port, out_dir):
 
 def test_two_rank_band_sharding(tmp_path, oracle):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
-    sys.path.insert(0, HERE)
+    mp.spawn(_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     import oracle_C
     from dmesh_renderer_amd import scenes
     H, W, B = 88, 72, 2
@@ -77,9 +66,6 @@ def test_two_rank_band_sharding(tmp_path, oracle):
 def _view_worker(rank, world, port, out_dir):
     """The "view_bands" partition: B = 2 views on `world` ranks (2: one view per rank; 4: two bands per view; 3: the middle
     rank's share straddles the view border -- two segments, two B = 1 calls)."""
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ["OMP_NUM_THREADS"] = "1"
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -125,8 +111,7 @@ def test_view_band_sharding(tmp_path, oracle, world):
     """with B views, (view, band) segments -- the rows of all views cut into `world` contiguous shares, every
     segment rendered with B = 1 tensors; one all-gather assembles the images, ONE all-reduce over the all-views flat buffer
     sums the gradients (a rank's per-view gradients are its views' rows, zero elsewhere).  Every rank ends with the unsharded result."""
-    mp.spawn(_view_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
-    sys.path.insert(0, HERE)
+    mp.spawn(_view_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     import oracle_C
     from dmesh_renderer_amd import scenes
     H, W, B = 88, 72, 2
@@ -150,9 +135,6 @@ def test_view_band_sharding(tmp_path, oracle, world):
 
 
 def _tet_worker(rank, world, port, out_dir):
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ["OMP_NUM_THREADS"] = "2"
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -179,8 +161,7 @@ def test_two_rank_tet_band_sharding(tmp_path, oracle):
     """ShardedTetRenderer ("the tet path shards identically"): bands of the march, one all-gather of the
     three images, ONE all-reduce over [3P | F] -- every rank ends with the unsharded result."""
     world = 2
-    mp.spawn(_tet_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
-    sys.path.insert(0, HERE)
+    mp.spawn(_tet_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     import oracle_C
     from dmesh_renderer_amd import scenes
     H, W, B = 88, 72, 2
@@ -218,9 +199,6 @@ def test_band_balance_counts_tiles_as_well_as_list_entries():
     C5: profiles/r03/shard_kernel_sums_c5*.json).  A frame whose entries sit in the middle rows: balanced by entries alone the
     edge bands get most of the (nearly empty) rows; with the per-tile cost they give rows up, every band still holds work, and
     the bands still partition the rows."""
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     from dmesh_renderer_amd import sharding
     B, gy, gx = 2, 64, 48
     lens = np.zeros((B, gy, gx), dtype=np.int64)
@@ -264,9 +242,6 @@ def test_row_work_counts_blended_pairs_when_given():
     """With `tile_hits` (blended pairs per tile of a forward) the work of a row is entries + PAIR_COST_ENTRIES per pair +
     TILE_COST_ENTRIES_WITH_PAIRS per tile (the model fitted in profiles/r03/shard_cost_model_c5.txt): two rows with the same
     list entries but different coverage no longer weigh the same."""
-    for p in (ROOT, HERE):
-        if p not in sys.path:
-            sys.path.insert(0, p)
     from dmesh_renderer_amd import sharding
     B, gy, gx = 1, 4, 8
     lens = np.full((B, gy, gx), 100, dtype=np.int64)

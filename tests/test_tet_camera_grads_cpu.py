@@ -9,6 +9,8 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
+from grad_cases import scene
+from harness import free_port
 from standins import _FakeC
 from tet_camera_grad_ref import TetCameraGradRef
 from util import rel_err, upstream_grads
@@ -23,10 +25,7 @@ CASES = {  # name: (m, B, H, W, opacity, ray_random_seed)
 
 
 def _setup(oracle, case):
-    m, B, H, W, op, seed = CASES[case]
-    d = scenes.kuhn_tets(m, B, H, W, seed=0, opacity=op)
-    if case == "opaque":
-        d["faces_opacity"][::7] = 1.0
+    d, B, H, W, seed = scene(case, cases=CASES)
     sc = oracle.scene_from_module_inputs(d, H, W, seed=seed)
     ocolor, odepth, _, ost = oracle.tet_forward(sc)
     ref = TetCameraGradRef(d, H, W, ost, seed=seed)
@@ -171,9 +170,5 @@ def _gloo_worker(rank, world, port):
 def test_sharded_module_routes_camera_grads_on_gloo():
     """ShardedTetRenderer(camera_grads=True) on two gloo ranks (CPU, stand-in kernels): the keyword reaches every rank's
     backward and the matrix gradients are summed over the ranks."""
-    import socket
     import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mp.spawn(_gloo_worker, args=(2, port), nprocs=2, join=True)
+    mp.spawn(_gloo_worker, args=(2, free_port()), nprocs=2, join=True)

@@ -10,6 +10,7 @@ import torch as th
 
 import capi_ctypes
 from dmesh_renderer_amd import scenes
+from grad_cases import scene
 from standins import _FakeC
 from tet_grad_ref import TetGradRef
 from util import rel_err, upstream_grads
@@ -24,10 +25,7 @@ CASES = {  # name: (m, B, H, W, opacity, ray_random_seed) -- a smaller "small" t
 
 
 def _setup(oracle, case):
-    m, B, H, W, op, seed = CASES[case]
-    d = scenes.kuhn_tets(m, B, H, W, seed=0, opacity=op)
-    if case == "opaque":
-        d["faces_opacity"][::7] = 1.0
+    d, B, H, W, seed = scene(case, cases=CASES)
     sc = oracle.scene_from_module_inputs(d, H, W, seed=seed)
     ocolor, odepth, _, ost = oracle.tet_forward(sc)
     return d, B, H, W, sc, ocolor, odepth, ost
