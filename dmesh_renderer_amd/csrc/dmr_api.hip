@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "dmr_kernels.hpp"
+#include "dmr_placement_key.hpp"
 
 namespace {
 
@@ -61,6 +62,8 @@ struct Carver {
 
 struct PointState { float4* vproj; };
 struct FaceState { uint2* rect; float* key_depth; float* max_depth; uint32_t* tiles_touched; void* facerec; void* colrec; void* tetrec; };
+// (tile_count and FaceState::rect are the exact path's: behind launch_bin_faces tile_count stays zero -- a tile's count is
+// tile_cursor - tile_offset there -- and rect keeps what an earlier call left; nothing reads either afterwards)
 struct ImageState {
     uint32_t* tile_count; uint32_t* tile_offset; uint32_t* tile_cursor; int* num_rendered;
     float* final_T; float* final_prev_T; uint32_t* n_contrib;
@@ -149,7 +152,7 @@ Scratch carve_scratch(const dmr_scene* s, bool tet, const Dims& d, const void* p
 }
 dmr::TriImageState tri_image(const Scratch& c) {
     const ImageState& is = c.is;
-    return {is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.mask_offset};
+    return {is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.tile_cursor, is.mask_offset};
 }
 dmr::TetImageState tet_image(const Scratch& c) {
     const ImageState& is = c.is;
@@ -288,6 +291,72 @@ double lookup_estimate(const SizeKey& key, double SizeGuess::* field) {
 }
 uint64_t padded(uint64_t n) { return n + n / 4 + 4096; }
 
+// Speculative PLACEMENT of the tile segments (tri, single frames up to SCAN_SINGLE_MAX tiles).  The exact path counts every
+// (face, tile) pair, scans the counts in one workgroup and visits every face again to scatter: three dependent launches
+// whose only purpose is to know where a tile's list starts.  Like the sizes above, that is taken from the previous call of
+// the key instead: a default call that went through the exact path (the first one of a key, and every redo) leaves, in
+// device memory the library owns, a segment per tile -- room for its count + 25 % + SEG_SLACK entries, in tile order -- and
+// its tile order.  Later calls of the key bin in ONE kernel straight into those segments (launch_bin_faces); a tile that
+// outgrew its segment raises the overflow bit of the size word (default call: redone through the exact path, which
+// refreshes the placement; asynchronous call: the sticky overflow word).  The arrays are allocated once per key and
+// rewritten in place, so a captured graph keeps valid addresses; the capacity a graph was captured with bounds every
+// store of its replays.  A default call whose R fell below HALF the R the placement was built from drops it: the next
+// default call rebuilds it through the exact path (a shrinking scene does not keep a stale order and padding for ever).
+struct Placement { uint32_t* start = nullptr; uint32_t* order = nullptr; int ntiles = 0; uint64_t capacity = 0, built_from = 0; bool valid = false; };
+// Keyed by DEVICE and view configuration (dmr_placement_key.hpp): the arrays are memory of the device that built them, and a
+// device only ever sees arrays it allocated.  g_placement_mu is held over a whole build (allocate, rewrite, publish), so two
+// threads' first default calls of one key neither allocate twice nor rewrite arrays the other one is about to hand out; the
+// arrays live as long as the process (one pair per key and device).
+std::mutex g_placement_mu;
+std::map<dmr::PlacementKey, Placement> g_placement;  // g_size_mu
+int current_device() { int dev = 0; if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; } return dev; }
+dmr::PlacementKey placement_key(const SizeKey& key) { return dmr::placement_key(current_device(), key.v, 7); }
+uint64_t placement_capacity(uint64_t R, int ntiles) { return R + R / 4 + (uint64_t)dmr::SEG_SLACK * (uint64_t)ntiles; }  // >= the segments' sum
+bool placement_eligible(bool tet, const Dims& d) { return !tet && d.ntiles <= dmr::SCAN_SINGLE_MAX; }
+Placement find_placement(const SizeKey& key, const Dims& d) {
+    const dmr::PlacementKey pk = placement_key(key);
+    if (pk.device < 0) return Placement{};
+    std::lock_guard<std::mutex> lk(g_size_mu);
+    auto it = g_placement.find(pk);
+    return it != g_placement.end() && it->second.valid && it->second.ntiles == d.ntiles ? it->second : Placement{};
+}
+void drop_placement(const SizeKey& key) {
+    const dmr::PlacementKey pk = placement_key(key);
+    std::lock_guard<std::mutex> lk(g_size_mu);
+    auto it = g_placement.find(pk);
+    if (it != g_placement.end()) it->second.valid = false;
+}
+// From the counts and the order a default call's exact path left in its image buffer (never inside a capture).  Calls of the
+// key that are still in flight on other streams read the arrays: the device is drained before they are rewritten, and the
+// stream before the next call can use them.
+int build_placement(const SizeKey& key, const Dims& d, uint64_t R, const ImageState& is, hipStream_t st) {
+    const uint64_t capacity = placement_capacity(R, d.ntiles);
+    if (capacity > 0x7fffffffu) { drop_placement(key); return 0; }
+    const dmr::PlacementKey pk = placement_key(key);
+    if (pk.device < 0) return 0;
+    std::lock_guard<std::mutex> build_lk(g_placement_mu);
+    Placement p;
+    {
+        std::lock_guard<std::mutex> lk(g_size_mu);
+        p = g_placement[pk];
+        g_placement[pk].valid = false;  // nobody takes it up while it is being rewritten
+    }
+    if (p.start && p.ntiles != d.ntiles) return 0;  // (cannot happen: the key holds B, W, H)
+    if (!p.start) {
+        void* mem = nullptr;
+        DMR_HIP(hipMalloc(&mem, sizeof(uint32_t) * (2 * (size_t)d.ntiles + 1)));
+        p.start = reinterpret_cast<uint32_t*>(mem); p.order = p.start + d.ntiles + 1; p.ntiles = d.ntiles;
+    } else {
+        DMR_HIP(hipDeviceSynchronize());
+    }
+    dmr::launch_build_placement(d.ntiles, is.tile_count, is.tile_order, p.start, p.order, st);
+    DMR_HIP(hipStreamSynchronize(st));
+    p.capacity = capacity; p.built_from = R; p.valid = true;
+    std::lock_guard<std::mutex> lk(g_size_mu);
+    g_placement[pk] = p;
+    return 0;
+}
+
 // tet: the key's SizeGuess::seq_steps word (created by a default forward: create; null: none) and, if asked for, the room for
 // the next forward's march sequence: the longest march + 25 %, a multiple of 4, within a memory budget (0: no march reported
 // yet, that call's backward re-marches).
@@ -361,7 +430,7 @@ int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_
 // Stages shared by both renderers up to the sorted per-tile lists, then `render` (the renderer's own kernels, which only need
 // the scratch buffers, the binning buffer included).
 int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc, void* ctx, hipStream_t st, int* num_rendered,
-                const std::function<void(const Scratch&)>& render) {
+                const std::function<void(const Scratch&, dmr::ListSize)>& render) {
     const Scratch need = carve_scratch(s, tet, d, nullptr, nullptr, nullptr);
     void* pb = alloc(ctx, DMR_BUF_POINT, need.point_bytes);
     void* fb = alloc(ctx, DMR_BUF_FACE, need.face_bytes);
@@ -373,6 +442,8 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
     const SizeKey key = size_key(s, tet, d);
     size_t seq_steps = 0;
     if (tet) march_estimate(key, d, !async, &seq_steps);
+    const bool placed = placement_eligible(tet, d);
+    const Placement pl = placed ? find_placement(key, d) : Placement{};
 
     auto front = [&](SizeOut out) {
         // (tile_count | tile_hits | tile_bound are contiguous: zeroed by k_project_verts, a slice per block)
@@ -397,7 +468,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
             if (d.ntiles > dmr::SCAN_SINGLE_MAX)
                 dmr::launch_sort_tiles(d.ntiles, is.tile_offset, is.tile_order, bs.keys, bs.face_list, bs.capacity, st);
         }
-        render(c);
+        render(c, dmr::ListSize{nullptr, nullptr, 0u, nullptr, 0u});
         return 0;
     };
 
@@ -405,11 +476,62 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
                               "asynchronous / captured call without a size estimate: run one default (waiting) call with the same "
                               "view configuration first"};
     uint64_t R = 0;
+    if (pl.valid) {  // speculative placement: projection -> one binning kernel -> render, whose first workgroup leaves the size word
+        auto binned = [&](SizeOut out) -> int {
+            BinningState& bs = c.bs;
+            BinningState tb;
+            void* bb = alloc(ctx, DMR_BUF_BINNING, carve_binning(nullptr, (size_t)pl.capacity, (size_t)d.ntiles, 0, 0, tb));
+            if (!bb) return fail("binning allocation failed");
+            carve_binning(bb, (size_t)pl.capacity, (size_t)d.ntiles, 0, 0, bs);
+            dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st,
+                                      dmr::SegInit{pl.start, pl.order, is.tile_offset, is.tile_cursor, is.tile_order, (uint32_t)d.ntiles});
+            dmr::launch_bin_faces(*s, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.tiles_touched, is.tile_offset, is.tile_cursor, bs.keys,
+                                  bs.capacity, is.mask_offset, bs.mask_offset, bs.mask_first, st);
+            render(c, dmr::ListSize{is.num_rendered, out.host, out.seq, out.overflow, 1u});  // (its first workgroup publishes R)
+            return 0;
+        };
+        int dev = 0;
+        DMR_HIP(hipGetDevice(&dev));
+        uint32_t* overflow = overflow_word(dev, !async);
+        if (async) {
+            if (!overflow) return fail(list_entries.no_estimate);
+            if (binned(SizeOut{nullptr, 0u, overflow, (uint32_t)pl.capacity})) return 1;
+            *num_rendered = (int)pl.capacity;  // an upper bound the backward accepts in R's place
+            DMR_HIP(hipGetLastError());
+            return 0;
+        }
+        SizeRead& sr = g_size_read[dev];
+        if (!sr.slot && !(sr.slot = pinned_words())) return fail("hipHostMalloc failed");
+        const uint32_t seq = sr.next_seq();
+        if (binned(SizeOut{const_cast<unsigned long long*>(sr.word(list_entries.word)), seq, nullptr, 0xffffffffu})) return 1;
+        unsigned long long n = 0;
+        if (wait_size(sr.word(list_entries.word), seq, st, &n)) return 1;
+        const bool full = (n & dmr::SIZE_WORD_OVERFLOW) != 0;
+        R = n & (dmr::SIZE_WORD_OVERFLOW - 1ull);
+        if (R > list_entries.limit) return fail(list_entries.too_large);
+        if (full) {  // a tile outgrew its segment: the exact path, which also refreshes the placement
+            g_redo_count.fetch_add(1, std::memory_order_relaxed);
+            DMR_HIP(hipStreamSynchronize(st));
+            front(NOWHERE);
+            if (rest(R)) return 1;
+            if (build_placement(key, d, R, is, st)) return 1;
+        } else if (2 * R < pl.built_from) {
+            drop_placement(key);
+        }
+        {
+            std::lock_guard<std::mutex> lk(g_size_mu);
+            g_size_cache[key].rendered_per_face = (double)std::max<uint64_t>(R, 1) / (double)std::max<size_t>(d.BF, 1);
+        }
+        *num_rendered = (int)R;
+        DMR_HIP(hipGetLastError());
+        return 0;
+    }
     // a redo enqueues the front again too: the scatter pass has used up the tile cursors
-    const int rc = sized(list_entries, key, d.BF, async, st, &R,
-                         [&](uint64_t guess, SizeOut out) { front(out); return guess ? rest(guess) : 0; },
-                         [&](uint64_t exact, bool redo) { if (redo) front(NOWHERE); return rest(exact); });
+    int rc = sized(list_entries, key, d.BF, async, st, &R,
+                   [&](uint64_t guess, SizeOut out) { front(out); return guess ? rest(guess) : 0; },
+                   [&](uint64_t exact, bool redo) { if (redo) front(NOWHERE); return rest(exact); });
     *num_rendered = (int)R;
+    if (rc == 0 && placed && !async) rc = build_placement(key, d, R, is, st);
     return rc;
 }
 
@@ -504,11 +626,11 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
     *num_rendered = 0;
     if (s->P == 0 || s->F == 0) return 0;  // render.cu:105 (and Q16: F == 0)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    auto render = [&](const Scratch& c) {
+    auto render = [&](const Scratch& c, dmr::ListSize size) {
         const dmr_scene sc = canonical(s, c.is.mats);
         dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, c.is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys,
                                 c.bs.face_list, c.bs.capacity, tri_image(c), out_color,
-                                out_depth, st, (s->flags & DMR_FLAG_ALPHA) != 0);
+                                out_depth, st, (s->flags & DMR_FLAG_ALPHA) != 0, size);
     };
     return run_forward(s, false, d, alloc, ctx, st, num_rendered, render);
 }
@@ -589,7 +711,7 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     const bool self_regions = d.ntiles <= dmr::SCAN_SINGLE_MAX;
     auto first = [&](uint64_t guess, SizeOut out) -> int {
         if (guess && self_regions) return rest(guess, self_laid(out));
-        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.hit_offset, is.tile_used, is.hit_total, out.host, out.seq,
+        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.tile_cursor, is.hit_offset, is.tile_used, is.hit_total, out.host, out.seq,
                               is.scan_tmp, out.capacity, out.overflow, st);
         return guess ? rest(guess, scanned) : 0;
     };
@@ -609,7 +731,7 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
     if (!alloc || !num_rendered || !out_color || !out_depth || !out_active) return fail("null argument");
     *num_rendered = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    auto render = [&](const Scratch& c) {
+    auto render = [&](const Scratch& c, dmr::ListSize) {
         const dmr::TetImageState img = tet_image(c);
         const dmr_scene sc = canonical(s, c.is.mats);
         dmr::launch_tet_prep(sc, img, c.bs.seq_steps, c.bs.seq_offset, st);
@@ -740,6 +862,32 @@ int64_t dmr_export(const dmr_scene* s, int is_tet, int num_rendered, const char*
         if (dst && d.BP && (size_t)cap >= bytes)
             k_export_vproj<<<dim3((unsigned)((d.BP + 255) / 256)), dim3(256), 0, st>>>(
                 c.ps.vproj, (int64_t)d.BP, n == "image" ? 0 : 1, reinterpret_cast<float*>(dst));
+        return (int64_t)bytes;
+    }
+    // Tri lists up to SCAN_SINGLE_MAX tiles may lie in padded segments (speculative placement): [tile_offset, list end).  The
+    // exports stay what the exact path's are -- contiguous ranges, packed face_list -- compacted here on the host (a waiting,
+    // untimed debug path either way).
+    if (!is_tet && d.ntiles <= dmr::SCAN_SINGLE_MAX && (n == "ranges" || n == "face_list")) {
+        const size_t nt = (size_t)d.ntiles, R = (size_t)std::max(0, num_rendered);
+        const size_t bytes = n == "ranges" ? nt * 8 : R * 4;
+        if (!dst || (size_t)cap < bytes || bytes == 0) return (int64_t)bytes;
+        if (!image_buf || (n == "face_list" && !binning_buf)) { g_err = "null scratch buffer"; return -1; }
+        std::vector<uint32_t> off(nt + 1), end(nt), out(bytes / 4, 0u);
+        if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(off.data(), is.tile_offset, 4 * (nt + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(end.data(), is.tile_cursor, 4 * nt, hipMemcpyDeviceToHost) != hipSuccess) { g_err = "export copy failed"; return -1; }
+        std::vector<uint32_t> lists;
+        if (n == "face_list") {
+            lists.resize(off[nt]);
+            if (off[nt] && hipMemcpy(lists.data(), c.bs.face_list, 4 * (size_t)off[nt], hipMemcpyDeviceToHost) != hipSuccess) { g_err = "export copy failed"; return -1; }
+        }
+        size_t run = 0;
+        for (size_t t = 0; t < nt; t++) {
+            const size_t len = dmr::list_end(off.data(), end.data(), (int)t) - off[t];
+            if (n == "ranges") { out[2 * t] = len ? (uint32_t)run : 0u; out[2 * t + 1] = len ? (uint32_t)(run + len) : 0u; }
+            else for (size_t k = 0; k < len && run + k < R; k++) out[run + k] = lists[off[t] + k];
+            run += len;
+        }
+        if (hipMemcpy(dst, out.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { g_err = "export copy failed"; return -1; }
         return (int64_t)bytes;
     }
     if (n == "ranges") {

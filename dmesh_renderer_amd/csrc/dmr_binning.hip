@@ -39,11 +39,20 @@ k_project_verts(int B, int P, const float* __restrict__ verts, const float* __re
                 const float* __restrict__ proj_mats, const float* __restrict__ inv_mv_mats,
                 const float* __restrict__ inv_proj_mats, int transposed, const float* __restrict__ verts_depth,
                 int W, int H, float4* __restrict__ vproj, float* __restrict__ mats,
-                uint32_t* __restrict__ counters, uint32_t ncounters) {
+                uint32_t* __restrict__ counters, uint32_t ncounters, SegInit seg) {
     {   // every block zeroes a slice of the tile counters (tile_count | tile_hits) the next kernels add into
         const uint32_t per = (ncounters + gridDim.x - 1) / gridDim.x;
         const uint32_t z0 = min(ncounters, blockIdx.x * per), z1 = min(ncounters, z0 + per);
         for (uint32_t i = z0 + threadIdx.x; i < z1; i += 256) counters[i] = 0u;
+    }
+    if (seg.start) {  // speculative placement (k_bin_faces): segment starts -> offsets and cursors, the order as it stands
+        const uint32_t n = seg.ntiles + 1u, per = (n + gridDim.x - 1) / gridDim.x;
+        const uint32_t z0 = min(n, blockIdx.x * per), z1 = min(n, z0 + per);
+        for (uint32_t i = z0 + threadIdx.x; i < z1; i += 256) {
+            const uint32_t o = seg.start[i];
+            seg.tile_offset[i] = o;
+            if (i < seg.ntiles) { seg.tile_cursor[i] = o; seg.tile_order[i] = seg.order[i]; }
+        }
     }
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < 64 * B; i += 256) {
@@ -316,6 +325,139 @@ k_scatter_faces_lds(int B, int F, int gx, int gy, const uint2* __restrict__ face
 }
 
 // ---------------------------------------------------------------------------
+// 2 + 4 in one visit of every face (tri, frames up to SCAN_SINGLE_MAX tiles, a placement exists: dmr_api.hip).  Every tile's
+//   segment [seg[t], seg[t + 1]) was placed from an earlier call's counts (k_build_placement), the cursors start at the
+//   segment starts (k_project_verts), so nothing has to be counted and scanned before entries can be emitted: the workgroup
+//   culls / bounds / keys its faces as the set-up pass does, counts them into its LDS window, reserves every non-empty bin
+//   with one returning atomic on the tile's cursor and hands the slots out with returning LDS atomics as the scatter pass
+//   does.  A reservation that ends behind its segment (or behind the buffer) emits NOTHING -- its bin hands out slots from
+//   SEG_FULL on, which no buffer holds; the cursor, which advances by the true count all the same, then stands behind the
+//   segment's end, which is how the compositing kernels recognise such a tile (they render it empty; the call is redone or flagged)
+//   and how the forward's size workgroup (ListSize, dmr_kernels.hpp) sees the overflow; R is the sum of cursor - start.
+//   No workgroup waits for another, and none touches a word that all the others touch.
+// ---------------------------------------------------------------------------
+constexpr uint32_t SEG_FULL = 0xC0000000u;
+
+template <int FPT>
+__global__ void __launch_bounds__(256)
+k_bin_faces(int B, int P, int F, const int* __restrict__ faces, const float4* __restrict__ vproj, int gx, int gy, int r0, int r1,
+            float* __restrict__ key_depth, uint32_t* __restrict__ tiles_touched, const uint32_t* __restrict__ seg,
+            uint32_t* __restrict__ tile_cursor, uint64_t* __restrict__ keys, uint32_t capacity,
+            unsigned long long* __restrict__ mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first) {
+    if (mask_offset_dst && blockIdx.x == 0 && threadIdx.x == 0) { mask_offset_dst[0] = mask_offset; mask_offset_dst[1] = mask_first; }
+    __shared__ uint32_t s_hist[LDS_HIST_MAX];
+    __shared__ int s_box[4];
+    __shared__ BigFace s_big[BIG_MAX];
+    __shared__ uint32_t s_nbig;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_nbig = 0u;  // (bin_window's barriers order this before the queueing below)
+    const int64_t BF = (int64_t)B * F;
+    const int64_t base = (int64_t)blockIdx.x * (256 * FPT);
+    const int view = (int)(base / F);
+    uint2 rr[FPT];
+    uint32_t touched[FPT], kd[FPT];
+    bool mine[FPT];  // face of the window's view
+#pragma unroll
+    for (int it = 0; it < FPT; it++) {
+        const int64_t idx = base + it * 256 + tid;
+        touched[it] = 0u; rr[it] = make_uint2(0, 0); mine[it] = false; kd[it] = 0u;
+        if (idx >= BF) continue;
+        const int b = (int)(idx / F), f = (int)(idx % F);
+        mine[it] = b == view;
+        const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
+        const float4 a0 = vproj[(int64_t)b * P + v0], a1 = vproj[(int64_t)b * P + v1], a2 = vproj[(int64_t)b * P + v2];
+        float max_z = a0.z, min_z = a0.z, depth = 0.0f;
+        depth += a0.z;
+        max_z = fmaxf(max_z, a1.z); min_z = fminf(min_z, a1.z); depth += a1.z;
+        max_z = fmaxf(max_z, a2.z); min_z = fminf(min_z, a2.z); depth += a2.z;
+        depth = depth / 3.0f;
+        Rect r = {0, 0, 0, 0};
+        if (!(max_z < -1.0f || min_z > 1.0f)) {
+            r = tile_rect({a0.x, a0.y}, {a1.x, a1.y}, {a2.x, a2.y}, gx, gy, r0, r1);
+            touched[it] = (r.maxy - r.miny) * (r.maxx - r.minx);
+        }
+        if (touched[it] == 0) r = {0, 0, 0, 0};
+        auto map01 = [](float z) { float d = (z + 1.0f) * 0.5f; if (d < 0.0f) d = 0.0f; if (d > 1.0f) d = 1.0f; return d; };
+        rr[it] = make_uint2(r.minx | (r.miny << 16), r.maxx | (r.maxy << 16));
+        const float k = touched[it] ? map01(depth) : 0.0f;
+        kd[it] = __float_as_uint(k);
+        tiles_touched[idx] = touched[it];
+        key_depth[idx] = k;
+    }
+    const BinWindow w = bin_window<FPT>(s_box, view, rr, touched, mine, tid);
+    const int nw = w.wx * w.wy;
+    for (int t = tid; t < nw; t += 256) s_hist[t] = 0u;
+    __syncthreads();
+    // pass 1: count this workgroup's entries per tile of the window
+#pragma unroll
+    for (int it = 0; it < FPT; it++) {
+        if (!(w.lds && mine[it]) || touched[it] == 0 || touched[it] > BIG_RECT) continue;
+        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
+        for (uint32_t y = miny; y < maxy; y++)
+            for (uint32_t x = minx; x < maxx; x++) atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
+    }
+    __syncthreads();
+    // reserve the workgroup's slots of every non-empty tile with one returning atomic; the bin now holds the cursor
+    for (int y = tid / 64; y < w.wy; y += 4)
+        for (int x = tid % 64; x < w.wx; x += 64) {
+            const uint32_t c = s_hist[y * w.wx + x];
+            if (c == 0u) continue;
+            const uint32_t tile = (uint32_t)view * gx * gy + (uint32_t)(w.y0 + y) * gx + (uint32_t)(w.x0 + x);
+            const uint32_t first = atomicAdd(&tile_cursor[tile], c);
+            s_hist[y * w.wx + x] = first + c <= min(seg[tile + 1], capacity) ? first : SEG_FULL;
+        }
+    __syncthreads();
+    // pass 2: hand out slots
+#pragma unroll
+    for (int it = 0; it < FPT; it++) {
+        if (touched[it] == 0) continue;
+        const int64_t idx = base + it * 256 + tid;
+        const int f = (int)(idx % F);
+        const uint32_t tb = (uint32_t)(idx / F) * gx * gy;
+        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
+        const uint64_t key = ((uint64_t)kd[it] << 32) | (uint32_t)f;
+        if (touched[it] > BIG_RECT) {
+            const uint32_t q = atomicAdd(&s_nbig, 1u);
+            if (q < (uint32_t)BIG_MAX) { s_big[q] = BigFace{rr[it].x, rr[it].y, tb, (uint32_t)key, (uint32_t)(key >> 32)}; continue; }
+        }
+        const bool direct = !(w.lds && mine[it]) || touched[it] > BIG_RECT;
+        for (uint32_t y = miny; y < maxy; y++)
+            for (uint32_t x = minx; x < maxx; x++) {
+                if (direct) {
+                    const uint32_t tile = tb + y * gx + x;
+                    const uint32_t slot = atomicAdd(&tile_cursor[tile], 1u);
+                    if (slot < min(seg[tile + 1], capacity)) keys[slot] = key;
+                } else {
+                    const uint32_t slot = atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
+                    if (slot < capacity) keys[slot] = key;  // (SEG_FULL and up: never)
+                }
+            }
+    }
+    __syncthreads();
+    const uint32_t nbig = min(s_nbig, (uint32_t)BIG_MAX);
+    for (uint32_t q = 0; q < nbig; q++) {
+        const BigFace f = s_big[q];
+        const uint64_t key = ((uint64_t)f.key_hi << 32) | f.key_lo;
+        // four returning atomics in flight per thread, as in the scatter pass
+        for (RectWalk t(f.rect_lo & 0xffffu, f.rect_lo >> 16, f.rect_hi & 0xffffu, f.rect_hi >> 16, (uint32_t)tid); t.valid();) {
+            uint32_t tile[4], slot[4], lim[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                tile[u] = 0xffffffffu;
+                if (t.valid()) { tile[u] = f.tile_base + t.y * gx + t.x; t.next(); }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                slot[u] = tile[u] != 0xffffffffu ? atomicAdd(&tile_cursor[tile[u]], 1u) : 0u;
+                lim[u] = tile[u] != 0xffffffffu ? min(seg[tile[u] + 1u], capacity) : 0xffffffffu;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (tile[u] != 0xffffffffu && slot[u] < lim[u]) keys[slot[u]] = key;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 3. exclusive scan of the per-tile counts -> segment starts (= the reference's `ranges`),
 //    cursor copy for the scatter, and R.  One workgroup: n = B * tiles is small (C4: 8160).
 // ---------------------------------------------------------------------------
@@ -443,6 +585,36 @@ k_scan_tiles(int n, const uint32_t* __restrict__ tile_count, uint32_t* __restric
         if (host_num_rendered) *host_num_rendered = host_size_word(host_seq, total);  // ONE 8-byte store: the host polls it
         if (overflow && total > capacity) *overflow = 1u;  // asynchronous call that outgrew its buffer (sticky, pinned host memory)
     }
+}
+
+// The placement k_bin_faces speculates on, built from the exact counts of a call that went through set-up -> scan ->
+// scatter: tile t gets room for its count + 25 % + SEG_SLACK entries (so that a tile that was empty can receive a few),
+// segments in tile order, start[n] = the padded total; the order is that call's (longest list first -- every tile has a
+// segment, so every tile's position is a first-chunk mask slot).  One workgroup, n <= SCAN_SLAB.
+__global__ void __launch_bounds__(1024)
+k_build_placement(int n, const uint32_t* __restrict__ tile_count, const uint32_t* __restrict__ tile_order,
+                  uint32_t* __restrict__ start, uint32_t* __restrict__ order) {
+    __shared__ uint32_t wave_sum[17];
+    __shared__ __attribute__((aligned(16))) uint32_t slab[SCAN_SLAB];
+    const int tid = threadIdx.x;
+    slab_load(slab, tile_count, n, tid);
+    __syncthreads();
+    uint32_t c[SCAN_BATCH], local = 0;
+    slab_read(slab, tid, c);
+#pragma unroll
+    for (int j = 0; j < SCAN_BATCH; j++) {
+        c[j] = tid * SCAN_BATCH + j < n ? c[j] + (c[j] >> 2) + SEG_SLACK : 0u;
+        local += c[j];
+    }
+    const uint32_t run = block_exclusive_scan(local, tid, wave_sum);
+    slab_write_offsets(slab, tid, run, c);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SCAN_BATCH; j++) {
+        const int i = j * 1024 + tid;
+        if (i < n) { start[i] = slab[i]; order[i] = tile_order[i]; }
+    }
+    if (tid == 0) start[n] = wave_sum[16];
 }
 
 // Records a tile's region of the backward's record buffer must hold.  The per-pixel kernel writes a face's blended pairs
@@ -596,7 +768,8 @@ k_scan_tiles_final(int n, const uint32_t* __restrict__ tile_count, const uint32_
 // exclusive scan of those bounds: every tile's region of the backward's record buffer (u32 offsets; the total is < 2^32 or
 // the backward fails) and the total.  Also clears tile_used (records the per-pixel kernel really wrote, per tile).
 __global__ void __launch_bounds__(1024)
-k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __restrict__ tile_offset, uint32_t* __restrict__ hit_offset,
+k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __restrict__ tile_offset, const uint32_t* __restrict__ tile_end,
+            uint32_t* __restrict__ hit_offset,
             uint32_t* __restrict__ tile_used, unsigned long long* __restrict__ hit_total, unsigned long long* __restrict__ host_hit_total, uint32_t host_seq,
             uint32_t capacity, uint32_t* __restrict__ overflow) {
     __shared__ uint32_t wave_sum[17];
@@ -607,7 +780,7 @@ k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __res
 #pragma unroll
     for (int j = 0; j < SCAN_BATCH; j++) {  // n <= SCAN_SLAB
         const int i = j * 1024 + tid;
-        slab[i] = i < n ? record_bound(tile_hits[i], tile_offset[i + 1] - tile_offset[i]) : 0u;
+        slab[i] = i < n ? record_bound(tile_hits[i], list_end(tile_offset, tile_end, i) - tile_offset[i]) : 0u;
         if (i < n) tile_used[i] = 0u;
     }
     __syncthreads();
@@ -656,12 +829,12 @@ k_sort_tiles(uint32_t ntiles, const uint32_t* __restrict__ tile_offset, const ui
 // host launchers
 // ---------------------------------------------------------------------------
 void launch_project_verts(const dmr_scene& s, float4* vproj, float* mats, uint32_t* counters, size_t ncounters,
-                          hipStream_t st) {
+                          hipStream_t st, SegInit seg) {
     const int64_t n = (int64_t)s.B * s.P;
     StageScope t(DMR_STAGE_PROJECT, st);
     k_project_verts<<<dim3((unsigned)std::max<int64_t>(1, (n + 255) / 256)), dim3(256), 0, st>>>(
         s.B, s.P, s.verts, s.mv_mats, s.proj_mats, s.inv_mv_mats, s.inv_proj_mats, s.mats_transposed, s.verts_depth,
-        s.W, s.H, vproj, mats, counters, (uint32_t)ncounters);
+        s.W, s.H, vproj, mats, counters, (uint32_t)ncounters, seg);
 }
 
 void launch_setup_faces(const dmr_scene& s, bool tet, const float4* vproj, int gx, int gy, int r0, int r1,
@@ -700,12 +873,12 @@ void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_of
 
 size_t scan_tmp_words(int ntiles) { return SCAN_TMP_BUCKETS + (size_t)(ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES + 1; }
 
-void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, uint32_t* hit_offset, uint32_t* tile_used,
+void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,
                       unsigned long long* hit_total, unsigned long long* host_hit_total, uint32_t host_seq, uint32_t* scan_tmp, uint32_t capacity,
                       uint32_t* overflow, hipStream_t st) {
     StageScope t(DMR_STAGE_SCAN, st);
     if (ntiles <= SCAN_SINGLE_MAX) {
-        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, hit_offset, tile_used, hit_total, host_hit_total, host_seq, capacity, overflow);
+        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, tile_end, hit_offset, tile_used, hit_total, host_hit_total, host_seq, capacity, overflow);
         return;
     }
     const int nblk = (ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES;
@@ -728,6 +901,25 @@ void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_
                                                                          tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first)
     if (fpt == 1) DMR_SCATTER(1); else if (fpt == 2) DMR_SCATTER(2); else DMR_SCATTER(4);
 #undef DMR_SCATTER
+}
+
+void launch_bin_faces(const dmr_scene& s, const float4* vproj, int gx, int gy, int r0, int r1, float* key_depth,
+                      uint32_t* tiles_touched, const uint32_t* seg, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
+                      unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st) {
+    const int64_t n = (int64_t)s.B * s.F;
+    StageScope t(DMR_STAGE_SCATTER, st);
+    const int fpt = bin_fpt(n);
+    const dim3 grid((unsigned)std::max<int64_t>(1, (n + 256 * fpt - 1) / (256 * fpt))), block(256);
+#define DMR_BIN(FPT) k_bin_faces<FPT><<<grid, block, 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, key_depth, tiles_touched, seg, \
+                                                             tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first)
+    if (fpt == 1) DMR_BIN(1); else if (fpt == 2) DMR_BIN(2); else DMR_BIN(4);
+#undef DMR_BIN
+}
+
+void launch_build_placement(int ntiles, const uint32_t* tile_count, const uint32_t* tile_order, uint32_t* start, uint32_t* order,
+                            hipStream_t st) {
+    StageScope t(DMR_STAGE_SCAN, st);
+    k_build_placement<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_count, tile_order, start, order);
 }
 
 void launch_sort_tiles(int ntiles, const uint32_t* tile_offset, const uint32_t* tile_order, uint64_t* keys,

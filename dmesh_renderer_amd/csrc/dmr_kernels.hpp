@@ -48,9 +48,22 @@ struct StageScope {
 };
 
 // ---- binning (dmr_binning.hip)
+// A tile's list is [tile_offset[t], tile_end[t]): tile_end is the tile's cursor after the entries were emitted.  Behind the exact
+// path (set-up -> scan -> scatter) that is tile_offset[t + 1]; behind the speculative one (launch_bin_faces) the list fills
+// only a part of its segment [tile_offset[t], tile_offset[t + 1]), and a cursor BEHIND the segment's end marks a list that did
+// not fit: nothing of it can be trusted, the tile counts as empty (the call is redone or its overflow flagged).
+__host__ __device__ inline uint32_t list_end(const uint32_t* tile_offset, const uint32_t* tile_end, int tile) {
+    const uint32_t e = tile_end[tile];
+    return e > tile_offset[tile + 1] ? tile_offset[tile] : e;
+}
+// Speculative placement: what k_project_verts copies into the call's image buffer (start: ntiles + 1 segment starts in tile
+// order, order: the tiles longest list first; both persistent, dmr_api.hip).  start == null: nothing.
+struct SegInit { const uint32_t* start; const uint32_t* order; uint32_t* tile_offset; uint32_t* tile_cursor; uint32_t* tile_order; uint32_t ntiles; };
+constexpr uint32_t SEG_SLACK = 32;  // entries every segment has room for beyond its last count + 25 %: the first row of faces of a
+                                  // silhouette that moves into a tile that was empty (12 B each: 3 MB at 8 192 tiles)
 // also zeroes counters[0, ncounters) (tile_count | tile_hits)
 void launch_project_verts(const dmr_scene& s, float4* vproj, float* mats, uint32_t* counters, size_t ncounters,
-                          hipStream_t st);
+                          hipStream_t st, SegInit seg = SegInit{nullptr, nullptr, nullptr, nullptr, nullptr, 0u});
 void launch_setup_faces(const dmr_scene& s, bool tet, const float4* vproj, int gx, int gy, int r0, int r1,
                         uint2* face_rect, float* key_depth, float* max_depth, uint32_t* tiles_touched,
                         uint32_t* tile_count, hipStream_t st);
@@ -64,6 +77,8 @@ size_t scan_tmp_words(int ntiles);
 __host__ __device__ inline unsigned long long host_size_word(uint32_t seq, unsigned long long size) {
     return ((unsigned long long)(seq & 0xffffffu) << 40) | (size < (1ull << 40) ? size : (1ull << 40) - 1ull);
 }
+// the forward behind launch_bin_faces sets this bit of the size it publishes when a tile's entries did not fit its segment (R < 2^31 lies below)
+constexpr unsigned long long SIZE_WORD_OVERFLOW = 1ull << 39;
 // host_num_rendered (pinned, may be null): receives host_size_word(host_seq, R).  overflow (pinned, may be null): set to 1 when
 // R > capacity (asynchronous calls, which never read R on the host)
 void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor,
@@ -72,6 +87,17 @@ void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_of
 void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_rect, const float* key_depth,
                           const uint32_t* tiles_touched, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
                           unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st);
+// One kernel in place of set-up, scan and scatter (tri, up to SCAN_SINGLE_MAX tiles): seg = the call's tile_offset, which
+// k_project_verts filled from a placement together with the cursors (SegInit).  Also writes key_depth and tiles_touched.
+// Nothing is summed here: R and the overflow come from the cursors, launch_tri_forward's ListSize.  (The first version let every
+// workgroup add its entries to one word and take a ticket, the last one publishing R: 55 us at C4 by the stage events, against
+// 39 us for set-up + scan + scatter, profiles/r05/bench_ab_c4_ticket_variant.txt.)
+void launch_bin_faces(const dmr_scene& s, const float4* vproj, int gx, int gy, int r0, int r1, float* key_depth,
+                      uint32_t* tiles_touched, const uint32_t* seg, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
+                      unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st);
+// start[ntiles + 1], order[ntiles] <- the placement for the counts (and order) of a call that went through launch_scan_tiles
+void launch_build_placement(int ntiles, const uint32_t* tile_count, const uint32_t* tile_order, uint32_t* start, uint32_t* order,
+                            hipStream_t st);
 // capacity: entries the binning buffer holds; it is below R only while a size guess is being refuted (dmr_api.hip):
 // every kernel that walks the tile lists clamps to it, the results are then thrown away and redone.
 // (frames above SCAN_SINGLE_MAX tiles: below, the tri forward / the tet first-hit kernel sort their tiles themselves)
@@ -86,6 +112,7 @@ struct TriImageState {
     const uint32_t* hit_offset;     // record regions: exclusive scan of the tiles' record bounds (k_scan_hits, backward)
     uint32_t* tile_used;            // records k_tri_backward_pix wrote into a tile's region (padded runs; <= the bound)
     const uint32_t* tile_order;  // all B * gx * gy tiles, longest list first (k_scan_tiles)
+    const uint32_t* tile_end;    // every tile's list end (list_end() above): the cursors the entries were emitted through
     // Coverage masks the forward keeps for the backward: one 4 KB slot (256 pixels x 128 face bits) per 128-entry chunk of a
     // tile's list.  Chunk 0 of the tile at position q of tile_order (busy tiles come first there: q < number of busy tiles
     // <= min(tiles, list entries)) is slot q of the first mask_first_slots() slots; chunk c >= 1 of a list that starts at entry
@@ -108,13 +135,18 @@ struct alignas(16) HitRecord { uint32_t id; uint32_t pixel; float T; float dL_da
 // upstream gradient, which reaches dL_dfopacity only.  A compile-time variant of the kernels; the default ones are unchanged.
 // keys: the unsorted (depth_bits << 32 | face) list entries of the scatter pass: every tile's workgroup sorts its own list
 // (dmr_sort.hpp) into face_list before compositing it, no launch_sort_tiles; null: face_list is sorted already
+// size (blocks = 1: behind launch_bin_faces, which sums nothing): one more workgroup adds up the lists and publishes R -- device
+// word, host_size_word(host_seq, R | SIZE_WORD_OVERFLOW if a list left its segment) in pinned memory (may be null), the sticky
+// overflow word (may be null) -- as launch_scan_tiles does on the exact path
+struct ListSize { int* num_rendered; unsigned long long* host; uint32_t host_seq; uint32_t* overflow; uint32_t blocks; };
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
-                        float* out_color, float* out_depth, hipStream_t st, bool alpha = false);
+                        float* out_color, float* out_depth, hipStream_t st, bool alpha = false,
+                        ListSize size = ListSize{nullptr, nullptr, 0u, nullptr, 0u});
 // host_*: pinned host memory the kernel also writes its total to (no separate device->host copy)
 // hit_offset: every tile's region of the record buffer, sized by the bound h + (HIT_GROUP - 1) * min(list length, h) of
 // its h blended pairs (tile_hits); tile_used is cleared (the per-pixel kernel fills it)
-void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, uint32_t* hit_offset, uint32_t* tile_used,
+void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,
                       unsigned long long* hit_total, unsigned long long* host_hit_total, uint32_t host_seq, uint32_t* scan_tmp, uint32_t capacity,
                       uint32_t* overflow, hipStream_t st);
 // Without launch_scan_hits (B * tiles <= SCAN_SINGLE_MAX): every workgroup of k_tri_backward_pix sums the record bounds of

@@ -88,11 +88,12 @@ struct TriParams {
     uint32_t list_capacity;  // entries face_list holds (< R only while a size guess is being refuted)
     const float* verts; const int* faces; const float* verts_color; const float* faces_opacity;
     const float* inv_mv; const float* inv_proj; const float* faces_intense; const float* bg;
-    const float4* vproj; const uint32_t* tile_offset; const uint32_t* face_list;
+    const float4* vproj; const uint32_t* tile_offset; const uint32_t* tile_end; const uint32_t* face_list;  // (list_end(), dmr_kernels.hpp)
     unsigned long long* keys;  // (depth_bits << 32 | face) of every list entry, unsorted: the forward sorts its tile's
     float* final_T; float* final_prev_T; uint32_t* n_contrib;
     uint32_t* tile_hits; uint32_t* tile_bound; const uint32_t* hit_offset; uint32_t* tile_used; const uint32_t* tile_order;
     const unsigned long long* mask_offset;  // coverage masks: byte offset behind face_list (TriImageState)
+    ListSize size;  // forward behind launch_bin_faces: where R goes (dmr_kernels.hpp); size.blocks = 1, else 0 and unused
 };
 
 // The tile's coverage masks, pixel-major, one slot of 256 x 16 bytes per chunk (layout: TriImageState, dmr_kernels.hpp): chunk
@@ -259,9 +260,37 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     __shared__ uint32_t s_hits[4];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // Behind the one-kernel binning nobody has summed the lists yet: workgroup 0 does, from the cursors (<= SCAN_SINGLE_MAX tiles:
+    // 64 coalesced loads per thread, next to ~3 000 compositing workgroups), and publishes R as the scan kernel does on the
+    // exact path -- with SIZE_WORD_OVERFLOW / the overflow word when a list left its segment or the buffer.  Every other
+    // workgroup takes the tile at its position - 1.
+    if (p.size.blocks && blockIdx.x == 0u) {
+        const int nt = p.B * p.gx * p.gy;
+        uint32_t total = 0u, full = 0u;
+        for (int t = tid; t < nt; t += 256) {
+            const uint32_t b0 = p.tile_offset[t], e = p.tile_end[t];
+            total += e - b0;
+            full |= (e > p.tile_offset[t + 1] || e > p.list_capacity) ? 1u : 0u;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) { total += __shfl_xor(total, d, 64); full |= __shfl_xor(full, d, 64); }
+        if (lane == 0) { s_hits[wave] = total; if (wave < 2) s_live[wave] = 0u; }
+        __syncthreads();
+        if (lane == 0 && full) atomicOr(&s_live[0], 1u);
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t R = s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3];
+            const bool any = s_live[0] != 0u;
+            *p.size.num_rendered = (int)R;
+            if (p.size.host) *p.size.host = host_size_word(p.size.host_seq, (unsigned long long)R | (any ? SIZE_WORD_OVERFLOW : 0ull));
+            if (p.size.overflow && any) *p.size.overflow = 1u;  // asynchronous call whose scene left its placement (sticky)
+        }
+        return;  // uniform
+    }
+    const uint32_t pos = blockIdx.x - p.size.blocks;  // position in tile_order
     const unsigned long long mask_first_slots = p.mask_offset[1];  // (requested with the tile's id, not behind its list range)
     // tiles are taken longest list first (tile_order, k_scan_tiles); rows outside this shard's band are skipped
-    const int tile = (int)p.tile_order[blockIdx.x];
+    const int tile = (int)p.tile_order[pos];
     const int tx = tile % p.gx, ty = (tile / p.gx) % p.gy, b = tile / (p.gx * p.gy);
     if (ty < p.r0 || ty >= p.r1) return;  // uniform
     const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
@@ -273,9 +302,9 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     // A list that does not fit the binning buffer (only while a size guess is being refuted; everything is redone
     // then) was neither completely scattered nor sorted: its entries are not face ids.  Such a tile renders as empty.
     // (The same for a tile whose position in tile_order has no first-chunk mask slot: more busy tiles than list capacity.)
-    uint32_t begin = p.tile_offset[tile], end = p.tile_offset[tile + 1];
+    uint32_t begin = p.tile_offset[tile], end = list_end(p.tile_offset, p.tile_end, tile);
     if (end > p.list_capacity) begin = end = 0u;
-    if ((unsigned long long)blockIdx.x >= mask_first_slots) begin = end = 0u;
+    if ((unsigned long long)pos >= mask_first_slots) begin = end = 0u;
     if (begin == end) {  // an empty tile (most of a frame: 5 244 of C4's 8 160) is background: no rays, no LDS, no barriers
         if (inside) {
             const int64_t bpix = (int64_t)b * HW + pix_id;
@@ -313,7 +342,7 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     int face_next = begin + MASK_CHUNK + sj < end ? (int)p.face_list[begin + MASK_CHUNK + sj] : -1;
 
     DMR_STAMP_RT(p, 0, 0);
-    const ChunkMasks masks = chunk_masks(p, blockIdx.x, begin);
+    const ChunkMasks masks = chunk_masks(p, pos, begin);
     AllDone all_done;
     all_done.init(s_live);
     for (uint32_t base = begin; base < end; base += MASK_CHUNK) {
@@ -542,7 +571,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     // tiles are taken longest list first (tile_order, k_scan_tiles); rows outside this shard's band are skipped
     const int tile = (int)p.tile_order[blockIdx.x];
     const int tx = tile % p.gx, ty = (tile / p.gx) % p.gy, b = tile / (p.gx * p.gy);
-    const uint32_t begin = p.tile_offset[tile], end = p.tile_offset[tile + 1];
+    const uint32_t begin = p.tile_offset[tile], end = list_end(p.tile_offset, p.tile_end, tile);
     // The tile's region of the record buffer.  Without a scan kernel (regions.hit_offset, dmr_kernels.hpp) it starts at the
     // sum of the bounds of all tiles before this one -- an empty tile, or one outside this shard's band, has none -- and this
     // workgroup publishes offset and use of its tile for the hit-parallel kernel (every tile has exactly one workgroup here).
@@ -1419,23 +1448,25 @@ static TriParams make_params(const dmr_scene& s, int gx, int gy, int r0, int r1,
 #endif
     p.verts = s.verts; p.faces = s.faces; p.verts_color = s.verts_color; p.faces_opacity = s.faces_opacity;
     p.inv_mv = s.inv_mv_mats; p.inv_proj = s.inv_proj_mats; p.faces_intense = s.faces_intense; p.bg = s.background;
-    p.vproj = vproj; p.tile_offset = tile_offset; p.face_list = face_list; p.keys = nullptr;
+    p.vproj = vproj; p.tile_offset = tile_offset; p.tile_end = img.tile_end; p.face_list = face_list; p.keys = nullptr;
     p.final_T = img.final_T; p.final_prev_T = img.final_prev_T; p.n_contrib = img.n_contrib;
     p.tile_hits = img.tile_hits; p.tile_bound = img.tile_bound; p.hit_offset = img.hit_offset; p.tile_used = img.tile_used; p.tile_order = img.tile_order;
     p.mask_offset = img.mask_offset;
     p.list_capacity = 0xffffffffu;
+    p.size = ListSize{nullptr, nullptr, 0u, nullptr, 0u};
     return p;
 }
 
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
-                        float* out_color, float* out_depth, hipStream_t st, bool alpha) {
-    if (r1 <= r0) return;
+                        float* out_color, float* out_depth, hipStream_t st, bool alpha, ListSize size) {
+    if (r1 <= r0 && !size.blocks) return;  // (the size is wanted of an empty band too; its tiles return at once)
     TriParams p = make_params(s, gx, gy, r0, r1, vproj, tile_offset, face_list, img);
     p.keys = reinterpret_cast<unsigned long long*>(keys);
     p.list_capacity = capacity;
+    p.size = size;
     StageScope t(DMR_STAGE_TRI_FORWARD, st);
-    const dim3 grid((unsigned)(s.B * gx * gy)), block(256);
+    const dim3 grid((unsigned)(s.B * gx * gy) + size.blocks), block(256);
     if (alpha) {  // out_depth [B,2,H,W]: depth | alpha
         if (keys) k_tri_forward<true, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
         else k_tri_forward<false, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
