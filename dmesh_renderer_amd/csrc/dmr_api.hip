@@ -62,8 +62,9 @@ struct Carver {
 
 struct PointState { float4* vproj; };
 struct FaceState { uint2* rect; float* key_depth; float* max_depth; uint32_t* tiles_touched; void* facerec; void* colrec; void* tetrec; };
-// (tile_count and FaceState::rect are the exact path's: behind launch_bin_faces tile_count stays zero -- a tile's count is
-// tile_cursor - tile_offset there -- and rect keeps what an earlier call left; nothing reads either afterwards)
+// (tile_count and FaceState::rect belong to the exact policy of the binning: the set-up pass leaves them for the scan and the
+// scatter.  Behind launch_bin_faces tile_count stays zero -- a tile's count is tile_cursor - tile_offset there -- and rect keeps
+// what an earlier call left; nothing reads either afterwards)
 struct ImageState {
     uint32_t* tile_count; uint32_t* tile_offset; uint32_t* tile_cursor; int* num_rendered;
     float* final_T; float* final_prev_T; uint32_t* n_contrib;
@@ -386,13 +387,15 @@ struct Sizing { double SizeGuess::* estimate; uint64_t limit; int word; const ch
 // The speculative sizing above, for both buffers.  first(guess, out): the stages that can be enqueued before the size is
 // known, `guess` the capacity (0: no estimate), `out` where the size goes; then(size, redo): the stages that need the exact
 // size (redo: they ran with a guess too small).  *size: the exact size, or an asynchronous call's capacity.
+// placed_capacity (0: none): the capacity of a placement (above), which takes the estimate's place as the guess; what then decides the
+// redo is not the size but the SIZE_WORD_OVERFLOW bit of the size word -- a tile outgrew its segment.
 template <class First, class Then>
-int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_t st, uint64_t* size, First first, Then then) {
+int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_t st, uint64_t placed_capacity, uint64_t* size, First first, Then then) {
     int dev = 0;
     DMR_HIP(hipGetDevice(&dev));
     uint32_t* overflow = overflow_word(dev, !async);
-    uint64_t guess = 0;
-    {
+    uint64_t guess = placed_capacity;
+    if (!placed_capacity) {
         std::lock_guard<std::mutex> lk(g_size_mu);
         const double per_face = lookup_estimate(key, z.estimate);
         if (per_face > 0.0) guess = std::min<uint64_t>(padded((uint64_t)(per_face * (double)BF)), z.limit);
@@ -410,11 +413,13 @@ int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_
     if (first(guess, SizeOut{const_cast<unsigned long long*>(sr.word(z.word)), seq, nullptr, 0xffffffffu})) return 1;
     unsigned long long n = 0;
     if (wait_size(sr.word(z.word), seq, st, &n)) return 1;  // the call's one host wait (rasterizer_impl.cu:287-292)
+    const bool full = placed_capacity ? (n & dmr::SIZE_WORD_OVERFLOW) != 0 : n > guess;
+    if (placed_capacity) n &= dmr::SIZE_WORD_OVERFLOW - 1ull;
     if (n > z.limit) return fail(z.too_large);
     *size = n;
     if (!guess) {
         if (then(n, false)) return 1;
-    } else if (n > guess) {  // the guess was too small: redo the affected stages with the exact size
+    } else if (full) {  // the guess was too small (a segment, with a placement): redo the affected stages with the exact size
         g_redo_count.fetch_add(1, std::memory_order_relaxed);
         DMR_HIP(hipStreamSynchronize(st));
         if (then(n, true)) return 1;
@@ -453,14 +458,20 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
         dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, out.host, out.seq, is.tile_order,
                                is.scan_tmp, out.capacity, out.overflow, st);
     };
-    auto rest = [&](uint64_t capacity) -> int {
+    // the call's binning buffer, carved into c.bs (none at all: a call with no entries and no march sequence)
+    auto binning = [&](uint64_t capacity) -> int {
         BinningState tb;
         const size_t mask_tiles = tet ? 0 : (size_t)d.ntiles;
         void* bb = alloc(ctx, DMR_BUF_BINNING, carve_binning(nullptr, (size_t)capacity, mask_tiles, (size_t)d.ntiles, seq_steps, tb));
         if (!bb && (capacity > 0 || seq_steps > 0)) return fail("binning allocation failed");
-        BinningState& bs = c.bs;
-        carve_binning(bb, (size_t)capacity, mask_tiles, (size_t)d.ntiles, seq_steps, bs);
-
+        carve_binning(bb, (size_t)capacity, mask_tiles, (size_t)d.ntiles, seq_steps, c.bs);
+        return 0;
+    };
+    bool exact = false;  // the lists come from the exact path: its counts and order are what a placement is built from
+    auto rest = [&](uint64_t capacity) -> int {
+        if (binning(capacity)) return 1;
+        const BinningState& bs = c.bs;
+        exact = true;
         if (capacity > 0) {
             dmr::launch_scatter_faces(*s, d.gx, d.gy, fs.rect, fs.key_depth, fs.tiles_touched, is.tile_cursor, bs.keys,
                                       (uint32_t)capacity, tet ? nullptr : is.mask_offset, bs.mask_offset, bs.mask_first, st);
@@ -471,67 +482,36 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
         render(c, dmr::ListSize{nullptr, nullptr, 0u, nullptr, 0u});
         return 0;
     };
+    // speculative placement: projection -> one binning kernel -> render, whose first workgroup leaves the size word
+    auto binned = [&](SizeOut out) -> int {
+        if (binning(pl.capacity)) return 1;
+        const BinningState& bs = c.bs;
+        dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st,
+                                  dmr::SegInit{pl.start, pl.order, is.tile_offset, is.tile_cursor, is.tile_order, (uint32_t)d.ntiles});
+        dmr::launch_bin_faces(*s, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.tiles_touched, is.tile_offset, is.tile_cursor, bs.keys,
+                              bs.capacity, is.mask_offset, bs.mask_offset, bs.mask_first, st);
+        render(c, dmr::ListSize{is.num_rendered, out.host, out.seq, out.overflow, 1u});  // (its first workgroup publishes R)
+        return 0;
+    };
 
     const Sizing list_entries{&SizeGuess::rendered_per_face, 0x7fffffffu, 0, "num_rendered overflows 31 bits",
                               "asynchronous / captured call without a size estimate: run one default (waiting) call with the same "
                               "view configuration first"};
     uint64_t R = 0;
-    if (pl.valid) {  // speculative placement: projection -> one binning kernel -> render, whose first workgroup leaves the size word
-        auto binned = [&](SizeOut out) -> int {
-            BinningState& bs = c.bs;
-            BinningState tb;
-            void* bb = alloc(ctx, DMR_BUF_BINNING, carve_binning(nullptr, (size_t)pl.capacity, (size_t)d.ntiles, 0, 0, tb));
-            if (!bb) return fail("binning allocation failed");
-            carve_binning(bb, (size_t)pl.capacity, (size_t)d.ntiles, 0, 0, bs);
-            dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st,
-                                      dmr::SegInit{pl.start, pl.order, is.tile_offset, is.tile_cursor, is.tile_order, (uint32_t)d.ntiles});
-            dmr::launch_bin_faces(*s, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.tiles_touched, is.tile_offset, is.tile_cursor, bs.keys,
-                                  bs.capacity, is.mask_offset, bs.mask_offset, bs.mask_first, st);
-            render(c, dmr::ListSize{is.num_rendered, out.host, out.seq, out.overflow, 1u});  // (its first workgroup publishes R)
-            return 0;
-        };
-        int dev = 0;
-        DMR_HIP(hipGetDevice(&dev));
-        uint32_t* overflow = overflow_word(dev, !async);
-        if (async) {
-            if (!overflow) return fail(list_entries.no_estimate);
-            if (binned(SizeOut{nullptr, 0u, overflow, (uint32_t)pl.capacity})) return 1;
-            *num_rendered = (int)pl.capacity;  // an upper bound the backward accepts in R's place
-            DMR_HIP(hipGetLastError());
-            return 0;
-        }
-        SizeRead& sr = g_size_read[dev];
-        if (!sr.slot && !(sr.slot = pinned_words())) return fail("hipHostMalloc failed");
-        const uint32_t seq = sr.next_seq();
-        if (binned(SizeOut{const_cast<unsigned long long*>(sr.word(list_entries.word)), seq, nullptr, 0xffffffffu})) return 1;
-        unsigned long long n = 0;
-        if (wait_size(sr.word(list_entries.word), seq, st, &n)) return 1;
-        const bool full = (n & dmr::SIZE_WORD_OVERFLOW) != 0;
-        R = n & (dmr::SIZE_WORD_OVERFLOW - 1ull);
-        if (R > list_entries.limit) return fail(list_entries.too_large);
-        if (full) {  // a tile outgrew its segment: the exact path, which also refreshes the placement
-            g_redo_count.fetch_add(1, std::memory_order_relaxed);
-            DMR_HIP(hipStreamSynchronize(st));
-            front(NOWHERE);
-            if (rest(R)) return 1;
-            if (build_placement(key, d, R, is, st)) return 1;
-        } else if (2 * R < pl.built_from) {
-            drop_placement(key);
-        }
-        {
-            std::lock_guard<std::mutex> lk(g_size_mu);
-            g_size_cache[key].rendered_per_face = (double)std::max<uint64_t>(R, 1) / (double)std::max<size_t>(d.BF, 1);
-        }
-        *num_rendered = (int)R;
-        DMR_HIP(hipGetLastError());
-        return 0;
-    }
-    // a redo enqueues the front again too: the scatter pass has used up the tile cursors
-    int rc = sized(list_entries, key, d.BF, async, st, &R,
-                   [&](uint64_t guess, SizeOut out) { front(out); return guess ? rest(guess) : 0; },
-                   [&](uint64_t exact, bool redo) { if (redo) front(NOWHERE); return rest(exact); });
+    // a redo enqueues the front again too: the scatter pass has used up the tile cursors (a placed call's redo -- a tile outgrew
+    // its segment -- goes through the exact path as well)
+    int rc = sized(list_entries, key, d.BF, async, st, pl.valid ? pl.capacity : 0, &R,
+                   [&](uint64_t guess, SizeOut out) {
+                       if (pl.valid) return binned(out);  // (guess = pl.capacity)
+                       front(out);
+                       return guess ? rest(guess) : 0;
+                   },
+                   [&](uint64_t size, bool redo) { if (redo) front(NOWHERE); return rest(size); });
     *num_rendered = (int)R;
-    if (rc == 0 && placed && !async) rc = build_placement(key, d, R, is, st);
+    if (rc == 0 && placed && !async) {  // the exact path refreshes the placement; one twice as large as the scene needs is dropped
+        if (exact) rc = build_placement(key, d, R, is, st);
+        else if (2 * R < pl.built_from) drop_placement(key);
+    }
     return rc;
 }
 
@@ -720,7 +700,7 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
                              "same view configuration first"};
     uint64_t nhits = 0;
     // a redo re-runs the record passes only: the scan's regions still stand
-    return sized(hit_records, size_key(s, false, d), d.BF, is_async(s, st), st, &nhits, first,
+    return sized(hit_records, size_key(s, false, d), d.BF, is_async(s, st), st, 0, &nhits, first,
                  [&](uint64_t exact, bool redo) { return rest(exact, redo && self_regions ? self_laid(NOWHERE) : scanned); });
 }
 

@@ -17,6 +17,7 @@
 // order = ascending face id (Q6).  The result -- per-tile face lists and ranges -- is
 // bit-identical to the reference's sorted list, whatever order the scatter ran in.
 #include <algorithm>
+#include <type_traits>
 
 #include "dmr_kernels.hpp"
 #include "dmr_sort.hpp"
@@ -123,35 +124,141 @@ struct RectWalk {
     }
 };
 
-// s_box: {min x, min y, max x, max y} of the rects that want the LDS histogram; uniform result.  Threads reduce
-// their own faces, waves reduce with shuffles, one lane per wave touches LDS (every thread doing ds_min / ds_max on
-// the same four words serialises: 2 cycles per lane and atomic).
+__device__ __forceinline__ Rect unpack_rect(uint2 r) { return {r.x & 0xffffu, r.x >> 16, r.y & 0xffffu, r.y >> 16}; }
+
+// The LDS of the three face kernels: the window's histogram, its box, the big-face queue.
+struct BinShared { uint32_t hist[LDS_HIST_MAX]; int box[4]; BigFace big[BIG_MAX]; uint32_t nbig; };
+__device__ __forceinline__ BinShared& bin_shared() { __shared__ BinShared sh; return sh; }
+
+// What a face contributes to the binning: the tiles of its rect (0: culled or off screen), the rect packed 4 x u16, the
+// depth its list entries are sorted by (tri: mean z, tet: min z, mapped to [0, 1]) and, tet only, its max depth.
+struct FaceBin { uint32_t touched; uint2 rect; float key, max_depth; };
+template <bool TET>
+__device__ __forceinline__ FaceBin face_bin(int b, int f, int P, const int* __restrict__ faces, const float4* __restrict__ vproj,
+                                            int gx, int gy, int r0, int r1) {
+    const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
+    const float4 a0 = vproj[(int64_t)b * P + v0], a1 = vproj[(int64_t)b * P + v1], a2 = vproj[(int64_t)b * P + v2];
+    float max_z = a0.z, min_z = a0.z, depth = 0.0f;
+    depth += a0.z;
+    max_z = fmaxf(max_z, a1.z); min_z = fminf(min_z, a1.z); depth += a1.z;
+    max_z = fmaxf(max_z, a2.z); min_z = fminf(min_z, a2.z); depth += a2.z;
+    depth = depth / 3.0f;
+    Rect r = {0, 0, 0, 0};
+    uint32_t touched = 0u;
+    if (!(max_z < -1.0f || min_z > 1.0f)) {
+        r = tile_rect({a0.x, a0.y}, {a1.x, a1.y}, {a2.x, a2.y}, gx, gy, r0, r1);
+        touched = (r.maxy - r.miny) * (r.maxx - r.minx);
+    }
+    if (touched == 0) r = {0, 0, 0, 0};
+    auto map01 = [](float z) { float d = (z + 1.0f) * 0.5f; if (d < 0.0f) d = 0.0f; if (d > 1.0f) d = 1.0f; return d; };
+    return {touched, make_uint2(r.minx | (r.miny << 16), r.maxx | (r.maxy << 16)),
+            touched ? (TET ? map01(min_z) : map01(depth)) : 0.0f, TET && touched ? map01(max_z) : 0.0f};
+}
+
+// A workgroup's 256 x FPT consecutive (view, face) pairs, FPT per thread; mine: face of the window's view (that of the first one)
 template <int FPT>
-__device__ __forceinline__ BinWindow bin_window(int* s_box, int view, const uint2* rr, const uint32_t* touched,
-                                                const bool* mine, int tid) {
+struct FaceBatch { int64_t base; int view; uint2 rr[FPT]; uint32_t touched[FPT], kd[FPT]; bool mine[FPT]; };
+// get(idx, b, f) -> FaceBin, for every pair of the thread
+template <int FPT, class Get>
+__device__ __forceinline__ FaceBatch<FPT> load_faces(int B, int F, Get get) {
+    FaceBatch<FPT> fb;
+    fb.base = (int64_t)blockIdx.x * (256 * FPT);
+    fb.view = (int)(fb.base / F);
+#pragma unroll
+    for (int it = 0; it < FPT; it++) {
+        const int64_t idx = fb.base + it * 256 + threadIdx.x;
+        fb.touched[it] = 0u; fb.rr[it] = make_uint2(0, 0); fb.kd[it] = 0u; fb.mine[it] = false;
+        if (idx >= (int64_t)B * F) continue;
+        const int b = (int)(idx / F);
+        const FaceBin r = get(idx, b, (int)(idx % F));
+        fb.touched[it] = r.touched; fb.rr[it] = r.rect; fb.kd[it] = __float_as_uint(r.key); fb.mine[it] = b == fb.view;
+    }
+    return fb;
+}
+
+// Opens the workgroup's window: sh.box = {min x, min y, max x, max y} of the rects that want the LDS histogram, the histogram
+// zeroed, the big-face queue empty; uniform result.  Threads reduce their own faces, waves reduce with shuffles, one lane per
+// wave touches LDS (every thread doing ds_min / ds_max on the same four words serialises: 2 cycles per lane and atomic).
+template <int FPT>
+__device__ __forceinline__ BinWindow bin_window(BinShared& sh, const FaceBatch<FPT>& fb) {
+    const int tid = threadIdx.x;
     int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = 0, by1 = 0;
 #pragma unroll
     for (int it = 0; it < FPT; it++) {
-        if (!mine[it] || touched[it] == 0 || touched[it] > BIG_RECT) continue;
-        bx0 = min(bx0, (int)(rr[it].x & 0xffffu)); by0 = min(by0, (int)(rr[it].x >> 16));
-        bx1 = max(bx1, (int)(rr[it].y & 0xffffu)); by1 = max(by1, (int)(rr[it].y >> 16));
+        if (!fb.mine[it] || fb.touched[it] == 0 || fb.touched[it] > BIG_RECT) continue;
+        bx0 = min(bx0, (int)(fb.rr[it].x & 0xffffu)); by0 = min(by0, (int)(fb.rr[it].x >> 16));
+        bx1 = max(bx1, (int)(fb.rr[it].y & 0xffffu)); by1 = max(by1, (int)(fb.rr[it].y >> 16));
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
         bx0 = min(bx0, __shfl_xor(bx0, d, 64)); by0 = min(by0, __shfl_xor(by0, d, 64));
         bx1 = max(bx1, __shfl_xor(bx1, d, 64)); by1 = max(by1, __shfl_xor(by1, d, 64));
     }
-    if (tid == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = 0; s_box[3] = 0; }
+    if (tid == 0) { sh.box[0] = 0x7fffffff; sh.box[1] = 0x7fffffff; sh.box[2] = 0; sh.box[3] = 0; sh.nbig = 0u; }
     __syncthreads();
     if ((tid & 63) == 0) {
-        atomicMin(&s_box[0], bx0); atomicMin(&s_box[1], by0); atomicMax(&s_box[2], bx1); atomicMax(&s_box[3], by1);
+        atomicMin(&sh.box[0], bx0); atomicMin(&sh.box[1], by0); atomicMax(&sh.box[2], bx1); atomicMax(&sh.box[3], by1);
     }
     __syncthreads();
     BinWindow w;
-    w.x0 = s_box[0]; w.y0 = s_box[1]; w.wx = s_box[2] - s_box[0]; w.wy = s_box[3] - s_box[1]; w.view = view;
+    w.x0 = sh.box[0]; w.y0 = sh.box[1]; w.wx = sh.box[2] - sh.box[0]; w.wy = sh.box[3] - sh.box[1]; w.view = fb.view;
     w.lds = w.wx > 0 && w.wy > 0 && (int64_t)w.wx * w.wy <= LDS_HIST_MAX;
     if (!w.lds) { w.wx = 0; w.wy = 0; }
+    const int nw = w.wx * w.wy;
+    for (int t = tid; t < nw; t += 256) sh.hist[t] = 0u;
+    __syncthreads();
     return w;
+}
+
+// op(bin, its count, tile) for every non-empty bin of the window, a bin per thread
+template <class Op>
+__device__ __forceinline__ void for_each_bin(BinShared& sh, const BinWindow& w, int gx, int gy, Op op) {
+    for (int y = threadIdx.x / 64; y < w.wy; y += 4)
+        for (int x = threadIdx.x % 64; x < w.wx; x += 64) {
+            const uint32_t c = sh.hist[y * w.wx + x];
+            if (c) op(sh.hist[y * w.wx + x], c, (uint32_t)w.view * gx * gy + (uint32_t)(w.y0 + y) * gx + (uint32_t)(w.x0 + x));
+        }
+}
+
+// Every touched face of the thread: a big one joins the queue with its key (while there is room; the count pass queues the key
+// too and ignores it); of any other, for every tile of its rect, in_window(bin, key) or -- no window, another view's face, a
+// big face the queue had no room for -- direct(tile, key).
+// (Two callables and two loops: one loop over a selected LDS-or-global address compiles to flat atomics.)
+template <int FPT, class InWindow, class Direct>
+__device__ __forceinline__ void for_each_face_tile(BinShared& sh, const BinWindow& w, const FaceBatch<FPT>& fb, int F, int gx, int gy,
+                                                   InWindow in_window, Direct direct) {
+#pragma unroll
+    for (int it = 0; it < FPT; it++) {
+        if (fb.touched[it] == 0) continue;
+        const int64_t idx = fb.base + it * 256 + threadIdx.x;
+        const uint32_t tb = (uint32_t)(idx / F) * gx * gy;
+        const Rect r = unpack_rect(fb.rr[it]);
+        const uint64_t key = ((uint64_t)fb.kd[it] << 32) | (uint32_t)(idx % F);
+        const bool big = fb.touched[it] > BIG_RECT;
+        if (big) {
+            const uint32_t q = atomicAdd(&sh.nbig, 1u);
+            if (q < (uint32_t)BIG_MAX) { sh.big[q] = BigFace{fb.rr[it].x, fb.rr[it].y, tb, (uint32_t)key, (uint32_t)(key >> 32)}; continue; }
+        }
+        if (w.lds && fb.mine[it] && !big) {
+            for (uint32_t y = r.miny; y < r.maxy; y++)
+                for (uint32_t x = r.minx; x < r.maxx; x++) in_window(sh.hist[(y - w.y0) * w.wx + (x - w.x0)], key);
+        } else {
+            for (uint32_t y = r.miny; y < r.maxy; y++)
+                for (uint32_t x = r.minx; x < r.maxx; x++) direct(tb + y * gx + x, key);
+        }
+    }
+}
+
+// op(face, walk) for every queued face, by the whole workgroup (behind a barrier that follows the queueing)
+template <class Op>
+__device__ __forceinline__ void for_each_big_face(const BinShared& sh, Op op) {
+    const uint32_t nbig = min(sh.nbig, (uint32_t)BIG_MAX);
+    for (uint32_t q = 0; q < nbig; q++) {
+        const BigFace f = sh.big[q];
+        const Rect r = unpack_rect(make_uint2(f.rect_lo, f.rect_hi));
+        RectWalk t(r.minx, r.miny, r.maxx, r.maxy, threadIdx.x);
+        op(f, t);
+    }
 }
 
 template <bool TET, int FPT>
@@ -160,286 +267,75 @@ k_setup_faces_lds(int B, int P, int F, const int* __restrict__ faces, const floa
                   int gx, int gy, int r0, int r1,
                   uint2* __restrict__ face_rect, float* __restrict__ key_depth, float* __restrict__ max_depth,
                   uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ tile_count) {
-    __shared__ uint32_t s_hist[LDS_HIST_MAX];
-    __shared__ int s_box[4];
-    __shared__ BigFace s_big[BIG_MAX];
-    __shared__ uint32_t s_nbig;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_nbig = 0u;  // (bin_window's barriers order this before the queueing below)
-    const int64_t BF = (int64_t)B * F;
-    const int64_t base = (int64_t)blockIdx.x * (256 * FPT);
-    const int view = (int)(base / F);
-    uint2 rr[FPT];
-    uint32_t touched[FPT];
-    bool mine[FPT];  // face of the window's view
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        const int64_t idx = base + it * 256 + tid;
-        touched[it] = 0u; rr[it] = make_uint2(0, 0); mine[it] = false;
-        if (idx >= BF) continue;
-        const int b = (int)(idx / F), f = (int)(idx % F);
-        mine[it] = b == view;
-        const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
-        const float4 a0 = vproj[(int64_t)b * P + v0], a1 = vproj[(int64_t)b * P + v1], a2 = vproj[(int64_t)b * P + v2];
-        float max_z = a0.z, min_z = a0.z, depth = 0.0f;
-        depth += a0.z;
-        max_z = fmaxf(max_z, a1.z); min_z = fminf(min_z, a1.z); depth += a1.z;
-        max_z = fmaxf(max_z, a2.z); min_z = fminf(min_z, a2.z); depth += a2.z;
-        depth = depth / 3.0f;
-        Rect r = {0, 0, 0, 0};
-        if (!(max_z < -1.0f || min_z > 1.0f)) {
-            r = tile_rect({a0.x, a0.y}, {a1.x, a1.y}, {a2.x, a2.y}, gx, gy, r0, r1);
-            touched[it] = (r.maxy - r.miny) * (r.maxx - r.minx);
-        }
-        if (touched[it] == 0) r = {0, 0, 0, 0};
-        auto map01 = [](float z) { float d = (z + 1.0f) * 0.5f; if (d < 0.0f) d = 0.0f; if (d > 1.0f) d = 1.0f; return d; };
-        rr[it] = make_uint2(r.minx | (r.miny << 16), r.maxx | (r.maxy << 16));
-        tiles_touched[idx] = touched[it];
-        face_rect[idx] = rr[it];
-        key_depth[idx] = touched[it] ? (TET ? map01(min_z) : map01(depth)) : 0.0f;
-        if (TET) max_depth[idx] = touched[it] ? map01(max_z) : 0.0f;
-    }
-    const BinWindow w = bin_window<FPT>(s_box, view, rr, touched, mine, tid);
-    const int nw = w.wx * w.wy;
-    for (int t = tid; t < nw; t += 256) s_hist[t] = 0u;
+    BinShared& sh = bin_shared();
+    const FaceBatch<FPT> fb = load_faces<FPT>(B, F, [&](int64_t idx, int b, int f) {
+        const FaceBin r = face_bin<TET>(b, f, P, faces, vproj, gx, gy, r0, r1);
+        tiles_touched[idx] = r.touched; face_rect[idx] = r.rect; key_depth[idx] = r.key;
+        if (TET) max_depth[idx] = r.max_depth;
+        return r;
+    });
+    const BinWindow w = bin_window(sh, fb);
+    // (none of these atomics returns a value)
+    for_each_face_tile(sh, w, fb, F, gx, gy, [&](uint32_t& bin, uint64_t) { atomicAdd(&bin, 1u); },
+                       [&](uint32_t tile, uint64_t) { atomicAdd(&tile_count[tile], 1u); });
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        if (touched[it] == 0) continue;
-        const int64_t idx = base + it * 256 + tid;
-        const uint32_t tb = (uint32_t)(idx / F) * gx * gy;
-        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
-        if (touched[it] > BIG_RECT) {
-            const uint32_t q = atomicAdd(&s_nbig, 1u);
-            if (q < (uint32_t)BIG_MAX) { s_big[q] = BigFace{rr[it].x, rr[it].y, tb, 0u, 0u}; continue; }
-        }
-        if (w.lds && mine[it] && touched[it] <= BIG_RECT) {
-            for (uint32_t y = miny; y < maxy; y++)
-                for (uint32_t x = minx; x < maxx; x++) atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
-        } else {
-            for (uint32_t y = miny; y < maxy; y++)
-                for (uint32_t x = minx; x < maxx; x++) atomicAdd(&tile_count[tb + y * gx + x], 1u);
-        }
-    }
-    __syncthreads();
-    for (int y = tid / 64; y < w.wy; y += 4)
-        for (int x = tid % 64; x < w.wx; x += 64) {
-            const uint32_t c = s_hist[y * w.wx + x];
-            if (c) atomicAdd(&tile_count[(uint32_t)view * gx * gy + (uint32_t)(w.y0 + y) * gx + (uint32_t)(w.x0 + x)], c);
-        }
-    const uint32_t nbig = min(s_nbig, (uint32_t)BIG_MAX);
-    for (uint32_t q = 0; q < nbig; q++) {
-        const BigFace f = s_big[q];
-        for (RectWalk t(f.rect_lo & 0xffffu, f.rect_lo >> 16, f.rect_hi & 0xffffu, f.rect_hi >> 16, (uint32_t)tid); t.valid(); t.next())
-            atomicAdd(&tile_count[f.tile_base + t.y * gx + t.x], 1u);
-    }
-}
-
-template <int FPT>
-__global__ void __launch_bounds__(256)
-k_scatter_faces_lds(int B, int F, int gx, int gy, const uint2* __restrict__ face_rect,
-                    const float* __restrict__ key_depth, const uint32_t* __restrict__ tiles_touched,
-                    uint32_t* __restrict__ tile_cursor, uint64_t* __restrict__ keys, uint32_t capacity,
-                    unsigned long long* __restrict__ mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first) {
-    // where the binning buffer of THIS capacity keeps the coverage masks (dmr_kernels.hpp, TriImageState::mask_offset)
-    if (mask_offset_dst && blockIdx.x == 0 && threadIdx.x == 0) { mask_offset_dst[0] = mask_offset; mask_offset_dst[1] = mask_first; }
-    __shared__ uint32_t s_hist[LDS_HIST_MAX];
-    __shared__ int s_box[4];
-    __shared__ BigFace s_big[BIG_MAX];
-    __shared__ uint32_t s_nbig;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_nbig = 0u;
-    const int64_t BF = (int64_t)B * F;
-    const int64_t base = (int64_t)blockIdx.x * (256 * FPT);
-    const int view = (int)(base / F);
-    uint2 rr[FPT];
-    uint32_t touched[FPT];
-    bool mine[FPT];
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        const int64_t idx = base + it * 256 + tid;
-        touched[it] = idx < BF ? tiles_touched[idx] : 0u;
-        rr[it] = touched[it] ? face_rect[idx] : make_uint2(0, 0);
-        mine[it] = idx < BF && (int)(idx / F) == view;
-    }
-    const BinWindow w = bin_window<FPT>(s_box, view, rr, touched, mine, tid);
-    const int nw = w.wx * w.wy;
-    for (int t = tid; t < nw; t += 256) s_hist[t] = 0u;
-    __syncthreads();
-    // pass 1: count this workgroup's entries per tile of the window
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        if (!(w.lds && mine[it]) || touched[it] == 0 || touched[it] > BIG_RECT) continue;
-        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
-        for (uint32_t y = miny; y < maxy; y++)
-            for (uint32_t x = minx; x < maxx; x++) atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
-    }
-    __syncthreads();
-    // reserve the workgroup's slots of every non-empty tile with one returning atomic; the bin now holds the cursor
-    for (int y = tid / 64; y < w.wy; y += 4)
-        for (int x = tid % 64; x < w.wx; x += 64) {
-            const uint32_t c = s_hist[y * w.wx + x];
-            if (c) s_hist[y * w.wx + x] = atomicAdd(&tile_cursor[(uint32_t)view * gx * gy + (uint32_t)(w.y0 + y) * gx + (uint32_t)(w.x0 + x)], c);
-        }
-    __syncthreads();
-    // pass 2: hand out slots
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        if (touched[it] == 0) continue;
-        const int64_t idx = base + it * 256 + tid;
-        const int f = (int)(idx % F);
-        const uint32_t tb = (uint32_t)(idx / F) * gx * gy;
-        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
-        const uint64_t key = ((uint64_t)__float_as_uint(key_depth[idx]) << 32) | (uint32_t)f;
-        if (touched[it] > BIG_RECT) {
-            const uint32_t q = atomicAdd(&s_nbig, 1u);
-            if (q < (uint32_t)BIG_MAX) { s_big[q] = BigFace{rr[it].x, rr[it].y, tb, (uint32_t)key, (uint32_t)(key >> 32)}; continue; }
-        }
-        const bool direct = !(w.lds && mine[it]) || touched[it] > BIG_RECT;
-        for (uint32_t y = miny; y < maxy; y++)
-            for (uint32_t x = minx; x < maxx; x++) {
-                const uint32_t slot = direct ? atomicAdd(&tile_cursor[tb + y * gx + x], 1u)
-                                             : atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
-                if (slot < capacity) keys[slot] = key;
-            }
-    }
-    __syncthreads();
-    const uint32_t nbig = min(s_nbig, (uint32_t)BIG_MAX);
-    for (uint32_t q = 0; q < nbig; q++) {
-        const BigFace f = s_big[q];
-        const uint64_t key = ((uint64_t)f.key_hi << 32) | f.key_lo;
-        // four returning atomics in flight per thread (one at a time: 0.28 ms for 64 screen-filling faces in one workgroup)
-        for (RectWalk t(f.rect_lo & 0xffffu, f.rect_lo >> 16, f.rect_hi & 0xffffu, f.rect_hi >> 16, (uint32_t)tid); t.valid();) {
-            uint32_t tile[4], slot[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                tile[u] = 0xffffffffu;
-                if (t.valid()) { tile[u] = f.tile_base + t.y * gx + t.x; t.next(); }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) slot[u] = tile[u] != 0xffffffffu ? atomicAdd(&tile_cursor[tile[u]], 1u) : 0xffffffffu;
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (slot[u] < capacity) keys[slot[u]] = key;
-        }
-    }
+    for_each_bin(sh, w, gx, gy, [&](uint32_t&, uint32_t c, uint32_t tile) { atomicAdd(&tile_count[tile], c); });
+    for_each_big_face(sh, [&](const BigFace& f, RectWalk& t) {
+        for (; t.valid(); t.next()) atomicAdd(&tile_count[f.tile_base + t.y * gx + t.x], 1u);
+    });
 }
 
 // ---------------------------------------------------------------------------
-// 2 + 4 in one visit of every face (tri, frames up to SCAN_SINGLE_MAX tiles, a placement exists: dmr_api.hip).  Every tile's
-//   segment [seg[t], seg[t + 1]) was placed from an earlier call's counts (k_build_placement), the cursors start at the
-//   segment starts (k_project_verts), so nothing has to be counted and scanned before entries can be emitted: the workgroup
-//   culls / bounds / keys its faces as the set-up pass does, counts them into its LDS window, reserves every non-empty bin
-//   with one returning atomic on the tile's cursor and hands the slots out with returning LDS atomics as the scatter pass
-//   does.  A reservation that ends behind its segment (or behind the buffer) emits NOTHING -- its bin hands out slots from
-//   SEG_FULL on, which no buffer holds; the cursor, which advances by the true count all the same, then stands behind the
-//   segment's end, which is how the compositing kernels recognise such a tile (they render it empty; the call is redone or flagged)
-//   and how the forward's size workgroup (ListSize, dmr_kernels.hpp) sees the overflow; R is the sum of cursor - start.
-//   No workgroup waits for another, and none touches a word that all the others touch.
+// 4, and 2 + 4 in one visit of every face (tri, frames up to SCAN_SINGLE_MAX tiles, a placement exists: dmr_api.hip): ONE
+//   emission, bin_emit, with two policies for where a tile's slots end.
+//   Exact (k_scatter_faces_lds, SEG = false): the scan laid the segments out from this call's counts, a slot is good below
+//   the buffer's capacity, the faces' rects and keys are the set-up pass's.
+//   Placed (k_bin_faces, SEG = true): every tile's segment [seg[t], seg[t + 1]) was placed from an earlier call's counts
+//   (k_build_placement), the cursors start at the segment starts (k_project_verts), so nothing has to be counted and scanned
+//   before entries can be emitted: the workgroup culls / bounds / keys its faces as the set-up pass does (face_bin) and emits.
+//   A slot is good below min(seg[t + 1], capacity).  A reservation that ends behind its segment (or behind the buffer) emits
+//   NOTHING -- its bin hands out slots from SEG_FULL on, which no buffer holds; the cursor, which advances by the true count all
+//   the same, then stands behind the segment's end, which is how the compositing kernels recognise such a tile (they render it
+//   empty; the call is redone or flagged) and how the forward's size workgroup (ListSize, dmr_kernels.hpp) sees the overflow;
+//   R is the sum of cursor - start.  No workgroup waits for another, and none touches a word that all the others touch.
 // ---------------------------------------------------------------------------
 constexpr uint32_t SEG_FULL = 0xC0000000u;
 
-template <int FPT>
-__global__ void __launch_bounds__(256)
-k_bin_faces(int B, int P, int F, const int* __restrict__ faces, const float4* __restrict__ vproj, int gx, int gy, int r0, int r1,
-            float* __restrict__ key_depth, uint32_t* __restrict__ tiles_touched, const uint32_t* __restrict__ seg,
-            uint32_t* __restrict__ tile_cursor, uint64_t* __restrict__ keys, uint32_t capacity,
-            unsigned long long* __restrict__ mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first) {
-    if (mask_offset_dst && blockIdx.x == 0 && threadIdx.x == 0) { mask_offset_dst[0] = mask_offset; mask_offset_dst[1] = mask_first; }
-    __shared__ uint32_t s_hist[LDS_HIST_MAX];
-    __shared__ int s_box[4];
-    __shared__ BigFace s_big[BIG_MAX];
-    __shared__ uint32_t s_nbig;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_nbig = 0u;  // (bin_window's barriers order this before the queueing below)
-    const int64_t BF = (int64_t)B * F;
-    const int64_t base = (int64_t)blockIdx.x * (256 * FPT);
-    const int view = (int)(base / F);
-    uint2 rr[FPT];
-    uint32_t touched[FPT], kd[FPT];
-    bool mine[FPT];  // face of the window's view
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        const int64_t idx = base + it * 256 + tid;
-        touched[it] = 0u; rr[it] = make_uint2(0, 0); mine[it] = false; kd[it] = 0u;
-        if (idx >= BF) continue;
-        const int b = (int)(idx / F), f = (int)(idx % F);
-        mine[it] = b == view;
-        const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
-        const float4 a0 = vproj[(int64_t)b * P + v0], a1 = vproj[(int64_t)b * P + v1], a2 = vproj[(int64_t)b * P + v2];
-        float max_z = a0.z, min_z = a0.z, depth = 0.0f;
-        depth += a0.z;
-        max_z = fmaxf(max_z, a1.z); min_z = fminf(min_z, a1.z); depth += a1.z;
-        max_z = fmaxf(max_z, a2.z); min_z = fminf(min_z, a2.z); depth += a2.z;
-        depth = depth / 3.0f;
-        Rect r = {0, 0, 0, 0};
-        if (!(max_z < -1.0f || min_z > 1.0f)) {
-            r = tile_rect({a0.x, a0.y}, {a1.x, a1.y}, {a2.x, a2.y}, gx, gy, r0, r1);
-            touched[it] = (r.maxy - r.miny) * (r.maxx - r.minx);
-        }
-        if (touched[it] == 0) r = {0, 0, 0, 0};
-        auto map01 = [](float z) { float d = (z + 1.0f) * 0.5f; if (d < 0.0f) d = 0.0f; if (d > 1.0f) d = 1.0f; return d; };
-        rr[it] = make_uint2(r.minx | (r.miny << 16), r.maxx | (r.maxy << 16));
-        const float k = touched[it] ? map01(depth) : 0.0f;
-        kd[it] = __float_as_uint(k);
-        tiles_touched[idx] = touched[it];
-        key_depth[idx] = k;
-    }
-    const BinWindow w = bin_window<FPT>(s_box, view, rr, touched, mine, tid);
-    const int nw = w.wx * w.wy;
-    for (int t = tid; t < nw; t += 256) s_hist[t] = 0u;
-    __syncthreads();
+// where the entries go; mask_*: where the binning buffer of THIS capacity keeps the coverage masks (dmr_kernels.hpp,
+// TriImageState::mask_offset), left on the device for the kernels behind (dst null: tet)
+struct BinOut { uint32_t* tile_cursor; uint64_t* keys; uint32_t capacity; unsigned long long* mask_offset_dst; unsigned long long mask_offset, mask_first; };
+
+template <int FPT, bool SEG>
+__device__ __forceinline__ void bin_emit(const FaceBatch<FPT>& fb, int F, int gx, int gy, const uint32_t* __restrict__ seg, const BinOut& o) {
+    if (o.mask_offset_dst && blockIdx.x == 0 && threadIdx.x == 0) { o.mask_offset_dst[0] = o.mask_offset; o.mask_offset_dst[1] = o.mask_first; }
+    BinShared& sh = bin_shared();
+    auto limit = [&](uint32_t tile) { if constexpr (SEG) return min(seg[tile + 1], o.capacity); else return o.capacity; };
+    const BinWindow w = bin_window(sh, fb);
     // pass 1: count this workgroup's entries per tile of the window
 #pragma unroll
     for (int it = 0; it < FPT; it++) {
-        if (!(w.lds && mine[it]) || touched[it] == 0 || touched[it] > BIG_RECT) continue;
-        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
-        for (uint32_t y = miny; y < maxy; y++)
-            for (uint32_t x = minx; x < maxx; x++) atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
+        if (!(w.lds && fb.mine[it]) || fb.touched[it] == 0 || fb.touched[it] > BIG_RECT) continue;
+        const Rect r = unpack_rect(fb.rr[it]);
+        for (uint32_t y = r.miny; y < r.maxy; y++)
+            for (uint32_t x = r.minx; x < r.maxx; x++) atomicAdd(&sh.hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
     }
     __syncthreads();
     // reserve the workgroup's slots of every non-empty tile with one returning atomic; the bin now holds the cursor
-    for (int y = tid / 64; y < w.wy; y += 4)
-        for (int x = tid % 64; x < w.wx; x += 64) {
-            const uint32_t c = s_hist[y * w.wx + x];
-            if (c == 0u) continue;
-            const uint32_t tile = (uint32_t)view * gx * gy + (uint32_t)(w.y0 + y) * gx + (uint32_t)(w.x0 + x);
-            const uint32_t first = atomicAdd(&tile_cursor[tile], c);
-            s_hist[y * w.wx + x] = first + c <= min(seg[tile + 1], capacity) ? first : SEG_FULL;
-        }
+    for_each_bin(sh, w, gx, gy, [&](uint32_t& bin, uint32_t c, uint32_t tile) {
+        const uint32_t first = atomicAdd(&o.tile_cursor[tile], c);
+        if constexpr (SEG) bin = first + c <= limit(tile) ? first : SEG_FULL;
+        else bin = first;
+    });
     __syncthreads();
-    // pass 2: hand out slots
-#pragma unroll
-    for (int it = 0; it < FPT; it++) {
-        if (touched[it] == 0) continue;
-        const int64_t idx = base + it * 256 + tid;
-        const int f = (int)(idx % F);
-        const uint32_t tb = (uint32_t)(idx / F) * gx * gy;
-        const uint32_t minx = rr[it].x & 0xffffu, miny = rr[it].x >> 16, maxx = rr[it].y & 0xffffu, maxy = rr[it].y >> 16;
-        const uint64_t key = ((uint64_t)kd[it] << 32) | (uint32_t)f;
-        if (touched[it] > BIG_RECT) {
-            const uint32_t q = atomicAdd(&s_nbig, 1u);
-            if (q < (uint32_t)BIG_MAX) { s_big[q] = BigFace{rr[it].x, rr[it].y, tb, (uint32_t)key, (uint32_t)(key >> 32)}; continue; }
-        }
-        const bool direct = !(w.lds && mine[it]) || touched[it] > BIG_RECT;
-        for (uint32_t y = miny; y < maxy; y++)
-            for (uint32_t x = minx; x < maxx; x++) {
-                if (direct) {
-                    const uint32_t tile = tb + y * gx + x;
-                    const uint32_t slot = atomicAdd(&tile_cursor[tile], 1u);
-                    if (slot < min(seg[tile + 1], capacity)) keys[slot] = key;
-                } else {
-                    const uint32_t slot = atomicAdd(&s_hist[(y - w.y0) * w.wx + (x - w.x0)], 1u);
-                    if (slot < capacity) keys[slot] = key;  // (SEG_FULL and up: never)
-                }
-            }
-    }
+    // pass 2: hand out slots (a bin that did not fit hands out SEG_FULL and up: never below the capacity)
+    for_each_face_tile(sh, w, fb, F, gx, gy,
+                       [&](uint32_t& bin, uint64_t key) { const uint32_t slot = atomicAdd(&bin, 1u); if (slot < o.capacity) o.keys[slot] = key; },
+                       [&](uint32_t tile, uint64_t key) { const uint32_t slot = atomicAdd(&o.tile_cursor[tile], 1u); if (slot < limit(tile)) o.keys[slot] = key; });
     __syncthreads();
-    const uint32_t nbig = min(s_nbig, (uint32_t)BIG_MAX);
-    for (uint32_t q = 0; q < nbig; q++) {
-        const BigFace f = s_big[q];
+    for_each_big_face(sh, [&](const BigFace& f, RectWalk& t) {
         const uint64_t key = ((uint64_t)f.key_hi << 32) | f.key_lo;
-        // four returning atomics in flight per thread, as in the scatter pass
-        for (RectWalk t(f.rect_lo & 0xffffu, f.rect_lo >> 16, f.rect_hi & 0xffffu, f.rect_hi >> 16, (uint32_t)tid); t.valid();) {
+        // four returning atomics in flight per thread (one at a time: 0.28 ms for 64 screen-filling faces in one workgroup)
+        while (t.valid()) {
             uint32_t tile[4], slot[4], lim[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -448,13 +344,37 @@ k_bin_faces(int B, int P, int F, const int* __restrict__ faces, const float4* __
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                slot[u] = tile[u] != 0xffffffffu ? atomicAdd(&tile_cursor[tile[u]], 1u) : 0u;
-                lim[u] = tile[u] != 0xffffffffu ? min(seg[tile[u] + 1u], capacity) : 0xffffffffu;
+                const bool live = tile[u] != 0xffffffffu;
+                slot[u] = live ? atomicAdd(&o.tile_cursor[tile[u]], 1u) : 0xffffffffu;
+                lim[u] = live ? limit(tile[u]) : 0u;
             }
 #pragma unroll
-            for (int u = 0; u < 4; u++) if (tile[u] != 0xffffffffu && slot[u] < lim[u]) keys[slot[u]] = key;
+            for (int u = 0; u < 4; u++) if (slot[u] < lim[u]) o.keys[slot[u]] = key;
         }
-    }
+    });
+}
+
+template <int FPT>
+__global__ void __launch_bounds__(256)
+k_scatter_faces_lds(int B, int F, int gx, int gy, const uint2* __restrict__ face_rect, const float* __restrict__ key_depth,
+                    const uint32_t* __restrict__ tiles_touched, BinOut out) {
+    const FaceBatch<FPT> fb = load_faces<FPT>(B, F, [&](int64_t idx, int, int) {
+        const uint32_t touched = tiles_touched[idx];
+        return touched ? FaceBin{touched, face_rect[idx], key_depth[idx], 0.0f} : FaceBin{0u, make_uint2(0, 0), 0.0f, 0.0f};
+    });
+    bin_emit<FPT, false>(fb, F, gx, gy, nullptr, out);
+}
+
+template <int FPT>
+__global__ void __launch_bounds__(256)
+k_bin_faces(int B, int P, int F, const int* __restrict__ faces, const float4* __restrict__ vproj, int gx, int gy, int r0, int r1,
+            float* __restrict__ key_depth, uint32_t* __restrict__ tiles_touched, const uint32_t* __restrict__ seg, BinOut out) {
+    const FaceBatch<FPT> fb = load_faces<FPT>(B, F, [&](int64_t idx, int b, int f) {
+        const FaceBin r = face_bin<false>(b, f, P, faces, vproj, gx, gy, r0, r1);
+        tiles_touched[idx] = r.touched; key_depth[idx] = r.key;
+        return r;
+    });
+    bin_emit<FPT, true>(fb, F, gx, gy, seg, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -837,19 +757,26 @@ void launch_project_verts(const dmr_scene& s, float4* vproj, float* mats, uint32
         s.W, s.H, vproj, mats, counters, (uint32_t)ncounters, seg);
 }
 
+// fn(std::integral_constant<int, FPT>, grid): the faces per thread of n (view, face) pairs and their workgroups
+template <class Fn>
+void with_fpt(int64_t n, Fn fn) {
+    const int fpt = bin_fpt(n);
+    const dim3 grid((unsigned)std::max<int64_t>(1, (n + 256 * fpt - 1) / (256 * fpt)));
+    if (fpt == 1) fn(std::integral_constant<int, 1>{}, grid);
+    else if (fpt == 2) fn(std::integral_constant<int, 2>{}, grid);
+    else fn(std::integral_constant<int, 4>{}, grid);
+}
+
 void launch_setup_faces(const dmr_scene& s, bool tet, const float4* vproj, int gx, int gy, int r0, int r1,
                         uint2* face_rect, float* key_depth, float* max_depth, uint32_t* tiles_touched,
                         uint32_t* tile_count, hipStream_t st) {
     const int64_t n = (int64_t)s.B * s.F;
     if (n == 0) return;
     StageScope t(DMR_STAGE_SETUP_FACES, st);
-    const int fpt = bin_fpt(n);
-    dim3 grid((unsigned)((n + 256 * fpt - 1) / (256 * fpt))), block(256);
-#define DMR_SETUP(TET, FPT) k_setup_faces_lds<TET, FPT><<<grid, block, 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, \
-                                face_rect, key_depth, max_depth, tiles_touched, tile_count)
-    if (tet) { if (fpt == 1) DMR_SETUP(true, 1); else if (fpt == 2) DMR_SETUP(true, 2); else DMR_SETUP(true, 4); }
-    else { if (fpt == 1) DMR_SETUP(false, 1); else if (fpt == 2) DMR_SETUP(false, 2); else DMR_SETUP(false, 4); }
-#undef DMR_SETUP
+    with_fpt(n, [&](auto fpt, dim3 grid) {
+        auto k = tet ? k_setup_faces_lds<true, fpt()> : k_setup_faces_lds<false, fpt()>;
+        k<<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, face_rect, key_depth, max_depth, tiles_touched, tile_count);
+    });
 }
 
 void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor,
@@ -895,25 +822,20 @@ void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_
     const int64_t n = (int64_t)s.B * s.F;
     if (n == 0) return;
     StageScope t(DMR_STAGE_SCATTER, st);
-    const int fpt = bin_fpt(n);
-    const dim3 grid((unsigned)((n + 256 * fpt - 1) / (256 * fpt))), block(256);
-#define DMR_SCATTER(FPT) k_scatter_faces_lds<FPT><<<grid, block, 0, st>>>(s.B, s.F, gx, gy, face_rect, key_depth, tiles_touched, \
-                                                                         tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first)
-    if (fpt == 1) DMR_SCATTER(1); else if (fpt == 2) DMR_SCATTER(2); else DMR_SCATTER(4);
-#undef DMR_SCATTER
+    const BinOut out{tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first};
+    with_fpt(n, [&](auto fpt, dim3 grid) {
+        k_scatter_faces_lds<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.F, gx, gy, face_rect, key_depth, tiles_touched, out);
+    });
 }
 
 void launch_bin_faces(const dmr_scene& s, const float4* vproj, int gx, int gy, int r0, int r1, float* key_depth,
                       uint32_t* tiles_touched, const uint32_t* seg, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
                       unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st) {
-    const int64_t n = (int64_t)s.B * s.F;
     StageScope t(DMR_STAGE_SCATTER, st);
-    const int fpt = bin_fpt(n);
-    const dim3 grid((unsigned)std::max<int64_t>(1, (n + 256 * fpt - 1) / (256 * fpt))), block(256);
-#define DMR_BIN(FPT) k_bin_faces<FPT><<<grid, block, 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, key_depth, tiles_touched, seg, \
-                                                             tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first)
-    if (fpt == 1) DMR_BIN(1); else if (fpt == 2) DMR_BIN(2); else DMR_BIN(4);
-#undef DMR_BIN
+    const BinOut out{tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first};
+    with_fpt((int64_t)s.B * s.F, [&](auto fpt, dim3 grid) {
+        k_bin_faces<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, key_depth, tiles_touched, seg, out);
+    });
 }
 
 void launch_build_placement(int ntiles, const uint32_t* tile_count, const uint32_t* tile_order, uint32_t* start, uint32_t* order,

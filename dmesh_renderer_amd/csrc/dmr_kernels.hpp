@@ -87,8 +87,10 @@ void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_of
 void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_rect, const float* key_depth,
                           const uint32_t* tiles_touched, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
                           unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st);
-// One kernel in place of set-up, scan and scatter (tri, up to SCAN_SINGLE_MAX tiles): seg = the call's tile_offset, which
-// k_project_verts filled from a placement together with the cursors (SegInit).  Also writes key_depth and tiles_touched.
+// One kernel in place of set-up, scan and scatter (tri, up to SCAN_SINGLE_MAX tiles): the set-up pass's per-face work and the
+// scatter pass's emission (the same code, dmr_binning.hip), a slot being good below min(seg[t + 1], capacity) instead of the
+// capacity.  seg = the call's tile_offset, which k_project_verts filled from a placement together with the cursors (SegInit).
+// Also writes key_depth and tiles_touched (not face_rect, not tile_count).
 // Nothing is summed here: R and the overflow come from the cursors, launch_tri_forward's ListSize.  (The first version let every
 // workgroup add its entries to one word and take a ticket, the last one publishing R: 55 us at C4 by the stage events, against
 // 39 us for set-up + scan + scatter, profiles/r05/bench_ab_c4_ticket_variant.txt.)
@@ -137,7 +139,7 @@ struct alignas(16) HitRecord { uint32_t id; uint32_t pixel; float T; float dL_da
 // (dmr_sort.hpp) into face_list before compositing it, no launch_sort_tiles; null: face_list is sorted already
 // size (blocks = 1: behind launch_bin_faces, which sums nothing): one more workgroup adds up the lists and publishes R -- device
 // word, host_size_word(host_seq, R | SIZE_WORD_OVERFLOW if a list left its segment) in pinned memory (may be null), the sticky
-// overflow word (may be null) -- as launch_scan_tiles does on the exact path
+// overflow word (may be null) -- as launch_scan_tiles does on the exact path; the host reads either through sized() (dmr_api.hip)
 struct ListSize { int* num_rendered; unsigned long long* host; uint32_t host_seq; uint32_t* overflow; uint32_t blocks; };
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
