@@ -374,11 +374,8 @@ uint32_t* march_estimate(const SizeKey& key, const Dims& d, bool create, size_t*
     return g.seq_steps;
 }
 
-// Where the kernel that computes a size publishes it ({host word, sequence number, overflow word} of the scans and
-// dmr::HitRegions): a default call's pinned word; an asynchronous call's overflow word, raised above `capacity`; or NOWHERE
-// (a redo: the size is known, and a late store could land in the word after a later call, on another stream, took it over).
-struct SizeOut { unsigned long long* host; uint32_t seq; uint32_t* overflow; uint32_t capacity; };
-const SizeOut NOWHERE{nullptr, 0u, nullptr, 0xffffffffu};
+using dmr::SizeOut;  // where the kernel that computes a size publishes it: the size port, dmr_kernels.hpp
+using dmr::NOWHERE;
 
 // One speculatively sized buffer: its estimate, its largest size (the clamp of a guess; an exact size above it is the error
 // too_large), its word in SizeRead, the error of an asynchronous call without an estimate.
@@ -402,7 +399,7 @@ int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_
     }
     if (async) {  // no host wait at all: capacity from the estimate, overflow checked on the device
         if (!guess || !overflow) return fail(z.no_estimate);
-        if (first(guess, SizeOut{nullptr, 0u, overflow, (uint32_t)guess})) return 1;
+        if (first(guess, SizeOut{nullptr, overflow, 0u, (uint32_t)guess})) return 1;
         *size = guess;  // an upper bound the backward accepts in R's place
         DMR_HIP(hipGetLastError());
         return 0;
@@ -410,7 +407,7 @@ int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_
     SizeRead& sr = g_size_read[dev];
     if (!sr.slot && !(sr.slot = pinned_words())) return fail("hipHostMalloc failed");
     const uint32_t seq = sr.next_seq();
-    if (first(guess, SizeOut{const_cast<unsigned long long*>(sr.word(z.word)), seq, nullptr, 0xffffffffu})) return 1;
+    if (first(guess, SizeOut{const_cast<unsigned long long*>(sr.word(z.word)), nullptr, seq, 0xffffffffu})) return 1;
     unsigned long long n = 0;
     if (wait_size(sr.word(z.word), seq, st, &n)) return 1;  // the call's one host wait (rasterizer_impl.cu:287-292)
     const bool full = placed_capacity ? (n & dmr::SIZE_WORD_OVERFLOW) != 0 : n > guess;
@@ -455,8 +452,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
         dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st);
         dmr::launch_setup_faces(*s, tet, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.rect, fs.key_depth, fs.max_depth,
                                 fs.tiles_touched, is.tile_count, st);
-        dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, out.host, out.seq, is.tile_order,
-                               is.scan_tmp, out.capacity, out.overflow, st);
+        dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, is.tile_order, is.scan_tmp, out, st);
     };
     // the call's binning buffer, carved into c.bs (none at all: a call with no entries and no march sequence)
     auto binning = [&](uint64_t capacity) -> int {
@@ -479,7 +475,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
             if (d.ntiles > dmr::SCAN_SINGLE_MAX)
                 dmr::launch_sort_tiles(d.ntiles, is.tile_offset, is.tile_order, bs.keys, bs.face_list, bs.capacity, st);
         }
-        render(c, dmr::ListSize{nullptr, nullptr, 0u, nullptr, 0u});
+        render(c, dmr::ListSize{nullptr, NOWHERE, 0u});
         return 0;
     };
     // speculative placement: projection -> one binning kernel -> render, whose first workgroup leaves the size word
@@ -490,7 +486,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
                                   dmr::SegInit{pl.start, pl.order, is.tile_offset, is.tile_cursor, is.tile_order, (uint32_t)d.ntiles});
         dmr::launch_bin_faces(*s, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.tiles_touched, is.tile_offset, is.tile_cursor, bs.keys,
                               bs.capacity, is.mask_offset, bs.mask_offset, bs.mask_first, st);
-        render(c, dmr::ListSize{is.num_rendered, out.host, out.seq, out.overflow, 1u});  // (its first workgroup publishes R)
+        render(c, dmr::ListSize{is.num_rendered, out, 1u});  // (its first workgroup publishes R)
         return 0;
     };
 
@@ -685,14 +681,13 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         if (camera) dmr::launch_camera_reduce(s->B, d.gx * d.gy, 32, cam_part, cam_out, st);
         return 0;
     };
-    const dmr::HitRegions scanned{nullptr, nullptr, nullptr, nullptr, 0u};
-    auto self_laid = [&](SizeOut out) { return dmr::HitRegions{is.hit_offset, is.hit_total, out.host, out.overflow, out.seq}; };
+    const dmr::HitRegions scanned{nullptr, nullptr, NOWHERE};
+    auto self_laid = [&](SizeOut out) { return dmr::HitRegions{is.hit_offset, is.hit_total, out}; };
     // With a size estimate and few enough tiles the per-pixel kernel lays the regions out itself: no scan launch.
     const bool self_regions = d.ntiles <= dmr::SCAN_SINGLE_MAX;
     auto first = [&](uint64_t guess, SizeOut out) -> int {
         if (guess && self_regions) return rest(guess, self_laid(out));
-        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.tile_cursor, is.hit_offset, is.tile_used, is.hit_total, out.host, out.seq,
-                              is.scan_tmp, out.capacity, out.overflow, st);
+        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.tile_cursor, is.hit_offset, is.tile_used, is.hit_total, is.scan_tmp, out, st);
         return guess ? rest(guess, scanned) : 0;
     };
     const Sizing hit_records{&SizeGuess::hits_per_face, 0xfffffffeu, 1, "more than 2^32 blended (pixel, face) pairs",

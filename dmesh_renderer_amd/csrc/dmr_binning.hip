@@ -450,8 +450,7 @@ __device__ __forceinline__ void slab_write_offsets(uint32_t* __restrict__ slab, 
 
 __global__ void __launch_bounds__(1024)
 k_scan_tiles(int n, const uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_offset,
-             uint32_t* __restrict__ tile_cursor, int* __restrict__ num_rendered, unsigned long long* __restrict__ host_num_rendered,
-             uint32_t host_seq, uint32_t* __restrict__ tile_order, uint32_t capacity, uint32_t* __restrict__ overflow) {
+             uint32_t* __restrict__ tile_cursor, int* __restrict__ num_rendered, uint32_t* __restrict__ tile_order, SizeOut out) {
     static_assert(ORDER_CELLS == 1024, "one counter cell per thread");
     __shared__ uint32_t wave_sum[17];
     __shared__ uint32_t bucket[ORDER_CELLS + 1];
@@ -499,11 +498,9 @@ k_scan_tiles(int n, const uint32_t* __restrict__ tile_count, uint32_t* __restric
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < SCAN_BATCH; j++) { const int i = j * 1024 + tid; if (i < n) tile_order[i] = slab[i]; }
-    // host_num_rendered: pinned host memory, read by the host after the event recorded behind this kernel
     if (tid == 0) {
         tile_offset[n] = total; *num_rendered = (int)total;
-        if (host_num_rendered) *host_num_rendered = host_size_word(host_seq, total);  // ONE 8-byte store: the host polls it
-        if (overflow && total > capacity) *overflow = 1u;  // asynchronous call that outgrew its buffer (sticky, pinned host memory)
+        out.publish(total);
     }
 }
 
@@ -587,9 +584,7 @@ k_scan_tiles_partial(int n, const uint32_t* __restrict__ tile_count, const uint3
 // (bucket 0 = longest lists first, empty tiles last): the cursors pass 3 claims from
 __global__ void __launch_bounds__(1024)
 k_scan_tiles_blocks(int nblk, int n, uint32_t* __restrict__ blk_sum, uint32_t* __restrict__ bucket_count,
-                    uint32_t* __restrict__ tile_offset, int* __restrict__ num_rendered, unsigned long long* __restrict__ host_num_rendered,
-                    unsigned long long* __restrict__ total64, unsigned long long* __restrict__ host_total64, uint32_t host_seq,
-                    uint32_t capacity, uint32_t* __restrict__ overflow) {
+                    uint32_t* __restrict__ tile_offset, int* __restrict__ num_rendered, unsigned long long* __restrict__ total64, SizeOut out) {
     __shared__ uint32_t wave_sum[17];
     const int tid = threadIdx.x, lane = tid & 63;
     unsigned long long carry = 0;  // the 32-bit offsets wrap harmlessly when the total does not fit (the host checks it)
@@ -602,9 +597,9 @@ k_scan_tiles_blocks(int nblk, int n, uint32_t* __restrict__ blk_sum, uint32_t* _
     }
     if (tid == 0) {
         tile_offset[n] = (uint32_t)carry;
-        if (num_rendered) { *num_rendered = (int)carry; if (host_num_rendered) *host_num_rendered = host_size_word(host_seq, carry); }
-        if (total64) { *total64 = carry; if (host_total64) *host_total64 = host_size_word(host_seq, carry); }
-        if (overflow && carry > (unsigned long long)capacity) *overflow = 1u;
+        if (num_rendered) *num_rendered = (int)carry;  // (one of the two device totals: the forward's R, the backward's records)
+        if (total64) *total64 = carry;
+        out.publish(carry);
     }
     if (bucket_count && tid < 128) {  // waves 0 and 1; only wave 0 holds buckets 0..63, the empty-tile bucket follows them
         const uint32_t c = tid < ORDER_BUCKETS ? bucket_count[tid] : 0u;
@@ -650,8 +645,7 @@ k_scan_tiles_final(int n, const uint32_t* __restrict__ tile_count, const uint32_
         }
     }
     if (ORDER) {  // empty tiles of the block: one LDS add per wave
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) n_empty += __shfl_xor(n_empty, d, 64);
+        n_empty = wave_total(n_empty);
         if (lane == 0 && n_empty) atomicAdd(&bucket[ORDER_CELLS], (uint32_t)n_empty);
     }
     uint32_t run = blk_sum[blockIdx.x] + block_exclusive_scan(local, tid, wave_sum);
@@ -690,8 +684,7 @@ k_scan_tiles_final(int n, const uint32_t* __restrict__ tile_count, const uint32_
 __global__ void __launch_bounds__(1024)
 k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __restrict__ tile_offset, const uint32_t* __restrict__ tile_end,
             uint32_t* __restrict__ hit_offset,
-            uint32_t* __restrict__ tile_used, unsigned long long* __restrict__ hit_total, unsigned long long* __restrict__ host_hit_total, uint32_t host_seq,
-            uint32_t capacity, uint32_t* __restrict__ overflow) {
+            uint32_t* __restrict__ tile_used, unsigned long long* __restrict__ hit_total, SizeOut out) {
     __shared__ uint32_t wave_sum[17];
     __shared__ unsigned long long s_total;
     __shared__ __attribute__((aligned(16))) uint32_t slab[SCAN_SLAB];
@@ -710,8 +703,7 @@ k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __res
 #pragma unroll
     for (int j = 0; j < SCAN_BATCH; j++) { local += c[j]; wide += c[j]; }
     // 64-bit total (overflow check on the host); the offsets themselves wrap harmlessly in that case
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) wide += __shfl_xor(wide, d, 64);
+    wide = wave_total(wide);
     const uint32_t run = block_exclusive_scan(local, tid, wave_sum);
     if (lane == 0) atomicAdd(&s_total, wide);
     slab_write_offsets(slab, tid, run, c);
@@ -720,8 +712,7 @@ k_scan_hits(int n, const uint32_t* __restrict__ tile_hits, const uint32_t* __res
     for (int j = 0; j < SCAN_BATCH; j++) { const int i = j * 1024 + tid; if (i < n) hit_offset[i] = slab[i]; }
     if (tid == 0) {
         hit_offset[n] = wave_sum[16]; *hit_total = s_total;
-        if (host_hit_total) *host_hit_total = host_size_word(host_seq, s_total);
-        if (overflow && s_total > (unsigned long long)capacity) *overflow = 1u;
+        out.publish(s_total);
     }
 }
 
@@ -780,12 +771,10 @@ void launch_setup_faces(const dmr_scene& s, bool tet, const float4* vproj, int g
 }
 
 void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor,
-                       int* num_rendered, unsigned long long* host_num_rendered, uint32_t host_seq, uint32_t* tile_order, uint32_t* scan_tmp,
-                       uint32_t capacity, uint32_t* overflow, hipStream_t st) {
+                       int* num_rendered, uint32_t* tile_order, uint32_t* scan_tmp, SizeOut out, hipStream_t st) {
     StageScope t(DMR_STAGE_SCAN, st);
     if (ntiles <= SCAN_SINGLE_MAX) {
-        k_scan_tiles<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_count, tile_offset, tile_cursor, num_rendered, host_num_rendered, host_seq, tile_order,
-                                                    capacity, overflow);
+        k_scan_tiles<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_count, tile_offset, tile_cursor, num_rendered, tile_order, out);
         return;
     }
     // scan_tmp: [ORDER_BUCKETS + 1 bucket counters, zeroed by k_project_verts | partial sums per block]
@@ -793,26 +782,23 @@ void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_of
     uint32_t* bucket = scan_tmp;
     uint32_t* blk_sum = scan_tmp + SCAN_TMP_BUCKETS;
     k_scan_tiles_partial<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_count, nullptr, blk_sum, bucket);
-    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, bucket, tile_offset, num_rendered, host_num_rendered,
-                                                        nullptr, nullptr, host_seq, capacity, overflow);
+    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, bucket, tile_offset, num_rendered, nullptr, out);
     k_scan_tiles_final<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_count, nullptr, blk_sum, bucket, tile_offset, tile_cursor, tile_order);
 }
 
 size_t scan_tmp_words(int ntiles) { return SCAN_TMP_BUCKETS + (size_t)(ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES + 1; }
 
 void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,
-                      unsigned long long* hit_total, unsigned long long* host_hit_total, uint32_t host_seq, uint32_t* scan_tmp, uint32_t capacity,
-                      uint32_t* overflow, hipStream_t st) {
+                      unsigned long long* hit_total, uint32_t* scan_tmp, SizeOut out, hipStream_t st) {
     StageScope t(DMR_STAGE_SCAN, st);
     if (ntiles <= SCAN_SINGLE_MAX) {
-        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, tile_end, hit_offset, tile_used, hit_total, host_hit_total, host_seq, capacity, overflow);
+        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, tile_end, hit_offset, tile_used, hit_total, out);
         return;
     }
     const int nblk = (ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES;
     uint32_t* blk_sum = scan_tmp + SCAN_TMP_BUCKETS;  // the forward's partial sums are no longer needed
     k_scan_tiles_partial<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, blk_sum, nullptr);
-    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, nullptr, hit_offset, nullptr, nullptr, hit_total,
-                                                        host_hit_total, host_seq, capacity, overflow);
+    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, nullptr, hit_offset, nullptr, hit_total, out);
     k_scan_tiles_final<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, blk_sum, nullptr, hit_offset, tile_used, nullptr);
 }
 

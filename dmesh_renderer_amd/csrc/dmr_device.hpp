@@ -50,6 +50,38 @@ constexpr int TILE = 16;            // cuda_*/config.h:5-6 (BLOCK_X = BLOCK_Y = 
 constexpr int TILE_PIX = 256;
 constexpr float T_EPS = 0.0001f;    // auxiliary.h:8
 
+// tile index (view-major, then rows) -> column, row, view
+struct TileCoords { int tx, ty, b; };
+__device__ __forceinline__ TileCoords tile_coords(int tile, int gx, int gy) { return {tile % gx, (tile / gx) % gy, tile / (gx * gy)}; }
+
+// Sum of one value per lane over the wave, on every lane (all 64 lanes active).
+template <class T>
+__device__ __forceinline__ T wave_total(T v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// ... and over a 256-thread workgroup (four waves), on every thread: ONE barrier; s4 is four words of LDS nobody else
+// touches until the next barrier after the call.  Two values share that barrier (s8: eight words, a's sums then b's).
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* s4) {
+    v = wave_total(v);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s4[0] + s4[1] + s4[2] + s4[3];
+}
+template <class T>
+__device__ __forceinline__ void block_sum(T& a, T& b, T* s8) {
+    a = wave_total(a); b = wave_total(b);
+    if ((threadIdx.x & 63) == 0) { s8[threadIdx.x >> 6] = a; s8[4 + (threadIdx.x >> 6)] = b; }
+    __syncthreads();
+    a = s8[0] + s8[1] + s8[2] + s8[3]; b = s8[4] + s8[5] + s8[6] + s8[7];
+}
+
+// g[N] += m * g[N] of the lane DPP selects, one v_fmac_f32_dpp: a line of the asm blocks of the tri backward's segmented
+// scan and the tet backward's merge (operands named g0.., m).
+#define DMR_FMAC_DPP(N, DPP) "v_fmac_f32_dpp %[g" #N "], %[g" #N "], %[m] " DPP "\n\t"
+
 struct V2 { float x, y; };
 struct V3 { float x, y, z; };
 struct V4 { float x, y, z, w; };
@@ -64,6 +96,23 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y 
 __device__ __forceinline__ V3 cross(V3 a, V3 b) {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
+
+// The backward kernels' arithmetic that decides nothing (no index, no branch): the compiler may contract a*b+c to FMA here,
+// and rcp is the 1-ulp v_rcp_f32.  Gradients are checked to 1e-4 and the reference's own sums are unordered float atomics.
+// F3 is that arithmetic's vector type: the V3 helpers above are compiled under -ffp-contract=off and keep that when inlined.
+#pragma clang fp contract(fast)
+namespace fast {
+struct F3 { float x, y, z; };
+__device__ __forceinline__ F3 operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ F3 operator-(F3 a) { return {-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ F3 operator*(float b, F3 a) { return {b * a.x, b * a.y, b * a.z}; }
+__device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ F3 load3(const float* __restrict__ a, int id) { return {a[3 * id], a[3 * id + 1], a[3 * id + 2]}; }
+__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+}  // namespace fast
+#pragma clang fp contract(off)  // (= the library's default: build.py compiles everything with -ffp-contract=off, see the top)
 
 // float -> int32, truncating, saturating, NaN -> 0 (v_cvt_i32_f32; same as CUDA's cvt.rzi)
 __device__ __forceinline__ int f2i(float v) { return __float2int_rz(v); }

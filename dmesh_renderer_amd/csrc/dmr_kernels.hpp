@@ -79,11 +79,28 @@ __host__ __device__ inline unsigned long long host_size_word(uint32_t seq, unsig
 }
 // the forward behind launch_bin_faces sets this bit of the size it publishes when a tile's entries did not fit its segment (R < 2^31 lies below)
 constexpr unsigned long long SIZE_WORD_OVERFLOW = 1ull << 39;
-// host_num_rendered (pinned, may be null): receives host_size_word(host_seq, R).  overflow (pinned, may be null): set to 1 when
-// R > capacity (asynchronous calls, which never read R on the host)
+// THE SIZE PORT: where the kernel that computes a size the host may wait on -- R of the tile scans and of the forward's size
+// workgroup, the record total of k_scan_hits / k_tri_backward_pix -- publishes it.  sized() (dmr_api.hip) fills one in per call
+// and the launchers hand it through by value; publish() is the only device code that forms a size word or touches the
+// overflow word.
+//   host      pinned word of a default (waiting) call, null otherwise: receives host_size_word(seq, size) in ONE 8-byte
+//             store, with SIZE_WORD_OVERFLOW or-ed in when a list left its segment (the host then redoes the call);
+//   overflow  pinned sticky word of an asynchronous / captured call, which never reads the size on the host, null otherwise:
+//             set to 1 when the size exceeds `capacity` or a segment overflowed; only dmr_overflowed() clears it;
+//   NOWHERE   publishes nothing: a redo, whose size is known -- a late store could land in the word after a later call, on
+//             another stream, took it over.
+// The device-side totals (*num_rendered, an int; *hit_total, 64 bits) are plain stores at their sites, not part of the port.
+struct SizeOut {
+    unsigned long long* host; uint32_t* overflow; uint32_t seq; uint32_t capacity;
+    __device__ __forceinline__ void publish(unsigned long long size, bool segment_overflow = false) const {
+        if (host) *host = host_size_word(seq, size | (segment_overflow ? SIZE_WORD_OVERFLOW : 0ull));
+        if (overflow && (size > (unsigned long long)capacity || segment_overflow)) *overflow = 1u;
+    }
+};
+constexpr SizeOut NOWHERE{nullptr, nullptr, 0u, 0xffffffffu};
+// out: where R goes (the size port above)
 void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor,
-                       int* num_rendered, unsigned long long* host_num_rendered, uint32_t host_seq, uint32_t* tile_order, uint32_t* scan_tmp,
-                       uint32_t capacity, uint32_t* overflow, hipStream_t st);
+                       int* num_rendered, uint32_t* tile_order, uint32_t* scan_tmp, SizeOut out, hipStream_t st);
 void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_rect, const float* key_depth,
                           const uint32_t* tiles_touched, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
                           unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st);
@@ -137,28 +154,26 @@ struct alignas(16) HitRecord { uint32_t id; uint32_t pixel; float T; float dL_da
 // upstream gradient, which reaches dL_dfopacity only.  A compile-time variant of the kernels; the default ones are unchanged.
 // keys: the unsorted (depth_bits << 32 | face) list entries of the scatter pass: every tile's workgroup sorts its own list
 // (dmr_sort.hpp) into face_list before compositing it, no launch_sort_tiles; null: face_list is sorted already
-// size (blocks = 1: behind launch_bin_faces, which sums nothing): one more workgroup adds up the lists and publishes R -- device
-// word, host_size_word(host_seq, R | SIZE_WORD_OVERFLOW if a list left its segment) in pinned memory (may be null), the sticky
-// overflow word (may be null) -- as launch_scan_tiles does on the exact path; the host reads either through sized() (dmr_api.hip)
-struct ListSize { int* num_rendered; unsigned long long* host; uint32_t host_seq; uint32_t* overflow; uint32_t blocks; };
+// size (blocks = 1: behind launch_bin_faces, which sums nothing): one more workgroup adds up the lists, stores R and publishes
+// it through the size port -- with the segment-overflow flag if a list left its segment -- as launch_scan_tiles does on the
+// exact path
+struct ListSize { int* num_rendered; SizeOut out; uint32_t blocks; };
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
                         float* out_color, float* out_depth, hipStream_t st, bool alpha = false,
-                        ListSize size = ListSize{nullptr, nullptr, 0u, nullptr, 0u});
-// host_*: pinned host memory the kernel also writes its total to (no separate device->host copy)
+                        ListSize size = ListSize{nullptr, NOWHERE, 0u});
 // hit_offset: every tile's region of the record buffer, sized by the bound h + (HIT_GROUP - 1) * min(list length, h) of
-// its h blended pairs (tile_hits); tile_used is cleared (the per-pixel kernel fills it)
+// its h blended pairs (tile_hits); tile_used is cleared (the per-pixel kernel fills it).  out: where the total goes (size port)
 void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,
-                      unsigned long long* hit_total, unsigned long long* host_hit_total, uint32_t host_seq, uint32_t* scan_tmp, uint32_t capacity,
-                      uint32_t* overflow, hipStream_t st);
+                      unsigned long long* hit_total, uint32_t* scan_tmp, SizeOut out, hipStream_t st);
 // Without launch_scan_hits (B * tiles <= SCAN_SINGLE_MAX): every workgroup of k_tri_backward_pix sums the record bounds of
 // the tiles before its own (tile_bound: eight 16-byte loads per thread, all in flight at once) and publishes hit_offset[tile] /
-// tile_used[tile] for the hit-parallel kernel; the last tile's workgroup also leaves the total (device, pinned host) and
-// raises the overflow word when it exceeds the capacity.  One launch and ~8 us of single-workgroup latency less per step.
+// tile_used[tile] for the hit-parallel kernel; the last tile's workgroup also stores the total and publishes it through the
+// size port.  One launch and ~8 us of single-workgroup latency less per step.
 struct HitRegions {
     uint32_t* hit_offset;                 // null: the regions come from launch_scan_hits
-    unsigned long long* hit_total; unsigned long long* host_hit_total; uint32_t* overflow;  // the last two may be null
-    uint32_t host_seq;                    // host_hit_total receives host_size_word(host_seq, total)
+    unsigned long long* hit_total;
+    SizeOut out;
 };
 // also zeroes work[0, work_floats) (the packed accumulators)
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,

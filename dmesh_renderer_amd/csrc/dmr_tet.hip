@@ -344,12 +344,6 @@ __device__ __forceinline__ bool march_step(const TetParams& p, V3 ro, V3 rd, int
     return true;
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {  // all 64 lanes must be active
 #pragma unroll
     for (int dlt = 32; dlt > 0; dlt >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, dlt, 64));
@@ -511,14 +505,8 @@ struct TetAccum {
 // 1-ulp reciprocals and the hardware exponential.  Gradients are checked to 1e-4; the forward and the re-marching kernel,
 // whose tests pick faces, keep the exact forms.
 #pragma clang fp contract(fast)
-namespace tfast {
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 operator*(float b, F3 a) { return {b * a.x, b * a.y, b * a.z}; }
-__device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+namespace tfast {  // fast's F3 (dmr_device.hpp) and what this renderer adds to it
+using namespace fast;
 // (t, u, v) of cuda_renderer/auxiliary.h:265-296 without the hit test (the march already decided)
 __device__ __forceinline__ void tuv(F3 o, F3 d, F3 p0, F3 p1, F3 p2, float& t, float& u, float& v) {
     const F3 T = o - p0, E1 = p1 - p0, E2 = p2 - p0;
@@ -753,12 +741,11 @@ struct TetBwdPixel {
 // value (a select + add is three instructions, and the DPP forms are half rate: 120 of this kernel's 530 VALU instructions per
 // step were these merges).  Non-finite values never get here (tet_accumulate takes such lanes out first): 0 * inf would
 // leak NaN into the partner's face.
-#define DMR_TET_FMAC(N, DPP) "v_fmac_f32_dpp %[g" #N "], %[g" #N "], %[m] " DPP "\n\t"
 // ten values g[0..9] of the array G (the full kernels merge their second ten, G = g + 10, with a block of their own)
 #define DMR_TET_MERGE10(DPP, G)                                                                                         \
     asm volatile("s_nop 1\n\t"                                                                                          \
-                 DMR_TET_FMAC(0, DPP) DMR_TET_FMAC(1, DPP) DMR_TET_FMAC(2, DPP) DMR_TET_FMAC(3, DPP) DMR_TET_FMAC(4, DPP)  \
-                 DMR_TET_FMAC(5, DPP) DMR_TET_FMAC(6, DPP) DMR_TET_FMAC(7, DPP) DMR_TET_FMAC(8, DPP) DMR_TET_FMAC(9, DPP)  \
+                 DMR_FMAC_DPP(0, DPP) DMR_FMAC_DPP(1, DPP) DMR_FMAC_DPP(2, DPP) DMR_FMAC_DPP(3, DPP) DMR_FMAC_DPP(4, DPP)  \
+                 DMR_FMAC_DPP(5, DPP) DMR_FMAC_DPP(6, DPP) DMR_FMAC_DPP(7, DPP) DMR_FMAC_DPP(8, DPP) DMR_FMAC_DPP(9, DPP)  \
                  : [g0] "+v"(G[0]), [g1] "+v"(G[1]), [g2] "+v"(G[2]), [g3] "+v"(G[3]), [g4] "+v"(G[4]),                  \
                    [g5] "+v"(G[5]), [g6] "+v"(G[6]), [g7] "+v"(G[7]), [g8] "+v"(G[8]), [g9] "+v"(G[9])                   \
                  : [m] "v"(m))
@@ -909,7 +896,7 @@ __device__ __forceinline__ void tet_camera_tile(const TetParams& p, int b, int p
         c[24] = cam.sz; c[25] = cam.sw;
     }
 #pragma unroll
-    for (int i = 0; i < 32; i++)
+    for (int i = 0; i < 32; i++)  // (not wave_total: the helper moves this kernel's registers)
 #pragma unroll
         for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
     __syncthreads();  // (the flush has read the table)

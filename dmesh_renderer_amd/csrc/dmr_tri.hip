@@ -262,8 +262,8 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // Behind the one-kernel binning nobody has summed the lists yet: workgroup 0 does, from the cursors (<= SCAN_SINGLE_MAX tiles:
     // 64 coalesced loads per thread, next to ~3 000 compositing workgroups), and publishes R as the scan kernel does on the
-    // exact path -- with SIZE_WORD_OVERFLOW / the overflow word when a list left its segment or the buffer.  Every other
-    // workgroup takes the tile at its position - 1.
+    // exact path -- flagged as a segment overflow when a list left its segment or the buffer.  Every other workgroup takes
+    // the tile at its position - 1.
     if (p.size.blocks && blockIdx.x == 0u) {
         const int nt = p.B * p.gx * p.gy;
         uint32_t total = 0u, full = 0u;
@@ -272,18 +272,10 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
             total += e - b0;
             full |= (e > p.tile_offset[t + 1] || e > p.list_capacity) ? 1u : 0u;
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { total += __shfl_xor(total, d, 64); full |= __shfl_xor(full, d, 64); }
-        if (lane == 0) { s_hits[wave] = total; if (wave < 2) s_live[wave] = 0u; }
-        __syncthreads();
-        if (lane == 0 && full) atomicOr(&s_live[0], 1u);
-        __syncthreads();
+        block_sum(total, full, reinterpret_cast<uint32_t*>(s_mem));  // (full: threads that saw such a list)
         if (tid == 0) {
-            const uint32_t R = s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3];
-            const bool any = s_live[0] != 0u;
-            *p.size.num_rendered = (int)R;
-            if (p.size.host) *p.size.host = host_size_word(p.size.host_seq, (unsigned long long)R | (any ? SIZE_WORD_OVERFLOW : 0ull));
-            if (p.size.overflow && any) *p.size.overflow = 1u;  // asynchronous call whose scene left its placement (sticky)
+            *p.size.num_rendered = (int)total;
+            p.size.out.publish(total, full != 0u);
         }
         return;  // uniform
     }
@@ -291,7 +283,7 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
     const unsigned long long mask_first_slots = p.mask_offset[1];  // (requested with the tile's id, not behind its list range)
     // tiles are taken longest list first (tile_order, k_scan_tiles); rows outside this shard's band are skipped
     const int tile = (int)p.tile_order[pos];
-    const int tx = tile % p.gx, ty = (tile / p.gx) % p.gy, b = tile / (p.gx * p.gy);
+    const int tx = tile % p.gx, ty = (tile / p.gx) % p.gy, b = tile / (p.gx * p.gy);  // (not tile_coords: it costs this kernel registers)
     if (ty < p.r0 || ty >= p.r1) return;  // uniform
     const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
     const int px = tx * TILE + lx, py = ty * TILE + ly;
@@ -417,12 +409,8 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
 
     {   // blended (pixel, face) pairs of the tile (sizes the backward's hit-record buffer) and the bound on its records: one
         // workgroup per tile, so both are plain stores (empty tiles keep the zeros of k_project_verts)
-#pragma unroll
-        for (int dlt = 32; dlt > 0; dlt >>= 1) n_hits += __shfl_xor(n_hits, dlt, 64);
-        if (lane == 0) s_hits[wave] = n_hits;
-        __syncthreads();
+        const uint32_t h = block_sum(n_hits, s_hits);
         if (tid == 0) {
-            const uint32_t h = s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3];
             const uint32_t bound = record_bound(h, end - begin);
             p.tile_hits[tile] = h;
             p.tile_bound[tile] = bound;
@@ -458,8 +446,6 @@ template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int dpp_i(int old, int src) {
     return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, 0xF, false);
 }
-// 1-ulp reciprocal (v_rcp_f32): gradients are checked to 1e-4, the forward keeps IEEE division
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 constexpr int DPP_ROW_SHR = 0x110;      // + n, n = 1..15
 
 // One level of the segmented inclusive scan over the 21 sums: g += m * g[source lane], m = 1.0 where the
@@ -468,13 +454,12 @@ constexpr int DPP_ROW_SHR = 0x110;      // + n, n = 1..15
 // EXEC mask cannot be used because DPP does not read EXEC-disabled source lanes).  Lanes without a valid source
 // read 0 (bound_ctrl:0); rows excluded by row_mask are not written.  A non-finite value (quirk Q12) would turn
 // 0 * inf into NaN for the neighbouring segment: such lanes are taken out of the scan by the caller.
-#define DMR_SEG1(N, DPP) "v_fmac_f32_dpp %[g" #N "], %[g" #N "], %[m] " DPP "\n\t"
 #define DMR_SEG_LEVEL(DPP)                                                                                     \
     asm volatile("s_nop 1\n\t"                                                                                 \
-                 DMR_SEG1(0, DPP) DMR_SEG1(1, DPP) DMR_SEG1(2, DPP) DMR_SEG1(3, DPP) DMR_SEG1(4, DPP) DMR_SEG1(5, DPP)  \
-                 DMR_SEG1(6, DPP) DMR_SEG1(7, DPP) DMR_SEG1(8, DPP) DMR_SEG1(9, DPP) DMR_SEG1(10, DPP) DMR_SEG1(11, DPP) \
-                 DMR_SEG1(12, DPP) DMR_SEG1(13, DPP) DMR_SEG1(14, DPP) DMR_SEG1(15, DPP) DMR_SEG1(16, DPP)          \
-                 DMR_SEG1(17, DPP) DMR_SEG1(18, DPP) DMR_SEG1(19, DPP) DMR_SEG1(20, DPP)                           \
+                 DMR_FMAC_DPP(0, DPP) DMR_FMAC_DPP(1, DPP) DMR_FMAC_DPP(2, DPP) DMR_FMAC_DPP(3, DPP) DMR_FMAC_DPP(4, DPP) DMR_FMAC_DPP(5, DPP)  \
+                 DMR_FMAC_DPP(6, DPP) DMR_FMAC_DPP(7, DPP) DMR_FMAC_DPP(8, DPP) DMR_FMAC_DPP(9, DPP) DMR_FMAC_DPP(10, DPP) DMR_FMAC_DPP(11, DPP) \
+                 DMR_FMAC_DPP(12, DPP) DMR_FMAC_DPP(13, DPP) DMR_FMAC_DPP(14, DPP) DMR_FMAC_DPP(15, DPP) DMR_FMAC_DPP(16, DPP)          \
+                 DMR_FMAC_DPP(17, DPP) DMR_FMAC_DPP(18, DPP) DMR_FMAC_DPP(19, DPP) DMR_FMAC_DPP(20, DPP)                           \
                  : [g0] "+v"(g[0]), [g1] "+v"(g[1]), [g2] "+v"(g[2]), [g3] "+v"(g[3]), [g4] "+v"(g[4]),              \
                    [g5] "+v"(g[5]), [g6] "+v"(g[6]), [g7] "+v"(g[7]), [g8] "+v"(g[8]), [g9] "+v"(g[9]),             \
                    [g10] "+v"(g[10]), [g11] "+v"(g[11]), [g12] "+v"(g[12]), [g13] "+v"(g[13]), [g14] "+v"(g[14]),   \
@@ -494,7 +479,7 @@ __device__ __forceinline__ void seg_scan_level(int k, float (&g)[NSCAN]) {
 }
 // The exact-gradient variants of k_tri_backward_hits carry two sums more (the y, z of a third ray moment): the same level
 // over both sets, one key comparison.
-#define DMR_SEG_EXTRA(DPP) asm volatile("s_nop 1\n\t" DMR_SEG1(0, DPP) DMR_SEG1(1, DPP) : [g0] "+v"(e[0]), [g1] "+v"(e[1]) : [m] "v"(m))
+#define DMR_SEG_EXTRA(DPP) asm volatile("s_nop 1\n\t" DMR_FMAC_DPP(0, DPP) DMR_FMAC_DPP(1, DPP) : [g0] "+v"(e[0]), [g1] "+v"(e[1]) : [m] "v"(m))
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void seg_scan_level(int k, float (&g)[NSCAN], float (&e)[2]) {
     const int ko = dpp_i<CTRL, ROW_MASK>((int)0x80000000, k);
@@ -547,6 +532,11 @@ constexpr uint32_t HIT_SKIPPED = 0x80000000u;
 // = T_final / (1 - opacity_i) is minus the factor of the background terms, so -g_a joins bd_dot (which only enters that tail
 // term): one more 4-byte load per pixel, no register more in the loop; only this variant's summation order differs.
 constexpr int PIX_WAVES = 6;
+// the last tile's workgroup, from either of its exits: the record total, on the device and through the size port
+__device__ __forceinline__ void publish_hit_total(const HitRegions& regions, unsigned long long total) {
+    *regions.hit_total = total;
+    regions.out.publish(total);
+}
 template <bool SCANNED, bool ALPHA = false>
 __global__ void __launch_bounds__(256, PIX_WAVES)
 k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
@@ -570,7 +560,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     }
     // tiles are taken longest list first (tile_order, k_scan_tiles); rows outside this shard's band are skipped
     const int tile = (int)p.tile_order[blockIdx.x];
-    const int tx = tile % p.gx, ty = (tile / p.gx) % p.gy, b = tile / (p.gx * p.gy);
+    const auto [tx, ty, b] = tile_coords(tile, p.gx, p.gy);
     const uint32_t begin = p.tile_offset[tile], end = list_end(p.tile_offset, p.tile_end, tile);
     // The tile's region of the record buffer.  Without a scan kernel (regions.hit_offset, dmr_kernels.hpp) it starts at the
     // sum of the bounds of all tiles before this one -- an empty tile, or one outside this shard's band, has none -- and this
@@ -614,15 +604,9 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
             before += (unsigned long long)((i + 2 < tile ? v[j].z : 0u)) + (i + 3 < tile ? v[j].w : 0u);
         }
         if (bound == 0u) {  // the last tile, and nothing blended in it: only the total is wanted of this workgroup
-#pragma unroll
-            for (int dlt = 32; dlt > 0; dlt >>= 1) before += __shfl_xor(before, dlt, 64);
-            if (lane == 0) s_before[wave] = before;
-            __syncthreads();
+            const unsigned long long total = block_sum(before, s_before);
             if (tid == 0) {
-                const unsigned long long total = s_before[0] + s_before[1] + s_before[2] + s_before[3];
-                *regions.hit_total = total;
-                if (regions.host_hit_total) *regions.host_hit_total = host_size_word(regions.host_seq, total);
-                if (regions.overflow && total > (unsigned long long)capacity) *regions.overflow = 1u;
+                publish_hit_total(regions, total);
                 p.tile_used[tile] = 0u;
             }
             return;
@@ -671,9 +655,8 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     if (tid < MASK_CHUNK) s_fcnt[tid] = 0u;
     __syncthreads();
     if (last_contributor) atomicMax(&s_max_last, last_contributor);
-    if (self) {
-#pragma unroll
-        for (int dlt = 32; dlt > 0; dlt >>= 1) before += __shfl_xor(before, dlt, 64);
+    if (self) {  // (not block_sum: the sum shares its barrier with s_max_last)
+        before = wave_total(before);
         if (lane == 0) s_before[wave] = before;
     }
     __syncthreads();
@@ -683,12 +666,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
         region0 = (uint32_t)before;  // (offsets beyond 2^32 wrap harmlessly: the total says so)
         if (tid == 0) {
             regions.hit_offset[tile] = region0;
-            if (last) {
-                const unsigned long long all = before + p.tile_bound[tile];
-                *regions.hit_total = all;
-                if (regions.host_hit_total) *regions.host_hit_total = host_size_word(regions.host_seq, all);
-                if (regions.overflow && all > (unsigned long long)capacity) *regions.overflow = 1u;
-            }
+            if (last) publish_hit_total(regions, before + p.tile_bound[tile]);
             if (total == 0) p.tile_used[tile] = 0u;  // (cannot happen for a tile with blended pairs; published all the same)
         }
     }
@@ -823,7 +801,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
                 if (slot < capacity && !DMR_DBG(p, 16384)) hits[slot] = hr;
                 continue;
             }
-            const float inv_denom = fast_rcp(denom);
+            const float inv_denom = fast::rcp(denom);
             const float iu = dot(Pv, Tv) * inv_denom;
             const float iv = dot(Q, rd) * inv_denom;
             float iuc, ivc; int code;
@@ -835,7 +813,7 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
             const float iC2 = (i0 * r.c0[2] + i1 * r.c1[2] + i2 * r.c2[2]) * intense;
             const float iD = i0 * r.d0 + i1 * r.d1 + i2 * r.d2;
             const float alpha = r.opacity;
-            const float inv_1ma = fast_rcp(1.f - alpha);
+            const float inv_1ma = fast::rcp(1.f - alpha);
             if (!first_pass) T = T * inv_1ma;  // Q10
             first_pass = false;
             float dL_dalpha = 0.0f;
@@ -876,20 +854,9 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
 // (backward.cu:389-418).
 // ---------------------------------------------------------------------------
 // From here to k_tri_backward_hits' end the compiler may contract a*b+c to FMA: gradients are checked to 1e-4
-// and the reference's own sums are unordered float atomics.  F3 is this block's vector type (the V3 helpers of
-// dmr_device.hpp were compiled under -ffp-contract=off and keep that when inlined).  The forward and everything
-// that decides an index stay exact.
+// and the reference's own sums are unordered float atomics.  fast::F3 (dmr_device.hpp) is this block's vector type.  The
+// forward and everything that decides an index stay exact.
 #pragma clang fp contract(fast)
-namespace fm {
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 operator-(F3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ F3 operator*(float b, F3 a) { return {b * a.x, b * a.y, b * a.z}; }
-__device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ F3 load3(const float* __restrict__ a, int id) { return {a[3 * id], a[3 * id + 1], a[3 * id + 2]}; }
-}  // namespace fm
 
 constexpr int VTAB = 560;   // vertex-row slots per workgroup
 constexpr int TAB_PROBES = 16;
@@ -924,12 +891,6 @@ struct HitsLdsCam : HitsLds {
     float dray[TILE_PIX][3];
     float red[4][24];
 };
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Rows 2k and 2k + 1 share a 64-byte line of `vrow`; they hash to the two slots of one PAIR of slots (the probe sequence
 // moves pair by pair and keeps the row's parity), so the flush -- consecutive slots in consecutive lane groups of one
@@ -1045,7 +1006,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
     }
     L.pixd[tid] = px0;
     L.pixc[tid][0] = px1.x; L.pixc[tid][1] = px1.y; L.pixc[tid][2] = px1.z;
-    fm::F3 camT = {0.f, 0.f, 0.f};  // camera variant: this lane's part of dL/d(ray origin) = sum of dL/dT
+    fast::F3 camT = {0.f, 0.f, 0.f};  // camera variant: this lane's part of dL/d(ray origin) = sum of dL/dT
     if constexpr (CAM) {
 #pragma unroll
         for (int c = 0; c < 3; c++) L.dray[tid][c] = 0.f;
@@ -1081,7 +1042,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         V3 xT = {0.f, 0.f, 0.f}, xE1 = xT, xE2 = xT, xQ = xT, xE12 = xT, xE2T = xT;
         float w2 = 0.f;
         if (valid) {
-            using namespace fm;
+            using namespace fast;
             // the face, once per group
             const float alpha = p.faces_opacity[face], intense = p.faces_intense[(int64_t)b * p.F + face];
             const F3 cc0 = load3(p.verts_color, v0), cc1 = load3(p.verts_color, v1), cc2 = load3(p.verts_color, v2);
@@ -1177,7 +1138,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
                             const V3 gd = su * xE2T + sv * xQ + sb * xE12;  // dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)
                             float* dr = L.dray[raw[q].y & 255u];
                             atomicAdd(dr, gd.x); atomicAdd(dr + 1, gd.y); atomicAdd(dr + 2, gd.z);
-                            camT = camT + fm::F3{dT.x, dT.y, dT.z};
+                            camT = camT + fast::F3{dT.x, dT.y, dT.z};
                         }
                     }
                     float h[NACC];
@@ -1262,9 +1223,9 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         DMR_STAMP(p, 2, g0 / 256u, 3);
         const int kn = __shfl_down(k, 1, 64);
         const bool tail = valid && ((lane & 15) == 15 || kn != k);
-        fm::F3 dp0, dp1, dp2;
+        fast::F3 dp0, dp1, dp2;
         {
-            using namespace fm;
+            using namespace fast;
             const F3 mB = {g[0], g[1], g[2]}, mA = {g[3], g[4], g[5]};
             const F3 fT = {xT.x, xT.y, xT.z}, fE1 = {xE1.x, xE1.y, xE1.z}, fE2 = {xE2.x, xE2.y, xE2.z};
             const F3 fQ = {xQ.x, xQ.y, xQ.z};
@@ -1348,7 +1309,8 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         float c[24];
 #pragma unroll
         for (int i = 0; i < 24; i++) c[i] = 0.f;
-        const int px = (tile % p.gx) * TILE + (tid & 15), py = ((tile / p.gx) % p.gy) * TILE + (tid >> 4);
+        const TileCoords tc = tile_coords(tile, p.gx, p.gy);
+        const int px = tc.tx * TILE + (tid & 15), py = tc.ty * TILE + (tid >> 4);  // (pixel t of the tile, row-major: L.dray's order)
         if (px < p.W && py < p.H) {
             const float* im = p.inv_mv + 16 * b; const float* ip = p.inv_proj + 16 * b;
             const float ndc[4] = {pix2ndc(px + 0.5f, p.W), pix2ndc(py + 0.5f, p.H), -1.0f, 1.0f};
@@ -1374,7 +1336,7 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
         }
         c[9] += camT.x; c[10] += camT.y; c[11] += camT.z;
 #pragma unroll
-        for (int i = 0; i < 24; i++)
+        for (int i = 0; i < 24; i++)  // (not wave_total: the helper moves the camera variant's instructions)
 #pragma unroll
             for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
         if (lane == 0) {
@@ -1453,7 +1415,7 @@ static TriParams make_params(const dmr_scene& s, int gx, int gy, int r0, int r1,
     p.tile_hits = img.tile_hits; p.tile_bound = img.tile_bound; p.hit_offset = img.hit_offset; p.tile_used = img.tile_used; p.tile_order = img.tile_order;
     p.mask_offset = img.mask_offset;
     p.list_capacity = 0xffffffffu;
-    p.size = ListSize{nullptr, nullptr, 0u, nullptr, 0u};
+    p.size = ListSize{nullptr, NOWHERE, 0u};
     return p;
 }
 
