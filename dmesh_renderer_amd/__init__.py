@@ -35,7 +35,7 @@ try:
 except ImportError as _e:  # not built yet, or its HIP library is missing / of another ABI version
     _C = _NotBuilt(_e)
 
-__all__ = ["TriRenderSettings", "render_tri", "TriRenderer", "TetRenderSettings", "render_tet", "TetRenderer"]
+__all__ = ["TriRenderSettings", "render_tri", "TriRenderer", "TetRenderSettings", "render_tet", "TetRenderer", "Fragments"]
 
 
 class TriRenderSettings(NamedTuple):
@@ -81,6 +81,20 @@ def _alpha_kw(alpha) -> dict:
     return {"alpha": True} if alpha else {}
 
 
+class Fragments(NamedTuple):
+    """Per-pixel fragment lists of the tri renderer (return_fragments=K; helpers in dmesh_renderer_amd.fragments): the faces each
+    pixel blended, front to back, and where its ray hit them.  Constants of every gradient, like coverage and list order."""
+    pix_to_face: th.Tensor  # int32 [B,K,H,W]: face ids in blend order, -1 in unused slots
+    bary: th.Tensor         # float32 [B,K,2,H,W]: clamped (u, v); the weights of the face's vertices are (1 - u - v, u, v)
+    count: th.Tensor        # int32 [B,H,W]: blended faces of the pixel; above K the list is truncated to its first K
+
+
+def _split_fragments(out, alpha):
+    """(color, depth, face, bary, count) of _TriFn called with fragments -> (color, depth[, alpha], Fragments)."""
+    head = _split_alpha(out[:2]) if alpha else tuple(out[:2])
+    return (*head, Fragments(*out[2:5]))
+
+
 def _split_alpha(out):
     """(color, depth | alpha [B,2,H,W], ...) of a Function called with alpha -> (color, depth, ..., alpha [B,1,H,W]).  Slices
     of one tensor: autograd assembles the two-channel upstream gradient (zeros for a channel the loss does not use)."""
@@ -92,20 +106,21 @@ def _impl(shard):
     return _C if shard is None else shard.impl
 
 
-def _forward(render, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows, alpha=False, topo=()):
+def _forward(render, settings, geom, mv_mats, proj_mats, verts_depth, faces_intense, rows, alpha=False, topo=(), **more):
     """One render_tris / render_tets (with topo) call -> (its three results: num_rendered, color, depth / color, depth,
-    active; what its backward needs after geom: the matrices, their inverses, verts_depth, faces_intense, topo and the four
-    scratch buffers).  alpha: depth is [B,2,H,W], depth | alpha."""
+    active -- followed by what `more`, further keywords of the call, adds behind the scratch buffers; what its backward needs
+    after geom: the matrices, their inverses, verts_depth, faces_intense, topo and the four scratch buffers).  alpha: depth is
+    [B,2,H,W], depth | alpha."""
     cams = _with_inverses(mv_mats, proj_mats)
     try:  # (settings[3:]: the tet settings' ray_random_seed)
         out = render(settings.bg, *geom, *cams, verts_depth, faces_intense, *topo, settings.image_height, settings.image_width,
-                     *settings[3:], rows=rows, **_alpha_kw(alpha))
+                     *settings[3:], rows=rows, **_alpha_kw(alpha), **more)
     except Exception as ex:
         print("\nAn error occured in forward.")
         if not topo:  # (as the reference: its tri wrapper prints the exception, its tet wrapper does not)
             print(ex)
         raise
-    return out[:3], (*cams, verts_depth, faces_intense, *topo, *out[3:7])
+    return (*out[:3], *out[7:]), (*cams, verts_depth, faces_intense, *topo, *out[3:7])
 
 
 def _one_backward(render_backward, settings, geom, saved, upstream, rows, kw):
@@ -204,28 +219,32 @@ def _backward(ctx, gs: _GradSet, *upstream) -> tuple:
 
 class _TriFn(th.autograd.Function):
     """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense, settings, rows, shard,
-    exact_grads, camera_grads, alpha (the last four only when set: see _trailing).  Gradients flow to verts, verts_color,
+    exact_grads, camera_grads, alpha, fragments (the last five only when set: see _trailing).  Gradients flow to verts, verts_color,
     faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  alpha: the
     second output is [B,2,H,W], depth | alpha (the caller slices it: _split_alpha), and so is its gradient.  shard: None
     on one device; from a sharded Module (sharding._Shard) its kernels, the band images to assemble and the gradients'
-    all-reduce."""
+    all-reduce.  fragments = K > 0 (one device only): three more outputs, the non-differentiable face [B,K,H,W], bary
+    [B,K,2,H,W] and count [B,H,W] of render_tris(fragments=K)."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False):
+                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False, fragments=0):
         geom = (verts, faces, verts_color, faces_opacity)
-        (num_rendered, color, depth), saved = _forward(_impl(shard).render_tris, settings, geom, mv_mats, proj_mats, verts_depth,
-                                                       faces_intense, rows, alpha)
+        if fragments and shard is not None:
+            raise ValueError("return_fragments is not available on the sharded Modules")
+        (num_rendered, color, depth, *frag), saved = _forward(_impl(shard).render_tris, settings, geom, mv_mats, proj_mats, verts_depth,
+                                                              faces_intense, rows, alpha, **({"fragments": fragments} if fragments else {}))
         if shard is not None:
             color, depth = shard.gather((color, depth))
         ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
         ctx.more_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved)
-        return color, depth
+        ctx.mark_non_differentiable(*frag)
+        return (color, depth, *frag)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth):
-        return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered) + (None,) * 6
+    def backward(ctx, grad_color, grad_depth, *_grad_fragments):
+        return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered) + (None,) * 7
 
 
 class _TetFn(th.autograd.Function):
@@ -254,11 +273,15 @@ class _TetFn(th.autograd.Function):
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-               render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False, return_alpha=False):
+               render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False, return_alpha=False,
+               return_fragments=0):
     """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices.  exact_grads,
-    camera_grads, return_alpha: see TriRenderer."""
+    camera_grads, return_alpha, return_fragments: see TriRenderer."""
     out = _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                       render_settings, tuple(rows), *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha)))
+                       render_settings, tuple(rows),
+                       *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha), int(return_fragments)))
+    if return_fragments:
+        return _split_fragments(out, return_alpha)
     return _split_alpha(out) if return_alpha else out
 
 
@@ -295,29 +318,40 @@ class TriRenderer(th.nn.Module):
     (d alpha / d opacity_i = T / (1 - opacity_i) for every blended face) and combines with the options above: a mask
     loss, or a per-pixel background composited in torch -- render with bg = 0, then color + (1 - alpha) * bg_image.
 
+    return_fragments=K, 1 <= K <= 32 (beyond the reference): the last output is a Fragments tuple (pix_to_face int32
+    [B,K,H,W], bary float32 [B,K,2,H,W], count int32 [B,H,W]): per pixel the first K faces it blended, front to back, the
+    clamped barycentrics its ray hit them at, and how many it blended in all (count > K: the list is truncated).  What a
+    general rasteriser hands to a shader: dmesh_renderer_amd.fragments rebuilds blend weights, interpolates any per-vertex
+    attribute, composites and sums per-face visibility from them in plain, differentiable torch.  The three tensors are
+    constants (no gradient flows into them); the images and the backward are those of a call without the option.  One
+    device only: the sharded Modules do not take it.
+
     forward(verts [P,3], faces [F,3], verts_color [P,3], faces_opacity [F],
             mv_mats [B,4,4], proj_mats [B,4,4], verts_depth [B,P], faces_intense [B,F])
-        -> color [B,3,H,W], depth [B,1,H,W] (, alpha [B,1,H,W] with return_alpha)
+        -> color [B,3,H,W], depth [B,1,H,W] (, alpha [B,1,H,W] with return_alpha) (, Fragments with return_fragments)
     """
 
     def __init__(self, render_settings: TriRenderSettings, exact_grads: bool = False, camera_grads: bool = False,
-                 return_alpha: bool = False):
+                 return_alpha: bool = False, return_fragments: int = 0):
         super().__init__()
         self.render_settings = render_settings
         self.exact_grads = bool(exact_grads)
         self.camera_grads = bool(camera_grads)
         self.return_alpha = bool(return_alpha)
+        self.return_fragments = int(return_fragments)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
         out = self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
                            mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense)
+        if self.return_fragments:
+            return _split_fragments(out, self.return_alpha)
         return _split_alpha(out) if self.return_alpha else out
 
     def _render(self, *inputs):
         """_TriFn on the normalised inputs (faces int32, the matrices transposed); ShardedTriRenderer adds a partition."""
         rows, shard = self._shard()
         return _TriFn.apply(*inputs, self.render_settings, rows,
-                            *_trailing(shard, self.exact_grads, self.camera_grads, self.return_alpha))
+                            *_trailing(shard, self.exact_grads, self.camera_grads, self.return_alpha, self.return_fragments))
 
     def _shard(self):
         """(rows, shard) of the Functions: all rows on one device (the sharded Modules return their band)."""

@@ -600,15 +600,31 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
     if (check_scene(s, false, d)) return 1;
     if (!alloc || !num_rendered || !out_color || !out_depth) return fail("null argument");
     *num_rendered = 0;
+    // DMR_FLAG_TRI_FRAGMENTS: K fragment slots per pixel, K in bits 8-15 of the flags
+    const int frag_k = (s->flags & DMR_FLAG_TRI_FRAGMENTS) ? DMR_FRAGMENTS_K(s->flags) : 0;
+    if ((s->flags & DMR_FLAG_TRI_FRAGMENTS) && (frag_k < 1 || frag_k > 32))
+        return fail("DMR_FLAG_TRI_FRAGMENTS: K (bits 8-15 of flags, DMR_FRAGMENTS_FLAGS(K)) must be in 1..32, got " + std::to_string(frag_k));
     if (s->P == 0 || s->F == 0) return 0;  // render.cu:105 (and Q16: F == 0)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* fragments = nullptr;  // the caller's [face | bary | count], requested once
+    if (caller_output(alloc, ctx, DMR_BUF_TRI_FRAGMENTS, frag_k ? 4 * d.npix * (3 * (size_t)frag_k + 1) : 0, "tri fragment", false, st, &fragments))
+        return 1;
+    Scratch last{};  // the scratch of the call's final k_tri_forward: a redo (a refuted size estimate) renders a second time
     auto render = [&](const Scratch& c, dmr::ListSize size) {
         const dmr_scene sc = canonical(s, c.is.mats);
         dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, c.is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys,
                                 c.bs.face_list, c.bs.capacity, tri_image(c), out_color,
                                 out_depth, st, (s->flags & DMR_FLAG_ALPHA) != 0, size);
+        last = c;
     };
-    return run_forward(s, false, d, alloc, ctx, st, num_rendered, render);
+    if (run_forward(s, false, d, alloc, ctx, st, num_rendered, render)) return 1;
+    // the fragments describe the colour the call returns: one launch, behind whichever k_tri_forward was the last
+    if (fragments && last.is.n_contrib) {
+        dmr::launch_tri_fragments(canonical(s, last.is.mats), d.gx, d.gy, d.r0, d.r1, last.is.tile_offset, last.bs.face_list, tri_image(last),
+                                  frag_k, fragments, st);
+        DMR_HIP(hipGetLastError());
+    }
+    return 0;
 }
 
 int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL_ddepth, int num_rendered,

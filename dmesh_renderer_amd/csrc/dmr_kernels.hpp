@@ -162,6 +162,12 @@ void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, cons
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
                         float* out_color, float* out_depth, hipStream_t st, bool alpha = false,
                         ListSize size = ListSize{nullptr, NOWHERE, 0u});
+// DMR_FLAG_TRI_FRAGMENTS, behind the call's final launch_tri_forward (whose state it reads: sorted lists, coverage masks,
+// n_contrib): per pixel of the band the first K blended (pixel, face) pairs in blend order and their number, into the
+// caller's buffer [face i32 B,K,H,W | bary (u_c, v_c) f32 B,K,2,H,W | count i32 B,H,W] (unused slots -1 / 0).  K in 1..32.
+// No stage of its own, no size, no host wait.
+void launch_tri_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, const uint32_t* tile_offset, const uint32_t* face_list,
+                          TriImageState img, int K, void* fragments, hipStream_t st);
 // hit_offset: every tile's region of the record buffer, sized by the bound h + (HIT_GROUP - 1) * min(list length, h) of
 // its h blended pairs (tile_hits); tile_used is cleared (the per-pixel kernel fills it).  out: where the total goes (size port)
 void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,

@@ -25,6 +25,8 @@
 //                            implies exact_grads) -> the five gradients, then those two
 //                            render_tets_backward: also dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats
 //                            [B,4,4] (DMR_FLAG_TET_CAMERA_GRADS, implies full_grads) -> the four full gradients, then those
+//   fragments=0              render_tris: K > 0 (at most 32): per-pixel fragment lists (DMR_FLAG_TRI_FRAGMENTS) -> the tuple gains
+//                            face i32 [B,K,H,W], bary f32 [B,K,2,H,W], count i32 [B,H,W] behind the four scratch tensors
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -195,7 +197,7 @@ at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at:
 // the gradient outputs the library asks for (GradTable::from): tensors the backward has put here for the library to fill.
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, DMR_BUF_TET_CAMERA_GRADS + 1> buf;
+    std::array<at::Tensor, DMR_BUF_TRI_FRAGMENTS + 1> buf;
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -204,7 +206,7 @@ struct Scratch {
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
     if (which < 0 || which >= (int)s->buf.size()) return nullptr;
-    if (which > DMR_BUF_WORK) {  // the caller's gradient tensor, which the library fills
+    if (which > DMR_BUF_WORK) {  // the caller's output tensor (gradients, fragments: 4-byte elements), which the library fills
         const at::Tensor& t = s->buf[which];
         return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
     }
@@ -287,18 +289,41 @@ struct Forward {
     }
 };
 
-// -> (num_rendered:int, color, depth, pointBuffer, faceBuffer, binningBuffer, imgBuffer)
-using TriFwdOut = std::tuple<int64_t, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+// The fragment lists of render_tris(fragments=K): ONE buffer [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W] -- what the
+// library requests as DMR_BUF_TRI_FRAGMENTS -- and its three pieces as views.  Pre-initialised (face -1, the rest 0) for the
+// images' reason: a row band, or P == 0 / F == 0, where nothing writes them (Forward::written).
+struct Fragments {
+    at::Tensor face, bary, count;
+    Fragments(Forward& f, int64_t K, int64_t H, int64_t W) {
+        const int64_t B = f.call.sc.B, n = B * H * W;
+        const at::Tensor buf = at::empty({n * (3 * K + 1)}, at::TensorOptions().dtype(at::kInt).device(f.dev));
+        face = buf.narrow(0, 0, K * n).view({B, K, H, W});
+        bary = buf.narrow(0, K * n, 2 * K * n).view(at::kFloat).view({B, K, 2, H, W});
+        count = buf.narrow(0, 3 * K * n, n).view({B, H, W});
+        if (!f.written) { face.fill_(-1); buf.narrow(0, K * n, (2 * K + 1) * n).zero_(); }
+        f.call.scratch.buf[DMR_BUF_TRI_FRAGMENTS] = buf;
+        f.call.sc.flags |= DMR_FRAGMENTS_FLAGS((int)K);
+    }
+};
+
+// -> (num_rendered:int, color, depth, pointBuffer, faceBuffer, binningBuffer, imgBuffer, face, bary, count): the last three
+// undefined tensors unless fragments=K > 0.  (Bound below with the GIL released and its tuple cut to the reference's seven
+// when there are no fragments.)
+using TriFwdOut = std::tuple<int64_t, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
 TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                       In inv_proj_mats, In verts_depth, In faces_intense, int64_t image_height, int64_t image_width, std::pair<int, int> rows,
-                      bool fill_outside, bool alpha) {
+                      bool fill_outside, bool alpha, int64_t fragments) {
     const Inputs in{background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense};
     check_common(in, false);
+    if (fragments < 0 || fragments > 32) err("fragments must be in 0..32 (fragment slots per pixel; 0: no fragment output), got " + std::to_string(fragments));
     Forward f(in, image_height, image_width, 0, rows, fill_outside, alpha);
+    std::optional<Fragments> frag;
+    if (fragments > 0) frag.emplace(f, fragments, image_height, image_width);
     int rendered = 0;
     // (the bindings release the GIL around this whole function: the default call waits for the size read-back)
     if (g_abi.tri_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), &alloc_cb, &f.call.scratch, f.call.stream(), &rendered)) raise_lib();
-    return f.result((int64_t)rendered, f.color, f.depth);
+    return std::tuple_cat(f.result((int64_t)rendered, f.color, f.depth),
+                          frag ? std::make_tuple(frag->face, frag->bary, frag->count) : std::make_tuple(at::Tensor(), at::Tensor(), at::Tensor()));
 }
 
 // -> (color, depth, active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
@@ -522,8 +547,18 @@ PYBIND11_MODULE(_C, m) {
               py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"), py::arg("verts_depth"),
               py::arg("faces_intense"), more...);
     };
-    def("render_tris", &render_tris, py::arg("image_height"), py::arg("image_width"), rows, py::arg("fill_outside") = true, py::kw_only(), alpha,
-        py::call_guard<py::gil_scoped_release>());
+    def("render_tris",
+        [](In bg, In verts, In faces, In vcolor, In fopacity, In mv, In proj, In inv_mv, In inv_proj, In vdepth, In fintense, int64_t H, int64_t W,
+           std::pair<int, int> band, bool fill_outside, bool with_alpha, int64_t fragments) {
+            TriFwdOut out;
+            {
+                py::gil_scoped_release nogil;
+                out = render_tris(bg, verts, faces, vcolor, fopacity, mv, proj, inv_mv, inv_proj, vdepth, fintense, H, W, band, fill_outside, with_alpha, fragments);
+            }
+            const py::tuple all = py::cast(out);  // the one place the tuple's length is decided
+            return fragments > 0 ? all : py::tuple(all[py::slice(0, 7, 1)]);
+        },
+        py::arg("image_height"), py::arg("image_width"), rows, py::arg("fill_outside") = true, py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tris_backward", &render_tris_backward, py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"), py::arg("pointBuffer"),
         py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out, py::kw_only(), py::arg("exact_grads") = false,
         camera_grads, alpha);

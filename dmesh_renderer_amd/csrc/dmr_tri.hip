@@ -380,6 +380,8 @@ k_tri_forward(TriParams p, float* __restrict__ out_color, float* __restrict__ ou
 
             const V3 E1 = {r.E1[0], r.E1[1], r.E1[2]}, E2 = {r.E2[0], r.E2[1], r.E2[2]};
             const V3 Tv = {r.T[0], r.T[1], r.T[2]}, Q = {r.Q[0], r.Q[1], r.Q[2]};
+            // (from here to clamp_bary_uv: restated by forward_uv() below for k_tri_fragments, whose barycentrics and skip decision
+            // are these bit for bit -- a change here is a change there; k_tri_backward_pix has the same lines with fast::rcp)
             const V3 Pv = cross(rd, E2);
             const float denom = dot(Pv, E1);
             if (denom == 0.0f) { n_skipped++; continue; }  // "edge case": counted, not blended (forward.cu:429-430)
@@ -839,6 +841,128 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
     }
     DMR_STAMP_RT(p, 1, 1);
     if (tid == 0) p.tile_used[tile] = hit_cursor - region0;  // what the hit-parallel kernel walks (a multiple of HIT_GROUP)
+}
+
+// ---------------------------------------------------------------------------
+// k_tri_fragments (DMR_FLAG_TRI_FRAGMENTS) -- per pixel, WHICH faces the forward blended and WHERE the ray hit them.
+//
+// A launch of its own behind the final k_tri_forward, reading what that kernel left: the tile's sorted list, the per-chunk
+// coverage masks (chunk_masks) and n_contrib.  Same tile order, pixel-to-lane mapping and row band as the other tri kernels.
+// Per chunk of MASK_CHUNK list entries, walked from the FRONT: the pixel's 128-bit mask is cut at its n_contrib (as
+// k_tri_backward_pix cuts it), threads < MASK_CHUNK stage the geometry half of the chunk's shading records
+// (stage_shade_geom: T, E1, E2, Q) and the face ids in LDS, and every lane visits its set bits in list order, a wave's trip
+// count being the longest walk of its lanes.  Per bit the Moeller-Trumbore (u, v) and the clamp are the forward's phase B
+// arithmetic, operation for operation (exact division, -ffp-contract=off: the same bits), so `denom == 0` decides here what it
+// decided there: such a pair was skipped by the forward and is no fragment.  Fragment k < K of the pixel goes straight to
+// face[b,k,y,x], bary[b,k,0:2,y,x] as it is found (no per-lane array: it would be indexed dynamically and live in scratch);
+// fragments beyond K are counted only.  Every pixel of the rendered rows is fully written: unused slots face = -1, bary = 0.
+// A tile that blended nothing (empty, or clamped by the forward while a size guess is refuted / an asynchronous call
+// overflowed: its n_contrib are 0) touches neither the list nor the masks.
+// It is not part of k_tri_forward because that kernel sits at its register cap (FWD_WAVES above): K stores per pixel and the
+// slot counter inside its walk were what two earlier attempts at per-face outputs spilled on.  No stage, no size, no host wait.
+// ---------------------------------------------------------------------------
+constexpr int FRAG_MAX_K = 32;
+// The (u_c, v_c) k_tri_forward's phase B blends a covered (pixel, face) pair with; false: the pair it skips (denom == 0,
+// forward.cu:429-430).  k_tri_forward has these operations inline in its walk (marked there) and is not edited for this -- it
+// sits at its register cap --, so this is their one restatement: the same operations in the same order, exact division,
+// no contraction (-ffp-contract=off), hence the same bits.
+__device__ __forceinline__ bool forward_uv(const ShadeRec& r, V3 rd, float& iuc, float& ivc) {
+    const V3 E1 = {r.E1[0], r.E1[1], r.E1[2]}, E2 = {r.E2[0], r.E2[1], r.E2[2]};
+    const V3 Tv = {r.T[0], r.T[1], r.T[2]}, Q = {r.Q[0], r.Q[1], r.Q[2]};
+    const V3 Pv = cross(rd, E2);
+    const float denom = dot(Pv, E1);
+    if (denom == 0.0f) return false;
+    const float inv_denom = 1.0f / denom;
+    const float iu = dot(Pv, Tv) * inv_denom;
+    const float iv = dot(Q, rd) * inv_denom;
+    int code;
+    clamp_bary_uv(iu, iv, iuc, ivc, code);
+    return true;
+}
+__global__ void __launch_bounds__(256)
+k_tri_fragments(TriParams p, int K, int32_t* __restrict__ out_face, float* __restrict__ out_bary, int32_t* __restrict__ out_count) {
+    constexpr int WORDS = MASK_CHUNK / 32;
+    static_assert(MASK_CHUNK == 128, "threads < MASK_CHUNK stage one record each");
+    __shared__ ShadeRec s_shade[MASK_CHUNK];  // (the geometry half is all that is staged and read)
+    __shared__ int s_face[MASK_CHUNK];
+    __shared__ uint32_t s_max_last;
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tile = (int)p.tile_order[blockIdx.x];
+    const auto [tx, ty, b] = tile_coords(tile, p.gx, p.gy);
+    if (ty < p.r0 || ty >= p.r1) return;  // uniform
+    const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
+    const int px = tx * TILE + lx, py = ty * TILE + ly;
+    const bool inside = px < p.W && py < p.H;
+    const int64_t HW = (int64_t)p.H * p.W;
+    const int64_t pix_id = (int64_t)p.W * py + px;
+    const int64_t bpix = (int64_t)b * HW + pix_id;
+    const int pl = ly * TILE + lx;
+    const uint32_t last_contributor = inside ? p.n_contrib[bpix] : 0u;
+
+    if (tid == 0) s_max_last = 0u;
+    __syncthreads();
+    if (last_contributor) atomicMax(&s_max_last, last_contributor);
+    __syncthreads();
+    const uint32_t total = s_max_last;  // list positions >= total contribute to no pixel of the tile
+
+    int cnt = 0;  // blended pairs of this pixel so far = the next fragment slot
+    if (total != 0u) {  // uniform
+        const uint32_t begin = p.tile_offset[tile];
+        V3 ro = {0, 0, 0}, rd = {0, 0, 0};
+        if (inside) pixel_ray<false>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd);
+        const V3 view_o = {p.inv_mv[16 * b + 12], p.inv_mv[16 * b + 13], p.inv_mv[16 * b + 14]};
+        const ChunkMasks masks = chunk_masks(p, blockIdx.x, begin);
+        const int64_t face0 = (int64_t)b * K * HW + pix_id, bary0 = (int64_t)b * K * 2 * HW + pix_id;
+        const uint32_t nchunks = (total + MASK_CHUNK - 1) / MASK_CHUNK;
+        for (uint32_t c = 0; c < nchunks; c++) {
+            const uint32_t lo = c * MASK_CHUNK, hi = min(total, lo + (uint32_t)MASK_CHUNK);  // chunk = list positions [lo, hi)
+            const uint4 mm = masks.at(c)[pl];  // requested before the barrier, in flight across it
+            __syncthreads();  // the previous chunk is done with the LDS records
+            if (tid < MASK_CHUNK && lo + (uint32_t)tid < hi) {
+                FaceIds f;
+                f.face = (int)p.face_list[begin + lo + tid];
+                f.v0 = p.faces[3 * f.face]; f.v1 = p.faces[3 * f.face + 1]; f.v2 = p.faces[3 * f.face + 2];
+                f.opacity = 0.f; f.intense = 0.f;  // (not read by the geometry half)
+                stage_shade_geom(p, f, view_o, s_shade[tid]);
+                s_face[tid] = f.face;
+            }
+            uint32_t m[WORDS] = {mm.x, mm.y, mm.z, mm.w};
+            {   // list positions below the pixel's n_contrib (k_tri_backward_pix's cut)
+                const int lim = last_contributor > lo ? (int)min(last_contributor - lo, (uint32_t)MASK_CHUNK) : 0;
+#pragma unroll
+                for (int w = 0; w < WORDS; w++) {
+                    const int keep = lim - 32 * w;  // bits of word w below the bound
+                    m[w] = keep >= 32 ? m[w] : (keep <= 0 ? 0u : (m[w] & ((1u << keep) - 1u)));
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < WORDS; w++) {
+                uint32_t mw = m[w];
+                while (mw) {
+                    const int k = 32 * w + __ffs(mw) - 1;
+                    mw &= mw - 1u;
+                    float iuc, ivc;
+                    if (!forward_uv(s_shade[k], rd, iuc, ivc)) continue;  // skipped by the forward: not a fragment
+                    if (cnt < K) {
+                        out_face[face0 + (int64_t)cnt * HW] = s_face[k];
+                        out_bary[bary0 + (int64_t)(2 * cnt) * HW] = iuc;
+                        out_bary[bary0 + (int64_t)(2 * cnt + 1) * HW] = ivc;
+                    }
+                    cnt++;
+                }
+            }
+        }
+    }
+    if (inside) {
+        out_count[bpix] = cnt;
+        for (int k = cnt; k < K; k++) {
+            out_face[((int64_t)b * K + k) * HW + pix_id] = -1;
+            out_bary[((int64_t)b * K + k) * 2 * HW + pix_id] = 0.f;
+            out_bary[(((int64_t)b * K + k) * 2 + 1) * HW + pix_id] = 0.f;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1434,6 +1558,17 @@ void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, cons
         else k_tri_forward<false, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
     } else if (keys) k_tri_forward<true><<<grid, block, 0, st>>>(p, out_color, out_depth);
     else k_tri_forward<false><<<grid, block, 0, st>>>(p, out_color, out_depth);
+}
+
+void launch_tri_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, const uint32_t* tile_offset, const uint32_t* face_list,
+                          TriImageState img, int K, void* fragments, hipStream_t st) {
+    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
+    const TriParams p = make_params(s, gx, gy, r0, r1, nullptr, tile_offset, face_list, img);
+    const size_t npix = (size_t)s.B * s.H * s.W;  // [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W]
+    int32_t* face = static_cast<int32_t*>(fragments);
+    float* bary = reinterpret_cast<float*>(face + (size_t)K * npix);
+    int32_t* count = face + 3 * (size_t)K * npix;
+    k_tri_fragments<<<dim3((unsigned)(s.B * gx * gy)), dim3(256), 0, st>>>(p, K, face, bary, count);
 }
 
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,

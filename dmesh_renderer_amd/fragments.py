@@ -1,0 +1,86 @@
+"""Shading from the tri renderer's per-pixel fragment lists (TriRenderer(return_fragments=K) / render_tri(...,
+return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,K,2,H,W], count [B,H,W])).
+
+Plain torch, differentiable, no kernels.  What is HELD CONSTANT by every function here -- it comes from the rasteriser as
+data, not as a function of the scene -- is
+  * which faces a pixel blends (coverage, and where its walk stopped),
+  * their order (the tile's depth sort),
+  * the barycentrics (the clamped (u, v) of the pixel's ray on each face),
+exactly the constants of the renderer's own default gradients.  Gradients flow into what the caller passes: opacities,
+per-vertex attributes, per-face scales.  A pixel with count > K holds the first K of its faces only: what is computed for it
+is the truncated sum.
+
+The renderer's own colour, for pixels with count <= K:
+    color, T = composite(frag, faces, faces_opacity, verts_color, face_scale=faces_intense);  color + T * bg.view(1, 3, 1, 1)
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch as th
+
+__all__ = ["blend_weights", "interpolate", "composite", "face_visibility"]
+
+
+def _opacity_slots(frag, faces_opacity: th.Tensor) -> Tuple[th.Tensor, th.Tensor]:
+    """(used [B,K,H,W] bool, opacity of every slot's face with 0 in the empty ones)."""
+    face = frag.pix_to_face
+    used = face >= 0
+    o = faces_opacity[face.clamp(min=0).long()]
+    return used, th.where(used, o, th.zeros((), dtype=o.dtype, device=o.device))
+
+
+def _transmittance(o: th.Tensor) -> th.Tensor:
+    """[B,K+1,H,W]: prod_{j<k} (1 - o_j) for k = 0..K (the exclusive cumulative product over the slots, and the total)."""
+    ones = th.ones_like(o[:, :1])
+    return th.cat([ones, th.cumprod(1 - o, dim=1)], dim=1)
+
+
+def blend_weights(frag, faces_opacity: th.Tensor) -> th.Tensor:
+    """w_k = o_k * prod_{j<k} (1 - o_j) of every slot, [B,K,H,W]; 0 in empty slots.  frag: Fragments; faces_opacity [F].
+    Constants: the faces and their order.  Differentiable in faces_opacity."""
+    _, o = _opacity_slots(frag, faces_opacity)
+    return o * _transmittance(o)[:, :-1]
+
+
+def interpolate(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
+    """Per-vertex attributes vert_attrs [P,C] at every fragment, [B,K,C,H,W]: (1 - u - v) a_0 + u a_1 + v a_2 over the three
+    vertices of the slot's face (faces [F,3]), with the rasteriser's clamped (u, v); 0 in empty slots.
+    Constants: the faces and the barycentrics.  Differentiable in vert_attrs."""
+    face = frag.pix_to_face
+    used = face >= 0
+    vid = faces.long()[face.clamp(min=0).long()]             # [B,K,H,W,3]
+    a = vert_attrs[vid]                                      # [B,K,H,W,3,C]
+    u, v = frag.bary[:, :, 0].to(a.dtype), frag.bary[:, :, 1].to(a.dtype)
+    w = th.stack([1 - u - v, u, v], dim=-1)                  # [B,K,H,W,3]
+    out = (w.unsqueeze(-1) * a).sum(-2)                      # [B,K,H,W,C]
+    out = out * used.unsqueeze(-1).to(a.dtype)
+    return out.permute(0, 1, 4, 2, 3)
+
+
+def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.Tensor,
+              face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """Front-to-back blend of interpolated attributes: (sum_k w_k s_k a_k [B,C,H,W], T = prod_k (1 - o_k) [B,1,H,W]), a_k =
+    interpolate(...), w_k = blend_weights(...), s_k = face_scale[b, face_k] (face_scale [B,F], e.g. faces_intense; None: 1).
+    T is what is left for a background: result + T * bg.  Constants: the faces, their order, the barycentrics.
+    Differentiable in faces_opacity, vert_attrs and face_scale."""
+    _, o = _opacity_slots(frag, faces_opacity)
+    t = _transmittance(o)
+    w = o * t[:, :-1]
+    a = interpolate(frag, faces, vert_attrs)                 # [B,K,C,H,W]
+    if face_scale is not None:
+        idx = frag.pix_to_face.clamp(min=0).long()
+        B = idx.shape[0]
+        s = th.gather(face_scale, 1, idx.reshape(B, -1)).reshape(idx.shape)
+        w = w * s.to(w.dtype)
+    return (w.unsqueeze(2).to(a.dtype) * a).sum(1), t[:, -1:]
+
+
+def face_visibility(frag, faces_opacity: th.Tensor, F: int) -> th.Tensor:
+    """Sum of the blend weights every face received over a view's pixels, [B,F] (one scatter_add): 0 for a face no pixel
+    blended -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.  Constants: the faces and their order.
+    Differentiable in faces_opacity."""
+    w = blend_weights(frag, faces_opacity)
+    B = w.shape[0]
+    idx = frag.pix_to_face.clamp(min=0).long().reshape(B, -1)  # (empty slots add their weight 0 to face 0)
+    return th.zeros(B, F, dtype=w.dtype, device=w.device).scatter_add(1, idx, w.reshape(B, -1))

@@ -371,7 +371,8 @@ class ShardedTriRenderer(_Banded, TriRenderer):
 
     Same call signature as TriRenderer, and the same exact_grads / camera_grads / return_alpha options (with camera_grads
     the flat all-reduce payload gains [B][dL/dinv_mv 16 | dL/dinv_proj 16]; return_alpha adds no gradient tensor: alpha
-    travels as a second channel of the depth image).  Every rank must pass identical inputs; every rank
+    travels as a second channel of the depth image).  TriRenderer's return_fragments is NOT available here: the per-pixel
+    fragment lists are a single-device output so far (a rank would hold its band's only).  Every rank must pass identical inputs; every rank
     gets the full summed gradients.  The bands may be refreshed at any time with `set_row_work` (e.g. every few
     iterations from `row_work_from_ranges` / `view_row_work_from_ranges`)."""
 

@@ -42,7 +42,8 @@ extern "C" {
 enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE = 3, DMR_BUF_WORK = 4,
        DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */,
        DMR_BUF_TRI_CAMERA_GRADS = 6 /* dmr_tri_backward with DMR_FLAG_TRI_CAMERA_GRADS: an OUTPUT, see there */,
-       DMR_BUF_TET_CAMERA_GRADS = 7 /* dmr_tet_backward with DMR_FLAG_TET_CAMERA_GRADS: an OUTPUT, see there */ };
+       DMR_BUF_TET_CAMERA_GRADS = 7 /* dmr_tet_backward with DMR_FLAG_TET_CAMERA_GRADS: an OUTPUT, see there */,
+       DMR_BUF_TRI_FRAGMENTS = 8 /* dmr_tri_forward with DMR_FLAG_TRI_FRAGMENTS: an OUTPUT, see the flag */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -56,7 +57,8 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record (+ 128 Nt with DMR_FLAG_TRI_CAMERA_GRADS); tri camera grads
  * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS or
  * DMR_FLAG_TET_CAMERA_GRADS only) 4 (3P + BF), exactly; work (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 per tile of
- * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly. */
+ * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly; tri fragments (tri
+ * forward with DMR_FLAG_TRI_FRAGMENTS only) 4 BWH (3K + 1), exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -134,6 +136,27 @@ typedef struct dmr_scene {
  * (DMR_FLAG_ASYNC and stream capture work as before); colour and depth are bit for bit those of a call without the flag.
  * Forward and backward of a step must agree on the flag only in the shapes they pass: the scratch buffers are the same. */
 #define DMR_FLAG_ALPHA 32
+/* dmr_tri_forward only (ignored by every other call): per-pixel fragment lists, what a general rasteriser returns for
+ * shading outside it.  K, the slots per pixel, travels in bits 8-15 of the flags: flags |= DMR_FRAGMENTS_FLAGS(K), K in
+ * 1..32 (the flag with K = 0 or K > 32 is an error).  The call then requests buffer DMR_BUF_TRI_FRAGMENTS through `alloc`,
+ * once, of exactly 4 BWH (3K + 1) bytes (not at all when P == 0 or F == 0, where nothing is launched), and one more kernel
+ * behind the forward fills, for every pixel of the rendered tile rows,
+ *   face  int32 [B,K,H,W]    the faces the pixel BLENDED, in blend order (front to back), -1 in unused slots;
+ *   bary  fp32  [B,K,2,H,W]  the clamped barycentrics (u_c, v_c) the forward interpolated that face's vertex attributes
+ *                            with -- weights (1 - u_c - v_c, u_c, v_c) for the face's three vertices --, 0 in unused slots;
+ *   count int32 [B,H,W]      the number of blended faces of the pixel; it may exceed K: the pairs beyond K are counted,
+ *                            not stored;
+ * back to back in that order.  A blended pair is a covered (pixel, face) pair below the pixel's last contributor that the
+ * forward did not skip (a degenerate ray-plane intersection is skipped, cuda_rasterizer/forward.cu:429-430): with opacities
+ * o_k the pixel's blend weights are w_k = o_k prod_{j<k} (1 - o_j), its colour sum_k w_k c_k + T bg with T = prod_k (1 - o_k),
+ * when count <= K.  Pixels outside the rendered tile rows are untouched, and nothing is written when P == 0 or F == 0: the
+ * caller initialises the buffer (face -1, the rest 0) where that can happen, as it does for the images.  The values describe
+ * the colour the call returns (after a redo, the redo's).  The images, the four scratch buffers and the backward are exactly
+ * those of a call without the flag; no host wait is added (DMR_FLAG_ASYNC and stream capture work as before).  The tet
+ * renderer has no such output. */
+#define DMR_FLAG_TRI_FRAGMENTS 64
+#define DMR_FRAGMENTS_K(flags) (((flags) >> 8) & 255)
+#define DMR_FRAGMENTS_FLAGS(k) (DMR_FLAG_TRI_FRAGMENTS | (((k) & 255) << 8))
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -144,7 +167,8 @@ uint64_t dmr_redo_count(void);
 
 /* out_color [B,3,H,W], out_depth [B,1,H,W] ([B,2,H,W] with DMR_FLAG_ALPHA: depth | alpha): every pixel of the rendered tile rows is written; the caller
  * zero-initialises them (render.cu:88-89) when a band leaves rows untouched or when P == 0 / F == 0
- * (nothing is launched, render.cu:105).  *num_rendered receives R = sum of tiles touched. */
+ * (nothing is launched, render.cu:105).  *num_rendered receives R = sum of tiles touched.
+ * With DMR_FLAG_TRI_FRAGMENTS also the fragment lists, in a buffer requested through `alloc` (see the flag). */
 int dmr_tri_forward(const dmr_scene* scene, float* out_color, float* out_depth,
                     dmr_alloc_fn alloc, void* alloc_ctx, void* stream, int* num_rendered);
 

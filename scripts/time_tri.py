@@ -8,6 +8,7 @@ ap = argparse.ArgumentParser(); ap.add_argument("--config", default="C4"); ap.ad
 ap.add_argument("--grads", choices=("default", "exact", "camera"), default="default",
                 help="backward variant: the reference's, exact_grads=True, camera_grads=True")
 ap.add_argument("--alpha", action="store_true", help="forward and backward with the alpha output (TriRenderer(return_alpha=True))")
+ap.add_argument("--fragments", type=int, default=0, help="forward with K fragment slots per pixel (TriRenderer(return_fragments=K))")
 a = ap.parse_args()
 dev = th.device("cuda:0")
 cfg = scenes.CONFIGS[a.config]
@@ -20,6 +21,8 @@ akw = {}
 if a.alpha:  # the depth image and its gradient gain a channel
     akw = {"alpha": True}; kw = dict(kw, alpha=True)
     gd = th.cat([gd, th.randn(B, 1, H, W, generator=th.Generator().manual_seed(5)).to(dev)], dim=1)
+if a.fragments:
+    akw = dict(akw, fragments=a.fragments)
 def step():
     o = _C.render_tris(*args, H, W, **akw)
     return o, _C.render_tris_backward(*args, gc, gd, o[0], *o[3:7], **kw)
@@ -30,5 +33,5 @@ th.cuda.synchronize(); dt = (time.perf_counter() - t0) / a.steps
 _C.profile_enable(0)
 ms, cnt = _C.profile_collect()
 st = {_C.stage_name(i): round(ms[i] / cnt[i], 4) for i in range(_C.NUM_STAGES) if cnt[i]}
-print(json.dumps({"config": a.config, "grads": a.grads, "alpha": a.alpha, "faces": int(d["faces"].shape[0]), "image": [H, W],
+print(json.dumps({"config": a.config, "grads": a.grads, "alpha": a.alpha, "fragments": a.fragments, "faces": int(d["faces"].shape[0]), "image": [H, W],
                   "ms_per_step": round(dt * 1e3, 4), "stages_ms": st}))
