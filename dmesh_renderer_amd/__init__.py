@@ -83,7 +83,9 @@ def _alpha_kw(alpha) -> dict:
 
 class Fragments(NamedTuple):
     """Per-pixel fragment lists of the tri renderer (return_fragments=K; helpers in dmesh_renderer_amd.fragments): the faces each
-    pixel blended, front to back, and where its ray hit them.  Constants of every gradient, like coverage and list order."""
+    pixel blended, front to back, and where its ray hit them.  Constants of every gradient, like coverage and list order --
+    unless the renderer was made with fragment_grads=True: `bary` then takes part in autograd (its gradient reaches verts and,
+    with camera_grads, the matrices); pix_to_face and count stay constants."""
     pix_to_face: th.Tensor  # int32 [B,K,H,W]: face ids in blend order, -1 in unused slots
     bary: th.Tensor         # float32 [B,K,2,H,W]: clamped (u, v); the weights of the face's vertices are (1 - u - v, u, v)
     count: th.Tensor        # int32 [B,H,W]: blended faces of the pixel; above K the list is truncated to its first K
@@ -202,12 +204,14 @@ def _input_grads(ctx, gs: _GradSet, level: int, g, inv_mv, inv_proj) -> tuple:
     return gs.pick[level]((*g[:k], *mats, None))
 
 
-def _backward(ctx, gs: _GradSet, *upstream) -> tuple:
+def _backward(ctx, gs: _GradSet, *upstream, extra_saved=0, **more) -> tuple:
     """The backward of _TriFn / _TetFn: one _one_backward at ctx's level, the all-reduce of a sharded Module, the gradients of
-    apply's eight tensors."""
+    apply's eight tensors.  more: further keywords of the call (_TriFn's fragment_grads) whose terms the library adds into
+    pieces of the level's gradient set: nothing new in the tuple.  extra_saved: tensors the Function saved behind _forward's."""
     saved = ctx.saved_tensors
-    geom, saved = saved[:4], saved[4:]
+    geom, saved = saved[:4], saved[4:len(saved) - extra_saved]
     level, kw = _grad_options(ctx, gs)
+    kw.update(more)
     shard, flat = ctx.shard, None
     if shard is not None and shard.flat_out:  # the gradients land back to back in the all-reduce payload
         flat = kw["flat_out"] = _flat(gs, level, geom[0].size(0), geom[1].size(0), saved[0].size(0), geom[0].device)[0]
@@ -219,32 +223,56 @@ def _backward(ctx, gs: _GradSet, *upstream) -> tuple:
 
 class _TriFn(th.autograd.Function):
     """Inputs: verts, faces, verts_color, faces_opacity, mv^T, proj^T, verts_depth, faces_intense, settings, rows, shard,
-    exact_grads, camera_grads, alpha, fragments (the last five only when set: see _trailing).  Gradients flow to verts, verts_color,
+    exact_grads, camera_grads, alpha, fragments, fragment_grads (the last six only when set: see _trailing).  Gradients flow to verts, verts_color,
     faces_opacity, verts_depth, faces_intense; with camera_grads also to mv^T and proj^T (see TriRenderer).  alpha: the
     second output is [B,2,H,W], depth | alpha (the caller slices it: _split_alpha), and so is its gradient.  shard: None
     on one device; from a sharded Module (sharding._Shard) its kernels, the band images to assemble and the gradients'
     all-reduce.  fragments = K > 0 (one device only): three more outputs, the non-differentiable face [B,K,H,W], bary
-    [B,K,2,H,W] and count [B,H,W] of render_tris(fragments=K)."""
+    [B,K,2,H,W] and count [B,H,W] of render_tris(fragments=K).  fragment_grads (needs fragments): bary is differentiable;
+    the gradient that arrives for it goes down with the backward call (fragment_grads=(face, grad_bary)), where the library
+    adds its term to the verts piece and, at level 2, to the camera piece: the gradient set (_TRI_GRADS) is unchanged.  Gradients
+    are then not materialised: a backward without one for bary is today's call."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
-                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False, fragments=0):
+                settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False, fragments=0,
+                fragment_grads=False):
         geom = (verts, faces, verts_color, faces_opacity)
+        if fragment_grads and shard is not None:
+            raise ValueError("fragment_grads is not available on the sharded Modules")
         if fragments and shard is not None:
             raise ValueError("return_fragments is not available on the sharded Modules")
+        if fragment_grads and not fragments:
+            raise ValueError("fragment_grads needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
         (num_rendered, color, depth, *frag), saved = _forward(_impl(shard).render_tris, settings, geom, mv_mats, proj_mats, verts_depth,
                                                               faces_intense, rows, alpha, **({"fragments": fragments} if fragments else {}))
         if shard is not None:
             color, depth = shard.gather((color, depth))
         ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
         ctx.more_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
-        ctx.save_for_backward(*geom, *saved)
-        ctx.mark_non_differentiable(*frag)
+        ctx.fragment_grads = bool(fragment_grads)
+        if fragment_grads:  # bary is differentiable: face is what the backward needs of the lists
+            ctx.save_for_backward(*geom, *saved, frag[0])
+            ctx.mark_non_differentiable(frag[0], frag[2])
+            ctx.set_materialize_grads(False)  # no zeros for the outputs a loss does not use: a None for bary is the call without the term
+            ctx.image_shapes = (color.shape, depth.shape)
+        else:
+            ctx.save_for_backward(*geom, *saved)
+            ctx.mark_non_differentiable(*frag)
         return (color, depth, *frag)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth, *_grad_fragments):
-        return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered) + (None,) * 7
+    def backward(ctx, grad_color, grad_depth, *grad_fragments):
+        more = {}
+        if ctx.fragment_grads:
+            more["extra_saved"] = 1  # (face)
+            if grad_color is None:
+                grad_color = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[0])
+            if grad_depth is None:
+                grad_depth = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[1])
+            if grad_fragments[1] is not None:
+                more["fragment_grads"] = (ctx.saved_tensors[-1], grad_fragments[1].contiguous())
+        return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered, **more) + (None,) * 8
 
 
 class _TetFn(th.autograd.Function):
@@ -272,14 +300,21 @@ class _TetFn(th.autograd.Function):
         return _backward(ctx, _TET_GRADS, grad_color, grad_depth) + (None,) * 9
 
 
+def _check_fragment_grads(fragment_grads, return_fragments):
+    if fragment_grads and not return_fragments:
+        raise ValueError("fragment_grads=True needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
+
+
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                render_settings: TriRenderSettings, rows=(0, 0), exact_grads=False, camera_grads=False, return_alpha=False,
-               return_fragments=0):
+               return_fragments=0, fragment_grads=False):
     """Functional form (reference :18-43).  mv_mats / proj_mats are the TRANSPOSED matrices.  exact_grads,
-    camera_grads, return_alpha, return_fragments: see TriRenderer."""
+    camera_grads, return_alpha, return_fragments, fragment_grads: see TriRenderer."""
+    _check_fragment_grads(fragment_grads, return_fragments)
     out = _TriFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                        render_settings, tuple(rows),
-                       *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha), int(return_fragments)))
+                       *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha), int(return_fragments),
+                                  bool(fragment_grads)))
     if return_fragments:
         return _split_fragments(out, return_alpha)
     return _split_alpha(out) if return_alpha else out
@@ -326,19 +361,29 @@ class TriRenderer(th.nn.Module):
     constants (no gradient flows into them); the images and the backward are those of a call without the option.  One
     device only: the sharded Modules do not take it.
 
+    fragment_grads=True (only with return_fragments=K): Fragments.bary takes part in autograd.  The gradient a loss sends
+    into it -- through fragments.interpolate / composite, or any torch code that reads bary -- reaches verts as the exact
+    derivative of the clamped Moeller-Trumbore (u_c, v_c) of each stored (pixel, face) pair, whatever exact_grads says about
+    the images' own gradient, and with camera_grads (when a matrix needs a gradient) mv_mats and proj_mats through the
+    pixel's ray.  Coverage, list order and the clamp region are constants, as for every gradient here; pix_to_face and
+    count stay non-differentiable; pairs beyond K are not stored and get nothing.  One more kernel in the backward when a
+    gradient for bary arrives; the forward and a backward without one are unchanged.
+
     forward(verts [P,3], faces [F,3], verts_color [P,3], faces_opacity [F],
             mv_mats [B,4,4], proj_mats [B,4,4], verts_depth [B,P], faces_intense [B,F])
         -> color [B,3,H,W], depth [B,1,H,W] (, alpha [B,1,H,W] with return_alpha) (, Fragments with return_fragments)
     """
 
     def __init__(self, render_settings: TriRenderSettings, exact_grads: bool = False, camera_grads: bool = False,
-                 return_alpha: bool = False, return_fragments: int = 0):
+                 return_alpha: bool = False, return_fragments: int = 0, fragment_grads: bool = False):
         super().__init__()
+        _check_fragment_grads(fragment_grads, return_fragments)
         self.render_settings = render_settings
         self.exact_grads = bool(exact_grads)
         self.camera_grads = bool(camera_grads)
         self.return_alpha = bool(return_alpha)
         self.return_fragments = int(return_fragments)
+        self.fragment_grads = bool(fragment_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
         out = self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
@@ -351,7 +396,8 @@ class TriRenderer(th.nn.Module):
         """_TriFn on the normalised inputs (faces int32, the matrices transposed); ShardedTriRenderer adds a partition."""
         rows, shard = self._shard()
         return _TriFn.apply(*inputs, self.render_settings, rows,
-                            *_trailing(shard, self.exact_grads, self.camera_grads, self.return_alpha, self.return_fragments))
+                            *_trailing(shard, self.exact_grads, self.camera_grads, self.return_alpha, self.return_fragments,
+                                       self.fragment_grads))
 
     def _shard(self):
         """(rows, shard) of the Functions: all rows on one device (the sharded Modules return their band)."""

@@ -634,6 +634,10 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     Dims d;
     if (check_scene(s, false, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // DMR_FLAG_TRI_FRAGMENT_GRADS: K slots per pixel in bits 8-15 of the flags, as for the forward
+    const int frag_k = (s->flags & DMR_FLAG_TRI_FRAGMENT_GRADS) ? DMR_FRAGMENTS_K(s->flags) : 0;
+    if ((s->flags & DMR_FLAG_TRI_FRAGMENT_GRADS) && (frag_k < 1 || frag_k > 32))
+        return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: K (bits 8-15 of flags, DMR_FRAGMENTS_K) must be in 1..32, got " + std::to_string(frag_k));
     // DMR_FLAG_TRI_EXACT_GRADS / DMR_FLAG_TRI_CAMERA_GRADS: which k_tri_backward_hits; with camera gradients the caller's
     // [B][dL/dinv_mv 16 | dL/dinv_proj 16] buffer, requested once
     const bool camera = (s->flags & DMR_FLAG_TRI_CAMERA_GRADS) != 0;
@@ -643,6 +647,16 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     const bool idle = s->P == 0 || s->F == 0 || num_rendered <= 0 || d.r1 <= d.r0;
     float* cam_out = nullptr;
     if (caller_output(alloc, ctx, DMR_BUF_TRI_CAMERA_GRADS, camera ? 128 * (size_t)s->B : 0, "tri camera gradient", idle, st, &cam_out)) return 1;
+    // the caller's two inputs, requested once each (not when idle: the term is zero then)
+    const int32_t* frag_face = nullptr;
+    const float* frag_grad = nullptr;
+    if (frag_k && !idle) {
+        if (!alloc) return fail("null argument");
+        frag_face = static_cast<const int32_t*>(alloc(ctx, DMR_BUF_TRI_FRAGMENT_FACES, 4 * d.npix * (size_t)frag_k));
+        if (!frag_face) return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: no tri fragment face buffer (DMR_BUF_TRI_FRAGMENT_FACES)");
+        frag_grad = static_cast<const float*>(alloc(ctx, DMR_BUF_TRI_FRAGMENT_BARY_GRADS, 8 * d.npix * (size_t)frag_k));
+        if (!frag_grad) return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: no tri fragment bary gradient buffer (DMR_BUF_TRI_FRAGMENT_BARY_GRADS)");
+    }
     if (idle) {
         if (s->P > 0) {
             DMR_HIP(hipMemsetAsync(dL_dverts, 0, sizeof(float) * 3 * (size_t)s->P, st));
@@ -693,6 +707,9 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
                                      (s->flags & DMR_FLAG_ALPHA) != 0);  // (dL_ddepth [B,2,H,W]: its alpha channel reaches dL_dfopacity)
         dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st,
                                       grads, camera ? cam_part : nullptr);
+        // the fragment lists' term joins the packed vertex rows (and the tiles' camera partials) before they are unpacked / reduced
+        if (frag_face)
+            dmr::launch_tri_fragment_grads(sc, d.gx, d.gy, d.r0, d.r1, img, frag_k, frag_face, frag_grad, vrow, camera ? cam_part : nullptr, st);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
         if (camera) dmr::launch_camera_reduce(s->B, d.gx * d.gy, 32, cam_part, cam_out, st);
         return 0;

@@ -196,6 +196,13 @@ enum { TRI_GRAD_REF = 0, TRI_GRAD_EXACT = 1, TRI_GRAD_CAMERA = 2 };
 void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* vproj, const uint32_t* face_list, TriImageState img,
                               const float4* pixrec, const HitRecord* hits, uint32_t capacity, float* vrow, float* frow,
                               hipStream_t st, int grads = TRI_GRAD_REF, float* cam_part = nullptr);
+// DMR_FLAG_TRI_FRAGMENT_GRADS, behind launch_tri_backward_hits and ahead of the unpack / launch_camera_reduce: for every pixel of
+// the band and each of its K slots, dL/d(u_c, v_c) (frag_grad, f32 [B,K,2,H,W]) of the pair (pixel, frag_face[slot], i32
+// [B,K,H,W]) through the clamp and the exact derivative of the pair's (u, v), added into the position columns of the packed
+// vertex rows and, cam_part != null, into every tile's 32-float camera partial.  A face outside [0, F) is no pair.  Reads the
+// scene, the contract-layout inverse matrices and the two inputs only.  K in 1..32.  No stage of its own, no size, no host wait.
+void launch_tri_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TriImageState img, int K, const int32_t* frag_face,
+                               const float* frag_grad, float* vrow, float* cam_part, hipStream_t st);
 // sums the B * tiles partials of a camera variant per view, in a fixed order: out [B][width]; width 32 (the tri
 // renderer's, see launch_tri_backward_hits) or 64 (the tet renderer's, see launch_tet_backward)
 void launch_camera_reduce(int B, int tiles, int width, const float* cam_part, float* out, hipStream_t st);

@@ -25,6 +25,9 @@
 //                            implies exact_grads) -> the five gradients, then those two
 //                            render_tets_backward: also dL_dinv_mv_mats, dL_dinv_proj_mats, dL_dmv_mats, dL_dproj_mats
 //                            [B,4,4] (DMR_FLAG_TET_CAMERA_GRADS, implies full_grads) -> the four full gradients, then those
+//   fragment_grads=None      render_tris_backward: (pix_to_face i32 [B,K,H,W], grad_bary f32 [B,K,2,H,W]), 1 <= K <= 32: the gradient
+//                            of the fragment lists' barycentrics joins dL_dverts (and, with camera_grads, the matrices' gradients):
+//                            DMR_FLAG_TRI_FRAGMENT_GRADS; the tuple is the level's, unchanged
 //   fragments=0              render_tris: K > 0 (at most 32): per-pixel fragment lists (DMR_FLAG_TRI_FRAGMENTS) -> the tuple gains
 //                            face i32 [B,K,H,W], bary f32 [B,K,2,H,W], count i32 [B,H,W] behind the four scratch tensors
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
@@ -197,7 +200,7 @@ at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at:
 // the gradient outputs the library asks for (GradTable::from): tensors the backward has put here for the library to fill.
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, DMR_BUF_TRI_FRAGMENTS + 1> buf;
+    std::array<at::Tensor, DMR_BUF_TRI_FRAGMENT_BARY_GRADS + 1> buf;
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -206,7 +209,8 @@ struct Scratch {
 void* alloc_cb(void* ctx, int which, size_t nbytes) {
     auto* s = reinterpret_cast<Scratch*>(ctx);
     if (which < 0 || which >= (int)s->buf.size()) return nullptr;
-    if (which > DMR_BUF_WORK) {  // the caller's output tensor (gradients, fragments: 4-byte elements), which the library fills
+    if (which > DMR_BUF_WORK) {  // the caller's tensor (4-byte elements): an output the library fills (gradients, fragments) or an
+                                 // input it reads (the fragment lists of fragment_grads=)
         const at::Tensor& t = s->buf[which];
         return t.defined() && (size_t)t.numel() * sizeof(float) >= nbytes ? t.data_ptr() : nullptr;
     }
@@ -453,15 +457,42 @@ py::tuple backward(const Inputs& in, In grad_color, In grad_depth, const char* c
     return py::tuple(py::cast(out));
 }
 
+// fragment_grads=(pix_to_face, grad_bary) of render_tris_backward: checked, then handed to the library as they are (the two
+// input buffers it requests; alloc_cb serves them from Scratch::buf) with the flag and K.
+using FragmentGrads = std::optional<std::pair<at::Tensor, at::Tensor>>;
+void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t W) {
+    if (!fg.has_value()) return;
+    const at::Tensor& face = fg->first;
+    const at::Tensor& grad = fg->second;
+    if (!face.defined() || !grad.defined()) err("fragment_grads must be (pix_to_face, grad_bary), two tensors");
+    if (face.device() != c.dev || grad.device() != c.dev)
+        err("fragment_grads: pix_to_face and grad_bary must be on " + c.dev.str() + " (they are on " + face.device().str() + ", " +
+            grad.device().str() + ")");
+    if (face.scalar_type() != at::kInt) err("fragment_grads: pix_to_face must be int32, found " + dtype_name(face));
+    if (grad.scalar_type() != at::kFloat) err("fragment_grads: grad_bary must be float32, found " + dtype_name(grad));
+    const int64_t B = c.sc.B, K = face.dim() == 4 ? face.size(1) : 0;
+    if (face.dim() != 4 || face.size(0) != B || face.size(2) != H || face.size(3) != W || K < 1 || K > 32)
+        err("fragment_grads: pix_to_face must have dimensions (B, K, H, W) = (" + std::to_string(B) + ", 1..32, " + std::to_string(H) + ", " +
+            std::to_string(W) + ")");
+    if (grad.dim() != 5 || grad.size(0) != B || grad.size(1) != K || grad.size(2) != 2 || grad.size(3) != H || grad.size(4) != W)
+        err("fragment_grads: grad_bary must have dimensions (B, K, 2, H, W) = (" + std::to_string(B) + ", " + std::to_string(K) + ", 2, " +
+            std::to_string(H) + ", " + std::to_string(W) + ")");
+    if (!face.is_contiguous() || !grad.is_contiguous()) err("fragment_grads: pix_to_face and grad_bary must be contiguous");
+    c.scratch.buf[DMR_BUF_TRI_FRAGMENT_FACES] = face;
+    c.scratch.buf[DMR_BUF_TRI_FRAGMENT_BARY_GRADS] = grad;
+    c.sc.flags |= DMR_FLAG_TRI_FRAGMENT_GRADS | ((int)K << 8);
+}
+
 // tri_grads' tuple; the keywords select its level
 py::tuple render_tris_backward(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                                In inv_proj_mats, In verts_depth, In faces_intense, In dL_dout_color, In dL_dout_depth, int64_t R, In pointBuffer,
                                In faceBuffer, In binningBuffer, In imageBuffer, std::pair<int, int> rows, const std::optional<at::Tensor>& flat_out,
-                               bool exact_grads, bool camera_grads, bool alpha) {
+                               bool exact_grads, bool camera_grads, bool alpha, const FragmentGrads& fragment_grads) {
     return backward({background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense},
                     dL_dout_color, dL_dout_depth, "dL_dout_color", "dL_dout_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out,
                     &tri_grads, camera_grads ? 2 : exact_grads, alpha,
-                    [R](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                    [R, &fragment_grads](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                        attach_fragment_grads(c, fragment_grads, c.sc.H, c.sc.W);
                         return g_abi.tri_backward(&c.sc, gc, gd, (int)R, b[0], b[1], b[2], b[3], g[0], g[1], g[2], g[3], g[4], &alloc_cb, &c.scratch,
                                                   c.stream());
                     });
@@ -561,7 +592,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("image_height"), py::arg("image_width"), rows, py::arg("fill_outside") = true, py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tris_backward", &render_tris_backward, py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"), py::arg("pointBuffer"),
         py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out, py::kw_only(), py::arg("exact_grads") = false,
-        camera_grads, alpha);
+        camera_grads, alpha, py::arg("fragment_grads") = py::none());
     def("render_tets", &render_tets, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("image_height"), py::arg("image_width"),
         py::arg("ray_random_seed"), rows, py::kw_only(), alpha, py::call_guard<py::gil_scoped_release>());
     def("render_tets_backward", &render_tets_backward, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("grad_color"),

@@ -5,7 +5,11 @@ Plain torch, differentiable, no kernels.  What is HELD CONSTANT by every functio
 data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
   * their order (the tile's depth sort),
-  * the barycentrics (the clamped (u, v) of the pixel's ray on each face),
+  * the barycentrics (the clamped (u, v) of the pixel's ray on each face) -- UNLESS the renderer was made with
+    fragment_grads=True: frag.bary then requires grad, interpolate and composite (which only read it) pass the gradient on, and
+    the renderer's backward carries it to verts and, with camera_grads, to mv_mats / proj_mats (the exact derivative of the
+    clamped (u, v), the clamp region held fixed).  Positions, normals, texture coordinates or a depth shaded here then see
+    the geometry,
 exactly the constants of the renderer's own default gradients.  Gradients flow into what the caller passes: opacities,
 per-vertex attributes, per-face scales.  A pixel with count > K holds the first K of its faces only: what is computed for it
 is the truncated sum.
@@ -46,7 +50,8 @@ def blend_weights(frag, faces_opacity: th.Tensor) -> th.Tensor:
 def interpolate(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
     """Per-vertex attributes vert_attrs [P,C] at every fragment, [B,K,C,H,W]: (1 - u - v) a_0 + u a_1 + v a_2 over the three
     vertices of the slot's face (faces [F,3]), with the rasteriser's clamped (u, v); 0 in empty slots.
-    Constants: the faces and the barycentrics.  Differentiable in vert_attrs."""
+    Constants: the faces and the barycentrics.  Differentiable in vert_attrs -- and in frag.bary when the renderer's
+    fragment_grads made it differentiable."""
     face = frag.pix_to_face
     used = face >= 0
     vid = faces.long()[face.clamp(min=0).long()]             # [B,K,H,W,3]
@@ -63,7 +68,7 @@ def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.T
     """Front-to-back blend of interpolated attributes: (sum_k w_k s_k a_k [B,C,H,W], T = prod_k (1 - o_k) [B,1,H,W]), a_k =
     interpolate(...), w_k = blend_weights(...), s_k = face_scale[b, face_k] (face_scale [B,F], e.g. faces_intense; None: 1).
     T is what is left for a background: result + T * bg.  Constants: the faces, their order, the barycentrics.
-    Differentiable in faces_opacity, vert_attrs and face_scale."""
+    Differentiable in faces_opacity, vert_attrs and face_scale (and in frag.bary with the renderer's fragment_grads)."""
     _, o = _opacity_slots(frag, faces_opacity)
     t = _transmittance(o)
     w = o * t[:, :-1]

@@ -372,14 +372,17 @@ class ShardedTriRenderer(_Banded, TriRenderer):
     Same call signature as TriRenderer, and the same exact_grads / camera_grads / return_alpha options (with camera_grads
     the flat all-reduce payload gains [B][dL/dinv_mv 16 | dL/dinv_proj 16]; return_alpha adds no gradient tensor: alpha
     travels as a second channel of the depth image).  TriRenderer's return_fragments is NOT available here: the per-pixel
-    fragment lists are a single-device output so far (a rank would hold its band's only).  Every rank must pass identical inputs; every rank
+    fragment lists are a single-device output so far (a rank would hold its band's only); nor is fragment_grads, their gradient
+    (ValueError).  Every rank must pass identical inputs; every rank
     gets the full summed gradients.  The bands may be refreshed at any time with `set_row_work` (e.g. every few
     iterations from `row_work_from_ranges` / `view_row_work_from_ranges`)."""
 
     def __init__(self, render_settings: TriRenderSettings, group=None, assemble: bool = True, impl=None, partition: str = "auto",
-                 exact_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False):
+                 exact_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False, fragment_grads: bool = False):
         if partition not in ("auto", "bands", "view_bands"):
             raise ValueError("partition must be 'auto', 'bands' or 'view_bands'")
+        if fragment_grads:
+            raise ValueError("fragment_grads is not available on the sharded Modules (nor is return_fragments, which it needs)")
         super().__init__(render_settings, group, assemble, impl, exact_grads=exact_grads, camera_grads=camera_grads,
                          return_alpha=return_alpha)
         self.partition = partition

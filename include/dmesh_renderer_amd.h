@@ -43,7 +43,9 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
        DMR_BUF_TET_GRADS = 5 /* dmr_tet_backward with DMR_FLAG_TET_FULL_GRADS: an OUTPUT, see there */,
        DMR_BUF_TRI_CAMERA_GRADS = 6 /* dmr_tri_backward with DMR_FLAG_TRI_CAMERA_GRADS: an OUTPUT, see there */,
        DMR_BUF_TET_CAMERA_GRADS = 7 /* dmr_tet_backward with DMR_FLAG_TET_CAMERA_GRADS: an OUTPUT, see there */,
-       DMR_BUF_TRI_FRAGMENTS = 8 /* dmr_tri_forward with DMR_FLAG_TRI_FRAGMENTS: an OUTPUT, see the flag */ };
+       DMR_BUF_TRI_FRAGMENTS = 8 /* dmr_tri_forward with DMR_FLAG_TRI_FRAGMENTS: an OUTPUT, see the flag */,
+       DMR_BUF_TRI_FRAGMENT_FACES = 9 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */,
+       DMR_BUF_TRI_FRAGMENT_BARY_GRADS = 10 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -58,7 +60,8 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS or
  * DMR_FLAG_TET_CAMERA_GRADS only) 4 (3P + BF), exactly; work (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 per tile of
  * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly; tri fragments (tri
- * forward with DMR_FLAG_TRI_FRAGMENTS only) 4 BWH (3K + 1), exactly. */
+ * forward with DMR_FLAG_TRI_FRAGMENTS only) 4 BWH (3K + 1), exactly; tri fragment faces and tri fragment bary grads (tri
+ * backward with DMR_FLAG_TRI_FRAGMENT_GRADS only; inputs) 4 BKWH and 8 BKWH, exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -155,6 +158,24 @@ typedef struct dmr_scene {
  * those of a call without the flag; no host wait is added (DMR_FLAG_ASYNC and stream capture work as before).  The tet
  * renderer has no such output. */
 #define DMR_FLAG_TRI_FRAGMENTS 64
+/* dmr_tri_backward only (ignored by every other call): the gradient of the fragment lists' barycentrics reaches the vertex
+ * positions and, with DMR_FLAG_TRI_CAMERA_GRADS, the inverse matrices.  K travels in bits 8-15 of the flags as for the forward
+ * (DMR_FRAGMENTS_K; the flag with K = 0 or K > 32 is an error, raised before anything is allocated or launched).  The call then
+ * requests two more buffers through `alloc`, once each -- INPUTS, which the caller has filled before the call:
+ *   DMR_BUF_TRI_FRAGMENT_FACES       int32 [B,K,H,W]    4 BKWH bytes, exactly: the face of every (pixel, slot) pair, as the forward
+ *                                                       returned it -- or any other face: the pair need not be one the forward blended;
+ *   DMR_BUF_TRI_FRAGMENT_BARY_GRADS  fp32  [B,K,2,H,W]  8 BKWH bytes, exactly: dL/d(u_c, v_c) of that pair
+ * (not at all when there is nothing to back-propagate: P == 0, F == 0, num_rendered <= 0 or an empty tile-row band; the term is
+ * then zero).  One more kernel behind the hit-parallel one recomputes, for every pixel of the rendered tile rows and every one of
+ * its K slots, the pair's Moeller-Trumbore (u, v) and clamp region from the pixel's ray with the forward's arithmetic, and adds
+ * the exact derivative of (u_c, v_c) times the upstream gradient -- coverage, list order and the clamp region held fixed, as for
+ * every gradient here -- into dL_dverts, whichever of the reference's, the exact or the camera gradients the other flags select,
+ * and with DMR_FLAG_TRI_CAMERA_GRADS also, through the pixel's ray, into the DMR_BUF_TRI_CAMERA_GRADS result.  A slot whose face
+ * lies outside [0, F) contributes nothing (-1, the forward's unused slots, and anything else), nor does a pair whose upstream
+ * gradient is (0, 0), a pair the forward would skip (denom == 0) or a pixel outside the rendered tile rows.  Pairs beyond K were
+ * never stored and get nothing.  The other four gradient outputs, the scratch buffers and the work space's size are those of a
+ * call without the flag; no host wait is added (DMR_FLAG_ASYNC and stream capture work as before). */
+#define DMR_FLAG_TRI_FRAGMENT_GRADS 128
 #define DMR_FRAGMENTS_K(flags) (((flags) >> 8) & 255)
 #define DMR_FRAGMENTS_FLAGS(k) (DMR_FLAG_TRI_FRAGMENTS | (((k) & 255) << 8))
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
@@ -183,7 +204,9 @@ int dmr_tri_forward(const dmr_scene* scene, float* out_color, float* out_depth,
  * normalize(inv_mv (inv_proj (ndc, -1, 1)).xyz - origin) with no w divide); their w rows are 0.  dL_dvdepth does not
  * involve the matrices.  No host wait is added (DMR_FLAG_ASYNC and stream capture work as without the flags).  Without
  * the flags the call is exactly as before and requests no buffer beyond the work space.
- * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term. */
+ * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term.
+ * With DMR_FLAG_TRI_FRAGMENT_GRADS dL_dverts (and the camera gradients) gain the fragment lists' term, from two input buffers
+ * requested through `alloc` (see the flag). */
 int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      int num_rendered, const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,
