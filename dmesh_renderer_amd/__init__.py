@@ -82,19 +82,21 @@ def _alpha_kw(alpha) -> dict:
 
 
 class Fragments(NamedTuple):
-    """Per-pixel fragment lists of the tri renderer (return_fragments=K; helpers in dmesh_renderer_amd.fragments): the faces each
+    """Per-pixel fragment lists of either renderer (return_fragments=K; helpers in dmesh_renderer_amd.fragments): the faces each
     pixel blended, front to back, and where its ray hit them.  Constants of every gradient, like coverage and list order --
-    unless the renderer was made with fragment_grads=True: `bary` then takes part in autograd (its gradient reaches verts and,
-    with camera_grads, the matrices); pix_to_face and count stay constants."""
+    unless the TRI renderer was made with fragment_grads=True: `bary` then takes part in autograd (its gradient reaches verts
+    and, with camera_grads, the matrices); pix_to_face and count stay constants.  The tet renderer's lists are in exact march
+    order, their barycentrics unclamped (a face the march crosses is hit in its interior), and always constants."""
     pix_to_face: th.Tensor  # int32 [B,K,H,W]: face ids in blend order, -1 in unused slots
-    bary: th.Tensor         # float32 [B,K,2,H,W]: clamped (u, v); the weights of the face's vertices are (1 - u - v, u, v)
-    count: th.Tensor        # int32 [B,H,W]: blended faces of the pixel; above K the list is truncated to its first K
+    bary: th.Tensor         # float32 [B,K,2,H,W]: (u, v), clamped by the tri renderer; the weights of the face's vertices are (1 - u - v, u, v)
+    count: th.Tensor        # int32 [B,H,W]: blended faces of the pixel (tet: 0 where the march failed); above K the list is truncated to its first K
 
 
 def _split_fragments(out, alpha):
-    """(color, depth, face, bary, count) of _TriFn called with fragments -> (color, depth[, alpha], Fragments)."""
-    head = _split_alpha(out[:2]) if alpha else tuple(out[:2])
-    return (*head, Fragments(*out[2:5]))
+    """(color, depth, face, bary, count) of _TriFn / (color, depth, active, face, bary, count) of _TetFn called with fragments
+    -> (color, depth[, active][, alpha], Fragments)."""
+    head = _split_alpha(out[:-3]) if alpha else tuple(out[:-3])
+    return (*head, Fragments(*out[-3:]))
 
 
 def _split_alpha(out):
@@ -277,27 +279,32 @@ class _TriFn(th.autograd.Function):
 
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
-    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha: as for _TriFn."""
+    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha: as for _TriFn.
+    fragments = K > 0 (one device only; the last argument, only when set: see _trailing): three more outputs, the
+    non-differentiable face [B,K,H,W], bary [B,K,2,H,W] and count [B,H,W] of render_tets(fragments=K)."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False,
-                alpha=False):
+                alpha=False, fragments=0):
         geom = (verts, faces, verts_color, faces_opacity)
-        (color, depth, active), saved = _forward(_impl(shard).render_tets, settings, geom, mv_mats, proj_mats, verts_depth,
-                                                 faces_intense, rows, alpha, (tets, face_tets, tet_faces))
+        if fragments and shard is not None:
+            raise ValueError("return_fragments is not available on the sharded Modules")
+        (color, depth, active, *frag), saved = _forward(_impl(shard).render_tets, settings, geom, mv_mats, proj_mats, verts_depth,
+                                                        faces_intense, rows, alpha, (tets, face_tets, tet_faces),
+                                                        **({"fragments": fragments} if fragments else {}))
         if shard is not None:
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
         ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
         ctx.more_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads, camera_grads, alpha
         ctx.save_for_backward(*geom, *saved)
-        ctx.mark_non_differentiable(active)
-        return color, depth, active
+        ctx.mark_non_differentiable(active, *frag)
+        return (color, depth, active, *frag)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth, _grad_active):
-        return _backward(ctx, _TET_GRADS, grad_color, grad_depth) + (None,) * 9
+    def backward(ctx, grad_color, grad_depth, _grad_active, *_grad_fragments):
+        return _backward(ctx, _TET_GRADS, grad_color, grad_depth) + (None,) * 10
 
 
 def _check_fragment_grads(fragment_grads, return_fragments):
@@ -322,12 +329,14 @@ def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False, camera_grads=False,
-               return_alpha=False):
+               return_alpha=False, return_fragments=0):
     """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads,
-    camera_grads, return_alpha: see TetRenderer."""
+    camera_grads, return_alpha, return_fragments: see TetRenderer."""
     out = _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                        tets, face_tets, tet_faces, render_settings, tuple(rows),
-                       *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha)))
+                       *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha), int(return_fragments)))
+    if return_fragments:
+        return _split_fragments(out, return_alpha)
     return _split_alpha(out) if return_alpha else out
 
 
@@ -423,18 +432,31 @@ class TetRenderer(th.nn.Module):
     return_alpha=True (beyond the reference): a fourth output, alpha [B,1,H,W] = 1 - T as TriRenderer's; 0 where the
     march fails (active == False: the colour there is the bare background).  Its gradient reaches faces_opacity only.
 
+    return_fragments=K, 1 <= K <= 32 (beyond the reference): the last output is a Fragments tuple (pix_to_face int32
+    [B,K,H,W], bary float32 [B,K,2,H,W], count int32 [B,H,W]), as TriRenderer's, here in EXACT march order: per pixel the
+    first K faces its ray composited, front to back, the unclamped (u, v) it hit them at (a tet hit is interior by
+    construction), and the number of its march steps (count > K: the list is truncated).  A pixel whose march fails
+    (active == False) has count 0 and no fragments, whatever it crossed: its colour is the bare background.
+    dmesh_renderer_amd.fragments shades from them -- normals, positions (interpolate(frag, faces, verts) is the hit point),
+    feature channels, texture coordinates, per-face visibility -- in plain torch: composite(...) + T * bg is this renderer's
+    colour where count <= K, except that behind a face of opacity 1 the renderer goes on with T = 1e-5 (T_EPS / 10), not 0.
+    The three tensors are constants (no gradient flows into them; there is no fragment_grads here); the images and the
+    backward are those of a call without the option.  One device only: the sharded Modules do not take it.
+
     forward(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
             tets [T,4], face_tets [F,2] (-1 = none), tet_faces [T,4])
         -> color [B,3,H,W], depth [B,1,H,W], active bool [B,H,W] (, alpha [B,1,H,W] with return_alpha)
+           (, Fragments with return_fragments)
     """
 
     def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False,
-                 return_alpha: bool = False):
+                 return_alpha: bool = False, return_fragments: int = 0):
         super().__init__()
         self.render_settings = render_settings
         self.full_grads = bool(full_grads)
         self.camera_grads = bool(camera_grads)
         self.return_alpha = bool(return_alpha)
+        self.return_fragments = int(return_fragments)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
@@ -444,7 +466,9 @@ class TetRenderer(th.nn.Module):
                            mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
                            verts_depth.to(**f32), faces_intense.to(**f32),
                            tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
-                           rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha))
+                           rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha, self.return_fragments))
+        if self.return_fragments:
+            return _split_fragments(out, self.return_alpha)
         return _split_alpha(out) if self.return_alpha else out
 
     _shard = TriRenderer._shard  # (rows, shard) of one device

@@ -358,8 +358,13 @@ int build_placement(const SizeKey& key, const Dims& d, uint64_t R, const ImageSt
     return 0;
 }
 
+constexpr uint64_t TET_SEQ_BUDGET = 16ull << 30;  // tet: bytes of march sequence a call may own
+// ... and the steps per pixel it has room for (a multiple of 4, at least 4)
+uint64_t march_budget_steps(const Dims& d) {
+    return std::max<uint64_t>(TET_SEQ_BUDGET / std::max<uint64_t>(dmr::tet_seq_bytes((size_t)d.ntiles, 4), 1), 1) * 4;
+}
 // tet: the key's SizeGuess::seq_steps word (created by a default forward: create; null: none) and, if asked for, the room for
-// the next forward's march sequence: the longest march + 25 %, a multiple of 4, within a memory budget (0: no march reported
+// the next forward's march sequence: the longest march + 25 %, a multiple of 4, within that budget (0: no march reported
 // yet, that call's backward re-marches).
 uint32_t* march_estimate(const SizeKey& key, const Dims& d, bool create, size_t* seq_steps = nullptr) {
     std::lock_guard<std::mutex> lk(g_size_mu);
@@ -367,9 +372,8 @@ uint32_t* march_estimate(const SizeKey& key, const Dims& d, bool create, size_t*
     if (!g.seq_steps && create && !(g.seq_steps = reinterpret_cast<uint32_t*>(pinned_words()))) (void)hipGetLastError();
     if (seq_steps) {
         const uint64_t longest = g.seq_steps ? *reinterpret_cast<volatile uint32_t*>(g.seq_steps) : 0u;
-        const uint64_t budget = 16ull << 30;  // bytes: beyond it the longest rays do not fit and such a call re-marches
-        const uint64_t per4 = dmr::tet_seq_bytes((size_t)d.ntiles, 4);
-        *seq_steps = longest ? (size_t)(std::min<uint64_t>((longest + longest / 4 + 4 + 3) / 4, std::max<uint64_t>(budget / std::max<uint64_t>(per4, 1), 1)) * 4) : 0;
+        // (beyond the budget the longest rays do not fit and such a call re-marches)
+        *seq_steps = longest ? (size_t)std::min<uint64_t>((longest + longest / 4 + 4 + 3) / 4 * 4, march_budget_steps(d)) : 0;
     }
     return g.seq_steps;
 }
@@ -430,9 +434,10 @@ int sized(const Sizing& z, const SizeKey& key, size_t BF, bool async, hipStream_
 }
 
 // Stages shared by both renderers up to the sorted per-tile lists, then `render` (the renderer's own kernels, which only need
-// the scratch buffers, the binning buffer included).
+// the scratch buffers, the binning buffer included).  min_seq_steps (tet, a multiple of 4): steps per pixel the march sequence
+// has room for whatever the estimate says (DMR_FLAG_TET_FRAGMENTS reads the first K steps of every pixel out of it).
 int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc, void* ctx, hipStream_t st, int* num_rendered,
-                const std::function<void(const Scratch&, dmr::ListSize)>& render) {
+                const std::function<void(const Scratch&, dmr::ListSize)>& render, size_t min_seq_steps = 0) {
     const Scratch need = carve_scratch(s, tet, d, nullptr, nullptr, nullptr);
     void* pb = alloc(ctx, DMR_BUF_POINT, need.point_bytes);
     void* fb = alloc(ctx, DMR_BUF_FACE, need.face_bytes);
@@ -444,6 +449,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
     const SizeKey key = size_key(s, tet, d);
     size_t seq_steps = 0;
     if (tet) march_estimate(key, d, !async, &seq_steps);
+    seq_steps = std::max(seq_steps, min_seq_steps);
     const bool placed = placement_eligible(tet, d);
     const Placement pl = placed ? find_placement(key, d) : Placement{};
 
@@ -739,6 +745,21 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
     if (!alloc || !num_rendered || !out_color || !out_depth || !out_active) return fail("null argument");
     *num_rendered = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // DMR_FLAG_TET_FRAGMENTS: K fragment slots per pixel, K in bits 8-15 of the flags as for the tri flag
+    int frag_k = (s->flags & DMR_FLAG_TET_FRAGMENTS) ? DMR_FRAGMENTS_K(s->flags) : 0;
+    if ((s->flags & DMR_FLAG_TET_FRAGMENTS) && (frag_k < 1 || frag_k > 32))
+        return fail("DMR_FLAG_TET_FRAGMENTS: K (bits 8-15 of flags, DMR_TET_FRAGMENTS_FLAGS(K)) must be in 1..32, got " + std::to_string(frag_k));
+    if (s->P == 0 || s->F == 0) frag_k = 0;  // nothing marches: the caller's initialisation (-1 / 0) is the result, no request
+    // the fragments are read out of the march sequence: room for the first K steps of every pixel, whatever the estimate says
+    const size_t frag_steps = ((size_t)frag_k + 3) / 4 * 4;
+    if (frag_steps > march_budget_steps(d))
+        return fail("DMR_FLAG_TET_FRAGMENTS: K = " + std::to_string(frag_k) + " needs a march sequence of " +
+                    std::to_string(dmr::tet_seq_bytes((size_t)d.ntiles, frag_steps)) + " bytes (" + std::to_string(frag_steps) +
+                    " steps for each of " + std::to_string((size_t)d.ntiles * dmr::TILE_PIX) + " tile pixels), beyond the budget of " +
+                    std::to_string(TET_SEQ_BUDGET) + " bytes (16 GiB)");
+    float* fragments = nullptr;  // the caller's [face | bary | count], requested once
+    if (caller_output(alloc, ctx, DMR_BUF_TET_FRAGMENTS, frag_k ? 4 * d.npix * (3 * (size_t)frag_k + 1) : 0, "tet fragment", false, st, &fragments))
+        return 1;
     auto render = [&](const Scratch& c, dmr::ListSize) {
         const dmr::TetImageState img = tet_image(c);
         const dmr_scene sc = canonical(s, c.is.mats);
@@ -746,8 +767,10 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
         dmr::launch_tet_first_intersect(sc, d.gx, d.gy, d.r0, d.r1, c.fs.key_depth, c.fs.max_depth, c.is.tile_offset,
                                         d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys, c.bs.face_list, c.bs.capacity, img, st);
         dmr::launch_tet_forward(sc, d.gx, d.gy, d.r0, d.r1, img, out_color, out_depth, out_active, st, (s->flags & DMR_FLAG_ALPHA) != 0);
+        // the fragments describe the images the call returns: behind every k_tet_forward, so after a redo the redo's
+        if (fragments) dmr::launch_tet_fragments(sc, d.gx, d.gy, d.r0, d.r1, img, frag_k, fragments, st);
     };
-    return run_forward(s, true, d, alloc, ctx, st, num_rendered, render);
+    return run_forward(s, true, d, alloc, ctx, st, num_rendered, render, frag_steps);
 }
 
 int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL_ddepth, const void* point_buf,

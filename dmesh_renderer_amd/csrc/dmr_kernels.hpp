@@ -221,6 +221,9 @@ void launch_tri_unpack(const dmr_scene& s, const float* vrow, const float* frow,
 // dynamic allocation of 4-KB chunks from an atomic counter was measured first: its bookkeeping inside the march loop cost
 // the forward 100 us at C3, more than the backward gained).  A sequence that did not fit (max_steps > cap_steps; cap_steps
 // == 0: no estimate yet) is ignored: the backward then re-marches like the reference.
+// Its second reader is k_tet_fragments (DMR_FLAG_TET_FRAGMENTS), which takes the first K entries of every pixel: a forward
+// with that flag has cap_steps >= K rounded up to 4 whatever the estimate (dmr_api.hip), and those entries are there whether
+// or not the whole sequence fits.
 // Bit 31 of an entry: the reference's reverse march would stop behind this face ("error case 3": a second face of the
 // tet the ray leaves through this one is hit from outside as well, backward.cu:456-460) -- the forward has those three
 // tests in its hands anyway, so the backward reproduces the reference's decision without repeating them.
@@ -250,6 +253,12 @@ void launch_tet_first_intersect(const dmr_scene& s, int gx, int gy, int r0, int 
                                 uint32_t capacity, TetImageState img, hipStream_t st);
 void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
                         float* out_color, float* out_depth, float* out_active, hipStream_t st, bool alpha = false);
+// DMR_FLAG_TET_FRAGMENTS, behind the call's final launch_tet_forward (whose state it reads: n_contrib, is_active and the march
+// sequence, which such a call sizes to at least K steps rounded up to 4): per pixel of the band the first K faces the march
+// composited, front to back, the (u, v) of the pixel's ray on each and their number, into the caller's buffer [face i32
+// B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W] (unused slots -1 / 0; count = n_contrib where is_active, else 0).  K in
+// 1..32.  No stage of its own, no size, no host wait.
+void launch_tet_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, void* fragments, hipStream_t st);
 void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopacity, int64_t n_fopacity, hipStream_t st);
 // Two launches, of which the device runs one: k_tet_backward_seq when the forward's march sequence is complete
 // (seq->max_steps <= seq->cap_steps != 0), else the re-marching k_tet_backward; the other one returns at once.  No host read.

@@ -1172,7 +1172,93 @@ k_tet_backward_seq(TetParams p, const float* __restrict__ dL_dcolor, const float
     if constexpr (CAM) tet_camera_tile(p, b, px, py, work, cam, tid, reinterpret_cast<float*>(&s_val[0][0]), cam_part);
 }
 
-
+// ---------------------------------------------------------------------------
+// k_tet_fragments (DMR_FLAG_TET_FRAGMENTS) -- per pixel, WHICH faces the march composited and WHERE the ray hit them.
+//
+// A launch of its own behind the call's final k_tet_forward, reading what that kernel left: n_contrib, is_active and the
+// first entries of the march sequence (dmr_kernels.hpp), which a call with the flag sizes to at least K steps.  No march, no
+// tet records, no candidate tests, no orientation logic: per slot one row entry (a lane's 16-byte word every fourth slot, a
+// contiguous kilobyte per wave), the face's record (the vertices: 48 bytes of one 64-byte line, the next slot's in flight
+// while this one computes, as k_tet_backward_seq does) and one ray_tri_hit for (u, v), the function face_tuv evaluates
+// for the forward -- exact arithmetic, but nothing is decided by it.  A pixel whose march failed (is_active == 0) has no
+// fragments, whatever it marched through: its colour is the bare background.  Slot k goes straight to face[b,k,y,x],
+// bary[b,k,0:2,y,x] as it is found (no per-lane array: it would be indexed dynamically and live in scratch); faces beyond K
+// are counted (count = n_contrib), not stored.  Every pixel of the rendered rows is fully written: unused slots face = -1,
+// bary = 0.  k_tet_forward's grid and pixel-to-lane mapping: the rows are addressed by (tile, wave, lane).
+// It is not part of k_tet_forward, which is VALU-bound at four waves per SIMD.  No stage, no size, no host wait.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_tet_fragments(TetParams p, int K, int32_t* __restrict__ out_face, float* __restrict__ out_bary, int32_t* __restrict__ out_count) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
+    const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
+    const bool inside = px < p.W && py < p.H;
+    const int64_t HW = (int64_t)p.H * p.W, pix_id = (int64_t)p.W * py + px, bpix = (int64_t)b * HW + pix_id;
+    V3 ro = {0, 0, 0}, rd = {0, 0, 0};
+    uint32_t count = 0u;
+    if (inside) {
+        pixel_ray<true>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd, *p.seed, (uint64_t)bpix);
+        if (p.img.is_active[bpix] != 0) count = p.img.n_contrib[bpix];
+    }
+    const uint32_t seq_cap = p.img.seq->cap_steps;  // (>= K rounded up to 4 in a call with the flag; clamped to all the same)
+    const uint32_t need = min(min(count, (uint32_t)K), seq_cap);
+    const uint32_t smax = wave_max_u32(need);
+    const uint4* const seq_row = reinterpret_cast<const uint4*>(p.img.binning + p.img.seq->offset) +
+                                 ((((size_t)b * p.gy + ty) * p.gx + tx) * 4 + wave) * (size_t)(seq_cap / 4u) * 64u + (uint32_t)lane;
+    const int64_t face0 = (int64_t)b * K * HW + pix_id, bary0 = (int64_t)b * K * 2 * HW + pix_id;
+    if (smax != 0u) {  // (uniform per wave)
+        struct Rec { float4 f0, f1, f2; };
+        auto load_row = [&](uint32_t s) -> uint4 {  // the row word of slot s (uniform s; only lanes that have a slot in that row read)
+            uint4 w = make_uint4(0u, 0u, 0u, 0u);
+            if ((s & ~3u) < need) w = seq_row[(size_t)(s >> 2) * 64u];
+            return w;
+        };
+        // the face of slot s of this lane out of the row word it belongs to (bit 31, the reverse-march flag, masked off);
+        // -1: no such slot, or an id that is not a face's
+        auto entry = [&](const uint4& w, uint32_t s) -> int {
+            if (s >= need) return -1;
+            const uint32_t q = s & 3u;
+            const uint32_t e = (q == 0u ? w.x : (q == 1u ? w.y : (q == 2u ? w.z : w.w))) & 0x7fffffffu;
+            return e < (uint32_t)p.F ? (int)e : -1;
+        };
+        auto load_rec = [&](int face, Rec& r) {
+            if (face < 0) return;
+            const float4* fq = reinterpret_cast<const float4*>(p.facerec + face);
+            r.f0 = fq[0]; r.f1 = fq[1]; r.f2 = fq[2];
+        };
+        Rec rc = {}, rn = {};
+        uint4 w_cur = load_row(0u), w_nxt = load_row(4u);  // the row of the slot being prepared, and the one behind it
+        int f_cur = entry(w_cur, 0u);
+        load_rec(f_cur, rc);
+        // slot s from `cur` while the record of slot s + 1 arrives in `nxt` (two sets used alternately, as k_tet_backward_seq)
+        auto one = [&](uint32_t s, const Rec& cur, Rec& nxt) {
+            if (((s + 1u) & 3u) == 0u) { w_cur = w_nxt; w_nxt = load_row(s + 5u); }
+            const int f_nxt = entry(w_cur, s + 1u);
+            load_rec(f_nxt, nxt);
+            if (s < need) {
+                V3 tuv = {0, 0, 0};
+                if (f_cur >= 0)
+                    ray_tri_hit(ro, rd, {cur.f0.x, cur.f0.y, cur.f0.z}, {cur.f0.w, cur.f1.x, cur.f1.y}, {cur.f1.z, cur.f1.w, cur.f2.x}, tuv);
+                out_face[face0 + (int64_t)s * HW] = f_cur;
+                out_bary[bary0 + (int64_t)(2u * s) * HW] = tuv.y;
+                out_bary[bary0 + (int64_t)(2u * s + 1u) * HW] = tuv.z;
+            }
+            f_cur = f_nxt;
+        };
+        for (uint32_t s = 0u; s < smax; s += 2u) {
+            one(s, rc, rn);
+            if (s + 1u < smax) one(s + 1u, rn, rc);
+        }
+    }
+    if (inside) {
+        out_count[bpix] = (int32_t)count;
+        for (uint32_t k = need; k < (uint32_t)K; k++) {
+            out_face[face0 + (int64_t)k * HW] = -1;
+            out_bary[bary0 + (int64_t)(2u * k) * HW] = 0.f;
+            out_bary[bary0 + (int64_t)(2u * k + 1u) * HW] = 0.f;
+        }
+    }
+}
 
 static TetParams make_params(const dmr_scene& s, int gx, int gy, int r0, TetImageState img) {
     TetParams p;
@@ -1224,6 +1310,16 @@ void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetI
     StageScope t(DMR_STAGE_TET_FORWARD, st);
     if (alpha) k_tet_forward<true><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
     else k_tet_forward<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
+}
+
+void launch_tet_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, void* fragments, hipStream_t st) {
+    if (r1 <= r0 || K < 1 || K > 32) return;
+    TetParams p = make_params(s, gx, gy, r0, img);
+    const size_t npix = (size_t)s.B * s.H * s.W;  // [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W]
+    int32_t* face = static_cast<int32_t*>(fragments);
+    float* bary = reinterpret_cast<float*>(face + (size_t)K * npix);
+    int32_t* count = face + 3 * (size_t)K * npix;
+    k_tet_fragments<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, K, face, bary, count);
 }
 
 // both gradient tensors zeroed by one launch (two hipMemsetAsync are three fill kernels of ~4.6 us each)

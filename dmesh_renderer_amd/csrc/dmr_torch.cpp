@@ -30,6 +30,7 @@
 //                            DMR_FLAG_TRI_FRAGMENT_GRADS; the tuple is the level's, unchanged
 //   fragments=0              render_tris: K > 0 (at most 32): per-pixel fragment lists (DMR_FLAG_TRI_FRAGMENTS) -> the tuple gains
 //                            face i32 [B,K,H,W], bary f32 [B,K,2,H,W], count i32 [B,H,W] behind the four scratch tensors
+//                            render_tets: the same (DMR_FLAG_TET_FRAGMENTS): the faces of the march, in march order
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -200,7 +201,7 @@ at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at:
 // the gradient outputs the library asks for (GradTable::from): tensors the backward has put here for the library to fill.
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, DMR_BUF_TRI_FRAGMENT_BARY_GRADS + 1> buf;
+    std::array<at::Tensor, DMR_BUF_TET_FRAGMENTS + 1> buf;
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -293,22 +294,27 @@ struct Forward {
     }
 };
 
-// The fragment lists of render_tris(fragments=K): ONE buffer [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W] -- what the
-// library requests as DMR_BUF_TRI_FRAGMENTS -- and its three pieces as views.  Pre-initialised (face -1, the rest 0) for the
-// images' reason: a row band, or P == 0 / F == 0, where nothing writes them (Forward::written).
+// The fragment lists of render_tris / render_tets(fragments=K): ONE buffer [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32
+// B,H,W] -- what the library requests as `which`, DMR_BUF_TRI_FRAGMENTS / DMR_BUF_TET_FRAGMENTS, when `flag` of the same
+// renderer is set -- and its three pieces as views.  Pre-initialised (face -1, the rest 0) for the images' reason: a row band,
+// or P == 0 / F == 0, where nothing writes them (Forward::written).
 struct Fragments {
     at::Tensor face, bary, count;
-    Fragments(Forward& f, int64_t K, int64_t H, int64_t W) {
+    Fragments(Forward& f, int64_t K, int64_t H, int64_t W, int which = DMR_BUF_TRI_FRAGMENTS, int flag = DMR_FLAG_TRI_FRAGMENTS) {
         const int64_t B = f.call.sc.B, n = B * H * W;
         const at::Tensor buf = at::empty({n * (3 * K + 1)}, at::TensorOptions().dtype(at::kInt).device(f.dev));
         face = buf.narrow(0, 0, K * n).view({B, K, H, W});
         bary = buf.narrow(0, K * n, 2 * K * n).view(at::kFloat).view({B, K, 2, H, W});
         count = buf.narrow(0, 3 * K * n, n).view({B, H, W});
         if (!f.written) { face.fill_(-1); buf.narrow(0, K * n, (2 * K + 1) * n).zero_(); }
-        f.call.scratch.buf[DMR_BUF_TRI_FRAGMENTS] = buf;
-        f.call.sc.flags |= DMR_FRAGMENTS_FLAGS((int)K);
+        f.call.scratch.buf[which] = buf;
+        f.call.sc.flags |= flag | ((int)K << 8);
     }
 };
+
+void check_fragments(int64_t fragments) {
+    if (fragments < 0 || fragments > 32) err("fragments must be in 0..32 (fragment slots per pixel; 0: no fragment output), got " + std::to_string(fragments));
+}
 
 // -> (num_rendered:int, color, depth, pointBuffer, faceBuffer, binningBuffer, imgBuffer, face, bary, count): the last three
 // undefined tensors unless fragments=K > 0.  (Bound below with the GIL released and its tuple cut to the reference's seven
@@ -319,7 +325,7 @@ TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In face
                       bool fill_outside, bool alpha, int64_t fragments) {
     const Inputs in{background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense};
     check_common(in, false);
-    if (fragments < 0 || fragments > 32) err("fragments must be in 0..32 (fragment slots per pixel; 0: no fragment output), got " + std::to_string(fragments));
+    check_fragments(fragments);
     Forward f(in, image_height, image_width, 0, rows, fill_outside, alpha);
     std::optional<Fragments> frag;
     if (fragments > 0) frag.emplace(f, fragments, image_height, image_width);
@@ -330,21 +336,26 @@ TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In face
                           frag ? std::make_tuple(frag->face, frag->bary, frag->count) : std::make_tuple(at::Tensor(), at::Tensor(), at::Tensor()));
 }
 
-// -> (color, depth, active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer)
-using TetFwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+// -> (color, depth, active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer, face, bary, count): the last three
+// undefined tensors unless fragments=K > 0 (bound below like render_tris: its tuple cut to the reference's seven without them)
+using TetFwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
 TetFwdOut render_tets(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                       In inv_proj_mats, In verts_depth, In faces_intense, In tets, In face_tets, In tet_faces, int64_t image_height,
-                      int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows, bool alpha) {
+                      int64_t image_width, int64_t ray_random_seed, std::pair<int, int> rows, bool alpha, int64_t fragments) {
     const Inputs in{background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense,
                     &tets, &face_tets, &tet_faces};
     check_common(in, true);
+    check_fragments(fragments);
     Forward f(in, image_height, image_width, ray_random_seed, rows, true, alpha);
     const at::Tensor active = f.image({f.call.sc.B, image_height, image_width});
+    std::optional<Fragments> frag;
+    if (fragments > 0) frag.emplace(f, fragments, image_height, image_width, DMR_BUF_TET_FRAGMENTS, DMR_FLAG_TET_FRAGMENTS);
     int rendered = 0;
     if (g_abi.tet_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), mptr<float>(active), &alloc_cb, &f.call.scratch, f.call.stream(),
                           &rendered))
         raise_lib();
-    return f.result(f.color, f.depth, active);
+    return std::tuple_cat(f.result(f.color, f.depth, active),
+                          frag ? std::make_tuple(frag->face, frag->bary, frag->count) : std::make_tuple(at::Tensor(), at::Tensor(), at::Tensor()));
 }
 
 // ---- the gradient set of a backward, stated once ------------------------------------------------------------------------
@@ -593,8 +604,20 @@ PYBIND11_MODULE(_C, m) {
     def("render_tris_backward", &render_tris_backward, py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"), py::arg("pointBuffer"),
         py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out, py::kw_only(), py::arg("exact_grads") = false,
         camera_grads, alpha, py::arg("fragment_grads") = py::none());
-    def("render_tets", &render_tets, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("image_height"), py::arg("image_width"),
-        py::arg("ray_random_seed"), rows, py::kw_only(), alpha, py::call_guard<py::gil_scoped_release>());
+    def("render_tets",
+        [](In bg, In verts, In faces, In vcolor, In fopacity, In mv, In proj, In inv_mv, In inv_proj, In vdepth, In fintense, In tets, In face_tets,
+           In tet_faces, int64_t H, int64_t W, int64_t seed, std::pair<int, int> band, bool with_alpha, int64_t fragments) {
+            TetFwdOut out;
+            {
+                py::gil_scoped_release nogil;
+                out = render_tets(bg, verts, faces, vcolor, fopacity, mv, proj, inv_mv, inv_proj, vdepth, fintense, tets, face_tets, tet_faces, H, W, seed, band,
+                                  with_alpha, fragments);
+            }
+            const py::tuple all = py::cast(out);
+            return fragments > 0 ? all : py::tuple(all[py::slice(0, 7, 1)]);
+        },
+        py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("image_height"), py::arg("image_width"), py::arg("ray_random_seed"), rows,
+        py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tets_backward", &render_tets_backward, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("grad_color"),
         py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out,
         py::kw_only(), py::arg("full_grads") = false, camera_grads, alpha);

@@ -1,21 +1,30 @@
-"""Shading from the tri renderer's per-pixel fragment lists (TriRenderer(return_fragments=K) / render_tri(...,
-return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,K,2,H,W], count [B,H,W])).
+"""Shading from either renderer's per-pixel fragment lists (TriRenderer / TetRenderer(return_fragments=K), render_tri /
+render_tet(..., return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,K,2,H,W], count [B,H,W])).
 
 Plain torch, differentiable, no kernels.  What is HELD CONSTANT by every function here -- it comes from the rasteriser as
 data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
   * their order (the tile's depth sort),
-  * the barycentrics (the clamped (u, v) of the pixel's ray on each face) -- UNLESS the renderer was made with
-    fragment_grads=True: frag.bary then requires grad, interpolate and composite (which only read it) pass the gradient on, and
-    the renderer's backward carries it to verts and, with camera_grads, to mv_mats / proj_mats (the exact derivative of the
-    clamped (u, v), the clamp region held fixed).  Positions, normals, texture coordinates or a depth shaded here then see
-    the geometry,
+  * the barycentrics (the (u, v) of the pixel's ray on each face: clamped to the face by the tri renderer, which blends every
+    face its coverage test accepts; UNCLAMPED from the tet renderer, whose march crosses a face in its interior by
+    construction) -- UNLESS the TRI renderer was made with fragment_grads=True: frag.bary then requires grad, interpolate and
+    composite (which only read it) pass the gradient on, and the renderer's backward carries it to verts and, with
+    camera_grads, to mv_mats / proj_mats (the exact derivative of the clamped (u, v), the clamp region held fixed).
+    Positions, normals, texture coordinates or a depth shaded here then see the geometry.  The tet renderer has no such
+    option: its barycentrics are always constants,
 exactly the constants of the renderer's own default gradients.  Gradients flow into what the caller passes: opacities,
 per-vertex attributes, per-face scales.  A pixel with count > K holds the first K of its faces only: what is computed for it
 is the truncated sum.
 
+The tet renderer's lists are in exact march order, front to back; a pixel whose march failed (active == False) has count 0
+and no fragments, and shades to the bare background like the renderer's own image.  interpolate(frag, faces, verts) is the
+hit point of every fragment.
+
 The renderer's own colour, for pixels with count <= K:
     color, T = composite(frag, faces, faces_opacity, verts_color, face_scale=faces_intense);  color + T * bg.view(1, 3, 1, 1)
+(and 1 - T its alpha).  The opacity-1 rule of the TET renderer is the one exception: behind a face of opacity 1 it goes on with
+T = T_EPS / 10 = 1e-5 where the product here gives 0 -- the march ends at such a face, so it is the list's last, and the
+renderer's colour and alpha differ from the lines above by 1e-5 bg and 1e-5 there.
 """
 from __future__ import annotations
 
@@ -49,7 +58,7 @@ def blend_weights(frag, faces_opacity: th.Tensor) -> th.Tensor:
 
 def interpolate(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
     """Per-vertex attributes vert_attrs [P,C] at every fragment, [B,K,C,H,W]: (1 - u - v) a_0 + u a_1 + v a_2 over the three
-    vertices of the slot's face (faces [F,3]), with the rasteriser's clamped (u, v); 0 in empty slots.
+    vertices of the slot's face (faces [F,3]), with the renderer's (u, v) (tri: clamped; tet: as hit); 0 in empty slots.
     Constants: the faces and the barycentrics.  Differentiable in vert_attrs -- and in frag.bary when the renderer's
     fragment_grads made it differentiable."""
     face = frag.pix_to_face
@@ -67,7 +76,8 @@ def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.T
               face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
     """Front-to-back blend of interpolated attributes: (sum_k w_k s_k a_k [B,C,H,W], T = prod_k (1 - o_k) [B,1,H,W]), a_k =
     interpolate(...), w_k = blend_weights(...), s_k = face_scale[b, face_k] (face_scale [B,F], e.g. faces_intense; None: 1).
-    T is what is left for a background: result + T * bg.  Constants: the faces, their order, the barycentrics.
+    T is what is left for a background: result + T * bg (the tet renderer keeps 1e-5 behind a face of opacity 1, see the
+    top).  Constants: the faces, their order, the barycentrics.
     Differentiable in faces_opacity, vert_attrs and face_scale (and in frag.bary with the renderer's fragment_grads)."""
     _, o = _opacity_slots(frag, faces_opacity)
     t = _transmittance(o)
@@ -83,7 +93,8 @@ def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.T
 
 def face_visibility(frag, faces_opacity: th.Tensor, F: int) -> th.Tensor:
     """Sum of the blend weights every face received over a view's pixels, [B,F] (one scatter_add): 0 for a face no pixel
-    blended -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.  Constants: the faces and their order.
+    blended (tet: no ray composited) -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.  Constants: the
+    faces and their order.
     Differentiable in faces_opacity."""
     w = blend_weights(frag, faces_opacity)
     B = w.shape[0]

@@ -432,9 +432,13 @@ class ShardedTetRenderer(_Banded, TetRenderer):
     its band only, back-propagates them, and joins ONE all-reduce over [dL_dverts_color 3P | dL_dfaces_opacity F]
     (full_grads: followed by [dL_dverts 3P | dL_dfaces_intense B*F], camera_grads: then by the 64 B matrix gradients,
     see TetRenderer).
-    Same call signature and outputs as TetRenderer (color, depth, active bool; with return_alpha also alpha)."""
+    Same call signature and outputs as TetRenderer (color, depth, active bool; with return_alpha also alpha).
+    TetRenderer's return_fragments is NOT available here, as ShardedTriRenderer's is not: the per-pixel fragment lists are
+    a single-device output so far (ValueError)."""
 
     def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
-                 full_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False):
+                 full_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False, return_fragments: int = 0):
+        if return_fragments:
+            raise ValueError("return_fragments is not available on the sharded Modules")
         super().__init__(render_settings, group, assemble, impl, full_grads=full_grads, camera_grads=camera_grads,
                          return_alpha=return_alpha)

@@ -45,7 +45,8 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
        DMR_BUF_TET_CAMERA_GRADS = 7 /* dmr_tet_backward with DMR_FLAG_TET_CAMERA_GRADS: an OUTPUT, see there */,
        DMR_BUF_TRI_FRAGMENTS = 8 /* dmr_tri_forward with DMR_FLAG_TRI_FRAGMENTS: an OUTPUT, see the flag */,
        DMR_BUF_TRI_FRAGMENT_FACES = 9 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */,
-       DMR_BUF_TRI_FRAGMENT_BARY_GRADS = 10 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */ };
+       DMR_BUF_TRI_FRAGMENT_BARY_GRADS = 10 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */,
+       DMR_BUF_TET_FRAGMENTS = 11 /* dmr_tet_forward with DMR_FLAG_TET_FRAGMENTS: an OUTPUT, see the flag */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -55,13 +56,17 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * tile's first chunk has the slot of the tile's rank among the busy tiles, so a sparse frame of 1 M tiles pays for its list
  * entries, not 4 GiB for its tiles; the reference's binning buffer scales with R only) -- plus, tet only, the forward's march sequence for
  * the backward: 4 bytes per tile pixel (256 Nt of them) and step of capacity, capacity = the longest march of the previous
- * call with the same view configuration * 1.25 + 4 steps (0 in the first such call), the whole capped at 16 GiB;
+ * call with the same view configuration * 1.25 + 4 steps (0 in the first such call), the whole capped at 16 GiB -- with
+ * DMR_FLAG_TET_FRAGMENTS at least K rounded up to a multiple of 4 steps, so such a call owns a larger binning buffer than one
+ * without the flag only while 1.25 * longest + 4 < K (always in the first call of a view configuration); a K whose steps alone
+ * exceed the 16 GiB (about 134 M tile pixels at K = 32) is an error;
  * work (tri backward) 32 BP + 8 BF + 8192 Nt + 16 per hit record (+ 128 Nt with DMR_FLAG_TRI_CAMERA_GRADS); tri camera grads
  * (tri backward with DMR_FLAG_TRI_CAMERA_GRADS only) 128 B, exactly; tet grads (tet backward with DMR_FLAG_TET_FULL_GRADS or
  * DMR_FLAG_TET_CAMERA_GRADS only) 4 (3P + BF), exactly; work (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 per tile of
  * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly; tri fragments (tri
  * forward with DMR_FLAG_TRI_FRAGMENTS only) 4 BWH (3K + 1), exactly; tri fragment faces and tri fragment bary grads (tri
- * backward with DMR_FLAG_TRI_FRAGMENT_GRADS only; inputs) 4 BKWH and 8 BKWH, exactly. */
+ * backward with DMR_FLAG_TRI_FRAGMENT_GRADS only; inputs) 4 BKWH and 8 BKWH, exactly; tet fragments (tet forward with
+ * DMR_FLAG_TET_FRAGMENTS only) 4 BWH (3K + 1), exactly. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -156,7 +161,7 @@ typedef struct dmr_scene {
  * caller initialises the buffer (face -1, the rest 0) where that can happen, as it does for the images.  The values describe
  * the colour the call returns (after a redo, the redo's).  The images, the four scratch buffers and the backward are exactly
  * those of a call without the flag; no host wait is added (DMR_FLAG_ASYNC and stream capture work as before).  The tet
- * renderer has no such output. */
+ * renderer's: DMR_FLAG_TET_FRAGMENTS. */
 #define DMR_FLAG_TRI_FRAGMENTS 64
 /* dmr_tri_backward only (ignored by every other call): the gradient of the fragment lists' barycentrics reaches the vertex
  * positions and, with DMR_FLAG_TRI_CAMERA_GRADS, the inverse matrices.  K travels in bits 8-15 of the flags as for the forward
@@ -178,6 +183,33 @@ typedef struct dmr_scene {
 #define DMR_FLAG_TRI_FRAGMENT_GRADS 128
 #define DMR_FRAGMENTS_K(flags) (((flags) >> 8) & 255)
 #define DMR_FRAGMENTS_FLAGS(k) (DMR_FLAG_TRI_FRAGMENTS | (((k) & 255) << 8))
+/* dmr_tet_forward only (ignored by every other call, as the tet calls ignore DMR_FLAG_TRI_FRAGMENTS): the tet renderer's
+ * per-pixel fragment lists, in exact march order.  The bit lies outside bits 8-15, which carry K exactly as for the tri flag:
+ * flags |= DMR_TET_FRAGMENTS_FLAGS(K), K in 1..32, read back with DMR_FRAGMENTS_K (the flag with K = 0 or K > 32 is an error,
+ * raised before anything is allocated or launched).  The call then requests buffer DMR_BUF_TET_FRAGMENTS through `alloc`,
+ * once, of exactly 4 BWH (3K + 1) bytes (not at all when P == 0 or F == 0, where nothing marches), and one more kernel behind
+ * the march fills, for every pixel of the rendered tile rows,
+ *   face  int32 [B,K,H,W]    the faces the pixel's march composited, in march order (front to back), -1 in unused slots;
+ *   bary  fp32  [B,K,2,H,W]  the (u, v) of the pixel's ray on that face (Moeller-Trumbore, as the march evaluates it) --
+ *                            weights (1 - u - v, u, v) for the face's three vertices --, UNCLAMPED: a face the march crosses
+ *                            is hit in its interior by construction; 0 in unused slots;
+ *   count int32 [B,H,W]      the pixel's number of march steps (n_contrib) where the march reached a valid end (out_active
+ *                            == 1), 0 elsewhere; it may exceed K: the faces beyond K are counted, not stored;
+ * back to back in that order.  A pixel whose march fails after some steps returns the bare background and has NO fragments.
+ * Every counted face k was blended with weight T_k o_k, T_k the transmittance in front of it: T_0 = 1, T_{k+1} = T_k (1 - o_k)
+ * -- with ONE exception: behind a face of opacity 1 the renderer goes on with T = T_EPS / 10 = 1e-5, not 0 (the march ends
+ * there, since T < T_EPS: such a face is the pixel's last, and T_EPS / 10 is what multiplies the background).  The pixel's
+ * colour is sum_k T_k o_k c_k + T bg when count <= K.  Pixels outside the rendered tile rows are untouched, and nothing is
+ * written when P == 0 or F == 0: the caller initialises the buffer (face -1, the rest 0) where that can happen, as it does
+ * for the images.  The values describe the images the call returns (after a redo, the redo's).  The kernel reads the first K
+ * entries of the march sequence the forward leaves for the backward, so the call sizes that sequence to at least K rounded up
+ * to a multiple of 4 steps (see the footprints: the binning buffer may be larger than without the flag, in the first call of a
+ * view configuration above all; a K whose sequence alone exceeds 16 GiB fails before anything is launched).  The images, the
+ * other three scratch buffers, the backward -- which decides on the device whether the sequence is complete, as before -- and
+ * the estimate left for the next call are exactly those of a call without the flag; no host wait is added (DMR_FLAG_ASYNC and
+ * stream capture work as before).  The barycentrics carry no gradient. */
+#define DMR_FLAG_TET_FRAGMENTS (1 << 16)
+#define DMR_TET_FRAGMENTS_FLAGS(k) (DMR_FLAG_TET_FRAGMENTS | (((k) & 255) << 8))
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -216,7 +248,8 @@ int dmr_tri_backward(const dmr_scene* scene, const float* dL_dcolor, const float
 
 /* out_active [B,H,W]: 1.0 where the ray marched to a valid end, else 0.0.  Like the tri forward, every pixel of the
  * rendered tile rows of all three outputs is written (background / 1 / 0 where the march fails).  With DMR_FLAG_ALPHA
- * out_depth is [B,2,H,W] (depth | alpha; alpha 0 where the march fails). */
+ * out_depth is [B,2,H,W] (depth | alpha; alpha 0 where the march fails).
+ * With DMR_FLAG_TET_FRAGMENTS also the fragment lists, in a buffer requested through `alloc` (see the flag). */
 int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, float* out_active,
                     dmr_alloc_fn alloc, void* alloc_ctx, void* stream, int* num_rendered);
 
