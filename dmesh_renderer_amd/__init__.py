@@ -86,7 +86,8 @@ class Fragments(NamedTuple):
     pixel blended, front to back, and where its ray hit them.  Constants of every gradient, like coverage and list order --
     unless the TRI renderer was made with fragment_grads=True: `bary` then takes part in autograd (its gradient reaches verts
     and, with camera_grads, the matrices); pix_to_face and count stay constants.  The tet renderer's lists are in exact march
-    order, their barycentrics unclamped (a face the march crosses is hit in its interior), and always constants."""
+    order, their barycentrics unclamped (a face the march crosses is hit in its interior); TetRenderer(fragment_grads=True)
+    makes its `bary` differentiable in the same way (there is no clamp, so no clamp region; the option implies full_grads)."""
     pix_to_face: th.Tensor  # int32 [B,K,H,W]: face ids in blend order, -1 in unused slots
     bary: th.Tensor         # float32 [B,K,2,H,W]: (u, v), clamped by the tri renderer; the weights of the face's vertices are (1 - u - v, u, v)
     count: th.Tensor        # int32 [B,H,W]: blended faces of the pixel (tet: 0 where the march failed); above K the list is truncated to its first K
@@ -208,7 +209,7 @@ def _input_grads(ctx, gs: _GradSet, level: int, g, inv_mv, inv_proj) -> tuple:
 
 def _backward(ctx, gs: _GradSet, *upstream, extra_saved=0, **more) -> tuple:
     """The backward of _TriFn / _TetFn: one _one_backward at ctx's level, the all-reduce of a sharded Module, the gradients of
-    apply's eight tensors.  more: further keywords of the call (_TriFn's fragment_grads) whose terms the library adds into
+    apply's eight tensors.  more: further keywords of the call (fragment_grads of either Function) whose terms the library adds into
     pieces of the level's gradient set: nothing new in the tuple.  extra_saved: tensors the Function saved behind _forward's."""
     saved = ctx.saved_tensors
     geom, saved = saved[:4], saved[4:len(saved) - extra_saved]
@@ -280,16 +281,24 @@ class _TriFn(th.autograd.Function):
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
     faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha: as for _TriFn.
-    fragments = K > 0 (one device only; the last argument, only when set: see _trailing): three more outputs, the
-    non-differentiable face [B,K,H,W], bary [B,K,2,H,W] and count [B,H,W] of render_tets(fragments=K)."""
+    fragments = K > 0 (one device only; only when set: see _trailing): three more outputs, the non-differentiable face
+    [B,K,H,W], bary [B,K,2,H,W] and count [B,H,W] of render_tets(fragments=K).  fragment_grads (the last argument; needs
+    fragments; implies full_grads, where dL/dverts exists): as _TriFn's -- bary is differentiable, the gradient that arrives for
+    it goes down with the backward call (fragment_grads=(face, grad_bary)), where the library adds its term to the verts piece
+    and, at level 2, to the inverse matrices' part of the camera piece: the gradient set (_TET_GRADS) is unchanged.  Gradients
+    are then not materialised: a backward without one for bary is the full_grads call."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False,
-                alpha=False, fragments=0):
+                alpha=False, fragments=0, fragment_grads=False):
         geom = (verts, faces, verts_color, faces_opacity)
+        if fragment_grads and shard is not None:
+            raise ValueError("fragment_grads is not available on the sharded Modules")
         if fragments and shard is not None:
             raise ValueError("return_fragments is not available on the sharded Modules")
+        if fragment_grads and not fragments:
+            raise ValueError("fragment_grads needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
         (color, depth, active, *frag), saved = _forward(_impl(shard).render_tets, settings, geom, mv_mats, proj_mats, verts_depth,
                                                         faces_intense, rows, alpha, (tets, face_tets, tet_faces),
                                                         **({"fragments": fragments} if fragments else {}))
@@ -297,19 +306,46 @@ class _TetFn(th.autograd.Function):
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
         ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
-        ctx.more_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads, camera_grads, alpha
-        ctx.save_for_backward(*geom, *saved)
-        ctx.mark_non_differentiable(active, *frag)
+        ctx.more_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads or bool(fragment_grads), camera_grads, alpha
+        ctx.fragment_grads = bool(fragment_grads)
+        if fragment_grads:  # bary is differentiable: face is what the backward needs of the lists
+            ctx.save_for_backward(*geom, *saved, frag[0])
+            ctx.mark_non_differentiable(active, frag[0], frag[2])
+            ctx.set_materialize_grads(False)  # no zeros for the outputs a loss does not use: a None for bary is the call without the term
+            ctx.image_shapes = (color.shape, depth.shape)
+        else:
+            ctx.save_for_backward(*geom, *saved)
+            ctx.mark_non_differentiable(active, *frag)
         return (color, depth, active, *frag)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth, _grad_active, *_grad_fragments):
-        return _backward(ctx, _TET_GRADS, grad_color, grad_depth) + (None,) * 10
+    def backward(ctx, grad_color, grad_depth, _grad_active, *grad_fragments):
+        more = {}
+        if ctx.fragment_grads:
+            more["extra_saved"] = 1  # (face)
+            if grad_color is None:
+                grad_color = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[0])
+            if grad_depth is None:
+                grad_depth = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[1])
+            if grad_fragments[1] is not None:
+                more["fragment_grads"] = (ctx.saved_tensors[-1], grad_fragments[1].contiguous())
+        return _backward(ctx, _TET_GRADS, grad_color, grad_depth, **more) + (None,) * 11
 
 
 def _check_fragment_grads(fragment_grads, return_fragments):
     if fragment_grads and not return_fragments:
         raise ValueError("fragment_grads=True needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
+
+
+def _check_tet_fragment_grads(fragment_grads, return_fragments):
+    """_check_fragment_grads, and: the binding in use must know render_tets_backward's fragment_grads keyword.  The binding is
+    a build product of its own (build.py rebuilds it by file times): one from before the keyword, or a stand-in without it,
+    would fail with pybind's argument dump in the first backward that carries a gradient for bary -- deep inside autograd.
+    Asked at construction instead, a TypeError that says what is missing."""
+    _check_fragment_grads(fragment_grads, return_fragments)
+    if fragment_grads and not getattr(_C, "SUPPORTS_TET_FRAGMENT_GRADS", False):
+        raise TypeError("fragment_grads=True: the loaded binding's render_tets_backward has no fragment_grads keyword "
+                        "(a `_C` built before it: rebuild with `python -m dmesh_renderer_amd.build --force`)")
 
 
 def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
@@ -329,12 +365,14 @@ def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                tets, face_tets, tet_faces, render_settings: TetRenderSettings, rows=(0, 0), full_grads=False, camera_grads=False,
-               return_alpha=False, return_fragments=0):
+               return_alpha=False, return_fragments=0, fragment_grads=False):
     """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads,
-    camera_grads, return_alpha, return_fragments: see TetRenderer."""
+    camera_grads, return_alpha, return_fragments, fragment_grads: see TetRenderer."""
+    _check_tet_fragment_grads(fragment_grads, return_fragments)
     out = _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                        tets, face_tets, tet_faces, render_settings, tuple(rows),
-                       *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha), int(return_fragments)))
+                       *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha), int(return_fragments),
+                                  bool(fragment_grads)))
     if return_fragments:
         return _split_fragments(out, return_alpha)
     return _split_alpha(out) if return_alpha else out
@@ -440,8 +478,22 @@ class TetRenderer(th.nn.Module):
     dmesh_renderer_amd.fragments shades from them -- normals, positions (interpolate(frag, faces, verts) is the hit point),
     feature channels, texture coordinates, per-face visibility -- in plain torch: composite(...) + T * bg is this renderer's
     colour where count <= K, except that behind a face of opacity 1 the renderer goes on with T = 1e-5 (T_EPS / 10), not 0.
-    The three tensors are constants (no gradient flows into them; there is no fragment_grads here); the images and the
+    The three tensors are constants (no gradient flows into them) unless fragment_grads is set; the images and the
     backward are those of a call without the option.  One device only: the sharded Modules do not take it.
+
+    fragment_grads=True (only with return_fragments=K; IMPLIES full_grads, the level at which this renderer has a gradient
+    for verts at all: with the option the images' own gradient reaches verts and faces_intense as well): Fragments.bary
+    takes part in autograd.  The gradient a loss sends into it -- through fragments.interpolate / composite, or any torch
+    code that reads bary -- reaches verts as the exact derivative of the unclamped Moeller-Trumbore (u, v) of each stored
+    (pixel, face) pair on the pixel's ray, and with camera_grads (when a matrix needs a gradient) mv_mats and proj_mats
+    through that ray (origin and direction come from the inverse matrices; (u, v) do not read the matrices themselves).
+    So the gradient of fragments.interpolate(frag, faces, verts) to verts is the full derivative of the hit point, the
+    direct term through the vertex rows plus the movement of (u, v).  Which faces the march crossed, their order and the
+    seeded jitter are constants; there is no clamp and so no clamp region; pix_to_face and count stay non-differentiable;
+    pairs beyond K are not stored and get nothing.  One more kernel in the backward when a gradient for bary arrives
+    (INTEGRATION.md); the forward is unchanged, and a backward without one is the full_grads call.  A binding that does not
+    announce render_tets_backward's fragment_grads keyword (_C.SUPPORTS_TET_FRAGMENT_GRADS: a stale build of `_C`, or a
+    stand-in for it) is a TypeError here, at construction, not in the first backward that would use it.
 
     forward(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
             tets [T,4], face_tets [F,2] (-1 = none), tet_faces [T,4])
@@ -450,13 +502,15 @@ class TetRenderer(th.nn.Module):
     """
 
     def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False,
-                 return_alpha: bool = False, return_fragments: int = 0):
+                 return_alpha: bool = False, return_fragments: int = 0, fragment_grads: bool = False):
         super().__init__()
+        _check_tet_fragment_grads(fragment_grads, return_fragments)
         self.render_settings = render_settings
         self.full_grads = bool(full_grads)
         self.camera_grads = bool(camera_grads)
         self.return_alpha = bool(return_alpha)
         self.return_fragments = int(return_fragments)
+        self.fragment_grads = bool(fragment_grads)
 
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces):
@@ -466,7 +520,8 @@ class TetRenderer(th.nn.Module):
                            mv_mats.to(**f32).transpose(1, 2), proj_mats.to(**f32).transpose(1, 2),
                            verts_depth.to(**f32), faces_intense.to(**f32),
                            tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
-                           rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha, self.return_fragments))
+                           rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha, self.return_fragments,
+                                            self.fragment_grads))
         if self.return_fragments:
             return _split_fragments(out, self.return_alpha)
         return _split_alpha(out) if self.return_alpha else out

@@ -779,6 +779,10 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     Dims d;
     if (check_scene(s, true, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // DMR_FLAG_TET_FRAGMENT_GRADS (implies the full gradients): K slots per pixel in bits 8-15 of the flags, as for the forward
+    const int frag_k = (s->flags & DMR_FLAG_TET_FRAGMENT_GRADS) ? DMR_FRAGMENTS_K(s->flags) : 0;
+    if ((s->flags & DMR_FLAG_TET_FRAGMENT_GRADS) && (frag_k < 1 || frag_k > 32))
+        return fail("DMR_FLAG_TET_FRAGMENT_GRADS: K (bits 8-15 of flags, DMR_FRAGMENTS_K) must be in 1..32, got " + std::to_string(frag_k));
     // DMR_FLAG_TET_CAMERA_GRADS (implies the full gradients): the caller's [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 |
     // dL/dproj 16] buffer, requested once, summed from per-tile partials in the work space
     const bool camera = (s->flags & DMR_FLAG_TET_CAMERA_GRADS) != 0;
@@ -790,13 +794,23 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
                       s->P == 0 || s->F == 0 || band_tiles == 0, st, &cam_out))
         return 1;
     float* full = nullptr;  // DMR_FLAG_TET_FULL_GRADS: [dL_dverts 3P | dL_dfintense BF], zeroed by the launch that follows
-    const bool full_grads = (s->flags & (DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS)) != 0;
+    const bool full_grads = (s->flags & (DMR_FLAG_TET_FULL_GRADS | DMR_FLAG_TET_CAMERA_GRADS | DMR_FLAG_TET_FRAGMENT_GRADS)) != 0;
     if (caller_output(alloc, ctx, DMR_BUF_TET_GRADS, full_grads ? sizeof(float) * (3 * (size_t)s->P + d.BF) : 0, "tet gradient", false, st, &full))
         return 1;
     if (full) dmr::launch_tet_zero_grads(full, 3 * (int64_t)s->P, full + 3 * (int64_t)s->P, (int64_t)d.BF, st);
     dmr::launch_tet_zero_grads(dL_dvcolor, 3 * (int64_t)s->P, dL_dfopacity, (int64_t)s->F, st);
     if (s->P == 0 || s->F == 0) return 0;
     if (!image_buf || !face_buf) return fail("null scratch buffer");
+    // the caller's two inputs, requested once each (not for an empty band: the term is zero then)
+    const int32_t* frag_face = nullptr;
+    const float* frag_grad = nullptr;
+    if (frag_k && band_tiles > 0) {
+        if (!alloc) return fail("null argument");
+        frag_face = static_cast<const int32_t*>(alloc(ctx, DMR_BUF_TET_FRAGMENT_FACES, 4 * d.npix * (size_t)frag_k));
+        if (!frag_face) return fail("DMR_FLAG_TET_FRAGMENT_GRADS: no tet fragment face buffer (DMR_BUF_TET_FRAGMENT_FACES)");
+        frag_grad = static_cast<const float*>(alloc(ctx, DMR_BUF_TET_FRAGMENT_BARY_GRADS, 8 * d.npix * (size_t)frag_k));
+        if (!frag_grad) return fail("DMR_FLAG_TET_FRAGMENT_GRADS: no tet fragment bary gradient buffer (DMR_BUF_TET_FRAGMENT_BARY_GRADS)");
+    }
     float* cam_part = nullptr;  // every tile's partial (launch_tet_backward)
     if (cam_out) {
         cam_part = static_cast<float*>(alloc(ctx, DMR_BUF_WORK, 256 * (size_t)band_tiles * (size_t)s->B));
@@ -809,6 +823,8 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     uint32_t* host_seq_steps = march_estimate(size_key(s, true, d), d, false);
     dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
                              full, full ? full + 3 * (int64_t)s->P : nullptr, cam_part, (s->flags & DMR_FLAG_ALPHA) != 0);
+    // the fragment lists' term joins dL_dverts (and the tiles' camera partials) before the partials are reduced
+    if (frag_face) dmr::launch_tet_fragment_grads(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), frag_k, frag_face, frag_grad, full, cam_part, st);
     if (cam_out) dmr::launch_camera_reduce(s->B, band_tiles, 64, cam_part, cam_out, st);
     DMR_HIP(hipGetLastError());
     return 0;

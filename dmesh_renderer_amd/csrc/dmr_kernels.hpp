@@ -270,5 +270,13 @@ void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, Tet
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
                          uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts = nullptr, float* dL_dfintense = nullptr,
                          float* cam_part = nullptr, bool alpha = false);
+// DMR_FLAG_TET_FRAGMENT_GRADS, behind launch_tet_backward (which zeroed and filled dL_dverts and stored every band tile's cam_part)
+// and ahead of launch_camera_reduce: for every pixel of the band and each of its K slots, dL/d(u, v) (frag_grad, f32
+// [B,K,2,H,W]) of the pair (pixel, frag_face[slot], i32 [B,K,H,W]) through the exact derivative of the pair's unclamped (u, v) on
+// the forward's ray, added into dL_dverts [P,3] and, cam_part != null, into the first 32 floats (dL/dinv_mv | dL/dinv_proj) of
+// every tile's 64-float camera partial.  A face outside [0, F) is no pair.  Reads the scene, the face records and the seed the
+// forward left, the contract-layout inverse matrices and the two inputs only.  K in 1..32.  No stage of its own, no size, no host wait.
+void launch_tet_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, const int32_t* frag_face,
+                               const float* frag_grad, float* dL_dverts, float* cam_part, hipStream_t st);
 
 }  // namespace dmr

@@ -1260,6 +1260,199 @@ k_tet_fragments(TetParams p, int K, int32_t* __restrict__ out_face, float* __res
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_tet_fragment_grads (DMR_FLAG_TET_FRAGMENT_GRADS) -- dL/d(u, v) of the caller's fragment lists -> vertex positions (and rays).
+//
+// A launch of its own behind the call's two backward launches (which zeroed and filled dL_dverts and stored every band tile's
+// cam_part) and ahead of launch_camera_reduce.  k_tet_fragments' grid and pixel-to-lane mapping: one workgroup per tile of the
+// band, an 8 x 8 pixel block per wave, so neighbouring lanes mostly hold the same face in the same slot.  A lane owns its
+// pixel: it builds the forward's ray once (pixel_ray<true>, the seed out of the image state) and, for each of the K slots,
+// takes the face's three vertices from its record (the next slot's id, record and upstream in flight while this one computes, two
+// sets used alternately as k_tet_fragments does), recomputes denom, nu, nv with ray_tri_hit's operations and forms dp0, dp1, dp2,
+// dT and dL/dd with the formulas of k_tri_fragment_grads' EXACT branch (dmr_tri.hip) -- the upstream enters directly: (u, v)
+// is unclamped.  It reads nothing of the march (no sequence, no n_contrib, no is_active): the pairs are the caller's; a face
+// outside [0, F), an upstream of (0, 0) and denom == 0 are no pair.
+// The nine position values of a pair are merged across the lanes that hold the same face (tet_accumulate's four DPP levels,
+// under this kernel's own use of them: a face uniform over the wave reaches LDS from 4 lanes, not 64), then summed per face in
+// a table of this kernel's own (TetAccum's probing, 9 f64 cells a slot: 33.6 KB) and leave once per tile into dL_dverts with
+// float atomics; a full table, a long probe sequence or a non-finite value goes out directly.  Camera variant: sum dT (= dL/do)
+// and sum dL/dd stay in the lane's registers over the slots, then one chain per pixel through d = w / max(|w|, 1e-4) -- the
+// arithmetic of tet_camera_tile with go, gd set and the four depth sums zero --, a block sum, and the tile's first 32 floats of
+// cam_part (dL/dinv_mv | dL/dinv_proj; the direct dL/dmv | dL/dproj half has no such term) gain it: this workgroup is their one
+// writer behind the backward.  A tile without a contributing pair neither flushes nor touches cam_part.
+// ---------------------------------------------------------------------------
+constexpr int TET_FRAG_TBL = 448;  // slots (a multiple of 16: the flush covers 16 per pass)
+struct TetFragGradLds {
+    double val[9][TET_FRAG_TBL];   // dp0 xyz, dp1 xyz, dp2 xyz of a face
+    int key[TET_FRAG_TBL];
+    float red[4][24];              // (camera variant) per-wave sums
+    int any;
+};
+
+template <bool CAM>
+__global__ void __launch_bounds__(256)
+k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, const float* __restrict__ frag_grad,
+                     float* __restrict__ dL_dverts, float* __restrict__ cam_part) {
+    __shared__ TetFragGradLds L;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
+    const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
+    const bool inside = px < p.W && py < p.H;
+    const int64_t HW = (int64_t)p.H * p.W, pix_id = (int64_t)p.W * py + px, bpix = (int64_t)b * HW + pix_id;
+    const int64_t face0 = (int64_t)b * K * HW + pix_id, grad0 = (int64_t)b * K * 2 * HW + pix_id;
+    // slot k of this lane: the face (-1: no pair -- outside the image, beyond K, or an id that is not a face's) ...
+    auto load_face = [&](int k) -> int {
+        if (!inside || k >= K) return -1;
+        const int f = frag_face[face0 + (int64_t)k * HW];
+        return (uint32_t)f < (uint32_t)p.F ? f : -1;
+    };
+    // ... and what its gradient needs: the three vertices and the upstream
+    struct Rec { float4 f0, f1, f2; float e1, e2; };
+    auto load_rec = [&](int k, int face, Rec& r) {
+        if (face < 0) return;
+        const float4* fq = reinterpret_cast<const float4*>(p.facerec + face);
+        r.f0 = fq[0]; r.f1 = fq[1]; r.f2 = fq[2];
+        r.e1 = frag_grad[grad0 + (int64_t)(2 * k) * HW]; r.e2 = frag_grad[grad0 + (int64_t)(2 * k + 1) * HW];
+    };
+    int f_cur = load_face(0), f_nxt = load_face(1);  // (requested before the table is cleared)
+    Rec rc = {}, rn = {};
+    load_rec(0, f_cur, rc);
+    for (int i = tid; i < TET_FRAG_TBL; i += 256) {
+        L.key[i] = -1;
+#pragma unroll
+        for (int c = 0; c < 9; c++) L.val[c][i] = 0.0;
+    }
+    if (tid == 0) L.any = 0;
+    V3 ro = {0, 0, 0}, rd = {0, 0, 0};
+    if (inside) pixel_ray<true>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd, *p.seed, (uint64_t)bpix);
+    V3 camT = {0.f, 0.f, 0.f}, camD = {0.f, 0.f, 0.f};  // camera variant: sum of dL/dT (= dL/do), dL/d(ray direction) of this pixel
+    bool some = false;
+    const TetAccum<TET_FRAG_TBL> acc{L.key, L.val};
+    __syncthreads();
+    // slot k from `cur` while slot k + 1's record and slot k + 2's id arrive; ALL lanes of the wave take part (the merge)
+    auto one = [&](int k, const Rec& cur, Rec& nxt) {
+        load_rec(k + 1, f_nxt, nxt);
+        const int f_nn = load_face(k + 2);
+        const int face = f_cur;
+        float g[10];
+#pragma unroll
+        for (int c = 0; c < 10; c++) g[c] = 0.f;
+        bool act = face >= 0 && !(cur.e1 == 0.f && cur.e2 == 0.f);  // nothing arrives for a pair with a zero upstream
+        if (act) {
+            const V3 p0 = {cur.f0.x, cur.f0.y, cur.f0.z}, p1 = {cur.f0.w, cur.f1.x, cur.f1.y}, p2 = {cur.f1.z, cur.f1.w, cur.f2.x};
+            // ray_tri_hit's operations (dmr_device.hpp); its u = nu * inv_denom, v = nv * inv_denom
+            const V3 xT = ro - p0, xE1 = p1 - p0, xE2 = p2 - p0;
+            const V3 xP = cross(rd, xE2), xQ = cross(xT, xE1);
+            const float denom = dot(xP, xE1);
+            if (denom == 0.0f) act = false;  // ray_tri_hit has no (u, v) for such a pair
+            else {
+                const float inv_denom = 1.0f / denom;
+                const float nu = dot(xP, xT), nv = dot(xQ, rd);
+                // the exact derivative of (u, v) = ((d x E2) . T, (T x E1) . d) / ((d x E2) . E1) (k_tri_fragment_grads, EXACT)
+                const float su = cur.e1 * inv_denom, sv = cur.e2 * inv_denom;
+                const float sb = (su * nu + sv * nv) * inv_denom;
+                const V3 xE1d = cross(xE1, rd);
+                const V3 dT = su * xP + sv * xE1d;
+                const V3 dp1 = sv * cross(rd, xT) - sb * xP;
+                const V3 dp2 = su * cross(xT, rd) - sb * xE1d;
+                const V3 dp0 = -(dT + dp1 + dp2);
+                if constexpr (CAM) {
+                    camD = camD + (su * cross(xE2, xT) + sv * xQ + sb * cross(xE1, xE2));  // dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)
+                    camT = camT + dT;
+                }
+                some = true;
+                g[0] = dp0.x; g[1] = dp0.y; g[2] = dp0.z; g[3] = dp1.x; g[4] = dp1.y; g[5] = dp1.z; g[6] = dp2.x; g[7] = dp2.y; g[8] = dp2.z;
+                // a lane with a non-finite value adds its rows directly and takes no part in the merges (0 * inf would leak into
+                // the partner's face)
+                float chk = 0.f;
+#pragma unroll
+                for (int c = 0; c < 9; c++) chk = fmaf(g[c], 0.f, chk);
+                if (!(chk == 0.f)) {
+#pragma unroll
+                    for (int c = 0; c < 9; c++) { atomicAdd(&dL_dverts[3 * p.faces[3 * face + c / 3] + c % 3], g[c]); g[c] = 0.f; }
+                    act = false;
+                }
+            }
+        }
+        int key = act ? face : -1;  // -1: nothing (left) in this lane
+        tet_merge_level<0>(lane, key, g);
+        tet_merge_level<1>(lane, key, g);
+        tet_merge_level<2>(lane, key, g);
+        tet_merge_level<3>(lane, key, g);
+        if (key >= 0) {
+            const int slot = acc.find(face);
+            if (slot >= 0) {
+#pragma unroll
+                for (int c = 0; c < 9; c++) atomicAdd(&L.val[c][slot], (double)g[c]);
+            } else {  // the table is full (or a long probe sequence): these rows go out directly
+#pragma unroll
+                for (int c = 0; c < 9; c++) atomicAdd(&dL_dverts[3 * p.faces[3 * face + c / 3] + c % 3], g[c]);
+            }
+        }
+        f_cur = f_nxt; f_nxt = f_nn;
+    };
+    for (int k = 0; k < K; k += 2) {  // (K is uniform: every lane runs every slot)
+        one(k, rc, rn);
+        if (k + 1 < K) one(k + 1, rn, rc);
+    }
+    if (some) L.any = 1;  // (every writer stores the same value)
+    __syncthreads();
+    if (!L.any) return;  // uniform
+    if constexpr (CAM) {
+        // this lane's pixel: dL/dd through d = w / max(|w|, 1e-4), w = inv_mv (pv, 1) - o, pv = inv_proj (ndc, -1, 1) (pixel_ray<true>)
+        // to the view's two inverse matrices, as tet_camera_tile does.  c[3 col + row]: dL/dinv_mv rows 0-2 (col 3 = dL/do),
+        // c[12 + 3 col + row]: dL/dinv_proj rows 0-2; the w rows get nothing.
+        float c[24];
+#pragma unroll
+        for (int i = 0; i < 24; i++) c[i] = 0.f;
+        if (some) {  // (inside)
+            const float* im = p.inv_mv + 16 * b;
+            const float* ip = p.inv_proj + 16 * b;
+            const V2 nd = pixel_ndc<true>(px, py, p.W, p.H, *p.seed, (uint64_t)bpix);
+            const float ndc[4] = {nd.x, nd.y, -1.0f, 1.0f};
+            const V4 pv = xform4x4({nd.x, nd.y, -1.0f}, ip);
+            const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
+            const V3 w = V3{pw.x, pw.y, pw.z} - V3{im[12], im[13], im[14]};
+            const float n = sqrtf(dot(w, w)), len = fmaxf(n, 0.0001f);
+            // dL/dw = gd / len - w (w . gd) / n^3 where the length is not clamped
+            const float kk = n > 0.0001f ? (w.x * camD.x + w.y * camD.y + w.z * camD.z) / (n * n * n) : 0.f;
+            const float dw[3] = {camD.x / len - kk * w.x, camD.y / len - kk * w.y, camD.z / len - kk * w.z};
+            const float pvv[3] = {pv.x, pv.y, pv.z};
+#pragma unroll
+            for (int row = 0; row < 3; row++) {
+#pragma unroll
+                for (int col = 0; col < 3; col++) c[3 * col + row] = dw[row] * pvv[col];
+                const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];  // (R^T dL/dw)_row
+#pragma unroll
+                for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
+            }
+            c[9] = camT.x; c[10] = camT.y; c[11] = camT.z;
+        }
+#pragma unroll
+        for (int i = 0; i < 24; i++)
+#pragma unroll
+            for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 24; i++) L.red[wave][i] = c[i];
+        }
+        __syncthreads();
+        if (tid < 32) {  // entry tid of the tile's partial, m[4 col + row] of inv_mv (tid < 16) / inv_proj
+            const int row = tid & 3, col = (tid >> 2) & 3, i = 12 * (tid >> 4) + 3 * col + row;
+            const int64_t tile = ((int64_t)b * gridDim.y + blockIdx.y) * p.gx + tx;  // launch_tet_backward's
+            if (row != 3) cam_part[64 * tile + tid] += L.red[0][i] + L.red[1][i] + L.red[2][i] + L.red[3][i];
+        }
+    }
+    // every face of the table goes out once: 16 lanes per slot (9 used), the three vertex-position rows
+    const int sub = tid & 15;
+    for (int s0 = 0; s0 < TET_FRAG_TBL; s0 += 16) {
+        const int slot = s0 + (tid >> 4);
+        const int face = L.key[slot];
+        if (face < 0 || sub > 8) continue;
+        atomicAdd(&dL_dverts[3 * p.faces[3 * face + sub / 3] + sub % 3], (float)L.val[sub][slot]);
+    }
+}
+
 static TetParams make_params(const dmr_scene& s, int gx, int gy, int r0, TetImageState img) {
     TetParams p;
     p.B = s.B; p.P = s.P; p.F = s.F; p.W = s.W; p.H = s.H; p.gx = gx; p.gy = gy; p.r0 = r0;
@@ -1363,6 +1556,15 @@ void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, Tet
         if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
         else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
     }
+}
+
+void launch_tet_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, const int32_t* frag_face,
+                               const float* frag_grad, float* dL_dverts, float* cam_part, hipStream_t st) {
+    if (r1 <= r0 || K < 1 || K > 32 || !frag_face || !frag_grad || !dL_dverts) return;
+    TetParams p = make_params(s, gx, gy, r0, img);
+    const dim3 grid(gx, r1 - r0, s.B), block(256);
+    if (cam_part) k_tet_fragment_grads<true><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, dL_dverts, cam_part);
+    else k_tet_fragment_grads<false><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, dL_dverts, nullptr);
 }
 
 }  // namespace dmr

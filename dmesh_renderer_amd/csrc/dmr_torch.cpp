@@ -28,6 +28,8 @@
 //   fragment_grads=None      render_tris_backward: (pix_to_face i32 [B,K,H,W], grad_bary f32 [B,K,2,H,W]), 1 <= K <= 32: the gradient
 //                            of the fragment lists' barycentrics joins dL_dverts (and, with camera_grads, the matrices' gradients):
 //                            DMR_FLAG_TRI_FRAGMENT_GRADS; the tuple is the level's, unchanged
+//                            render_tets_backward: the same two tensors for the tet fragment lists' unclamped barycentrics
+//                            (DMR_FLAG_TET_FRAGMENT_GRADS); raises the level to at least full_grads, whose tuple is unchanged
 //   fragments=0              render_tris: K > 0 (at most 32): per-pixel fragment lists (DMR_FLAG_TRI_FRAGMENTS) -> the tuple gains
 //                            face i32 [B,K,H,W], bary f32 [B,K,2,H,W], count i32 [B,H,W] behind the four scratch tensors
 //                            render_tets: the same (DMR_FLAG_TET_FRAGMENTS): the faces of the march, in march order
@@ -201,7 +203,7 @@ at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at:
 // the gradient outputs the library asks for (GradTable::from): tensors the backward has put here for the library to fill.
 struct Scratch {
     c10::Device dev;
-    std::array<at::Tensor, DMR_BUF_TET_FRAGMENTS + 1> buf;
+    std::array<at::Tensor, DMR_BUF_TET_FRAGMENT_BARY_GRADS + 1> buf;
     explicit Scratch(c10::Device d) : dev(d) {}
     at::Tensor get(int which) const {
         return buf[which].defined() ? buf[which] : at::empty({0}, at::TensorOptions().dtype(at::kByte).device(dev));
@@ -468,10 +470,12 @@ py::tuple backward(const Inputs& in, In grad_color, In grad_depth, const char* c
     return py::tuple(py::cast(out));
 }
 
-// fragment_grads=(pix_to_face, grad_bary) of render_tris_backward: checked, then handed to the library as they are (the two
-// input buffers it requests; alloc_cb serves them from Scratch::buf) with the flag and K.
+// fragment_grads=(pix_to_face, grad_bary) of render_tris_backward / render_tets_backward: checked, then handed to the library as
+// they are (the two input buffers it requests, `faces_buf` and `grads_buf` of that renderer; alloc_cb serves them from
+// Scratch::buf) with the renderer's `flag` and K.
 using FragmentGrads = std::optional<std::pair<at::Tensor, at::Tensor>>;
-void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t W) {
+void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t W, int flag = DMR_FLAG_TRI_FRAGMENT_GRADS,
+                           int faces_buf = DMR_BUF_TRI_FRAGMENT_FACES, int grads_buf = DMR_BUF_TRI_FRAGMENT_BARY_GRADS) {
     if (!fg.has_value()) return;
     const at::Tensor& face = fg->first;
     const at::Tensor& grad = fg->second;
@@ -489,9 +493,9 @@ void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t 
         err("fragment_grads: grad_bary must have dimensions (B, K, 2, H, W) = (" + std::to_string(B) + ", " + std::to_string(K) + ", 2, " +
             std::to_string(H) + ", " + std::to_string(W) + ")");
     if (!face.is_contiguous() || !grad.is_contiguous()) err("fragment_grads: pix_to_face and grad_bary must be contiguous");
-    c.scratch.buf[DMR_BUF_TRI_FRAGMENT_FACES] = face;
-    c.scratch.buf[DMR_BUF_TRI_FRAGMENT_BARY_GRADS] = grad;
-    c.sc.flags |= DMR_FLAG_TRI_FRAGMENT_GRADS | ((int)K << 8);
+    c.scratch.buf[faces_buf] = face;
+    c.scratch.buf[grads_buf] = grad;
+    c.sc.flags |= flag | ((int)K << 8);
 }
 
 // tri_grads' tuple; the keywords select its level
@@ -509,15 +513,19 @@ py::tuple render_tris_backward(In background, In verts, In faces, In verts_color
                     });
 }
 
-// tet_grads' tuple; the keywords select its level
+// tet_grads' tuple; the keywords select its level (fragment_grads: at least 1 -- dL_dverts exists from there on)
 py::tuple render_tets_backward(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                                In inv_proj_mats, In verts_depth, In faces_intense, In tets, In face_tets, In tet_faces, In grad_color, In grad_depth,
                                In pointBuffer, In faceBuffer, In binningBuffer, In imageBuffer, std::pair<int, int> rows,
-                               const std::optional<at::Tensor>& flat_out, bool full_grads, bool camera_grads, bool alpha) {
+                               const std::optional<at::Tensor>& flat_out, bool full_grads, bool camera_grads, bool alpha,
+                               const FragmentGrads& fragment_grads) {
     return backward({background, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, inv_mv_mats, inv_proj_mats, verts_depth, faces_intense,
                      &tets, &face_tets, &tet_faces},
                     grad_color, grad_depth, "grad_color", "grad_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out, &tet_grads,
-                    camera_grads ? 2 : full_grads, alpha, [](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                    camera_grads ? 2 : (full_grads || fragment_grads.has_value()), alpha,
+                    [&fragment_grads](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
+                        attach_fragment_grads(c, fragment_grads, c.sc.H, c.sc.W, DMR_FLAG_TET_FRAGMENT_GRADS, DMR_BUF_TET_FRAGMENT_FACES,
+                                              DMR_BUF_TET_FRAGMENT_BARY_GRADS);
                         return g_abi.tet_backward(&c.sc, gc, gd, b[0], b[1], b[2], b[3], g[0], g[1], &alloc_cb, &c.scratch, c.stream());
                     });
 }
@@ -620,7 +628,7 @@ PYBIND11_MODULE(_C, m) {
         py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tets_backward", &render_tets_backward, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("grad_color"),
         py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out,
-        py::kw_only(), py::arg("full_grads") = false, camera_grads, alpha);
+        py::kw_only(), py::arg("full_grads") = false, camera_grads, alpha, py::arg("fragment_grads") = py::none());
     m.def("invert_mats", &invert_mats);
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
@@ -643,6 +651,7 @@ PYBIND11_MODULE(_C, m) {
     m.attr("ABI_VERSION") = (int)DMR_ABI_VERSION;
     m.attr("NUM_CHANNELS") = NUM_CHANNELS;
     m.attr("SUPPORTS_FLAT_OUT") = true;  // render_*_backward(flat_out=...), used by sharding.py
+    m.attr("SUPPORTS_TET_FRAGMENT_GRADS") = true;  // render_tets_backward(fragment_grads=...), asked for by TetRenderer(fragment_grads=True)
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

@@ -7,18 +7,19 @@ data, not as a function of the scene -- is
   * their order (the tile's depth sort),
   * the barycentrics (the (u, v) of the pixel's ray on each face: clamped to the face by the tri renderer, which blends every
     face its coverage test accepts; UNCLAMPED from the tet renderer, whose march crosses a face in its interior by
-    construction) -- UNLESS the TRI renderer was made with fragment_grads=True: frag.bary then requires grad, interpolate and
+    construction) -- UNLESS the renderer was made with fragment_grads=True: frag.bary then requires grad, interpolate and
     composite (which only read it) pass the gradient on, and the renderer's backward carries it to verts and, with
-    camera_grads, to mv_mats / proj_mats (the exact derivative of the clamped (u, v), the clamp region held fixed).
-    Positions, normals, texture coordinates or a depth shaded here then see the geometry.  The tet renderer has no such
-    option: its barycentrics are always constants,
+    camera_grads, to mv_mats / proj_mats (tri: the exact derivative of the clamped (u, v), the clamp region held fixed; tet:
+    that of the unclamped (u, v), and the option implies full_grads).  Positions, normals, texture coordinates or a depth
+    shaded here then see the geometry,
 exactly the constants of the renderer's own default gradients.  Gradients flow into what the caller passes: opacities,
 per-vertex attributes, per-face scales.  A pixel with count > K holds the first K of its faces only: what is computed for it
 is the truncated sum.
 
 The tet renderer's lists are in exact march order, front to back; a pixel whose march failed (active == False) has count 0
 and no fragments, and shades to the bare background like the renderer's own image.  interpolate(frag, faces, verts) is the
-hit point of every fragment.
+hit point of every fragment; with TetRenderer(fragment_grads=True) its gradient to verts is the hit point's full derivative
+(the direct term through the vertex rows plus the movement of (u, v)), without it the direct term only.
 
 The renderer's own colour, for pixels with count <= K:
     color, T = composite(frag, faces, faces_opacity, verts_color, face_scale=faces_intense);  color + T * bg.view(1, 3, 1, 1)

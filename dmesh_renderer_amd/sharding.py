@@ -434,10 +434,13 @@ class ShardedTetRenderer(_Banded, TetRenderer):
     see TetRenderer).
     Same call signature and outputs as TetRenderer (color, depth, active bool; with return_alpha also alpha).
     TetRenderer's return_fragments is NOT available here, as ShardedTriRenderer's is not: the per-pixel fragment lists are
-    a single-device output so far (ValueError)."""
+    a single-device output so far; nor is fragment_grads, their gradient (ValueError)."""
 
     def __init__(self, render_settings: TetRenderSettings, group=None, assemble: bool = True, impl=None,
-                 full_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False, return_fragments: int = 0):
+                 full_grads: bool = False, camera_grads: bool = False, return_alpha: bool = False, return_fragments: int = 0,
+                 fragment_grads: bool = False):
+        if fragment_grads:
+            raise ValueError("fragment_grads is not available on the sharded Modules (nor is return_fragments, which it needs)")
         if return_fragments:
             raise ValueError("return_fragments is not available on the sharded Modules")
         super().__init__(render_settings, group, assemble, impl, full_grads=full_grads, camera_grads=camera_grads,

@@ -46,7 +46,9 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
        DMR_BUF_TRI_FRAGMENTS = 8 /* dmr_tri_forward with DMR_FLAG_TRI_FRAGMENTS: an OUTPUT, see the flag */,
        DMR_BUF_TRI_FRAGMENT_FACES = 9 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */,
        DMR_BUF_TRI_FRAGMENT_BARY_GRADS = 10 /* dmr_tri_backward with DMR_FLAG_TRI_FRAGMENT_GRADS: an INPUT, see the flag */,
-       DMR_BUF_TET_FRAGMENTS = 11 /* dmr_tet_forward with DMR_FLAG_TET_FRAGMENTS: an OUTPUT, see the flag */ };
+       DMR_BUF_TET_FRAGMENTS = 11 /* dmr_tet_forward with DMR_FLAG_TET_FRAGMENTS: an OUTPUT, see the flag */,
+       DMR_BUF_TET_FRAGMENT_FACES = 12 /* dmr_tet_backward with DMR_FLAG_TET_FRAGMENT_GRADS: an INPUT, see the flag */,
+       DMR_BUF_TET_FRAGMENT_BARY_GRADS = 13 /* dmr_tet_backward with DMR_FLAG_TET_FRAGMENT_GRADS: an INPUT, see the flag */ };
 
 /* Footprints (bytes; B views, P verts, F faces, T tets, Nt = B * ceil(W/16) * ceil(H/16) tiles, R list entries; every
  * sub-array rounded up to 256): point 16 BP; face 16 BF (tet: 20 BF + 128 F + 224 T); image ~76 B + 40 Nt + 12 BWH (tet: 29 BWH);
@@ -66,7 +68,9 @@ enum { DMR_BUF_POINT = 0, DMR_BUF_FACE = 1, DMR_BUF_BINNING = 2, DMR_BUF_IMAGE =
  * the call's band; tet camera grads (tet backward with DMR_FLAG_TET_CAMERA_GRADS only) 256 B, exactly; tri fragments (tri
  * forward with DMR_FLAG_TRI_FRAGMENTS only) 4 BWH (3K + 1), exactly; tri fragment faces and tri fragment bary grads (tri
  * backward with DMR_FLAG_TRI_FRAGMENT_GRADS only; inputs) 4 BKWH and 8 BKWH, exactly; tet fragments (tet forward with
- * DMR_FLAG_TET_FRAGMENTS only) 4 BWH (3K + 1), exactly. */
+ * DMR_FLAG_TET_FRAGMENTS only) 4 BWH (3K + 1), exactly; tet fragment faces and tet fragment bary grads (tet backward with
+ * DMR_FLAG_TET_FRAGMENT_GRADS only; inputs) 4 BKWH and 8 BKWH, exactly -- that flag implies DMR_FLAG_TET_FULL_GRADS, so such a
+ * call also owns the tet grads buffer. */
 
 /* C equivalent of the reference's four std::function<char*(size_t)> allocators
  * (rasterizer.h:14-17, render.cu:18-24): must return a device pointer to at least
@@ -207,9 +211,30 @@ typedef struct dmr_scene {
  * view configuration above all; a K whose sequence alone exceeds 16 GiB fails before anything is launched).  The images, the
  * other three scratch buffers, the backward -- which decides on the device whether the sequence is complete, as before -- and
  * the estimate left for the next call are exactly those of a call without the flag; no host wait is added (DMR_FLAG_ASYNC and
- * stream capture work as before).  The barycentrics carry no gradient. */
+ * stream capture work as before).  The barycentrics' gradient is the backward's DMR_FLAG_TET_FRAGMENT_GRADS. */
 #define DMR_FLAG_TET_FRAGMENTS (1 << 16)
 #define DMR_TET_FRAGMENTS_FLAGS(k) (DMR_FLAG_TET_FRAGMENTS | (((k) & 255) << 8))
+/* dmr_tet_backward only (ignored by every other call): the gradient of the tet fragment lists' barycentrics reaches the vertex
+ * positions and, with DMR_FLAG_TET_CAMERA_GRADS, the inverse matrices.  Implies DMR_FLAG_TET_FULL_GRADS (dL_dverts exists at
+ * that level only: the call requests DMR_BUF_TET_GRADS and the images' own gradient fills it as with that flag).  K travels in
+ * bits 8-15 of the flags (DMR_FRAGMENTS_K; the flag with K = 0 or K > 32 is an error, raised before anything is requested or
+ * launched, whatever the scene; without the flag the K bits are ignored).  The call then requests two more buffers through
+ * `alloc`, once each -- INPUTS, which the caller has filled before the call:
+ *   DMR_BUF_TET_FRAGMENT_FACES       int32 [B,K,H,W]    4 BKWH bytes, exactly: the face of every (pixel, slot) pair, as the forward
+ *                                                       returned it -- or any other face: the pair need not be one the march crossed;
+ *   DMR_BUF_TET_FRAGMENT_BARY_GRADS  fp32  [B,K,2,H,W]  8 BKWH bytes, exactly: dL/d(u, v) of that pair
+ * (not at all when there is nothing to back-propagate: P == 0, F == 0 or an empty tile-row band; the term is then zero).  One
+ * more kernel behind the march's backward recomputes, for every pixel of the rendered tile rows and every one of its K slots,
+ * the pair's unclamped Moeller-Trumbore (u, v) on the pixel's ray -- the forward's ray: origin inv_mv's translation column,
+ * direction w / max(|w|, 1e-4), the seeded jitter a constant -- and adds the exact derivative of (u, v) times the upstream
+ * gradient into the dL_dverts part of DMR_BUF_TET_GRADS and, with DMR_FLAG_TET_CAMERA_GRADS, through the ray into the dL/dinv_mv |
+ * dL/dinv_proj half of DMR_BUF_TET_CAMERA_GRADS ((u, v) read the inverse matrices only: the dL/dmv | dL/dproj half gains
+ * nothing).  There is no clamp and so no clamp region.  A slot whose face lies outside [0, F) contributes nothing, nor does a
+ * pair whose upstream gradient is (0, 0), a pair with denom == 0 or a pixel outside the rendered tile rows; whether the pixel's
+ * march was valid (out_active) is not consulted.  Pairs beyond K were never stored and get nothing.  The other outputs, the
+ * scratch buffers, the work space and the march-sequence estimate are those of a call with DMR_FLAG_TET_FULL_GRADS (and the
+ * camera flag) alone; no host wait is added (DMR_FLAG_ASYNC and stream capture work as before). */
+#define DMR_FLAG_TET_FRAGMENT_GRADS (1 << 17)
 /* 1 if an asynchronous / captured call on `device` (-1: the current one) overflowed its capacity since the flag was
  * last reset; call it after the stream (or the graph launch) has completed.  reset != 0 clears the flag. */
 int dmr_overflowed(int device, int reset);
@@ -267,7 +292,9 @@ int dmr_tet_forward(const dmr_scene* scene, float* out_color, float* out_depth, 
  * no w divide and the length clamped to 1e-4, the seeded jitter held fixed); mv and proj through the ndc depth of each
  * marched face's hit point (rows 0-2 of mv, rows 2-3 of proj).  The w rows of the inverses get 0.  Per-tile partials go to
  * a DMR_BUF_WORK request.  No host wait is added.  Without the flags the call is exactly as before and requests no buffer.
- * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term. */
+ * With DMR_FLAG_ALPHA dL_ddepth is [B,2,H,W] (dL/ddepth | dL/dalpha); only dL_dfopacity gains a term.
+ * With DMR_FLAG_TET_FRAGMENT_GRADS (implies DMR_FLAG_TET_FULL_GRADS) dL_dverts (and the inverse matrices' camera gradients) gain
+ * the fragment lists' term, from two input buffers requested through `alloc` (see the flag). */
 int dmr_tet_backward(const dmr_scene* scene, const float* dL_dcolor, const float* dL_ddepth,
                      const void* point_buf, const void* face_buf,
                      const void* binning_buf, const void* image_buf,
