@@ -8,7 +8,7 @@ from dmesh_renderer_amd import _through_inverse, scenes
 from tet_camera_grad_ref import TetCameraGradRef
 from tet_grad_ref import TetGradRef
 from tri_grad_ref import TriGradRef
-from util import upstream_grads
+from util import upstream_grads, with_bg
 
 TRI_VERTS_TOL = 1e-4   # dL_dverts against the float64 model
 TET_VERTS_TOL = 1e-3
@@ -33,13 +33,16 @@ TRI_CASES = {
 }
 
 
-def scene(case, W_extra=0, cases=TET_CASES):
-    """The tet scene of a case; W_extra widens the frame, which gives a test a view configuration of its own."""
+def scene(case, W_extra=0, cases=TET_CASES, bg=None):
+    """The tet scene of a case; W_extra widens the frame, which gives a test a view configuration of its own; bg: its
+    background (default: the scene's own, zero)."""
     m, B, H, W, op, seed = cases[case]
     W = W + W_extra
     d = scenes.kuhn_tets(m, B, H, W, seed=0, opacity=op)
     if case == "opaque":
         d["faces_opacity"][::7] = 1.0
+    if bg is not None:
+        d = with_bg(d, bg)
     return d, B, H, W, seed
 
 
@@ -70,10 +73,14 @@ def module_mats(args, g):
     return g_mv.transpose(1, 2).cpu().numpy(), g_proj.transpose(1, 2).cpu().numpy()
 
 
-def setup(oracle, case):
-    """The tri scene of a case, the upstream gradients masked to the pixels the float64 model keeps, its gradients."""
+def setup(oracle, case, bg=None, W_extra=0):
+    """The tri scene of a case (bg: its background, default the scene's own, zero; W_extra widens the frame, as for scene),
+    the upstream gradients masked to the pixels the float64 model keeps, its gradients."""
     L, n, B, H, W, rows = TRI_CASES[case]
+    W = W + W_extra
     d = scenes.layered_sheets(L, n, B, H, W, seed=7, opacity=(0.1, 0.5))
+    if bg is not None:
+        d = with_bg(d, bg)
     sc = oracle.scene_from_module_inputs(d, H, W)
     _, _, ost = oracle.tri_forward(sc)
     ref = TriGradRef(d, H, W, ost)

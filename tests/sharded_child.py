@@ -14,6 +14,7 @@ import torch.distributed as dist
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import scenes, sharding
 from harness import module_step
+from util import with_bg
 
 DEV = th.device("cuda:0")
 GRAD_TOL = 1e-5
@@ -30,8 +31,9 @@ def compare(full, sharded, names, tol, what):
 
 
 def on_device(d, B, H, W, alpha=False):
-    """The scene and the upstream gradients (g_c, g_d[, g_a]) on the device, and the renderer's settings."""
-    t = {k: v.to(DEV) for k, v in d.items()}
+    """The scene over util.BG and the upstream gradients (g_c, g_d[, g_a]) on the device, and the renderer's settings.  (A
+    band's image is zero outside its rows, not background: the assembled images are still compared bit for bit.)"""
+    t = {k: v.to(DEV) for k, v in with_bg(d).items()}
     up = list(scenes.upstream_grads(B, H, W))
     if alpha:
         up.append(th.randn(B, 1, H, W, generator=th.Generator().manual_seed(5)))

@@ -16,7 +16,7 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
-from util import SUM_ORDER_TOL, c_args, elementwise_close, rel_err, sum_order_tol, upstream_grads
+from util import SUM_ORDER_TOL, c_args, elementwise_close, rel_err, sum_order_tol, upstream_grads, with_bg
 
 pytestmark = pytest.mark.gpu
 
@@ -190,10 +190,11 @@ def test_c3_tet_matches_oracle_and_repeats(hip_device, oracle):
 def test_c3_tet_bands_compose(hip_device, oracle):
     """The tet renderer as tile-row bands ("the tet path shards identically"; renderer_impl.cu:355-409 is
     the path): three bands of C3 -- uneven, the last one EMPTY -- rendered and back-propagated separately give the
-    full image, active mask and both gradients, and every band agrees with the oracle's band."""
+    full image, active mask and both gradients, and every band agrees with the oracle's band.  Over a background: the pixels
+    outside a band are zero, not background."""
     from dmesh_renderer_amd import _C
     H = W = 800
-    d = scenes.kuhn_tets(16, 1, H, W)
+    d = with_bg(scenes.kuhn_tets(16, 1, H, W))
     args = c_args(d, hip_device, tet=True)
     gc, gd = upstream_grads(1, H, W)
     gc, gd = gc.to(hip_device), gd.to(hip_device)

@@ -14,7 +14,7 @@ NAMES = ("verts", "verts_color", "faces_opacity", "verts_depth", "faces_intense"
 
 def _soup(seed, P, F, B, H, W):
     g = th.Generator().manual_seed(seed)
-    base = scenes.layered_sheets(1, 3, B, H, W, seed=seed)  # cameras, bg
+    base = scenes.layered_sheets(1, 3, B, H, W, seed=seed)  # cameras
     spread = th.tensor([2.5, 2.5, 4.0])
     verts = (th.rand(P, 3, generator=g) - 0.5) * 2.0 * spread
     faces = th.randint(0, P, (F, 3), generator=g, dtype=th.int32)
@@ -31,6 +31,7 @@ def _soup(seed, P, F, B, H, W):
     d["verts"] = verts.float(); d["faces"] = faces
     d["verts_color"] = th.rand(P, 3, generator=g); d["faces_opacity"] = op
     d["verts_depth"] = th.randn(B, P, generator=g); d["faces_intense"] = th.rand(B, F, generator=g) + 0.5
+    d["bg"] = th.rand(3, generator=g) * 3.0 - 1.0  # uniform in [-1, 2]^3
     return d
 
 
@@ -86,7 +87,7 @@ def _delaunay(seed, npts, B, H, W):
     cnt = np.searchsorted(inv_s, np.arange(F), side="right") - start
     face_tets[:, 0] = own_s[start]
     face_tets[cnt > 1, 1] = own_s[start[cnt > 1] + 1]
-    base = scenes.kuhn_tets(2, B, H, W, seed=seed)  # cameras, bg
+    base = scenes.kuhn_tets(2, B, H, W, seed=seed)  # cameras
     g = th.Generator().manual_seed(seed)
     d = dict(base)
     d["verts"] = th.from_numpy(pts).float(); d["faces"] = th.from_numpy(faces); d["tets"] = th.from_numpy(tets.astype(np.int32))
@@ -94,6 +95,7 @@ def _delaunay(seed, npts, B, H, W):
     d["verts_color"] = th.rand(npts, 3, generator=g); d["faces_opacity"] = th.rand(F, generator=g) * 0.4 + 0.02
     d["faces_intense"] = th.rand(B, F, generator=g) * 0.5 + 0.5
     d["verts_depth"] = th.randn(B, npts, generator=g)
+    d["bg"] = th.rand(3, generator=g) * 3.0 - 1.0  # uniform in [-1, 2]^3
     return d
 
 

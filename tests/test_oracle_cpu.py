@@ -11,7 +11,10 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
-from util import upstream_grads
+from util import BG, upstream_grads, with_bg
+
+# the brute-force forward tests run over no background and over one: `T * bg` vanishes with the first
+BGS = pytest.mark.parametrize("bg", [(0.0, 0.0, 0.0), BG], ids=["bg_zero", "bg_set"])
 
 
 # ---------------------------------------------------------------------------
@@ -156,10 +159,11 @@ def _brute_tri(sc, st):
     return color, depth
 
 
+@BGS
 @pytest.mark.parametrize("opacity", [(0.1, 0.5), (0.7, 0.99)])
-def test_tri_forward_matches_brute_force(oracle, opacity):
+def test_tri_forward_matches_brute_force(oracle, opacity, bg):
     H, W = 40, 56
-    d = scenes.layered_sheets(3, 5, 2, H, W, seed=2, opacity=opacity)
+    d = with_bg(scenes.layered_sheets(3, 5, 2, H, W, seed=2, opacity=opacity), bg)
     sc = oracle.scene_from_module_inputs(d, H, W)
     color, depth, st = oracle.tri_forward(sc)
     bcolor, bdepth = _brute_tri(sc, st)
@@ -244,11 +248,12 @@ def test_tri_empty_and_culled(oracle):
 # ---------------------------------------------------------------------------
 # tet renderer
 # ---------------------------------------------------------------------------
-def test_tet_march_matches_sorted_intersections(oracle):
+@BGS
+def test_tet_march_matches_sorted_intersections(oracle, bg):
     """For active pixels the march must visit exactly the faces the ray really intersects, in order of
     the ray parameter t (that is the point of the tet renderer, README.md:4)."""
     H = W = 48
-    d = scenes.kuhn_tets(3, 1, H, W, seed=0, opacity=(0.05, 0.3))
+    d = with_bg(scenes.kuhn_tets(3, 1, H, W, seed=0, opacity=(0.05, 0.3)), bg)
     sc = oracle.scene_from_module_inputs(d, H, W)
     color, depth, active, st = oracle.tet_forward(sc)
     assert active.mean() > 0.3

@@ -8,7 +8,7 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
-from util import SUM_ORDER_TOL, c_args, rel_err, sum_order_tol, upstream_grads
+from util import SUM_ORDER_TOL, c_args, rel_err, sum_order_tol, upstream_grads, with_bg
 
 pytestmark = pytest.mark.gpu
 
@@ -118,10 +118,11 @@ def test_backward(oracle, hip_device, case):
 
 
 def test_band_rows_compose(oracle, hip_device):
-    """Two tile-row bands rendered separately == the full render (forward pixels and summed grads)."""
+    """Two tile-row bands rendered separately == the full render (forward pixels and summed grads), over a background: the
+    pixels outside a band are zero, not background, so the bands still sum to the full frame bit for bit."""
     from dmesh_renderer_amd import _C
     L, n, B, H, W, op = CASES["ragged"]
-    d = scenes.layered_sheets(L, n, B, H, W, seed=3, opacity=op)
+    d = with_bg(scenes.layered_sheets(L, n, B, H, W, seed=3, opacity=op))
     args = c_args(d, hip_device)
     gc, gd = upstream_grads(B, H, W)
     gc, gd = gc.to(hip_device), gd.to(hip_device)
