@@ -106,6 +106,53 @@ def _split_alpha(out):
     return (out[0], out[1][:, :1], *out[2:], out[1][:, 1:])
 
 
+def _outputs(out, alpha, fragments):
+    """What a Function returned -> what render_tri / render_tet and the Modules return."""
+    if fragments:
+        return _split_fragments(out, alpha)
+    return _split_alpha(out) if alpha else out
+
+
+def _fragment_kw(fragments, fragment_grads, shard) -> dict:
+    """The option checks of _TriFn / _TetFn and the `fragments` keyword of their _forward (none by default)."""
+    if fragment_grads and shard is not None:
+        raise ValueError("fragment_grads is not available on the sharded Modules")
+    if fragments and shard is not None:
+        raise ValueError("return_fragments is not available on the sharded Modules")
+    if fragment_grads and not fragments:
+        raise ValueError("fragment_grads needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
+    return {"fragments": fragments} if fragments else {}
+
+
+def _save(ctx, saved, fragment_grads, color, depth, frag, constants=()):
+    """The end of _TriFn / _TetFn.forward: what the backward needs, and which outputs are constants (`constants` and the
+    fragment lists -- but for bary with fragment_grads: face is then what the backward needs of the lists)."""
+    ctx.fragment_grads = bool(fragment_grads)
+    if fragment_grads:
+        ctx.save_for_backward(*saved, frag[0])
+        ctx.mark_non_differentiable(*constants, frag[0], frag[2])
+        ctx.set_materialize_grads(False)  # no zeros for the outputs a loss does not use: a None for bary is the call without the term
+        ctx.image_shapes = (color.shape, depth.shape)
+    else:
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(*constants, *frag)
+
+
+def _upstream(ctx, grad_color, grad_depth, grad_fragments):
+    """The gradients autograd hands to _TriFn / _TetFn.backward -> (grad_color, grad_depth, further keywords of _backward).
+    With fragment_grads the image gradients may be missing (zeros then), and one for bary goes down with the call."""
+    more = {}
+    if ctx.fragment_grads:
+        more["extra_saved"] = 1  # (face)
+        if grad_color is None:
+            grad_color = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[0])
+        if grad_depth is None:
+            grad_depth = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[1])
+        if grad_fragments[1] is not None:
+            more["fragment_grads"] = (ctx.saved_tensors[-1], grad_fragments[1].contiguous())
+    return grad_color, grad_depth, more
+
+
 def _impl(shard):
     """The kernels of a Function: `_C` as it is at call time on one device (tests swap it), a sharded Module's otherwise."""
     return _C if shard is None else shard.impl
@@ -232,118 +279,67 @@ class _TriFn(th.autograd.Function):
     on one device; from a sharded Module (sharding._Shard) its kernels, the band images to assemble and the gradients'
     all-reduce.  fragments = K > 0 (one device only): three more outputs, the non-differentiable face [B,K,H,W], bary
     [B,K,2,H,W] and count [B,H,W] of render_tris(fragments=K).  fragment_grads (needs fragments): bary is differentiable;
-    the gradient that arrives for it goes down with the backward call (fragment_grads=(face, grad_bary)), where the library
-    adds its term to the verts piece and, at level 2, to the camera piece: the gradient set (_TRI_GRADS) is unchanged.  Gradients
-    are then not materialised: a backward without one for bary is today's call."""
+    the gradient that arrives for it goes down with the backward call (fragment_grads=(face, grad_bary): _upstream), where the
+    library adds its term to the verts piece and, at level 2, to the inverse matrices' part of the camera piece: the gradient
+    set is unchanged.  Gradients are then not materialised: a backward without one for bary is the call without the keyword."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 settings: TriRenderSettings, rows, shard=None, exact_grads=False, camera_grads=False, alpha=False, fragments=0,
                 fragment_grads=False):
         geom = (verts, faces, verts_color, faces_opacity)
-        if fragment_grads and shard is not None:
-            raise ValueError("fragment_grads is not available on the sharded Modules")
-        if fragments and shard is not None:
-            raise ValueError("return_fragments is not available on the sharded Modules")
-        if fragment_grads and not fragments:
-            raise ValueError("fragment_grads needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
+        kw = _fragment_kw(fragments, fragment_grads, shard)
         (num_rendered, color, depth, *frag), saved = _forward(_impl(shard).render_tris, settings, geom, mv_mats, proj_mats, verts_depth,
-                                                              faces_intense, rows, alpha, **({"fragments": fragments} if fragments else {}))
+                                                              faces_intense, rows, alpha, **kw)
         if shard is not None:
             color, depth = shard.gather((color, depth))
         ctx.settings, ctx.rows, ctx.shard, ctx.num_rendered = settings, rows, shard, num_rendered
         ctx.more_grads, ctx.camera_grads, ctx.alpha = exact_grads or camera_grads, camera_grads, alpha
-        ctx.fragment_grads = bool(fragment_grads)
-        if fragment_grads:  # bary is differentiable: face is what the backward needs of the lists
-            ctx.save_for_backward(*geom, *saved, frag[0])
-            ctx.mark_non_differentiable(frag[0], frag[2])
-            ctx.set_materialize_grads(False)  # no zeros for the outputs a loss does not use: a None for bary is the call without the term
-            ctx.image_shapes = (color.shape, depth.shape)
-        else:
-            ctx.save_for_backward(*geom, *saved)
-            ctx.mark_non_differentiable(*frag)
+        _save(ctx, (*geom, *saved), fragment_grads, color, depth, frag)
         return (color, depth, *frag)
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth, *grad_fragments):
-        more = {}
-        if ctx.fragment_grads:
-            more["extra_saved"] = 1  # (face)
-            if grad_color is None:
-                grad_color = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[0])
-            if grad_depth is None:
-                grad_depth = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[1])
-            if grad_fragments[1] is not None:
-                more["fragment_grads"] = (ctx.saved_tensors[-1], grad_fragments[1].contiguous())
+        grad_color, grad_depth, more = _upstream(ctx, grad_color, grad_depth, grad_fragments)
         return _backward(ctx, _TRI_GRADS, grad_color, grad_depth, ctx.num_rendered, **more) + (None,) * 8
 
 
 class _TetFn(th.autograd.Function):
     """Gradients flow to verts_color and faces_opacity only (reference :407-422); with full_grads also to verts and
-    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha: as for _TriFn.
-    fragments = K > 0 (one device only; only when set: see _trailing): three more outputs, the non-differentiable face
-    [B,K,H,W], bary [B,K,2,H,W] and count [B,H,W] of render_tets(fragments=K).  fragment_grads (the last argument; needs
-    fragments; implies full_grads, where dL/dverts exists): as _TriFn's -- bary is differentiable, the gradient that arrives for
-    it goes down with the backward call (fragment_grads=(face, grad_bary)), where the library adds its term to the verts piece
-    and, at level 2, to the inverse matrices' part of the camera piece: the gradient set (_TET_GRADS) is unchanged.  Gradients
-    are then not materialised: a backward without one for bary is the full_grads call."""
+    faces_intense, with camera_grads also to mv^T and proj^T (beyond the reference).  shard, alpha, fragments (the lists of
+    render_tets(fragments=K)) and fragment_grads (the last argument): as for _TriFn; fragment_grads implies full_grads, where
+    dL/dverts exists, so a backward without a gradient for bary is the full_grads call."""
 
     @staticmethod
     def forward(ctx, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                 tets, face_tets, tet_faces, settings: TetRenderSettings, rows, shard=None, full_grads=False, camera_grads=False,
                 alpha=False, fragments=0, fragment_grads=False):
         geom = (verts, faces, verts_color, faces_opacity)
-        if fragment_grads and shard is not None:
-            raise ValueError("fragment_grads is not available on the sharded Modules")
-        if fragments and shard is not None:
-            raise ValueError("return_fragments is not available on the sharded Modules")
-        if fragment_grads and not fragments:
-            raise ValueError("fragment_grads needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
+        kw = _fragment_kw(fragments, fragment_grads, shard)
         (color, depth, active, *frag), saved = _forward(_impl(shard).render_tets, settings, geom, mv_mats, proj_mats, verts_depth,
-                                                        faces_intense, rows, alpha, (tets, face_tets, tet_faces),
-                                                        **({"fragments": fragments} if fragments else {}))
+                                                        faces_intense, rows, alpha, (tets, face_tets, tet_faces), **kw)
         if shard is not None:
             color, depth, active = shard.gather((color, depth, active))
         active = active > 0.5  # bool mask, reference :333
         ctx.settings, ctx.rows, ctx.shard = settings, rows, shard
         ctx.more_grads, ctx.camera_grads, ctx.alpha = full_grads or camera_grads or bool(fragment_grads), camera_grads, alpha
-        ctx.fragment_grads = bool(fragment_grads)
-        if fragment_grads:  # bary is differentiable: face is what the backward needs of the lists
-            ctx.save_for_backward(*geom, *saved, frag[0])
-            ctx.mark_non_differentiable(active, frag[0], frag[2])
-            ctx.set_materialize_grads(False)  # no zeros for the outputs a loss does not use: a None for bary is the call without the term
-            ctx.image_shapes = (color.shape, depth.shape)
-        else:
-            ctx.save_for_backward(*geom, *saved)
-            ctx.mark_non_differentiable(active, *frag)
+        _save(ctx, (*geom, *saved), fragment_grads, color, depth, frag, constants=(active,))
         return (color, depth, active, *frag)
 
     @staticmethod
     def backward(ctx, grad_color, grad_depth, _grad_active, *grad_fragments):
-        more = {}
-        if ctx.fragment_grads:
-            more["extra_saved"] = 1  # (face)
-            if grad_color is None:
-                grad_color = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[0])
-            if grad_depth is None:
-                grad_depth = ctx.saved_tensors[0].new_zeros(ctx.image_shapes[1])
-            if grad_fragments[1] is not None:
-                more["fragment_grads"] = (ctx.saved_tensors[-1], grad_fragments[1].contiguous())
+        grad_color, grad_depth, more = _upstream(ctx, grad_color, grad_depth, grad_fragments)
         return _backward(ctx, _TET_GRADS, grad_color, grad_depth, **more) + (None,) * 11
 
 
-def _check_fragment_grads(fragment_grads, return_fragments):
+def _check_fragment_grads(fragment_grads, return_fragments, tet=False):
+    """The options of render_tri / render_tet and the Modules.  tet: the binding in use must also know render_tets_backward's
+    fragment_grads keyword.  The binding is a build product of its own (build.py rebuilds it by file times): one from before
+    the keyword, or a stand-in without it, would fail with pybind's argument dump in the first backward that carries a gradient
+    for bary -- deep inside autograd.  Asked at construction instead, a TypeError that says what is missing."""
     if fragment_grads and not return_fragments:
         raise ValueError("fragment_grads=True needs return_fragments=K: it is the gradient of the fragment lists' barycentrics")
-
-
-def _check_tet_fragment_grads(fragment_grads, return_fragments):
-    """_check_fragment_grads, and: the binding in use must know render_tets_backward's fragment_grads keyword.  The binding is
-    a build product of its own (build.py rebuilds it by file times): one from before the keyword, or a stand-in without it,
-    would fail with pybind's argument dump in the first backward that carries a gradient for bary -- deep inside autograd.
-    Asked at construction instead, a TypeError that says what is missing."""
-    _check_fragment_grads(fragment_grads, return_fragments)
-    if fragment_grads and not getattr(_C, "SUPPORTS_TET_FRAGMENT_GRADS", False):
+    if tet and fragment_grads and not getattr(_C, "SUPPORTS_TET_FRAGMENT_GRADS", False):
         raise TypeError("fragment_grads=True: the loaded binding's render_tets_backward has no fragment_grads keyword "
                         "(a `_C` built before it: rebuild with `python -m dmesh_renderer_amd.build --force`)")
 
@@ -358,9 +354,7 @@ def render_tri(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
                        render_settings, tuple(rows),
                        *_trailing(None, bool(exact_grads), bool(camera_grads), bool(return_alpha), int(return_fragments),
                                   bool(fragment_grads)))
-    if return_fragments:
-        return _split_fragments(out, return_alpha)
-    return _split_alpha(out) if return_alpha else out
+    return _outputs(out, return_alpha, return_fragments)
 
 
 def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
@@ -368,14 +362,12 @@ def render_tet(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, ver
                return_alpha=False, return_fragments=0, fragment_grads=False):
     """Functional form (reference :243-275).  mv_mats / proj_mats are the TRANSPOSED matrices.  full_grads,
     camera_grads, return_alpha, return_fragments, fragment_grads: see TetRenderer."""
-    _check_tet_fragment_grads(fragment_grads, return_fragments)
+    _check_fragment_grads(fragment_grads, return_fragments, tet=True)
     out = _TetFn.apply(verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense,
                        tets, face_tets, tet_faces, render_settings, tuple(rows),
                        *_trailing(None, bool(full_grads), bool(camera_grads), bool(return_alpha), int(return_fragments),
                                   bool(fragment_grads)))
-    if return_fragments:
-        return _split_fragments(out, return_alpha)
-    return _split_alpha(out) if return_alpha else out
+    return _outputs(out, return_alpha, return_fragments)
 
 
 class TriRenderer(th.nn.Module):
@@ -435,9 +427,7 @@ class TriRenderer(th.nn.Module):
     def forward(self, verts, faces, verts_color, faces_opacity, mv_mats, proj_mats, verts_depth, faces_intense):
         out = self._render(verts, faces.to(dtype=th.int32), verts_color, faces_opacity,
                            mv_mats.transpose(1, 2), proj_mats.transpose(1, 2), verts_depth, faces_intense)
-        if self.return_fragments:
-            return _split_fragments(out, self.return_alpha)
-        return _split_alpha(out) if self.return_alpha else out
+        return _outputs(out, self.return_alpha, self.return_fragments)
 
     def _render(self, *inputs):
         """_TriFn on the normalised inputs (faces int32, the matrices transposed); ShardedTriRenderer adds a partition."""
@@ -504,7 +494,7 @@ class TetRenderer(th.nn.Module):
     def __init__(self, render_settings: TetRenderSettings, full_grads: bool = False, camera_grads: bool = False,
                  return_alpha: bool = False, return_fragments: int = 0, fragment_grads: bool = False):
         super().__init__()
-        _check_tet_fragment_grads(fragment_grads, return_fragments)
+        _check_fragment_grads(fragment_grads, return_fragments, tet=True)
         self.render_settings = render_settings
         self.full_grads = bool(full_grads)
         self.camera_grads = bool(camera_grads)
@@ -522,8 +512,6 @@ class TetRenderer(th.nn.Module):
                            tets.to(**i32), face_tets.to(**i32), tet_faces.to(**i32), self.render_settings,
                            rows, *_trailing(shard, self.full_grads, self.camera_grads, self.return_alpha, self.return_fragments,
                                             self.fragment_grads))
-        if self.return_fragments:
-            return _split_fragments(out, self.return_alpha)
-        return _split_alpha(out) if self.return_alpha else out
+        return _outputs(out, self.return_alpha, self.return_fragments)
 
     _shard = TriRenderer._shard  # (rows, shard) of one device

@@ -46,6 +46,28 @@ int caller_output(dmr_alloc_fn alloc, void* ctx, int which, size_t bytes, const 
     return 0;
 }
 
+// K of a call, the fragment slots per pixel in bits 8-15 of the flags, when `flag` (one of the four fragment flags, `name`;
+// `macro`: what the header offers for those bits) is set, else 0.  -1, with the error set: K outside 1..FRAG_MAX_K.
+int fragment_k(const dmr_scene* s, int flag, const char* name, const char* macro) {
+    const int K = (s->flags & flag) ? DMR_FRAGMENTS_K(s->flags) : 0;
+    if ((s->flags & flag) && (K < 1 || K > dmr::FRAG_MAX_K))
+        return -fail(std::string(name) + ": K (bits 8-15 of flags, " + macro + ") must be in 1..32, got " + std::to_string(K));
+    return K;
+}
+
+// The two inputs of a fragment-gradient call, the caller's face and bary-gradient buffers, requested once each.  r / R: the
+// renderer in the messages, "tri" / "TRI" or "tet" / "TET".
+int fragment_grad_inputs(dmr_alloc_fn alloc, void* ctx, const char* r, const std::string& R, int face_id, int grad_id, size_t npix, int K,
+                         const int32_t** face, const float** grad) {
+    if (!alloc) return fail("null argument");
+    const std::string no = "DMR_FLAG_" + R + "_FRAGMENT_GRADS: no " + r + " fragment ";
+    *face = static_cast<const int32_t*>(alloc(ctx, face_id, dmr::FragmentLists::face_bytes(npix, K)));
+    if (!*face) return fail(no + "face buffer (DMR_BUF_" + R + "_FRAGMENT_FACES)");
+    *grad = static_cast<const float*>(alloc(ctx, grad_id, dmr::FragmentLists::bary_bytes(npix, K)));
+    if (!*grad) return fail(no + "bary gradient buffer (DMR_BUF_" + R + "_FRAGMENT_BARY_GRADS)");
+    return 0;
+}
+
 constexpr size_t ALIGN = 256;
 inline size_t up(size_t n) { return (n + ALIGN - 1) & ~(ALIGN - 1); }
 
@@ -607,13 +629,12 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
     if (!alloc || !num_rendered || !out_color || !out_depth) return fail("null argument");
     *num_rendered = 0;
     // DMR_FLAG_TRI_FRAGMENTS: K fragment slots per pixel, K in bits 8-15 of the flags
-    const int frag_k = (s->flags & DMR_FLAG_TRI_FRAGMENTS) ? DMR_FRAGMENTS_K(s->flags) : 0;
-    if ((s->flags & DMR_FLAG_TRI_FRAGMENTS) && (frag_k < 1 || frag_k > 32))
-        return fail("DMR_FLAG_TRI_FRAGMENTS: K (bits 8-15 of flags, DMR_FRAGMENTS_FLAGS(K)) must be in 1..32, got " + std::to_string(frag_k));
+    const int frag_k = fragment_k(s, DMR_FLAG_TRI_FRAGMENTS, "DMR_FLAG_TRI_FRAGMENTS", "DMR_FRAGMENTS_FLAGS(K)");
+    if (frag_k < 0) return 1;
     if (s->P == 0 || s->F == 0) return 0;  // render.cu:105 (and Q16: F == 0)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* fragments = nullptr;  // the caller's [face | bary | count], requested once
-    if (caller_output(alloc, ctx, DMR_BUF_TRI_FRAGMENTS, frag_k ? 4 * d.npix * (3 * (size_t)frag_k + 1) : 0, "tri fragment", false, st, &fragments))
+    if (caller_output(alloc, ctx, DMR_BUF_TRI_FRAGMENTS, frag_k ? dmr::FragmentLists::bytes(d.npix, frag_k) : 0, "tri fragment", false, st, &fragments))
         return 1;
     Scratch last{};  // the scratch of the call's final k_tri_forward: a redo (a refuted size estimate) renders a second time
     auto render = [&](const Scratch& c, dmr::ListSize size) {
@@ -641,9 +662,8 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     if (check_scene(s, false, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // DMR_FLAG_TRI_FRAGMENT_GRADS: K slots per pixel in bits 8-15 of the flags, as for the forward
-    const int frag_k = (s->flags & DMR_FLAG_TRI_FRAGMENT_GRADS) ? DMR_FRAGMENTS_K(s->flags) : 0;
-    if ((s->flags & DMR_FLAG_TRI_FRAGMENT_GRADS) && (frag_k < 1 || frag_k > 32))
-        return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: K (bits 8-15 of flags, DMR_FRAGMENTS_K) must be in 1..32, got " + std::to_string(frag_k));
+    const int frag_k = fragment_k(s, DMR_FLAG_TRI_FRAGMENT_GRADS, "DMR_FLAG_TRI_FRAGMENT_GRADS", "DMR_FRAGMENTS_K");
+    if (frag_k < 0) return 1;
     // DMR_FLAG_TRI_EXACT_GRADS / DMR_FLAG_TRI_CAMERA_GRADS: which k_tri_backward_hits; with camera gradients the caller's
     // [B][dL/dinv_mv 16 | dL/dinv_proj 16] buffer, requested once
     const bool camera = (s->flags & DMR_FLAG_TRI_CAMERA_GRADS) != 0;
@@ -656,13 +676,8 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     // the caller's two inputs, requested once each (not when idle: the term is zero then)
     const int32_t* frag_face = nullptr;
     const float* frag_grad = nullptr;
-    if (frag_k && !idle) {
-        if (!alloc) return fail("null argument");
-        frag_face = static_cast<const int32_t*>(alloc(ctx, DMR_BUF_TRI_FRAGMENT_FACES, 4 * d.npix * (size_t)frag_k));
-        if (!frag_face) return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: no tri fragment face buffer (DMR_BUF_TRI_FRAGMENT_FACES)");
-        frag_grad = static_cast<const float*>(alloc(ctx, DMR_BUF_TRI_FRAGMENT_BARY_GRADS, 8 * d.npix * (size_t)frag_k));
-        if (!frag_grad) return fail("DMR_FLAG_TRI_FRAGMENT_GRADS: no tri fragment bary gradient buffer (DMR_BUF_TRI_FRAGMENT_BARY_GRADS)");
-    }
+    if (frag_k && !idle && fragment_grad_inputs(alloc, ctx, "tri", "TRI", DMR_BUF_TRI_FRAGMENT_FACES, DMR_BUF_TRI_FRAGMENT_BARY_GRADS, d.npix, frag_k, &frag_face, &frag_grad))
+        return 1;
     if (idle) {
         if (s->P > 0) {
             DMR_HIP(hipMemsetAsync(dL_dverts, 0, sizeof(float) * 3 * (size_t)s->P, st));
@@ -746,9 +761,8 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
     *num_rendered = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // DMR_FLAG_TET_FRAGMENTS: K fragment slots per pixel, K in bits 8-15 of the flags as for the tri flag
-    int frag_k = (s->flags & DMR_FLAG_TET_FRAGMENTS) ? DMR_FRAGMENTS_K(s->flags) : 0;
-    if ((s->flags & DMR_FLAG_TET_FRAGMENTS) && (frag_k < 1 || frag_k > 32))
-        return fail("DMR_FLAG_TET_FRAGMENTS: K (bits 8-15 of flags, DMR_TET_FRAGMENTS_FLAGS(K)) must be in 1..32, got " + std::to_string(frag_k));
+    int frag_k = fragment_k(s, DMR_FLAG_TET_FRAGMENTS, "DMR_FLAG_TET_FRAGMENTS", "DMR_TET_FRAGMENTS_FLAGS(K)");
+    if (frag_k < 0) return 1;
     if (s->P == 0 || s->F == 0) frag_k = 0;  // nothing marches: the caller's initialisation (-1 / 0) is the result, no request
     // the fragments are read out of the march sequence: room for the first K steps of every pixel, whatever the estimate says
     const size_t frag_steps = ((size_t)frag_k + 3) / 4 * 4;
@@ -758,7 +772,7 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
                     " steps for each of " + std::to_string((size_t)d.ntiles * dmr::TILE_PIX) + " tile pixels), beyond the budget of " +
                     std::to_string(TET_SEQ_BUDGET) + " bytes (16 GiB)");
     float* fragments = nullptr;  // the caller's [face | bary | count], requested once
-    if (caller_output(alloc, ctx, DMR_BUF_TET_FRAGMENTS, frag_k ? 4 * d.npix * (3 * (size_t)frag_k + 1) : 0, "tet fragment", false, st, &fragments))
+    if (caller_output(alloc, ctx, DMR_BUF_TET_FRAGMENTS, frag_k ? dmr::FragmentLists::bytes(d.npix, frag_k) : 0, "tet fragment", false, st, &fragments))
         return 1;
     auto render = [&](const Scratch& c, dmr::ListSize) {
         const dmr::TetImageState img = tet_image(c);
@@ -780,9 +794,8 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     if (check_scene(s, true, d)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // DMR_FLAG_TET_FRAGMENT_GRADS (implies the full gradients): K slots per pixel in bits 8-15 of the flags, as for the forward
-    const int frag_k = (s->flags & DMR_FLAG_TET_FRAGMENT_GRADS) ? DMR_FRAGMENTS_K(s->flags) : 0;
-    if ((s->flags & DMR_FLAG_TET_FRAGMENT_GRADS) && (frag_k < 1 || frag_k > 32))
-        return fail("DMR_FLAG_TET_FRAGMENT_GRADS: K (bits 8-15 of flags, DMR_FRAGMENTS_K) must be in 1..32, got " + std::to_string(frag_k));
+    const int frag_k = fragment_k(s, DMR_FLAG_TET_FRAGMENT_GRADS, "DMR_FLAG_TET_FRAGMENT_GRADS", "DMR_FRAGMENTS_K");
+    if (frag_k < 0) return 1;
     // DMR_FLAG_TET_CAMERA_GRADS (implies the full gradients): the caller's [B][dL/dinv_mv 16 | dL/dinv_proj 16 | dL/dmv 16 |
     // dL/dproj 16] buffer, requested once, summed from per-tile partials in the work space
     const bool camera = (s->flags & DMR_FLAG_TET_CAMERA_GRADS) != 0;
@@ -804,13 +817,8 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     // the caller's two inputs, requested once each (not for an empty band: the term is zero then)
     const int32_t* frag_face = nullptr;
     const float* frag_grad = nullptr;
-    if (frag_k && band_tiles > 0) {
-        if (!alloc) return fail("null argument");
-        frag_face = static_cast<const int32_t*>(alloc(ctx, DMR_BUF_TET_FRAGMENT_FACES, 4 * d.npix * (size_t)frag_k));
-        if (!frag_face) return fail("DMR_FLAG_TET_FRAGMENT_GRADS: no tet fragment face buffer (DMR_BUF_TET_FRAGMENT_FACES)");
-        frag_grad = static_cast<const float*>(alloc(ctx, DMR_BUF_TET_FRAGMENT_BARY_GRADS, 8 * d.npix * (size_t)frag_k));
-        if (!frag_grad) return fail("DMR_FLAG_TET_FRAGMENT_GRADS: no tet fragment bary gradient buffer (DMR_BUF_TET_FRAGMENT_BARY_GRADS)");
-    }
+    if (frag_k && band_tiles > 0 && fragment_grad_inputs(alloc, ctx, "tet", "TET", DMR_BUF_TET_FRAGMENT_FACES, DMR_BUF_TET_FRAGMENT_BARY_GRADS, d.npix, frag_k, &frag_face, &frag_grad))
+        return 1;
     float* cam_part = nullptr;  // every tile's partial (launch_tet_backward)
     if (cam_out) {
         cam_part = static_cast<float*>(alloc(ctx, DMR_BUF_WORK, 256 * (size_t)band_tiles * (size_t)s->B));

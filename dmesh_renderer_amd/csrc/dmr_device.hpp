@@ -359,4 +359,110 @@ __device__ __forceinline__ EdgeSetup edge_setup(V2 p1, V2 p2, V2 p3, int x0, int
 
 static_assert(sizeof(FaceCov) == 32, "FaceCov");
 
+// ---------------------------------------------------------------------------
+// Gradients of the fragment lists' barycentrics: what k_tri_fragment_grads (dmr_tri.hip) and k_tet_fragment_grads
+// (dmr_tet.hip) share.  Compiled as both kernels are: the scalar combinations may contract, the V3 helpers do not.
+// (k_tri_backward_hits and tet_camera_tile hold look-alike code of their own on purpose: DESIGN.md 5b.)
+// ---------------------------------------------------------------------------
+#pragma clang fp contract(fast)
+
+// A lane's pixel and its K slots of the caller's face i32 [B,K,H,W] and grad f32 [B,K,2,H,W].  The forward fragment kernels'
+// pixel-to-lane mapping: one workgroup per tile, 8 x 8 pixels per wave, so neighbouring lanes mostly hold the same face.
+struct FragSlots {
+    int px, py;
+    bool inside;
+    int64_t HW, face0, grad0;
+    __device__ __forceinline__ FragSlots(int tx, int ty, int b, int K, int W, int H) {
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        px = tx * TILE + (wave & 1) * 8 + (lane & 7); py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
+        inside = px < W && py < H;
+        HW = (int64_t)H * W;
+        const int64_t pix_id = (int64_t)W * py + px;
+        face0 = (int64_t)b * K * HW + pix_id; grad0 = (int64_t)b * K * 2 * HW + pix_id;
+    }
+    __device__ __forceinline__ int64_t face_at(int k) const { return face0 + (int64_t)k * HW; }
+    __device__ __forceinline__ int64_t grad_at(int k, int c) const { return grad0 + (int64_t)(2 * k + c) * HW; }  // c: 0 dL/du, 1 dL/dv
+};
+
+// Moeller-Trumbore (u, v) = (nu, nv) / denom of the ray (o, d) on the face (p0, p1, p2), with T = o - p0, E1 = p1 - p0,
+// E2 = p2 - p0, P = d x E2, Q = T x E1: nu = P . T, nv = Q . d, denom = P . E1 -- the forward's operations (forward_uv,
+// ray_tri_hit: V3 helpers, exact division), kept for the derivative.  The caller forms its upstream (dL/du, dL/dv) of the
+// unclamped pair in between (the tri renderer sends it through the clamp region's Jacobian, which it selects by u(), v()).
+struct PairUV {
+    V3 T, E1, E2, P, Q;
+    float inv_denom, nu, nv;
+    // false: denom == 0, no (u, v) -- the forwards skip such a pair
+    __device__ __forceinline__ bool set(V3 o, V3 d, V3 p0, V3 p1, V3 p2) {
+        T = o - p0; E1 = p1 - p0; E2 = p2 - p0;
+        P = cross(d, E2); Q = cross(T, E1);
+        const float denom = dot(P, E1);
+        if (denom == 0.0f) return false;
+        inv_denom = 1.0f / denom;
+        nu = dot(P, T); nv = dot(Q, d);
+        return true;
+    }
+    __device__ __forceinline__ float u() const { return nu * inv_denom; }
+    __device__ __forceinline__ float v() const { return nv * inv_denom; }
+    // The exact derivative: with su = dL/du / denom, sv = dL/dv / denom, sb = (su nu + sv nv) / denom
+    //   dL/dT = su P + sv (E1 x d),  dL/dp1 = sv (d x T) - sb P,  dL/dp2 = su (T x d) - sb (E1 x d),  dL/dp0 = -(dT + dp1 + dp2)
+    //   and, RAY, dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)        (dL/do = dL/dT)
+    template <bool RAY>
+    __device__ __forceinline__ void grad(V3 d, float dL_du, float dL_dv, V3& dp0, V3& dp1, V3& dp2, V3& dT, V3& dd) const {
+        const float su = dL_du * inv_denom, sv = dL_dv * inv_denom;
+        const float sb = (su * nu + sv * nv) * inv_denom;
+        const V3 E1d = cross(E1, d);
+        dT = su * P + sv * E1d;
+        dp1 = sv * cross(d, T) - sb * P;
+        dp2 = su * cross(T, d) - sb * E1d;
+        dp0 = -(dT + dp1 + dp2);
+        if constexpr (RAY) dd = su * cross(E2, T) + sv * Q + sb * cross(E1, E2);
+    }
+};
+
+// A pixel's summed dL/dd (gd) and dL/do (go) -> c[3 col + row]: dL/dinv_mv rows 0-2 (col 3 = dL/do), c[12 + 3 col + row]:
+// dL/dinv_proj rows 0-2 (the w rows get nothing), through d = w / len, w = inv_mv (pv, 1) - o, pv = inv_proj (nd, -1, 1)
+// (pixel_ray<TET>; nd: the ndc it sends the ray through).  len = max(|w|, 1e-4) (TET) / |w| + 1e-7, so
+// dL/dw = gd / len - w (w . gd) / (|w| len^2), where the tet length is not clamped.
+template <bool TET>
+__device__ __forceinline__ void ray_chain(const float* __restrict__ im, const float* __restrict__ ip, V2 nd, V3 o, V3 gd, V3 go, float (&c)[24]) {
+    const float ndc[4] = {nd.x, nd.y, -1.0f, 1.0f};
+    const V4 pv = xform4x4({nd.x, nd.y, -1.0f}, ip);
+    const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
+    const V3 w = V3{pw.x, pw.y, pw.z} - o;
+    const float n = sqrtf(dot(w, w)), len = TET ? fmaxf(n, 0.0001f) : n + 0.0000001f;
+    const float wg = w.x * gd.x + w.y * gd.y + w.z * gd.z;
+    const float kk = TET ? (n > 0.0001f ? wg / (n * n * n) : 0.f) : (n > 0.f ? wg / (n * len * len) : 0.f);
+    const float dw[3] = {gd.x / len - kk * w.x, gd.y / len - kk * w.y, gd.z / len - kk * w.z};
+    const float pvv[3] = {pv.x, pv.y, pv.z};
+#pragma unroll
+    for (int row = 0; row < 3; row++) {
+#pragma unroll
+        for (int col = 0; col < 3; col++) c[3 * col + row] = dw[row] * pvv[col];
+        const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];  // (R^T dL/dw)_row, R = inv_mv's upper 3x3
+#pragma unroll
+        for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
+    }
+    c[9] = go.x; c[10] = go.y; c[11] = go.z;
+}
+
+// Those 24 values summed over the 256-thread workgroup (red: 4 x 24 floats of LDS) and added to the first 32 floats of the
+// tile's camera partial, entry m[4 col + row] of inv_mv (threads 0-15) / inv_proj (16-31): the workgroup is their one writer.
+__device__ __forceinline__ void ray_chain_add(float (&c)[24], float (*red)[24], float* __restrict__ tile_part) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 24; i++)
+#pragma unroll
+        for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 24; i++) red[tid >> 6][i] = c[i];
+    }
+    __syncthreads();
+    if (tid < 32) {
+        const int row = tid & 3, col = (tid >> 2) & 3, i = 12 * (tid >> 4) + 3 * col + row;
+        if (row != 3) tile_part[tid] += red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    }
+}
+#pragma clang fp contract(off)
+
 }  // namespace dmr

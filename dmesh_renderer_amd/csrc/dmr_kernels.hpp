@@ -158,13 +158,25 @@ struct alignas(16) HitRecord { uint32_t id; uint32_t pixel; float T; float dL_da
 // it through the size port -- with the segment-overflow flag if a list left its segment -- as launch_scan_tiles does on the
 // exact path
 struct ListSize { int* num_rendered; SizeOut out; uint32_t blocks; };
+// The fragment lists of either renderer (DMR_FLAG_TRI_FRAGMENTS / DMR_FLAG_TET_FRAGMENTS): K slots per pixel, 1 <= K <=
+// FRAG_MAX_K, in the caller's ONE buffer [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W] of npix = B H W pixels.
+// The inputs of the gradient flags: face as above, the gradient of bary in its layout.
+constexpr int FRAG_MAX_K = 32;
+struct FragmentLists {
+    int32_t* face; float* bary; int32_t* count;
+    FragmentLists(void* buf, size_t npix, int K)
+        : face(static_cast<int32_t*>(buf)), bary(reinterpret_cast<float*>(face + (size_t)K * npix)), count(face + 3 * (size_t)K * npix) {}
+    static size_t bytes(size_t npix, int K) { return 4 * npix * (3 * (size_t)K + 1); }
+    static size_t face_bytes(size_t npix, int K) { return 4 * npix * (size_t)K; }
+    static size_t bary_bytes(size_t npix, int K) { return 8 * npix * (size_t)K; }
+};
 void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
                         const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
                         float* out_color, float* out_depth, hipStream_t st, bool alpha = false,
                         ListSize size = ListSize{nullptr, NOWHERE, 0u});
 // DMR_FLAG_TRI_FRAGMENTS, behind the call's final launch_tri_forward (whose state it reads: sorted lists, coverage masks,
 // n_contrib): per pixel of the band the first K blended (pixel, face) pairs in blend order and their number, into the
-// caller's buffer [face i32 B,K,H,W | bary (u_c, v_c) f32 B,K,2,H,W | count i32 B,H,W] (unused slots -1 / 0).  K in 1..32.
+// caller's buffer (FragmentLists; bary: (u_c, v_c); unused slots -1 / 0).
 // No stage of its own, no size, no host wait.
 void launch_tri_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, const uint32_t* tile_offset, const uint32_t* face_list,
                           TriImageState img, int K, void* fragments, hipStream_t st);
@@ -198,9 +210,10 @@ void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* 
                               hipStream_t st, int grads = TRI_GRAD_REF, float* cam_part = nullptr);
 // DMR_FLAG_TRI_FRAGMENT_GRADS, behind launch_tri_backward_hits and ahead of the unpack / launch_camera_reduce: for every pixel of
 // the band and each of its K slots, dL/d(u_c, v_c) (frag_grad, f32 [B,K,2,H,W]) of the pair (pixel, frag_face[slot], i32
-// [B,K,H,W]) through the clamp and the exact derivative of the pair's (u, v), added into the position columns of the packed
-// vertex rows and, cam_part != null, into every tile's 32-float camera partial.  A face outside [0, F) is no pair.  Reads the
-// scene, the contract-layout inverse matrices and the two inputs only.  K in 1..32.  No stage of its own, no size, no host wait.
+// [B,K,H,W]) through the clamp and the exact derivative of the pair's (u, v) (PairUV, dmr_device.hpp), added into the position
+// columns of the packed vertex rows and, cam_part != null, into every tile's 32-float camera partial (ray_chain).  A face outside
+// [0, F) is no pair.  Reads the scene, the contract-layout inverse matrices and the two inputs only.  No stage of its own, no
+// size, no host wait.
 void launch_tri_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TriImageState img, int K, const int32_t* frag_face,
                                const float* frag_grad, float* vrow, float* cam_part, hipStream_t st);
 // sums the B * tiles partials of a camera variant per view, in a fixed order: out [B][width]; width 32 (the tri
@@ -255,9 +268,8 @@ void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetI
                         float* out_color, float* out_depth, float* out_active, hipStream_t st, bool alpha = false);
 // DMR_FLAG_TET_FRAGMENTS, behind the call's final launch_tet_forward (whose state it reads: n_contrib, is_active and the march
 // sequence, which such a call sizes to at least K steps rounded up to 4): per pixel of the band the first K faces the march
-// composited, front to back, the (u, v) of the pixel's ray on each and their number, into the caller's buffer [face i32
-// B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W] (unused slots -1 / 0; count = n_contrib where is_active, else 0).  K in
-// 1..32.  No stage of its own, no size, no host wait.
+// composited, front to back, the (u, v) of the pixel's ray on each and their number, into the caller's buffer (FragmentLists;
+// unused slots -1 / 0; count = n_contrib where is_active, else 0).  No stage of its own, no size, no host wait.
 void launch_tet_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, void* fragments, hipStream_t st);
 void launch_tet_zero_grads(float* dL_dvcolor, int64_t n_vcolor, float* dL_dfopacity, int64_t n_fopacity, hipStream_t st);
 // Two launches, of which the device runs one: k_tet_backward_seq when the forward's march sequence is complete
@@ -273,9 +285,10 @@ void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, Tet
 // DMR_FLAG_TET_FRAGMENT_GRADS, behind launch_tet_backward (which zeroed and filled dL_dverts and stored every band tile's cam_part)
 // and ahead of launch_camera_reduce: for every pixel of the band and each of its K slots, dL/d(u, v) (frag_grad, f32
 // [B,K,2,H,W]) of the pair (pixel, frag_face[slot], i32 [B,K,H,W]) through the exact derivative of the pair's unclamped (u, v) on
-// the forward's ray, added into dL_dverts [P,3] and, cam_part != null, into the first 32 floats (dL/dinv_mv | dL/dinv_proj) of
-// every tile's 64-float camera partial.  A face outside [0, F) is no pair.  Reads the scene, the face records and the seed the
-// forward left, the contract-layout inverse matrices and the two inputs only.  K in 1..32.  No stage of its own, no size, no host wait.
+// the forward's ray (PairUV, dmr_device.hpp), added into dL_dverts [P,3] and, cam_part != null, into the first 32 floats
+// (dL/dinv_mv | dL/dinv_proj) of every tile's 64-float camera partial (ray_chain).  A face outside [0, F) is no pair.  Reads the
+// scene, the face records and the seed the forward left, the contract-layout inverse matrices and the two inputs only.  No stage
+// of its own, no size, no host wait.
 void launch_tet_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, const int32_t* frag_face,
                                const float* frag_grad, float* dL_dverts, float* cam_part, hipStream_t st);
 

@@ -1264,22 +1264,19 @@ k_tet_fragments(TetParams p, int K, int32_t* __restrict__ out_face, float* __res
 // k_tet_fragment_grads (DMR_FLAG_TET_FRAGMENT_GRADS) -- dL/d(u, v) of the caller's fragment lists -> vertex positions (and rays).
 //
 // A launch of its own behind the call's two backward launches (which zeroed and filled dL_dverts and stored every band tile's
-// cam_part) and ahead of launch_camera_reduce.  k_tet_fragments' grid and pixel-to-lane mapping: one workgroup per tile of the
-// band, an 8 x 8 pixel block per wave, so neighbouring lanes mostly hold the same face in the same slot.  A lane owns its
-// pixel: it builds the forward's ray once (pixel_ray<true>, the seed out of the image state) and, for each of the K slots,
-// takes the face's three vertices from its record (the next slot's id, record and upstream in flight while this one computes, two
-// sets used alternately as k_tet_fragments does), recomputes denom, nu, nv with ray_tri_hit's operations and forms dp0, dp1, dp2,
-// dT and dL/dd with the formulas of k_tri_fragment_grads' EXACT branch (dmr_tri.hip) -- the upstream enters directly: (u, v)
-// is unclamped.  It reads nothing of the march (no sequence, no n_contrib, no is_active): the pairs are the caller's; a face
-// outside [0, F), an upstream of (0, 0) and denom == 0 are no pair.
+// cam_part) and ahead of launch_camera_reduce.  k_tet_fragments' grid: one workgroup per tile of the band.  A lane owns its
+// pixel (FragSlots, dmr_device.hpp): it builds the forward's ray once (pixel_ray<true>, the seed out of the image state) and,
+// for each of the K slots, takes the face's three vertices from its record (the next slot's id, record and upstream in flight
+// while this one computes, two sets used alternately as k_tet_fragments does) and forms the pair's exact derivative (PairUV)
+// -- the upstream enters directly: (u, v) is unclamped.  It reads nothing of the march (no sequence, no n_contrib, no
+// is_active): the pairs are the caller's; a face outside [0, F), an upstream of (0, 0) and denom == 0 are no pair.
 // The nine position values of a pair are merged across the lanes that hold the same face (tet_accumulate's four DPP levels,
 // under this kernel's own use of them: a face uniform over the wave reaches LDS from 4 lanes, not 64), then summed per face in
 // a table of this kernel's own (TetAccum's probing, 9 f64 cells a slot: 33.6 KB) and leave once per tile into dL_dverts with
 // float atomics; a full table, a long probe sequence or a non-finite value goes out directly.  Camera variant: sum dT (= dL/do)
-// and sum dL/dd stay in the lane's registers over the slots, then one chain per pixel through d = w / max(|w|, 1e-4) -- the
-// arithmetic of tet_camera_tile with go, gd set and the four depth sums zero --, a block sum, and the tile's first 32 floats of
-// cam_part (dL/dinv_mv | dL/dinv_proj; the direct dL/dmv | dL/dproj half has no such term) gain it: this workgroup is their one
-// writer behind the backward.  A tile without a contributing pair neither flushes nor touches cam_part.
+// and sum dL/dd stay in the lane's registers over the slots, then one ray_chain<true> per pixel, a block sum, and the tile's
+// first 32 floats of cam_part (dL/dinv_mv | dL/dinv_proj; the direct dL/dmv | dL/dproj half has no such term) gain it, behind
+// the backward.  A tile without a contributing pair neither flushes nor touches cam_part.
 // ---------------------------------------------------------------------------
 constexpr int TET_FRAG_TBL = 448;  // slots (a multiple of 16: the flush covers 16 per pass)
 struct TetFragGradLds {
@@ -1294,16 +1291,14 @@ __global__ void __launch_bounds__(256)
 k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, const float* __restrict__ frag_grad,
                      float* __restrict__ dL_dverts, float* __restrict__ cam_part) {
     __shared__ TetFragGradLds L;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int tx = blockIdx.x, ty = blockIdx.y + p.r0, b = blockIdx.z;
-    const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < p.W && py < p.H;
-    const int64_t HW = (int64_t)p.H * p.W, pix_id = (int64_t)p.W * py + px, bpix = (int64_t)b * HW + pix_id;
-    const int64_t face0 = (int64_t)b * K * HW + pix_id, grad0 = (int64_t)b * K * 2 * HW + pix_id;
+    const FragSlots S(tx, ty, b, K, p.W, p.H);
+    const int64_t bpix = (int64_t)b * S.HW + (int64_t)p.W * S.py + S.px;
     // slot k of this lane: the face (-1: no pair -- outside the image, beyond K, or an id that is not a face's) ...
     auto load_face = [&](int k) -> int {
-        if (!inside || k >= K) return -1;
-        const int f = frag_face[face0 + (int64_t)k * HW];
+        if (!S.inside || k >= K) return -1;
+        const int f = frag_face[S.face_at(k)];
         return (uint32_t)f < (uint32_t)p.F ? f : -1;
     };
     // ... and what its gradient needs: the three vertices and the upstream
@@ -1312,7 +1307,7 @@ k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, 
         if (face < 0) return;
         const float4* fq = reinterpret_cast<const float4*>(p.facerec + face);
         r.f0 = fq[0]; r.f1 = fq[1]; r.f2 = fq[2];
-        r.e1 = frag_grad[grad0 + (int64_t)(2 * k) * HW]; r.e2 = frag_grad[grad0 + (int64_t)(2 * k + 1) * HW];
+        r.e1 = frag_grad[S.grad_at(k, 0)]; r.e2 = frag_grad[S.grad_at(k, 1)];
     };
     int f_cur = load_face(0), f_nxt = load_face(1);  // (requested before the table is cleared)
     Rec rc = {}, rn = {};
@@ -1324,7 +1319,7 @@ k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, 
     }
     if (tid == 0) L.any = 0;
     V3 ro = {0, 0, 0}, rd = {0, 0, 0};
-    if (inside) pixel_ray<true>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd, *p.seed, (uint64_t)bpix);
+    if (S.inside) pixel_ray<true>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, S.px, S.py, p.W, p.H, ro, rd, *p.seed, (uint64_t)bpix);
     V3 camT = {0.f, 0.f, 0.f}, camD = {0.f, 0.f, 0.f};  // camera variant: sum of dL/dT (= dL/do), dL/d(ray direction) of this pixel
     bool some = false;
     const TetAccum<TET_FRAG_TBL> acc{L.key, L.val};
@@ -1338,40 +1333,24 @@ k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, 
 #pragma unroll
         for (int c = 0; c < 10; c++) g[c] = 0.f;
         bool act = face >= 0 && !(cur.e1 == 0.f && cur.e2 == 0.f);  // nothing arrives for a pair with a zero upstream
+        PairUV uv;
+        if (act && !uv.set(ro, rd, {cur.f0.x, cur.f0.y, cur.f0.z}, {cur.f0.w, cur.f1.x, cur.f1.y}, {cur.f1.z, cur.f1.w, cur.f2.x}))
+            act = false;  // ray_tri_hit has no (u, v) for such a pair
         if (act) {
-            const V3 p0 = {cur.f0.x, cur.f0.y, cur.f0.z}, p1 = {cur.f0.w, cur.f1.x, cur.f1.y}, p2 = {cur.f1.z, cur.f1.w, cur.f2.x};
-            // ray_tri_hit's operations (dmr_device.hpp); its u = nu * inv_denom, v = nv * inv_denom
-            const V3 xT = ro - p0, xE1 = p1 - p0, xE2 = p2 - p0;
-            const V3 xP = cross(rd, xE2), xQ = cross(xT, xE1);
-            const float denom = dot(xP, xE1);
-            if (denom == 0.0f) act = false;  // ray_tri_hit has no (u, v) for such a pair
-            else {
-                const float inv_denom = 1.0f / denom;
-                const float nu = dot(xP, xT), nv = dot(xQ, rd);
-                // the exact derivative of (u, v) = ((d x E2) . T, (T x E1) . d) / ((d x E2) . E1) (k_tri_fragment_grads, EXACT)
-                const float su = cur.e1 * inv_denom, sv = cur.e2 * inv_denom;
-                const float sb = (su * nu + sv * nv) * inv_denom;
-                const V3 xE1d = cross(xE1, rd);
-                const V3 dT = su * xP + sv * xE1d;
-                const V3 dp1 = sv * cross(rd, xT) - sb * xP;
-                const V3 dp2 = su * cross(xT, rd) - sb * xE1d;
-                const V3 dp0 = -(dT + dp1 + dp2);
-                if constexpr (CAM) {
-                    camD = camD + (su * cross(xE2, xT) + sv * xQ + sb * cross(xE1, xE2));  // dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)
-                    camT = camT + dT;
-                }
-                some = true;
-                g[0] = dp0.x; g[1] = dp0.y; g[2] = dp0.z; g[3] = dp1.x; g[4] = dp1.y; g[5] = dp1.z; g[6] = dp2.x; g[7] = dp2.y; g[8] = dp2.z;
-                // a lane with a non-finite value adds its rows directly and takes no part in the merges (0 * inf would leak into
-                // the partner's face)
-                float chk = 0.f;
+            V3 dp0, dp1, dp2, dT, gd;
+            uv.grad<CAM>(rd, cur.e1, cur.e2, dp0, dp1, dp2, dT, gd);
+            if constexpr (CAM) { camD = camD + gd; camT = camT + dT; }
+            some = true;
+            g[0] = dp0.x; g[1] = dp0.y; g[2] = dp0.z; g[3] = dp1.x; g[4] = dp1.y; g[5] = dp1.z; g[6] = dp2.x; g[7] = dp2.y; g[8] = dp2.z;
+            // a lane with a non-finite value adds its rows directly and takes no part in the merges (0 * inf would leak into
+            // the partner's face)
+            float chk = 0.f;
 #pragma unroll
-                for (int c = 0; c < 9; c++) chk = fmaf(g[c], 0.f, chk);
-                if (!(chk == 0.f)) {
+            for (int c = 0; c < 9; c++) chk = fmaf(g[c], 0.f, chk);
+            if (!(chk == 0.f)) {
 #pragma unroll
-                    for (int c = 0; c < 9; c++) { atomicAdd(&dL_dverts[3 * p.faces[3 * face + c / 3] + c % 3], g[c]); g[c] = 0.f; }
-                    act = false;
-                }
+                for (int c = 0; c < 9; c++) { atomicAdd(&dL_dverts[3 * p.faces[3 * face + c / 3] + c % 3], g[c]); g[c] = 0.f; }
+                act = false;
             }
         }
         int key = act ? face : -1;  // -1: nothing (left) in this lane
@@ -1399,49 +1378,14 @@ k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, 
     __syncthreads();
     if (!L.any) return;  // uniform
     if constexpr (CAM) {
-        // this lane's pixel: dL/dd through d = w / max(|w|, 1e-4), w = inv_mv (pv, 1) - o, pv = inv_proj (ndc, -1, 1) (pixel_ray<true>)
-        // to the view's two inverse matrices, as tet_camera_tile does.  c[3 col + row]: dL/dinv_mv rows 0-2 (col 3 = dL/do),
-        // c[12 + 3 col + row]: dL/dinv_proj rows 0-2; the w rows get nothing.
         float c[24];
 #pragma unroll
         for (int i = 0; i < 24; i++) c[i] = 0.f;
-        if (some) {  // (inside)
-            const float* im = p.inv_mv + 16 * b;
-            const float* ip = p.inv_proj + 16 * b;
-            const V2 nd = pixel_ndc<true>(px, py, p.W, p.H, *p.seed, (uint64_t)bpix);
-            const float ndc[4] = {nd.x, nd.y, -1.0f, 1.0f};
-            const V4 pv = xform4x4({nd.x, nd.y, -1.0f}, ip);
-            const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
-            const V3 w = V3{pw.x, pw.y, pw.z} - V3{im[12], im[13], im[14]};
-            const float n = sqrtf(dot(w, w)), len = fmaxf(n, 0.0001f);
-            // dL/dw = gd / len - w (w . gd) / n^3 where the length is not clamped
-            const float kk = n > 0.0001f ? (w.x * camD.x + w.y * camD.y + w.z * camD.z) / (n * n * n) : 0.f;
-            const float dw[3] = {camD.x / len - kk * w.x, camD.y / len - kk * w.y, camD.z / len - kk * w.z};
-            const float pvv[3] = {pv.x, pv.y, pv.z};
-#pragma unroll
-            for (int row = 0; row < 3; row++) {
-#pragma unroll
-                for (int col = 0; col < 3; col++) c[3 * col + row] = dw[row] * pvv[col];
-                const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];  // (R^T dL/dw)_row
-#pragma unroll
-                for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
-            }
-            c[9] = camT.x; c[10] = camT.y; c[11] = camT.z;
-        }
-#pragma unroll
-        for (int i = 0; i < 24; i++)
-#pragma unroll
-            for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 24; i++) L.red[wave][i] = c[i];
-        }
-        __syncthreads();
-        if (tid < 32) {  // entry tid of the tile's partial, m[4 col + row] of inv_mv (tid < 16) / inv_proj
-            const int row = tid & 3, col = (tid >> 2) & 3, i = 12 * (tid >> 4) + 3 * col + row;
-            const int64_t tile = ((int64_t)b * gridDim.y + blockIdx.y) * p.gx + tx;  // launch_tet_backward's
-            if (row != 3) cam_part[64 * tile + tid] += L.red[0][i] + L.red[1][i] + L.red[2][i] + L.red[3][i];
-        }
+        const float* im = p.inv_mv + 16 * b;
+        if (some)  // (inside) this lane's pixel, through the forward's (jittered) sample
+            ray_chain<true>(im, p.inv_proj + 16 * b, pixel_ndc<true>(S.px, S.py, p.W, p.H, *p.seed, (uint64_t)bpix), {im[12], im[13], im[14]}, camD, camT, c);
+        const int64_t tile = ((int64_t)b * gridDim.y + blockIdx.y) * p.gx + tx;  // launch_tet_backward's
+        ray_chain_add(c, L.red, cam_part + 64 * tile);
     }
     // every face of the table goes out once: 16 lanes per slot (9 used), the three vertex-position rows
     const int sub = tid & 15;
@@ -1506,13 +1450,10 @@ void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetI
 }
 
 void launch_tet_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, void* fragments, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > 32) return;
+    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
     TetParams p = make_params(s, gx, gy, r0, img);
-    const size_t npix = (size_t)s.B * s.H * s.W;  // [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W]
-    int32_t* face = static_cast<int32_t*>(fragments);
-    float* bary = reinterpret_cast<float*>(face + (size_t)K * npix);
-    int32_t* count = face + 3 * (size_t)K * npix;
-    k_tet_fragments<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, K, face, bary, count);
+    const FragmentLists out(fragments, (size_t)s.B * s.H * s.W, K);
+    k_tet_fragments<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
 }
 
 // both gradient tensors zeroed by one launch (two hipMemsetAsync are three fill kernels of ~4.6 us each)
@@ -1560,7 +1501,7 @@ void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, Tet
 
 void launch_tet_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, const int32_t* frag_face,
                                const float* frag_grad, float* dL_dverts, float* cam_part, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > 32 || !frag_face || !frag_grad || !dL_dverts) return;
+    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K || !frag_face || !frag_grad || !dL_dverts) return;
     TetParams p = make_params(s, gx, gy, r0, img);
     const dim3 grid(gx, r1 - r0, s.B), block(256);
     if (cam_part) k_tet_fragment_grads<true><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, dL_dverts, cam_part);

@@ -296,22 +296,31 @@ struct Forward {
     }
 };
 
+// A renderer's fragment ids in the C ABI: the forward's flag and its one output buffer, the backward's flag and its two inputs.
+struct FragmentIds { int flag, buf, grads_flag, faces_buf, grads_buf; };
+constexpr FragmentIds TRI_FRAGMENTS{DMR_FLAG_TRI_FRAGMENTS, DMR_BUF_TRI_FRAGMENTS, DMR_FLAG_TRI_FRAGMENT_GRADS, DMR_BUF_TRI_FRAGMENT_FACES,
+                                    DMR_BUF_TRI_FRAGMENT_BARY_GRADS};
+constexpr FragmentIds TET_FRAGMENTS{DMR_FLAG_TET_FRAGMENTS, DMR_BUF_TET_FRAGMENTS, DMR_FLAG_TET_FRAGMENT_GRADS, DMR_BUF_TET_FRAGMENT_FACES,
+                                    DMR_BUF_TET_FRAGMENT_BARY_GRADS};
+
 // The fragment lists of render_tris / render_tets(fragments=K): ONE buffer [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32
-// B,H,W] -- what the library requests as `which`, DMR_BUF_TRI_FRAGMENTS / DMR_BUF_TET_FRAGMENTS, when `flag` of the same
-// renderer is set -- and its three pieces as views.  Pre-initialised (face -1, the rest 0) for the images' reason: a row band,
-// or P == 0 / F == 0, where nothing writes them (Forward::written).
+// B,H,W] -- what the library requests as ids.buf when ids.flag is set -- and its three pieces as views.  Pre-initialised (face
+// -1, the rest 0) for the images' reason: a row band, or P == 0 / F == 0, where nothing writes them (Forward::written).
+// K == 0: no request, three undefined tensors.
 struct Fragments {
     at::Tensor face, bary, count;
-    Fragments(Forward& f, int64_t K, int64_t H, int64_t W, int which = DMR_BUF_TRI_FRAGMENTS, int flag = DMR_FLAG_TRI_FRAGMENTS) {
+    Fragments(Forward& f, const FragmentIds& ids, int64_t K, int64_t H, int64_t W) {
+        if (K == 0) return;
         const int64_t B = f.call.sc.B, n = B * H * W;
         const at::Tensor buf = at::empty({n * (3 * K + 1)}, at::TensorOptions().dtype(at::kInt).device(f.dev));
         face = buf.narrow(0, 0, K * n).view({B, K, H, W});
         bary = buf.narrow(0, K * n, 2 * K * n).view(at::kFloat).view({B, K, 2, H, W});
         count = buf.narrow(0, 3 * K * n, n).view({B, H, W});
         if (!f.written) { face.fill_(-1); buf.narrow(0, K * n, (2 * K + 1) * n).zero_(); }
-        f.call.scratch.buf[which] = buf;
-        f.call.sc.flags |= flag | ((int)K << 8);
+        f.call.scratch.buf[ids.buf] = buf;
+        f.call.sc.flags |= ids.flag | ((int)K << 8);
     }
+    auto tuple() const { return std::make_tuple(face, bary, count); }
 };
 
 void check_fragments(int64_t fragments) {
@@ -319,8 +328,7 @@ void check_fragments(int64_t fragments) {
 }
 
 // -> (num_rendered:int, color, depth, pointBuffer, faceBuffer, binningBuffer, imgBuffer, face, bary, count): the last three
-// undefined tensors unless fragments=K > 0.  (Bound below with the GIL released and its tuple cut to the reference's seven
-// when there are no fragments.)
+// undefined tensors unless fragments=K > 0.  (Bound below through bind_forward.)
 using TriFwdOut = std::tuple<int64_t, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
 TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                       In inv_proj_mats, In verts_depth, In faces_intense, int64_t image_height, int64_t image_width, std::pair<int, int> rows,
@@ -329,17 +337,15 @@ TriFwdOut render_tris(In background, In verts, In faces, In verts_color, In face
     check_common(in, false);
     check_fragments(fragments);
     Forward f(in, image_height, image_width, 0, rows, fill_outside, alpha);
-    std::optional<Fragments> frag;
-    if (fragments > 0) frag.emplace(f, fragments, image_height, image_width);
+    const Fragments frag(f, TRI_FRAGMENTS, fragments, image_height, image_width);
     int rendered = 0;
     // (the bindings release the GIL around this whole function: the default call waits for the size read-back)
     if (g_abi.tri_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), &alloc_cb, &f.call.scratch, f.call.stream(), &rendered)) raise_lib();
-    return std::tuple_cat(f.result((int64_t)rendered, f.color, f.depth),
-                          frag ? std::make_tuple(frag->face, frag->bary, frag->count) : std::make_tuple(at::Tensor(), at::Tensor(), at::Tensor()));
+    return std::tuple_cat(f.result((int64_t)rendered, f.color, f.depth), frag.tuple());
 }
 
 // -> (color, depth, active f32 [B,H,W], pointBuffer, faceBuffer, binningBuffer, imgBuffer, face, bary, count): the last three
-// undefined tensors unless fragments=K > 0 (bound below like render_tris: its tuple cut to the reference's seven without them)
+// undefined tensors unless fragments=K > 0 (bound below like render_tris)
 using TetFwdOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
 TetFwdOut render_tets(In background, In verts, In faces, In verts_color, In faces_opacity, In mv_mats, In proj_mats, In inv_mv_mats,
                       In inv_proj_mats, In verts_depth, In faces_intense, In tets, In face_tets, In tet_faces, int64_t image_height,
@@ -350,14 +356,12 @@ TetFwdOut render_tets(In background, In verts, In faces, In verts_color, In face
     check_fragments(fragments);
     Forward f(in, image_height, image_width, ray_random_seed, rows, true, alpha);
     const at::Tensor active = f.image({f.call.sc.B, image_height, image_width});
-    std::optional<Fragments> frag;
-    if (fragments > 0) frag.emplace(f, fragments, image_height, image_width, DMR_BUF_TET_FRAGMENTS, DMR_FLAG_TET_FRAGMENTS);
+    const Fragments frag(f, TET_FRAGMENTS, fragments, image_height, image_width);
     int rendered = 0;
     if (g_abi.tet_forward(&f.call.sc, mptr<float>(f.color), mptr<float>(f.depth), mptr<float>(active), &alloc_cb, &f.call.scratch, f.call.stream(),
                           &rendered))
         raise_lib();
-    return std::tuple_cat(f.result(f.color, f.depth, active),
-                          frag ? std::make_tuple(frag->face, frag->bary, frag->count) : std::make_tuple(at::Tensor(), at::Tensor(), at::Tensor()));
+    return std::tuple_cat(f.result(f.color, f.depth, active), frag.tuple());
 }
 
 // ---- the gradient set of a backward, stated once ------------------------------------------------------------------------
@@ -471,11 +475,10 @@ py::tuple backward(const Inputs& in, In grad_color, In grad_depth, const char* c
 }
 
 // fragment_grads=(pix_to_face, grad_bary) of render_tris_backward / render_tets_backward: checked, then handed to the library as
-// they are (the two input buffers it requests, `faces_buf` and `grads_buf` of that renderer; alloc_cb serves them from
-// Scratch::buf) with the renderer's `flag` and K.
+// they are (the two input buffers it requests, ids.faces_buf and ids.grads_buf; alloc_cb serves them from Scratch::buf) with
+// ids.grads_flag and K.
 using FragmentGrads = std::optional<std::pair<at::Tensor, at::Tensor>>;
-void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t W, int flag = DMR_FLAG_TRI_FRAGMENT_GRADS,
-                           int faces_buf = DMR_BUF_TRI_FRAGMENT_FACES, int grads_buf = DMR_BUF_TRI_FRAGMENT_BARY_GRADS) {
+void attach_fragment_grads(Call& c, const FragmentIds& ids, const FragmentGrads& fg, int64_t H, int64_t W) {
     if (!fg.has_value()) return;
     const at::Tensor& face = fg->first;
     const at::Tensor& grad = fg->second;
@@ -493,9 +496,9 @@ void attach_fragment_grads(Call& c, const FragmentGrads& fg, int64_t H, int64_t 
         err("fragment_grads: grad_bary must have dimensions (B, K, 2, H, W) = (" + std::to_string(B) + ", " + std::to_string(K) + ", 2, " +
             std::to_string(H) + ", " + std::to_string(W) + ")");
     if (!face.is_contiguous() || !grad.is_contiguous()) err("fragment_grads: pix_to_face and grad_bary must be contiguous");
-    c.scratch.buf[faces_buf] = face;
-    c.scratch.buf[grads_buf] = grad;
-    c.sc.flags |= flag | ((int)K << 8);
+    c.scratch.buf[ids.faces_buf] = face;
+    c.scratch.buf[ids.grads_buf] = grad;
+    c.sc.flags |= ids.grads_flag | ((int)K << 8);
 }
 
 // tri_grads' tuple; the keywords select its level
@@ -507,7 +510,7 @@ py::tuple render_tris_backward(In background, In verts, In faces, In verts_color
                     dL_dout_color, dL_dout_depth, "dL_dout_color", "dL_dout_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out,
                     &tri_grads, camera_grads ? 2 : exact_grads, alpha,
                     [R, &fragment_grads](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
-                        attach_fragment_grads(c, fragment_grads, c.sc.H, c.sc.W);
+                        attach_fragment_grads(c, TRI_FRAGMENTS, fragment_grads, c.sc.H, c.sc.W);
                         return g_abi.tri_backward(&c.sc, gc, gd, (int)R, b[0], b[1], b[2], b[3], g[0], g[1], g[2], g[3], g[4], &alloc_cb, &c.scratch,
                                                   c.stream());
                     });
@@ -524,8 +527,7 @@ py::tuple render_tets_backward(In background, In verts, In faces, In verts_color
                     grad_color, grad_depth, "grad_color", "grad_depth", pointBuffer, faceBuffer, binningBuffer, imageBuffer, rows, flat_out, &tet_grads,
                     camera_grads ? 2 : (full_grads || fragment_grads.has_value()), alpha,
                     [&fragment_grads](Call& c, const float* gc, const float* gd, const void* const* b, float* const* g) {
-                        attach_fragment_grads(c, fragment_grads, c.sc.H, c.sc.W, DMR_FLAG_TET_FRAGMENT_GRADS, DMR_BUF_TET_FRAGMENT_FACES,
-                                              DMR_BUF_TET_FRAGMENT_BARY_GRADS);
+                        attach_fragment_grads(c, TET_FRAGMENTS, fragment_grads, c.sc.H, c.sc.W);
                         return g_abi.tet_backward(&c.sc, gc, gd, b[0], b[1], b[2], b[3], g[0], g[1], &alloc_cb, &c.scratch, c.stream());
                     });
 }
@@ -585,6 +587,21 @@ py::tuple profile_collect() {
     return py::make_tuple(ms, cnt);
 }
 
+// render_tris / render_tets as bound: run with the GIL released (the default call waits for the size read-back); the one place
+// the tuple's length is decided -- cut to the reference's seven unless fragments (the last argument) = K > 0.
+template <class R, class... A>
+auto bind_forward(R (*fn)(A...)) {
+    return [fn](A... a) {
+        R out;
+        {
+            py::gil_scoped_release nogil;
+            out = fn(a...);
+        }
+        const py::tuple all = py::cast(out);
+        return std::get<sizeof...(A) - 1>(std::forward_as_tuple(a...)) > 0 ? all : py::tuple(all[py::slice(0, 7, 1)]);
+    };
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -597,33 +614,12 @@ PYBIND11_MODULE(_C, m) {
               py::arg("mv_mats"), py::arg("proj_mats"), py::arg("inv_mv_mats"), py::arg("inv_proj_mats"), py::arg("verts_depth"),
               py::arg("faces_intense"), more...);
     };
-    def("render_tris",
-        [](In bg, In verts, In faces, In vcolor, In fopacity, In mv, In proj, In inv_mv, In inv_proj, In vdepth, In fintense, int64_t H, int64_t W,
-           std::pair<int, int> band, bool fill_outside, bool with_alpha, int64_t fragments) {
-            TriFwdOut out;
-            {
-                py::gil_scoped_release nogil;
-                out = render_tris(bg, verts, faces, vcolor, fopacity, mv, proj, inv_mv, inv_proj, vdepth, fintense, H, W, band, fill_outside, with_alpha, fragments);
-            }
-            const py::tuple all = py::cast(out);  // the one place the tuple's length is decided
-            return fragments > 0 ? all : py::tuple(all[py::slice(0, 7, 1)]);
-        },
+    def("render_tris", bind_forward(&render_tris),
         py::arg("image_height"), py::arg("image_width"), rows, py::arg("fill_outside") = true, py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tris_backward", &render_tris_backward, py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("R"), py::arg("pointBuffer"),
         py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out, py::kw_only(), py::arg("exact_grads") = false,
         camera_grads, alpha, py::arg("fragment_grads") = py::none());
-    def("render_tets",
-        [](In bg, In verts, In faces, In vcolor, In fopacity, In mv, In proj, In inv_mv, In inv_proj, In vdepth, In fintense, In tets, In face_tets,
-           In tet_faces, int64_t H, int64_t W, int64_t seed, std::pair<int, int> band, bool with_alpha, int64_t fragments) {
-            TetFwdOut out;
-            {
-                py::gil_scoped_release nogil;
-                out = render_tets(bg, verts, faces, vcolor, fopacity, mv, proj, inv_mv, inv_proj, vdepth, fintense, tets, face_tets, tet_faces, H, W, seed, band,
-                                  with_alpha, fragments);
-            }
-            const py::tuple all = py::cast(out);
-            return fragments > 0 ? all : py::tuple(all[py::slice(0, 7, 1)]);
-        },
+    def("render_tets", bind_forward(&render_tets),
         py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("image_height"), py::arg("image_width"), py::arg("ray_random_seed"), rows,
         py::kw_only(), alpha, py::arg("fragments") = 0);
     def("render_tets_backward", &render_tets_backward, py::arg("tets"), py::arg("face_tets"), py::arg("tet_faces"), py::arg("grad_color"),

@@ -861,7 +861,6 @@ k_tri_backward_pix(TriParams p, const float* __restrict__ dL_dcolor, const float
 // It is not part of k_tri_forward because that kernel sits at its register cap (FWD_WAVES above): K stores per pixel and the
 // slot counter inside its walk were what two earlier attempts at per-face outputs spilled on.  No stage, no size, no host wait.
 // ---------------------------------------------------------------------------
-constexpr int FRAG_MAX_K = 32;
 // The (u_c, v_c) k_tri_forward's phase B blends a covered (pixel, face) pair with; false: the pair it skips (denom == 0,
 // forward.cu:429-430).  k_tri_forward has these operations inline in its walk (marked there) and is not edited for this -- it
 // sits at its register cap --, so this is their one restatement: the same operations in the same order, exact division,
@@ -1498,17 +1497,15 @@ k_tri_backward_hits(TriParams p, const float4* __restrict__ pixrec, const HitRec
 // ---------------------------------------------------------------------------
 // DMR_FLAG_TRI_FRAGMENT_GRADS: k_tri_fragment_grads -- dL/d(u_c, v_c) of the caller's fragment lists -> vertex positions (and rays).
 //
-// One workgroup per tile, k_tri_fragments' pixel-to-lane mapping (8 x 8 pixels per wave: neighbouring lanes mostly hold the
-// same face).  A lane owns its pixel: it builds the ray once and, for each of the K slots, recomputes the pair's (u, v), denom
-// and clamp region with the forward's operations (forward_uv's, restated because the derivative needs nu, nv and the code:
-// V3 helpers, exact division, no contraction), takes the upstream gradient through clamp_bary_uv_grad and forms dp0, dp1,
-// dp2, dT and dL/dd with the EXACT branch's formulas of k_tri_backward_hits.  It reads nothing of the forward's lists, masks
-// or n_contrib: the pairs are the caller's, a face outside [0, F) is no pair.
+// One workgroup per tile; a lane owns its pixel (FragSlots, dmr_device.hpp): it builds the ray once and, for each of the K
+// slots, recomputes the pair's (u, v) (PairUV: the forward's operations), takes the upstream gradient through the clamp
+// region's Jacobian (clamp_bary_uv_grad) and forms the pair's exact derivative (PairUV::grad).  It reads nothing of the
+// forward's lists, masks or n_contrib: the pairs are the caller's, a face outside [0, F) is no pair.
 // The three position rows of a pair go into a table like k_tri_backward_hits' (its helpers under tags of this kernel's own, so
 // that its instantiations stay as they are; position columns only: 28 bytes a slot, 15.7 KB) and leave once per tile into the
 // packed vertex rows, ahead of the unpack.  Camera variant: dL/dd and sum dT stay in the lane's registers over the slots
-// (no LDS ray atomics: the lane is the pixel), then one chain through d = w / (|w| + 1e-7) per pixel and a block sum, added
-// to the tile's entry of cam_part behind k_tri_backward_hits, which stored it (or left k_tri_backward_pix' zeros).
+// (no LDS ray atomics: the lane is the pixel), then one ray_chain<false> per pixel and a block sum, added to the tile's
+// entry of cam_part behind k_tri_backward_hits, which stored it (or left k_tri_backward_pix' zeros).
 // A tile without a contributing pair neither flushes nor touches cam_part.
 // ---------------------------------------------------------------------------
 struct FragGradLds {
@@ -1523,19 +1520,14 @@ template <bool CAM>
 __global__ void __launch_bounds__(256)
 k_tri_fragment_grads(TriParams p, int K, const int32_t* __restrict__ frag_face, const float* __restrict__ frag_grad,
                      float* __restrict__ vrow, float* __restrict__ cam_part) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int tile = (int)blockIdx.x;
     const auto [tx, ty, b] = tile_coords(tile, p.gx, p.gy);
     if (ty < p.r0 || ty >= p.r1) return;  // uniform: pixels outside the call's row band contribute nothing
     __shared__ FragGradLds L;
-    const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
-    const int px = tx * TILE + lx, py = ty * TILE + ly;
-    const bool inside = px < p.W && py < p.H;
-    const int64_t HW = (int64_t)p.H * p.W;
-    const int64_t pix_id = (int64_t)p.W * py + px;
-    const int64_t face0 = (int64_t)b * K * HW + pix_id, grad0 = (int64_t)b * K * 2 * HW + pix_id;
+    const FragSlots S(tx, ty, b, K, p.W, p.H);
     // the first slot is requested before the table is cleared
-    int nface = inside ? frag_face[face0] : -1;
+    int nface = S.inside ? frag_face[S.face_at(0)] : -1;
     for (int i = tid; i < VTAB; i += 256) {
         L.vkey[i] = TAB_EMPTY;
 #pragma unroll
@@ -1543,46 +1535,26 @@ k_tri_fragment_grads(TriParams p, int K, const int32_t* __restrict__ frag_face, 
     }
     if (tid == 0) L.any = 0;
     V3 ro = {0, 0, 0}, rd = {0, 0, 0};
-    if (inside) pixel_ray<false>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, px, py, p.W, p.H, ro, rd);
-    fast::F3 camT = {0.f, 0.f, 0.f}, camD = {0.f, 0.f, 0.f};  // camera variant: sum of dL/dT, dL/d(ray direction) of this pixel
+    if (S.inside) pixel_ray<false>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, S.px, S.py, p.W, p.H, ro, rd);
+    V3 camT = {0.f, 0.f, 0.f}, camD = {0.f, 0.f, 0.f};  // camera variant: sum of dL/dT (= dL/do), dL/d(ray direction) of this pixel
     bool some = false;
     __syncthreads();
     for (int k = 0; k < K; k++) {
         const int face = nface;
-        if (k + 1 < K) nface = inside ? frag_face[face0 + (int64_t)(k + 1) * HW] : -1;
+        if (k + 1 < K) nface = S.inside ? frag_face[S.face_at(k + 1)] : -1;
         if ((uint32_t)face >= (uint32_t)p.F) continue;  // -1 (unused) and anything else outside [0, F): no pair
-        const float e1 = frag_grad[grad0 + (int64_t)(2 * k) * HW], e2 = frag_grad[grad0 + (int64_t)(2 * k + 1) * HW];
+        const float e1 = frag_grad[S.grad_at(k, 0)], e2 = frag_grad[S.grad_at(k, 1)];
         if (e1 == 0.f && e2 == 0.f) continue;  // nothing arrives for this pair
         const int v0 = p.faces[3 * face], v1 = p.faces[3 * face + 1], v2 = p.faces[3 * face + 2];
-        const V3 xp0 = load_v3(p.verts, v0), xp1 = load_v3(p.verts, v1), xp2 = load_v3(p.verts, v2);
-        // the forward's (u, v) of the pair (stage_shade_geom, forward_uv): exact arithmetic, the clamp region selects the Jacobian
-        const V3 xT = ro - xp0, xE1 = xp1 - xp0, xE2 = xp2 - xp0;
-        const V3 xQ = dmr::cross(xT, xE1);
-        const V3 xP = dmr::cross(rd, xE2);
-        const float denom = dmr::dot(xP, xE1);
-        if (denom == 0.0f) continue;  // the forward skips such a pair: it is no fragment
-        const float inv_denom = 1.0f / denom;
-        const float nu = dmr::dot(xP, xT), nv = dmr::dot(xQ, rd);
-        const float iu = nu * inv_denom, iv = nv * inv_denom;
+        PairUV uv;
+        if (!uv.set(ro, rd, load_v3(p.verts, v0), load_v3(p.verts, v1), load_v3(p.verts, v2))) continue;  // no fragment
         float iuc, ivc; int code;
-        clamp_bary_uv(iu, iv, iuc, ivc, code);
+        clamp_bary_uv(uv.u(), uv.v(), iuc, ivc, code);
         float duc_du, duc_dv, dvc_du, dvc_dv;
         clamp_bary_uv_grad(code, duc_du, duc_dv, dvc_du, dvc_dv);
-        const float dL_diu = e1 * duc_du + e2 * dvc_du;
-        const float dL_div = e1 * duc_dv + e2 * dvc_dv;
-        // the exact derivative of (u, v) = ((d x E2) . T, (T x E1) . d) / ((d x E2) . E1) (k_tri_backward_hits, EXACT)
-        const float su = dL_diu * inv_denom, sv = dL_div * inv_denom;
-        const float sb = (su * nu + sv * nv) * inv_denom;
-        const V3 xE1d = dmr::cross(xE1, rd);
-        const V3 dT = su * xP + sv * xE1d;
-        const V3 dp1 = sv * dmr::cross(rd, xT) - sb * xP;
-        const V3 dp2 = su * dmr::cross(xT, rd) - sb * xE1d;
-        const V3 dp0 = -(dT + dp1 + dp2);
-        if constexpr (CAM) {
-            const V3 gd = su * dmr::cross(xE2, xT) + sv * xQ + sb * dmr::cross(xE1, xE2);  // dL/dd = su (E2 x T) + sv Q - sb (E2 x E1)
-            camD = camD + fast::F3{gd.x, gd.y, gd.z};
-            camT = camT + fast::F3{dT.x, dT.y, dT.z};
-        }
+        V3 dp0, dp1, dp2, dT, gd;
+        uv.grad<CAM>(rd, e1 * duc_du + e2 * dvc_du, e1 * duc_dv + e2 * dvc_dv, dp0, dp1, dp2, dT, gd);
+        if constexpr (CAM) { camD = camD + gd; camT = camT + dT; }
         some = true;
         const float rows[3][3] = {{dp0.x, dp0.y, dp0.z}, {dp1.x, dp1.y, dp1.z}, {dp2.x, dp2.y, dp2.z}};
         const uint32_t rid[3] = {(uint32_t)b * (uint32_t)p.P + (uint32_t)v0, (uint32_t)b * (uint32_t)p.P + (uint32_t)v1,
@@ -1604,49 +1576,12 @@ k_tri_fragment_grads(TriParams p, int K, const int32_t* __restrict__ frag_face, 
     __syncthreads();
     if (!L.any) return;  // uniform
     if constexpr (CAM) {
-        // this lane's pixel: dL/dd through d = w / (|w| + 1e-7), w = inv_mv (pv, 1) - o, pv = inv_proj (ndc, -1, 1) (pixel_ray) to the
-        // view's two inverse matrices, as in k_tri_backward_hits' epilogue.  c[3 col + row]: dL/dinv_mv rows 0-2 (col 3 = dL/do),
-        // c[12 + 3 col + row]: dL/dinv_proj rows 0-2; the w rows get nothing.
         float c[24];
 #pragma unroll
         for (int i = 0; i < 24; i++) c[i] = 0.f;
-        if (some) {  // (inside)
-            const float* im = p.inv_mv + 16 * b; const float* ip = p.inv_proj + 16 * b;
-            const float ndc[4] = {pix2ndc(px + 0.5f, p.W), pix2ndc(py + 0.5f, p.H), -1.0f, 1.0f};
-            const V4 pv = xform4x4({ndc[0], ndc[1], ndc[2]}, ip);
-            const V4 pw = xform4x4({pv.x, pv.y, pv.z}, im);
-            const V3 w = V3{pw.x, pw.y, pw.z} - ro;
-            const float n = sqrtf(dmr::dot(w, w)), len = n + 0.0000001f;
-            const float gd[3] = {camD.x, camD.y, camD.z};
-            // dL/dw = g / len - w (w . g) / (n len^2)
-            const float kk = n > 0.f ? (w.x * gd[0] + w.y * gd[1] + w.z * gd[2]) / (n * len * len) : 0.f;
-            const float dw[3] = {gd[0] / len - kk * w.x, gd[1] / len - kk * w.y, gd[2] / len - kk * w.z};
-            const float pvv[3] = {pv.x, pv.y, pv.z};
-#pragma unroll
-            for (int col = 0; col < 3; col++)
-#pragma unroll
-                for (int row = 0; row < 3; row++) c[3 * col + row] = dw[row] * pvv[col];
-#pragma unroll
-            for (int row = 0; row < 3; row++) {  // (R^T dL/dw)_row, R = inv_mv's upper 3x3
-                const float a = im[4 * row] * dw[0] + im[4 * row + 1] * dw[1] + im[4 * row + 2] * dw[2];
-#pragma unroll
-                for (int col = 0; col < 4; col++) c[12 + 3 * col + row] = a * ndc[col];
-            }
-            c[9] = camT.x; c[10] = camT.y; c[11] = camT.z;
-        }
-#pragma unroll
-        for (int i = 0; i < 24; i++)
-#pragma unroll
-            for (int dlt = 32; dlt > 0; dlt >>= 1) c[i] += __shfl_xor(c[i], dlt, 64);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 24; i++) L.red[wave][i] = c[i];
-        }
-        __syncthreads();
-        if (tid < 32) {  // entry tid of the tile's partial, m[4 col + row] of inv_mv (tid < 16) / inv_proj: this workgroup is its one writer
-            const int row = tid & 3, col = (tid >> 2) & 3, i = 12 * (tid >> 4) + 3 * col + row;
-            if (row != 3) cam_part[(int64_t)tile * 32 + tid] += L.red[0][i] + L.red[1][i] + L.red[2][i] + L.red[3][i];
-        }
+        if (some)  // (inside) this lane's pixel, through the pixel centre
+            ray_chain<false>(p.inv_mv + 16 * b, p.inv_proj + 16 * b, {pix2ndc(S.px + 0.5f, p.W), pix2ndc(S.py + 0.5f, p.H)}, ro, camD, camT, c);
+        ray_chain_add(c, L.red, cam_part + (int64_t)tile * 32);
     }
     // every row of the table goes out once: 4 lanes per vertex row (3 used), neighbouring slots -- rows that share a line -- together
     const int comp = tid & 3;
@@ -1725,11 +1660,8 @@ void launch_tri_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, co
                           TriImageState img, int K, void* fragments, hipStream_t st) {
     if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
     const TriParams p = make_params(s, gx, gy, r0, r1, nullptr, tile_offset, face_list, img);
-    const size_t npix = (size_t)s.B * s.H * s.W;  // [face i32 B,K,H,W | bary f32 B,K,2,H,W | count i32 B,H,W]
-    int32_t* face = static_cast<int32_t*>(fragments);
-    float* bary = reinterpret_cast<float*>(face + (size_t)K * npix);
-    int32_t* count = face + 3 * (size_t)K * npix;
-    k_tri_fragments<<<dim3((unsigned)(s.B * gx * gy)), dim3(256), 0, st>>>(p, K, face, bary, count);
+    const FragmentLists out(fragments, (size_t)s.B * s.H * s.W, K);
+    k_tri_fragments<<<dim3((unsigned)(s.B * gx * gy)), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
 }
 
 void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,

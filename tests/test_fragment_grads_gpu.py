@@ -101,6 +101,52 @@ def test_synthetic_pairs_reach_every_clamp_region(hip_device, synthetic):
         assert e <= sum_order_tol("verts"), (name, e)
 
 
+def test_full_table_rows_leave_directly(hip_device):
+    """The kernel's full-table fallback: a pair whose (view, vertex) row finds no slot adds its three values to the packed
+    vertex rows with float atomics.  One 16 x 16 image (one tile), K = 3, caller-made pairs as in the synthetic test: its 768
+    slots hold a permutation of the 768 faces of a six-sheet scene taken apart into a soup (P = 3 F: no two faces share a
+    vertex), so the tile references three distinct rows per pair with an upstream, four times the table's slots.  Same
+    model, same bounds as the synthetic test.  Measured on the MI355X: 768 pairs, 2304 rows, dL_dverts 4.8e-7 at the three
+    levels (max |ref| 39.9), dL_dmv_mats 3.5e-7, dL_dproj_mats 2.2e-7."""
+    from dmesh_renderer_amd import _C
+    VTAB = 560  # dmr_tri.hip: VTAB, the vertex-row slots of a workgroup's table (k_tri_fragment_grads' FragGradLds)
+    dev = hip_device
+    B, H, W, K = 1, 16, 16, 3
+    d = scenes.layered_sheets(6, 9, B, H, W, seed=7, opacity=(0.1, 0.5))
+    vid = d["faces"].long().reshape(-1)
+    F = d["faces"].shape[0]
+    assert F == B * K * H * W
+    d.update(verts=d["verts"][vid], verts_color=d["verts_color"][vid], verts_depth=d["verts_depth"][:, vid],
+             faces=th.arange(3 * F, dtype=th.int32).reshape(F, 3))
+    gen = th.Generator().manual_seed(23)
+    face = th.randperm(F, generator=gen).reshape(B, K, H, W)
+    gb = th.randn(B, K, 2, H, W, generator=gen)
+    pairs, (b, k, y, x) = FGR.pairs_of_lists(d, H, W, face)
+    keep = ~pairs.near_border()
+    mask = th.zeros(B, K, H, W)
+    mask[b, k, y, x] = keep.to(mask.dtype)
+    gb = (gb * mask[:, :, None]).contiguous()
+    live = (gb[b, k, :, y, x] != 0).any(1).numpy()
+    rows = np.unique(d["faces"].numpy()[pairs.face.numpy()[live]])  # (one view, one tile: a row is a vertex)
+    assert len(rows) > 2 * VTAB, len(rows)
+    rg = pairs.grads(gb[b, k, :, y, x])
+    args = c_args(d, dev)
+    zc, zd = _zeros(B, H, W, dev)
+    out = _C.render_tris(*args, H, W)
+    for kw in LEVELS:
+        g = _C.render_tris_backward(*args, zc, zd, out[0], *out[3:7], fragment_grads=(face.int().to(dev), gb.to(dev)), **kw)
+        ev = _rel(g[0].cpu().numpy(), rg["verts"], "verts")
+        print(f"\nfull table {kw or 'reference level'}: {int(live.sum())} pairs, {len(rows)} rows in the tile, dL_dverts {ev:.2e} "
+              f"(max |ref| {np.abs(rg['verts']).max():.3g})")
+        assert ev <= TRI_VERTS_TOL, (kw, ev)
+        if "camera_grads" in kw:
+            gm, gp = _module_mats(args, g)
+            em, ep = _rel(gm, rg["mv_mats"], "mv_mats"), _rel(gp, rg["proj_mats"], "proj_mats")
+            print(f"full table: dL_dmv_mats {em:.2e} dL_dproj_mats {ep:.2e} (max |ref| {np.abs(rg['mv_mats']).max():.3g}, "
+                  f"{np.abs(rg['proj_mats']).max():.3g})")
+            assert em <= CAM_TOL and ep <= CAM_TOL, (em, ep)
+
+
 def _rasterised(oracle, dev, case):
     """A case of TRI_CASES: its K = 8 lists from render_tris(fragments=K) (confirmed to be the model's), a random upstream on
     the kept pixels of the band, the model's gradients for it."""

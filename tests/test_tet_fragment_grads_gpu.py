@@ -136,6 +136,37 @@ def test_edge_on_pair_with_an_upstream_contributes_nothing(hip_device, synthetic
         assert e <= sum_order_tol("verts"), (name, e)
 
 
+def test_full_table_faces_leave_directly(hip_device):
+    """The kernel's full-table fallback: a pair whose face finds no slot adds its nine values to dL_dverts with float atomics.
+    One 16 x 16 image (one tile), K = 4, caller-made pairs on the synthetic test's scene: the 1024 slots hold a permutation of
+    its 864 faces (the rest unused), so no two lanes share a face for the merge to combine and the tile references nearly
+    twice the faces its table has slots for.  Same model, same bounds as the synthetic test.  Measured on the MI355X: 848
+    pairs (16 more graze), dL_dverts 5.7e-6 at both levels (max |ref| 5.8e4), dL_dmv_mats 3.1e-6, dL_dproj_mats 3.4e-6."""
+    from dmesh_renderer_amd import _C, scenes
+    TET_FRAG_TBL = 448  # dmr_tet.hip: TET_FRAG_TBL, the face slots of a workgroup's table (k_tet_fragment_grads' TetFragGradLds)
+    dev = hip_device
+    s = TFG.SYNTH
+    B, H, W, K = 1, 16, 16, 4
+    d = scenes.kuhn_tets(s["m"], B, H, W, seed=s["scene_seed"], opacity=s["opacity"])
+    F = d["faces"].shape[0]
+    assert F == 864
+    gen = th.Generator().manual_seed(23)
+    ids = th.cat([th.randperm(F, generator=gen), th.full((B * K * H * W - F,), -1, dtype=th.int64)])
+    face = ids[th.randperm(len(ids), generator=gen)].reshape(B, K, H, W)
+    pairs, where = TFG.pairs_of_lists(d, H, W, face)
+    gb, g, dropped = TFG.masked_upstream((B, K, 2, H, W), pairs, where, gen)
+    live = (g != 0).any(1).numpy()
+    rows = np.unique(pairs.face.numpy()[live])  # (a row of this table is a face)
+    assert len(rows) > 1.5 * TET_FRAG_TBL, len(rows)
+    rg = pairs.grads(g)
+    args = c_args(d, dev, tet=True)
+    zc, zd = _zeros(B, H, W, dev)
+    out = _C.render_tets(*args, H, W, 0)
+    for kw in LEVELS:
+        gk = _C.render_tets_backward(*args, zc, zd, *out[3:7], fragment_grads=(face.int().to(dev), gb.to(dev)), **kw)
+        _check(gk, rg, args, f"full table {kw}: {int(live.sum())} pairs, {len(rows)} faces in the tile, {int(dropped.sum())} grazing")
+
+
 _refs = {}
 # W_extra / 16 that no other test of the suite gives the case (grad_cases.scene): view configurations of this file's own
 OWN_WIDTHS = {"two_views_ragged": (1, 3), "opaque": (1, 2), "jitter": (1, 2)}
