@@ -68,6 +68,13 @@ int fragment_grad_inputs(dmr_alloc_fn alloc, void* ctx, const char* r, const std
     return 0;
 }
 
+using dmr::Dims;  // a call's scratch, as the launchers see it: dmr_kernels.hpp
+using dmr::PointState;
+using dmr::FaceState;
+using dmr::ImageState;
+using dmr::BinningState;
+using dmr::Scratch;
+
 constexpr size_t ALIGN = 256;
 inline size_t up(size_t n) { return (n + ALIGN - 1) & ~(ALIGN - 1); }
 
@@ -80,26 +87,6 @@ struct Carver {
         off += up(count * sizeof(T));
         return p;
     }
-};
-
-struct PointState { float4* vproj; };
-struct FaceState { uint2* rect; float* key_depth; float* max_depth; uint32_t* tiles_touched; void* facerec; void* colrec; void* tetrec; };
-// (tile_count and FaceState::rect belong to the exact policy of the binning: the set-up pass leaves them for the scan and the
-// scatter.  Behind launch_bin_faces tile_count stays zero -- a tile's count is tile_cursor - tile_offset there -- and rect keeps
-// what an earlier call left; nothing reads either afterwards)
-struct ImageState {
-    uint32_t* tile_count; uint32_t* tile_offset; uint32_t* tile_cursor; int* num_rendered;
-    float* final_T; float* final_prev_T; uint32_t* n_contrib;
-    uint32_t* tile_hits; uint32_t* tile_bound; uint32_t* scan_tmp; uint32_t* hit_offset; uint32_t* tile_used; unsigned long long* hit_total; uint32_t* tile_order;
-    int32_t* first_face; int32_t* first_tet; int32_t* last_face; int32_t* last_tet; uint8_t* is_active;
-    float* mats;  // [mv | proj | inv_mv | inv_proj], [B,16] each, contract layout (written by k_project_verts)
-    int* seed;    // tet: ray_random_seed of the forward (the backward recomputes the same jittered rays)
-    unsigned long long* mask_offset;  // tri: {byte offset of the coverage masks inside the binning buffer, their first-chunk slots} (written on the device)
-    dmr::TetSeq* seq;  // tet: the march sequence's descriptor (dmr_kernels.hpp)
-};
-struct BinningState {
-    uint64_t* keys; uint32_t* face_list; uint32_t capacity; unsigned long long mask_offset, mask_first;
-    char* base; unsigned long long seq_offset; uint32_t seq_steps;  // tet: the march sequence's region
 };
 
 size_t carve_point(void* b, size_t BP, PointState& s) { Carver c(b); s.vproj = c.take<float4>(BP); return c.off; }
@@ -159,11 +146,8 @@ size_t carve_binning(void* b, size_t R, size_t mask_tiles, size_t seq_tiles, siz
     return c.off;
 }
 
-struct Dims { int gx, gy, r0, r1, ntiles; size_t BP, BF, npix; };
-
-// The four scratch buffers of a call (null buffers: sizes only, null pointers).  The binning buffer as the backward passes and
-// dmr_export see it: its lists of R entries (run_forward carves the forward's, with its capacity, itself).
-struct Scratch { PointState ps; FaceState fs; ImageState is; BinningState bs; size_t point_bytes, face_bytes, image_bytes; };
+// The four scratch buffers of a call (dmr::Scratch; null buffers: sizes only, null pointers), the binning buffer's lists of R
+// entries included.
 Scratch carve_scratch(const dmr_scene* s, bool tet, const Dims& d, const void* pb, const void* fb, const void* ib,
                       const void* bb = nullptr, size_t R = 0) {
     Scratch c;
@@ -173,16 +157,6 @@ Scratch carve_scratch(const dmr_scene* s, bool tet, const Dims& d, const void* p
     carve_binning(const_cast<void*>(bb), R, 0, 0, 0, c.bs);
     return c;
 }
-dmr::TriImageState tri_image(const Scratch& c) {
-    const ImageState& is = c.is;
-    return {is.final_T, is.final_prev_T, is.n_contrib, is.tile_hits, is.tile_bound, is.hit_offset, is.tile_used, is.tile_order, is.tile_cursor, is.mask_offset};
-}
-dmr::TetImageState tet_image(const Scratch& c) {
-    const ImageState& is = c.is;
-    return {is.final_T, is.final_prev_T, is.n_contrib, is.first_face, is.first_tet, is.last_face, is.last_tet, is.is_active,
-            c.fs.facerec, c.fs.colrec, c.fs.tetrec, is.seed, is.seq, c.bs.base};
-}
-
 // The scene as every kernel behind k_project_verts sees it: matrices in contract layout, read from the image buffer.
 dmr_scene canonical(const dmr_scene* s, const float* mats) {
     dmr_scene c = *s;
@@ -466,7 +440,6 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
     void* ib = alloc(ctx, DMR_BUF_IMAGE, need.image_bytes);
     if (!pb || !fb || !ib) return fail("scratch allocation failed");
     Scratch c = carve_scratch(s, tet, d, pb, fb, ib);
-    const PointState& ps = c.ps; const FaceState& fs = c.fs; const ImageState& is = c.is;
     const bool async = is_async(s, st);
     const SizeKey key = size_key(s, tet, d);
     size_t seq_steps = 0;
@@ -476,11 +449,9 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
     const Placement pl = placed ? find_placement(key, d) : Placement{};
 
     auto front = [&](SizeOut out) {
-        // (tile_count | tile_hits | tile_bound are contiguous: zeroed by k_project_verts, a slice per block)
-        dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st);
-        dmr::launch_setup_faces(*s, tet, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.rect, fs.key_depth, fs.max_depth,
-                                fs.tiles_touched, is.tile_count, st);
-        dmr::launch_scan_tiles(d.ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, is.tile_order, is.scan_tmp, out, st);
+        dmr::launch_project_verts(*s, d, c, dmr::NO_SEGMENTS, st);
+        dmr::launch_setup_faces(*s, d, c, tet, st);
+        dmr::launch_scan_tiles(d, c, out, st);
     };
     // the call's binning buffer, carved into c.bs (none at all: a call with no entries and no march sequence)
     auto binning = [&](uint64_t capacity) -> int {
@@ -494,27 +465,20 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
     bool exact = false;  // the lists come from the exact path: its counts and order are what a placement is built from
     auto rest = [&](uint64_t capacity) -> int {
         if (binning(capacity)) return 1;
-        const BinningState& bs = c.bs;
         exact = true;
         if (capacity > 0) {
-            dmr::launch_scatter_faces(*s, d.gx, d.gy, fs.rect, fs.key_depth, fs.tiles_touched, is.tile_cursor, bs.keys,
-                                      (uint32_t)capacity, tet ? nullptr : is.mask_offset, bs.mask_offset, bs.mask_first, st);
-            // (up to SCAN_SINGLE_MAX tiles the tri forward / the tet first-hit kernel sort a tile's list at the start of its workgroup)
-            if (d.ntiles > dmr::SCAN_SINGLE_MAX)
-                dmr::launch_sort_tiles(d.ntiles, is.tile_offset, is.tile_order, bs.keys, bs.face_list, bs.capacity, st);
+            dmr::launch_scatter_faces(*s, d, c, !tet, st);
+            if (!dmr::sorts_own_tiles(d)) dmr::launch_sort_tiles(d, c, st);
         }
-        render(c, dmr::ListSize{nullptr, NOWHERE, 0u});
+        render(c, dmr::NO_LIST_SIZE);
         return 0;
     };
     // speculative placement: projection -> one binning kernel -> render, whose first workgroup leaves the size word
     auto binned = [&](SizeOut out) -> int {
         if (binning(pl.capacity)) return 1;
-        const BinningState& bs = c.bs;
-        dmr::launch_project_verts(*s, ps.vproj, is.mats, is.tile_count, (size_t)(is.scan_tmp + dmr::SCAN_TMP_BUCKETS - is.tile_count), st,
-                                  dmr::SegInit{pl.start, pl.order, is.tile_offset, is.tile_cursor, is.tile_order, (uint32_t)d.ntiles});
-        dmr::launch_bin_faces(*s, ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.key_depth, fs.tiles_touched, is.tile_offset, is.tile_cursor, bs.keys,
-                              bs.capacity, is.mask_offset, bs.mask_offset, bs.mask_first, st);
-        render(c, dmr::ListSize{is.num_rendered, out, 1u});  // (its first workgroup publishes R)
+        dmr::launch_project_verts(*s, d, c, dmr::SegInit{pl.start, pl.order}, st);
+        dmr::launch_bin_faces(*s, d, c, st);
+        render(c, dmr::ListSize{c.is.num_rendered, out, 1u});  // (its first workgroup publishes R)
         return 0;
     };
 
@@ -533,7 +497,7 @@ int run_forward(const dmr_scene* s, bool tet, const Dims& d, dmr_alloc_fn alloc,
                    [&](uint64_t size, bool redo) { if (redo) front(NOWHERE); return rest(size); });
     *num_rendered = (int)R;
     if (rc == 0 && placed && !async) {  // the exact path refreshes the placement; one twice as large as the scene needs is dropped
-        if (exact) rc = build_placement(key, d, R, is, st);
+        if (exact) rc = build_placement(key, d, R, c.is, st);
         else if (2 * R < pl.built_from) drop_placement(key);
     }
     return rc;
@@ -638,17 +602,13 @@ int dmr_tri_forward(const dmr_scene* s, float* out_color, float* out_depth, dmr_
         return 1;
     Scratch last{};  // the scratch of the call's final k_tri_forward: a redo (a refuted size estimate) renders a second time
     auto render = [&](const Scratch& c, dmr::ListSize size) {
-        const dmr_scene sc = canonical(s, c.is.mats);
-        dmr::launch_tri_forward(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, c.is.tile_offset, d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys,
-                                c.bs.face_list, c.bs.capacity, tri_image(c), out_color,
-                                out_depth, st, (s->flags & DMR_FLAG_ALPHA) != 0, size);
+        dmr::launch_tri_forward(canonical(s, c.is.mats), d, c, out_color, out_depth, (s->flags & DMR_FLAG_ALPHA) != 0, size, st);
         last = c;
     };
     if (run_forward(s, false, d, alloc, ctx, st, num_rendered, render)) return 1;
     // the fragments describe the colour the call returns: one launch, behind whichever k_tri_forward was the last
     if (fragments && last.is.n_contrib) {
-        dmr::launch_tri_fragments(canonical(s, last.is.mats), d.gx, d.gy, d.r0, d.r1, last.is.tile_offset, last.bs.face_list, tri_image(last),
-                                  frag_k, fragments, st);
+        dmr::launch_tri_fragments(canonical(s, last.is.mats), d, last, frag_k, fragments, st);
         DMR_HIP(hipGetLastError());
     }
     return 0;
@@ -714,7 +674,6 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         float* cam_part = reinterpret_cast<float*>(work + vbytes + fbytes);  // (zeroed with the accumulators)
         float4* pixrec = reinterpret_cast<float4*>(work + vbytes + fbytes + cbytes);
         dmr::HitRecord* hits = reinterpret_cast<dmr::HitRecord*>(work + vbytes + fbytes + cbytes + pbytes);
-        const dmr::TriImageState img = tri_image(c);
         const dmr_scene sc = canonical(s, is.mats);
         // (Splitting the tiles into bands whose hit-parallel kernel runs on a second stream while the next band's
         // per-pixel kernel computes -- atomic unit and SIMDs busy at the same time -- was measured and lost: 0.56 ms
@@ -722,15 +681,13 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
         // k_tri_backward_pix also zeroes the packed accumulators (every block a slice).  (Handing out the tiles'
         // record regions from an atomic cursor: the 2.9 k returning same-address atomics stall their waves, in order
         // with every younger load -- 17 us.)
-        dmr::launch_tri_backward_pix(sc, d.gx, d.gy, d.r0, d.r1, c.ps.vproj, is.tile_offset, c.bs.face_list, img,
-                                     dL_dcolor, dL_ddepth, pixrec, hits, (uint32_t)capacity,
-                                     reinterpret_cast<float*>(work), (vbytes + fbytes + cbytes) / sizeof(float), regions, st,
-                                     (s->flags & DMR_FLAG_ALPHA) != 0);  // (dL_ddepth [B,2,H,W]: its alpha channel reaches dL_dfopacity)
-        dmr::launch_tri_backward_hits(sc, d.gx, d.gy, c.ps.vproj, c.bs.face_list, img, pixrec, hits, (uint32_t)capacity, vrow, frow, st,
-                                      grads, camera ? cam_part : nullptr);
+        dmr::launch_tri_backward_pix(sc, d, c, dL_dcolor, dL_ddepth, pixrec, hits, (uint32_t)capacity, reinterpret_cast<float*>(work),
+                                     (vbytes + fbytes + cbytes) / sizeof(float), regions,
+                                     (s->flags & DMR_FLAG_ALPHA) != 0, st);  // (dL_ddepth [B,2,H,W]: its alpha channel reaches dL_dfopacity)
+        dmr::launch_tri_backward_hits(sc, d, c, pixrec, hits, (uint32_t)capacity, vrow, frow, grads, camera ? cam_part : nullptr, st);
         // the fragment lists' term joins the packed vertex rows (and the tiles' camera partials) before they are unpacked / reduced
         if (frag_face)
-            dmr::launch_tri_fragment_grads(sc, d.gx, d.gy, d.r0, d.r1, img, frag_k, frag_face, frag_grad, vrow, camera ? cam_part : nullptr, st);
+            dmr::launch_tri_fragment_grads(sc, d, c, frag_k, frag_face, frag_grad, vrow, camera ? cam_part : nullptr, st);
         dmr::launch_tri_unpack(*s, vrow, frow, dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense, st);
         if (camera) dmr::launch_camera_reduce(s->B, d.gx * d.gy, 32, cam_part, cam_out, st);
         return 0;
@@ -741,7 +698,7 @@ int dmr_tri_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     const bool self_regions = d.ntiles <= dmr::SCAN_SINGLE_MAX;
     auto first = [&](uint64_t guess, SizeOut out) -> int {
         if (guess && self_regions) return rest(guess, self_laid(out));
-        dmr::launch_scan_hits(d.ntiles, is.tile_hits, is.tile_offset, is.tile_cursor, is.hit_offset, is.tile_used, is.hit_total, is.scan_tmp, out, st);
+        dmr::launch_scan_hits(d, c, out, st);
         return guess ? rest(guess, scanned) : 0;
     };
     const Sizing hit_records{&SizeGuess::hits_per_face, 0xfffffffeu, 1, "more than 2^32 blended (pixel, face) pairs",
@@ -775,14 +732,12 @@ int dmr_tet_forward(const dmr_scene* s, float* out_color, float* out_depth, floa
     if (caller_output(alloc, ctx, DMR_BUF_TET_FRAGMENTS, frag_k ? dmr::FragmentLists::bytes(d.npix, frag_k) : 0, "tet fragment", false, st, &fragments))
         return 1;
     auto render = [&](const Scratch& c, dmr::ListSize) {
-        const dmr::TetImageState img = tet_image(c);
         const dmr_scene sc = canonical(s, c.is.mats);
-        dmr::launch_tet_prep(sc, img, c.bs.seq_steps, c.bs.seq_offset, st);
-        dmr::launch_tet_first_intersect(sc, d.gx, d.gy, d.r0, d.r1, c.fs.key_depth, c.fs.max_depth, c.is.tile_offset,
-                                        d.ntiles > dmr::SCAN_SINGLE_MAX ? nullptr : c.bs.keys, c.bs.face_list, c.bs.capacity, img, st);
-        dmr::launch_tet_forward(sc, d.gx, d.gy, d.r0, d.r1, img, out_color, out_depth, out_active, st, (s->flags & DMR_FLAG_ALPHA) != 0);
+        dmr::launch_tet_prep(sc, d, c, st);
+        dmr::launch_tet_first_intersect(sc, d, c, st);
+        dmr::launch_tet_forward(sc, d, c, out_color, out_depth, out_active, (s->flags & DMR_FLAG_ALPHA) != 0, st);
         // the fragments describe the images the call returns: behind every k_tet_forward, so after a redo the redo's
-        if (fragments) dmr::launch_tet_fragments(sc, d.gx, d.gy, d.r0, d.r1, img, frag_k, fragments, st);
+        if (fragments) dmr::launch_tet_fragments(sc, d, c, frag_k, fragments, st);
     };
     return run_forward(s, true, d, alloc, ctx, st, num_rendered, render, frag_steps);
 }
@@ -829,10 +784,10 @@ int dmr_tet_backward(const dmr_scene* s, const float* dL_dcolor, const float* dL
     const Scratch c = carve_scratch(s, true, d, point_buf, face_buf, image_buf, binning_buf);
     const dmr_scene sc = canonical(s, c.is.mats);
     uint32_t* host_seq_steps = march_estimate(size_key(s, true, d), d, false);
-    dmr::launch_tet_backward(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st,
-                             full, full ? full + 3 * (int64_t)s->P : nullptr, cam_part, (s->flags & DMR_FLAG_ALPHA) != 0);
+    dmr::launch_tet_backward(sc, d, c, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, full,
+                             full ? full + 3 * (int64_t)s->P : nullptr, cam_part, (s->flags & DMR_FLAG_ALPHA) != 0, st);
     // the fragment lists' term joins dL_dverts (and the tiles' camera partials) before the partials are reduced
-    if (frag_face) dmr::launch_tet_fragment_grads(sc, d.gx, d.gy, d.r0, d.r1, tet_image(c), frag_k, frag_face, frag_grad, full, cam_part, st);
+    if (frag_face) dmr::launch_tet_fragment_grads(sc, d, c, frag_k, frag_face, frag_grad, full, cam_part, st);
     if (cam_out) dmr::launch_camera_reduce(s->B, band_tiles, 64, cam_part, cam_out, st);
     DMR_HIP(hipGetLastError());
     return 0;

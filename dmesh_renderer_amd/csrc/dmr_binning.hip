@@ -302,7 +302,7 @@ k_setup_faces_lds(int B, int P, int F, const int* __restrict__ faces, const floa
 constexpr uint32_t SEG_FULL = 0xC0000000u;
 
 // where the entries go; mask_*: where the binning buffer of THIS capacity keeps the coverage masks (dmr_kernels.hpp,
-// TriImageState::mask_offset), left on the device for the kernels behind (dst null: tet)
+// ImageState::mask_offset), left on the device for the kernels behind (dst null: tet)
 struct BinOut { uint32_t* tile_cursor; uint64_t* keys; uint32_t capacity; unsigned long long* mask_offset_dst; unsigned long long mask_offset, mask_first; };
 
 template <int FPT, bool SEG>
@@ -739,13 +739,14 @@ k_sort_tiles(uint32_t ntiles, const uint32_t* __restrict__ tile_offset, const ui
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-void launch_project_verts(const dmr_scene& s, float4* vproj, float* mats, uint32_t* counters, size_t ncounters,
-                          hipStream_t st, SegInit seg) {
+void launch_project_verts(const dmr_scene& s, const Dims& d, const Scratch& c, SegInit seg, hipStream_t st) {
+    const ImageState& is = c.is;
     const int64_t n = (int64_t)s.B * s.P;
+    if (seg.start) { seg.tile_offset = is.tile_offset; seg.tile_cursor = is.tile_cursor; seg.tile_order = is.tile_order; seg.ntiles = (uint32_t)d.ntiles; }
     StageScope t(DMR_STAGE_PROJECT, st);
     k_project_verts<<<dim3((unsigned)std::max<int64_t>(1, (n + 255) / 256)), dim3(256), 0, st>>>(
         s.B, s.P, s.verts, s.mv_mats, s.proj_mats, s.inv_mv_mats, s.inv_proj_mats, s.mats_transposed, s.verts_depth,
-        s.W, s.H, vproj, mats, counters, (uint32_t)ncounters, seg);
+        s.W, s.H, c.ps.vproj, is.mats, is.tile_count, (uint32_t)(is.scan_tmp + SCAN_TMP_BUCKETS - is.tile_count), seg);
 }
 
 // fn(std::integral_constant<int, FPT>, grid): the faces per thread of n (view, face) pairs and their workgroups
@@ -758,69 +759,73 @@ void with_fpt(int64_t n, Fn fn) {
     else fn(std::integral_constant<int, 4>{}, grid);
 }
 
-void launch_setup_faces(const dmr_scene& s, bool tet, const float4* vproj, int gx, int gy, int r0, int r1,
-                        uint2* face_rect, float* key_depth, float* max_depth, uint32_t* tiles_touched,
-                        uint32_t* tile_count, hipStream_t st) {
+void launch_setup_faces(const dmr_scene& s, const Dims& d, const Scratch& c, bool tet, hipStream_t st) {
+    const FaceState& fs = c.fs;
     const int64_t n = (int64_t)s.B * s.F;
     if (n == 0) return;
     StageScope t(DMR_STAGE_SETUP_FACES, st);
     with_fpt(n, [&](auto fpt, dim3 grid) {
         auto k = tet ? k_setup_faces_lds<true, fpt()> : k_setup_faces_lds<false, fpt()>;
-        k<<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, face_rect, key_depth, max_depth, tiles_touched, tile_count);
+        k<<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, c.ps.vproj, d.gx, d.gy, d.r0, d.r1, fs.rect, fs.key_depth, fs.max_depth,
+                                      fs.tiles_touched, c.is.tile_count);
     });
 }
 
-void launch_scan_tiles(int ntiles, const uint32_t* tile_count, uint32_t* tile_offset, uint32_t* tile_cursor,
-                       int* num_rendered, uint32_t* tile_order, uint32_t* scan_tmp, SizeOut out, hipStream_t st) {
+void launch_scan_tiles(const Dims& d, const Scratch& c, SizeOut out, hipStream_t st) {
+    const ImageState& is = c.is;
+    const int ntiles = d.ntiles;
     StageScope t(DMR_STAGE_SCAN, st);
     if (ntiles <= SCAN_SINGLE_MAX) {
-        k_scan_tiles<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_count, tile_offset, tile_cursor, num_rendered, tile_order, out);
+        k_scan_tiles<<<dim3(1), dim3(1024), 0, st>>>(ntiles, is.tile_count, is.tile_offset, is.tile_cursor, is.num_rendered, is.tile_order, out);
         return;
     }
     // scan_tmp: [ORDER_BUCKETS + 1 bucket counters, zeroed by k_project_verts | partial sums per block]
     const int nblk = (ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES;
-    uint32_t* bucket = scan_tmp;
-    uint32_t* blk_sum = scan_tmp + SCAN_TMP_BUCKETS;
-    k_scan_tiles_partial<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_count, nullptr, blk_sum, bucket);
-    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, bucket, tile_offset, num_rendered, nullptr, out);
-    k_scan_tiles_final<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_count, nullptr, blk_sum, bucket, tile_offset, tile_cursor, tile_order);
+    uint32_t* bucket = is.scan_tmp;
+    uint32_t* blk_sum = is.scan_tmp + SCAN_TMP_BUCKETS;
+    k_scan_tiles_partial<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, is.tile_count, nullptr, blk_sum, bucket);
+    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, bucket, is.tile_offset, is.num_rendered, nullptr, out);
+    k_scan_tiles_final<true><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, is.tile_count, nullptr, blk_sum, bucket, is.tile_offset, is.tile_cursor, is.tile_order);
 }
 
 size_t scan_tmp_words(int ntiles) { return SCAN_TMP_BUCKETS + (size_t)(ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES + 1; }
 
-void launch_scan_hits(int ntiles, const uint32_t* tile_hits, const uint32_t* tile_offset, const uint32_t* tile_end, uint32_t* hit_offset, uint32_t* tile_used,
-                      unsigned long long* hit_total, uint32_t* scan_tmp, SizeOut out, hipStream_t st) {
+void launch_scan_hits(const Dims& d, const Scratch& c, SizeOut out, hipStream_t st) {
+    const ImageState& is = c.is;
+    const int ntiles = d.ntiles;
     StageScope t(DMR_STAGE_SCAN, st);
     if (ntiles <= SCAN_SINGLE_MAX) {
-        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, tile_end, hit_offset, tile_used, hit_total, out);
+        k_scan_hits<<<dim3(1), dim3(1024), 0, st>>>(ntiles, is.tile_hits, is.tile_offset, is.tile_cursor, is.hit_offset, is.tile_used, is.hit_total, out);
         return;
     }
     const int nblk = (ntiles + SCAN_BLOCK_TILES - 1) / SCAN_BLOCK_TILES;
-    uint32_t* blk_sum = scan_tmp + SCAN_TMP_BUCKETS;  // the forward's partial sums are no longer needed
-    k_scan_tiles_partial<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, blk_sum, nullptr);
-    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, nullptr, hit_offset, nullptr, hit_total, out);
-    k_scan_tiles_final<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, tile_hits, tile_offset, blk_sum, nullptr, hit_offset, tile_used, nullptr);
+    uint32_t* blk_sum = is.scan_tmp + SCAN_TMP_BUCKETS;  // the forward's partial sums are no longer needed
+    k_scan_tiles_partial<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, is.tile_hits, is.tile_offset, blk_sum, nullptr);
+    k_scan_tiles_blocks<<<dim3(1), dim3(1024), 0, st>>>(nblk, ntiles, blk_sum, nullptr, is.hit_offset, nullptr, is.hit_total, out);
+    k_scan_tiles_final<false><<<dim3(nblk), dim3(1024), 0, st>>>(ntiles, is.tile_hits, is.tile_offset, blk_sum, nullptr, is.hit_offset, is.tile_used, nullptr);
 }
 
-void launch_scatter_faces(const dmr_scene& s, int gx, int gy, const uint2* face_rect, const float* key_depth,
-                          const uint32_t* tiles_touched, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
-                          unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st) {
+// where the emit pass of either binning policy writes: the cursors, the binning buffer's keys, the masks' place
+static BinOut bin_out(const Scratch& c, bool masks) {
+    return BinOut{c.is.tile_cursor, c.bs.keys, c.bs.capacity, masks ? c.is.mask_offset : nullptr, c.bs.mask_offset, c.bs.mask_first};
+}
+
+void launch_scatter_faces(const dmr_scene& s, const Dims& d, const Scratch& c, bool masks, hipStream_t st) {
     const int64_t n = (int64_t)s.B * s.F;
     if (n == 0) return;
     StageScope t(DMR_STAGE_SCATTER, st);
-    const BinOut out{tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first};
+    const BinOut out = bin_out(c, masks);
     with_fpt(n, [&](auto fpt, dim3 grid) {
-        k_scatter_faces_lds<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.F, gx, gy, face_rect, key_depth, tiles_touched, out);
+        k_scatter_faces_lds<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.F, d.gx, d.gy, c.fs.rect, c.fs.key_depth, c.fs.tiles_touched, out);
     });
 }
 
-void launch_bin_faces(const dmr_scene& s, const float4* vproj, int gx, int gy, int r0, int r1, float* key_depth,
-                      uint32_t* tiles_touched, const uint32_t* seg, uint32_t* tile_cursor, uint64_t* keys, uint32_t capacity,
-                      unsigned long long* mask_offset_dst, unsigned long long mask_offset, unsigned long long mask_first, hipStream_t st) {
+void launch_bin_faces(const dmr_scene& s, const Dims& d, const Scratch& c, hipStream_t st) {
     StageScope t(DMR_STAGE_SCATTER, st);
-    const BinOut out{tile_cursor, keys, capacity, mask_offset_dst, mask_offset, mask_first};
+    const BinOut out = bin_out(c, true);
     with_fpt((int64_t)s.B * s.F, [&](auto fpt, dim3 grid) {
-        k_bin_faces<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, vproj, gx, gy, r0, r1, key_depth, tiles_touched, seg, out);
+        k_bin_faces<fpt()><<<grid, dim3(256), 0, st>>>(s.B, s.P, s.F, s.faces, c.ps.vproj, d.gx, d.gy, d.r0, d.r1, c.fs.key_depth,
+                                                      c.fs.tiles_touched, c.is.tile_offset, out);
     });
 }
 
@@ -830,11 +835,11 @@ void launch_build_placement(int ntiles, const uint32_t* tile_count, const uint32
     k_build_placement<<<dim3(1), dim3(1024), 0, st>>>(ntiles, tile_count, tile_order, start, order);
 }
 
-void launch_sort_tiles(int ntiles, const uint32_t* tile_offset, const uint32_t* tile_order, uint64_t* keys,
-                       uint32_t* face_list, uint32_t capacity, hipStream_t st) {
-    if (ntiles == 0) return;
+void launch_sort_tiles(const Dims& d, const Scratch& c, hipStream_t st) {
+    if (d.ntiles == 0) return;
     StageScope t(DMR_STAGE_SORT, st);
-    k_sort_tiles<<<dim3((unsigned)std::min(ntiles, 256 * 64)), dim3(256), 0, st>>>((uint32_t)ntiles, tile_offset, tile_order, keys, face_list, capacity);
+    k_sort_tiles<<<dim3((unsigned)std::min(d.ntiles, 256 * 64)), dim3(256), 0, st>>>((uint32_t)d.ntiles, c.is.tile_offset, c.is.tile_order, c.bs.keys,
+                                                                                    c.bs.face_list, c.bs.capacity);
 }
 
 }  // namespace dmr

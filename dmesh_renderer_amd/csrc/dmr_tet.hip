@@ -48,6 +48,15 @@ constexpr int TET_FACE_MASK = 0x0fffffff;  // (check_scene: F < 2^28)
 // masks, four compares and a count, all of the 4.5-cycle kind in a kernel whose VALUs are busy all the time.
 constexpr int TET_FACE_DUP = 0x10000000;
 
+// What the kernels keep of the call's Scratch (make_params below); part of TetParams, so of the kernels' ABI.
+struct TetImageState {
+    float* final_log_T; float* final_prev_log_T; uint32_t* n_contrib;
+    int32_t* first_face; int32_t* first_tet; int32_t* last_face; int32_t* last_tet; uint8_t* is_active;
+    void* facerec; void* colrec; void* tetrec;  // packed march records (above), in the face buffer
+    int* seed;                                  // ray_random_seed of the forward (image buffer)
+    TetSeq* seq;                                // the march sequence's descriptor (image buffer)
+    char* binning;                              // start of the binning buffer (the sequence region lies at seq->offset)
+};
 struct TetParams {
     int B, P, F, W, H, gx, gy, r0;
 #ifdef DMR_ABLATION
@@ -1397,21 +1406,23 @@ k_tet_fragment_grads(TetParams p, int K, const int32_t* __restrict__ frag_face, 
     }
 }
 
-static TetParams make_params(const dmr_scene& s, int gx, int gy, int r0, TetImageState img) {
+static TetParams make_params(const dmr_scene& s, const Dims& d, const Scratch& c) {
+    const ImageState& is = c.is;
     TetParams p;
-    p.B = s.B; p.P = s.P; p.F = s.F; p.W = s.W; p.H = s.H; p.gx = gx; p.gy = gy; p.r0 = r0;
+    p.B = s.B; p.P = s.P; p.F = s.F; p.W = s.W; p.H = s.H; p.gx = d.gx; p.gy = d.gy; p.r0 = d.r0;
 #ifdef DMR_ABLATION
-    { static const int dbg = getenv("DMR_ABLATE") ? atoi(getenv("DMR_ABLATE")) : 0; p.dbg = dbg; }  // ablation build only
+    p.dbg = ablate_bits();
 #endif
     p.verts = s.verts; p.faces = s.faces; p.verts_color = s.verts_color; p.faces_opacity = s.faces_opacity;
     p.mv = s.mv_mats; p.proj = s.proj_mats; p.inv_mv = s.inv_mv_mats; p.inv_proj = s.inv_proj_mats;
     p.faces_intense = s.faces_intense; p.bg = s.background;
     p.tets = s.tets; p.face_tets = s.face_tets; p.tet_faces = s.tet_faces;
-    p.seed = img.seed;
-    p.facerec = reinterpret_cast<const TetFaceRec*>(img.facerec);
-    p.colrec = reinterpret_cast<const TetColRec*>(img.colrec);
-    p.tetrec = reinterpret_cast<const TetBlock*>(img.tetrec);
-    p.img = img;
+    p.seed = is.seed;
+    p.facerec = reinterpret_cast<const TetFaceRec*>(c.fs.facerec);
+    p.colrec = reinterpret_cast<const TetColRec*>(c.fs.colrec);
+    p.tetrec = reinterpret_cast<const TetBlock*>(c.fs.tetrec);
+    p.img = TetImageState{is.final_T, is.final_prev_T, is.n_contrib, is.first_face, is.first_tet, is.last_face, is.last_tet, is.is_active,
+                          c.fs.facerec, c.fs.colrec, c.fs.tetrec, is.seed, is.seq, c.bs.base};
     return p;
 }
 
@@ -1419,41 +1430,44 @@ size_t tet_facerec_bytes() { return sizeof(TetFaceRec); }
 size_t tet_colrec_bytes() { return sizeof(TetColRec); }
 size_t tet_tetrec_bytes() { return sizeof(TetBlock); }
 
-void launch_tet_prep(const dmr_scene& s, TetImageState img, uint32_t seq_steps, unsigned long long seq_offset, hipStream_t st) {
+void launch_tet_prep(const dmr_scene& s, const Dims&, const Scratch& c, hipStream_t st) {
     k_tet_prep_faces<<<dim3((unsigned)std::max(1, (s.F + 255) / 256)), dim3(256), 0, st>>>(
         s.F, s.verts, s.faces, s.verts_color, s.faces_opacity, s.face_tets,
-        reinterpret_cast<TetFaceRec*>(img.facerec), reinterpret_cast<TetColRec*>(img.colrec), s.ray_random_seed, img.seed,
-        img.seq, seq_steps, seq_offset);
+        reinterpret_cast<TetFaceRec*>(c.fs.facerec), reinterpret_cast<TetColRec*>(c.fs.colrec), s.ray_random_seed, c.is.seed,
+        c.is.seq, c.bs.seq_steps, c.bs.seq_offset);
     if (s.T > 0)
         k_tet_prep_tets<<<dim3((unsigned)((s.T + 255) / 256)), dim3(256), 0, st>>>(
-            s.T, s.F, s.verts, s.faces, s.tets, s.tet_faces, s.face_tets, reinterpret_cast<TetBlock*>(img.tetrec));
+            s.T, s.F, s.verts, s.faces, s.tets, s.tet_faces, s.face_tets, reinterpret_cast<TetBlock*>(c.fs.tetrec));
 }
 
-void launch_tet_first_intersect(const dmr_scene& s, int gx, int gy, int r0, int r1, const float* key_depth,
-                                const float* max_depth, const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list,
-                                uint32_t capacity, TetImageState img, hipStream_t st) {
-    if (r1 <= r0) return;
-    TetParams p = make_params(s, gx, gy, r0, img);
+// one workgroup per tile of the call's row band, per view
+static dim3 band_grid(const dmr_scene& s, const Dims& d) { return dim3(d.gx, d.r1 - d.r0, s.B); }
+
+void launch_tet_first_intersect(const dmr_scene& s, const Dims& d, const Scratch& c, hipStream_t st) {
+    if (d.r1 <= d.r0) return;
+    const TetParams p = make_params(s, d, c);
     StageScope t(DMR_STAGE_TET_FIRST, st);
-    const dim3 grid(gx, r1 - r0, s.B), block(256);
-    if (keys) k_tet_first_intersect<true><<<grid, block, 0, st>>>(p, key_depth, max_depth, tile_offset, face_list, keys, capacity);
-    else k_tet_first_intersect<false><<<grid, block, 0, st>>>(p, key_depth, max_depth, tile_offset, face_list, nullptr, capacity);
+    const dim3 grid = band_grid(s, d), block(256);
+    const FaceState& fs = c.fs; const BinningState& bs = c.bs;
+    uint64_t* keys = sorts_own_tiles(d) ? bs.keys : nullptr;
+    if (keys) k_tet_first_intersect<true><<<grid, block, 0, st>>>(p, fs.key_depth, fs.max_depth, c.is.tile_offset, bs.face_list, keys, bs.capacity);
+    else k_tet_first_intersect<false><<<grid, block, 0, st>>>(p, fs.key_depth, fs.max_depth, c.is.tile_offset, bs.face_list, nullptr, bs.capacity);
 }
 
-void launch_tet_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
-                        float* out_color, float* out_depth, float* out_active, hipStream_t st, bool alpha) {
-    if (r1 <= r0) return;
-    TetParams p = make_params(s, gx, gy, r0, img);
+void launch_tet_forward(const dmr_scene& s, const Dims& d, const Scratch& c, float* out_color, float* out_depth, float* out_active,
+                        bool alpha, hipStream_t st) {
+    if (d.r1 <= d.r0) return;
+    const TetParams p = make_params(s, d, c);
     StageScope t(DMR_STAGE_TET_FORWARD, st);
-    if (alpha) k_tet_forward<true><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
-    else k_tet_forward<><<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
+    if (alpha) k_tet_forward<true><<<band_grid(s, d), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
+    else k_tet_forward<><<<band_grid(s, d), dim3(256), 0, st>>>(p, out_color, out_depth, out_active);
 }
 
-void launch_tet_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, void* fragments, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
-    TetParams p = make_params(s, gx, gy, r0, img);
-    const FragmentLists out(fragments, (size_t)s.B * s.H * s.W, K);
-    k_tet_fragments<<<dim3(gx, r1 - r0, s.B), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
+void launch_tet_fragments(const dmr_scene& s, const Dims& d, const Scratch& c, int K, void* fragments, hipStream_t st) {
+    if (d.r1 <= d.r0 || K < 1 || K > FRAG_MAX_K) return;
+    const TetParams p = make_params(s, d, c);
+    const FragmentLists out(fragments, d.npix, K);
+    k_tet_fragments<<<band_grid(s, d), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
 }
 
 // both gradient tensors zeroed by one launch (two hipMemsetAsync are three fill kernels of ~4.6 us each)
@@ -1480,30 +1494,27 @@ static void tet_backward_pair(const TetParams& p, int gx, int rows, int B, const
                                                                                                dL_dfopacity, full...);
 }
 
-void launch_tet_backward(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img,
-                         const float* dL_dcolor, const float* dL_ddepth, float* dL_dvcolor, float* dL_dfopacity,
-                         uint32_t* host_seq_steps, hipStream_t st, float* dL_dverts, float* dL_dfintense, float* cam_part, bool alpha) {
-    if (r1 <= r0) return;
-    TetParams p = make_params(s, gx, gy, r0, img);
+void launch_tet_backward(const dmr_scene& s, const Dims& d, const Scratch& c, const float* dL_dcolor, const float* dL_ddepth,
+                         float* dL_dvcolor, float* dL_dfopacity, uint32_t* host_seq_steps, float* dL_dverts, float* dL_dfintense,
+                         float* cam_part, bool alpha, hipStream_t st) {
+    if (d.r1 <= d.r0) return;
+    const TetParams p = make_params(s, d, c);
     StageScope t(DMR_STAGE_TET_BACKWARD, st);
-    const int rows = r1 - r0;
-    if (cam_part) {
-        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense, cam_part);
-        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense, cam_part);
-    } else if (!dL_dverts) {
-        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st);
-        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st);
-    } else {
-        if (alpha) tet_backward_pair<true>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
-        else tet_backward_pair<false>(p, gx, rows, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, dL_dverts, dL_dfintense);
-    }
+    auto pair = [&](auto... full) {
+        with_flag(alpha, [&](auto a) {
+            tet_backward_pair<decltype(a)::value>(p, d.gx, d.r1 - d.r0, s.B, dL_dcolor, dL_ddepth, dL_dvcolor, dL_dfopacity, host_seq_steps, st, full...);
+        });
+    };
+    if (cam_part) pair(dL_dverts, dL_dfintense, cam_part);
+    else if (!dL_dverts) pair();
+    else pair(dL_dverts, dL_dfintense);
 }
 
-void launch_tet_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TetImageState img, int K, const int32_t* frag_face,
+void launch_tet_fragment_grads(const dmr_scene& s, const Dims& d, const Scratch& c, int K, const int32_t* frag_face,
                                const float* frag_grad, float* dL_dverts, float* cam_part, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K || !frag_face || !frag_grad || !dL_dverts) return;
-    TetParams p = make_params(s, gx, gy, r0, img);
-    const dim3 grid(gx, r1 - r0, s.B), block(256);
+    if (d.r1 <= d.r0 || K < 1 || K > FRAG_MAX_K || !frag_face || !frag_grad || !dL_dverts) return;
+    const TetParams p = make_params(s, d, c);
+    const dim3 grid = band_grid(s, d), block(256);
     if (cam_part) k_tet_fragment_grads<true><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, dL_dverts, cam_part);
     else k_tet_fragment_grads<false><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, dL_dverts, nullptr);
 }

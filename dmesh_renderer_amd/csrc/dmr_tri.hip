@@ -92,11 +92,11 @@ struct TriParams {
     unsigned long long* keys;  // (depth_bits << 32 | face) of every list entry, unsorted: the forward sorts its tile's
     float* final_T; float* final_prev_T; uint32_t* n_contrib;
     uint32_t* tile_hits; uint32_t* tile_bound; const uint32_t* hit_offset; uint32_t* tile_used; const uint32_t* tile_order;
-    const unsigned long long* mask_offset;  // coverage masks: byte offset behind face_list (TriImageState)
+    const unsigned long long* mask_offset;  // coverage masks: byte offset behind face_list (ImageState)
     ListSize size;  // forward behind launch_bin_faces: where R goes (dmr_kernels.hpp); size.blocks = 1, else 0 and unused
 };
 
-// The tile's coverage masks, pixel-major, one slot of 256 x 16 bytes per chunk (layout: TriImageState, dmr_kernels.hpp): chunk
+// The tile's coverage masks, pixel-major, one slot of 256 x 16 bytes per chunk (layout: ImageState::mask_offset, dmr_kernels.hpp): chunk
 // 0 in the slot of the tile's position in tile_order, the later chunks behind the list offset.  The forward writes them
 // right after rasterising, the per-pixel backward reads them back instead of staging the coverage records and
 // rasterising the chunk a second time (that was 13 k of its 25 k cycles per chunk, profiles/r02/phase_times_c4.txt).
@@ -1621,78 +1621,72 @@ k_tri_unpack(int B, int P, int F, const float* __restrict__ vrow, const float* _
     }
 }
 
-static TriParams make_params(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
-                             const uint32_t* tile_offset, const uint32_t* face_list, TriImageState img) {
+// What every tri kernel reads of the scene, the call's Dims and its Scratch; the forward adds what is its own.
+static TriParams make_params(const dmr_scene& s, const Dims& d, const Scratch& c) {
+    const ImageState& is = c.is;
     TriParams p;
-    p.B = s.B; p.P = s.P; p.F = s.F; p.W = s.W; p.H = s.H; p.gx = gx; p.gy = gy; p.r0 = r0; p.r1 = r1;
+    p.B = s.B; p.P = s.P; p.F = s.F; p.W = s.W; p.H = s.H; p.gx = d.gx; p.gy = d.gy; p.r0 = d.r0; p.r1 = d.r1;
 #ifdef DMR_ABLATION
-    { static const int dbg = getenv("DMR_ABLATE") ? atoi(getenv("DMR_ABLATE")) : 0; p.dbg = dbg; }  // ablation build only
+    p.dbg = ablate_bits();
 #endif
     p.verts = s.verts; p.faces = s.faces; p.verts_color = s.verts_color; p.faces_opacity = s.faces_opacity;
     p.inv_mv = s.inv_mv_mats; p.inv_proj = s.inv_proj_mats; p.faces_intense = s.faces_intense; p.bg = s.background;
-    p.vproj = vproj; p.tile_offset = tile_offset; p.tile_end = img.tile_end; p.face_list = face_list; p.keys = nullptr;
-    p.final_T = img.final_T; p.final_prev_T = img.final_prev_T; p.n_contrib = img.n_contrib;
-    p.tile_hits = img.tile_hits; p.tile_bound = img.tile_bound; p.hit_offset = img.hit_offset; p.tile_used = img.tile_used; p.tile_order = img.tile_order;
-    p.mask_offset = img.mask_offset;
+    p.vproj = c.ps.vproj; p.tile_offset = is.tile_offset; p.tile_end = is.tile_cursor; p.face_list = c.bs.face_list; p.keys = nullptr;
+    p.final_T = is.final_T; p.final_prev_T = is.final_prev_T; p.n_contrib = is.n_contrib;
+    p.tile_hits = is.tile_hits; p.tile_bound = is.tile_bound; p.hit_offset = is.hit_offset; p.tile_used = is.tile_used; p.tile_order = is.tile_order;
+    p.mask_offset = is.mask_offset;
     p.list_capacity = 0xffffffffu;
-    p.size = ListSize{nullptr, NOWHERE, 0u};
+    p.size = NO_LIST_SIZE;
     return p;
 }
 
-void launch_tri_forward(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
-                        const uint32_t* tile_offset, uint64_t* keys, uint32_t* face_list, uint32_t capacity, TriImageState img,
-                        float* out_color, float* out_depth, hipStream_t st, bool alpha, ListSize size) {
-    if (r1 <= r0 && !size.blocks) return;  // (the size is wanted of an empty band too; its tiles return at once)
-    TriParams p = make_params(s, gx, gy, r0, r1, vproj, tile_offset, face_list, img);
-    p.keys = reinterpret_cast<unsigned long long*>(keys);
-    p.list_capacity = capacity;
+void launch_tri_forward(const dmr_scene& s, const Dims& d, const Scratch& c, float* out_color, float* out_depth, bool alpha,
+                        ListSize size, hipStream_t st) {
+    if (d.r1 <= d.r0 && !size.blocks) return;  // (the size is wanted of an empty band too; its tiles return at once)
+    TriParams p = make_params(s, d, c);
+    if (sorts_own_tiles(d)) p.keys = reinterpret_cast<unsigned long long*>(c.bs.keys);
+    p.list_capacity = c.bs.capacity;
     p.size = size;
     StageScope t(DMR_STAGE_TRI_FORWARD, st);
-    const dim3 grid((unsigned)(s.B * gx * gy) + size.blocks), block(256);
-    if (alpha) {  // out_depth [B,2,H,W]: depth | alpha
-        if (keys) k_tri_forward<true, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
-        else k_tri_forward<false, true><<<grid, block, 0, st>>>(p, out_color, out_depth);
-    } else if (keys) k_tri_forward<true><<<grid, block, 0, st>>>(p, out_color, out_depth);
-    else k_tri_forward<false><<<grid, block, 0, st>>>(p, out_color, out_depth);
+    const dim3 grid((unsigned)d.ntiles + size.blocks), block(256);
+    with_flag(alpha, [&](auto a) {  // alpha: out_depth [B,2,H,W]: depth | alpha
+        with_flag(p.keys != nullptr, [&](auto sort) {
+            k_tri_forward<decltype(sort)::value, decltype(a)::value><<<grid, block, 0, st>>>(p, out_color, out_depth);
+        });
+    });
 }
 
-void launch_tri_fragments(const dmr_scene& s, int gx, int gy, int r0, int r1, const uint32_t* tile_offset, const uint32_t* face_list,
-                          TriImageState img, int K, void* fragments, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
-    const TriParams p = make_params(s, gx, gy, r0, r1, nullptr, tile_offset, face_list, img);
-    const FragmentLists out(fragments, (size_t)s.B * s.H * s.W, K);
-    k_tri_fragments<<<dim3((unsigned)(s.B * gx * gy)), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
+void launch_tri_fragments(const dmr_scene& s, const Dims& d, const Scratch& c, int K, void* fragments, hipStream_t st) {
+    if (d.r1 <= d.r0 || K < 1 || K > FRAG_MAX_K) return;
+    const TriParams p = make_params(s, d, c);
+    const FragmentLists out(fragments, d.npix, K);
+    k_tri_fragments<<<dim3((unsigned)d.ntiles), dim3(256), 0, st>>>(p, K, out.face, out.bary, out.count);
 }
 
-void launch_tri_backward_pix(const dmr_scene& s, int gx, int gy, int r0, int r1, const float4* vproj,
-                             const uint32_t* tile_offset, const uint32_t* face_list, TriImageState img,
-                             const float* dL_dcolor, const float* dL_ddepth, float4* pixrec, HitRecord* hits,
-                             uint32_t capacity, float* work, size_t work_floats, HitRegions regions, hipStream_t st, bool alpha) {
+void launch_tri_backward_pix(const dmr_scene& s, const Dims& d, const Scratch& c, const float* dL_dcolor, const float* dL_ddepth,
+                             float4* pixrec, HitRecord* hits, uint32_t capacity, float* work, size_t work_floats,
+                             HitRegions regions, bool alpha, hipStream_t st) {
     // (an empty band never gets here: dmr_tri_backward zeroes the gradients itself -- this kernel is also what zeroes `work`)
-    TriParams p = make_params(s, gx, gy, r0, r1, vproj, tile_offset, face_list, img);
+    const TriParams p = make_params(s, d, c);
     StageScope t(DMR_STAGE_TRI_BACKWARD, st);
-    dim3 grid((unsigned)(s.B * gx * gy)), block(256);
+    dim3 grid((unsigned)d.ntiles), block(256);
 #ifdef DMR_ABLATION
     if (DMR_DBG(p, 131072)) grid.x = std::min(grid.x, 3072u);  // timing experiment (results invalid): only the busiest tiles' workgroups
 #endif
-    if (alpha) {  // dL_ddepth [B,2,H,W]: dL/ddepth | dL/dalpha
-        if (regions.hit_offset)
-            k_tri_backward_pix<false, true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
-        else
-            k_tri_backward_pix<true, true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
-    } else if (regions.hit_offset)
-        k_tri_backward_pix<false><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
-    else
-        k_tri_backward_pix<true><<<grid, block, 0, st>>>(p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
+    with_flag(alpha, [&](auto a) {  // alpha: dL_ddepth [B,2,H,W]: dL/ddepth | dL/dalpha
+        with_flag(regions.hit_offset != nullptr, [&](auto self_laid) {  // (else launch_scan_hits has laid the regions out)
+            k_tri_backward_pix<!decltype(self_laid)::value, decltype(a)::value><<<grid, block, 0, st>>>(
+                p, dL_dcolor, dL_ddepth, pixrec, hits, capacity, work, (uint32_t)work_floats, regions);
+        });
+    });
 }
 
-void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* vproj, const uint32_t* face_list, TriImageState img,
-                              const float4* pixrec, const HitRecord* hits, uint32_t capacity, float* vrow, float* frow,
-                              hipStream_t st, int grads, float* cam_part) {
+void launch_tri_backward_hits(const dmr_scene& s, const Dims& d, const Scratch& c, const float4* pixrec, const HitRecord* hits,
+                              uint32_t capacity, float* vrow, float* frow, int grads, float* cam_part, hipStream_t st) {
     if (capacity == 0) return;
-    TriParams p = make_params(s, gx, gy, 0, 0, vproj, nullptr, face_list, img);
+    const TriParams p = make_params(s, d, c);
     StageScope t(DMR_STAGE_TRI_BACKWARD_HITS, st);
-    unsigned nblocks = (unsigned)(s.B * gx * gy);
+    unsigned nblocks = (unsigned)d.ntiles;
 #ifdef DMR_ABLATION
     if (DMR_DBG(p, 131072)) nblocks = std::min(nblocks, 3072u);  // timing experiment, as above
 #endif
@@ -1704,11 +1698,11 @@ void launch_tri_backward_hits(const dmr_scene& s, int gx, int gy, const float4* 
         k_tri_backward_hits<TRI_GRAD_REF><<<dim3(nblocks), dim3(256), 0, st>>>(p, pixrec, hits, capacity, vrow, frow);
 }
 
-void launch_tri_fragment_grads(const dmr_scene& s, int gx, int gy, int r0, int r1, TriImageState img, int K, const int32_t* frag_face,
+void launch_tri_fragment_grads(const dmr_scene& s, const Dims& d, const Scratch& c, int K, const int32_t* frag_face,
                                const float* frag_grad, float* vrow, float* cam_part, hipStream_t st) {
-    if (r1 <= r0 || K < 1 || K > FRAG_MAX_K) return;
-    const TriParams p = make_params(s, gx, gy, r0, r1, nullptr, nullptr, nullptr, img);
-    const dim3 grid((unsigned)(s.B * gx * gy)), block(256);
+    if (d.r1 <= d.r0 || K < 1 || K > FRAG_MAX_K) return;
+    const TriParams p = make_params(s, d, c);
+    const dim3 grid((unsigned)d.ntiles), block(256);
     if (cam_part) k_tri_fragment_grads<true><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, vrow, cam_part);
     else k_tri_fragment_grads<false><<<grid, block, 0, st>>>(p, K, frag_face, frag_grad, vrow, nullptr);
 }
