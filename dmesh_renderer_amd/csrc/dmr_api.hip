@@ -534,6 +534,8 @@ StageScope::~StageScope() {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_live.push_back(r);
 }
+// dmr_last_error()'s message, for a translation unit with exports of its own (dmr_shade.hip); returns 1
+int api_fail(const char* m) { return fail(m); }
 }  // namespace dmr
 
 extern "C" {

@@ -33,6 +33,9 @@
 //   fragments=0              render_tris: K > 0 (at most 32): per-pixel fragment lists (DMR_FLAG_TRI_FRAGMENTS) -> the tuple gains
 //                            face i32 [B,K,H,W], bary f32 [B,K,2,H,W], count i32 [B,H,W] behind the four scratch tensors
 //                            render_tets: the same (DMR_FLAG_TET_FRAGMENTS): the faces of the march, in march order
+//   composite_fragments(face, bary, faces, faces_opacity, vert_attrs, face_scale=None) -> (image [B,C,H,W], T [B,1,H,W]) and
+//   composite_fragments_backward(..., grad_image, grad_T, need=(opacity, attrs, scale, bary)) -> those four gradients or None:
+//                            fragments.composite_fused, over include/dmesh_renderer_amd_shade.h (SUPPORTS_FRAGMENT_COMPOSITE)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -51,6 +54,7 @@
 #include <vector>
 
 #include "../../include/dmesh_renderer_amd.h"
+#include "../../include/dmesh_renderer_amd_shade.h"
 
 namespace {
 
@@ -76,6 +80,9 @@ struct Abi {
     decltype(&dmr_redo_count) redo_count = nullptr;
     decltype(&dmr_abi_version) abi_version = nullptr;
     decltype(&dmr_build_arch) build_arch = nullptr;
+    // dmesh_renderer_amd_shade.h: optional (SUPPORTS_FRAGMENT_COMPOSITE), a library without them still loads
+    decltype(&dmr_composite_fragments) composite_fragments = nullptr;
+    decltype(&dmr_composite_fragments_backward) composite_fragments_backward = nullptr;
 };
 
 Abi g_abi;
@@ -114,6 +121,10 @@ void load_abi() {
     bind(g_abi.stage_name, "dmr_stage_name"); bind(g_abi.last_error, "dmr_last_error");
     bind(g_abi.overflowed, "dmr_overflowed"); bind(g_abi.redo_count, "dmr_redo_count"); bind(g_abi.abi_version, "dmr_abi_version");
     bind(g_abi.build_arch, "dmr_build_arch");
+    g_abi.composite_fragments = reinterpret_cast<decltype(g_abi.composite_fragments)>(dlsym(g_abi.handle, "dmr_composite_fragments"));
+    g_abi.composite_fragments_backward =
+        reinterpret_cast<decltype(g_abi.composite_fragments_backward)>(dlsym(g_abi.handle, "dmr_composite_fragments_backward"));
+    if (!g_abi.composite_fragments || !g_abi.composite_fragments_backward) g_abi.composite_fragments = nullptr, g_abi.composite_fragments_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -580,6 +591,89 @@ at::Tensor export_item(const std::string& name, const py::sequence& call_args, b
     return out.narrow(0, 0, n).view(torch::python::detail::py_object_to_dtype(dtype));
 }
 
+// ---- composite_fragments / composite_fragments_backward (dmesh_renderer_amd_shade.h): fragments.composite_fused ----------------
+// The tensors both calls start with, checked and made contiguous; sizes as the C calls take them.
+struct ShadeArgs {
+    at::Tensor face, bary, faces, opacity, attrs, scale;  // scale: undefined = none
+    int B, K, H, W, P, F, C;
+    c10::Device dev;
+    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+    const float* scale_ptr() const { return scale.defined() ? mptr<const float>(scale) : nullptr; }
+};
+
+ShadeArgs shade_args(In face, In bary, In faces, In faces_opacity, In vert_attrs, const std::optional<at::Tensor>& face_scale) {
+    if (!g_abi.composite_fragments)
+        err(g_abi.path + " does not export dmr_composite_fragments: rebuild it (python -m dmesh_renderer_amd.build)");
+    const c10::Device dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    const int64_t B = face.size(0), K = face.size(1), H = face.size(2), W = face.size(3);
+    if (bary.dim() != 5 || bary.size(0) != B || bary.size(1) != K || bary.size(2) != 2 || bary.size(3) != H || bary.size(4) != W)
+        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
+    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
+    const int64_t F = faces.size(0);
+    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != F) err("faces_opacity must have dimensions (num_faces,)");
+    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
+    const int64_t P = vert_attrs.size(0), C = vert_attrs.size(1);
+    if (K < 1 || K > 32) err("composite_fragments: K must be in 1..32, got " + std::to_string(K));
+    if (C < 1 || C > 256) err("composite_fragments: C must be in 1..256, got " + std::to_string(C));
+    if (B < 1 || H < 1 || W < 1) err("composite_fragments: empty fragment lists");
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != B || face_scale->size(1) != F))
+        err("face_scale must have dimensions (B, num_faces)");
+    const std::pair<const at::Tensor*, const char*> same[5] = {{&bary, "bary"}, {&faces, "faces"}, {&faces_opacity, "faces_opacity"},
+                                                               {&vert_attrs, "vert_attrs"}, {face_scale ? &*face_scale : nullptr, "face_scale"}};
+    for (auto& t : same)
+        if (t.first && t.first->device() != dev) err(std::string(t.second) + " must be on the device of pix_to_face");
+    return {i32(face, "pix_to_face"), f32(bary, "bary"), i32(faces, "faces"), f32(faces_opacity, "faces_opacity"), f32(vert_attrs, "vert_attrs"),
+            face_scale ? f32(*face_scale, "face_scale") : at::Tensor(), (int)B, (int)K, (int)H, (int)W, (int)P, (int)F, (int)C, dev};
+}
+
+// -> (image [B,C,H,W], T [B,1,H,W])
+std::tuple<at::Tensor, at::Tensor> composite_fragments(In face, In bary, In faces, In faces_opacity, In vert_attrs,
+                                                       const std::optional<at::Tensor>& face_scale) {
+    const ShadeArgs a = shade_args(face, bary, faces, faces_opacity, vert_attrs, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    if (g_abi.composite_fragments(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                  mptr<const int32_t>(a.faces), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
+                                  mptr<float>(image), mptr<float>(T), a.stream()))
+        raise_lib();
+    return {image, T};
+}
+
+// need = (faces_opacity, vert_attrs, face_scale, bary) -> those four gradients, None where not asked for; grad_image
+// [B,C,H,W] / grad_T [B,1,H,W]: None = zero
+py::tuple composite_fragments_backward(In face, In bary, In faces, In faces_opacity, In vert_attrs, const std::optional<at::Tensor>& face_scale,
+                                       const std::optional<at::Tensor>& grad_image, const std::optional<at::Tensor>& grad_T,
+                                       const std::array<bool, 4>& need) {
+    const ShadeArgs a = shade_args(face, bary, faces, faces_opacity, vert_attrs, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    if (need[2] && !face_scale) err("composite_fragments_backward: the gradient of face_scale without face_scale");
+    at::Tensor gi, gt;
+    if (grad_image) {
+        if (grad_image->dim() != 4 || grad_image->size(0) != a.B || grad_image->size(1) != a.C || grad_image->size(2) != a.H ||
+            grad_image->size(3) != a.W || grad_image->device() != a.dev)
+            err("grad_image must have dimensions (B, C, H, W) on the device of pix_to_face");
+        gi = f32(*grad_image, "grad_image");
+    }
+    if (grad_T) {
+        if (grad_T->numel() != (int64_t)a.B * a.H * a.W || grad_T->device() != a.dev) err("grad_T must have dimensions (B, 1, H, W) on the device of pix_to_face");
+        gt = f32(*grad_T, "grad_T");
+    }
+    at::Tensor d_op, d_attrs, d_scale, d_bary;
+    if (need[0]) d_op = at::empty({a.F}, f32_on(a.dev));
+    if (need[1]) d_attrs = at::empty({a.P, a.C}, f32_on(a.dev));
+    if (need[2]) d_scale = at::empty({a.B, a.F}, f32_on(a.dev));
+    if (need[3]) d_bary = at::empty({a.B, a.K, 2, a.H, a.W}, f32_on(a.dev));
+    const auto out = [](at::Tensor& t) { return t.defined() ? mptr<float>(t) : nullptr; };
+    if (g_abi.composite_fragments_backward(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                           mptr<const int32_t>(a.faces), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
+                                           gi.defined() ? mptr<const float>(gi) : nullptr, gt.defined() ? mptr<const float>(gt) : nullptr,
+                                           out(d_op), out(d_attrs), out(d_scale), out(d_bary), a.stream()))
+        raise_lib();
+    const auto res = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+    return py::make_tuple(res(d_op), res(d_attrs), res(d_scale), res(d_bary));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -626,6 +720,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("grad_depth"), py::arg("pointBuffer"), py::arg("faceBuffer"), py::arg("binningBuffer"), py::arg("imageBuffer"), rows, flat_out,
         py::kw_only(), py::arg("full_grads") = false, camera_grads, alpha, py::arg("fragment_grads") = py::none());
     m.def("invert_mats", &invert_mats);
+    m.def("composite_fragments", &composite_fragments, py::arg("face"), py::arg("bary"), py::arg("faces"), py::arg("faces_opacity"),
+          py::arg("vert_attrs"), py::arg("face_scale") = py::none());
+    m.def("composite_fragments_backward", &composite_fragments_backward, py::arg("face"), py::arg("bary"), py::arg("faces"),
+          py::arg("faces_opacity"), py::arg("vert_attrs"), py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"),
+          py::arg("need") = std::array<bool, 4>{true, true, true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -648,6 +747,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("NUM_CHANNELS") = NUM_CHANNELS;
     m.attr("SUPPORTS_FLAT_OUT") = true;  // render_*_backward(flat_out=...), used by sharding.py
     m.attr("SUPPORTS_TET_FRAGMENT_GRADS") = true;  // render_tets_backward(fragment_grads=...), asked for by TetRenderer(fragment_grads=True)
+    // fragments.composite_fused; False: the loaded library predates dmesh_renderer_amd_shade.h
+    m.attr("SUPPORTS_FRAGMENT_COMPOSITE") = g_abi.composite_fragments != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

@@ -1,8 +1,9 @@
 """Shading from either renderer's per-pixel fragment lists (TriRenderer / TetRenderer(return_fragments=K), render_tri /
 render_tet(..., return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,K,2,H,W], count [B,H,W])).
 
-Plain torch, differentiable, no kernels.  What is HELD CONSTANT by every function here -- it comes from the rasteriser as
-data, not as a function of the scene -- is
+Plain torch and differentiable -- but for composite_fused, which is composite as one pair of HIP kernels (forward, backward:
+csrc/dmr_shade.hip) without the [B,K,H,W,3,C] intermediates composite keeps for autograd.  What is HELD CONSTANT by every
+function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
   * their order (the tile's depth sort),
   * the barycentrics (the (u, v) of the pixel's ray on each face: clamped to the face by the tri renderer, which blends every
@@ -33,7 +34,7 @@ from typing import Optional, Tuple
 
 import torch as th
 
-__all__ = ["blend_weights", "interpolate", "composite", "face_visibility"]
+__all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused"]
 
 
 def _opacity_slots(frag, faces_opacity: th.Tensor) -> Tuple[th.Tensor, th.Tensor]:
@@ -101,3 +102,83 @@ def face_visibility(frag, faces_opacity: th.Tensor, F: int) -> th.Tensor:
     B = w.shape[0]
     idx = frag.pix_to_face.clamp(min=0).long().reshape(B, -1)  # (empty slots add their weight 0 to face 0)
     return th.zeros(B, F, dtype=w.dtype, device=w.device).scatter_add(1, idx, w.reshape(B, -1))
+
+
+class _CompositeFn(th.autograd.Function):
+    """composite_fused's one Function over _C.composite_fragments / _C.composite_fragments_backward.  Arguments: pix_to_face, bary,
+    faces, faces_opacity, vert_attrs, face_scale (a tensor or None)."""
+
+    @staticmethod
+    def forward(ctx, face, bary, faces, faces_opacity, vert_attrs, face_scale):
+        image, t = _kernels().composite_fragments(face, bary, faces, faces_opacity, vert_attrs, face_scale)
+        ctx.save_for_backward(face, bary, faces, faces_opacity, vert_attrs, *(() if face_scale is None else (face_scale,)))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
+        return image, t
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_t):
+        face, bary, faces, faces_opacity, vert_attrs, *scale = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (face, bary, faces, faces_opacity, vert_attrs, face_scale)
+        need = (need[3], need[4], bool(scale) and need[5], need[1])
+        if (grad_image is None and grad_t is None) or not any(need):
+            return (None,) * 6
+        d_op, d_attrs, d_scale, d_bary = _kernels().composite_fragments_backward(
+            face, bary, faces, faces_opacity, vert_attrs, scale[0] if scale else None,
+            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
+        return None, d_bary, None, d_op, d_attrs, d_scale
+
+
+def _kernels():
+    """`_C` as the package holds it at call time (tests swap it), with the two composite calls -- or a TypeError."""
+    from . import _impl
+    c = _impl(None)
+    if not getattr(c, "SUPPORTS_FRAGMENT_COMPOSITE", False):
+        raise TypeError("composite_fused: the loaded libdmesh_renderer_hip.so / _C has no fused fragment compositing: rebuild "
+                        "(python -m dmesh_renderer_amd.build); fragments.composite is the torch path")
+    return c
+
+
+def composite_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.Tensor,
+                    face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """composite(...) as one fused HIP kernel, and one for its backward: the same (sum_k w_k s_k a_k [B,C,H,W], T [B,1,H,W]),
+    the same constants, gradients to faces_opacity, vert_attrs, face_scale and (with the renderer's fragment_grads) frag.bary --
+    each computed only when autograd asks for it -- without composite's [B,K,H,W,3,C] intermediates.  K <= 32, 1 <= C <= 256
+    (ValueError).  A slot whose face id lies outside [0, F) is empty, wherever it sits in the list; frag.count is not read.
+    HIP float32 tensors only (pix_to_face int32; faces of another integer dtype are cast, as TriRenderer does): anything else
+    is a TypeError -- composite is the torch path for it; nothing falls back silently."""
+    _kernels()
+    face, bary = frag.pix_to_face, frag.bary
+    if face.dim() != 4:
+        raise ValueError(f"composite_fused: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
+    B, K, H, W = face.shape
+    if tuple(bary.shape) != (B, K, 2, H, W):
+        raise ValueError(f"composite_fused: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {tuple(bary.shape)}")
+    if not 1 <= K <= 32:
+        raise ValueError(f"composite_fused: K must be in 1..32, got {K}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"composite_fused: faces must be [F,3], got {tuple(faces.shape)}")
+    F = faces.shape[0]
+    if tuple(faces_opacity.shape) != (F,):
+        raise ValueError(f"composite_fused: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
+    if vert_attrs.dim() != 2:
+        raise ValueError(f"composite_fused: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
+    if not 1 <= vert_attrs.shape[1] <= 256:
+        raise ValueError(f"composite_fused: C must be in 1..256, got {vert_attrs.shape[1]}")
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"composite_fused: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("frag.bary", bary), ("faces_opacity", faces_opacity), ("vert_attrs", vert_attrs)]
+    if face_scale is not None:
+        floats.append(("face_scale", face_scale))
+    torch_path = "fragments.composite is the torch path for anything else"
+    for name, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"composite_fused: {name} must be float32, got {t.dtype}; {torch_path}")
+    if face.dtype != th.int32:
+        raise TypeError(f"composite_fused: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == th.bool:
+        raise TypeError(f"composite_fused: faces must be an integer tensor, got {faces.dtype}; {torch_path}")
+    for name, t in [("frag.pix_to_face", face), ("faces", faces)] + floats:
+        if not t.is_cuda or t.device != face.device:
+            raise TypeError(f"composite_fused: {name} is on {t.device}: every tensor must be on one HIP device (there is no CPU "
+                            f"path); {torch_path}")
+    return _CompositeFn.apply(face, bary, faces.to(th.int32), faces_opacity, vert_attrs, face_scale)
