@@ -36,6 +36,9 @@
 //   composite_fragments(face, bary, faces, faces_opacity, vert_attrs, face_scale=None) -> (image [B,C,H,W], T [B,1,H,W]) and
 //   composite_fragments_backward(..., grad_image, grad_T, need=(opacity, attrs, scale, bary)) -> those four gradients or None:
 //                            fragments.composite_fused, over include/dmesh_renderer_amd_shade.h (SUPPORTS_FRAGMENT_COMPOSITE)
+//   composite_texture(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale=None, wrap=0) -> (image, T) and
+//   composite_texture_backward(..., grad_image, grad_T, need=(opacity, uvs, texture, scale, bary)) -> those five gradients or None:
+//                            fragments.composite_texture_fused, over include/dmesh_renderer_amd_texture.h (SUPPORTS_FRAGMENT_TEXTURE)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -55,6 +58,7 @@
 
 #include "../../include/dmesh_renderer_amd.h"
 #include "../../include/dmesh_renderer_amd_shade.h"
+#include "../../include/dmesh_renderer_amd_texture.h"
 
 namespace {
 
@@ -83,6 +87,9 @@ struct Abi {
     // dmesh_renderer_amd_shade.h: optional (SUPPORTS_FRAGMENT_COMPOSITE), a library without them still loads
     decltype(&dmr_composite_fragments) composite_fragments = nullptr;
     decltype(&dmr_composite_fragments_backward) composite_fragments_backward = nullptr;
+    // dmesh_renderer_amd_texture.h: optional too (SUPPORTS_FRAGMENT_TEXTURE)
+    decltype(&dmr_composite_texture) composite_texture = nullptr;
+    decltype(&dmr_composite_texture_backward) composite_texture_backward = nullptr;
 };
 
 Abi g_abi;
@@ -125,6 +132,10 @@ void load_abi() {
     g_abi.composite_fragments_backward =
         reinterpret_cast<decltype(g_abi.composite_fragments_backward)>(dlsym(g_abi.handle, "dmr_composite_fragments_backward"));
     if (!g_abi.composite_fragments || !g_abi.composite_fragments_backward) g_abi.composite_fragments = nullptr, g_abi.composite_fragments_backward = nullptr;
+    g_abi.composite_texture = reinterpret_cast<decltype(g_abi.composite_texture)>(dlsym(g_abi.handle, "dmr_composite_texture"));
+    g_abi.composite_texture_backward =
+        reinterpret_cast<decltype(g_abi.composite_texture_backward)>(dlsym(g_abi.handle, "dmr_composite_texture_backward"));
+    if (!g_abi.composite_texture || !g_abi.composite_texture_backward) g_abi.composite_texture = nullptr, g_abi.composite_texture_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -674,6 +685,96 @@ py::tuple composite_fragments_backward(In face, In bary, In faces, In faces_opac
     return py::make_tuple(res(d_op), res(d_attrs), res(d_scale), res(d_bary));
 }
 
+// ---- composite_texture / composite_texture_backward (dmesh_renderer_amd_texture.h): fragments.composite_texture_fused ----------
+struct TextureArgs {
+    at::Tensor face, bary, uvf, opacity, uvs, tex, scale;  // scale: undefined = none
+    int B, K, H, W, Pu, F, C, Ht, Wt, wrap;
+    c10::Device dev;
+    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+    const float* scale_ptr() const { return scale.defined() ? mptr<const float>(scale) : nullptr; }
+};
+
+TextureArgs texture_args(In face, In bary, In uv_faces, In faces_opacity, In vert_uvs, In texture, const std::optional<at::Tensor>& face_scale,
+                         int wrap) {
+    if (!g_abi.composite_texture)
+        err(g_abi.path + " does not export dmr_composite_texture: rebuild it (python -m dmesh_renderer_amd.build)");
+    const c10::Device dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    const int64_t B = face.size(0), K = face.size(1), H = face.size(2), W = face.size(3);
+    if (bary.dim() != 5 || bary.size(0) != B || bary.size(1) != K || bary.size(2) != 2 || bary.size(3) != H || bary.size(4) != W)
+        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
+    if (uv_faces.dim() != 2 || uv_faces.size(1) != 3) err("uv_faces must have dimensions (num_faces, 3)");
+    const int64_t F = uv_faces.size(0);
+    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != F) err("faces_opacity must have dimensions (num_faces,)");
+    if (vert_uvs.dim() != 2 || vert_uvs.size(1) != 2) err("vert_uvs must have dimensions (num_uvs, 2)");
+    if (texture.dim() != 3) err("texture must have dimensions (Ht, Wt, C)");
+    const int64_t Pu = vert_uvs.size(0), Ht = texture.size(0), Wt = texture.size(1), C = texture.size(2);
+    if (K < 1 || K > 32) err("composite_texture: K must be in 1..32, got " + std::to_string(K));
+    if (C < 1 || C > 32) err("composite_texture: C must be in 1..32, got " + std::to_string(C));
+    if (Ht < 1 || Wt < 1 || Ht >= ((int64_t)1 << 31) || Wt >= ((int64_t)1 << 31)) err("composite_texture: the texture must have at least one texel");
+    if (B < 1 || H < 1 || W < 1) err("composite_texture: empty fragment lists");
+    if (wrap != 0 && wrap != 1) err("composite_texture: wrap must be 0 (clamp) or 1 (repeat), got " + std::to_string(wrap));
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != B || face_scale->size(1) != F))
+        err("face_scale must have dimensions (B, num_faces)");
+    const std::pair<const at::Tensor*, const char*> same[6] = {{&bary, "bary"}, {&uv_faces, "uv_faces"}, {&faces_opacity, "faces_opacity"},
+                                                               {&vert_uvs, "vert_uvs"}, {&texture, "texture"},
+                                                               {face_scale ? &*face_scale : nullptr, "face_scale"}};
+    for (auto& t : same)
+        if (t.first && t.first->device() != dev) err(std::string(t.second) + " must be on the device of pix_to_face");
+    return {i32(face, "pix_to_face"), f32(bary, "bary"), i32(uv_faces, "uv_faces"), f32(faces_opacity, "faces_opacity"), f32(vert_uvs, "vert_uvs"),
+            f32(texture, "texture"), face_scale ? f32(*face_scale, "face_scale") : at::Tensor(),
+            (int)B, (int)K, (int)H, (int)W, (int)Pu, (int)F, (int)C, (int)Ht, (int)Wt, wrap, dev};
+}
+
+// -> (image [B,C,H,W], T [B,1,H,W])
+std::tuple<at::Tensor, at::Tensor> composite_texture(In face, In bary, In uv_faces, In faces_opacity, In vert_uvs, In texture,
+                                                     const std::optional<at::Tensor>& face_scale, int wrap) {
+    const TextureArgs a = texture_args(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    if (g_abi.composite_texture(a.B, a.K, a.H, a.W, a.Pu, a.F, a.C, a.Ht, a.Wt, a.wrap, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                mptr<const int32_t>(a.uvf), mptr<const float>(a.opacity), mptr<const float>(a.uvs), mptr<const float>(a.tex),
+                                a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
+        raise_lib();
+    return {image, T};
+}
+
+// need = (faces_opacity, vert_uvs, texture, face_scale, bary) -> those five gradients, None where not asked for; grad_image
+// [B,C,H,W] / grad_T [B,1,H,W]: None = zero
+py::tuple composite_texture_backward(In face, In bary, In uv_faces, In faces_opacity, In vert_uvs, In texture,
+                                     const std::optional<at::Tensor>& face_scale, int wrap, const std::optional<at::Tensor>& grad_image,
+                                     const std::optional<at::Tensor>& grad_T, const std::array<bool, 5>& need) {
+    const TextureArgs a = texture_args(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap);
+    c10::DeviceGuard guard(a.dev);
+    if (need[3] && !face_scale) err("composite_texture_backward: the gradient of face_scale without face_scale");
+    at::Tensor gi, gt;
+    if (grad_image) {
+        if (grad_image->dim() != 4 || grad_image->size(0) != a.B || grad_image->size(1) != a.C || grad_image->size(2) != a.H ||
+            grad_image->size(3) != a.W || grad_image->device() != a.dev)
+            err("grad_image must have dimensions (B, C, H, W) on the device of pix_to_face");
+        gi = f32(*grad_image, "grad_image");
+    }
+    if (grad_T) {
+        if (grad_T->numel() != (int64_t)a.B * a.H * a.W || grad_T->device() != a.dev) err("grad_T must have dimensions (B, 1, H, W) on the device of pix_to_face");
+        gt = f32(*grad_T, "grad_T");
+    }
+    at::Tensor d_op, d_uvs, d_tex, d_scale, d_bary;
+    if (need[0]) d_op = at::empty({a.F}, f32_on(a.dev));
+    if (need[1]) d_uvs = at::empty({a.Pu, 2}, f32_on(a.dev));
+    if (need[2]) d_tex = at::empty({a.Ht, a.Wt, a.C}, f32_on(a.dev));
+    if (need[3]) d_scale = at::empty({a.B, a.F}, f32_on(a.dev));
+    if (need[4]) d_bary = at::empty({a.B, a.K, 2, a.H, a.W}, f32_on(a.dev));
+    const auto out = [](at::Tensor& t) { return t.defined() ? mptr<float>(t) : nullptr; };
+    if (g_abi.composite_texture_backward(a.B, a.K, a.H, a.W, a.Pu, a.F, a.C, a.Ht, a.Wt, a.wrap, mptr<const int32_t>(a.face),
+                                         mptr<const float>(a.bary), mptr<const int32_t>(a.uvf), mptr<const float>(a.opacity),
+                                         mptr<const float>(a.uvs), mptr<const float>(a.tex), a.scale_ptr(),
+                                         gi.defined() ? mptr<const float>(gi) : nullptr, gt.defined() ? mptr<const float>(gt) : nullptr,
+                                         out(d_op), out(d_uvs), out(d_tex), out(d_scale), out(d_bary), a.stream()))
+        raise_lib();
+    const auto res = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+    return py::make_tuple(res(d_op), res(d_uvs), res(d_tex), res(d_scale), res(d_bary));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -725,6 +826,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("composite_fragments_backward", &composite_fragments_backward, py::arg("face"), py::arg("bary"), py::arg("faces"),
           py::arg("faces_opacity"), py::arg("vert_attrs"), py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"),
           py::arg("need") = std::array<bool, 4>{true, true, true, true});
+    m.def("composite_texture", &composite_texture, py::arg("face"), py::arg("bary"), py::arg("uv_faces"), py::arg("faces_opacity"),
+          py::arg("vert_uvs"), py::arg("texture"), py::arg("face_scale") = py::none(), py::arg("wrap") = 0);
+    m.def("composite_texture_backward", &composite_texture_backward, py::arg("face"), py::arg("bary"), py::arg("uv_faces"),
+          py::arg("faces_opacity"), py::arg("vert_uvs"), py::arg("texture"), py::arg("face_scale"), py::arg("wrap"), py::arg("grad_image"),
+          py::arg("grad_T"), py::arg("need") = std::array<bool, 5>{true, true, true, true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -749,6 +855,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_TET_FRAGMENT_GRADS") = true;  // render_tets_backward(fragment_grads=...), asked for by TetRenderer(fragment_grads=True)
     // fragments.composite_fused; False: the loaded library predates dmesh_renderer_amd_shade.h
     m.attr("SUPPORTS_FRAGMENT_COMPOSITE") = g_abi.composite_fragments != nullptr;
+    // fragments.composite_texture_fused; False: the loaded library predates dmesh_renderer_amd_texture.h
+    m.attr("SUPPORTS_FRAGMENT_TEXTURE") = g_abi.composite_texture != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

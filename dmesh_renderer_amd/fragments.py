@@ -2,7 +2,9 @@
 render_tet(..., return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,K,2,H,W], count [B,H,W])).
 
 Plain torch and differentiable -- but for composite_fused, which is composite as one pair of HIP kernels (forward, backward:
-csrc/dmr_shade.hip) without the [B,K,H,W,3,C] intermediates composite keeps for autograd.  What is HELD CONSTANT by every
+csrc/dmr_shade.hip) without the [B,K,H,W,3,C] intermediates composite keeps for autograd, and composite_texture_fused, which
+is composite_texture (a bilinear texture sampled at per-corner UVs, then blended) as another pair (csrc/dmr_texture.hip).
+What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
   * their order (the tile's depth sort),
@@ -34,7 +36,10 @@ from typing import Optional, Tuple
 
 import torch as th
 
-__all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused"]
+__all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
+           "composite_texture_fused"]
+
+WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
 
 def _opacity_slots(frag, faces_opacity: th.Tensor) -> Tuple[th.Tensor, th.Tensor]:
@@ -182,3 +187,145 @@ def composite_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs
             raise TypeError(f"composite_fused: {name} is on {t.device}: every tensor must be on one HIP device (there is no CPU "
                             f"path); {torch_path}")
     return _CompositeFn.apply(face, bary, faces.to(th.int32), faces_opacity, vert_attrs, face_scale)
+
+
+def _wrap_index(i: th.Tensor, n: int, wrap: str) -> th.Tensor:
+    return i.clamp(0, n - 1) if wrap == "clamp" else th.remainder(i, n)
+
+
+def composite_texture(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_uvs: th.Tensor, texture: th.Tensor,
+                      face_scale: Optional[th.Tensor] = None, *, uv_faces: Optional[th.Tensor] = None,
+                      wrap: str = "clamp") -> Tuple[th.Tensor, th.Tensor]:
+    """Front-to-back blend of a texture sampled at every fragment: (sum_k w_k s_k c_k [B,C,H,W], T [B,1,H,W]), with w_k, s_k,
+    T and the empty-slot rule exactly those of composite, and c_k the bilinear sample of texture [Ht,Wt,C] (channel-last; one
+    image shared by every view) at
+        (s, t)_k = (1 - u - v) UV[c0] + u UV[c1] + v UV[c2],   (c0, c1, c2) = uv_faces[face_k],  UV = vert_uvs [Pu,2]
+    uv_faces [F,3] holds per-corner rows of vert_uvs (the OBJ `vt` convention: seams work); None: faces.  Texel centres sit at
+    half-integers, t = 0 is row 0 (no flip):
+        x = s Wt - 0.5, x0 = floor(x), fx = x - x0, ix0 = wrap(x0, Wt), ix1 = wrap(x0 + 1, Wt)           (likewise y, t, Ht)
+        c_k = (1-fy) ((1-fx) tex[iy0,ix0] + fx tex[iy0,ix1]) + fy ((1-fx) tex[iy1,ix0] + fx tex[iy1,ix1])
+    wrap: "clamp" (indices clamped to [0, n-1]) or "repeat" (remainder mod n); fx, fy come from the unwrapped coordinate, so the
+    derivative in x is the difference of the two wrapped texels -- 0 at a clamped border without a special case.
+    Bilinear only: no mip levels, no nearest filter, no per-view textures.
+    Constants: the faces, their order, the texel cell (the floor) -- and the barycentrics unless the renderer's fragment_grads
+    made frag.bary differentiable.  Differentiable in faces_opacity, vert_uvs, texture, face_scale and frag.bary."""
+    if wrap not in WRAPS:
+        raise ValueError(f"composite_texture: wrap must be one of {WRAPS}, got {wrap!r}")
+    face = frag.pix_to_face
+    used = face >= 0
+    _, o = _opacity_slots(frag, faces_opacity)
+    t = _transmittance(o)
+    w = o * t[:, :-1]
+    idx = face.clamp(min=0).long()
+    if face_scale is not None:
+        B = idx.shape[0]
+        w = w * th.gather(face_scale, 1, idx.reshape(B, -1)).reshape(idx.shape).to(w.dtype)
+    Ht, Wt, _ = texture.shape
+    uv = vert_uvs[(faces if uv_faces is None else uv_faces).long()[idx]]   # [B,K,H,W,3,2]
+    u, v = frag.bary[:, :, 0].to(uv.dtype), frag.bary[:, :, 1].to(uv.dtype)
+    st = (th.stack([1 - u - v, u, v], dim=-1).unsqueeze(-1) * uv).sum(-2)  # [B,K,H,W,2]
+    x, y = st[..., 0] * Wt - 0.5, st[..., 1] * Ht - 0.5
+    x0, y0 = th.floor(x.detach()), th.floor(y.detach())
+    fx, fy = (x - x0).unsqueeze(-1), (y - y0).unsqueeze(-1)
+    ix0, ix1 = _wrap_index(x0.long(), Wt, wrap), _wrap_index(x0.long() + 1, Wt, wrap)
+    iy0, iy1 = _wrap_index(y0.long(), Ht, wrap), _wrap_index(y0.long() + 1, Ht, wrap)
+    c = (1 - fy) * ((1 - fx) * texture[iy0, ix0] + fx * texture[iy0, ix1]) + fy * ((1 - fx) * texture[iy1, ix0] + fx * texture[iy1, ix1])
+    c = c * used.unsqueeze(-1).to(c.dtype)                                  # [B,K,H,W,C]
+    return (w.unsqueeze(-1).to(c.dtype) * c).sum(1).permute(0, 3, 1, 2), t[:, -1:]
+
+
+class _CompositeTextureFn(th.autograd.Function):
+    """composite_texture_fused's one Function over _C.composite_texture / _C.composite_texture_backward.  Arguments: pix_to_face,
+    bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale (a tensor or None), wrap (0 / 1)."""
+
+    @staticmethod
+    def forward(ctx, face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap):
+        image, t = _texture_kernels().composite_texture(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap)
+        ctx.save_for_backward(face, bary, uv_faces, faces_opacity, vert_uvs, texture, *(() if face_scale is None else (face_scale,)))
+        ctx.wrap = wrap
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
+        return image, t
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_t):
+        face, bary, uv_faces, faces_opacity, vert_uvs, texture, *scale = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap)
+        need = (need[3], need[4], need[5], bool(scale) and need[6], need[1])
+        if (grad_image is None and grad_t is None) or not any(need):
+            return (None,) * 8
+        d_op, d_uvs, d_tex, d_scale, d_bary = _texture_kernels().composite_texture_backward(
+            face, bary, uv_faces, faces_opacity, vert_uvs, texture, scale[0] if scale else None, ctx.wrap,
+            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
+        return None, d_bary, None, d_op, d_uvs, d_tex, d_scale, None
+
+
+def _texture_kernels():
+    """`_C` as the package holds it at call time (tests swap it), with the two texture calls -- or a TypeError."""
+    from . import _impl
+    c = _impl(None)
+    if not getattr(c, "SUPPORTS_FRAGMENT_TEXTURE", False):
+        raise TypeError("composite_texture_fused: the loaded libdmesh_renderer_hip.so / _C has no fused texture compositing: rebuild "
+                        "(python -m dmesh_renderer_amd.build); fragments.composite_texture is the torch path")
+    return c
+
+
+def composite_texture_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_uvs: th.Tensor, texture: th.Tensor,
+                            face_scale: Optional[th.Tensor] = None, *, uv_faces: Optional[th.Tensor] = None,
+                            wrap: str = "clamp") -> Tuple[th.Tensor, th.Tensor]:
+    """composite_texture(...) as one fused HIP kernel, and one for its backward: the same (image [B,C,H,W], T [B,1,H,W]), the same
+    constants, gradients to faces_opacity, vert_uvs, texture, face_scale and (with the renderer's fragment_grads) frag.bary --
+    each computed only when autograd asks for it -- without the [B,K,H,W,C] samples and the index_put backward of the torch
+    path.  Bilinear only: no mip levels, no nearest filter, no per-view textures.  K <= 32, 1 <= C <= 32, Ht, Wt >= 1,
+    Ht * Wt * ceil(C / 4) < 2^32 - 1, wrap in {"clamp", "repeat"} (ValueError).  A slot whose face id lies outside [0, F) is
+    empty, wherever it sits in the list; frag.count is not read.  Where a sample sits exactly on a texel-centre line the UV and
+    barycentric gradients are those of the cell the float32 coordinate fell in.  HIP float32 tensors only (pix_to_face int32;
+    faces / uv_faces of another integer dtype are cast): anything else is a TypeError -- composite_texture is the torch path
+    for it; nothing falls back silently."""
+    name = "composite_texture_fused"
+    _texture_kernels()
+    if wrap not in WRAPS:
+        raise ValueError(f"{name}: wrap must be one of {WRAPS}, got {wrap!r}")
+    face, bary = frag.pix_to_face, frag.bary
+    if face.dim() != 4:
+        raise ValueError(f"{name}: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
+    B, K, H, W = face.shape
+    if tuple(bary.shape) != (B, K, 2, H, W):
+        raise ValueError(f"{name}: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {tuple(bary.shape)}")
+    if not 1 <= K <= 32:
+        raise ValueError(f"{name}: K must be in 1..32, got {K}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    F = faces.shape[0]
+    corners = faces if uv_faces is None else uv_faces
+    if tuple(corners.shape) != (F, 3):
+        raise ValueError(f"{name}: uv_faces must be [F,3] = {(F, 3)}, got {tuple(corners.shape)}")
+    if tuple(faces_opacity.shape) != (F,):
+        raise ValueError(f"{name}: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
+    if vert_uvs.dim() != 2 or vert_uvs.shape[1] != 2:
+        raise ValueError(f"{name}: vert_uvs must be [Pu,2], got {tuple(vert_uvs.shape)}")
+    if texture.dim() != 3:
+        raise ValueError(f"{name}: texture must be [Ht,Wt,C], got {tuple(texture.shape)}")
+    Ht, Wt, C = texture.shape
+    if not 1 <= C <= 32:
+        raise ValueError(f"{name}: C must be in 1..32, got {C}")
+    if Ht < 1 or Wt < 1 or Ht * Wt * ((C + 3) // 4) >= 2 ** 32 - 1:
+        raise ValueError(f"{name}: texture must have Ht, Wt >= 1 and Ht * Wt * ceil(C / 4) < 2^32 - 1, got {tuple(texture.shape)}")
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("frag.bary", bary), ("faces_opacity", faces_opacity), ("vert_uvs", vert_uvs), ("texture", texture)]
+    if face_scale is not None:
+        floats.append(("face_scale", face_scale))
+    torch_path = "fragments.composite_texture is the torch path for anything else"
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if face.dtype != th.int32:
+        raise TypeError(f"{name}: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
+    ints = [("faces", faces)] + ([] if uv_faces is None else [("uv_faces", uv_faces)])
+    for n, t in ints:
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == th.bool:
+            raise TypeError(f"{name}: {n} must be an integer tensor, got {t.dtype}; {torch_path}")
+    for n, t in [("frag.pix_to_face", face)] + ints + floats:
+        if not t.is_cuda or t.device != face.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    return _CompositeTextureFn.apply(face, bary, corners.to(th.int32), faces_opacity, vert_uvs, texture, face_scale, WRAPS.index(wrap))
