@@ -17,6 +17,7 @@
 
 #include "dmr_kernels.hpp"
 #include "dmr_shade_table.hpp"
+#include "dmr_texture_wrap.hpp"
 #include "../../include/dmesh_renderer_amd_texture.h"
 
 namespace dmr {
@@ -48,23 +49,7 @@ struct TexParams {
     const float* __restrict__ scale;      // [B,F] or null
 };
 
-// wrap(x0, n), wrap(x0 + 1, n) of an integer-valued float x0 (or anything else a float can hold): both in [0, n-1].
-__device__ __forceinline__ void wrap_pair(float x0, int n, int wrap, int& i0, int& i1) {
-    const float nf = (float)n;
-    if (wrap) x0 = x0 - floorf(x0 / nf) * nf;  // remainder, in float: exact while |x0| < 2^24
-    x0 = x0 >= -1.f ? x0 : -1.f;               // (false for a NaN too)
-    x0 = x0 <= nf ? x0 : nf;
-    int i = (int)x0;                           // in [-1, n] (saturated where float(n) rounded up to 2^31)
-    if (wrap) {
-        if (i < 0) i += n;
-        if (i >= n) i -= n;
-        i0 = min(max(i, 0), n - 1);
-        i1 = i0 + 1 >= n ? 0 : i0 + 1;
-    } else {
-        i0 = min(max(i, 0), n - 1);
-        i1 = max(min(i, n - 2) + 1, 0);        // min(max(i + 1, 0), n - 1) without the overflow of i + 1
-    }
-}
+// wrap_pair(x0, n, wrap, i0, i1): dmr_texture_wrap.hpp.
 
 // A slot's sample: the four texels (row-major indices into [Ht*Wt]: 00 = (iy0, ix0), 01 = (iy0, ix1), 10, 11) and the cell's
 // fractions.  (S_j, T_j): the corners' UVs.

@@ -14,22 +14,25 @@ import fragments_ref as FR
 from dmesh_renderer_amd import Fragments, scenes
 from dmesh_renderer_amd import fragments as FG
 from harness import TET_ARGS, TRI_ARGS, capture_replay, replay
+from shading_cases import (EDGE_FRAME_C, EDGE_FRAME_K, EDGE_FRAMES, FRAME, MERGE_F, MERGE_FRAME, MERGE_K, MERGE_P, NEW_FRAME, SHADE_C,
+                           SHADE_GRAPH, SHADE_K, SHADE_MATRIX, SHADE_MERGE_C, SHADE_MISALIGNED, SHADE_ONLY_SOME, SIZES, one_float_in)
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = FR.FWD_TOL
 GRAD_TOL = 1e-4
-B, H, W = 2, 24, 40  # partial tiles in both axes
+B, H, W = FRAME  # partial tiles in both axes
 GRADS = ("faces_opacity", "vert_attrs", "face_scale", "bary")
-# many lanes of a wave share a key (the merge path) / a tile holds more distinct vertex rows than the table's 560 slots
-SIZES = {"shared_keys": (7, 9), "table_overflow": (6000, 9000)}
+# SIZES (shading_cases): many lanes of a wave share a key (the merge path) / a tile holds more distinct vertex rows than the
+# table's 560 slots
 
 
 @functools.lru_cache(maxsize=None)
-def _lists(K, C, size):
+def _lists(K, C, size, frame=FRAME):
     """Caller-made lists (CPU float32 / int32): random face ids with -1 and ids >= F anywhere in a list, one face of opacity
     exactly 1 and one of opacity exactly 0, and the upstream gradients of the image and of T."""
+    B, H, W = frame
     F, P = SIZES[size]
     g = th.Generator().manual_seed(1000 * K + 10 * C + (F > 100))
     face = th.randint(0, F, (B, K, H, W), generator=g, dtype=th.int32)
@@ -49,9 +52,12 @@ def _lists(K, C, size):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(K, C, size, with_scale):
+def _reference(K, C, size, with_scale, frame=FRAME):
     """fragments.composite in float64 on the CPU -> image, T, the four gradients (numpy).  Ids >= F are empty slots: -1 here."""
-    d = _lists(K, C, size)
+    return _model(_lists(K, C, size, frame), with_scale)
+
+
+def _model(d, with_scale):
     F = d["faces"].shape[0]
     face = th.where(d["face"] >= F, th.full_like(d["face"], -1), d["face"])
     lv = {k: d[k].double().requires_grad_(True) for k in GRADS if with_scale or k != "face_scale"}
@@ -61,11 +67,12 @@ def _reference(K, C, size, with_scale):
     return image.detach().numpy(), T.detach().numpy(), {k: v.grad.numpy() for k, v in lv.items()}
 
 
-def _fused(d, dev, with_scale, want=GRADS, g_image=True, g_T=True):
-    """composite_fused on the device, gradients of `want` only -> image, T, {name: grad}."""
+def _fused(d, dev, with_scale, want=GRADS, g_image=True, g_T=True, leaves=None):
+    """composite_fused on the device, gradients of `want` only -> image, T, {name: grad}.  leaves: {name: the device tensor to
+    differentiate, as it is (its storage and offset)} in place of a fresh copy of d[name]."""
     t = {k: v.to(dev) for k, v in d.items()}
     names = [k for k in want if with_scale or k != "face_scale"]
-    lv = {k: t[k].clone().requires_grad_(True) for k in names}
+    lv = {k: (leaves[k].detach() if leaves and k in leaves else t[k].clone()).requires_grad_(True) for k in names}
     image, T = FG.composite_fused(Fragments(t["face"], lv.get("bary", t["bary"]), None), t["faces"], lv.get("faces_opacity", t["faces_opacity"]),
                                   lv.get("vert_attrs", t["vert_attrs"]), face_scale=lv.get("face_scale", t["face_scale"]) if with_scale else None)
     loss = 0
@@ -79,8 +86,8 @@ def _fused(d, dev, with_scale, want=GRADS, g_image=True, g_T=True):
 
 @pytest.mark.parametrize("size", list(SIZES))
 @pytest.mark.parametrize("with_scale", (False, True), ids=("no_scale", "scale"))
-@pytest.mark.parametrize("C", (1, 3, 5, 35))
-@pytest.mark.parametrize("K", (1, 5, 32))
+@pytest.mark.parametrize("C", SHADE_C)
+@pytest.mark.parametrize("K", SHADE_K)
 def test_caller_made_lists(hip_device, K, C, with_scale, size):
     """(a) image, T and all four gradients against the float64 model.
     Measured on the MI355X over the 48 cases: image <= 5.0e-7, T <= 1.9e-7 absolute; rel_err of the gradients <= 4.3e-7
@@ -109,7 +116,7 @@ def test_only_some_gradients_wanted(hip_device):
     """(b) each of the four alone equals the four together; a backward with only T's upstream equals one with a zero image
     upstream beside it, one with only the image's equals one with a zero upstream of T, and the two add up to the model's
     gradients.  Two evaluations of the same sums: sum_order_tol."""
-    K, C, size = 5, 5, "shared_keys"
+    K, C, size = SHADE_ONLY_SOME
     d = _lists(K, C, size)
     dev = hip_device
     _, _, g_all = _fused(d, dev, True)
@@ -185,8 +192,8 @@ def test_rendered_tet_lists(hip_device):
 
 def test_graph_capture(hip_device):
     """(e) one forward + backward captured into a HIP graph and replayed: the replayed gradients are the eager ones."""
-    K, C = 5, 35
-    d = _lists(K, C, "table_overflow")
+    K, C, size = SHADE_GRAPH
+    d = _lists(K, C, size)
     dev = hip_device
     t = {k: v.to(dev) for k, v in d.items()}
     lv = [t[k].clone().requires_grad_(True) for k in GRADS]
@@ -203,3 +210,137 @@ def test_graph_capture(hip_device):
         e = rel_err(a.cpu().numpy(), b.cpu().numpy())
         print(f"\ngraph replay vs eager dL_d{k}: {e:.2e} (max |eager| {float(b.abs().max()):.3g})")
         assert float(b.abs().max()) > 0 and e <= sum_order_tol(k), (k, e)
+
+
+# ---------------------------------------------------------------------------
+# Every instantiation (shading_cases: the tables below and what each row reaches; tests/test_shading_coverage_cpu.py checks
+# without a GPU that together they reach all 20, and that every case here meets check_inputs).
+# ---------------------------------------------------------------------------
+def check_inputs(d, ref, signed=True):
+    """What a case's inputs must give before anything is compared: a non-zero reference for every gradient (an all-empty list
+    cannot pass), and, under a one-signed upstream, opacity and scale gradients that no cancellation made small."""
+    _, _, g_r = ref
+    for k, r in g_r.items():
+        assert float(np.abs(r).max()) > 0, k
+    if not signed:
+        assert float(np.abs(g_r["faces_opacity"]).max()) > 1 and float(np.abs(g_r["face_scale"]).max()) > 1
+
+
+def _check(tag, d, ref, got, signed=True):
+    """image, T and every gradient of `got` (device) against the float64 model `ref`, as test_caller_made_lists does."""
+    check_inputs(d, ref, signed)
+    image_r, T_r, g_r = ref
+    image, T, g = got
+    assert tuple(image.shape) == image_r.shape and tuple(T.shape) == T_r.shape
+    ei, eT = float(np.abs(image.cpu().numpy() - image_r).max()), float(np.abs(T.cpu().numpy() - T_r).max())
+    print(f"\n{tag}: image {ei:.2e} T {eT:.2e} (max |image| {np.abs(image_r).max():.3g})")
+    assert ei <= FWD_TOL and eT <= FWD_TOL
+    assert set(g) == set(g_r)
+    for k, r in g_r.items():
+        x = g[k].cpu().numpy()
+        assert x.shape == r.shape and x.dtype == np.float32
+        e = rel_err(x, r)
+        print(f"  dL_d{k} {e:.2e} (max |ref| {np.abs(r).max():.3g})")
+        assert e <= GRAD_TOL, (k, e)
+    F = d["faces"].shape[0]
+    empty = ((d["face"] < 0) | (d["face"] >= F))[:, :, None].expand(-1, -1, 2, -1, -1)
+    if bool(empty.any()):  # empty slots: exact zeros in dL/dbary
+        assert float(g["bary"].cpu()[empty].abs().max()) == 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_lists(C):
+    """K = 6 on a 32 x 32 view, F = 5.  Slot j < 5 holds face (px >> j) & 1 in the rows py < 16 and (py >> j) & 1 below: stripes of
+    period 2, 4, 8, 16, 32 along either axis, so each butterfly level of shade_merge meets equal keys alone, whichever lanes
+    FragSlots gives a pixel's neighbours.  Slot 5: one face over every pixel (the real workload's most common tile: the most
+    retirements, 16 rows adding into one f64 cell).  Opacities in (0.05, 0.4), no empty slot, one-signed upstreams."""
+    B, H, W = MERGE_FRAME
+    g = th.Generator().manual_seed(77 + C)
+    py, px = th.meshgrid(th.arange(H), th.arange(W), indexing="ij")
+    face = th.empty(B, MERGE_K, H, W, dtype=th.int32)
+    for j in range(5):
+        face[:, j] = th.where(py < 16, (px >> j) & 1, (py >> j) & 1).to(th.int32)
+    face[:, 5] = 3
+    bary = th.rand(B, MERGE_K, 2, H, W, generator=g) * 0.6 - 0.05
+    faces = th.randint(0, MERGE_P, (MERGE_F, 3), generator=g, dtype=th.int32)
+    opacity = 0.05 + 0.35 * th.rand(MERGE_F, generator=g)
+    assert bool(((opacity > 0.05) & (opacity < 0.4)).all())
+    attrs = th.randn(MERGE_P, C, generator=g)
+    scale = th.rand(B, MERGE_F, generator=g) + 0.5
+    g_image = th.rand(B, C, H, W, generator=g) + 0.5
+    g_T = th.rand(B, 1, H, W, generator=g) + 0.5
+    return dict(face=face, bary=bary, faces=faces, faces_opacity=opacity, vert_attrs=attrs, face_scale=scale, g_image=g_image, g_T=g_T)
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_reference(C):
+    return _model(_merge_lists(C), True)
+
+
+def new_cases():
+    """(tag, lists, float64 reference, one-signed upstream) of every case below: what check_inputs must hold for."""
+    for K, C, with_scale, size in SHADE_MATRIX:
+        yield f"matrix K{K} C{C} {size} scale {with_scale}", _lists(K, C, size, NEW_FRAME), _reference(K, C, size, with_scale, NEW_FRAME), True
+    for K, C in SHADE_MISALIGNED:
+        yield f"misaligned K{K} C{C}", _lists(K, C, "table_overflow", NEW_FRAME), _reference(K, C, "table_overflow", True, NEW_FRAME), True
+    yield "merge levels", _merge_lists(SHADE_MERGE_C), _merge_reference(SHADE_MERGE_C), False
+    for frame in EDGE_FRAMES:
+        yield (f"frame {frame}", _lists(EDGE_FRAME_K, EDGE_FRAME_C, "shared_keys", frame),
+               _reference(EDGE_FRAME_K, EDGE_FRAME_C, "shared_keys", True, frame), True)
+
+
+@pytest.mark.parametrize("K,C,with_scale,size", SHADE_MATRIX,
+                         ids=[f"K{K}-C{C}-{'scale' if s else 'no_scale'}-{size}" for K, C, s, size in SHADE_MATRIX])
+def test_instantiation_matrix(hip_device, K, C, with_scale, size):
+    """(f) the backward's KMAX = 16 kernels, K == KMAX at 4, 8 and 16, the first K of the next instantiation (9, 17), and the
+    float4 row loads (C % 4 == 0) with the forward's CH 16 guard at C = 20 and both walks at SHADE_MAX_C: image, T and all four
+    gradients against the float64 model, on a 17 x 33 view.
+    Measured on the MI355X over the 27 cases: image <= 4.8e-7, T <= 1.9e-7 absolute; rel_err of the gradients <= 3.2e-7
+    (faces_opacity), 1.5e-7 (vert_attrs), 8.8e-7 (face_scale), 2.4e-7 (bary)."""
+    d = _lists(K, C, size, NEW_FRAME)
+    _check(f"K {K} C {C} {size} scale {with_scale}", d, _reference(K, C, size, with_scale, NEW_FRAME), _fused(d, hip_device, with_scale))
+
+
+@pytest.mark.parametrize("K,C", SHADE_MISALIGNED, ids=[f"K{K}-C{C}" for K, C in SHADE_MISALIGNED])
+def test_misaligned_base(hip_device, K, C):
+    """(g) C % 4 == 0 with vert_attrs one float into a larger buffer: the binding's .contiguous() keeps that pointer, so the
+    scalar loads run (vec = 0) where the same values in a buffer of their own take the float4 loads.  Both against the float64
+    model, and against each other (forward FWD_TOL; gradients: the same sums in another order, sum_order_tol).
+    Measured on the MI355X over the 3 cases, either call against the model: image, T <= 1.6e-7, gradients <= 1.7e-7; misaligned
+    against aligned: the forward bit-equal, dL_dfaces_opacity 6.8e-8, dL_dvert_attrs 3.0e-8, dL_dface_scale 5.1e-8, dL_dbary 0."""
+    dev, size = hip_device, "table_overflow"
+    d = _lists(K, C, size, NEW_FRAME)
+    ref = _reference(K, C, size, True, NEW_FRAME)
+    off, own = one_float_in(d["vert_attrs"].to(dev)), d["vert_attrs"].to(dev).clone()
+    assert off.is_contiguous() and off.data_ptr() % 16 == 4 and own.data_ptr() % 16 == 0
+    assert bool((off == own).all())
+    got = _fused(d, dev, True, leaves={"vert_attrs": off})
+    _check(f"K {K} C {C} misaligned", d, ref, got)
+    alg = _fused(d, dev, True, leaves={"vert_attrs": own})
+    _check(f"K {K} C {C} aligned", d, ref, alg)
+    ei, eT = float((got[0] - alg[0]).abs().max()), float((got[1] - alg[1]).abs().max())
+    print(f"misaligned vs aligned: image {ei:.2e} T {eT:.2e}; forward bit-equal: {bool(th.equal(got[0], alg[0]) and th.equal(got[1], alg[1]))}")
+    assert ei <= FWD_TOL and eT <= FWD_TOL
+    for k in GRADS:
+        e = rel_err(got[2][k].cpu().numpy(), alg[2][k].cpu().numpy())
+        print(f"  dL_d{k} misaligned vs aligned {e:.2e}")
+        assert e <= sum_order_tol(k), (k, e)
+
+
+def test_merge_levels(hip_device):
+    """(h) shade_merge's four levels one at a time, and one face over a whole tile (_merge_lists), against the float64 model;
+    the upstreams are one-signed, so the opacity and scale gradients (max |ref| > 1, asserted) cannot agree by cancellation.
+    Measured on the MI355X: image 3.9e-7, T 3.1e-8; dL_dfaces_opacity 1.5e-7, dL_dvert_attrs 4.3e-8, dL_dface_scale 7.5e-8,
+    dL_dbary 1.5e-7."""
+    d = _merge_lists(SHADE_MERGE_C)
+    _check(f"merge levels K {MERGE_K} C {SHADE_MERGE_C}", d, _merge_reference(SHADE_MERGE_C), _fused(d, hip_device, True), signed=False)
+
+
+@pytest.mark.parametrize("frame", EDGE_FRAMES, ids=["x".join(map(str, f)) for f in EDGE_FRAMES])
+def test_frames(hip_device, frame):
+    """(i) a view of whole tiles only, and views of one pixel: one live lane per workgroup, the other 255 through every merge
+    and barrier with key -1.
+    Measured on the MI355X over both: image <= 2.0e-7, T <= 6.0e-8; gradients <= 2.3e-7 (face_scale)."""
+    K, C, size = EDGE_FRAME_K, EDGE_FRAME_C, "shared_keys"
+    d = _lists(K, C, size, frame)
+    _check(f"frame {frame} K {K} C {C}", d, _reference(K, C, size, True, frame), _fused(d, hip_device, True))

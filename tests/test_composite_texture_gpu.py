@@ -22,6 +22,9 @@ import fragments_ref as FR
 from dmesh_renderer_amd import Fragments, scenes
 from dmesh_renderer_amd import fragments as FG
 from harness import TRI_ARGS, capture_replay, replay
+from shading_cases import (EDGE_FRAME_C, EDGE_FRAME_K, EDGE_FRAMES, FRAME, MERGE_F, MERGE_FRAME, MERGE_K, MERGE_P, NEW_FRAME, SIZES,
+                           TEXTURE_CASES, TEXTURE_EDGE_FRAME, TEXTURE_GRAPH, TEXTURE_MATRIX, TEXTURE_MERGE, TEXTURE_MISALIGNED,
+                           TEXTURE_NO_TEX_GRAD, TEXTURE_ONLY_SOME, one_float_in)
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
@@ -29,12 +32,12 @@ pytestmark = pytest.mark.gpu
 FWD_TOL = FR.FWD_TOL
 GRAD_TOL = 1e-4
 LINE_BAND = 1e-3
-B, H, W = 2, 24, 40  # partial tiles in both axes
+B, H, W = FRAME  # partial tiles in both axes
 GRADS = ("faces_opacity", "vert_uvs", "texture", "face_scale", "bary")
-# (F, Pu): many lanes of a wave share a key (the merge path, a handful of table cells) / a tile holds more distinct UV rows than
-# the 560 cells of that table and, with the 32 x 48 texture, fills the texel table to its probe limit at K = 5 (about 1400 of
-# the 1536 texels against 1408 cells) and past its size at K = 32 (1024 cells): rows leave with direct atomics
-SIZES = {"shared_keys": (7, 9), "table_overflow": (6000, 9000)}
+# SIZES (shading_cases), (F, Pu): many lanes of a wave share a key (the merge path, a handful of table cells) / a tile holds
+# more distinct UV rows than the 560 cells of that table and, with the 32 x 48 texture, fills the texel table to its probe limit
+# at K = 5 (about 1400 of the 1536 texels against 1408 cells) and past its size at K = 32 (1024 cells): rows leave with direct
+# atomics
 
 
 def _sample_xy(face, bary, corners, uvs, Ht, Wt):
@@ -58,10 +61,11 @@ def _off_the_lines(face, bary, corners, uvs, Ht, Wt):
 
 
 @functools.lru_cache(maxsize=None)
-def _lists(K, C, tex, size, with_uvf):
+def _lists(K, C, tex, size, with_uvf, frame=FRAME):
     """Caller-made lists (CPU float32 / int32), as test_composite_fused_gpu makes them: random face ids with -1 and ids >= F
     anywhere in a list, one face of opacity exactly 1 and one of opacity exactly 0; UVs in [-1, 2] (both wraps act on both
     sides); the upstream gradients of the image and of T.  Slots near a texel-centre line are already emptied."""
+    B, H, W = frame
     F, Pu = SIZES[size]
     Ht, Wt = tex
     g = th.Generator().manual_seed(1000 * K + 10 * C + (F > 100) + 100000 * Wt)
@@ -98,20 +102,24 @@ def _model(d, wrap, with_scale, dtype, grads=True):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(K, C, tex, size, with_uvf, wrap, with_scale):
+def _reference(K, C, tex, size, with_uvf, wrap, with_scale, frame=FRAME):
     """The float64 model and the image bound: max(FWD_TOL, 4 x |model in float32 - model in float64|)."""
-    d = _lists(K, C, tex, size, with_uvf)
+    return _reference_of(_lists(K, C, tex, size, with_uvf, frame), wrap, with_scale)
+
+
+def _reference_of(d, wrap, with_scale):
     image, T, grads = _model(d, wrap, with_scale, th.float64)
     image32, _, _ = _model(d, wrap, with_scale, th.float32, grads=False)
     noise = float(np.abs(image32.astype(np.float64) - image).max())
     return image, T, grads, noise, max(FWD_TOL, 4 * noise)
 
 
-def _fused(d, dev, wrap, with_scale, want=GRADS, g_image=True, g_T=True):
-    """composite_texture_fused on the device, gradients of `want` only -> image, T, {name: grad}."""
+def _fused(d, dev, wrap, with_scale, want=GRADS, g_image=True, g_T=True, leaves=None):
+    """composite_texture_fused on the device, gradients of `want` only -> image, T, {name: grad}.  leaves: {name: the device
+    tensor to differentiate, as it is (its storage and offset)} in place of a fresh copy of d[name]."""
     t = {k: v.to(dev) for k, v in d.items() if isinstance(v, th.Tensor)}
     names = [k for k in want if with_scale or k != "face_scale"]
-    lv = {k: t[k].clone().requires_grad_(True) for k in names}
+    lv = {k: (leaves[k].detach() if leaves and k in leaves else t[k].clone()).requires_grad_(True) for k in names}
     image, T = FG.composite_texture_fused(Fragments(t["face"], lv.get("bary", t["bary"]), None), t["faces"], lv.get("faces_opacity", t["faces_opacity"]),
                                           lv.get("vert_uvs", t["vert_uvs"]), lv.get("texture", t["texture"]),
                                           lv.get("face_scale", t["face_scale"]) if with_scale else None, uv_faces=t.get("uv_faces"), wrap=wrap)
@@ -124,18 +132,8 @@ def _fused(d, dev, wrap, with_scale, want=GRADS, g_image=True, g_T=True):
     return image.detach(), T.detach(), dict(zip(names, grads))
 
 
-# K, C, texture (Ht, Wt), wrap, face_scale, uv_faces, size: every value of every axis, and both table regimes with both wraps
-CASES = [
-    (1, 1, (1, 1), "clamp", False, False, "shared_keys"),
-    (5, 3, (7, 13), "repeat", True, True, "shared_keys"),
-    (32, 9, (7, 13), "clamp", False, True, "shared_keys"),
-    (32, 1, (1, 1), "repeat", True, True, "table_overflow"),
-    (1, 4, (7, 13), "repeat", False, False, "table_overflow"),
-    (5, 4, (32, 48), "clamp", True, True, "table_overflow"),
-    (5, 9, (32, 48), "repeat", False, True, "table_overflow"),
-    (32, 3, (32, 48), "repeat", True, False, "table_overflow"),
-    (5, 3, (32, 48), "clamp", True, False, "shared_keys"),
-]
+# K, C, texture (Ht, Wt), wrap, face_scale, uv_faces, size (shading_cases)
+CASES = TEXTURE_CASES
 
 
 @pytest.mark.parametrize("K,C,tex,wrap,with_scale,with_uvf,size", CASES,
@@ -172,7 +170,7 @@ def test_only_some_gradients_wanted(hip_device):
     upstream beside it, one with only the image's equals one with a zero upstream of T, and the two add up to the model's
     gradients.  Two evaluations of the same sums: sum_order_tol.  With only T's upstream everything but dL_dfaces_opacity is
     exactly 0."""
-    K, C, tex, size, with_uvf, wrap = 5, 3, (7, 13), "shared_keys", True, "repeat"
+    K, C, tex, size, with_uvf, wrap = TEXTURE_ONLY_SOME
     d = _lists(K, C, tex, size, with_uvf)
     dev = hip_device
     _, _, g_all = _fused(d, dev, wrap, True)
@@ -284,8 +282,8 @@ def test_rendered_tri_lists(hip_device):
 
 def test_graph_capture(hip_device):
     """(e) one forward + backward captured into a HIP graph and replayed: the replayed gradients are the eager ones."""
-    K, C, tex = 5, 9, (32, 48)
-    d = _lists(K, C, tex, "table_overflow", True)
+    K, C, tex, size, with_uvf = TEXTURE_GRAPH
+    d = _lists(K, C, tex, size, with_uvf)
     dev = hip_device
     t = {k: v.to(dev) for k, v in d.items() if isinstance(v, th.Tensor)}
     lv = [t[k].clone().requires_grad_(True) for k in GRADS]
@@ -303,3 +301,182 @@ def test_graph_capture(hip_device):
         e = rel_err(a.cpu().numpy(), b.cpu().numpy())
         print(f"\ngraph replay vs eager dL_d{k}: {e:.2e} (max |eager| {float(b.abs().max()):.3g})")
         assert float(b.abs().max()) > 0 and e <= sum_order_tol(k), (k, e)
+
+
+# ---------------------------------------------------------------------------
+# Every instantiation (shading_cases: the tables below and what each row reaches; tests/test_shading_coverage_cpu.py checks
+# without a GPU that together they reach all 10 with both kinds of load, and that every case here meets check_inputs).
+# ---------------------------------------------------------------------------
+NO_TEX_GRAD = tuple(k for k in GRADS if k != "texture")
+
+
+def check_inputs(d, ref, names=GRADS, signed=True):
+    """What a case's inputs must give before anything is compared: at most 2 % of the used slots emptied near a texel-centre
+    line, a non-zero reference for every compared gradient (an all-empty list cannot pass), and, under a one-signed upstream,
+    opacity and scale gradients that no cancellation made small.  On a texture of one texel every sample is that texel: the UV
+    and barycentric gradients are identically zero in the model (they are still compared), and only the others must be
+    non-zero."""
+    assert d["removed"] <= 0.02, d["removed"]
+    g_r = ref[2]
+    one_texel = d["texture"].shape[0] * d["texture"].shape[1] == 1
+    for k in names:
+        if k in g_r and not (one_texel and k in ("vert_uvs", "bary")):
+            assert float(np.abs(g_r[k]).max()) > 0, k
+    if not signed:
+        assert float(np.abs(g_r["faces_opacity"]).max()) > 1 and float(np.abs(g_r["face_scale"]).max()) > 1
+
+
+def _check(tag, d, ref, got, names=GRADS, signed=True):
+    """image, T and the gradients `names` of `got` (device) against the float64 model `ref`, as test_caller_made_lists does."""
+    check_inputs(d, ref, names, signed)
+    image_r, T_r, g_r, noise, bound = ref
+    image, T, g = got
+    print(f"\n{tag}: {100 * d['removed']:.2f} % of the used slots near a texel-centre line")
+    assert tuple(image.shape) == image_r.shape and tuple(T.shape) == T_r.shape
+    ei, eT = float(np.abs(image.cpu().numpy() - image_r).max()), float(np.abs(T.cpu().numpy() - T_r).max())
+    print(f"  image {ei:.2e} (float32 noise of the model {noise:.2e}, bound {bound:.2e}; max |image| {np.abs(image_r).max():.3g}) T {eT:.2e}")
+    assert ei <= bound and eT <= FWD_TOL
+    assert set(g) == {k for k in names if k in g_r}
+    for k in g:
+        x, r = g[k].cpu().numpy(), g_r[k]
+        assert x.shape == r.shape and x.dtype == np.float32
+        e = rel_err(x, r)
+        print(f"  dL_d{k} {e:.2e} (max |ref| {np.abs(r).max():.3g})")
+        assert e <= GRAD_TOL, (k, e)
+    F = d["faces"].shape[0]
+    empty = ((d["face"] < 0) | (d["face"] >= F))[:, :, None].expand(-1, -1, 2, -1, -1)
+    if bool(empty.any()):  # empty slots: exact zeros in dL/dbary
+        assert float(g["bary"].cpu()[empty].abs().max()) == 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_lists(C, tex):
+    """The merge-level lists of test_composite_fused_gpu._merge_lists (K = 6 on a 32 x 32 view, F = 5: stripes of period 2 .. 32
+    along either axis in slots 0 .. 4, one face over every pixel in slot 5; opacities in (0.05, 0.4); one-signed upstreams), with
+    UVs, a texture and uv_faces from the usual generator; slots near a texel-centre line emptied as everywhere."""
+    B, H, W = MERGE_FRAME
+    Ht, Wt = tex
+    g = th.Generator().manual_seed(177 + C)
+    py, px = th.meshgrid(th.arange(H), th.arange(W), indexing="ij")
+    face = th.empty(B, MERGE_K, H, W, dtype=th.int32)
+    for j in range(5):
+        face[:, j] = th.where(py < 16, (px >> j) & 1, (py >> j) & 1).to(th.int32)
+    face[:, 5] = 3
+    bary = th.rand(B, MERGE_K, 2, H, W, generator=g) * 0.6 - 0.05
+    faces = th.randint(0, MERGE_P, (MERGE_F, 3), generator=g, dtype=th.int32)
+    uv_faces = th.randint(0, MERGE_P, (MERGE_F, 3), generator=g, dtype=th.int32)
+    opacity = 0.05 + 0.35 * th.rand(MERGE_F, generator=g)
+    assert bool(((opacity > 0.05) & (opacity < 0.4)).all())
+    uvs = th.rand(MERGE_P, 2, generator=g) * 3 - 1
+    texture = th.randn(Ht, Wt, C, generator=g)
+    scale = th.rand(B, MERGE_F, generator=g) + 0.5
+    g_image = th.rand(B, C, H, W, generator=g) + 0.5
+    g_T = th.rand(B, 1, H, W, generator=g) + 0.5
+    face, share = _off_the_lines(face, bary, uv_faces, uvs, Ht, Wt)
+    return dict(face=face, bary=bary, faces=faces, uv_faces=uv_faces, faces_opacity=opacity, vert_uvs=uvs, texture=texture,
+                face_scale=scale, g_image=g_image, g_T=g_T, removed=share)
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_reference(C, tex, wrap):
+    return _reference_of(_merge_lists(C, tex), wrap, True)
+
+
+def new_cases():
+    """(tag, lists, float64 reference, compared gradients, one-signed upstream) of every case below: what check_inputs must
+    hold for."""
+    for K, C, tex, wrap, with_scale, with_uvf, size in TEXTURE_MATRIX:
+        yield (f"matrix K{K} C{C} {tex} {wrap} {size}", _lists(K, C, tex, size, with_uvf, NEW_FRAME),
+               _reference(K, C, tex, size, with_uvf, wrap, with_scale, NEW_FRAME), GRADS, True)
+    for K, C, tex, wrap, size in TEXTURE_NO_TEX_GRAD:
+        yield (f"no texture gradient K{K} C{C} {tex} {wrap} {size}", _lists(K, C, tex, size, True, NEW_FRAME),
+               _reference(K, C, tex, size, True, wrap, True, NEW_FRAME), NO_TEX_GRAD, True)
+    for K, C, tex, wrap in TEXTURE_MISALIGNED:
+        yield (f"misaligned K{K} C{C} {tex} {wrap}", _lists(K, C, tex, "table_overflow", True, NEW_FRAME),
+               _reference(K, C, tex, "table_overflow", True, wrap, True, NEW_FRAME), GRADS, True)
+    C, tex, wrap = TEXTURE_MERGE
+    yield "merge levels", _merge_lists(C, tex), _merge_reference(C, tex, wrap), GRADS, False
+    tex, wrap = TEXTURE_EDGE_FRAME
+    for frame in EDGE_FRAMES:
+        yield (f"frame {frame}", _lists(EDGE_FRAME_K, EDGE_FRAME_C, tex, "shared_keys", True, frame),
+               _reference(EDGE_FRAME_K, EDGE_FRAME_C, tex, "shared_keys", True, wrap, True, frame), GRADS, True)
+
+
+def _id(c):
+    return "-".join(f"{x[0]}x{x[1]}" if isinstance(x, tuple) else (f"K{x}" if i == 0 else (f"C{x}" if i == 1 else str(x))) for i, x in enumerate(c))
+
+
+@pytest.mark.parametrize("K,C,tex,wrap,with_scale,with_uvf,size", TEXTURE_MATRIX,
+                         ids=[f"K{c[0]}-C{c[1]}-{c[2][0]}x{c[2][1]}-{c[3]}-{'scale' if c[4] else 'no_scale'}-{'uvf' if c[5] else 'faces'}-{c[6]}" for c in TEXTURE_MATRIX])
+def test_instantiation_matrix(hip_device, K, C, tex, wrap, with_scale, with_uvf, size):
+    """(f) the backward's KMAX = 16 kernels (1024 texel cells beside 32 KB of T_k and e_k), K == KMAX at 4, 8, 16 and 32, the
+    first K of the next instantiation (9, 17), NCH = 8 with float4 loads, two scalar chunks (C = 5) and TEX_MAX_C, where the
+    texel key t * nch + ch has its largest multiplier: image, T and all five gradients against the float64 model, on a 17 x 33
+    view.
+    Measured on the MI355X over the 7 cases: image <= 6.3e-6 (the model's float32 noise up to 9.0e-6, bound up to 3.6e-5; at most
+    0.32 of a case's bound), T <= 1.8e-7; rel_err of the gradients <= 7.1e-6 (faces_opacity), 4.5e-6 (vert_uvs), 2.6e-6
+    (texture), 6.1e-6 (face_scale), 3.8e-6 (bary); at most 0.47 % of the used slots emptied near a texel-centre line."""
+    d = _lists(K, C, tex, size, with_uvf, NEW_FRAME)
+    _check(f"K {K} C {C} tex {tex} {wrap} {size} scale {with_scale} uv_faces {with_uvf}", d,
+           _reference(K, C, tex, size, with_uvf, wrap, with_scale, NEW_FRAME), _fused(d, hip_device, wrap, with_scale))
+
+
+@pytest.mark.parametrize("K,C,tex,wrap,size", TEXTURE_NO_TEX_GRAD, ids=[_id(c) for c in TEXTURE_NO_TEX_GRAD])
+def test_texture_gradient_not_wanted(hip_device, K, C, tex, wrap, size):
+    """(g) the TEX = false instantiations (no texel table in LDS) at every KMAX, scalar and float4: the other four gradients
+    against the float64 model.
+    Measured on the MI355X over the 7 cases: image <= 5.9e-6 (bound up to 3.6e-5), T <= 1.5e-7; rel_err of the gradients <= 7.8e-6
+    (faces_opacity), 5.9e-6 (vert_uvs), 7.5e-6 (face_scale), 4.8e-6 (bary); at most 0.52 % of the used slots emptied."""
+    d = _lists(K, C, tex, size, True, NEW_FRAME)
+    got = _fused(d, hip_device, wrap, True, want=NO_TEX_GRAD)
+    assert list(got[2]) == list(NO_TEX_GRAD)
+    _check(f"no texture gradient: K {K} C {C} tex {tex} {wrap} {size}", d, _reference(K, C, tex, size, True, wrap, True, NEW_FRAME), got,
+           names=NO_TEX_GRAD)
+
+
+@pytest.mark.parametrize("K,C,tex,wrap", TEXTURE_MISALIGNED, ids=[_id(c) for c in TEXTURE_MISALIGNED])
+def test_misaligned_base(hip_device, K, C, tex, wrap):
+    """(h) C % 4 == 0 with the texture one float into a larger buffer: the binding's .contiguous() keeps that pointer, so the
+    scalar loads run (vec = 0) where the same values in a buffer of their own take the float4 loads.  Both against the float64
+    model, and against each other (forward FWD_TOL; gradients: the same sums in another order, sum_order_tol).
+    Measured on the MI355X over the 3 cases, either call against the model: image <= 3.5e-6 (bound up to 1.4e-5), T <= 1.8e-7,
+    gradients <= 4.7e-6 (face_scale); misaligned against aligned: the forward bit-equal, dL_dfaces_opacity 3.5e-8, dL_dvert_uvs
+    1.2e-7, dL_dtexture 7.6e-8, dL_dface_scale 3.0e-8, dL_dbary 0."""
+    dev, size = hip_device, "table_overflow"
+    d = _lists(K, C, tex, size, True, NEW_FRAME)
+    ref = _reference(K, C, tex, size, True, wrap, True, NEW_FRAME)
+    off, own = one_float_in(d["texture"].to(dev)), d["texture"].to(dev).clone()
+    assert off.is_contiguous() and off.data_ptr() % 16 == 4 and own.data_ptr() % 16 == 0
+    assert bool((off == own).all())
+    got = _fused(d, dev, wrap, True, leaves={"texture": off})
+    _check(f"K {K} C {C} tex {tex} {wrap} misaligned", d, ref, got)
+    alg = _fused(d, dev, wrap, True, leaves={"texture": own})
+    _check(f"K {K} C {C} tex {tex} {wrap} aligned", d, ref, alg)
+    ei, eT = float((got[0] - alg[0]).abs().max()), float((got[1] - alg[1]).abs().max())
+    print(f"misaligned vs aligned: image {ei:.2e} T {eT:.2e}; forward bit-equal: {bool(th.equal(got[0], alg[0]) and th.equal(got[1], alg[1]))}")
+    assert ei <= FWD_TOL and eT <= FWD_TOL
+    for k in GRADS:
+        e = rel_err(got[2][k].cpu().numpy(), alg[2][k].cpu().numpy())
+        print(f"  dL_d{k} misaligned vs aligned {e:.2e}")
+        assert e <= sum_order_tol(k), (k, e)
+
+
+def test_merge_levels(hip_device):
+    """(i) shade_merge's four levels one at a time, and one face over a whole tile (_merge_lists), against the float64 model;
+    the upstreams are one-signed, so the opacity and scale gradients (max |ref| > 1, asserted) cannot agree by cancellation.
+    Measured on the MI355X: image 1.5e-6 (bound 1e-5), T 1.1e-7; dL_dfaces_opacity 6.1e-8 (max |ref| 2.4e3), dL_dvert_uvs 2.5e-7,
+    dL_dtexture 2.5e-7, dL_dface_scale 3.4e-7 (max |ref| 167), dL_dbary 2.3e-6; 0.65 % of the used slots emptied."""
+    C, tex, wrap = TEXTURE_MERGE
+    d = _merge_lists(C, tex)
+    _check(f"merge levels K {MERGE_K} C {C} tex {tex} {wrap}", d, _merge_reference(C, tex, wrap), _fused(d, hip_device, wrap, True), signed=False)
+
+
+@pytest.mark.parametrize("frame", EDGE_FRAMES, ids=["x".join(map(str, f)) for f in EDGE_FRAMES])
+def test_frames(hip_device, frame):
+    """(j) a view of whole tiles only, and views of one pixel: one live lane per workgroup, the other 255 through every merge
+    and barrier with key -1.
+    Measured on the MI355X over both: image <= 5.0e-6 (bound 1.7e-5), T <= 5.5e-8; gradients <= 5.4e-6 (face_scale)."""
+    K, C, size = EDGE_FRAME_K, EDGE_FRAME_C, "shared_keys"
+    tex, wrap = TEXTURE_EDGE_FRAME
+    d = _lists(K, C, tex, size, True, frame)
+    _check(f"frame {frame} K {K} C {C}", d, _reference(K, C, tex, size, True, wrap, True, frame), _fused(d, hip_device, wrap, True))
