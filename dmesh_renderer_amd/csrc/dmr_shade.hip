@@ -8,22 +8,15 @@
 // A slot whose face id lies outside [0, F) is empty wherever it sits; the lists' count is not read.
 //
 // None of the arithmetic here decides an index or a branch another kernel depends on: it may contract to FMA.
-#include <string>
-
-#include "dmr_kernels.hpp"
-#include "dmr_shade_table.hpp"
+#include "dmr_shade_common.hpp"
 #include "../../include/dmesh_renderer_amd_shade.h"
 
 namespace dmr {
-
-int api_fail(const char* m);  // dmr_api.hip: sets dmr_last_error()'s message, returns 1
-
 namespace {
 
 #pragma clang fp contract(fast)
 
 constexpr int SHADE_MAX_C = 256;
-// The backward's per-tile table (STAB slots) and the merge of lanes of equal key: dmr_shade_table.hpp.
 
 struct ShadeParams {
     int B, K, H, W, P, F, C, gx, gy;
@@ -106,7 +99,7 @@ k_composite_fragments(ShadeParams p, float* __restrict__ image, float* __restric
 // ---------------------------------------------------------------------------
 // Backward.
 //
-// Lanes that hold the same key (a face) merge before they go to the table (shade_merge, stab_find: dmr_shade_table.hpp).
+// Lanes that hold the same key (a face) merge before they go to the table (shade_merge, stab_find: dmr_shade_common.hpp).
 // ---------------------------------------------------------------------------
 
 // T_k and e_k = a_k . g of every slot of the tile's pixels (what the opacity recurrence needs from the front-to-back walk),
@@ -263,32 +256,20 @@ k_composite_fragments_backward(ShadeParams p, const float* __restrict__ gimg, co
 int shade_params(const char* name, int B, int K, int H, int W, int P, int F, int C, const int32_t* face, const float* bary,
                  const int32_t* faces, const float* faces_opacity, const float* vert_attrs, const float* face_scale, ShadeParams& p) {
     const std::string n = std::string(name) + ": ";
-    if (B <= 0 || H <= 0 || W <= 0 || P < 0 || F < 0) return api_fail((n + "bad dimensions").c_str());
-    if (K < 1 || K > FRAG_MAX_K) return api_fail((n + "K must be in 1.." + std::to_string(FRAG_MAX_K) + ", got " + std::to_string(K)).c_str());
-    if (C < 1 || C > SHADE_MAX_C) return api_fail((n + "C must be in 1.." + std::to_string(SHADE_MAX_C) + ", got " + std::to_string(C)).c_str());
-    if (!face || !bary) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && (!faces || !faces_opacity)) return api_fail((n + "null faces / faces_opacity").c_str());
-    if (F > 0 && P > 0 && !vert_attrs) return api_fail((n + "null vert_attrs").c_str());
-    const int64_t gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    if ((int64_t)B * gx * gy >= (int64_t)1 << 31 || (int64_t)B * F >= (int64_t)1 << 31 || (int64_t)P >= (int64_t)1 << 31)
-        return api_fail((n + "problem too large").c_str());
-    p.B = B; p.K = K; p.H = H; p.W = W; p.P = P; p.F = F; p.C = C; p.gx = (int)gx; p.gy = (int)gy;
-    p.vec = (C % 4 == 0 && (reinterpret_cast<uintptr_t>(vert_attrs) & 15u) == 0u) ? 1 : 0;
-    p.face = face; p.bary = bary; p.faces = faces; p.opacity = faces_opacity; p.attrs = vert_attrs; p.scale = face_scale;
-    return 0;
-}
-
-int launched(const char* name) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail((std::string(name) + ": " + hipGetErrorString(e)).c_str());
+    if (shade_check_sizes(n, B, K, H, W, P, F, C, SHADE_MAX_C)) return 1;
+    const char* missing = (F > 0 && P > 0 && !vert_attrs) ? "vert_attrs" : nullptr;
+    if (shade_check_lists(n, "faces", B, K, H, W, F, face, bary, faces, faces_opacity, face_scale, missing, p)) return 1;
+    p.P = P; p.C = C;
+    p.vec = shade_vec(C, vert_attrs);
+    p.faces = faces; p.attrs = vert_attrs;
     return 0;
 }
 
 template <int KMAX>
-void launch_backward(const ShadeParams& p, dim3 grid, hipStream_t st, const float* gi, const float* gt, float* dop, float* dattr,
+void launch_backward(const ShadeParams& p, hipStream_t st, const float* gi, const float* gt, float* dop, float* dattr,
                      float* dsc, float* dbary) {
-    if (p.C <= 4) k_composite_fragments_backward<KMAX, 4><<<grid, dim3(256), 0, st>>>(p, gi, gt, dop, dattr, dsc, dbary);
-    else k_composite_fragments_backward<KMAX, 8><<<grid, dim3(256), 0, st>>>(p, gi, gt, dop, dattr, dsc, dbary);
+    if (p.C <= 4) k_composite_fragments_backward<KMAX, 4><<<dim3((unsigned)(p.B * p.gx * p.gy)), dim3(256), 0, st>>>(p, gi, gt, dop, dattr, dsc, dbary);
+    else k_composite_fragments_backward<KMAX, 8><<<dim3((unsigned)(p.B * p.gx * p.gy)), dim3(256), 0, st>>>(p, gi, gt, dop, dattr, dsc, dbary);
 }
 
 }  // namespace
@@ -319,22 +300,13 @@ int dmr_composite_fragments_backward(int B, int K, int H, int W, int P, int F, i
     const char* name = "dmr_composite_fragments_backward";
     ShadeParams p;
     if (shade_params(name, B, K, H, W, P, F, C, face, bary, faces, faces_opacity, vert_attrs, face_scale, p)) return 1;
-    if (dL_dface_scale && !face_scale) return api_fail("dmr_composite_fragments_backward: dL_dface_scale without face_scale");
-    if (!dL_dfaces_opacity && !dL_dvert_attrs && !dL_dface_scale && !dL_dbary) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const auto zero = [&](float* q, int64_t n) { return (q && n > 0) ? hipMemsetAsync(q, 0, (size_t)n * sizeof(float), st) : hipSuccess; };
-    hipError_t e = zero(dL_dfaces_opacity, F);
-    if (e == hipSuccess) e = zero(dL_dvert_attrs, (int64_t)P * C);
-    if (e == hipSuccess) e = zero(dL_dface_scale, (int64_t)B * F);
-    if (e == hipSuccess && !grad_image) e = zero(dL_dbary, (int64_t)B * K * 2 * H * W);  // (else the kernel stores every slot)
-    if (e != hipSuccess) return api_fail((std::string(name) + ": hipMemsetAsync: " + hipGetErrorString(e)).c_str());
-    if (!grad_image && !grad_T) return 0;  // nothing arrives: the zeros are the gradients
-    if (!grad_image && !dL_dfaces_opacity) return 0;  // only T's upstream, which reaches the opacities alone
-    const dim3 grid((unsigned)(B * p.gx * p.gy));
-    if (K <= 4) launch_backward<4>(p, grid, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);
-    else if (K <= 8) launch_backward<8>(p, grid, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);
-    else if (K <= 16) launch_backward<16>(p, grid, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);
-    else launch_backward<32>(p, grid, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);
+    const int r = shade_backward_prologue(name, p, grad_image, grad_T, dL_dfaces_opacity, dL_dface_scale, dL_dbary,
+                                          {{dL_dvert_attrs, (int64_t)P * C}}, st);
+    if (r != SHADE_LAUNCH) return r;
+    with_kmax(K, [&](auto kmax) {
+        launch_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);
+    });
     return launched(name);
 }
 

@@ -13,17 +13,11 @@
 // its texel from there.  A NaN, an infinity or a UV of 1e30 addresses the texture in bounds (what it computes is unspecified).
 //
 // None of the arithmetic here decides an index or a branch another kernel depends on: it may contract to FMA.
-#include <string>
-
-#include "dmr_kernels.hpp"
-#include "dmr_shade_table.hpp"
+#include "dmr_shade_common.hpp"
 #include "dmr_texture_wrap.hpp"
 #include "../../include/dmesh_renderer_amd_texture.h"
 
 namespace dmr {
-
-int api_fail(const char* m);  // dmr_api.hip: sets dmr_last_error()'s message, returns 1
-
 namespace {
 
 #pragma clang fp contract(fast)
@@ -31,7 +25,7 @@ namespace {
 constexpr int TEX_MAX_C = 32;
 constexpr int TEX_CHUNKS = TEX_MAX_C / 4;
 // The backward's table of texel gradients: keyed by texel x channel chunk, four f64 sums per cell; the scheme and the probe
-// bound of dmr_shade_table.hpp at a size of its own (a tile's pixels share a few hundred texels per layer), as large as
+// bound of dmr_shade_common.hpp at a size of its own (a tile's pixels share a few hundred texels per layer), as large as
 // leaves two workgroups per CU their LDS beside the KMAX slots of T_k and e_k (160 KB per CU): 1600 cells at KMAX 4, 1408 at 8,
 // 1024 above.
 template <int KMAX> constexpr int TTAB = KMAX <= 4 ? 1600 : (KMAX <= 8 ? 1408 : 1024);
@@ -142,8 +136,8 @@ k_composite_texture(TexParams p, float* __restrict__ image, float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// Backward.  The structure of k_composite_fragments_backward (dmr_shade.hip), with the helpers it shares through
-// dmr_shade_table.hpp.
+// Backward.  The structure of k_composite_fragments_backward (dmr_shade.hip), with the merge and the table it shares through
+// dmr_shade_common.hpp.  Walk 0, the last walk and the forward's slot head are copies of that unit's text on purpose: DESIGN.md 5c.
 //
 // LDS: T_k and e_k = c_k . g of every slot of the tile's pixels; the table of UV rows (STAB cells of two f64 sums, re-keyed
 // by face for the opacity walk, whose two sums it then holds); and, only in the instantiation that writes dL/dtexture
@@ -338,39 +332,27 @@ int tex_params(const char* name, int B, int K, int H, int W, int Pu, int F, int 
                const float* bary, const int32_t* uv_faces, const float* faces_opacity, const float* vert_uvs, const float* texture,
                const float* face_scale, TexParams& p) {
     const std::string n = std::string(name) + ": ";
-    if (B <= 0 || H <= 0 || W <= 0 || Pu < 0 || F < 0) return api_fail((n + "bad dimensions").c_str());
-    if (K < 1 || K > FRAG_MAX_K) return api_fail((n + "K must be in 1.." + std::to_string(FRAG_MAX_K) + ", got " + std::to_string(K)).c_str());
-    if (C < 1 || C > TEX_MAX_C) return api_fail((n + "C must be in 1.." + std::to_string(TEX_MAX_C) + ", got " + std::to_string(C)).c_str());
+    if (shade_check_sizes(n, B, K, H, W, Pu, F, C, TEX_MAX_C)) return 1;
     if (Ht < 1 || Wt < 1) return api_fail((n + "the texture must have at least one texel").c_str());
     if (wrap != 0 && wrap != 1) return api_fail((n + "wrap must be 0 (clamp) or 1 (repeat), got " + std::to_string(wrap)).c_str());
     const int64_t nch = (C + 3) / 4, texels = (int64_t)Ht * Wt;
     if (texels >= (int64_t)0xffffffff || texels * nch >= (int64_t)0xffffffff)
         return api_fail((n + "texture too large: Ht * Wt * ceil(C / 4) must be below 2^32 - 1").c_str());
-    if (!face || !bary) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && (!uv_faces || !faces_opacity)) return api_fail((n + "null uv_faces / faces_opacity").c_str());
-    if (F > 0 && Pu > 0 && !vert_uvs) return api_fail((n + "null vert_uvs").c_str());
-    if (!texture) return api_fail((n + "null texture").c_str());
-    const int64_t gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    if ((int64_t)B * gx * gy >= (int64_t)1 << 31 || (int64_t)B * F >= (int64_t)1 << 31) return api_fail((n + "problem too large").c_str());
-    p.B = B; p.K = K; p.H = H; p.W = W; p.Pu = Pu; p.F = F; p.C = C; p.Ht = Ht; p.Wt = Wt; p.wrap = wrap; p.gx = (int)gx; p.gy = (int)gy;
+    const char* missing = (F > 0 && Pu > 0 && !vert_uvs) ? "vert_uvs" : (!texture ? "texture" : nullptr);
+    if (shade_check_lists(n, "uv_faces", B, K, H, W, F, face, bary, uv_faces, faces_opacity, face_scale, missing, p)) return 1;
+    p.Pu = Pu; p.C = C; p.Ht = Ht; p.Wt = Wt; p.wrap = wrap;
     p.nch = (int)nch;
-    p.vec = (C % 4 == 0 && (reinterpret_cast<uintptr_t>(texture) & 15u) == 0u) ? 1 : 0;
-    p.face = face; p.bary = bary; p.uvf = uv_faces; p.opacity = faces_opacity; p.uvs = vert_uvs; p.tex = texture; p.scale = face_scale;
-    return 0;
-}
-
-int launched(const char* name) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return api_fail((std::string(name) + ": " + hipGetErrorString(e)).c_str());
+    p.vec = shade_vec(C, texture);
+    p.uvf = uv_faces; p.uvs = vert_uvs; p.tex = texture;
     return 0;
 }
 
 template <int KMAX>
-void launch_backward(const TexParams& p, dim3 grid, hipStream_t st, const float* gi, const float* gt, float* dop, float* duv, float* dtex,
+void launch_backward(const TexParams& p, hipStream_t st, const float* gi, const float* gt, float* dop, float* duv, float* dtex,
                      float* dsc, float* dbary) {
     // (without an image upstream nothing reaches the texture: its zeros are its gradient, and the table is not needed)
-    if (dtex && gi) k_composite_texture_backward<KMAX, true><<<grid, dim3(256), 0, st>>>(p, gi, gt, dop, duv, dtex, dsc, dbary);
-    else k_composite_texture_backward<KMAX, false><<<grid, dim3(256), 0, st>>>(p, gi, gt, dop, duv, nullptr, dsc, dbary);
+    if (dtex && gi) k_composite_texture_backward<KMAX, true><<<dim3((unsigned)(p.B * p.gx * p.gy)), dim3(256), 0, st>>>(p, gi, gt, dop, duv, dtex, dsc, dbary);
+    else k_composite_texture_backward<KMAX, false><<<dim3((unsigned)(p.B * p.gx * p.gy)), dim3(256), 0, st>>>(p, gi, gt, dop, duv, nullptr, dsc, dbary);
 }
 
 }  // namespace
@@ -402,24 +384,13 @@ int dmr_composite_texture_backward(int B, int K, int H, int W, int Pu, int F, in
     const char* name = "dmr_composite_texture_backward";
     TexParams p;
     if (tex_params(name, B, K, H, W, Pu, F, C, Ht, Wt, wrap, face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, p)) return 1;
-    if (dL_dface_scale && !face_scale) return api_fail("dmr_composite_texture_backward: dL_dface_scale without face_scale");
-    if (!dL_dfaces_opacity && !dL_dvert_uvs && !dL_dtexture && !dL_dface_scale && !dL_dbary) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const auto zero = [&](float* q, int64_t n) { return (q && n > 0) ? hipMemsetAsync(q, 0, (size_t)n * sizeof(float), st) : hipSuccess; };
-    hipError_t e = zero(dL_dfaces_opacity, F);
-    if (e == hipSuccess) e = zero(dL_dvert_uvs, (int64_t)Pu * 2);
-    if (e == hipSuccess) e = zero(dL_dtexture, (int64_t)Ht * Wt * C);
-    if (e == hipSuccess) e = zero(dL_dface_scale, (int64_t)B * F);
-    if (e == hipSuccess && !grad_image) e = zero(dL_dbary, (int64_t)B * K * 2 * H * W);  // (else the kernel stores every slot)
-    if (e != hipSuccess) return api_fail((std::string(name) + ": hipMemsetAsync: " + hipGetErrorString(e)).c_str());
-    if (!grad_image && !grad_T) return 0;  // nothing arrives: the zeros are the gradients
-    if (!grad_image && !dL_dfaces_opacity) return 0;  // only T's upstream, which reaches the opacities alone
-    const dim3 grid((unsigned)(B * p.gx * p.gy));
-    const auto go = [&](auto fn) { fn(p, grid, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_uvs, dL_dtexture, dL_dface_scale, dL_dbary); };
-    if (K <= 4) go(launch_backward<4>);
-    else if (K <= 8) go(launch_backward<8>);
-    else if (K <= 16) go(launch_backward<16>);
-    else go(launch_backward<32>);
+    const int r = shade_backward_prologue(name, p, grad_image, grad_T, dL_dfaces_opacity, dL_dface_scale, dL_dbary,
+                                          {{dL_dvert_uvs, (int64_t)Pu * 2}, {dL_dtexture, (int64_t)Ht * Wt * C}}, st);
+    if (r != SHADE_LAUNCH) return r;
+    with_kmax(K, [&](auto kmax) {
+        launch_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_uvs, dL_dtexture, dL_dface_scale, dL_dbary);
+    });
     return launched(name);
 }
 

@@ -602,40 +602,90 @@ at::Tensor export_item(const std::string& name, const py::sequence& call_args, b
     return out.narrow(0, 0, n).view(torch::python::detail::py_object_to_dtype(dtype));
 }
 
-// ---- composite_fragments / composite_fragments_backward (dmesh_renderer_amd_shade.h): fragments.composite_fused ----------------
-// The tensors both calls start with, checked and made contiguous; sizes as the C calls take them.
-struct ShadeArgs {
-    at::Tensor face, bary, faces, opacity, attrs, scale;  // scale: undefined = none
-    int B, K, H, W, P, F, C;
-    c10::Device dev;
+// ---- shading over fragment lists: composite_fragments* (dmesh_renderer_amd_shade.h, fragments.composite_fused) and
+// composite_texture* (dmesh_renderer_amd_texture.h, fragments.composite_texture_fused) --------------------------------------------
+// What every shading call starts with -- the lists, the unit's [F,3] corner table (faces / uv_faces), the opacities, the
+// optional per-face scale -- checked and made contiguous.  A unit extends it with its own tensors and calls the four steps
+// below in this order, each of its own checks at its place between them: the first check that fails decides the message.
+struct ListArgs {
+    at::Tensor face, bary, corners, opacity, scale;  // scale: undefined = none
+    int64_t B = 0, K = 0, H = 0, W = 0, F = 0;
+    c10::Device dev{c10::kCPU};
+    const char *call, *corner_name;  // "composite_fragments" / "composite_texture"; what the unit calls `corners`
     void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
     const float* scale_ptr() const { return scale.defined() ? mptr<const float>(scale) : nullptr; }
 };
+struct OwnTensor { In in; const char* name; at::Tensor& out; };  // one of a unit's own f32 tensors, and where its contiguous form goes
+
+// 1: the device, and the dimensions of the lists, the corner table and the opacities
+void list_dims(ListArgs& a, const char* call, const char* corner_name, In face, In bary, In corners, In faces_opacity) {
+    a.call = call; a.corner_name = corner_name;
+    a.dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+    if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
+        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
+    if (corners.dim() != 2 || corners.size(1) != 3) err(std::string(a.corner_name) + " must have dimensions (num_faces, 3)");
+    a.F = corners.size(0);
+    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != a.F) err("faces_opacity must have dimensions (num_faces,)");
+    a.face = face; a.bary = bary; a.corners = corners; a.opacity = faces_opacity;
+}
+void list_k(const ListArgs& a) { if (a.K < 1 || a.K > 32) err(std::string(a.call) + ": K must be in 1..32, got " + std::to_string(a.K)); }
+void list_not_empty(const ListArgs& a) { if (a.B < 1 || a.H < 1 || a.W < 1) err(std::string(a.call) + ": empty fragment lists"); }
+// 4: face_scale's dimensions, one device for every tensor, then dtypes: the tensors of `a` and the unit's `own` made contiguous
+void list_finish(ListArgs& a, const std::optional<at::Tensor>& face_scale, std::initializer_list<OwnTensor> own) {
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
+        err("face_scale must have dimensions (B, num_faces)");
+    const auto same = [&a](In t, const char* name) {
+        if (t.device() != a.dev) err(std::string(name) + " must be on the device of pix_to_face");
+    };
+    same(a.bary, "bary"); same(a.corners, a.corner_name); same(a.opacity, "faces_opacity");
+    for (const OwnTensor& o : own) same(o.in, o.name);
+    if (face_scale) same(*face_scale, "face_scale");
+    a.face = i32(a.face, "pix_to_face"); a.bary = f32(a.bary, "bary"); a.corners = i32(a.corners, a.corner_name);
+    a.opacity = f32(a.opacity, "faces_opacity");
+    for (const OwnTensor& o : own) o.out = f32(o.in, o.name);
+    if (face_scale) a.scale = f32(*face_scale, "face_scale");
+}
+
+// The two upstreams of a backward call, grad_image [B,C,H,W] / grad_T [B,1,H,W], checked and contiguous; undefined: None = zero.
+std::pair<at::Tensor, at::Tensor> upstreams(const ListArgs& a, int64_t C, const std::optional<at::Tensor>& grad_image,
+                                            const std::optional<at::Tensor>& grad_T) {
+    at::Tensor gi, gt;
+    if (grad_image) {
+        if (grad_image->dim() != 4 || grad_image->size(0) != a.B || grad_image->size(1) != C || grad_image->size(2) != a.H ||
+            grad_image->size(3) != a.W || grad_image->device() != a.dev)
+            err("grad_image must have dimensions (B, C, H, W) on the device of pix_to_face");
+        gi = f32(*grad_image, "grad_image");
+    }
+    if (grad_T) {
+        if (grad_T->numel() != (int64_t)a.B * a.H * a.W || grad_T->device() != a.dev) err("grad_T must have dimensions (B, 1, H, W) on the device of pix_to_face");
+        gt = f32(*grad_T, "grad_T");
+    }
+    return {gi, gt};
+}
+
+// an optional tensor as the C calls take it (null = none / not wanted) and as Python gets it back; a gradient output if asked for
+const float* in_ptr(const at::Tensor& t) { return t.defined() ? mptr<const float>(t) : nullptr; }
+float* out_ptr(at::Tensor& t) { return t.defined() ? mptr<float>(t) : nullptr; }
+py::object or_none(const at::Tensor& t) { return t.defined() ? py::cast(t) : py::none(); }
+at::Tensor grad_if(bool need, at::IntArrayRef shape, c10::Device dev) { return need ? at::empty(shape, f32_on(dev)) : at::Tensor(); }
+
+// -- composite_fragments: per-vertex attributes
+struct ShadeArgs : ListArgs { at::Tensor attrs; int64_t P = 0, C = 0; };
 
 ShadeArgs shade_args(In face, In bary, In faces, In faces_opacity, In vert_attrs, const std::optional<at::Tensor>& face_scale) {
     if (!g_abi.composite_fragments)
         err(g_abi.path + " does not export dmr_composite_fragments: rebuild it (python -m dmesh_renderer_amd.build)");
-    const c10::Device dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    const int64_t B = face.size(0), K = face.size(1), H = face.size(2), W = face.size(3);
-    if (bary.dim() != 5 || bary.size(0) != B || bary.size(1) != K || bary.size(2) != 2 || bary.size(3) != H || bary.size(4) != W)
-        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
-    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
-    const int64_t F = faces.size(0);
-    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != F) err("faces_opacity must have dimensions (num_faces,)");
+    ShadeArgs a;
+    list_dims(a, "composite_fragments", "faces", face, bary, faces, faces_opacity);
     if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
-    const int64_t P = vert_attrs.size(0), C = vert_attrs.size(1);
-    if (K < 1 || K > 32) err("composite_fragments: K must be in 1..32, got " + std::to_string(K));
-    if (C < 1 || C > 256) err("composite_fragments: C must be in 1..256, got " + std::to_string(C));
-    if (B < 1 || H < 1 || W < 1) err("composite_fragments: empty fragment lists");
-    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != B || face_scale->size(1) != F))
-        err("face_scale must have dimensions (B, num_faces)");
-    const std::pair<const at::Tensor*, const char*> same[5] = {{&bary, "bary"}, {&faces, "faces"}, {&faces_opacity, "faces_opacity"},
-                                                               {&vert_attrs, "vert_attrs"}, {face_scale ? &*face_scale : nullptr, "face_scale"}};
-    for (auto& t : same)
-        if (t.first && t.first->device() != dev) err(std::string(t.second) + " must be on the device of pix_to_face");
-    return {i32(face, "pix_to_face"), f32(bary, "bary"), i32(faces, "faces"), f32(faces_opacity, "faces_opacity"), f32(vert_attrs, "vert_attrs"),
-            face_scale ? f32(*face_scale, "face_scale") : at::Tensor(), (int)B, (int)K, (int)H, (int)W, (int)P, (int)F, (int)C, dev};
+    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1);
+    list_k(a);
+    if (a.C < 1 || a.C > 256) err("composite_fragments: C must be in 1..256, got " + std::to_string(a.C));
+    list_not_empty(a);
+    list_finish(a, face_scale, {{vert_attrs, "vert_attrs", a.attrs}});
+    return a;
 }
 
 // -> (image [B,C,H,W], T [B,1,H,W])
@@ -645,7 +695,7 @@ std::tuple<at::Tensor, at::Tensor> composite_fragments(In face, In bary, In face
     c10::DeviceGuard guard(a.dev);
     at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
     if (g_abi.composite_fragments(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
-                                  mptr<const int32_t>(a.faces), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
+                                  mptr<const int32_t>(a.corners), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
                                   mptr<float>(image), mptr<float>(T), a.stream()))
         raise_lib();
     return {image, T};
@@ -659,71 +709,35 @@ py::tuple composite_fragments_backward(In face, In bary, In faces, In faces_opac
     const ShadeArgs a = shade_args(face, bary, faces, faces_opacity, vert_attrs, face_scale);
     c10::DeviceGuard guard(a.dev);
     if (need[2] && !face_scale) err("composite_fragments_backward: the gradient of face_scale without face_scale");
-    at::Tensor gi, gt;
-    if (grad_image) {
-        if (grad_image->dim() != 4 || grad_image->size(0) != a.B || grad_image->size(1) != a.C || grad_image->size(2) != a.H ||
-            grad_image->size(3) != a.W || grad_image->device() != a.dev)
-            err("grad_image must have dimensions (B, C, H, W) on the device of pix_to_face");
-        gi = f32(*grad_image, "grad_image");
-    }
-    if (grad_T) {
-        if (grad_T->numel() != (int64_t)a.B * a.H * a.W || grad_T->device() != a.dev) err("grad_T must have dimensions (B, 1, H, W) on the device of pix_to_face");
-        gt = f32(*grad_T, "grad_T");
-    }
-    at::Tensor d_op, d_attrs, d_scale, d_bary;
-    if (need[0]) d_op = at::empty({a.F}, f32_on(a.dev));
-    if (need[1]) d_attrs = at::empty({a.P, a.C}, f32_on(a.dev));
-    if (need[2]) d_scale = at::empty({a.B, a.F}, f32_on(a.dev));
-    if (need[3]) d_bary = at::empty({a.B, a.K, 2, a.H, a.W}, f32_on(a.dev));
-    const auto out = [](at::Tensor& t) { return t.defined() ? mptr<float>(t) : nullptr; };
+    const auto [gi, gt] = upstreams(a, a.C, grad_image, grad_T);
+    at::Tensor d_op = grad_if(need[0], {a.F}, a.dev), d_attrs = grad_if(need[1], {a.P, a.C}, a.dev);
+    at::Tensor d_scale = grad_if(need[2], {a.B, a.F}, a.dev), d_bary = grad_if(need[3], {a.B, a.K, 2, a.H, a.W}, a.dev);
     if (g_abi.composite_fragments_backward(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
-                                           mptr<const int32_t>(a.faces), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
-                                           gi.defined() ? mptr<const float>(gi) : nullptr, gt.defined() ? mptr<const float>(gt) : nullptr,
-                                           out(d_op), out(d_attrs), out(d_scale), out(d_bary), a.stream()))
+                                           mptr<const int32_t>(a.corners), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
+                                           in_ptr(gi), in_ptr(gt), out_ptr(d_op), out_ptr(d_attrs), out_ptr(d_scale), out_ptr(d_bary), a.stream()))
         raise_lib();
-    const auto res = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
-    return py::make_tuple(res(d_op), res(d_attrs), res(d_scale), res(d_bary));
+    return py::make_tuple(or_none(d_op), or_none(d_attrs), or_none(d_scale), or_none(d_bary));
 }
 
-// ---- composite_texture / composite_texture_backward (dmesh_renderer_amd_texture.h): fragments.composite_texture_fused ----------
-struct TextureArgs {
-    at::Tensor face, bary, uvf, opacity, uvs, tex, scale;  // scale: undefined = none
-    int B, K, H, W, Pu, F, C, Ht, Wt, wrap;
-    c10::Device dev;
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
-    const float* scale_ptr() const { return scale.defined() ? mptr<const float>(scale) : nullptr; }
-};
+// -- composite_texture: a bilinear texture at per-corner UVs
+struct TextureArgs : ListArgs { at::Tensor uvs, tex; int64_t Pu = 0, C = 0, Ht = 0, Wt = 0; int wrap = 0; };
 
 TextureArgs texture_args(In face, In bary, In uv_faces, In faces_opacity, In vert_uvs, In texture, const std::optional<at::Tensor>& face_scale,
                          int wrap) {
     if (!g_abi.composite_texture)
         err(g_abi.path + " does not export dmr_composite_texture: rebuild it (python -m dmesh_renderer_amd.build)");
-    const c10::Device dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    const int64_t B = face.size(0), K = face.size(1), H = face.size(2), W = face.size(3);
-    if (bary.dim() != 5 || bary.size(0) != B || bary.size(1) != K || bary.size(2) != 2 || bary.size(3) != H || bary.size(4) != W)
-        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
-    if (uv_faces.dim() != 2 || uv_faces.size(1) != 3) err("uv_faces must have dimensions (num_faces, 3)");
-    const int64_t F = uv_faces.size(0);
-    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != F) err("faces_opacity must have dimensions (num_faces,)");
+    TextureArgs a;
+    list_dims(a, "composite_texture", "uv_faces", face, bary, uv_faces, faces_opacity);
     if (vert_uvs.dim() != 2 || vert_uvs.size(1) != 2) err("vert_uvs must have dimensions (num_uvs, 2)");
     if (texture.dim() != 3) err("texture must have dimensions (Ht, Wt, C)");
-    const int64_t Pu = vert_uvs.size(0), Ht = texture.size(0), Wt = texture.size(1), C = texture.size(2);
-    if (K < 1 || K > 32) err("composite_texture: K must be in 1..32, got " + std::to_string(K));
-    if (C < 1 || C > 32) err("composite_texture: C must be in 1..32, got " + std::to_string(C));
-    if (Ht < 1 || Wt < 1 || Ht >= ((int64_t)1 << 31) || Wt >= ((int64_t)1 << 31)) err("composite_texture: the texture must have at least one texel");
-    if (B < 1 || H < 1 || W < 1) err("composite_texture: empty fragment lists");
+    a.Pu = vert_uvs.size(0); a.Ht = texture.size(0); a.Wt = texture.size(1); a.C = texture.size(2); a.wrap = wrap;
+    list_k(a);
+    if (a.C < 1 || a.C > 32) err("composite_texture: C must be in 1..32, got " + std::to_string(a.C));
+    if (a.Ht < 1 || a.Wt < 1 || a.Ht >= ((int64_t)1 << 31) || a.Wt >= ((int64_t)1 << 31)) err("composite_texture: the texture must have at least one texel");
+    list_not_empty(a);
     if (wrap != 0 && wrap != 1) err("composite_texture: wrap must be 0 (clamp) or 1 (repeat), got " + std::to_string(wrap));
-    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != B || face_scale->size(1) != F))
-        err("face_scale must have dimensions (B, num_faces)");
-    const std::pair<const at::Tensor*, const char*> same[6] = {{&bary, "bary"}, {&uv_faces, "uv_faces"}, {&faces_opacity, "faces_opacity"},
-                                                               {&vert_uvs, "vert_uvs"}, {&texture, "texture"},
-                                                               {face_scale ? &*face_scale : nullptr, "face_scale"}};
-    for (auto& t : same)
-        if (t.first && t.first->device() != dev) err(std::string(t.second) + " must be on the device of pix_to_face");
-    return {i32(face, "pix_to_face"), f32(bary, "bary"), i32(uv_faces, "uv_faces"), f32(faces_opacity, "faces_opacity"), f32(vert_uvs, "vert_uvs"),
-            f32(texture, "texture"), face_scale ? f32(*face_scale, "face_scale") : at::Tensor(),
-            (int)B, (int)K, (int)H, (int)W, (int)Pu, (int)F, (int)C, (int)Ht, (int)Wt, wrap, dev};
+    list_finish(a, face_scale, {{vert_uvs, "vert_uvs", a.uvs}, {texture, "texture", a.tex}});
+    return a;
 }
 
 // -> (image [B,C,H,W], T [B,1,H,W])
@@ -733,7 +747,7 @@ std::tuple<at::Tensor, at::Tensor> composite_texture(In face, In bary, In uv_fac
     c10::DeviceGuard guard(a.dev);
     at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
     if (g_abi.composite_texture(a.B, a.K, a.H, a.W, a.Pu, a.F, a.C, a.Ht, a.Wt, a.wrap, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
-                                mptr<const int32_t>(a.uvf), mptr<const float>(a.opacity), mptr<const float>(a.uvs), mptr<const float>(a.tex),
+                                mptr<const int32_t>(a.corners), mptr<const float>(a.opacity), mptr<const float>(a.uvs), mptr<const float>(a.tex),
                                 a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
         raise_lib();
     return {image, T};
@@ -747,32 +761,15 @@ py::tuple composite_texture_backward(In face, In bary, In uv_faces, In faces_opa
     const TextureArgs a = texture_args(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap);
     c10::DeviceGuard guard(a.dev);
     if (need[3] && !face_scale) err("composite_texture_backward: the gradient of face_scale without face_scale");
-    at::Tensor gi, gt;
-    if (grad_image) {
-        if (grad_image->dim() != 4 || grad_image->size(0) != a.B || grad_image->size(1) != a.C || grad_image->size(2) != a.H ||
-            grad_image->size(3) != a.W || grad_image->device() != a.dev)
-            err("grad_image must have dimensions (B, C, H, W) on the device of pix_to_face");
-        gi = f32(*grad_image, "grad_image");
-    }
-    if (grad_T) {
-        if (grad_T->numel() != (int64_t)a.B * a.H * a.W || grad_T->device() != a.dev) err("grad_T must have dimensions (B, 1, H, W) on the device of pix_to_face");
-        gt = f32(*grad_T, "grad_T");
-    }
-    at::Tensor d_op, d_uvs, d_tex, d_scale, d_bary;
-    if (need[0]) d_op = at::empty({a.F}, f32_on(a.dev));
-    if (need[1]) d_uvs = at::empty({a.Pu, 2}, f32_on(a.dev));
-    if (need[2]) d_tex = at::empty({a.Ht, a.Wt, a.C}, f32_on(a.dev));
-    if (need[3]) d_scale = at::empty({a.B, a.F}, f32_on(a.dev));
-    if (need[4]) d_bary = at::empty({a.B, a.K, 2, a.H, a.W}, f32_on(a.dev));
-    const auto out = [](at::Tensor& t) { return t.defined() ? mptr<float>(t) : nullptr; };
+    const auto [gi, gt] = upstreams(a, a.C, grad_image, grad_T);
+    at::Tensor d_op = grad_if(need[0], {a.F}, a.dev), d_uvs = grad_if(need[1], {a.Pu, 2}, a.dev), d_tex = grad_if(need[2], {a.Ht, a.Wt, a.C}, a.dev);
+    at::Tensor d_scale = grad_if(need[3], {a.B, a.F}, a.dev), d_bary = grad_if(need[4], {a.B, a.K, 2, a.H, a.W}, a.dev);
     if (g_abi.composite_texture_backward(a.B, a.K, a.H, a.W, a.Pu, a.F, a.C, a.Ht, a.Wt, a.wrap, mptr<const int32_t>(a.face),
-                                         mptr<const float>(a.bary), mptr<const int32_t>(a.uvf), mptr<const float>(a.opacity),
-                                         mptr<const float>(a.uvs), mptr<const float>(a.tex), a.scale_ptr(),
-                                         gi.defined() ? mptr<const float>(gi) : nullptr, gt.defined() ? mptr<const float>(gt) : nullptr,
-                                         out(d_op), out(d_uvs), out(d_tex), out(d_scale), out(d_bary), a.stream()))
+                                         mptr<const float>(a.bary), mptr<const int32_t>(a.corners), mptr<const float>(a.opacity),
+                                         mptr<const float>(a.uvs), mptr<const float>(a.tex), a.scale_ptr(), in_ptr(gi), in_ptr(gt),
+                                         out_ptr(d_op), out_ptr(d_uvs), out_ptr(d_tex), out_ptr(d_scale), out_ptr(d_bary), a.stream()))
         raise_lib();
-    const auto res = [](const at::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
-    return py::make_tuple(res(d_op), res(d_uvs), res(d_tex), res(d_scale), res(d_bary));
+    return py::make_tuple(or_none(d_op), or_none(d_uvs), or_none(d_tex), or_none(d_scale), or_none(d_bary));
 }
 
 py::tuple profile_collect() {

@@ -115,7 +115,7 @@ class _CompositeFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, face, bary, faces, faces_opacity, vert_attrs, face_scale):
-        image, t = _kernels().composite_fragments(face, bary, faces, faces_opacity, vert_attrs, face_scale)
+        image, t = _fused_kernels("composite").composite_fragments(face, bary, faces, faces_opacity, vert_attrs, face_scale)
         ctx.save_for_backward(face, bary, faces, faces_opacity, vert_attrs, *(() if face_scale is None else (face_scale,)))
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
         return image, t
@@ -127,20 +127,65 @@ class _CompositeFn(th.autograd.Function):
         need = (need[3], need[4], bool(scale) and need[5], need[1])
         if (grad_image is None and grad_t is None) or not any(need):
             return (None,) * 6
-        d_op, d_attrs, d_scale, d_bary = _kernels().composite_fragments_backward(
+        d_op, d_attrs, d_scale, d_bary = _fused_kernels("composite").composite_fragments_backward(
             face, bary, faces, faces_opacity, vert_attrs, scale[0] if scale else None,
             None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
         return None, d_bary, None, d_op, d_attrs, d_scale
 
 
-def _kernels():
-    """`_C` as the package holds it at call time (tests swap it), with the two composite calls -- or a TypeError."""
+# torch path -> (the flag of `_C` that announces its fused pair of calls, what they fuse)
+_FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_texture": ("SUPPORTS_FRAGMENT_TEXTURE", "texture")}
+
+
+def _fused_kernels(torch_path: str):
+    """`_C` as the package holds it at call time (tests swap it), with the fused calls of `torch_path` -- or a TypeError."""
     from . import _impl
     c = _impl(None)
-    if not getattr(c, "SUPPORTS_FRAGMENT_COMPOSITE", False):
-        raise TypeError("composite_fused: the loaded libdmesh_renderer_hip.so / _C has no fused fragment compositing: rebuild "
-                        "(python -m dmesh_renderer_amd.build); fragments.composite is the torch path")
+    flag, what = _FUSED[torch_path]
+    if not getattr(c, flag, False):
+        raise TypeError(f"{torch_path}_fused: the loaded libdmesh_renderer_hip.so / _C has no fused {what} compositing: rebuild "
+                        f"(python -m dmesh_renderer_amd.build); fragments.{torch_path} is the torch path")
     return c
+
+
+def _check_fused(name: str, torch_path: str, frag, faces, faces_opacity, face_scale, uv_faces, own_shapes, own_floats):
+    """What both fused entry points refuse, in the order they refuse it: the lists' shapes, K, faces, uv_faces (None: not given),
+    faces_opacity; the unit's own shapes (own_shapes() raises); face_scale's shape; float32 for the lists' floats, own_floats
+    [(name, tensor)] and face_scale; int32 lists, integer faces / uv_faces; one HIP device for all.  -> (pix_to_face, bary)"""
+    face, bary = frag.pix_to_face, frag.bary
+    if face.dim() != 4:
+        raise ValueError(f"{name}: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
+    B, K, H, W = face.shape
+    if tuple(bary.shape) != (B, K, 2, H, W):
+        raise ValueError(f"{name}: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {tuple(bary.shape)}")
+    if not 1 <= K <= 32:
+        raise ValueError(f"{name}: K must be in 1..32, got {K}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    F = faces.shape[0]
+    if uv_faces is not None and tuple(uv_faces.shape) != (F, 3):
+        raise ValueError(f"{name}: uv_faces must be [F,3] = {(F, 3)}, got {tuple(uv_faces.shape)}")
+    if tuple(faces_opacity.shape) != (F,):
+        raise ValueError(f"{name}: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
+    own_shapes()
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("frag.bary", bary), ("faces_opacity", faces_opacity)] + own_floats
+    if face_scale is not None:
+        floats.append(("face_scale", face_scale))
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if face.dtype != th.int32:
+        raise TypeError(f"{name}: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
+    ints = [("faces", faces)] + ([] if uv_faces is None else [("uv_faces", uv_faces)])
+    for n, t in ints:
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == th.bool:
+            raise TypeError(f"{name}: {n} must be an integer tensor, got {t.dtype}; {torch_path}")
+    for n, t in [("frag.pix_to_face", face)] + ints + floats:
+        if not t.is_cuda or t.device != face.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    return face, bary
 
 
 def composite_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.Tensor,
@@ -151,41 +196,15 @@ def composite_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs
     (ValueError).  A slot whose face id lies outside [0, F) is empty, wherever it sits in the list; frag.count is not read.
     HIP float32 tensors only (pix_to_face int32; faces of another integer dtype are cast, as TriRenderer does): anything else
     is a TypeError -- composite is the torch path for it; nothing falls back silently."""
-    _kernels()
-    face, bary = frag.pix_to_face, frag.bary
-    if face.dim() != 4:
-        raise ValueError(f"composite_fused: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
-    B, K, H, W = face.shape
-    if tuple(bary.shape) != (B, K, 2, H, W):
-        raise ValueError(f"composite_fused: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {tuple(bary.shape)}")
-    if not 1 <= K <= 32:
-        raise ValueError(f"composite_fused: K must be in 1..32, got {K}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"composite_fused: faces must be [F,3], got {tuple(faces.shape)}")
-    F = faces.shape[0]
-    if tuple(faces_opacity.shape) != (F,):
-        raise ValueError(f"composite_fused: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
-    if vert_attrs.dim() != 2:
-        raise ValueError(f"composite_fused: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
-    if not 1 <= vert_attrs.shape[1] <= 256:
-        raise ValueError(f"composite_fused: C must be in 1..256, got {vert_attrs.shape[1]}")
-    if face_scale is not None and tuple(face_scale.shape) != (B, F):
-        raise ValueError(f"composite_fused: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
-    floats = [("frag.bary", bary), ("faces_opacity", faces_opacity), ("vert_attrs", vert_attrs)]
-    if face_scale is not None:
-        floats.append(("face_scale", face_scale))
-    torch_path = "fragments.composite is the torch path for anything else"
-    for name, t in floats:
-        if t.dtype != th.float32:
-            raise TypeError(f"composite_fused: {name} must be float32, got {t.dtype}; {torch_path}")
-    if face.dtype != th.int32:
-        raise TypeError(f"composite_fused: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
-    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == th.bool:
-        raise TypeError(f"composite_fused: faces must be an integer tensor, got {faces.dtype}; {torch_path}")
-    for name, t in [("frag.pix_to_face", face), ("faces", faces)] + floats:
-        if not t.is_cuda or t.device != face.device:
-            raise TypeError(f"composite_fused: {name} is on {t.device}: every tensor must be on one HIP device (there is no CPU "
-                            f"path); {torch_path}")
+    _fused_kernels("composite")
+    def own_shapes():
+        if vert_attrs.dim() != 2:
+            raise ValueError(f"composite_fused: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
+        if not 1 <= vert_attrs.shape[1] <= 256:
+            raise ValueError(f"composite_fused: C must be in 1..256, got {vert_attrs.shape[1]}")
+
+    face, bary = _check_fused("composite_fused", "fragments.composite is the torch path for anything else", frag, faces, faces_opacity,
+                              face_scale, None, own_shapes, [("vert_attrs", vert_attrs)])
     return _CompositeFn.apply(face, bary, faces.to(th.int32), faces_opacity, vert_attrs, face_scale)
 
 
@@ -240,7 +259,7 @@ class _CompositeTextureFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap):
-        image, t = _texture_kernels().composite_texture(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap)
+        image, t = _fused_kernels("composite_texture").composite_texture(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap)
         ctx.save_for_backward(face, bary, uv_faces, faces_opacity, vert_uvs, texture, *(() if face_scale is None else (face_scale,)))
         ctx.wrap = wrap
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
@@ -253,20 +272,10 @@ class _CompositeTextureFn(th.autograd.Function):
         need = (need[3], need[4], need[5], bool(scale) and need[6], need[1])
         if (grad_image is None and grad_t is None) or not any(need):
             return (None,) * 8
-        d_op, d_uvs, d_tex, d_scale, d_bary = _texture_kernels().composite_texture_backward(
+        d_op, d_uvs, d_tex, d_scale, d_bary = _fused_kernels("composite_texture").composite_texture_backward(
             face, bary, uv_faces, faces_opacity, vert_uvs, texture, scale[0] if scale else None, ctx.wrap,
             None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
         return None, d_bary, None, d_op, d_uvs, d_tex, d_scale, None
-
-
-def _texture_kernels():
-    """`_C` as the package holds it at call time (tests swap it), with the two texture calls -- or a TypeError."""
-    from . import _impl
-    c = _impl(None)
-    if not getattr(c, "SUPPORTS_FRAGMENT_TEXTURE", False):
-        raise TypeError("composite_texture_fused: the loaded libdmesh_renderer_hip.so / _C has no fused texture compositing: rebuild "
-                        "(python -m dmesh_renderer_amd.build); fragments.composite_texture is the torch path")
-    return c
 
 
 def composite_texture_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_uvs: th.Tensor, texture: th.Tensor,
@@ -282,50 +291,22 @@ def composite_texture_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, ve
     faces / uv_faces of another integer dtype are cast): anything else is a TypeError -- composite_texture is the torch path
     for it; nothing falls back silently."""
     name = "composite_texture_fused"
-    _texture_kernels()
+    _fused_kernels("composite_texture")
     if wrap not in WRAPS:
         raise ValueError(f"{name}: wrap must be one of {WRAPS}, got {wrap!r}")
-    face, bary = frag.pix_to_face, frag.bary
-    if face.dim() != 4:
-        raise ValueError(f"{name}: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
-    B, K, H, W = face.shape
-    if tuple(bary.shape) != (B, K, 2, H, W):
-        raise ValueError(f"{name}: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {tuple(bary.shape)}")
-    if not 1 <= K <= 32:
-        raise ValueError(f"{name}: K must be in 1..32, got {K}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
-    F = faces.shape[0]
+
+    def own_shapes():
+        if vert_uvs.dim() != 2 or vert_uvs.shape[1] != 2:
+            raise ValueError(f"{name}: vert_uvs must be [Pu,2], got {tuple(vert_uvs.shape)}")
+        if texture.dim() != 3:
+            raise ValueError(f"{name}: texture must be [Ht,Wt,C], got {tuple(texture.shape)}")
+        Ht, Wt, C = texture.shape
+        if not 1 <= C <= 32:
+            raise ValueError(f"{name}: C must be in 1..32, got {C}")
+        if Ht < 1 or Wt < 1 or Ht * Wt * ((C + 3) // 4) >= 2 ** 32 - 1:
+            raise ValueError(f"{name}: texture must have Ht, Wt >= 1 and Ht * Wt * ceil(C / 4) < 2^32 - 1, got {tuple(texture.shape)}")
+
+    face, bary = _check_fused(name, "fragments.composite_texture is the torch path for anything else", frag, faces, faces_opacity, face_scale,
+                              uv_faces, own_shapes, [("vert_uvs", vert_uvs), ("texture", texture)])
     corners = faces if uv_faces is None else uv_faces
-    if tuple(corners.shape) != (F, 3):
-        raise ValueError(f"{name}: uv_faces must be [F,3] = {(F, 3)}, got {tuple(corners.shape)}")
-    if tuple(faces_opacity.shape) != (F,):
-        raise ValueError(f"{name}: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
-    if vert_uvs.dim() != 2 or vert_uvs.shape[1] != 2:
-        raise ValueError(f"{name}: vert_uvs must be [Pu,2], got {tuple(vert_uvs.shape)}")
-    if texture.dim() != 3:
-        raise ValueError(f"{name}: texture must be [Ht,Wt,C], got {tuple(texture.shape)}")
-    Ht, Wt, C = texture.shape
-    if not 1 <= C <= 32:
-        raise ValueError(f"{name}: C must be in 1..32, got {C}")
-    if Ht < 1 or Wt < 1 or Ht * Wt * ((C + 3) // 4) >= 2 ** 32 - 1:
-        raise ValueError(f"{name}: texture must have Ht, Wt >= 1 and Ht * Wt * ceil(C / 4) < 2^32 - 1, got {tuple(texture.shape)}")
-    if face_scale is not None and tuple(face_scale.shape) != (B, F):
-        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
-    floats = [("frag.bary", bary), ("faces_opacity", faces_opacity), ("vert_uvs", vert_uvs), ("texture", texture)]
-    if face_scale is not None:
-        floats.append(("face_scale", face_scale))
-    torch_path = "fragments.composite_texture is the torch path for anything else"
-    for n, t in floats:
-        if t.dtype != th.float32:
-            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
-    if face.dtype != th.int32:
-        raise TypeError(f"{name}: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
-    ints = [("faces", faces)] + ([] if uv_faces is None else [("uv_faces", uv_faces)])
-    for n, t in ints:
-        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == th.bool:
-            raise TypeError(f"{name}: {n} must be an integer tensor, got {t.dtype}; {torch_path}")
-    for n, t in [("frag.pix_to_face", face)] + ints + floats:
-        if not t.is_cuda or t.device != face.device:
-            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
     return _CompositeTextureFn.apply(face, bary, corners.to(th.int32), faces_opacity, vert_uvs, texture, face_scale, WRAPS.index(wrap))

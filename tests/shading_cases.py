@@ -8,8 +8,9 @@ from collections import namedtuple
 import torch as th
 
 # ---------------------------------------------------------------------------
-# The host dispatch, restated.  tests/test_shading_coverage_cpu.py holds the lines of the two .hip files this mirrors
-# (DISPATCH_LINES there) and fails when one of them is no longer in the file: then this follows the new dispatch.
+# The host dispatch, restated.  tests/test_shading_coverage_cpu.py holds the lines of the two .hip files and of their common
+# header (csrc/dmr_shade_common.hpp) this mirrors (DISPATCH_LINES there) and fails when one of them is no longer in its file:
+# then this follows the new dispatch.
 # ---------------------------------------------------------------------------
 FRAG_MAX_K = 32     # dmr_kernels.hpp
 SHADE_MAX_C = 256   # dmr_shade.hip
@@ -18,8 +19,8 @@ KMAXES = (4, 8, 16, 32)
 
 
 def kmax_of(K):
-    """dmr_composite_fragments_backward / dmr_composite_texture_backward: if (K <= 4) <4> else if (K <= 8) <8> else if
-    (K <= 16) <16> else <32>."""
+    """with_kmax of dmr_shade_common.hpp, which both backward calls launch through: if (K <= 4) <4> else if (K <= 8) <8> else
+    if (K <= 16) <16> else <32>."""
     assert 1 <= K <= FRAG_MAX_K
     return 4 if K <= 4 else (8 if K <= 8 else (16 if K <= 16 else 32))
 
@@ -45,7 +46,8 @@ def texture_forward_nch(C):
 
 
 def vec_of(C, aligned):
-    """shade_params / tex_params: p.vec = C % 4 == 0 and a 16-byte aligned base of vert_attrs / texture."""
+    """shade_vec of dmr_shade_common.hpp, as shade_params / tex_params call it: p.vec = C % 4 == 0 and a 16-byte aligned base
+    of vert_attrs / texture."""
     return int(C % 4 == 0 and aligned)
 
 
@@ -228,3 +230,61 @@ EDGES = {
     "texture: C % 4 == 0 on a misaligned base, NCH 8": lambda r: r.unit == "texture" and r.C > 4 and r.C % 4 == 0 and not r.aligned,
     "texture: TEX_MAX_C on a misaligned base": lambda r: r.unit == "texture" and r.C == TEX_MAX_C and not r.aligned,
 }
+
+
+# ---------------------------------------------------------------------------
+# The binding's refusals (csrc/dmr_torch.cpp), below Python's checks: one wrong argument per call, at B, K, H, W = 1, 1, 1, 1,
+# F = 1, P = Pu = 3, so that no call reaches a kernel.  The expected messages (tests/golden/shading_refusals.json, "binding")
+# were copied from the source text of the binding before its list checks were merged, and compared on the GPU with a run of that
+# binding over these cases: 82 calls, the same text in each.
+# ---------------------------------------------------------------------------
+def binding_refusals(unit, dev):
+    """[(case, name of the call in _C, positional arguments)] for unit "shade" / "texture": every case through the forward
+    call and through the backward call (need: nothing, so that a call that were not refused would return before its memsets)."""
+    z = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype, device=dev)
+    good = dict(face=z(1, 1, 1, 1, dtype=th.int32), bary=z(1, 1, 2, 1, 1), corners=th.tensor([[0, 1, 2]], dtype=th.int32, device=dev),
+                opacity=z(1) + 0.5, scale=None, grad_image=z(1, 3, 1, 1), grad_T=z(1, 1, 1, 1))
+    if unit == "shade":
+        good.update(attrs=z(3, 3))
+        own, fwd, n_need = ("attrs",), "composite_fragments", 4
+    else:
+        good.update(uvs=z(3, 2), tex=z(2, 2, 3), wrap=0)
+        own, fwd, n_need = ("uvs", "tex"), "composite_texture", 5
+    cases = {
+        "pix_to_face on the CPU": dict(face=good["face"].cpu()),
+        "pix_to_face with three dimensions": dict(face=good["face"][0]),
+        "bary of another shape": dict(bary=z(1, 1, 3, 1, 1)),
+        "corner table [F,2]": dict(corners=good["corners"][:, :2]),
+        "faces_opacity of another length": dict(opacity=z(2)),
+        "K = 33": dict(face=z(1, 33, 1, 1, dtype=th.int32), bary=z(1, 33, 2, 1, 1)),
+        "K = 0": dict(face=z(1, 0, 1, 1, dtype=th.int32), bary=z(1, 0, 2, 1, 1)),
+        "empty fragment lists": dict(face=z(1, 1, 0, 1, dtype=th.int32), bary=z(1, 1, 2, 0, 1)),
+        "face_scale of another shape": dict(scale=z(1, 2)),
+        "bary on the CPU": dict(bary=good["bary"].cpu()),
+        "face_scale on the CPU": dict(scale=th.zeros(1, 1)),
+        "bary float64": dict(bary=good["bary"].double()),
+        "pix_to_face int64": dict(face=good["face"].long()),
+    }
+    if unit == "shade":
+        cases.update({"vert_attrs with one dimension": dict(attrs=z(3)), "C = 257": dict(attrs=z(3, 257)), "C = 0": dict(attrs=z(3, 0)),
+                      "vert_attrs on the CPU": dict(attrs=th.zeros(3, 3))})
+    else:
+        cases.update({"vert_uvs [Pu,3]": dict(uvs=z(3, 3)), "texture with two dimensions": dict(tex=z(2, 2)), "C = 33": dict(tex=z(2, 2, 33)),
+                      "no texel": dict(tex=z(0, 2, 3)), "wrap = 2": dict(wrap=2), "texture on the CPU": dict(tex=th.zeros(2, 2, 3)),
+                      "bad C and bad wrap": dict(tex=z(2, 2, 33), wrap=2)})
+    backward_only = {
+        "need face_scale without face_scale": dict(need=(False,) * (n_need - 2) + (True, False)),
+        "grad_image of another shape": dict(grad_image=z(1, 4, 1, 1)),
+        "grad_T of another size": dict(grad_T=z(1, 1, 1, 2)),
+        "grad_image on the CPU": dict(grad_image=th.zeros(1, 3, 1, 1)),
+    }
+    out = []
+    for table, calls in ((cases, (fwd, fwd + "_backward")), (backward_only, (fwd + "_backward",))):
+        for case, changes in table.items():
+            a = dict(good, need=(False,) * n_need)
+            a.update(changes)
+            lists = [a["face"], a["bary"], a["corners"], a["opacity"]] + [a[k] for k in own] + [a["scale"]]
+            for call in calls:
+                tail = ([a["wrap"]] if unit == "texture" else []) + ([a["grad_image"], a["grad_T"], a["need"]] if call.endswith("_backward") else [])
+                out.append((case, call, lists + tail))
+    return out

@@ -32,7 +32,7 @@ def test_library_exports_the_declared_symbols():
 def test_source_and_headers_are_build_dependencies():
     from dmesh_renderer_amd import build
     assert "dmr_texture.hip" in build.SOURCES
-    assert "dmr_shade_table.hpp" in build.HEADERS
+    assert "dmr_shade_common.hpp" in build.HEADERS
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_texture.h" for d in deps)
         assert all(os.path.exists(os.path.join(build.CSRC, d)) for d in deps)

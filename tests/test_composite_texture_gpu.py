@@ -480,3 +480,21 @@ def test_frames(hip_device, frame):
     tex, wrap = TEXTURE_EDGE_FRAME
     d = _lists(K, C, tex, size, True, frame)
     _check(f"frame {frame} K {K} C {C}", d, _reference(K, C, tex, size, True, wrap, True, frame), _fused(d, hip_device, wrap, True))
+
+
+def test_binding_refusals(hip_device):
+    """The binding's own refusals, below fragments.py's: every case of shading_cases.binding_refusals("texture") raises a
+    RuntimeError with the message the binding had before its list checks were merged (tests/golden/shading_refusals.json:
+    copied from that source text and compared with a run of that binding over the same cases).
+    One wrong argument per call, at one pixel: no call reaches a kernel."""
+    import json
+    import os
+    import shading_cases as SC
+    from dmesh_renderer_amd import _C
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shading_refusals.json")))["binding"]["texture"]
+    cases = SC.binding_refusals("texture", hip_device)
+    assert sorted({case for case, _, _ in cases}) == sorted(golden)
+    for case, call, args in cases:
+        with pytest.raises(RuntimeError) as e:
+            getattr(_C, call)(*args)
+        assert str(e.value) == golden[case], (case, call)

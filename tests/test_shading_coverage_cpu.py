@@ -1,7 +1,7 @@
 """The fused shading units compile 20 + 10 kernel instantiations, picked at run time from K, C and a pointer's alignment.
 Without a GPU: the case tables of their GPU tests (tests/shading_cases.py) together reach every one of them, with float4 and
-with scalar loads; the dispatch that claim rests on is still the one in the two .hip files; and every new GPU case meets the
-conditions on its inputs (they depend on the float64 model and the generator alone)."""
+with scalar loads; the dispatch that claim rests on is still the one in the two .hip files and their common header; and
+every new GPU case meets the conditions on its inputs (they depend on the float64 model and the generator alone)."""
 import os
 
 import torch as th
@@ -12,30 +12,33 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 # The host code shading_cases restates, line by line.
 DISPATCH_LINES = {
+    "dmr_shade_common.hpp": [  # what the two units share: the K ladder and the float4 rule, once
+        "if (K <= 4) f(std::integral_constant<int, 4>());",
+        "else if (K <= 8) f(std::integral_constant<int, 8>());",
+        "else if (K <= 16) f(std::integral_constant<int, 16>());",
+        "else f(std::integral_constant<int, 32>());",
+        "inline int shade_vec(int C, const float* base) { return (C % 4 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0u) ? 1 : 0; }",
+    ],
     "dmr_shade.hip": [
         "constexpr int SHADE_MAX_C = 256;",
-        "p.vec = (C % 4 == 0 && (reinterpret_cast<uintptr_t>(vert_attrs) & 15u) == 0u) ? 1 : 0;",
+        "p.vec = shade_vec(C, vert_attrs);",
         "if (C <= 4) k_composite_fragments<4><<<grid, block, 0, st>>>(p, image, T);",
         "else k_composite_fragments<16><<<grid, block, 0, st>>>(p, image, T);",
         "if (p.C <= 4) k_composite_fragments_backward<KMAX, 4><<<",
         "else k_composite_fragments_backward<KMAX, 8><<<",
-        "if (K <= 4) launch_backward<4>(",
-        "else if (K <= 8) launch_backward<8>(",
-        "else if (K <= 16) launch_backward<16>(",
-        "else launch_backward<32>(",
+        "with_kmax(K, [&](auto kmax) {",
+        "launch_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_attrs, dL_dface_scale, dL_dbary);",
     ],
     "dmr_texture.hip": [
         "constexpr int TEX_MAX_C = 32;",
         "constexpr int TEX_CHUNKS = TEX_MAX_C / 4;",
-        "p.vec = (C % 4 == 0 && (reinterpret_cast<uintptr_t>(texture) & 15u) == 0u) ? 1 : 0;",
+        "p.vec = shade_vec(C, texture);",
         "if (C <= 4) k_composite_texture<1><<<grid, block, 0, st>>>(p, image, T);",
         "else k_composite_texture<TEX_CHUNKS><<<grid, block, 0, st>>>(p, image, T);",
         "if (dtex && gi) k_composite_texture_backward<KMAX, true><<<",
         "else k_composite_texture_backward<KMAX, false><<<",
-        "if (K <= 4) go(launch_backward<4>);",
-        "else if (K <= 8) go(launch_backward<8>);",
-        "else if (K <= 16) go(launch_backward<16>);",
-        "else go(launch_backward<32>);",
+        "with_kmax(K, [&](auto kmax) {",
+        "launch_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dL_dfaces_opacity, dL_dvert_uvs, dL_dtexture, dL_dface_scale, dL_dbary);",
     ],
 }
 
@@ -45,7 +48,7 @@ def _all_cases():
 
 
 def test_dispatch_restated_as_the_units_have_it():
-    """The lines shading_cases mirrors are in the two files as text: a change of the dispatch fails here until the helper (and
+    """The lines shading_cases mirrors are in the units' files as text, each once: a change of the dispatch fails here until the helper (and
     the tables) follow it.  And the restatement itself, at the thresholds."""
     for name, lines in DISPATCH_LINES.items():
         unit = open(os.path.join(CSRC, name)).read()
