@@ -1,5 +1,6 @@
-// dmr_shade_common.hpp -- what the shading units over fragment lists (dmr_shade.hip, dmr_texture.hip) share, each fact once:
-//   device: of the backward kernels the merge of a wave's lanes of equal key (shade_merge) and the per-tile LDS table
+// dmr_shade_common.hpp -- what the shading units over fragment lists (dmr_shade.hip, dmr_texture.hip, dmr_visibility.hip) share,
+// each fact once:
+//   device: the merge of a wave's lanes of equal key (shade_merge; shade_merge_max for a maximum) and the per-tile LDS table
 //           (stab_find*).  The kernels' walks are each unit's own text, those they have in common too: DESIGN.md 5c;
 //   host:   the list arguments' validation (shade_check_sizes, shade_check_lists), shade_vec, the K ladder (with_kmax), the
 //           backward calls' prologue (shade_backward_prologue), the check after a launch (launched).
@@ -53,6 +54,29 @@ __device__ __forceinline__ void shade_merge(int lane, int& key, float (&g)[NV]) 
     shade_merge_level<1>(lane, key, g);
     shade_merge_level<2>(lane, key, g);
     shade_merge_level<3>(lane, key, g);
+}
+
+// The same merge for a value that is a maximum, not a sum (dmr_visibility.hip's largest weight): run it on a COPY of the key
+// shade_merge is about to get -- the keys alone decide who takes and who retires, so both end on the same survivors.
+template <int LEVEL>
+__device__ __forceinline__ void shade_merge_max_level(int lane, int& key, float& m) {
+    constexpr int offset = 1 << LEVEL;
+    constexpr int FROM_UPPER = LEVEL == 0 ? 0xB1 : (LEVEL == 1 ? 0x4E : (LEVEL == 2 ? 0x104 : 0x108));
+    constexpr int FROM_LOWER = LEVEL == 0 ? 0xB1 : (LEVEL == 1 ? 0x4E : (LEVEL == 2 ? 0x114 : 0x118));
+    const bool lower = (lane & offset) == 0;
+    const int k_up = __builtin_amdgcn_update_dpp(-1, key, FROM_UPPER, 0xF, 0xF, false);
+    const int k_lo = __builtin_amdgcn_update_dpp(-1, key, FROM_LOWER, 0xF, 0xF, false);
+    const bool take = lower && key >= 0 && k_up == key;
+    const bool retire = !lower && key >= 0 && k_lo == key;
+    const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), FROM_UPPER, 0xF, 0xF, false));
+    m = (take && other > m) ? other : m;
+    if (retire) key = -1;
+}
+__device__ __forceinline__ void shade_merge_max(int lane, int key, float& m) {
+    shade_merge_max_level<0>(lane, key, m);
+    shade_merge_max_level<1>(lane, key, m);
+    shade_merge_max_level<2>(lane, key, m);
+    shade_merge_max_level<3>(lane, key, m);
 }
 
 // the slot of row `rid` in a table of N slots; -1: none within STAB_PROBES probes (the row goes out with direct atomics)

@@ -39,6 +39,9 @@
 //   composite_texture(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale=None, wrap=0) -> (image, T) and
 //   composite_texture_backward(..., grad_image, grad_T, need=(opacity, uvs, texture, scale, bary)) -> those five gradients or None:
 //                            fragments.composite_texture_fused, over include/dmesh_renderer_amd_texture.h (SUPPORTS_FRAGMENT_TEXTURE)
+//   face_visibility(face, faces_opacity, pixel_weight=None, coverage=False) -> (vis [B,F], max_weight [B,F] | None, pixels i32 [B,F] | None) and
+//   face_visibility_backward(face, faces_opacity, pixel_weight, grad_vis, need=(opacity, pixel_weight)) -> those two gradients or None:
+//                            fragments.face_visibility_fused, over include/dmesh_renderer_amd_visibility.h (SUPPORTS_FRAGMENT_VISIBILITY)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -59,6 +62,7 @@
 #include "../../include/dmesh_renderer_amd.h"
 #include "../../include/dmesh_renderer_amd_shade.h"
 #include "../../include/dmesh_renderer_amd_texture.h"
+#include "../../include/dmesh_renderer_amd_visibility.h"
 
 namespace {
 
@@ -90,6 +94,9 @@ struct Abi {
     // dmesh_renderer_amd_texture.h: optional too (SUPPORTS_FRAGMENT_TEXTURE)
     decltype(&dmr_composite_texture) composite_texture = nullptr;
     decltype(&dmr_composite_texture_backward) composite_texture_backward = nullptr;
+    // dmesh_renderer_amd_visibility.h: optional too (SUPPORTS_FRAGMENT_VISIBILITY)
+    decltype(&dmr_face_visibility) face_visibility = nullptr;
+    decltype(&dmr_face_visibility_backward) face_visibility_backward = nullptr;
 };
 
 Abi g_abi;
@@ -136,6 +143,10 @@ void load_abi() {
     g_abi.composite_texture_backward =
         reinterpret_cast<decltype(g_abi.composite_texture_backward)>(dlsym(g_abi.handle, "dmr_composite_texture_backward"));
     if (!g_abi.composite_texture || !g_abi.composite_texture_backward) g_abi.composite_texture = nullptr, g_abi.composite_texture_backward = nullptr;
+    g_abi.face_visibility = reinterpret_cast<decltype(g_abi.face_visibility)>(dlsym(g_abi.handle, "dmr_face_visibility"));
+    g_abi.face_visibility_backward =
+        reinterpret_cast<decltype(g_abi.face_visibility_backward)>(dlsym(g_abi.handle, "dmr_face_visibility_backward"));
+    if (!g_abi.face_visibility || !g_abi.face_visibility_backward) g_abi.face_visibility = nullptr, g_abi.face_visibility_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -772,6 +783,68 @@ py::tuple composite_texture_backward(In face, In bary, In uv_faces, In faces_opa
     return py::make_tuple(or_none(d_op), or_none(d_uvs), or_none(d_tex), or_none(d_scale), or_none(d_bary));
 }
 
+// -- face_visibility: per-face visibility and coverage (dmesh_renderer_amd_visibility.h, fragments.face_visibility_fused).  It reads
+// the face ids and the opacities alone, so its checks are its own, in the order of fragments.py's: the lists' shape, K, the
+// opacities' and the pixel weights' shapes, one device, dtypes.
+struct VisArgs {
+    at::Tensor face, opacity, weight;  // weight: undefined = none
+    int64_t B = 0, K = 0, H = 0, W = 0, F = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+};
+
+VisArgs vis_args(In face, In faces_opacity, const std::optional<at::Tensor>& pixel_weight) {
+    if (!g_abi.face_visibility)
+        err(g_abi.path + " does not export dmr_face_visibility: rebuild it (python -m dmesh_renderer_amd.build)");
+    VisArgs a;
+    a.dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+    if (a.K < 1 || a.K > 32) err("face_visibility: K must be in 1..32, got " + std::to_string(a.K));
+    if (a.B < 1 || a.H < 1 || a.W < 1) err("face_visibility: empty fragment lists");
+    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
+    a.F = faces_opacity.size(0);
+    if (pixel_weight && (pixel_weight->dim() != 3 || pixel_weight->size(0) != a.B || pixel_weight->size(1) != a.H || pixel_weight->size(2) != a.W))
+        err("pixel_weight must have dimensions (B, H, W) of pix_to_face's B, H, W");
+    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
+    if (pixel_weight && pixel_weight->device() != a.dev) err("pixel_weight must be on the device of pix_to_face");
+    a.face = i32(face, "pix_to_face"); a.opacity = f32(faces_opacity, "faces_opacity");
+    if (pixel_weight) a.weight = f32(*pixel_weight, "pixel_weight");
+    return a;
+}
+
+// -> (vis [B,F], max_weight [B,F], pixels i32 [B,F]); the last two None without coverage
+py::tuple face_visibility(In face, In faces_opacity, const std::optional<at::Tensor>& pixel_weight, bool coverage) {
+    const VisArgs a = vis_args(face, faces_opacity, pixel_weight);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor vis = at::empty({a.B, a.F}, f32_on(a.dev)), max_weight, pixels;
+    if (coverage) {
+        max_weight = at::empty({a.B, a.F}, f32_on(a.dev));
+        pixels = at::empty({a.B, a.F}, at::TensorOptions().dtype(at::kInt).device(a.dev));
+    }
+    // (F == 0: the three are empty and their pointers null, which the call takes: it has nothing to write)
+    if (a.F > 0 && g_abi.face_visibility(a.B, a.K, a.H, a.W, a.F, mptr<const int32_t>(a.face), mptr<const float>(a.opacity), in_ptr(a.weight),
+                                         mptr<float>(vis), out_ptr(max_weight), coverage ? mptr<int32_t>(pixels) : nullptr, a.stream()))
+        raise_lib();
+    return py::make_tuple(vis, or_none(max_weight), or_none(pixels));
+}
+
+// need = (faces_opacity, pixel_weight) -> those two gradients, None where not asked for; grad_vis [B,F]
+py::tuple face_visibility_backward(In face, In faces_opacity, const std::optional<at::Tensor>& pixel_weight, In grad_vis,
+                                   const std::array<bool, 2>& need) {
+    const VisArgs a = vis_args(face, faces_opacity, pixel_weight);
+    c10::DeviceGuard guard(a.dev);
+    if (need[1] && !pixel_weight) err("face_visibility_backward: the gradient of pixel_weight without pixel_weight");
+    if (grad_vis.dim() != 2 || grad_vis.size(0) != a.B || grad_vis.size(1) != a.F || grad_vis.device() != a.dev)
+        err("grad_vis must have dimensions (B, num_faces) on the device of pix_to_face");
+    const at::Tensor gv = f32(grad_vis, "grad_vis");
+    at::Tensor d_op = grad_if(need[0], {a.F}, a.dev), d_pw = grad_if(need[1], {a.B, a.H, a.W}, a.dev);
+    if (g_abi.face_visibility_backward(a.B, a.K, a.H, a.W, a.F, mptr<const int32_t>(a.face), mptr<const float>(a.opacity), in_ptr(a.weight),
+                                       mptr<const float>(gv), out_ptr(d_op), out_ptr(d_pw), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_op), or_none(d_pw));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -828,6 +901,10 @@ PYBIND11_MODULE(_C, m) {
     m.def("composite_texture_backward", &composite_texture_backward, py::arg("face"), py::arg("bary"), py::arg("uv_faces"),
           py::arg("faces_opacity"), py::arg("vert_uvs"), py::arg("texture"), py::arg("face_scale"), py::arg("wrap"), py::arg("grad_image"),
           py::arg("grad_T"), py::arg("need") = std::array<bool, 5>{true, true, true, true, true});
+    m.def("face_visibility", &face_visibility, py::arg("face"), py::arg("faces_opacity"), py::arg("pixel_weight") = py::none(),
+          py::arg("coverage") = false);
+    m.def("face_visibility_backward", &face_visibility_backward, py::arg("face"), py::arg("faces_opacity"), py::arg("pixel_weight"),
+          py::arg("grad_vis"), py::arg("need") = std::array<bool, 2>{true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -854,6 +931,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_COMPOSITE") = g_abi.composite_fragments != nullptr;
     // fragments.composite_texture_fused; False: the loaded library predates dmesh_renderer_amd_texture.h
     m.attr("SUPPORTS_FRAGMENT_TEXTURE") = g_abi.composite_texture != nullptr;
+    // fragments.face_visibility_fused; False: the loaded library predates dmesh_renderer_amd_visibility.h
+    m.attr("SUPPORTS_FRAGMENT_VISIBILITY") = g_abi.face_visibility != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

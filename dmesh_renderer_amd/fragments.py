@@ -3,7 +3,10 @@ render_tet(..., return_fragments=K) -> Fragments(pix_to_face [B,K,H,W], bary [B,
 
 Plain torch and differentiable -- but for composite_fused, which is composite as one pair of HIP kernels (forward, backward:
 csrc/dmr_shade.hip) without the [B,K,H,W,3,C] intermediates composite keeps for autograd, and composite_texture_fused, which
-is composite_texture (a bilinear texture sampled at per-corner UVs, then blended) as another pair (csrc/dmr_texture.hip).
+is composite_texture (a bilinear texture sampled at per-corner UVs, then blended) as another pair (csrc/dmr_texture.hip), and
+face_visibility_fused, which is face_visibility (per-face sums of the blend weights, optionally weighted per pixel) and
+face_coverage (per face the largest weight and the number of list slots that hold it) from one walk of the lists as a third
+pair (csrc/dmr_visibility.hip): what a mesh optimiser reads to prune faces and to attribute per-pixel error to them.
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -37,7 +40,7 @@ from typing import Optional, Tuple
 import torch as th
 
 __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
-           "composite_texture_fused"]
+           "composite_texture_fused", "face_coverage", "face_visibility_fused"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -98,15 +101,32 @@ def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.T
     return (w.unsqueeze(2).to(a.dtype) * a).sum(1), t[:, -1:]
 
 
-def face_visibility(frag, faces_opacity: th.Tensor, F: int) -> th.Tensor:
+def face_visibility(frag, faces_opacity: th.Tensor, F: int, pixel_weight: Optional[th.Tensor] = None) -> th.Tensor:
     """Sum of the blend weights every face received over a view's pixels, [B,F] (one scatter_add): 0 for a face no pixel
-    blended (tet: no ray composited) -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.  Constants: the
-    faces and their order.
-    Differentiable in faces_opacity."""
+    blended (tet: no ray composited) -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.
+    pixel_weight [B,H,W] multiplies every pixel's weights before the sum (a per-pixel error, say: its attribution to the faces);
+    over all faces that sums to sum(pixel_weight * (1 - T)).  Constants: the faces and their order.
+    Differentiable in faces_opacity and pixel_weight."""
     w = blend_weights(frag, faces_opacity)
+    if pixel_weight is not None:
+        w = w * pixel_weight.unsqueeze(1).to(w.dtype)
     B = w.shape[0]
     idx = frag.pix_to_face.clamp(min=0).long().reshape(B, -1)  # (empty slots add their weight 0 to face 0)
     return th.zeros(B, F, dtype=w.dtype, device=w.device).scatter_add(1, idx, w.reshape(B, -1))
+
+
+def face_coverage(frag, faces_opacity: th.Tensor, F: int) -> Tuple[th.Tensor, th.Tensor]:
+    """What pruning reads beside face_visibility, from the same lists: (max_weight [B,F], the largest blend weight any pixel
+    gave the face, 0 for a face in no list; pixels [B,F] int64, the number of list slots that hold the face, whatever their
+    weight).  Not differentiable.  Constants: the faces and their order."""
+    w = blend_weights(frag, faces_opacity).detach()
+    B = w.shape[0]
+    used = (frag.pix_to_face >= 0).reshape(B, -1)
+    idx = frag.pix_to_face.clamp(min=0).long().reshape(B, -1)
+    w = th.where(used, w.reshape(B, -1), th.zeros((), dtype=w.dtype, device=w.device))
+    max_weight = th.zeros(B, F, dtype=w.dtype, device=w.device).scatter_reduce(1, idx, w, "amax", include_self=True)
+    pixels = th.zeros(B, F, dtype=th.int64, device=w.device).scatter_add(1, idx, used.long())
+    return max_weight, pixels
 
 
 class _CompositeFn(th.autograd.Function):
@@ -134,7 +154,8 @@ class _CompositeFn(th.autograd.Function):
 
 
 # torch path -> (the flag of `_C` that announces its fused pair of calls, what they fuse)
-_FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_texture": ("SUPPORTS_FRAGMENT_TEXTURE", "texture")}
+_FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_texture": ("SUPPORTS_FRAGMENT_TEXTURE", "texture"),
+          "face_visibility": ("SUPPORTS_FRAGMENT_VISIBILITY", "face-visibility")}
 
 
 def _fused_kernels(torch_path: str):
@@ -310,3 +331,67 @@ def composite_texture_fused(frag, faces: th.Tensor, faces_opacity: th.Tensor, ve
                               uv_faces, own_shapes, [("vert_uvs", vert_uvs), ("texture", texture)])
     corners = faces if uv_faces is None else uv_faces
     return _CompositeTextureFn.apply(face, bary, corners.to(th.int32), faces_opacity, vert_uvs, texture, face_scale, WRAPS.index(wrap))
+
+
+class _FaceVisibilityFn(th.autograd.Function):
+    """face_visibility_fused's one Function over _C.face_visibility / _C.face_visibility_backward.  Arguments: pix_to_face,
+    faces_opacity, pixel_weight (a tensor or None), coverage (bool) -> vis, or (vis, max_weight, pixels)."""
+
+    @staticmethod
+    def forward(ctx, face, faces_opacity, pixel_weight, coverage):
+        vis, max_weight, pixels = _fused_kernels("face_visibility").face_visibility(face, faces_opacity, pixel_weight, coverage)
+        ctx.save_for_backward(face, faces_opacity, *(() if pixel_weight is None else (pixel_weight,)))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
+        if not coverage:
+            return vis
+        ctx.mark_non_differentiable(max_weight, pixels)
+        return vis, max_weight, pixels
+
+    @staticmethod
+    def backward(ctx, grad_vis, *_):
+        face, faces_opacity, *weight = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (face, faces_opacity, pixel_weight, coverage)
+        need = (need[1], bool(weight) and need[2])
+        if grad_vis is None or not any(need):
+            return (None,) * 4
+        d_op, d_weight = _fused_kernels("face_visibility").face_visibility_backward(
+            face, faces_opacity, weight[0] if weight else None, grad_vis.contiguous(), need)
+        return None, d_op, d_weight, None
+
+
+def face_visibility_fused(frag, faces_opacity: th.Tensor, F: int, pixel_weight: Optional[th.Tensor] = None, *, coverage: bool = False):
+    """face_visibility(...) as one fused HIP kernel, and one for its backward, without the [B,K+1,H,W] transmittances and the
+    scatter_add of B K H W weights: vis [B,F], differentiable in faces_opacity and pixel_weight [B,H,W] (None: 1), each gradient
+    computed only when autograd asks for it.  coverage=True: (vis, max_weight [B,F], pixels [B,F] int32) -- face_coverage's two
+    from the same walk, not differentiable.  A slot whose face id lies outside [0, F) is empty, wherever it sits in the list;
+    frag.count and frag.bary are not read (bary may be None).  K <= 32, faces_opacity [F] (ValueError); F == 0 gives empty
+    [B,0] tensors.  HIP float32 tensors only (pix_to_face int32): anything else is a TypeError -- face_visibility (and
+    face_coverage) is the torch path for it; nothing falls back silently."""
+    name = "face_visibility_fused"
+    torch_path = "fragments.face_visibility (and face_coverage) is the torch path for anything else"
+    _fused_kernels("face_visibility")
+    face = frag.pix_to_face
+    if face.dim() != 4:
+        raise ValueError(f"{name}: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
+    B, K, H, W = face.shape
+    if not 1 <= K <= 32:
+        raise ValueError(f"{name}: K must be in 1..32, got {K}")
+    if isinstance(F, bool) or not isinstance(F, int) or F < 0:
+        raise ValueError(f"{name}: F must be a non-negative int, got {F!r}")
+    if tuple(faces_opacity.shape) != (F,):
+        raise ValueError(f"{name}: faces_opacity must be [F] = {(F,)}, got {tuple(faces_opacity.shape)}")
+    if pixel_weight is not None and tuple(pixel_weight.shape) != (B, H, W):
+        raise ValueError(f"{name}: pixel_weight must be [B,H,W] = {(B, H, W)}, got {tuple(pixel_weight.shape)}")
+    floats = [("faces_opacity", faces_opacity)] + ([] if pixel_weight is None else [("pixel_weight", pixel_weight)])
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if face.dtype != th.int32:
+        raise TypeError(f"{name}: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
+    for n, t in [("frag.pix_to_face", face)] + floats:
+        if not t.is_cuda or t.device != face.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    if F == 0:  # nothing to launch
+        vis = faces_opacity.new_zeros(B, 0)
+        return (vis, faces_opacity.new_zeros(B, 0), th.zeros(B, 0, dtype=th.int32, device=face.device)) if coverage else vis
+    return _FaceVisibilityFn.apply(face, faces_opacity, pixel_weight, bool(coverage))
