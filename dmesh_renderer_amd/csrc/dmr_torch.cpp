@@ -42,6 +42,11 @@
 //   face_visibility(face, faces_opacity, pixel_weight=None, coverage=False) -> (vis [B,F], max_weight [B,F] | None, pixels i32 [B,F] | None) and
 //   face_visibility_backward(face, faces_opacity, pixel_weight, grad_vis, need=(opacity, pixel_weight)) -> those two gradients or None:
 //                            fragments.face_visibility_fused, over include/dmesh_renderer_amd_visibility.h (SUPPORTS_FRAGMENT_VISIBILITY)
+//   interpolate_fragments(face, bary, faces, vert_attrs) -> out [B,K,C,H,W] and
+//   interpolate_fragments_backward(..., grad_out, need=(attrs, bary)) -> those two gradients or None; composite_values(face,
+//   faces_opacity, values, face_scale=None) -> (image, T) and composite_values_backward(..., grad_image, grad_T,
+//   need=(opacity, values, scale)) -> those three or None: fragments.interpolate_fused / composite_values_fused, over
+//                            include/dmesh_renderer_amd_deferred.h (SUPPORTS_FRAGMENT_DEFERRED)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -63,6 +68,7 @@
 #include "../../include/dmesh_renderer_amd_shade.h"
 #include "../../include/dmesh_renderer_amd_texture.h"
 #include "../../include/dmesh_renderer_amd_visibility.h"
+#include "../../include/dmesh_renderer_amd_deferred.h"
 
 namespace {
 
@@ -97,6 +103,11 @@ struct Abi {
     // dmesh_renderer_amd_visibility.h: optional too (SUPPORTS_FRAGMENT_VISIBILITY)
     decltype(&dmr_face_visibility) face_visibility = nullptr;
     decltype(&dmr_face_visibility_backward) face_visibility_backward = nullptr;
+    // dmesh_renderer_amd_deferred.h: optional too (SUPPORTS_FRAGMENT_DEFERRED), all four or none
+    decltype(&dmr_interpolate_fragments) interpolate_fragments = nullptr;
+    decltype(&dmr_interpolate_fragments_backward) interpolate_fragments_backward = nullptr;
+    decltype(&dmr_composite_values) composite_values = nullptr;
+    decltype(&dmr_composite_values_backward) composite_values_backward = nullptr;
 };
 
 Abi g_abi;
@@ -147,6 +158,15 @@ void load_abi() {
     g_abi.face_visibility_backward =
         reinterpret_cast<decltype(g_abi.face_visibility_backward)>(dlsym(g_abi.handle, "dmr_face_visibility_backward"));
     if (!g_abi.face_visibility || !g_abi.face_visibility_backward) g_abi.face_visibility = nullptr, g_abi.face_visibility_backward = nullptr;
+    g_abi.interpolate_fragments = reinterpret_cast<decltype(g_abi.interpolate_fragments)>(dlsym(g_abi.handle, "dmr_interpolate_fragments"));
+    g_abi.interpolate_fragments_backward =
+        reinterpret_cast<decltype(g_abi.interpolate_fragments_backward)>(dlsym(g_abi.handle, "dmr_interpolate_fragments_backward"));
+    g_abi.composite_values = reinterpret_cast<decltype(g_abi.composite_values)>(dlsym(g_abi.handle, "dmr_composite_values"));
+    g_abi.composite_values_backward =
+        reinterpret_cast<decltype(g_abi.composite_values_backward)>(dlsym(g_abi.handle, "dmr_composite_values_backward"));
+    if (!g_abi.interpolate_fragments || !g_abi.interpolate_fragments_backward || !g_abi.composite_values || !g_abi.composite_values_backward)
+        g_abi.interpolate_fragments = nullptr, g_abi.interpolate_fragments_backward = nullptr, g_abi.composite_values = nullptr,
+        g_abi.composite_values_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -845,6 +865,124 @@ py::tuple face_visibility_backward(In face, In faces_opacity, const std::optiona
     return py::make_tuple(or_none(d_op), or_none(d_pw));
 }
 
+// -- interpolate_fragments / composite_values: the two ends of a deferred shader (dmesh_renderer_amd_deferred.h,
+// fragments.interpolate_fused / composite_values_fused).  Neither fits list_dims -- one has no opacities, the other no
+// barycentrics and no corner table -- so their checks are their own, in the order of fragments.py's: the lists' shapes, K, the
+// unit's shapes, C, one device, dtypes.  ValuesArgs is a ListArgs (bary and corners undefined) for upstreams().
+struct InterpArgs {
+    at::Tensor face, bary, faces, attrs;
+    int64_t B = 0, K = 0, H = 0, W = 0, F = 0, P = 0, C = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+};
+
+InterpArgs interp_args(In face, In bary, In faces, In vert_attrs) {
+    if (!g_abi.interpolate_fragments)
+        err(g_abi.path + " does not export dmr_interpolate_fragments: rebuild it (python -m dmesh_renderer_amd.build)");
+    InterpArgs a;
+    a.dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+    if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
+        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
+    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
+    a.F = faces.size(0);
+    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
+    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1);
+    if (a.K < 1 || a.K > 32) err("interpolate_fragments: K must be in 1..32, got " + std::to_string(a.K));
+    if (a.C < 1 || a.C > 256) err("interpolate_fragments: C must be in 1..256, got " + std::to_string(a.C));
+    if (a.B < 1 || a.H < 1 || a.W < 1) err("interpolate_fragments: empty fragment lists");
+    if (bary.device() != a.dev) err("bary must be on the device of pix_to_face");
+    if (faces.device() != a.dev) err("faces must be on the device of pix_to_face");
+    if (vert_attrs.device() != a.dev) err("vert_attrs must be on the device of pix_to_face");
+    a.face = i32(face, "pix_to_face"); a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(vert_attrs, "vert_attrs");
+    return a;
+}
+
+// -> out [B,K,C,H,W]
+at::Tensor interpolate_fragments(In face, In bary, In faces, In vert_attrs) {
+    const InterpArgs a = interp_args(face, bary, faces, vert_attrs);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor out = at::empty({a.B, a.K, a.C, a.H, a.W}, f32_on(a.dev));
+    if (g_abi.interpolate_fragments(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                    mptr<const int32_t>(a.faces), mptr<const float>(a.attrs), mptr<float>(out), a.stream()))
+        raise_lib();
+    return out;
+}
+
+// need = (vert_attrs, bary) -> those two gradients, None where not asked for; grad_out [B,K,C,H,W]
+py::tuple interpolate_fragments_backward(In face, In bary, In faces, In vert_attrs, In grad_out, const std::array<bool, 2>& need) {
+    const InterpArgs a = interp_args(face, bary, faces, vert_attrs);
+    c10::DeviceGuard guard(a.dev);
+    if (grad_out.dim() != 5 || grad_out.size(0) != a.B || grad_out.size(1) != a.K || grad_out.size(2) != a.C || grad_out.size(3) != a.H ||
+        grad_out.size(4) != a.W || grad_out.device() != a.dev)
+        err("grad_out must have dimensions (B, K, C, H, W) on the device of pix_to_face");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor d_attrs = grad_if(need[0], {a.P, a.C}, a.dev), d_bary = grad_if(need[1], {a.B, a.K, 2, a.H, a.W}, a.dev);
+    if (g_abi.interpolate_fragments_backward(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                             mptr<const int32_t>(a.faces), mptr<const float>(a.attrs), mptr<const float>(go),
+                                             out_ptr(d_attrs), out_ptr(d_bary), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_attrs), or_none(d_bary));
+}
+
+struct ValuesArgs : ListArgs { at::Tensor values; int64_t C = 0; };
+
+ValuesArgs values_args(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    if (!g_abi.composite_values)
+        err(g_abi.path + " does not export dmr_composite_values: rebuild it (python -m dmesh_renderer_amd.build)");
+    ValuesArgs a;
+    a.call = "composite_values"; a.corner_name = "";
+    a.dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
+    a.F = faces_opacity.size(0);
+    if (values.dim() != 5 || values.size(0) != a.B || values.size(1) != a.K || values.size(3) != a.H || values.size(4) != a.W)
+        err("values must have dimensions (B, K, C, H, W) of pix_to_face's B, K, H, W");
+    a.C = values.size(2);
+    list_k(a);
+    if (a.C < 1 || a.C > 256) err("composite_values: C must be in 1..256, got " + std::to_string(a.C));
+    list_not_empty(a);
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
+        err("face_scale must have dimensions (B, num_faces)");
+    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
+    if (values.device() != a.dev) err("values must be on the device of pix_to_face");
+    if (face_scale && face_scale->device() != a.dev) err("face_scale must be on the device of pix_to_face");
+    a.face = i32(face, "pix_to_face"); a.opacity = f32(faces_opacity, "faces_opacity"); a.values = f32(values, "values");
+    if (face_scale) a.scale = f32(*face_scale, "face_scale");
+    return a;
+}
+
+// -> (image [B,C,H,W], T [B,1,H,W])
+std::tuple<at::Tensor, at::Tensor> composite_values(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    const ValuesArgs a = values_args(face, faces_opacity, values, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    if (g_abi.composite_values(a.B, a.K, a.H, a.W, a.F, a.C, mptr<const int32_t>(a.face), in_ptr(a.opacity), mptr<const float>(a.values),
+                               a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
+        raise_lib();
+    return {image, T};
+}
+
+// need = (faces_opacity, values, face_scale) -> those three gradients, None where not asked for; grad_image [B,C,H,W] /
+// grad_T [B,1,H,W]: None = zero
+py::tuple composite_values_backward(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale,
+                                    const std::optional<at::Tensor>& grad_image, const std::optional<at::Tensor>& grad_T,
+                                    const std::array<bool, 3>& need) {
+    const ValuesArgs a = values_args(face, faces_opacity, values, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    if (need[2] && !face_scale) err("composite_values_backward: the gradient of face_scale without face_scale");
+    const auto [gi, gt] = upstreams(a, a.C, grad_image, grad_T);
+    at::Tensor d_op = grad_if(need[0], {a.F}, a.dev), d_values = grad_if(need[1], {a.B, a.K, a.C, a.H, a.W}, a.dev);
+    at::Tensor d_scale = grad_if(need[2], {a.B, a.F}, a.dev);
+    if (g_abi.composite_values_backward(a.B, a.K, a.H, a.W, a.F, a.C, mptr<const int32_t>(a.face), in_ptr(a.opacity),
+                                        mptr<const float>(a.values), a.scale_ptr(), in_ptr(gi), in_ptr(gt), out_ptr(d_op),
+                                        out_ptr(d_values), out_ptr(d_scale), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -905,6 +1043,12 @@ PYBIND11_MODULE(_C, m) {
           py::arg("coverage") = false);
     m.def("face_visibility_backward", &face_visibility_backward, py::arg("face"), py::arg("faces_opacity"), py::arg("pixel_weight"),
           py::arg("grad_vis"), py::arg("need") = std::array<bool, 2>{true, true});
+    m.def("interpolate_fragments", &interpolate_fragments, py::arg("face"), py::arg("bary"), py::arg("faces"), py::arg("vert_attrs"));
+    m.def("interpolate_fragments_backward", &interpolate_fragments_backward, py::arg("face"), py::arg("bary"), py::arg("faces"),
+          py::arg("vert_attrs"), py::arg("grad_out"), py::arg("need") = std::array<bool, 2>{true, true});
+    m.def("composite_values", &composite_values, py::arg("face"), py::arg("faces_opacity"), py::arg("values"), py::arg("face_scale") = py::none());
+    m.def("composite_values_backward", &composite_values_backward, py::arg("face"), py::arg("faces_opacity"), py::arg("values"),
+          py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"), py::arg("need") = std::array<bool, 3>{true, true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -933,6 +1077,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_TEXTURE") = g_abi.composite_texture != nullptr;
     // fragments.face_visibility_fused; False: the loaded library predates dmesh_renderer_amd_visibility.h
     m.attr("SUPPORTS_FRAGMENT_VISIBILITY") = g_abi.face_visibility != nullptr;
+    // fragments.interpolate_fused / composite_values_fused; False: the loaded library predates dmesh_renderer_amd_deferred.h
+    m.attr("SUPPORTS_FRAGMENT_DEFERRED") = g_abi.interpolate_fragments != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

@@ -7,6 +7,10 @@ is composite_texture (a bilinear texture sampled at per-corner UVs, then blended
 face_visibility_fused, which is face_visibility (per-face sums of the blend weights, optionally weighted per pixel) and
 face_coverage (per face the largest weight and the number of list slots that hold it) from one walk of the lists as a third
 pair (csrc/dmr_visibility.hip): what a mesh optimiser reads to prune faces and to attribute per-pixel error to them.
+interpolate_fused and composite_values_fused (csrc/dmr_interp.hip) are the two ENDS of a shader as kernels of their own, for a
+deferred shader that fits none of the fused shapes: interpolate_fused is interpolate, the caller's own torch code then runs on
+every fragment (an MLP, a lighting model), and composite_values_fused blends the per-slot results front to back
+(composite_values is its torch model): composite_values(frag, o, interpolate(frag, faces, A), s) == composite(frag, faces, o, A, s).
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -40,7 +44,8 @@ from typing import Optional, Tuple
 import torch as th
 
 __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
-           "composite_texture_fused", "face_coverage", "face_visibility_fused"]
+           "composite_texture_fused", "face_coverage", "face_visibility_fused", "composite_values", "interpolate_fused",
+           "composite_values_fused"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -101,6 +106,24 @@ def composite(frag, faces: th.Tensor, faces_opacity: th.Tensor, vert_attrs: th.T
     return (w.unsqueeze(2).to(a.dtype) * a).sum(1), t[:, -1:]
 
 
+def composite_values(frag, faces_opacity: th.Tensor, values: th.Tensor, face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """Front-to-back blend of per-slot values the caller computed, values [B,K,C,H,W] (the layout interpolate returns):
+    (sum_k w_k s_k values_k [B,C,H,W], T = prod_k (1 - o_k) [B,1,H,W]) with w_k = blend_weights(...), s_k = face_scale[b, face_k]
+    (face_scale [B,F]; None: 1) -- composite with the interpolation taken out:
+        composite_values(frag, o, interpolate(frag, faces, A), s) == composite(frag, faces, o, A, s).
+    The value of an empty slot is not read (masked, so a NaN there does not reach the image).  Any device, any float dtype.
+    Constants: the faces and their order.  Differentiable in faces_opacity, values and face_scale."""
+    used, o = _opacity_slots(frag, faces_opacity)
+    t = _transmittance(o)
+    w = o * t[:, :-1]
+    if face_scale is not None:
+        idx = frag.pix_to_face.clamp(min=0).long()
+        B = idx.shape[0]
+        w = w * th.gather(face_scale, 1, idx.reshape(B, -1)).reshape(idx.shape).to(w.dtype)
+    v = th.where(used.unsqueeze(2), values, th.zeros((), dtype=values.dtype, device=values.device))
+    return (w.unsqueeze(2).to(v.dtype) * v).sum(1), t[:, -1:]
+
+
 def face_visibility(frag, faces_opacity: th.Tensor, F: int, pixel_weight: Optional[th.Tensor] = None) -> th.Tensor:
     """Sum of the blend weights every face received over a view's pixels, [B,F] (one scatter_add): 0 for a face no pixel
     blended (tet: no ray composited) -- the faces to prune.  Over all faces it sums to H * W - sum(T) per view.
@@ -155,16 +178,18 @@ class _CompositeFn(th.autograd.Function):
 
 # torch path -> (the flag of `_C` that announces its fused pair of calls, what they fuse)
 _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_texture": ("SUPPORTS_FRAGMENT_TEXTURE", "texture"),
-          "face_visibility": ("SUPPORTS_FRAGMENT_VISIBILITY", "face-visibility")}
+          "face_visibility": ("SUPPORTS_FRAGMENT_VISIBILITY", "face-visibility"),
+          "interpolate": ("SUPPORTS_FRAGMENT_DEFERRED", "fragment", "interpolation"),
+          "composite_values": ("SUPPORTS_FRAGMENT_DEFERRED", "per-slot value")}  # (a third entry: what stands for "compositing" in the message)
 
 
 def _fused_kernels(torch_path: str):
     """`_C` as the package holds it at call time (tests swap it), with the fused calls of `torch_path` -- or a TypeError."""
     from . import _impl
     c = _impl(None)
-    flag, what = _FUSED[torch_path]
+    flag, what, *noun = _FUSED[torch_path]
     if not getattr(c, flag, False):
-        raise TypeError(f"{torch_path}_fused: the loaded libdmesh_renderer_hip.so / _C has no fused {what} compositing: rebuild "
+        raise TypeError(f"{torch_path}_fused: the loaded libdmesh_renderer_hip.so / _C has no fused {what} {noun[0] if noun else 'compositing'}: rebuild "
                         f"(python -m dmesh_renderer_amd.build); fragments.{torch_path} is the torch path")
     return c
 
@@ -395,3 +420,123 @@ def face_visibility_fused(frag, faces_opacity: th.Tensor, F: int, pixel_weight: 
         vis = faces_opacity.new_zeros(B, 0)
         return (vis, faces_opacity.new_zeros(B, 0), th.zeros(B, 0, dtype=th.int32, device=face.device)) if coverage else vis
     return _FaceVisibilityFn.apply(face, faces_opacity, pixel_weight, bool(coverage))
+
+
+class _InterpolateFn(th.autograd.Function):
+    """interpolate_fused's one Function over _C.interpolate_fragments / _C.interpolate_fragments_backward.  Arguments: pix_to_face,
+    bary, faces, vert_attrs."""
+
+    @staticmethod
+    def forward(ctx, face, bary, faces, vert_attrs):
+        out = _fused_kernels("interpolate").interpolate_fragments(face, bary, faces, vert_attrs)
+        ctx.save_for_backward(face, bary, faces, vert_attrs)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        face, bary, faces, vert_attrs = ctx.saved_tensors
+        need = (ctx.needs_input_grad[3], ctx.needs_input_grad[1])  # (vert_attrs, bary)
+        if grad_out is None or not any(need):
+            return (None,) * 4
+        d_attrs, d_bary = _fused_kernels("interpolate").interpolate_fragments_backward(face, bary, faces, vert_attrs, grad_out.contiguous(), need)
+        return None, d_bary, None, d_attrs
+
+
+class _CompositeValuesFn(th.autograd.Function):
+    """composite_values_fused's one Function over _C.composite_values / _C.composite_values_backward.  Arguments: pix_to_face,
+    faces_opacity, values, face_scale (a tensor or None)."""
+
+    @staticmethod
+    def forward(ctx, face, faces_opacity, values, face_scale):
+        image, t = _fused_kernels("composite_values").composite_values(face, faces_opacity, values, face_scale)
+        ctx.save_for_backward(face, faces_opacity, values, *(() if face_scale is None else (face_scale,)))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
+        return image, t
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_t):
+        face, faces_opacity, values, *scale = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (face, faces_opacity, values, face_scale)
+        need = (need[1], need[2], bool(scale) and need[3])
+        if (grad_image is None and grad_t is None) or not any(need):
+            return (None,) * 4
+        d_op, d_values, d_scale = _fused_kernels("composite_values").composite_values_backward(
+            face, faces_opacity, values, scale[0] if scale else None,
+            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
+        return None, d_op, d_values, d_scale
+
+
+def _check_lists(name: str, frag, bary_wanted: bool):
+    """frag.pix_to_face [B,K,H,W] with K in 1..32 (and frag.bary [B,K,2,H,W]) -> B, K, H, W, or a ValueError."""
+    face = frag.pix_to_face
+    if face.dim() != 4:
+        raise ValueError(f"{name}: frag.pix_to_face must be [B,K,H,W], got {tuple(face.shape)}")
+    B, K, H, W = face.shape
+    if bary_wanted and (frag.bary is None or tuple(frag.bary.shape) != (B, K, 2, H, W)):
+        raise ValueError(f"{name}: frag.bary must be [B,K,2,H,W] = {(B, K, 2, H, W)}, got {None if frag.bary is None else tuple(frag.bary.shape)}")
+    if not 1 <= K <= 32:
+        raise ValueError(f"{name}: K must be in 1..32, got {K}")
+    return B, K, H, W
+
+
+def _check_tensors(name: str, torch_path: str, face, ints, floats):
+    """float32 for `floats`, int32 lists, integer `ints` ([(name, tensor)]), one HIP device for all -- or a TypeError."""
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if face.dtype != th.int32:
+        raise TypeError(f"{name}: frag.pix_to_face must be int32, got {face.dtype}; {torch_path}")
+    for n, t in ints:
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == th.bool:
+            raise TypeError(f"{name}: {n} must be an integer tensor, got {t.dtype}; {torch_path}")
+    for n, t in [("frag.pix_to_face", face)] + ints + floats:
+        if not t.is_cuda or t.device != face.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+
+
+def interpolate_fused(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
+    """interpolate(...) as one HIP kernel, and one for its backward: the same [B,K,C,H,W], 0 in empty slots, without the
+    [B,K,H,W,3,C] gather interpolate keeps for autograd and without its index_put backward.  Gradients to vert_attrs and (with the
+    renderer's fragment_grads) frag.bary, each computed only when autograd asks for it.  A slot whose face id lies outside [0, F)
+    is empty, wherever it sits in the list, and a face whose row of `faces` holds a vertex index outside [0, P) gives 0;
+    frag.count is not read.  K <= 32, 1 <= C <= 256 (ValueError).  HIP float32 tensors only (pix_to_face int32; faces of another
+    integer dtype are cast): anything else is a TypeError -- interpolate is the torch path for it; nothing falls back silently."""
+    name, torch_path = "interpolate_fused", "fragments.interpolate is the torch path for anything else"
+    _fused_kernels("interpolate")
+    _check_lists(name, frag, True)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    if vert_attrs.dim() != 2:
+        raise ValueError(f"{name}: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
+    if not 1 <= vert_attrs.shape[1] <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {vert_attrs.shape[1]}")
+    _check_tensors(name, torch_path, frag.pix_to_face, [("faces", faces)], [("frag.bary", frag.bary), ("vert_attrs", vert_attrs)])
+    return _InterpolateFn.apply(frag.pix_to_face, frag.bary, faces.to(th.int32), vert_attrs)
+
+
+def composite_values_fused(frag, faces_opacity: th.Tensor, values: th.Tensor,
+                           face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """composite_values(...) as one HIP kernel, and one for its backward: the same (sum_k w_k s_k values_k [B,C,H,W], T [B,1,H,W]),
+    the same constants, gradients to faces_opacity, values and face_scale -- each computed only when autograd asks for it --
+    without the index_put backward of faces_opacity[face].  values is [B,K,C,H,W] (made contiguous if it is not).  A slot whose
+    face id lies outside [0, F) is empty, wherever it sits in the list: its value is NOT READ (a NaN there reaches nothing) and
+    its gradient is an exact 0.  A used slot of weight 0 (opacity 0, or behind a face of opacity 1) may skip its load: what a
+    non-finite value there computes is unspecified.  frag.bary and frag.count are not read (bary may be None).  K <= 32,
+    1 <= C <= 256 (ValueError).  HIP float32 tensors only (pix_to_face int32): anything else is a TypeError -- composite_values is
+    the torch path for it; nothing falls back silently."""
+    name, torch_path = "composite_values_fused", "fragments.composite_values is the torch path for anything else"
+    _fused_kernels("composite_values")
+    B, K, H, W = _check_lists(name, frag, False)
+    if faces_opacity.dim() != 1:
+        raise ValueError(f"{name}: faces_opacity must be [F], got {tuple(faces_opacity.shape)}")
+    F = faces_opacity.shape[0]
+    if values.dim() != 5 or tuple(values.shape[:2]) != (B, K) or tuple(values.shape[3:]) != (H, W):
+        raise ValueError(f"{name}: values must be [B,K,C,H,W] = {(B, K, 'C', H, W)}, got {tuple(values.shape)}")
+    if not 1 <= values.shape[2] <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {values.shape[2]}")
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
+    _check_tensors(name, torch_path, frag.pix_to_face, [], floats)
+    return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale)
