@@ -20,6 +20,7 @@
 
 #include "dmr_kernels.hpp"
 #include "dmr_placement_key.hpp"
+#include "dmr_tile_order.hpp"
 
 namespace {
 
@@ -347,6 +348,19 @@ int build_placement(const SizeKey& key, const Dims& d, uint64_t R, const ImageSt
         DMR_HIP(hipDeviceSynchronize());
     }
     dmr::launch_build_placement(d.ntiles, is.tile_count, is.tile_order, p.start, p.order, st);
+    // The order placed calls take their tiles in: not the exact path's "longest list first" over the whole frame but the
+    // XCD-local one of dmr_tile_order.hpp, from the counts and the blended pairs this call's forward left (host C++: 32 KB
+    // each way, once per placement, behind a wait this function needs anyway).  Busy tiles need not come first in it: a
+    // placed call's capacity is at least SEG_SLACK entries per tile, so mask_first_slots(capacity, ntiles) == ntiles and
+    // every position is a first-chunk mask slot (dmr_kernels.hpp, ImageState::mask_offset).
+    static_assert(dmr::SEG_SLACK >= 1, "a placed call's list capacity covers one entry per tile");
+    const size_t n = (size_t)d.ntiles;
+    std::vector<uint32_t> host(3 * n);
+    DMR_HIP(hipMemcpyAsync(host.data(), is.tile_count, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    DMR_HIP(hipMemcpyAsync(host.data() + n, is.tile_hits, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    DMR_HIP(hipStreamSynchronize(st));
+    dmr::tile_order(d.ntiles / (d.gx * d.gy), d.gx, d.gy,host.data(), host.data() + n, host.data() + 2 * n);
+    DMR_HIP(hipMemcpyAsync(p.order, host.data() + 2 * n, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
     DMR_HIP(hipStreamSynchronize(st));
     p.capacity = capacity; p.built_from = R; p.valid = true;
     std::lock_guard<std::mutex> lk(g_size_mu);

@@ -506,8 +506,9 @@ k_scan_tiles(int n, const uint32_t* __restrict__ tile_count, uint32_t* __restric
 
 // The placement k_bin_faces speculates on, built from the exact counts of a call that went through set-up -> scan ->
 // scatter: tile t gets room for its count + 25 % + SEG_SLACK entries (so that a tile that was empty can receive a few),
-// segments in tile order, start[n] = the padded total; the order is that call's (longest list first -- every tile has a
-// segment, so every tile's position is a first-chunk mask slot).  One workgroup, n <= SCAN_SLAB.
+// segments in tile order, start[n] = the padded total; the order is that call's (longest list first), which
+// build_placement (dmr_api.hip) then replaces by the XCD-local one of dmr_tile_order.hpp -- every tile has a segment, so
+// every tile's position is a first-chunk mask slot whatever the order.  One workgroup, n <= SCAN_SLAB.
 __global__ void __launch_bounds__(1024)
 k_build_placement(int n, const uint32_t* __restrict__ tile_count, const uint32_t* __restrict__ tile_order,
                   uint32_t* __restrict__ start, uint32_t* __restrict__ order) {

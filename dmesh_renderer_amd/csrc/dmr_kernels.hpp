@@ -117,7 +117,8 @@ __host__ __device__ inline uint32_t list_end(const uint32_t* tile_offset, const 
     return e > tile_offset[tile + 1] ? tile_offset[tile] : e;
 }
 // Speculative placement: what k_project_verts copies into the call's image buffer (start: ntiles + 1 segment starts in tile
-// order, order: the tiles longest list first; both persistent, dmr_api.hip).  start == null: nothing.
+// order, order: the tiles in the placed order of dmr_tile_order.hpp -- blocks of neighbouring tiles per XCD class, longest
+// list first inside a class; both persistent, dmr_api.hip).  start == null: nothing.
 // (the launcher fills in the image buffer's three arrays and the tile count)
 struct SegInit { const uint32_t* start; const uint32_t* order; uint32_t* tile_offset; uint32_t* tile_cursor; uint32_t* tile_order; uint32_t ntiles; };
 constexpr SegInit NO_SEGMENTS{nullptr, nullptr, nullptr, nullptr, nullptr, 0u};

@@ -3,6 +3,9 @@
 Runs one forward + backward of a BASELINE config on the ABLATION build (`python -m dmesh_renderer_amd.build --ablation`)
 with DMR_ABLATE bit 4096: lane 0 of every wave of the first 3072 workgroups (tile_order: the longest lists) writes s_memtime
 at every phase boundary of its first 6 chunks (dmr_tri.hip, DMR_STAMP).  The product library has no such code.
+"The longest lists" holds for a call that went through the exact path (the first call of a view configuration).  On the placed
+path (every later call: dmr_tile_order.hpp) the first 3072 workgroups are no longer simply the longest lists: positions x,
+x + 8, ... hold the tiles of XCD class x, longest first inside the class, and a class's empty tiles start where its busy ones end.
 
     python scripts/phase_times.py [--config C4] [--band R0 R1] [--json out.json]
 
