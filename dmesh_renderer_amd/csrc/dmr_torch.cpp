@@ -47,6 +47,12 @@
 //   faces_opacity, values, face_scale=None) -> (image, T) and composite_values_backward(..., grad_image, grad_T,
 //   need=(opacity, values, scale)) -> those three or None: fragments.interpolate_fused / composite_values_fused, over
 //                            include/dmesh_renderer_amd_deferred.h (SUPPORTS_FRAGMENT_DEFERRED)
+//   pack_slots(face, F, capacity) -> (row [B,K,H,W] int32, n_used [1] int32); interpolate_packed(face, bary, row, n_used, faces,
+//   vert_attrs, N) -> out [N,C] and interpolate_packed_backward(..., grad_out, need=(attrs, bary)); composite_values_packed(face,
+//   row, faces_opacity, values [N,C], face_scale=None) -> (image, T) and composite_values_packed_backward(face, row, n_used, ...,
+//   grad_image, grad_T, need=(opacity, values, scale)): the packed, channel-last form of the four above
+//   (fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused), over
+//                            include/dmesh_renderer_amd_packed.h (SUPPORTS_FRAGMENT_PACKED)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -69,6 +75,7 @@
 #include "../../include/dmesh_renderer_amd_texture.h"
 #include "../../include/dmesh_renderer_amd_visibility.h"
 #include "../../include/dmesh_renderer_amd_deferred.h"
+#include "../../include/dmesh_renderer_amd_packed.h"
 
 namespace {
 
@@ -108,6 +115,12 @@ struct Abi {
     decltype(&dmr_interpolate_fragments_backward) interpolate_fragments_backward = nullptr;
     decltype(&dmr_composite_values) composite_values = nullptr;
     decltype(&dmr_composite_values_backward) composite_values_backward = nullptr;
+    // dmesh_renderer_amd_packed.h: optional too (SUPPORTS_FRAGMENT_PACKED), all five or none
+    decltype(&dmr_pack_slots) pack_slots = nullptr;
+    decltype(&dmr_interpolate_packed) interpolate_packed = nullptr;
+    decltype(&dmr_interpolate_packed_backward) interpolate_packed_backward = nullptr;
+    decltype(&dmr_composite_values_packed) composite_values_packed = nullptr;
+    decltype(&dmr_composite_values_packed_backward) composite_values_packed_backward = nullptr;
 };
 
 Abi g_abi;
@@ -167,6 +180,17 @@ void load_abi() {
     if (!g_abi.interpolate_fragments || !g_abi.interpolate_fragments_backward || !g_abi.composite_values || !g_abi.composite_values_backward)
         g_abi.interpolate_fragments = nullptr, g_abi.interpolate_fragments_backward = nullptr, g_abi.composite_values = nullptr,
         g_abi.composite_values_backward = nullptr;
+    g_abi.pack_slots = reinterpret_cast<decltype(g_abi.pack_slots)>(dlsym(g_abi.handle, "dmr_pack_slots"));
+    g_abi.interpolate_packed = reinterpret_cast<decltype(g_abi.interpolate_packed)>(dlsym(g_abi.handle, "dmr_interpolate_packed"));
+    g_abi.interpolate_packed_backward =
+        reinterpret_cast<decltype(g_abi.interpolate_packed_backward)>(dlsym(g_abi.handle, "dmr_interpolate_packed_backward"));
+    g_abi.composite_values_packed = reinterpret_cast<decltype(g_abi.composite_values_packed)>(dlsym(g_abi.handle, "dmr_composite_values_packed"));
+    g_abi.composite_values_packed_backward =
+        reinterpret_cast<decltype(g_abi.composite_values_packed_backward)>(dlsym(g_abi.handle, "dmr_composite_values_packed_backward"));
+    if (!g_abi.pack_slots || !g_abi.interpolate_packed || !g_abi.interpolate_packed_backward || !g_abi.composite_values_packed ||
+        !g_abi.composite_values_packed_backward)
+        g_abi.pack_slots = nullptr, g_abi.interpolate_packed = nullptr, g_abi.interpolate_packed_backward = nullptr,
+        g_abi.composite_values_packed = nullptr, g_abi.composite_values_packed_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -983,6 +1007,153 @@ py::tuple composite_values_backward(In face, In faces_opacity, In values, const 
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
+// -- pack_slots / interpolate_packed / composite_values_packed: the deferred shader's two ends on packed, channel-last rows
+// (dmesh_renderer_amd_packed.h, fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused).  The
+// lists' checks are interp_args' / values_args' in spirit, in fragments.py's order; row [B,K,H,W] and n_used [1] come from pack_slots.
+void packed_built() {
+    if (!g_abi.pack_slots) err(g_abi.path + " does not export dmr_pack_slots: rebuild it (python -m dmesh_renderer_amd.build)");
+}
+
+struct PackedLists {
+    at::Tensor face, row, n_used;
+    int64_t B = 0, K = 0, H = 0, W = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+};
+
+// face [B,K,H,W] with K in 1..32 and at least one pixel; row (if given) of its shape, n_used (if given) one element, on its device
+PackedLists packed_lists(const char* call, In face, const at::Tensor* row, const at::Tensor* n_used) {
+    packed_built();
+    PackedLists a;
+    a.dev = hip_device_of(face);
+    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
+    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+    if (row && (row->dim() != 4 || row->sizes() != face.sizes())) err("row must have the dimensions (B, K, H, W) of pix_to_face");
+    if (n_used && n_used->numel() != 1) err("n_used must have one element");
+    if (a.K < 1 || a.K > 32) err(std::string(call) + ": K must be in 1..32, got " + std::to_string(a.K));
+    if (a.B < 1 || a.H < 1 || a.W < 1) err(std::string(call) + ": empty fragment lists");
+    if (a.B * a.K * a.H * a.W >= ((int64_t)1 << 31)) err(std::string(call) + ": B K H W must be below 2^31");
+    if (row && row->device() != a.dev) err("row must be on the device of pix_to_face");
+    if (n_used && n_used->device() != a.dev) err("n_used must be on the device of pix_to_face");
+    a.face = i32(face, "pix_to_face");
+    if (row) a.row = i32(*row, "row");
+    if (n_used) a.n_used = i32(*n_used, "n_used");
+    return a;
+}
+
+// -> (row [B,K,H,W] int32, n_used [1] int32); a used slot (face id in [0, F)) whose row would be >= capacity gets -1
+std::tuple<at::Tensor, at::Tensor> pack_slots(In face, int64_t F, int64_t capacity) {
+    const PackedLists a = packed_lists("pack_slots", face, nullptr, nullptr);
+    if (F < 0 || F >= ((int64_t)1 << 31)) err("pack_slots: F must be in 0..2^31 - 1, got " + std::to_string(F));
+    if (capacity < 0) err("pack_slots: capacity must not be negative, got " + std::to_string(capacity));
+    c10::DeviceGuard guard(a.dev);
+    const at::TensorOptions i32_on = at::TensorOptions().dtype(at::kInt).device(a.dev);
+    at::Tensor row = at::empty({a.B, a.K, a.H, a.W}, i32_on), n_used = at::empty({1}, i32_on);
+    if (g_abi.pack_slots(a.B, a.K, a.H, a.W, (int)F, (int)std::min<int64_t>(capacity, INT32_MAX), mptr<const int32_t>(a.face),
+                         mptr<int32_t>(row), mptr<int32_t>(n_used), a.stream()))
+        raise_lib();
+    return {row, n_used};
+}
+
+struct PackedInterpArgs : PackedLists { at::Tensor bary, faces, attrs; int64_t F = 0, P = 0, C = 0, N = 0; };
+
+PackedInterpArgs packed_interp_args(In face, In bary, In row, In n_used, In faces, In vert_attrs, int64_t N) {
+    PackedInterpArgs a;
+    static_cast<PackedLists&>(a) = packed_lists("interpolate_packed", face, &row, &n_used);
+    if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
+        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
+    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
+    a.F = faces.size(0);
+    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
+    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1); a.N = N;
+    if (a.C < 1 || a.C > 256) err("interpolate_packed: C must be in 1..256, got " + std::to_string(a.C));
+    if (N < 0 || N >= ((int64_t)1 << 31)) err("interpolate_packed: rows must be in 0..2^31 - 1, got " + std::to_string(N));
+    if (bary.device() != a.dev) err("bary must be on the device of pix_to_face");
+    if (faces.device() != a.dev) err("faces must be on the device of pix_to_face");
+    if (vert_attrs.device() != a.dev) err("vert_attrs must be on the device of pix_to_face");
+    a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(vert_attrs, "vert_attrs");
+    return a;
+}
+
+// -> out [N,C]
+at::Tensor interpolate_packed(In face, In bary, In row, In n_used, In faces, In vert_attrs, int64_t N) {
+    const PackedInterpArgs a = packed_interp_args(face, bary, row, n_used, faces, vert_attrs, N);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor out = at::empty({a.N, a.C}, f32_on(a.dev));
+    if (g_abi.interpolate_packed(a.B, a.K, a.H, a.W, a.P, a.F, a.C, a.N, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                 mptr<const int32_t>(a.row), mptr<const int32_t>(a.n_used), mptr<const int32_t>(a.faces),
+                                 mptr<const float>(a.attrs), mptr<float>(out), a.stream()))
+        raise_lib();
+    return out;
+}
+
+// need = (vert_attrs, bary) -> those two gradients, None where not asked for; grad_out [N,C]
+py::tuple interpolate_packed_backward(In face, In bary, In row, In n_used, In faces, In vert_attrs, In grad_out, const std::array<bool, 2>& need) {
+    const PackedInterpArgs a = packed_interp_args(face, bary, row, n_used, faces, vert_attrs, grad_out.dim() == 2 ? grad_out.size(0) : -1);
+    c10::DeviceGuard guard(a.dev);
+    if (grad_out.dim() != 2 || grad_out.size(1) != a.C || grad_out.device() != a.dev) err("grad_out must have dimensions (rows, C) on the device of pix_to_face");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor d_attrs = grad_if(need[0], {a.P, a.C}, a.dev), d_bary = grad_if(need[1], {a.B, a.K, 2, a.H, a.W}, a.dev);
+    if (g_abi.interpolate_packed_backward(a.B, a.K, a.H, a.W, a.P, a.F, a.C, a.N, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                          mptr<const int32_t>(a.row), mptr<const int32_t>(a.n_used), mptr<const int32_t>(a.faces),
+                                          mptr<const float>(a.attrs), mptr<const float>(go), out_ptr(d_attrs), out_ptr(d_bary), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_attrs), or_none(d_bary));
+}
+
+// ListArgs for upstreams(); bary and corners stay undefined, row / n_used beside it
+struct PackedValuesArgs : ListArgs { at::Tensor row, n_used, values; int64_t C = 0, N = 0; };
+
+PackedValuesArgs packed_values_args(In face, In row, const at::Tensor* n_used, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    const PackedLists l = packed_lists("composite_values_packed", face, &row, n_used);
+    PackedValuesArgs a;
+    a.call = "composite_values_packed"; a.corner_name = "";
+    a.dev = l.dev; a.B = l.B; a.K = l.K; a.H = l.H; a.W = l.W; a.face = l.face; a.row = l.row; a.n_used = l.n_used;
+    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
+    a.F = faces_opacity.size(0);
+    if (values.dim() != 2) err("values must have dimensions (rows, C)");
+    a.N = values.size(0); a.C = values.size(1);
+    if (a.C < 1 || a.C > 256) err("composite_values_packed: C must be in 1..256, got " + std::to_string(a.C));
+    if (a.N >= ((int64_t)1 << 31)) err("composite_values_packed: rows must be in 0..2^31 - 1, got " + std::to_string(a.N));
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
+        err("face_scale must have dimensions (B, num_faces)");
+    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
+    if (values.device() != a.dev) err("values must be on the device of pix_to_face");
+    if (face_scale && face_scale->device() != a.dev) err("face_scale must be on the device of pix_to_face");
+    a.opacity = f32(faces_opacity, "faces_opacity"); a.values = f32(values, "values");
+    if (face_scale) a.scale = f32(*face_scale, "face_scale");
+    return a;
+}
+
+// -> (image [B,C,H,W], T [B,1,H,W])
+std::tuple<at::Tensor, at::Tensor> composite_values_packed(In face, In row, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    const PackedValuesArgs a = packed_values_args(face, row, nullptr, faces_opacity, values, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    if (g_abi.composite_values_packed(a.B, a.K, a.H, a.W, a.F, a.C, a.N, mptr<const int32_t>(a.face), mptr<const int32_t>(a.row), in_ptr(a.opacity),
+                                      in_ptr(a.values), a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
+        raise_lib();
+    return {image, T};
+}
+
+// need = (faces_opacity, values, face_scale) -> those three gradients, None where not asked for; grad_image [B,C,H,W] /
+// grad_T [B,1,H,W]: None = zero
+py::tuple composite_values_packed_backward(In face, In row, In n_used, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale,
+                                           const std::optional<at::Tensor>& grad_image, const std::optional<at::Tensor>& grad_T,
+                                           const std::array<bool, 3>& need) {
+    const PackedValuesArgs a = packed_values_args(face, row, &n_used, faces_opacity, values, face_scale);
+    c10::DeviceGuard guard(a.dev);
+    if (need[2] && !face_scale) err("composite_values_packed_backward: the gradient of face_scale without face_scale");
+    const auto [gi, gt] = upstreams(a, a.C, grad_image, grad_T);
+    at::Tensor d_op = grad_if(need[0], {a.F}, a.dev), d_values = grad_if(need[1], {a.N, a.C}, a.dev);
+    at::Tensor d_scale = grad_if(need[2], {a.B, a.F}, a.dev);
+    if (g_abi.composite_values_packed_backward(a.B, a.K, a.H, a.W, a.F, a.C, a.N, mptr<const int32_t>(a.face), mptr<const int32_t>(a.row),
+                                               mptr<const int32_t>(a.n_used), in_ptr(a.opacity), in_ptr(a.values), a.scale_ptr(), in_ptr(gi),
+                                               in_ptr(gt), out_ptr(d_op), out_ptr(d_values), out_ptr(d_scale), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1049,6 +1220,16 @@ PYBIND11_MODULE(_C, m) {
     m.def("composite_values", &composite_values, py::arg("face"), py::arg("faces_opacity"), py::arg("values"), py::arg("face_scale") = py::none());
     m.def("composite_values_backward", &composite_values_backward, py::arg("face"), py::arg("faces_opacity"), py::arg("values"),
           py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"), py::arg("need") = std::array<bool, 3>{true, true, true});
+    m.def("pack_slots", &pack_slots, py::arg("face"), py::arg("F"), py::arg("capacity"));
+    m.def("interpolate_packed", &interpolate_packed, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"), py::arg("faces"),
+          py::arg("vert_attrs"), py::arg("rows"));
+    m.def("interpolate_packed_backward", &interpolate_packed_backward, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"),
+          py::arg("faces"), py::arg("vert_attrs"), py::arg("grad_out"), py::arg("need") = std::array<bool, 2>{true, true});
+    m.def("composite_values_packed", &composite_values_packed, py::arg("face"), py::arg("row"), py::arg("faces_opacity"), py::arg("values"),
+          py::arg("face_scale") = py::none());
+    m.def("composite_values_packed_backward", &composite_values_packed_backward, py::arg("face"), py::arg("row"), py::arg("n_used"),
+          py::arg("faces_opacity"), py::arg("values"), py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"),
+          py::arg("need") = std::array<bool, 3>{true, true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1079,6 +1260,9 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_VISIBILITY") = g_abi.face_visibility != nullptr;
     // fragments.interpolate_fused / composite_values_fused; False: the loaded library predates dmesh_renderer_amd_deferred.h
     m.attr("SUPPORTS_FRAGMENT_DEFERRED") = g_abi.interpolate_fragments != nullptr;
+    // fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused; False: the loaded library predates
+    // dmesh_renderer_amd_packed.h
+    m.attr("SUPPORTS_FRAGMENT_PACKED") = g_abi.pack_slots != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

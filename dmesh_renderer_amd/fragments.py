@@ -11,6 +11,16 @@ interpolate_fused and composite_values_fused (csrc/dmr_interp.hip) are the two E
 deferred shader that fits none of the fused shapes: interpolate_fused is interpolate, the caller's own torch code then runs on
 every fragment (an MLP, a lighting model), and composite_values_fused blends the per-slot results front to back
 (composite_values is its torch model): composite_values(frag, o, interpolate(frag, faces, A), s) == composite(frag, faces, o, A, s).
+A NEURAL shader (an MLP, a learned BRDF, a neural texture) wants rows [N,C], and only of the slots that hold a face: the packed
+path (csrc/dmr_packed.hip).  pack_slots_fused numbers the used slots of the lists 0 .. n - 1 in the order of
+pix_to_face.flatten(), interpolate_packed_fused writes one channel-last row per used slot, ready for nn.Linear, and
+composite_values_packed_fused blends the rows the shader returns -- no permute, and nothing computed for an empty slot:
+    packed = pack_slots_fused(frag, F)                                  # or capacity=M: no host wait, capturable
+    x = interpolate_packed_fused(frag, packed, faces, features)         # [N,C]
+    rgb = mlp(x)                                                        # [N,3], the caller's own torch code
+    image, T = composite_values_packed_fused(frag, packed, faces_opacity, rgb)
+    color = image + T * bg.view(1, 3, 1, 1)
+(pack_slots, interpolate_packed, composite_values_packed are the torch models, unpack_values the way back to [B,K,C,H,W]).
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -39,13 +49,14 @@ renderer's colour and alpha differ from the lines above by 1e-5 bg and 1e-5 ther
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch as th
 
 __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
            "composite_texture_fused", "face_coverage", "face_visibility_fused", "composite_values", "interpolate_fused",
-           "composite_values_fused"]
+           "composite_values_fused", "PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused",
+           "composite_values_packed", "composite_values_packed_fused", "unpack_values"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -180,7 +191,10 @@ class _CompositeFn(th.autograd.Function):
 _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_texture": ("SUPPORTS_FRAGMENT_TEXTURE", "texture"),
           "face_visibility": ("SUPPORTS_FRAGMENT_VISIBILITY", "face-visibility"),
           "interpolate": ("SUPPORTS_FRAGMENT_DEFERRED", "fragment", "interpolation"),
-          "composite_values": ("SUPPORTS_FRAGMENT_DEFERRED", "per-slot value")}  # (a third entry: what stands for "compositing" in the message)
+          "composite_values": ("SUPPORTS_FRAGMENT_DEFERRED", "per-slot value"),
+          "pack_slots": ("SUPPORTS_FRAGMENT_PACKED", "fragment", "slot packing"),
+          "interpolate_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed fragment", "interpolation"),
+          "composite_values_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed per-slot value")}  # (a third entry: what stands for "compositing" in the message)
 
 
 def _fused_kernels(torch_path: str):
@@ -540,3 +554,223 @@ def composite_values_fused(frag, faces_opacity: th.Tensor, values: th.Tensor,
     floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
     _check_tensors(name, torch_path, frag.pix_to_face, [], floats)
     return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale)
+
+
+# ---------------------------------------------------------------------------
+# Packed, channel-last rows: the used slots of the lists as rows 0 .. N - 1 of [N,C] tensors (csrc/dmr_packed.hip)
+# ---------------------------------------------------------------------------
+class PackedSlots(NamedTuple):
+    """What pack_slots / pack_slots_fused return: which row of a packed [N,C] tensor every slot of the lists owns."""
+    row: th.Tensor      # int32 [B,K,H,W]: the row of every used slot, -1 in an empty (or dropped) one
+    n_used: th.Tensor   # int32 [1], on the lists' device: the number of used slots (may exceed `rows`: slots were dropped)
+    rows: int           # N: the number of rows of every packed tensor made with this
+
+
+def _capacity(name: str, capacity, face: th.Tensor):
+    """capacity as given (None, or an int >= 0) -- None needs a host wait, which a stream capture cannot make."""
+    if capacity is None:
+        if face.is_cuda and th.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{name}: capacity=None reads the number of used slots on the host, which a stream capture cannot do: "
+                               f"pass capacity=M (the rows to provide for; n_used tells afterwards whether they sufficed)")
+        return None
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0:
+        raise ValueError(f"{name}: capacity must be None or a non-negative int, got {capacity!r}")
+    return capacity
+
+
+def _check_f(name: str, F):
+    if isinstance(F, bool) or not isinstance(F, int) or F < 0:
+        raise ValueError(f"{name}: F must be a non-negative int, got {F!r}")
+
+
+def pack_slots(frag, F: int, capacity: Optional[int] = None) -> PackedSlots:
+    """Numbers the used slots of the lists: a slot is USED when its face id lies in [0, F) (the empty-slot rule of every fused
+    unit), and the used slots get the rows 0, 1, ... in the order of frag.pix_to_face.flatten(), that is (b, k, y, x).
+    capacity=None: `rows` is the exact count (one host wait to read it; under stream capture a RuntimeError).  capacity=M: no
+    host wait, rows = M, and a used slot whose row would be >= M gets row -1: it is DROPPED and behaves as empty in everything
+    made with the result; n_used still holds the true count, so n_used > rows tells of the overflow.  Plain torch, any device."""
+    face = frag.pix_to_face
+    _check_f("pack_slots", F)
+    capacity = _capacity("pack_slots", capacity, face)
+    used = ((face >= 0) & (face < F)).reshape(-1)
+    number = th.cumsum(used.to(th.int64), 0) - 1
+    n_used = used.sum().to(th.int32).reshape(1)
+    rows = int(n_used.item()) if capacity is None else capacity
+    row = th.where(used & (number < rows), number, th.full_like(number, -1)).to(th.int32).reshape(face.shape)
+    return PackedSlots(row, n_used, rows)
+
+
+def _counting(frag, packed: PackedSlots, F: Optional[int]) -> th.Tensor:
+    """[B,K,H,W] bool: the slots that count -- 0 <= row < rows, and (F given) a face id in [0, F)."""
+    live = (packed.row >= 0) & (packed.row < packed.rows)
+    if F is not None:
+        live = live & (frag.pix_to_face >= 0) & (frag.pix_to_face < F)
+    return live
+
+
+def unpack_values(frag, packed: PackedSlots, values: th.Tensor) -> th.Tensor:
+    """Packed rows values [N,C] back in the dense layout [B,K,C,H,W] interpolate returns: slot (b, k, y, x) holds
+    values[packed.row[b, k, y, x]], 0 in a slot without a row.  Torch only (for tests and debugging); differentiable in values."""
+    live = _counting(frag, packed, None)
+    v = values[packed.row.clamp(min=0).long()]                  # [B,K,H,W,C]
+    v = th.where(live.unsqueeze(-1), v, th.zeros((), dtype=v.dtype, device=v.device))
+    return v.permute(0, 1, 4, 2, 3)
+
+
+def interpolate_packed(frag, packed: PackedSlots, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
+    """interpolate(...) on packed, channel-last rows, [N,C] with N = packed.rows: the row of a slot that counts (0 <= row < N and a
+    face id in [0, F), F = len(faces)) holds its interpolated attributes, every other row is 0:
+        interpolate_packed(frag, packed, faces, A) == interpolate(frag, faces, A).permute(0, 1, 3, 4, 2)[packed.row >= 0]
+    for a `packed` made with capacity=None on the same lists and F (in general: those rows reordered by `row`, zeros in the rest).
+    Constants and gradients as interpolate's.  Plain torch, any device, any float dtype."""
+    live = _counting(frag, packed, faces.shape[0])
+    face = th.where(live, frag.pix_to_face, th.full_like(frag.pix_to_face, -1))
+    dense = interpolate(frag._replace(pix_to_face=face), faces, vert_attrs).permute(0, 1, 3, 4, 2)   # [B,K,H,W,C]
+    out = dense.new_zeros(packed.rows, vert_attrs.shape[1])
+    return out.index_put((packed.row[live].long(),), dense[live])
+
+
+def composite_values_packed(frag, packed: PackedSlots, faces_opacity: th.Tensor, values: th.Tensor,
+                            face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """composite_values(...) over packed rows values [N,C] (N = packed.rows): (image [B,C,H,W], T [B,1,H,W]) with
+        composite_values_packed(frag, packed, o, v, s) == composite_values(frag', o, unpack_values(frag, packed, v), s)
+    where frag' is frag with every slot that does not count (no row in [0, N), or a face id outside [0, F), F = len(faces_opacity))
+    set to -1: a dropped slot is skipped by the blend, as an empty one.  Differentiable in faces_opacity, values and face_scale."""
+    live = _counting(frag, packed, faces_opacity.shape[0])
+    face = th.where(live, frag.pix_to_face, th.full_like(frag.pix_to_face, -1))
+    return composite_values(frag._replace(pix_to_face=face), faces_opacity, unpack_values(frag, packed, values), face_scale)
+
+
+def _check_packed(name: str, torch_path: str, frag, packed) -> int:
+    """packed.row of pix_to_face's shape, one n_used, rows an int >= 0 (ValueError); both int32 on the lists' device (TypeError)
+    -> rows."""
+    face = frag.pix_to_face
+    if tuple(packed.row.shape) != tuple(face.shape):
+        raise ValueError(f"{name}: packed.row must have frag.pix_to_face's shape {tuple(face.shape)}, got {tuple(packed.row.shape)}")
+    if packed.n_used.numel() != 1:
+        raise ValueError(f"{name}: packed.n_used must hold one element, got {tuple(packed.n_used.shape)}")
+    if isinstance(packed.rows, bool) or not isinstance(packed.rows, int) or packed.rows < 0:
+        raise ValueError(f"{name}: packed.rows must be a non-negative int, got {packed.rows!r}")
+    for n, t in (("packed.row", packed.row), ("packed.n_used", packed.n_used)):
+        if t.dtype != th.int32:
+            raise TypeError(f"{name}: {n} must be int32, got {t.dtype}; {torch_path}")
+    return packed.rows
+
+
+def pack_slots_fused(frag, F: int, capacity: Optional[int] = None) -> PackedSlots:
+    """pack_slots(...) as three stream-ordered HIP launches (per-workgroup counts, one workgroup's scan, the rows): the same
+    row, n_used and rows, exactly.  capacity=None waits for the device once, to read the count (under stream capture a
+    RuntimeError: pass capacity=M); capacity=M never waits.  K <= 32, B K H W < 2^31 (ValueError).  HIP int32 lists only: anything else
+    is a TypeError -- pack_slots is the torch path for it; nothing falls back silently.  frag.bary and frag.count are not read."""
+    name, torch_path = "pack_slots_fused", "fragments.pack_slots is the torch path for anything else"
+    c = _fused_kernels("pack_slots")
+    B, K, H, W = _check_lists(name, frag, False)
+    _check_f(name, F)
+    if B * K * H * W >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"{name}: B K H W and F must be below 2^31, got {B * K * H * W} slots, F = {F}")
+    face = frag.pix_to_face
+    _check_tensors(name, torch_path, face, [], [])
+    capacity = _capacity(name, capacity, face)
+    if B * H * W == 0:
+        return PackedSlots(th.full_like(face, -1), th.zeros(1, dtype=th.int32, device=face.device), capacity or 0)
+    row, n_used = c.pack_slots(face, F, B * K * H * W if capacity is None else capacity)
+    return PackedSlots(row, n_used, int(n_used.item()) if capacity is None else capacity)
+
+
+class _InterpolatePackedFn(th.autograd.Function):
+    """interpolate_packed_fused's one Function over _C.interpolate_packed / _C.interpolate_packed_backward.  Arguments: pix_to_face,
+    bary, row, n_used, faces, vert_attrs, rows."""
+
+    @staticmethod
+    def forward(ctx, face, bary, row, n_used, faces, vert_attrs, rows):
+        out = _fused_kernels("interpolate_packed").interpolate_packed(face, bary, row, n_used, faces, vert_attrs, rows)
+        ctx.save_for_backward(face, bary, row, n_used, faces, vert_attrs)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        face, bary, row, n_used, faces, vert_attrs = ctx.saved_tensors
+        need = (ctx.needs_input_grad[5], ctx.needs_input_grad[1])  # (vert_attrs, bary)
+        if grad_out is None or not any(need):
+            return (None,) * 7
+        d_attrs, d_bary = _fused_kernels("interpolate_packed").interpolate_packed_backward(face, bary, row, n_used, faces, vert_attrs,
+                                                                                         grad_out.contiguous(), need)
+        return None, d_bary, None, None, None, d_attrs, None
+
+
+class _CompositeValuesPackedFn(th.autograd.Function):
+    """composite_values_packed_fused's one Function over _C.composite_values_packed / _C.composite_values_packed_backward.
+    Arguments: pix_to_face, row, n_used, faces_opacity, values, face_scale (a tensor or None)."""
+
+    @staticmethod
+    def forward(ctx, face, row, n_used, faces_opacity, values, face_scale):
+        image, t = _fused_kernels("composite_values_packed").composite_values_packed(face, row, faces_opacity, values, face_scale)
+        ctx.save_for_backward(face, row, n_used, faces_opacity, values, *(() if face_scale is None else (face_scale,)))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
+        return image, t
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_t):
+        face, row, n_used, faces_opacity, values, *scale = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (face, row, n_used, faces_opacity, values, face_scale)
+        need = (need[3], need[4], bool(scale) and need[5])
+        if (grad_image is None and grad_t is None) or not any(need):
+            return (None,) * 6
+        d_op, d_values, d_scale = _fused_kernels("composite_values_packed").composite_values_packed_backward(
+            face, row, n_used, faces_opacity, values, scale[0] if scale else None,
+            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
+        return None, None, None, d_op, d_values, d_scale
+
+
+def interpolate_packed_fused(frag, packed: PackedSlots, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
+    """interpolate_packed(...) as one HIP kernel, and one for its backward: the same [N,C] channel-last rows, what nn.Linear
+    takes, without the [B,K,C,H,W] tensor and its permute.  A slot counts only if 0 <= row < N and its face id lies in [0, F): a
+    `packed` made for another F or capacity stays in bounds; a slot with a row that does not count, and a face whose row of
+    `faces` holds a vertex index outside [0, P), gives a row of zeros.  Rows [min(n_used, N), N) are exact zeros (the count is
+    read on the device).  Gradients to vert_attrs and (with the renderer's fragment_grads) frag.bary, each computed only when
+    autograd asks for it; dL_dbary is an exact 0 in empty and dropped slots.  N == 0 gives an empty [0,C] tensor without a launch
+    (it carries no gradient).  K <= 32, 1 <= C <= 256, packed.row of pix_to_face's shape (ValueError).  HIP float32 / int32 tensors
+    on one device only: anything else is a TypeError -- interpolate_packed is the torch path for it; nothing falls back silently."""
+    name, torch_path = "interpolate_packed_fused", "fragments.interpolate_packed is the torch path for anything else"
+    _fused_kernels("interpolate_packed")
+    _check_lists(name, frag, True)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    if vert_attrs.dim() != 2:
+        raise ValueError(f"{name}: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
+    if not 1 <= vert_attrs.shape[1] <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {vert_attrs.shape[1]}")
+    rows = _check_packed(name, torch_path, frag, packed)
+    _check_tensors(name, torch_path, frag.pix_to_face, [("faces", faces), ("packed.row", packed.row), ("packed.n_used", packed.n_used)],
+                   [("frag.bary", frag.bary), ("vert_attrs", vert_attrs)])
+    if rows == 0:
+        return vert_attrs.new_zeros((0, vert_attrs.shape[1]))
+    return _InterpolatePackedFn.apply(frag.pix_to_face, frag.bary, packed.row, packed.n_used, faces.to(th.int32), vert_attrs, rows)
+
+
+def composite_values_packed_fused(frag, packed: PackedSlots, faces_opacity: th.Tensor, values: th.Tensor,
+                                  face_scale: Optional[th.Tensor] = None) -> Tuple[th.Tensor, th.Tensor]:
+    """composite_values_packed(...) as one HIP kernel, and one for its backward: the same (image [B,C,H,W], T [B,1,H,W]) from
+    packed rows values [N,C] (made contiguous if they are not), N = packed.rows.  A slot counts only if 0 <= row < N and its face
+    id lies in [0, F); every other slot is skipped, its row (if it has one) is NOT READ and gets exact zeros in dL_dvalues, as do
+    the rows [min(n_used, N), N).  A counting slot of weight 0 (opacity 0, or behind a face of opacity 1) may skip its load.
+    Gradients to faces_opacity, values and face_scale, each computed only when autograd asks for it.  frag.bary and frag.count are
+    not read.  K <= 32, 1 <= C <= 256, values [packed.rows, C] (ValueError).  HIP float32 / int32 tensors on one device only:
+    anything else is a TypeError -- composite_values_packed is the torch path for it; nothing falls back silently."""
+    name, torch_path = "composite_values_packed_fused", "fragments.composite_values_packed is the torch path for anything else"
+    _fused_kernels("composite_values_packed")
+    B, K, H, W = _check_lists(name, frag, False)
+    if faces_opacity.dim() != 1:
+        raise ValueError(f"{name}: faces_opacity must be [F], got {tuple(faces_opacity.shape)}")
+    F = faces_opacity.shape[0]
+    rows = _check_packed(name, torch_path, frag, packed)
+    if values.dim() != 2 or values.shape[0] != rows:
+        raise ValueError(f"{name}: values must be [packed.rows, C] = {(rows, 'C')}, got {tuple(values.shape)}")
+    if not 1 <= values.shape[1] <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {values.shape[1]}")
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
+    _check_tensors(name, torch_path, frag.pix_to_face, [("packed.row", packed.row), ("packed.n_used", packed.n_used)], floats)
+    return _CompositeValuesPackedFn.apply(frag.pix_to_face, packed.row, packed.n_used, faces_opacity, values, face_scale)
