@@ -32,7 +32,7 @@ LIB = os.path.join(HERE, "libdmesh_renderer_hip.so")
 LIB_ABLATION = os.path.join(HERE, "libdmesh_renderer_hip_ablation.so")
 SOURCES = ["dmr_api.hip", "dmr_binning.hip", "dmr_tri.hip", "dmr_tet.hip", "dmr_shade.hip", "dmr_texture.hip", "dmr_visibility.hip",
            "dmr_interp.hip", "dmr_packed.hip"]
-HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_texture_wrap.hpp",
+HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_deferred_common.hpp", "dmr_texture_wrap.hpp",
            os.path.join("..", "..", "include", "dmesh_renderer_amd.h"), os.path.join("..", "..", "include", "dmesh_renderer_amd_shade.h"),
            os.path.join("..", "..", "include", "dmesh_renderer_amd_texture.h"),
            os.path.join("..", "..", "include", "dmesh_renderer_amd_visibility.h"),

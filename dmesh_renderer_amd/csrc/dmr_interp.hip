@@ -7,7 +7,10 @@
 // are: no dmr_scene, no scratch buffer.  out, values and their gradients are [B,K,C,H,W] planes: B K C H W passes 2^31 at real
 // sizes, so every offset into them is an int64_t.
 //
-// Two pixel-to-lane mappings, RowPix and TilePix below.  The two forwards merge nothing and stream B K C H W floats: they use
+// What this unit shares with its packed twin (dmr_packed.hip) -- the lane mappings, the backward kernels' LDS tables, the
+// vertex lookup, the zeroing kernel, the host checks -- is stated once, in dmr_deferred_common.hpp; the walks and the row load
+// (interp_row) are this unit's own text.
+// Two pixel-to-lane mappings, RowPix and TilePix.  The two forwards merge nothing and stream B K C H W floats: they use
 // RowPix, a wave on 64 pixels of one image row, so that a plane is touched in 256 contiguous bytes per wave-instruction.  The two
 // backward kernels merge lanes of equal face (shade_merge) and sum in a per-workgroup LDS table (stab_find); each runs on the
 // mapping it measured faster on (profiles/deferred/lane_shapes.txt): the interpolation's, which merges 3 CH values
@@ -16,7 +19,7 @@
 // A slot whose face id lies outside [0, F) is empty wherever it sits; the lists' count is not read.
 //
 // None of the arithmetic here decides an index or a branch another kernel depends on: it may contract to FMA.
-#include "dmr_shade_common.hpp"
+#include "dmr_deferred_common.hpp"
 #include "../../include/dmesh_renderer_amd_deferred.h"
 
 namespace dmr {
@@ -25,41 +28,6 @@ namespace {
 #pragma clang fp contract(fast)
 
 constexpr int DEFER_MAX_C = 256;
-
-// The streaming kernels' mapping: a 256-thread workgroup on ROW_W x ROW_H pixels, each wave on one row of them.
-constexpr int ROW_W = 64, ROW_H = 4;
-struct RowPix {
-    int px, py, b;
-    bool inside;
-    int64_t HW, pix;
-    __device__ __forceinline__ RowPix(int block, int sx, int sy, int W, int H) {
-        px = (block % sx) * ROW_W + (int)(threadIdx.x & 63); py = ((block / sx) % sy) * ROW_H + (int)(threadIdx.x >> 6);
-        b = block / (sx * sy);
-        inside = px < W && py < H;
-        HW = (int64_t)H * W;
-        pix = (int64_t)W * py + px;
-    }
-    template <class P> __host__ __device__ static int nx(const P& p) { return p.sx; }
-    template <class P> __host__ __device__ static int ny(const P& p) { return p.sy; }
-};
-// The fragment kernels' mapping (FragSlots) with RowPix's members: a workgroup on a 16 x 16 tile, 8 x 8 pixels per wave.
-struct TilePix {
-    int b;
-    bool inside;
-    int64_t HW, pix;
-    __device__ __forceinline__ TilePix(int block, int gx, int gy, int W, int H) {
-        const auto [tx, ty, view] = tile_coords(block, gx, gy);
-        const FragSlots S(tx, ty, view, 1, W, H);
-        b = view; inside = S.inside; HW = S.HW;
-        pix = (int64_t)W * S.py + S.px;
-    }
-    template <class P> __host__ __device__ static int nx(const P& p) { return p.gx; }
-    template <class P> __host__ __device__ static int ny(const P& p) { return p.gy; }
-};
-// Which of the two a backward kernel runs on: both merge lanes of equal face inside 16-lane DPP rows -- 16 x 1 pixels under
-// RowPix, 8 x 2 under TilePix -- and sum per workgroup; chosen per kernel by measurement.
-using InterpBackwardPix = TilePix;
-using ValuesBackwardPix = RowPix;
 
 struct InterpParams {
     int B, K, H, W, P, F, C, gx, gy, sx, sy;
@@ -94,12 +62,6 @@ __device__ __forceinline__ void interp_row(const InterpParams& p, int v, int c0,
 #pragma unroll
         for (int c = 0; c < CH; c++) r[c] = c0 + c < p.C ? row[c] : 0.f;
     }
-}
-
-// The three vertices of a face; false when one of them is no row of vert_attrs (such a slot gathers and scatters nothing).
-__device__ __forceinline__ bool interp_verts(const InterpParams& p, int face, int (&v)[3]) {
-    v[0] = p.faces[3 * face]; v[1] = p.faces[3 * face + 1]; v[2] = p.faces[3 * face + 2];
-    return (uint32_t)v[0] < (uint32_t)p.P && (uint32_t)v[1] < (uint32_t)p.P && (uint32_t)v[2] < (uint32_t)p.P;
 }
 
 // ---------------------------------------------------------------------------
@@ -141,15 +103,8 @@ k_interpolate_fragments(InterpParams p, float* __restrict__ out) {
 }
 
 // ---------------------------------------------------------------------------
-// interpolate, backward.  The per-tile table: vertex -> CH sums in f64 cells (as the other units' tables: an f64 LDS add on
-// distinct cells costs a tenth of an f32 one on this part, profiles/r02/lds_atomics.txt): 20 KB (CH 4), 38 KB (CH 8).
+// interpolate, backward.  The per-tile table is InterpLds<CH> (dmr_deferred_common.hpp).
 // ---------------------------------------------------------------------------
-template <int CH>
-struct InterpLds {
-    double val[STAB][CH];
-    uint32_t key[STAB];
-};
-
 // One workgroup per tile, a lane owns its pixel (InterpBackwardPix).  Per chunk of CH channels, front to back, with g_k the slot's
 // upstream: dL/dbary = ((A[v1] - A[v0]) . g_k, (A[v2] - A[v0]) . g_k) (the lane is the slot's one writer: the first chunk
 // stores -- an exact 0 in empty slots, so nothing is zeroed beforehand -- later ones add), and the rows beta_j g_k of the three
@@ -279,18 +234,8 @@ k_composite_values(ValuesParams p, float* __restrict__ image, float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-// composite_values, backward.  T_k and e_k = values_k . g of every slot of the workgroup's pixels (what the opacity recurrence
-// needs from the front-to-back walk), and the table: face -> (dL/do, dL/ds) in f64 cells.
-// 8 KB + 11 KB (KMAX 4) ... 64 KB + 11 KB (KMAX 32).
+// composite_values, backward.  T_k, e_k and the per-workgroup table are ValuesLds<KMAX> (dmr_deferred_common.hpp).
 // ---------------------------------------------------------------------------
-template <int KMAX>
-struct ValuesLds {
-    float tv[KMAX][TILE_PIX];
-    float ev[KMAX][TILE_PIX];
-    double val[STAB][2];
-    uint32_t key[STAB];
-};
-
 // One workgroup per 64 x 4 pixels, a lane owns its pixel (ValuesBackwardPix).  With g the pixel's upstream of the image, gT that of T:
 //   walk 0 (front to back, no values): T_k of every slot -> LDS.
 //   per chunk of CH channels, front to back: dL/dvalues[b,k,c] = w_k s_k g[c], a plain store to every slot of every pixel of
@@ -384,69 +329,16 @@ k_composite_values_backward(ValuesParams p, const float* __restrict__ gimg, cons
 
 #pragma clang fp contract(off)
 
-// Up to three buffers of 4-byte words zeroed by one launch (null: none), each with its own length: what the tiles add into, and
-// dL/dvalues when no upstream of the image arrives.  A kernel, not hipMemsetAsync: as a node of a captured graph that left
-// small non-zero words behind from the second replay on.
-__global__ void __launch_bounds__(256)
-k_deferred_zero(uint32_t* __restrict__ a, int64_t na, uint32_t* __restrict__ b, int64_t nb, uint32_t* __restrict__ c, int64_t nc) {
-    const int64_t step = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; (a && i < na) || (b && i < nb) || (c && i < nc); i += step) {
-        if (a && i < na) a[i] = 0u;
-        if (b && i < nb) b[i] = 0u;
-        if (c && i < nc) c[i] = 0u;
-    }
-}
-constexpr int64_t ZERO_MAX_BLOCKS = 1 << 16;  // (a grid stride beyond: B K C H W words may pass what one grid dimension holds)
-void zero_on(hipStream_t st, void* a, int64_t na, void* b, int64_t nb, void* c, int64_t nc) {
-    int64_t n = 0;
-    if (a && na > n) n = na;
-    if (b && nb > n) n = nb;
-    if (c && nc > n) n = nc;
-    if (n <= 0) return;
-    const int64_t blocks = (n + 255) / 256;
-    k_deferred_zero<<<dim3((unsigned)(blocks < ZERO_MAX_BLOCKS ? blocks : ZERO_MAX_BLOCKS)), dim3(256), 0, st>>>(
-        static_cast<uint32_t*>(a), na, static_cast<uint32_t*>(b), nb, static_cast<uint32_t*>(c), nc);
-}
-
-// The grids of both mappings -> the fields of the unit's parameter blocks; non-zero with the error set.  (Neither pair fits
-// shade_check_lists: one has no opacities, the other no barycentrics and no corner table.  The list checks here are the unit's.)
-template <class P>
-int defer_grids(const std::string& n, int B, int K, int H, int W, int F, int C, P& p) {
-    const int64_t gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const int64_t sx = (W + ROW_W - 1) / ROW_W, sy = (H + ROW_H - 1) / ROW_H;
-    if ((int64_t)B * gx * gy >= (int64_t)1 << 31 || (int64_t)B * sx * sy >= (int64_t)1 << 31 || (int64_t)B * F >= (int64_t)1 << 31 ||
-        (int64_t)K * H * W >= (int64_t)1 << 31)
-        return api_fail((n + "problem too large").c_str());
-    p.B = B; p.K = K; p.H = H; p.W = W; p.F = F; p.C = C; p.gx = (int)gx; p.gy = (int)gy; p.sx = (int)sx; p.sy = (int)sy;
-    return 0;
-}
-
 // the arguments both interpolate calls share -> InterpParams
 int interp_params(const char* name, int B, int K, int H, int W, int P, int F, int C, const int32_t* face, const float* bary,
                   const int32_t* faces, const float* vert_attrs, InterpParams& p) {
-    const std::string n = std::string(name) + ": ";
-    if (shade_check_sizes(n, B, K, H, W, P, F, C, DEFER_MAX_C)) return 1;
-    if (!face || !bary) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && !faces) return api_fail((n + "null faces").c_str());
-    if (F > 0 && P > 0 && !vert_attrs) return api_fail((n + "null vert_attrs").c_str());
-    if (defer_grids(n, B, K, H, W, F, C, p)) return 1;
-    p.P = P;
-    p.vec = shade_vec(C, vert_attrs);
-    p.face = face; p.bary = bary; p.faces = faces; p.attrs = vert_attrs;
-    return 0;
+    return deferred_interp_params(name, DEFER_MAX_C, B, K, H, W, P, F, C, face, bary, faces, vert_attrs, nullptr, 0, (int64_t)K * H * W, p);
 }
 
 // the arguments both composite_values calls share -> ValuesParams
 int values_params(const char* name, int B, int K, int H, int W, int F, int C, const int32_t* face, const float* faces_opacity,
                   const float* values, const float* face_scale, ValuesParams& p) {
-    const std::string n = std::string(name) + ": ";
-    if (shade_check_sizes(n, B, K, H, W, 0, F, C, DEFER_MAX_C)) return 1;
-    if (!face) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && !faces_opacity) return api_fail((n + "null faces_opacity").c_str());
-    if (!values) return api_fail((n + "null values").c_str());
-    if (defer_grids(n, B, K, H, W, F, C, p)) return 1;
-    p.face = face; p.opacity = faces_opacity; p.values = values; p.scale = face_scale;
-    return 0;
+    return deferred_values_params(name, DEFER_MAX_C, B, K, H, W, F, C, face, faces_opacity, values, face_scale, nullptr, 0, (int64_t)K * H * W, p);
 }
 
 template <int KMAX>
@@ -517,14 +409,10 @@ int dmr_composite_values_backward(int B, int K, int H, int W, int F, int C, cons
     if (dL_dface_scale && !face_scale) return api_fail("dmr_composite_values_backward: dL_dface_scale without face_scale");
     if (!dL_dfaces_opacity && !dL_dvalues && !dL_dface_scale) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // (without an upstream of the image dL/dvalues is zero, and the kernel does not store it)
-    zero_on(st, dL_dfaces_opacity, F, dL_dface_scale, (int64_t)B * F, grad_image ? nullptr : dL_dvalues, (int64_t)B * K * C * H * W);
-    if (launched(name)) return 1;
-    if (!grad_image && !(grad_T && dL_dfaces_opacity)) return 0;  // nothing arrives, or T's upstream alone, which reaches the opacities alone
-    float* dop = F > 0 ? dL_dfaces_opacity : nullptr;
-    float* dsc = F > 0 ? dL_dface_scale : nullptr;
-    float* dval = grad_image ? dL_dvalues : nullptr;
-    if (!dop && !dsc && !dval) return 0;
+    float *dop, *dval, *dsc;
+    const int go = values_backward_prologue(name, st, B, F, (int64_t)B * K * C * H * W, grad_image, grad_T, dL_dfaces_opacity, dL_dvalues,
+                                            dL_dface_scale, dop, dval, dsc);
+    if (go != SHADE_LAUNCH) return go;
     with_kmax(K, [&](auto kmax) {
         launch_values_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dop, dval, dsc);
     });

@@ -8,11 +8,13 @@
 // A slot COUNTS when 0 <= row < N and its face id lies in [0, F): every access to an [N,C] buffer is behind the first test, so
 // a `row` made for other lists' sizes stays in bounds.  Offsets into the [N,C] buffers are int64_t.
 //
-// The lane mappings are dmr_interp.hip's, restated (RowPix, TilePix): a wave of the forwards sits on 64 pixels of one image
+// The lane mappings, the backward kernels' LDS tables, the vertex lookup, the zeroing kernel and the host checks are
+// dmr_interp.hip's, stated once for both in dmr_deferred_common.hpp; the walks are this unit's own text.  A wave
+// of the forwards sits on 64 pixels of one image
 // row at one k, which are 64 consecutive slots of the flattened lists -- its rows are one contiguous range, and its cnt * C
 // output floats too.  The arithmetic of a slot is dmr_interp.hip's expression for expression, under the same contraction, so
 // the forwards give the dense unit's numbers bit for bit.
-#include "dmr_shade_common.hpp"
+#include "dmr_deferred_common.hpp"
 #include "../../include/dmesh_renderer_amd_packed.h"
 
 namespace dmr {
@@ -21,40 +23,6 @@ namespace {
 #pragma clang fp contract(fast)
 
 constexpr int PACKED_MAX_C = 256;
-
-// The streaming kernels' mapping: a 256-thread workgroup on ROW_W x ROW_H pixels, each wave on one row of them.
-constexpr int ROW_W = 64, ROW_H = 4;
-struct RowPix {
-    int px, py, b;
-    bool inside;
-    int64_t HW, pix;
-    __device__ __forceinline__ RowPix(int block, int sx, int sy, int W, int H) {
-        px = (block % sx) * ROW_W + (int)(threadIdx.x & 63); py = ((block / sx) % sy) * ROW_H + (int)(threadIdx.x >> 6);
-        b = block / (sx * sy);
-        inside = px < W && py < H;
-        HW = (int64_t)H * W;
-        pix = (int64_t)W * py + px;
-    }
-    template <class P> __host__ __device__ static int nx(const P& p) { return p.sx; }
-    template <class P> __host__ __device__ static int ny(const P& p) { return p.sy; }
-};
-// The fragment kernels' mapping (FragSlots) with RowPix's members: a workgroup on a 16 x 16 tile, 8 x 8 pixels per wave.
-struct TilePix {
-    int b;
-    bool inside;
-    int64_t HW, pix;
-    __device__ __forceinline__ TilePix(int block, int gx, int gy, int W, int H) {
-        const auto [tx, ty, view] = tile_coords(block, gx, gy);
-        const FragSlots S(tx, ty, view, 1, W, H);
-        b = view; inside = S.inside; HW = S.HW;
-        pix = (int64_t)W * S.py + S.px;
-    }
-    template <class P> __host__ __device__ static int nx(const P& p) { return p.gx; }
-    template <class P> __host__ __device__ static int ny(const P& p) { return p.gy; }
-};
-// as the dense unit's backward kernels
-using PackedInterpBackwardPix = TilePix;
-using PackedValuesBackwardPix = RowPix;
 
 struct PackedInterpParams {
     int B, K, H, W, P, F, C, N, gx, gy, sx, sy;
@@ -108,12 +76,6 @@ __device__ __forceinline__ void packed_store(float* __restrict__ row, int C, int
         for (int c = 0; c < CH; c++)
             if (c0 + c < C) row[c0 + c] = r[c];
     }
-}
-
-// The three vertices of a face; false when one of them is no row of vert_attrs (such a slot gathers and scatters nothing).
-__device__ __forceinline__ bool packed_verts(const PackedInterpParams& p, int face, int (&v)[3]) {
-    v[0] = p.faces[3 * face]; v[1] = p.faces[3 * face + 1]; v[2] = p.faces[3 * face + 2];
-    return (uint32_t)v[0] < (uint32_t)p.P && (uint32_t)v[1] < (uint32_t)p.P && (uint32_t)v[2] < (uint32_t)p.P;
 }
 
 // Rows min(n_used, N) .. N - 1 of an [N,C] buffer -> exact zeros: what TAIL_GROUPS workgroups past a kernel's own do (tail:
@@ -263,7 +225,7 @@ k_interpolate_packed(PackedInterpParams p, int main_groups, float* __restrict__ 
             if (!has) continue;
         }
         int v[3] = {0, 0, 0};
-        const bool used = has && (uint32_t)face < (uint32_t)p.F && packed_verts(p, face, v);
+        const bool used = has && (uint32_t)face < (uint32_t)p.F && interp_verts(p, face, v);
         float bu = 0.f, bv = 0.f;
         if (used) { bu = p.bary[(2 * slot) * S.HW + S.pix]; bv = p.bary[(2 * slot + 1) * S.HW + S.pix]; }
         const float b0 = 1.f - bu - bv;
@@ -308,16 +270,9 @@ k_interpolate_packed(PackedInterpParams p, int main_groups, float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// interpolate, backward: k_interpolate_fragments_backward with g_k read from the slot's row of grad_out.  The per-tile table:
-// vertex -> CH sums in f64 cells: 20 KB (CH 4), 38 KB (CH 8).
+// interpolate, backward: k_interpolate_fragments_backward with g_k read from the slot's row of grad_out, on its table (InterpLds).
 // ---------------------------------------------------------------------------
-template <int CH>
-struct PackedInterpLds {
-    double val[STAB][CH];
-    uint32_t key[STAB];
-};
-
-// One workgroup per tile, a lane owns its pixel (PackedInterpBackwardPix).  Per chunk of CH channels, front to back, with g_k
+// One workgroup per tile, a lane owns its pixel (InterpBackwardPix).  Per chunk of CH channels, front to back, with g_k
 // the upstream's row of the slot: dL/dbary = ((A[v1] - A[v0]) . g_k, (A[v2] - A[v0]) . g_k) (the lane is the slot's one
 // writer: the first chunk stores -- an exact 0 in slots that do not count, so nothing is zeroed beforehand -- later ones
 // add), and the rows beta_j g_k of the three vertices: merged over the wave's lanes of equal face, then into the table keyed
@@ -327,10 +282,10 @@ template <int CH>
 __global__ void __launch_bounds__(256)
 k_interpolate_packed_backward(PackedInterpParams p, const float* __restrict__ gout, float* __restrict__ dattr, float* __restrict__ dbary) {
     const int tid = threadIdx.x, lane = tid & 63;
-    const PackedInterpBackwardPix S((int)blockIdx.x, PackedInterpBackwardPix::nx(p), PackedInterpBackwardPix::ny(p), p.W, p.H);
+    const InterpBackwardPix S((int)blockIdx.x, InterpBackwardPix::nx(p), InterpBackwardPix::ny(p), p.W, p.H);
     const int b = S.b;
     const int64_t pix = S.pix;
-    __shared__ PackedInterpLds<CH> L;
+    __shared__ InterpLds<CH> L;
     if (dattr) {
         for (int i = tid; i < STAB; i += 256) {
             L.key[i] = STAB_EMPTY;
@@ -350,7 +305,7 @@ k_interpolate_packed_backward(PackedInterpParams p, const float* __restrict__ go
             float rows[3 * CH];
 #pragma unroll
             for (int c = 0; c < 3 * CH; c++) rows[c] = 0.f;
-            if ((uint32_t)row < (uint32_t)p.N && (uint32_t)face < (uint32_t)p.F && packed_verts(p, face, v)) {
+            if ((uint32_t)row < (uint32_t)p.N && (uint32_t)face < (uint32_t)p.F && interp_verts(p, face, v)) {
                 float g[CH];
                 packed_load<CH>(gout + (int64_t)row * p.C, p.C, c0, p.rvec, g);
                 if (dbary) {
@@ -447,18 +402,9 @@ k_composite_values_packed(PackedValuesParams p, float* __restrict__ image, float
 }
 
 // ---------------------------------------------------------------------------
-// composite_values, backward.  T_k and e_k = values_k . g of every slot of the workgroup's pixels, and the table: face ->
-// (dL/do, dL/ds) in f64 cells.  8 KB + 11 KB (KMAX 4) ... 64 KB + 11 KB (KMAX 32).
+// composite_values, backward, on k_composite_values_backward's LDS (ValuesLds).
 // ---------------------------------------------------------------------------
-template <int KMAX>
-struct PackedValuesLds {
-    float tv[KMAX][TILE_PIX];
-    float ev[KMAX][TILE_PIX];
-    double val[STAB][2];
-    uint32_t key[STAB];
-};
-
-// One workgroup per 64 x 4 pixels, a lane owns its pixel (PackedValuesBackwardPix): k_composite_values_backward's three walks.
+// One workgroup per 64 x 4 pixels, a lane owns its pixel (ValuesBackwardPix): k_composite_values_backward's three walks.
 //   walk 0 (front to back, no values): T_k of every slot -> LDS.
 //   per chunk of CH channels, front to back: dL/dvalues[row_k, c] = w_k s_k g[c], a plain store to the row of every slot that
 //     has one (a literal 0 where the slot is empty for this call), and e_k += values[row_k] . g (LDS) when dL/do or dL/ds is wanted.
@@ -472,10 +418,10 @@ k_composite_values_packed_backward(PackedValuesParams p, int main_groups, const 
                                    float* __restrict__ dop, float* __restrict__ dval, float* __restrict__ dsc) {
     if ((int)blockIdx.x >= main_groups) { packed_zero_tail(p.n_used, p.N, p.C, dval, (int)blockIdx.x - main_groups); return; }
     const int tid = threadIdx.x, lane = tid & 63;
-    const PackedValuesBackwardPix S((int)blockIdx.x, PackedValuesBackwardPix::nx(p), PackedValuesBackwardPix::ny(p), p.W, p.H);
+    const ValuesBackwardPix S((int)blockIdx.x, ValuesBackwardPix::nx(p), ValuesBackwardPix::ny(p), p.W, p.H);
     const int b = S.b;
     const int64_t pix = S.pix, list = (int64_t)b * p.K * S.HW + pix;  // (slot k of face / row [B,K,H,W]: list + k HW)
-    __shared__ PackedValuesLds<KMAX> L;
+    __shared__ ValuesLds<KMAX> L;
     for (int i = tid; i < STAB; i += 256) { L.key[i] = STAB_EMPTY; L.val[i][0] = 0.0; L.val[i][1] = 0.0; }
     {
         float T = 1.f;
@@ -558,76 +504,28 @@ k_composite_values_packed_backward(PackedValuesParams p, int main_groups, const 
 
 #pragma clang fp contract(off)
 
-// Up to three buffers of 4-byte words zeroed by one launch (null: none), each with its own length: what the tiles add into, and
-// dL/dvalues when no upstream of the image arrives.  A kernel, not hipMemsetAsync.
-__global__ void __launch_bounds__(256)
-k_packed_zero(uint32_t* __restrict__ a, int64_t na, uint32_t* __restrict__ b, int64_t nb, uint32_t* __restrict__ c, int64_t nc) {
-    const int64_t step = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; (a && i < na) || (b && i < nb) || (c && i < nc); i += step) {
-        if (a && i < na) a[i] = 0u;
-        if (b && i < nb) b[i] = 0u;
-        if (c && i < nc) c[i] = 0u;
-    }
-}
-constexpr int64_t ZERO_MAX_BLOCKS = 1 << 16;  // (a grid stride beyond)
-void packed_zero_on(hipStream_t st, void* a, int64_t na, void* b, int64_t nb, void* c, int64_t nc) {
-    int64_t n = 0;
-    if (a && na > n) n = na;
-    if (b && nb > n) n = nb;
-    if (c && nc > n) n = nc;
-    if (n <= 0) return;
-    const int64_t blocks = (n + 255) / 256;
-    k_packed_zero<<<dim3((unsigned)(blocks < ZERO_MAX_BLOCKS ? blocks : ZERO_MAX_BLOCKS)), dim3(256), 0, st>>>(
-        static_cast<uint32_t*>(a), na, static_cast<uint32_t*>(b), nb, static_cast<uint32_t*>(c), nc);
-}
-
-// The grids of both mappings -> the fields of the unit's parameter blocks; non-zero with the error set.
-template <class P>
-int packed_grids(const std::string& n, int B, int K, int H, int W, int F, int C, int N, P& p) {
-    const int64_t gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const int64_t sx = (W + ROW_W - 1) / ROW_W, sy = (H + ROW_H - 1) / ROW_H;
-    if ((int64_t)B * gx * gy + TAIL_GROUPS >= (int64_t)1 << 31 || (int64_t)B * sx * sy + TAIL_GROUPS >= (int64_t)1 << 31 ||
-        (int64_t)B * F >= (int64_t)1 << 31 || (int64_t)B * K * H * W >= (int64_t)1 << 31)
-        return api_fail((n + "problem too large").c_str());
-    p.B = B; p.K = K; p.H = H; p.W = W; p.F = F; p.C = C; p.N = N; p.gx = (int)gx; p.gy = (int)gy; p.sx = (int)sx; p.sy = (int)sy;
-    return 0;
-}
-
 // the arguments both interpolate calls share -> PackedInterpParams
 int packed_interp_params(const char* name, int B, int K, int H, int W, int P, int F, int C, int N, const int32_t* face, const float* bary,
                          const int32_t* row, const int32_t* n_used, const int32_t* faces, const float* vert_attrs, PackedInterpParams& p) {
-    const std::string n = std::string(name) + ": ";
-    if (shade_check_sizes(n, B, K, H, W, P, F, C, PACKED_MAX_C)) return 1;
-    if (N < 0) return api_fail((n + "bad rows").c_str());
-    if (!face || !bary || !row) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && !faces) return api_fail((n + "null faces").c_str());
-    if (F > 0 && P > 0 && !vert_attrs) return api_fail((n + "null vert_attrs").c_str());
-    if (!n_used) return api_fail((n + "null n_used").c_str());
-    if (packed_grids(n, B, K, H, W, F, C, N, p)) return 1;
-    p.P = P;
-    p.vec = shade_vec(C, vert_attrs);
-    p.face = face; p.bary = bary; p.row = row; p.n_used = n_used; p.faces = faces; p.attrs = vert_attrs;
+    const PackedRows r = {N, row, n_used};
+    if (deferred_interp_params(name, PACKED_MAX_C, B, K, H, W, P, F, C, face, bary, faces, vert_attrs, &r, TAIL_GROUPS, (int64_t)B * K * H * W, p)) return 1;
+    p.N = N; p.row = row; p.n_used = n_used;
     return 0;
 }
 
-// the arguments both composite_values calls share -> PackedValuesParams
+// the arguments both composite_values calls share -> PackedValuesParams (n_used: the backward call's alone, which sets it)
 int packed_values_params(const char* name, int B, int K, int H, int W, int F, int C, int N, const int32_t* face, const int32_t* row,
                          const float* faces_opacity, const float* values, const float* face_scale, PackedValuesParams& p) {
-    const std::string n = std::string(name) + ": ";
-    if (shade_check_sizes(n, B, K, H, W, 0, F, C, PACKED_MAX_C)) return 1;
-    if (N < 0) return api_fail((n + "bad rows").c_str());
-    if (!face || !row) return api_fail((n + "null fragment lists").c_str());
-    if (F > 0 && !faces_opacity) return api_fail((n + "null faces_opacity").c_str());
-    if (N > 0 && !values) return api_fail((n + "null values").c_str());
-    if (packed_grids(n, B, K, H, W, F, C, N, p)) return 1;
+    const PackedRows r = {N, row, nullptr};
+    if (deferred_values_params(name, PACKED_MAX_C, B, K, H, W, F, C, face, faces_opacity, values, face_scale, &r, TAIL_GROUPS, (int64_t)B * K * H * W, p)) return 1;
     p.rvec = shade_vec(C, values);
-    p.face = face; p.row = row; p.n_used = nullptr; p.opacity = faces_opacity; p.values = values; p.scale = face_scale;
+    p.N = N; p.row = row; p.n_used = nullptr;
     return 0;
 }
 
 template <int KMAX>
 void launch_packed_values_backward(const PackedValuesParams& p, hipStream_t st, const float* gi, const float* gt, float* dop, float* dval, float* dsc) {
-    const int main_groups = p.B * PackedValuesBackwardPix::nx(p) * PackedValuesBackwardPix::ny(p);
+    const int main_groups = p.B * ValuesBackwardPix::nx(p) * ValuesBackwardPix::ny(p);
     const dim3 groups((unsigned)(main_groups + (dval ? TAIL_GROUPS : 0))), block(256);
     if (p.C <= 4) k_composite_values_packed_backward<KMAX, 4><<<groups, block, 0, st>>>(p, main_groups, gi, gt, dop, dval, dsc);
     else k_composite_values_packed_backward<KMAX, 8><<<groups, block, 0, st>>>(p, main_groups, gi, gt, dop, dval, dsc);
@@ -693,9 +591,9 @@ int dmr_interpolate_packed_backward(int B, int K, int H, int W, int P, int F, in
     if (!dL_dvert_attrs && !dL_dbary) return 0;
     p.rvec = shade_vec(C, grad_out);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    packed_zero_on(st, dL_dvert_attrs, (int64_t)P * C, nullptr, 0, nullptr, 0);
+    zero_on(st, dL_dvert_attrs, (int64_t)P * C, nullptr, 0, nullptr, 0);
     if (launched(name)) return 1;
-    const dim3 groups((unsigned)(B * PackedInterpBackwardPix::nx(p) * PackedInterpBackwardPix::ny(p))), block(256);
+    const dim3 groups((unsigned)(B * InterpBackwardPix::nx(p) * InterpBackwardPix::ny(p))), block(256);
     if (C <= 4) k_interpolate_packed_backward<4><<<groups, block, 0, st>>>(p, grad_out, dL_dvert_attrs, dL_dbary);
     else k_interpolate_packed_backward<8><<<groups, block, 0, st>>>(p, grad_out, dL_dvert_attrs, dL_dbary);
     return launched(name);
@@ -731,14 +629,10 @@ int dmr_composite_values_packed_backward(int B, int K, int H, int W, int F, int 
     p.n_used = n_used;
     p.rvec = p.rvec && (!dL_dvalues || shade_vec(C, dL_dvalues));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // (without an upstream of the image dL/dvalues is zero, and the kernel does not store it)
-    packed_zero_on(st, dL_dfaces_opacity, F, dL_dface_scale, (int64_t)B * F, grad_image ? nullptr : dL_dvalues, (int64_t)N * C);
-    if (launched(name)) return 1;
-    if (!grad_image && !(grad_T && dL_dfaces_opacity)) return 0;  // nothing arrives, or T's upstream alone, which reaches the opacities alone
-    float* dop = F > 0 ? dL_dfaces_opacity : nullptr;
-    float* dsc = F > 0 ? dL_dface_scale : nullptr;
-    float* dval = grad_image ? dL_dvalues : nullptr;
-    if (!dop && !dsc && !dval) return 0;
+    float *dop, *dval, *dsc;
+    const int go = values_backward_prologue(name, st, B, F, (int64_t)N * C, grad_image, grad_T, dL_dfaces_opacity, dL_dvalues, dL_dface_scale,
+                                            dop, dval, dsc);
+    if (go != SHADE_LAUNCH) return go;
     with_kmax(K, [&](auto kmax) {
         launch_packed_values_backward<decltype(kmax)::value>(p, st, grad_image, grad_T, dop, dval, dsc);
     });

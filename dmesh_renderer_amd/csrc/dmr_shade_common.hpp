@@ -1,5 +1,6 @@
 // dmr_shade_common.hpp -- what the shading units over fragment lists (dmr_shade.hip, dmr_texture.hip, dmr_visibility.hip,
-// dmr_interp.hip) share, each fact once:
+// dmr_interp.hip, dmr_packed.hip; the last three through dmr_deferred_common.hpp, which adds what they alone share) share, each
+// fact once:
 //   device: the merge of a wave's lanes of equal key (shade_merge; shade_merge_max for a maximum) and the per-tile LDS table
 //           (stab_find*).  The kernels' walks are each unit's own text, those they have in common too: DESIGN.md 5c;
 //   host:   the list arguments' validation (shade_check_sizes, shade_check_lists), shade_vec, the K ladder (with_kmax), the

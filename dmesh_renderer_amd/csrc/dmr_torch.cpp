@@ -274,6 +274,7 @@ c10::Device hip_device_of(const at::Tensor& verts) {
 }
 
 at::TensorOptions f32_on(c10::Device dev) { return at::TensorOptions().dtype(at::kFloat).device(dev); }
+void* stream_on(c10::Device dev) { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }  // PyTorch's current stream
 
 // the caller-owned buffers of one call, by DMR_BUF_* id.  Up to DMR_BUF_WORK scratch, allocated on request: the C equivalent of
 // the reference's four resizeFunctional lambdas (render.cu:18-24,91-100), plus the backward's transient workspace.  Beyond it
@@ -342,7 +343,7 @@ struct Call {
             if (t.device() != dev) err("all tensors must be on " + dev.str() + " (one is on " + t.device().str() + ")");
     }
 
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+    void* stream() const { return stream_on(dev); }
 };
 
 template <class T> T* mptr(const at::Tensor& t) { return t.numel() ? reinterpret_cast<T*>(t.data_ptr()) : nullptr; }
@@ -619,7 +620,7 @@ py::tuple invert_mats(const py::args& mats) {
     for (const auto& h : mats) in.push_back(h.cast<at::Tensor>());
     const c10::Device dev = hip_device_of(in[0]);
     c10::DeviceGuard guard(dev);
-    void* st = reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream());
+    void* st = stream_on(dev);
     py::tuple res(in.size());
     for (size_t i = 0; i < in.size(); i++) {
         const at::Tensor& m = in[i];
@@ -657,54 +658,105 @@ at::Tensor export_item(const std::string& name, const py::sequence& call_args, b
     return out.narrow(0, 0, n).view(torch::python::detail::py_object_to_dtype(dtype));
 }
 
-// ---- shading over fragment lists: composite_fragments* (dmesh_renderer_amd_shade.h, fragments.composite_fused) and
-// composite_texture* (dmesh_renderer_amd_texture.h, fragments.composite_texture_fused) --------------------------------------------
-// What every shading call starts with -- the lists, the unit's [F,3] corner table (faces / uv_faces), the opacities, the
-// optional per-face scale -- checked and made contiguous.  A unit extends it with its own tensors and calls the four steps
-// below in this order, each of its own checks at its place between them: the first check that fails decides the message.
-struct ListArgs {
-    at::Tensor face, bary, corners, opacity, scale;  // scale: undefined = none
-    int64_t B = 0, K = 0, H = 0, W = 0, F = 0;
+// ---- shading over fragment lists: composite_fragments* (dmesh_renderer_amd_shade.h), composite_texture* (.._texture.h),
+// face_visibility* (.._visibility.h), interpolate_fragments* / composite_values* (.._deferred.h) and pack_slots /
+// interpolate_packed* / composite_values_packed* (.._packed.h); fragments.py's *_fused functions ----------------------------------
+// Every shading call starts from pix_to_face [B,K,H,W] on a HIP device: Lists.  A unit's argument block extends it with the
+// unit's own tensors, checked and made contiguous by a builder that calls the named checks below in the unit's order, which is
+// fragments.py's: the first check that fails decides the message (tests/golden/shading_refusals.json, "binding").
+struct Lists {
+    at::Tensor face;
+    int64_t B = 0, K = 0, H = 0, W = 0;
     c10::Device dev{c10::kCPU};
-    const char *call, *corner_name;  // "composite_fragments" / "composite_texture"; what the unit calls `corners`
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
+    const char* call = "";  // what the unit's own messages start with: "composite_fragments", ...
+    void* stream() const { return stream_on(dev); }
+};
+// ... and what the calls that blend add: the opacities [F] and the optional per-face scale [B,F] (undefined = none)
+struct Blend {
+    at::Tensor opacity, scale;
+    int64_t F = 0;
     const float* scale_ptr() const { return scale.defined() ? mptr<const float>(scale) : nullptr; }
 };
-struct OwnTensor { In in; const char* name; at::Tensor& out; };  // one of a unit's own f32 tensors, and where its contiguous form goes
 
-// 1: the device, and the dimensions of the lists, the corner table and the opacities
-void list_dims(ListArgs& a, const char* call, const char* corner_name, In face, In bary, In corners, In faces_opacity) {
-    a.call = call; a.corner_name = corner_name;
+template <class Fn>
+void built(Fn fn, const char* symbol) {
+    if (!fn) err(g_abi.path + " does not export " + symbol + ": rebuild it (python -m dmesh_renderer_amd.build)");
+}
+// the device and B, K, H, W (face itself is kept once it is checked: the builder's last step)
+void lists_begin(Lists& a, const char* call, In face) {
+    a.call = call;
     a.dev = hip_device_of(face);
     if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
     a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
+}
+void check_bary(const Lists& a, In bary) {
     if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
         err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
-    if (corners.dim() != 2 || corners.size(1) != 3) err(std::string(a.corner_name) + " must have dimensions (num_faces, 3)");
-    a.F = corners.size(0);
-    if (faces_opacity.dim() != 1 || faces_opacity.size(0) != a.F) err("faces_opacity must have dimensions (num_faces,)");
+}
+// an [F,3] table of corners (faces / uv_faces) -> F
+int64_t check_corners(In corners, const char* name) {
+    if (corners.dim() != 2 || corners.size(1) != 3) err(std::string(name) + " must have dimensions (num_faces, 3)");
+    return corners.size(0);
+}
+// faces_opacity [F] -> F; F < 0: any length
+int64_t check_opacity(In faces_opacity, int64_t F = -1) {
+    if (faces_opacity.dim() != 1 || (F >= 0 && faces_opacity.size(0) != F)) err("faces_opacity must have dimensions (num_faces,)");
+    return faces_opacity.size(0);
+}
+// vert_attrs [P,C] -> P, C
+void check_attrs(In vert_attrs, int64_t& P, int64_t& C) {
+    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
+    P = vert_attrs.size(0); C = vert_attrs.size(1);
+}
+void check_scale(const Lists& a, int64_t F, const std::optional<at::Tensor>& face_scale) {
+    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != F))
+        err("face_scale must have dimensions (B, num_faces)");
+}
+void check_k(const Lists& a) { if (a.K < 1 || a.K > 32) err(std::string(a.call) + ": K must be in 1..32, got " + std::to_string(a.K)); }
+void check_c(const Lists& a, int64_t C, int64_t max_c) {
+    if (C < 1 || C > max_c) err(std::string(a.call) + ": C must be in 1.." + std::to_string(max_c) + ", got " + std::to_string(C));
+}
+void check_not_empty(const Lists& a) { if (a.B < 1 || a.H < 1 || a.W < 1) err(std::string(a.call) + ": empty fragment lists"); }
+void same_device(const Lists& a, In t, const char* name) {
+    if (t.device() != a.dev) err(std::string(name) + " must be on the device of pix_to_face");
+}
+void same_device(const Lists& a, const std::optional<at::Tensor>& t, const char* name) { if (t) same_device(a, *t, name); }
+
+// composite_fragments and composite_texture have the same lists -- barycentrics, the unit's [F,3] corner table, opacities,
+// scale -- and tensors of their own between.  Such a unit calls list_dims, its own shape checks, check_k, its own size checks,
+// check_not_empty, list_finish.
+struct ListArgs : Lists, Blend {
+    at::Tensor bary, corners;
+    const char* corner_name = "";  // what the unit calls `corners`
+};
+struct OwnTensor { In in; const char* name; at::Tensor& out; };  // one of a unit's own f32 tensors, and where its contiguous form goes
+
+void list_dims(ListArgs& a, const char* call, const char* corner_name, In face, In bary, In corners, In faces_opacity) {
+    a.corner_name = corner_name;
+    lists_begin(a, call, face);
+    check_bary(a, bary);
+    a.F = check_corners(corners, corner_name);
+    check_opacity(faces_opacity, a.F);
     a.face = face; a.bary = bary; a.corners = corners; a.opacity = faces_opacity;
 }
-void list_k(const ListArgs& a) { if (a.K < 1 || a.K > 32) err(std::string(a.call) + ": K must be in 1..32, got " + std::to_string(a.K)); }
-void list_not_empty(const ListArgs& a) { if (a.B < 1 || a.H < 1 || a.W < 1) err(std::string(a.call) + ": empty fragment lists"); }
-// 4: face_scale's dimensions, one device for every tensor, then dtypes: the tensors of `a` and the unit's `own` made contiguous
+// face_scale's dimensions, one device for every tensor, then dtypes: the tensors of `a` and the unit's `own` made contiguous
 void list_finish(ListArgs& a, const std::optional<at::Tensor>& face_scale, std::initializer_list<OwnTensor> own) {
-    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
-        err("face_scale must have dimensions (B, num_faces)");
-    const auto same = [&a](In t, const char* name) {
-        if (t.device() != a.dev) err(std::string(name) + " must be on the device of pix_to_face");
-    };
-    same(a.bary, "bary"); same(a.corners, a.corner_name); same(a.opacity, "faces_opacity");
-    for (const OwnTensor& o : own) same(o.in, o.name);
-    if (face_scale) same(*face_scale, "face_scale");
+    check_scale(a, a.F, face_scale);
+    same_device(a, a.bary, "bary"); same_device(a, a.corners, a.corner_name); same_device(a, a.opacity, "faces_opacity");
+    for (const OwnTensor& o : own) same_device(a, o.in, o.name);
+    same_device(a, face_scale, "face_scale");
     a.face = i32(a.face, "pix_to_face"); a.bary = f32(a.bary, "bary"); a.corners = i32(a.corners, a.corner_name);
     a.opacity = f32(a.opacity, "faces_opacity");
     for (const OwnTensor& o : own) o.out = f32(o.in, o.name);
     if (face_scale) a.scale = f32(*face_scale, "face_scale");
 }
 
-// The two upstreams of a backward call, grad_image [B,C,H,W] / grad_T [B,1,H,W], checked and contiguous; undefined: None = zero.
-std::pair<at::Tensor, at::Tensor> upstreams(const ListArgs& a, int64_t C, const std::optional<at::Tensor>& grad_image,
+// The two outputs of a compositing forward, image [B,C,H,W] and T [B,1,H,W] ...
+std::tuple<at::Tensor, at::Tensor> image_and_T(const Lists& a, int64_t C) {
+    return {at::empty({a.B, C, a.H, a.W}, f32_on(a.dev)), at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev))};
+}
+// ... and the two upstreams of its backward, grad_image [B,C,H,W] / grad_T [B,1,H,W], checked and contiguous; undefined: None = zero.
+std::pair<at::Tensor, at::Tensor> upstreams(const Lists& a, int64_t C, const std::optional<at::Tensor>& grad_image,
                                             const std::optional<at::Tensor>& grad_T) {
     at::Tensor gi, gt;
     if (grad_image) {
@@ -730,15 +782,13 @@ at::Tensor grad_if(bool need, at::IntArrayRef shape, c10::Device dev) { return n
 struct ShadeArgs : ListArgs { at::Tensor attrs; int64_t P = 0, C = 0; };
 
 ShadeArgs shade_args(In face, In bary, In faces, In faces_opacity, In vert_attrs, const std::optional<at::Tensor>& face_scale) {
-    if (!g_abi.composite_fragments)
-        err(g_abi.path + " does not export dmr_composite_fragments: rebuild it (python -m dmesh_renderer_amd.build)");
+    built(g_abi.composite_fragments, "dmr_composite_fragments");
     ShadeArgs a;
     list_dims(a, "composite_fragments", "faces", face, bary, faces, faces_opacity);
-    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
-    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1);
-    list_k(a);
-    if (a.C < 1 || a.C > 256) err("composite_fragments: C must be in 1..256, got " + std::to_string(a.C));
-    list_not_empty(a);
+    check_attrs(vert_attrs, a.P, a.C);
+    check_k(a);
+    check_c(a, a.C, 256);
+    check_not_empty(a);
     list_finish(a, face_scale, {{vert_attrs, "vert_attrs", a.attrs}});
     return a;
 }
@@ -748,7 +798,7 @@ std::tuple<at::Tensor, at::Tensor> composite_fragments(In face, In bary, In face
                                                        const std::optional<at::Tensor>& face_scale) {
     const ShadeArgs a = shade_args(face, bary, faces, faces_opacity, vert_attrs, face_scale);
     c10::DeviceGuard guard(a.dev);
-    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    auto [image, T] = image_and_T(a, a.C);
     if (g_abi.composite_fragments(a.B, a.K, a.H, a.W, a.P, a.F, a.C, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
                                   mptr<const int32_t>(a.corners), mptr<const float>(a.opacity), mptr<const float>(a.attrs), a.scale_ptr(),
                                   mptr<float>(image), mptr<float>(T), a.stream()))
@@ -779,17 +829,16 @@ struct TextureArgs : ListArgs { at::Tensor uvs, tex; int64_t Pu = 0, C = 0, Ht =
 
 TextureArgs texture_args(In face, In bary, In uv_faces, In faces_opacity, In vert_uvs, In texture, const std::optional<at::Tensor>& face_scale,
                          int wrap) {
-    if (!g_abi.composite_texture)
-        err(g_abi.path + " does not export dmr_composite_texture: rebuild it (python -m dmesh_renderer_amd.build)");
+    built(g_abi.composite_texture, "dmr_composite_texture");
     TextureArgs a;
     list_dims(a, "composite_texture", "uv_faces", face, bary, uv_faces, faces_opacity);
     if (vert_uvs.dim() != 2 || vert_uvs.size(1) != 2) err("vert_uvs must have dimensions (num_uvs, 2)");
     if (texture.dim() != 3) err("texture must have dimensions (Ht, Wt, C)");
     a.Pu = vert_uvs.size(0); a.Ht = texture.size(0); a.Wt = texture.size(1); a.C = texture.size(2); a.wrap = wrap;
-    list_k(a);
-    if (a.C < 1 || a.C > 32) err("composite_texture: C must be in 1..32, got " + std::to_string(a.C));
+    check_k(a);
+    check_c(a, a.C, 32);
     if (a.Ht < 1 || a.Wt < 1 || a.Ht >= ((int64_t)1 << 31) || a.Wt >= ((int64_t)1 << 31)) err("composite_texture: the texture must have at least one texel");
-    list_not_empty(a);
+    check_not_empty(a);
     if (wrap != 0 && wrap != 1) err("composite_texture: wrap must be 0 (clamp) or 1 (repeat), got " + std::to_string(wrap));
     list_finish(a, face_scale, {{vert_uvs, "vert_uvs", a.uvs}, {texture, "texture", a.tex}});
     return a;
@@ -800,7 +849,7 @@ std::tuple<at::Tensor, at::Tensor> composite_texture(In face, In bary, In uv_fac
                                                      const std::optional<at::Tensor>& face_scale, int wrap) {
     const TextureArgs a = texture_args(face, bary, uv_faces, faces_opacity, vert_uvs, texture, face_scale, wrap);
     c10::DeviceGuard guard(a.dev);
-    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    auto [image, T] = image_and_T(a, a.C);
     if (g_abi.composite_texture(a.B, a.K, a.H, a.W, a.Pu, a.F, a.C, a.Ht, a.Wt, a.wrap, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
                                 mptr<const int32_t>(a.corners), mptr<const float>(a.opacity), mptr<const float>(a.uvs), mptr<const float>(a.tex),
                                 a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
@@ -827,31 +876,20 @@ py::tuple composite_texture_backward(In face, In bary, In uv_faces, In faces_opa
     return py::make_tuple(or_none(d_op), or_none(d_uvs), or_none(d_tex), or_none(d_scale), or_none(d_bary));
 }
 
-// -- face_visibility: per-face visibility and coverage (dmesh_renderer_amd_visibility.h, fragments.face_visibility_fused).  It reads
-// the face ids and the opacities alone, so its checks are its own, in the order of fragments.py's: the lists' shape, K, the
-// opacities' and the pixel weights' shapes, one device, dtypes.
-struct VisArgs {
-    at::Tensor face, opacity, weight;  // weight: undefined = none
-    int64_t B = 0, K = 0, H = 0, W = 0, F = 0;
-    c10::Device dev{c10::kCPU};
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
-};
+// -- face_visibility: per-face visibility and coverage.  It reads the face ids and the opacities alone.
+struct VisArgs : Lists { at::Tensor opacity, weight; int64_t F = 0; };  // weight: undefined = none
 
 VisArgs vis_args(In face, In faces_opacity, const std::optional<at::Tensor>& pixel_weight) {
-    if (!g_abi.face_visibility)
-        err(g_abi.path + " does not export dmr_face_visibility: rebuild it (python -m dmesh_renderer_amd.build)");
+    built(g_abi.face_visibility, "dmr_face_visibility");
     VisArgs a;
-    a.dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
-    if (a.K < 1 || a.K > 32) err("face_visibility: K must be in 1..32, got " + std::to_string(a.K));
-    if (a.B < 1 || a.H < 1 || a.W < 1) err("face_visibility: empty fragment lists");
-    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
-    a.F = faces_opacity.size(0);
+    lists_begin(a, "face_visibility", face);
+    check_k(a);
+    check_not_empty(a);
+    a.F = check_opacity(faces_opacity);
     if (pixel_weight && (pixel_weight->dim() != 3 || pixel_weight->size(0) != a.B || pixel_weight->size(1) != a.H || pixel_weight->size(2) != a.W))
         err("pixel_weight must have dimensions (B, H, W) of pix_to_face's B, H, W");
-    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
-    if (pixel_weight && pixel_weight->device() != a.dev) err("pixel_weight must be on the device of pix_to_face");
+    same_device(a, faces_opacity, "faces_opacity");
+    same_device(a, pixel_weight, "pixel_weight");
     a.face = i32(face, "pix_to_face"); a.opacity = f32(faces_opacity, "faces_opacity");
     if (pixel_weight) a.weight = f32(*pixel_weight, "pixel_weight");
     return a;
@@ -889,37 +927,102 @@ py::tuple face_visibility_backward(In face, In faces_opacity, const std::optiona
     return py::make_tuple(or_none(d_op), or_none(d_pw));
 }
 
-// -- interpolate_fragments / composite_values: the two ends of a deferred shader (dmesh_renderer_amd_deferred.h,
-// fragments.interpolate_fused / composite_values_fused).  Neither fits list_dims -- one has no opacities, the other no
-// barycentrics and no corner table -- so their checks are their own, in the order of fragments.py's: the lists' shapes, K, the
-// unit's shapes, C, one device, dtypes.  ValuesArgs is a ListArgs (bary and corners undefined) for upstreams().
-struct InterpArgs {
-    at::Tensor face, bary, faces, attrs;
-    int64_t B = 0, K = 0, H = 0, W = 0, F = 0, P = 0, C = 0;
-    c10::Device dev{c10::kCPU};
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
-};
+// -- interpolate_fragments / composite_values, the two ends of a deferred shader on [B,K,C,H,W] planes, and pack_slots /
+// interpolate_packed / composite_values_packed, the same on [N,C] rows: row [B,K,H,W] and n_used [1] come from pack_slots.  A
+// packed argument block is the dense one and PackedRows; the two builders of a pair share the checks of the pair's own tensors.
+struct InterpArgs : Lists { at::Tensor bary, faces, attrs; int64_t F = 0, P = 0, C = 0; };
+struct ValuesArgs : Lists, Blend { at::Tensor values; int64_t C = 0; };
+struct PackedRows { at::Tensor row, n_used; int64_t N = 0; };
+struct PackedInterpArgs : InterpArgs, PackedRows {};
+struct PackedValuesArgs : ValuesArgs, PackedRows {};
+
+// face [B,K,H,W] with K in 1..32 and at least one pixel; row (if given) of its shape, n_used (if given) one element, on its device
+void packed_lists(Lists& a, PackedRows& r, const char* call, In face, const at::Tensor* row, const at::Tensor* n_used) {
+    built(g_abi.pack_slots, "dmr_pack_slots");
+    lists_begin(a, call, face);
+    if (row && (row->dim() != 4 || row->sizes() != face.sizes())) err("row must have the dimensions (B, K, H, W) of pix_to_face");
+    if (n_used && n_used->numel() != 1) err("n_used must have one element");
+    check_k(a);
+    check_not_empty(a);
+    if (a.B * a.K * a.H * a.W >= ((int64_t)1 << 31)) err(std::string(call) + ": B K H W must be below 2^31");
+    if (row) same_device(a, *row, "row");
+    if (n_used) same_device(a, *n_used, "n_used");
+    a.face = i32(face, "pix_to_face");
+    if (row) r.row = i32(*row, "row");
+    if (n_used) r.n_used = i32(*n_used, "n_used");
+}
+void check_rows(const Lists& a, int64_t N) {
+    if (N < 0 || N >= ((int64_t)1 << 31)) err(std::string(a.call) + ": rows must be in 0..2^31 - 1, got " + std::to_string(N));
+}
+
+// an interpolate call's own tensors: their shapes ...
+void interp_shapes(InterpArgs& a, In bary, In faces, In vert_attrs) {
+    check_bary(a, bary);
+    a.F = check_corners(faces, "faces");
+    check_attrs(vert_attrs, a.P, a.C);
+}
+// ... and, after the unit's size checks, one device, then dtypes (a packed call's face is contiguous already: packed_lists)
+void interp_finish(InterpArgs& a, In face, In bary, In faces, In vert_attrs) {
+    same_device(a, bary, "bary"); same_device(a, faces, "faces"); same_device(a, vert_attrs, "vert_attrs");
+    if (!a.face.defined()) a.face = i32(face, "pix_to_face");
+    a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(vert_attrs, "vert_attrs");
+}
+// what a composite_values call does after its size checks: face_scale's shape, one device, then dtypes
+void values_finish(ValuesArgs& a, In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    check_scale(a, a.F, face_scale);
+    same_device(a, faces_opacity, "faces_opacity"); same_device(a, values, "values"); same_device(a, face_scale, "face_scale");
+    if (!a.face.defined()) a.face = i32(face, "pix_to_face");
+    a.opacity = f32(faces_opacity, "faces_opacity"); a.values = f32(values, "values");
+    if (face_scale) a.scale = f32(*face_scale, "face_scale");
+}
 
 InterpArgs interp_args(In face, In bary, In faces, In vert_attrs) {
-    if (!g_abi.interpolate_fragments)
-        err(g_abi.path + " does not export dmr_interpolate_fragments: rebuild it (python -m dmesh_renderer_amd.build)");
+    built(g_abi.interpolate_fragments, "dmr_interpolate_fragments");
     InterpArgs a;
-    a.dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
-    if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
-        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
-    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
-    a.F = faces.size(0);
-    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
-    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1);
-    if (a.K < 1 || a.K > 32) err("interpolate_fragments: K must be in 1..32, got " + std::to_string(a.K));
-    if (a.C < 1 || a.C > 256) err("interpolate_fragments: C must be in 1..256, got " + std::to_string(a.C));
-    if (a.B < 1 || a.H < 1 || a.W < 1) err("interpolate_fragments: empty fragment lists");
-    if (bary.device() != a.dev) err("bary must be on the device of pix_to_face");
-    if (faces.device() != a.dev) err("faces must be on the device of pix_to_face");
-    if (vert_attrs.device() != a.dev) err("vert_attrs must be on the device of pix_to_face");
-    a.face = i32(face, "pix_to_face"); a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(vert_attrs, "vert_attrs");
+    lists_begin(a, "interpolate_fragments", face);
+    interp_shapes(a, bary, faces, vert_attrs);
+    check_k(a);
+    check_c(a, a.C, 256);
+    check_not_empty(a);
+    interp_finish(a, face, bary, faces, vert_attrs);
+    return a;
+}
+
+PackedInterpArgs packed_interp_args(In face, In bary, In row, In n_used, In faces, In vert_attrs, int64_t N) {
+    PackedInterpArgs a;
+    packed_lists(a, a, "interpolate_packed", face, &row, &n_used);
+    interp_shapes(a, bary, faces, vert_attrs);
+    a.N = N;
+    check_c(a, a.C, 256);
+    check_rows(a, N);
+    interp_finish(a, face, bary, faces, vert_attrs);
+    return a;
+}
+
+ValuesArgs values_args(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    built(g_abi.composite_values, "dmr_composite_values");
+    ValuesArgs a;
+    lists_begin(a, "composite_values", face);
+    a.F = check_opacity(faces_opacity);
+    if (values.dim() != 5 || values.size(0) != a.B || values.size(1) != a.K || values.size(3) != a.H || values.size(4) != a.W)
+        err("values must have dimensions (B, K, C, H, W) of pix_to_face's B, K, H, W");
+    a.C = values.size(2);
+    check_k(a);
+    check_c(a, a.C, 256);
+    check_not_empty(a);
+    values_finish(a, face, faces_opacity, values, face_scale);
+    return a;
+}
+
+PackedValuesArgs packed_values_args(In face, In row, const at::Tensor* n_used, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
+    PackedValuesArgs a;
+    packed_lists(a, a, "composite_values_packed", face, &row, n_used);
+    a.F = check_opacity(faces_opacity);
+    if (values.dim() != 2) err("values must have dimensions (rows, C)");
+    a.N = values.size(0); a.C = values.size(1);
+    check_c(a, a.C, 256);
+    check_rows(a, a.N);
+    values_finish(a, face, faces_opacity, values, face_scale);
     return a;
 }
 
@@ -950,39 +1053,11 @@ py::tuple interpolate_fragments_backward(In face, In bary, In faces, In vert_att
     return py::make_tuple(or_none(d_attrs), or_none(d_bary));
 }
 
-struct ValuesArgs : ListArgs { at::Tensor values; int64_t C = 0; };
-
-ValuesArgs values_args(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
-    if (!g_abi.composite_values)
-        err(g_abi.path + " does not export dmr_composite_values: rebuild it (python -m dmesh_renderer_amd.build)");
-    ValuesArgs a;
-    a.call = "composite_values"; a.corner_name = "";
-    a.dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
-    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
-    a.F = faces_opacity.size(0);
-    if (values.dim() != 5 || values.size(0) != a.B || values.size(1) != a.K || values.size(3) != a.H || values.size(4) != a.W)
-        err("values must have dimensions (B, K, C, H, W) of pix_to_face's B, K, H, W");
-    a.C = values.size(2);
-    list_k(a);
-    if (a.C < 1 || a.C > 256) err("composite_values: C must be in 1..256, got " + std::to_string(a.C));
-    list_not_empty(a);
-    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
-        err("face_scale must have dimensions (B, num_faces)");
-    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
-    if (values.device() != a.dev) err("values must be on the device of pix_to_face");
-    if (face_scale && face_scale->device() != a.dev) err("face_scale must be on the device of pix_to_face");
-    a.face = i32(face, "pix_to_face"); a.opacity = f32(faces_opacity, "faces_opacity"); a.values = f32(values, "values");
-    if (face_scale) a.scale = f32(*face_scale, "face_scale");
-    return a;
-}
-
 // -> (image [B,C,H,W], T [B,1,H,W])
 std::tuple<at::Tensor, at::Tensor> composite_values(In face, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
     const ValuesArgs a = values_args(face, faces_opacity, values, face_scale);
     c10::DeviceGuard guard(a.dev);
-    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    auto [image, T] = image_and_T(a, a.C);
     if (g_abi.composite_values(a.B, a.K, a.H, a.W, a.F, a.C, mptr<const int32_t>(a.face), in_ptr(a.opacity), mptr<const float>(a.values),
                                a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
         raise_lib();
@@ -1007,43 +1082,11 @@ py::tuple composite_values_backward(In face, In faces_opacity, In values, const 
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
-// -- pack_slots / interpolate_packed / composite_values_packed: the deferred shader's two ends on packed, channel-last rows
-// (dmesh_renderer_amd_packed.h, fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused).  The
-// lists' checks are interp_args' / values_args' in spirit, in fragments.py's order; row [B,K,H,W] and n_used [1] come from pack_slots.
-void packed_built() {
-    if (!g_abi.pack_slots) err(g_abi.path + " does not export dmr_pack_slots: rebuild it (python -m dmesh_renderer_amd.build)");
-}
-
-struct PackedLists {
-    at::Tensor face, row, n_used;
-    int64_t B = 0, K = 0, H = 0, W = 0;
-    c10::Device dev{c10::kCPU};
-    void* stream() const { return reinterpret_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream()); }
-};
-
-// face [B,K,H,W] with K in 1..32 and at least one pixel; row (if given) of its shape, n_used (if given) one element, on its device
-PackedLists packed_lists(const char* call, In face, const at::Tensor* row, const at::Tensor* n_used) {
-    packed_built();
-    PackedLists a;
-    a.dev = hip_device_of(face);
-    if (face.dim() != 4) err("pix_to_face must have dimensions (B, K, H, W)");
-    a.B = face.size(0); a.K = face.size(1); a.H = face.size(2); a.W = face.size(3);
-    if (row && (row->dim() != 4 || row->sizes() != face.sizes())) err("row must have the dimensions (B, K, H, W) of pix_to_face");
-    if (n_used && n_used->numel() != 1) err("n_used must have one element");
-    if (a.K < 1 || a.K > 32) err(std::string(call) + ": K must be in 1..32, got " + std::to_string(a.K));
-    if (a.B < 1 || a.H < 1 || a.W < 1) err(std::string(call) + ": empty fragment lists");
-    if (a.B * a.K * a.H * a.W >= ((int64_t)1 << 31)) err(std::string(call) + ": B K H W must be below 2^31");
-    if (row && row->device() != a.dev) err("row must be on the device of pix_to_face");
-    if (n_used && n_used->device() != a.dev) err("n_used must be on the device of pix_to_face");
-    a.face = i32(face, "pix_to_face");
-    if (row) a.row = i32(*row, "row");
-    if (n_used) a.n_used = i32(*n_used, "n_used");
-    return a;
-}
-
 // -> (row [B,K,H,W] int32, n_used [1] int32); a used slot (face id in [0, F)) whose row would be >= capacity gets -1
 std::tuple<at::Tensor, at::Tensor> pack_slots(In face, int64_t F, int64_t capacity) {
-    const PackedLists a = packed_lists("pack_slots", face, nullptr, nullptr);
+    Lists a;
+    PackedRows none;
+    packed_lists(a, none, "pack_slots", face, nullptr, nullptr);
     if (F < 0 || F >= ((int64_t)1 << 31)) err("pack_slots: F must be in 0..2^31 - 1, got " + std::to_string(F));
     if (capacity < 0) err("pack_slots: capacity must not be negative, got " + std::to_string(capacity));
     c10::DeviceGuard guard(a.dev);
@@ -1054,27 +1097,6 @@ std::tuple<at::Tensor, at::Tensor> pack_slots(In face, int64_t F, int64_t capaci
         raise_lib();
     return {row, n_used};
 }
-
-struct PackedInterpArgs : PackedLists { at::Tensor bary, faces, attrs; int64_t F = 0, P = 0, C = 0, N = 0; };
-
-PackedInterpArgs packed_interp_args(In face, In bary, In row, In n_used, In faces, In vert_attrs, int64_t N) {
-    PackedInterpArgs a;
-    static_cast<PackedLists&>(a) = packed_lists("interpolate_packed", face, &row, &n_used);
-    if (bary.dim() != 5 || bary.size(0) != a.B || bary.size(1) != a.K || bary.size(2) != 2 || bary.size(3) != a.H || bary.size(4) != a.W)
-        err("bary must have dimensions (B, K, 2, H, W) of pix_to_face's B, K, H, W");
-    if (faces.dim() != 2 || faces.size(1) != 3) err("faces must have dimensions (num_faces, 3)");
-    a.F = faces.size(0);
-    if (vert_attrs.dim() != 2) err("vert_attrs must have dimensions (num_points, C)");
-    a.P = vert_attrs.size(0); a.C = vert_attrs.size(1); a.N = N;
-    if (a.C < 1 || a.C > 256) err("interpolate_packed: C must be in 1..256, got " + std::to_string(a.C));
-    if (N < 0 || N >= ((int64_t)1 << 31)) err("interpolate_packed: rows must be in 0..2^31 - 1, got " + std::to_string(N));
-    if (bary.device() != a.dev) err("bary must be on the device of pix_to_face");
-    if (faces.device() != a.dev) err("faces must be on the device of pix_to_face");
-    if (vert_attrs.device() != a.dev) err("vert_attrs must be on the device of pix_to_face");
-    a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(vert_attrs, "vert_attrs");
-    return a;
-}
-
 // -> out [N,C]
 at::Tensor interpolate_packed(In face, In bary, In row, In n_used, In faces, In vert_attrs, int64_t N) {
     const PackedInterpArgs a = packed_interp_args(face, bary, row, n_used, faces, vert_attrs, N);
@@ -1101,35 +1123,11 @@ py::tuple interpolate_packed_backward(In face, In bary, In row, In n_used, In fa
     return py::make_tuple(or_none(d_attrs), or_none(d_bary));
 }
 
-// ListArgs for upstreams(); bary and corners stay undefined, row / n_used beside it
-struct PackedValuesArgs : ListArgs { at::Tensor row, n_used, values; int64_t C = 0, N = 0; };
-
-PackedValuesArgs packed_values_args(In face, In row, const at::Tensor* n_used, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
-    const PackedLists l = packed_lists("composite_values_packed", face, &row, n_used);
-    PackedValuesArgs a;
-    a.call = "composite_values_packed"; a.corner_name = "";
-    a.dev = l.dev; a.B = l.B; a.K = l.K; a.H = l.H; a.W = l.W; a.face = l.face; a.row = l.row; a.n_used = l.n_used;
-    if (faces_opacity.dim() != 1) err("faces_opacity must have dimensions (num_faces,)");
-    a.F = faces_opacity.size(0);
-    if (values.dim() != 2) err("values must have dimensions (rows, C)");
-    a.N = values.size(0); a.C = values.size(1);
-    if (a.C < 1 || a.C > 256) err("composite_values_packed: C must be in 1..256, got " + std::to_string(a.C));
-    if (a.N >= ((int64_t)1 << 31)) err("composite_values_packed: rows must be in 0..2^31 - 1, got " + std::to_string(a.N));
-    if (face_scale && (face_scale->dim() != 2 || face_scale->size(0) != a.B || face_scale->size(1) != a.F))
-        err("face_scale must have dimensions (B, num_faces)");
-    if (faces_opacity.device() != a.dev) err("faces_opacity must be on the device of pix_to_face");
-    if (values.device() != a.dev) err("values must be on the device of pix_to_face");
-    if (face_scale && face_scale->device() != a.dev) err("face_scale must be on the device of pix_to_face");
-    a.opacity = f32(faces_opacity, "faces_opacity"); a.values = f32(values, "values");
-    if (face_scale) a.scale = f32(*face_scale, "face_scale");
-    return a;
-}
-
 // -> (image [B,C,H,W], T [B,1,H,W])
 std::tuple<at::Tensor, at::Tensor> composite_values_packed(In face, In row, In faces_opacity, In values, const std::optional<at::Tensor>& face_scale) {
     const PackedValuesArgs a = packed_values_args(face, row, nullptr, faces_opacity, values, face_scale);
     c10::DeviceGuard guard(a.dev);
-    at::Tensor image = at::empty({a.B, a.C, a.H, a.W}, f32_on(a.dev)), T = at::empty({a.B, 1, a.H, a.W}, f32_on(a.dev));
+    auto [image, T] = image_and_T(a, a.C);
     if (g_abi.composite_values_packed(a.B, a.K, a.H, a.W, a.F, a.C, a.N, mptr<const int32_t>(a.face), mptr<const int32_t>(a.row), in_ptr(a.opacity),
                                       in_ptr(a.values), a.scale_ptr(), mptr<float>(image), mptr<float>(T), a.stream()))
         raise_lib();

@@ -11,7 +11,7 @@
 // A slot whose face id lies outside [0, F) is empty wherever it sits; the lists' count is not read.
 //
 // None of the arithmetic here decides an index or a branch another kernel depends on: it may contract to FMA.
-#include "dmr_shade_common.hpp"
+#include "dmr_deferred_common.hpp"  // (for its zeroing kernel)
 #include "../../include/dmesh_renderer_amd_visibility.h"
 
 namespace dmr {
@@ -191,22 +191,6 @@ int vis_params(const char* name, int B, int K, int H, int W, int F, const int32_
     return 0;
 }
 
-// Up to three buffers of n 4-byte words each zeroed by one launch (null: none): what the tiles add into.  A kernel, not
-// hipMemsetAsync: that is a fill kernel per buffer (k_tet_zero_grads, dmr_tet.hip), and as a node of a captured graph it left
-// small non-zero words behind from the second replay on (seen in max_weight and pixels; in a float sum they vanish).
-__global__ void __launch_bounds__(256)
-k_vis_zero(uint32_t* __restrict__ a, uint32_t* __restrict__ b, uint32_t* __restrict__ c, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (a) a[i] = 0u;
-    if (b) b[i] = 0u;
-    if (c) c[i] = 0u;
-}
-void zero_on(hipStream_t st, void* a, void* b, void* c, int64_t n) {
-    if (n <= 0 || (!a && !b && !c)) return;
-    k_vis_zero<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(static_cast<uint32_t*>(a), static_cast<uint32_t*>(b), static_cast<uint32_t*>(c), n);
-}
-
 }  // namespace
 }  // namespace dmr
 
@@ -222,7 +206,8 @@ int dmr_face_visibility(int B, int K, int H, int W, int F, const int32_t* face, 
     if (F == 0) return 0;  // [B,0] outputs: nothing to write
     if (!vis) return api_fail("dmr_face_visibility: null output");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    zero_on(st, vis, max_weight, pixels, (int64_t)B * F);
+    const int64_t n = (int64_t)B * F;
+    zero_on(st, vis, n, max_weight, n, pixels, n);  // (k_deferred_zero, dmr_deferred_common.hpp: a kernel, not hipMemsetAsync -- DESIGN.md 5e)
     if (launched(name)) return 1;
     const dim3 grid((unsigned)(B * p.gx * p.gy)), block(256);
     if (max_weight) k_face_visibility<true><<<grid, block, 0, st>>>(p, vis, max_weight, pixels);
@@ -241,7 +226,7 @@ int dmr_face_visibility_backward(int B, int K, int H, int W, int F, const int32_
     if (dL_dpixel_weight && !pixel_weight) return api_fail("dmr_face_visibility_backward: dL_dpixel_weight without pixel_weight");
     if (!dL_dfaces_opacity && !dL_dpixel_weight) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    zero_on(st, dL_dfaces_opacity, nullptr, nullptr, F);  // (one buffer for all views: the tiles add into it)
+    zero_on(st, dL_dfaces_opacity, F, nullptr, 0, nullptr, 0);  // (one buffer for all views: the tiles add into it)
     if (launched(name)) return 1;
     if (F == 0 && !dL_dpixel_weight) return 0;
     // (F == 0 with dL_dpixel_weight: every slot is empty, and the kernel stores the zeros)

@@ -437,48 +437,65 @@ def face_visibility_fused(frag, faces_opacity: th.Tensor, F: int, pixel_weight: 
 
 
 class _InterpolateFn(th.autograd.Function):
-    """interpolate_fused's one Function over _C.interpolate_fragments / _C.interpolate_fragments_backward.  Arguments: pix_to_face,
-    bary, faces, vert_attrs."""
+    """The one Function of interpolate_fused (over _C.interpolate_fragments / _C.interpolate_fragments_backward) and of
+    interpolate_packed_fused (over _C.interpolate_packed / _C.interpolate_packed_backward).  Arguments: pix_to_face, bary, faces,
+    vert_attrs, and the packed call's row, n_used, rows -- three None for the dense one."""
 
     @staticmethod
-    def forward(ctx, face, bary, faces, vert_attrs):
-        out = _fused_kernels("interpolate").interpolate_fragments(face, bary, faces, vert_attrs)
-        ctx.save_for_backward(face, bary, faces, vert_attrs)
+    def forward(ctx, face, bary, faces, vert_attrs, row, n_used, rows):
+        if row is None:
+            out = _fused_kernels("interpolate").interpolate_fragments(face, bary, faces, vert_attrs)
+        else:
+            out = _fused_kernels("interpolate_packed").interpolate_packed(face, bary, row, n_used, faces, vert_attrs, rows)
+        ctx.save_for_backward(face, bary, faces, vert_attrs, *(() if row is None else (row, n_used)))
         ctx.set_materialize_grads(False)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        face, bary, faces, vert_attrs = ctx.saved_tensors
+        face, bary, faces, vert_attrs, *packed = ctx.saved_tensors
         need = (ctx.needs_input_grad[3], ctx.needs_input_grad[1])  # (vert_attrs, bary)
         if grad_out is None or not any(need):
-            return (None,) * 4
-        d_attrs, d_bary = _fused_kernels("interpolate").interpolate_fragments_backward(face, bary, faces, vert_attrs, grad_out.contiguous(), need)
-        return None, d_bary, None, d_attrs
+            return (None,) * 7
+        if packed:
+            d_attrs, d_bary = _fused_kernels("interpolate_packed").interpolate_packed_backward(face, bary, *packed, faces, vert_attrs,
+                                                                                             grad_out.contiguous(), need)
+        else:
+            d_attrs, d_bary = _fused_kernels("interpolate").interpolate_fragments_backward(face, bary, faces, vert_attrs, grad_out.contiguous(), need)
+        return None, d_bary, None, d_attrs, None, None, None
 
 
 class _CompositeValuesFn(th.autograd.Function):
-    """composite_values_fused's one Function over _C.composite_values / _C.composite_values_backward.  Arguments: pix_to_face,
-    faces_opacity, values, face_scale (a tensor or None)."""
+    """The one Function of composite_values_fused (over _C.composite_values / _C.composite_values_backward) and of
+    composite_values_packed_fused (over _C.composite_values_packed / _C.composite_values_packed_backward).  Arguments: pix_to_face,
+    faces_opacity, values, face_scale (a tensor or None), and the packed call's row, n_used -- two None for the dense one."""
 
     @staticmethod
-    def forward(ctx, face, faces_opacity, values, face_scale):
-        image, t = _fused_kernels("composite_values").composite_values(face, faces_opacity, values, face_scale)
-        ctx.save_for_backward(face, faces_opacity, values, *(() if face_scale is None else (face_scale,)))
+    def forward(ctx, face, faces_opacity, values, face_scale, row, n_used):
+        if row is None:
+            image, t = _fused_kernels("composite_values").composite_values(face, faces_opacity, values, face_scale)
+        else:
+            image, t = _fused_kernels("composite_values_packed").composite_values_packed(face, row, faces_opacity, values, face_scale)
+        ctx.packed = row is not None
+        ctx.save_for_backward(face, faces_opacity, values, *((row, n_used) if ctx.packed else ()), *(() if face_scale is None else (face_scale,)))
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
         return image, t
 
     @staticmethod
     def backward(ctx, grad_image, grad_t):
-        face, faces_opacity, values, *scale = ctx.saved_tensors
-        need = ctx.needs_input_grad  # (face, faces_opacity, values, face_scale)
+        face, faces_opacity, values, *rest = ctx.saved_tensors
+        packed, scale = (rest[:2], rest[2:]) if ctx.packed else ([], rest)
+        need = ctx.needs_input_grad  # (face, faces_opacity, values, face_scale, row, n_used)
         need = (need[1], need[2], bool(scale) and need[3])
         if (grad_image is None and grad_t is None) or not any(need):
-            return (None,) * 4
-        d_op, d_values, d_scale = _fused_kernels("composite_values").composite_values_backward(
-            face, faces_opacity, values, scale[0] if scale else None,
-            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
-        return None, d_op, d_values, d_scale
+            return (None,) * 6
+        tail = (faces_opacity, values, scale[0] if scale else None,
+                None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
+        if packed:
+            d_op, d_values, d_scale = _fused_kernels("composite_values_packed").composite_values_packed_backward(face, *packed, *tail)
+        else:
+            d_op, d_values, d_scale = _fused_kernels("composite_values").composite_values_backward(face, *tail)
+        return None, d_op, d_values, d_scale, None, None
 
 
 def _check_lists(name: str, frag, bary_wanted: bool):
@@ -509,6 +526,61 @@ def _check_tensors(name: str, torch_path: str, face, ints, floats):
             raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
 
 
+def _check_packed(name: str, torch_path: str, frag, packed) -> int:
+    """packed.row of pix_to_face's shape, one n_used, rows an int >= 0 (ValueError); both int32 on the lists' device (TypeError)
+    -> rows."""
+    face = frag.pix_to_face
+    if tuple(packed.row.shape) != tuple(face.shape):
+        raise ValueError(f"{name}: packed.row must have frag.pix_to_face's shape {tuple(face.shape)}, got {tuple(packed.row.shape)}")
+    if packed.n_used.numel() != 1:
+        raise ValueError(f"{name}: packed.n_used must hold one element, got {tuple(packed.n_used.shape)}")
+    if isinstance(packed.rows, bool) or not isinstance(packed.rows, int) or packed.rows < 0:
+        raise ValueError(f"{name}: packed.rows must be a non-negative int, got {packed.rows!r}")
+    for n, t in (("packed.row", packed.row), ("packed.n_used", packed.n_used)):
+        if t.dtype != th.int32:
+            raise TypeError(f"{name}: {n} must be int32, got {t.dtype}; {torch_path}")
+    return packed.rows
+
+
+def _check_interpolate(name: str, torch_path: str, frag, faces, vert_attrs, packed=None):
+    """What interpolate_fused and (packed: a PackedSlots) interpolate_packed_fused refuse, in the order they refuse it
+    -> packed.rows, or None."""
+    _check_lists(name, frag, True)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    if vert_attrs.dim() != 2:
+        raise ValueError(f"{name}: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
+    if not 1 <= vert_attrs.shape[1] <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {vert_attrs.shape[1]}")
+    rows = None if packed is None else _check_packed(name, torch_path, frag, packed)
+    ints = [("faces", faces)] + ([] if packed is None else [("packed.row", packed.row), ("packed.n_used", packed.n_used)])
+    _check_tensors(name, torch_path, frag.pix_to_face, ints, [("frag.bary", frag.bary), ("vert_attrs", vert_attrs)])
+    return rows
+
+
+def _check_composite_values(name: str, torch_path: str, frag, faces_opacity, values, face_scale, packed=None):
+    """What composite_values_fused (values [B,K,C,H,W]) and (packed: a PackedSlots) composite_values_packed_fused (values
+    [packed.rows, C]) refuse, in the order they refuse it."""
+    B, K, H, W = _check_lists(name, frag, False)
+    if faces_opacity.dim() != 1:
+        raise ValueError(f"{name}: faces_opacity must be [F], got {tuple(faces_opacity.shape)}")
+    F = faces_opacity.shape[0]
+    if packed is None:
+        if values.dim() != 5 or tuple(values.shape[:2]) != (B, K) or tuple(values.shape[3:]) != (H, W):
+            raise ValueError(f"{name}: values must be [B,K,C,H,W] = {(B, K, 'C', H, W)}, got {tuple(values.shape)}")
+    else:
+        rows = _check_packed(name, torch_path, frag, packed)
+        if values.dim() != 2 or values.shape[0] != rows:
+            raise ValueError(f"{name}: values must be [packed.rows, C] = {(rows, 'C')}, got {tuple(values.shape)}")
+    C = values.shape[2 if packed is None else 1]
+    if not 1 <= C <= 256:
+        raise ValueError(f"{name}: C must be in 1..256, got {C}")
+    if face_scale is not None and tuple(face_scale.shape) != (B, F):
+        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
+    floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
+    _check_tensors(name, torch_path, frag.pix_to_face, [] if packed is None else [("packed.row", packed.row), ("packed.n_used", packed.n_used)], floats)
+
+
 def interpolate_fused(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
     """interpolate(...) as one HIP kernel, and one for its backward: the same [B,K,C,H,W], 0 in empty slots, without the
     [B,K,H,W,3,C] gather interpolate keeps for autograd and without its index_put backward.  Gradients to vert_attrs and (with the
@@ -518,15 +590,8 @@ def interpolate_fused(frag, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tenso
     integer dtype are cast): anything else is a TypeError -- interpolate is the torch path for it; nothing falls back silently."""
     name, torch_path = "interpolate_fused", "fragments.interpolate is the torch path for anything else"
     _fused_kernels("interpolate")
-    _check_lists(name, frag, True)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
-    if vert_attrs.dim() != 2:
-        raise ValueError(f"{name}: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
-    if not 1 <= vert_attrs.shape[1] <= 256:
-        raise ValueError(f"{name}: C must be in 1..256, got {vert_attrs.shape[1]}")
-    _check_tensors(name, torch_path, frag.pix_to_face, [("faces", faces)], [("frag.bary", frag.bary), ("vert_attrs", vert_attrs)])
-    return _InterpolateFn.apply(frag.pix_to_face, frag.bary, faces.to(th.int32), vert_attrs)
+    _check_interpolate(name, torch_path, frag, faces, vert_attrs)
+    return _InterpolateFn.apply(frag.pix_to_face, frag.bary, faces.to(th.int32), vert_attrs, None, None, None)
 
 
 def composite_values_fused(frag, faces_opacity: th.Tensor, values: th.Tensor,
@@ -541,19 +606,8 @@ def composite_values_fused(frag, faces_opacity: th.Tensor, values: th.Tensor,
     the torch path for it; nothing falls back silently."""
     name, torch_path = "composite_values_fused", "fragments.composite_values is the torch path for anything else"
     _fused_kernels("composite_values")
-    B, K, H, W = _check_lists(name, frag, False)
-    if faces_opacity.dim() != 1:
-        raise ValueError(f"{name}: faces_opacity must be [F], got {tuple(faces_opacity.shape)}")
-    F = faces_opacity.shape[0]
-    if values.dim() != 5 or tuple(values.shape[:2]) != (B, K) or tuple(values.shape[3:]) != (H, W):
-        raise ValueError(f"{name}: values must be [B,K,C,H,W] = {(B, K, 'C', H, W)}, got {tuple(values.shape)}")
-    if not 1 <= values.shape[2] <= 256:
-        raise ValueError(f"{name}: C must be in 1..256, got {values.shape[2]}")
-    if face_scale is not None and tuple(face_scale.shape) != (B, F):
-        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
-    floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
-    _check_tensors(name, torch_path, frag.pix_to_face, [], floats)
-    return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale)
+    _check_composite_values(name, torch_path, frag, faces_opacity, values, face_scale)
+    return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale, None, None)
 
 
 # ---------------------------------------------------------------------------
@@ -641,22 +695,6 @@ def composite_values_packed(frag, packed: PackedSlots, faces_opacity: th.Tensor,
     return composite_values(frag._replace(pix_to_face=face), faces_opacity, unpack_values(frag, packed, values), face_scale)
 
 
-def _check_packed(name: str, torch_path: str, frag, packed) -> int:
-    """packed.row of pix_to_face's shape, one n_used, rows an int >= 0 (ValueError); both int32 on the lists' device (TypeError)
-    -> rows."""
-    face = frag.pix_to_face
-    if tuple(packed.row.shape) != tuple(face.shape):
-        raise ValueError(f"{name}: packed.row must have frag.pix_to_face's shape {tuple(face.shape)}, got {tuple(packed.row.shape)}")
-    if packed.n_used.numel() != 1:
-        raise ValueError(f"{name}: packed.n_used must hold one element, got {tuple(packed.n_used.shape)}")
-    if isinstance(packed.rows, bool) or not isinstance(packed.rows, int) or packed.rows < 0:
-        raise ValueError(f"{name}: packed.rows must be a non-negative int, got {packed.rows!r}")
-    for n, t in (("packed.row", packed.row), ("packed.n_used", packed.n_used)):
-        if t.dtype != th.int32:
-            raise TypeError(f"{name}: {n} must be int32, got {t.dtype}; {torch_path}")
-    return packed.rows
-
-
 def pack_slots_fused(frag, F: int, capacity: Optional[int] = None) -> PackedSlots:
     """pack_slots(...) as three stream-ordered HIP launches (per-workgroup counts, one workgroup's scan, the rows): the same
     row, n_used and rows, exactly.  capacity=None waits for the device once, to read the count (under stream capture a
@@ -677,52 +715,6 @@ def pack_slots_fused(frag, F: int, capacity: Optional[int] = None) -> PackedSlot
     return PackedSlots(row, n_used, int(n_used.item()) if capacity is None else capacity)
 
 
-class _InterpolatePackedFn(th.autograd.Function):
-    """interpolate_packed_fused's one Function over _C.interpolate_packed / _C.interpolate_packed_backward.  Arguments: pix_to_face,
-    bary, row, n_used, faces, vert_attrs, rows."""
-
-    @staticmethod
-    def forward(ctx, face, bary, row, n_used, faces, vert_attrs, rows):
-        out = _fused_kernels("interpolate_packed").interpolate_packed(face, bary, row, n_used, faces, vert_attrs, rows)
-        ctx.save_for_backward(face, bary, row, n_used, faces, vert_attrs)
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        face, bary, row, n_used, faces, vert_attrs = ctx.saved_tensors
-        need = (ctx.needs_input_grad[5], ctx.needs_input_grad[1])  # (vert_attrs, bary)
-        if grad_out is None or not any(need):
-            return (None,) * 7
-        d_attrs, d_bary = _fused_kernels("interpolate_packed").interpolate_packed_backward(face, bary, row, n_used, faces, vert_attrs,
-                                                                                         grad_out.contiguous(), need)
-        return None, d_bary, None, None, None, d_attrs, None
-
-
-class _CompositeValuesPackedFn(th.autograd.Function):
-    """composite_values_packed_fused's one Function over _C.composite_values_packed / _C.composite_values_packed_backward.
-    Arguments: pix_to_face, row, n_used, faces_opacity, values, face_scale (a tensor or None)."""
-
-    @staticmethod
-    def forward(ctx, face, row, n_used, faces_opacity, values, face_scale):
-        image, t = _fused_kernels("composite_values_packed").composite_values_packed(face, row, faces_opacity, values, face_scale)
-        ctx.save_for_backward(face, row, n_used, faces_opacity, values, *(() if face_scale is None else (face_scale,)))
-        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no zeros
-        return image, t
-
-    @staticmethod
-    def backward(ctx, grad_image, grad_t):
-        face, row, n_used, faces_opacity, values, *scale = ctx.saved_tensors
-        need = ctx.needs_input_grad  # (face, row, n_used, faces_opacity, values, face_scale)
-        need = (need[3], need[4], bool(scale) and need[5])
-        if (grad_image is None and grad_t is None) or not any(need):
-            return (None,) * 6
-        d_op, d_values, d_scale = _fused_kernels("composite_values_packed").composite_values_packed_backward(
-            face, row, n_used, faces_opacity, values, scale[0] if scale else None,
-            None if grad_image is None else grad_image.contiguous(), None if grad_t is None else grad_t.contiguous(), need)
-        return None, None, None, d_op, d_values, d_scale
-
-
 def interpolate_packed_fused(frag, packed: PackedSlots, faces: th.Tensor, vert_attrs: th.Tensor) -> th.Tensor:
     """interpolate_packed(...) as one HIP kernel, and one for its backward: the same [N,C] channel-last rows, what nn.Linear
     takes, without the [B,K,C,H,W] tensor and its permute.  A slot counts only if 0 <= row < N and its face id lies in [0, F): a
@@ -734,19 +726,10 @@ def interpolate_packed_fused(frag, packed: PackedSlots, faces: th.Tensor, vert_a
     on one device only: anything else is a TypeError -- interpolate_packed is the torch path for it; nothing falls back silently."""
     name, torch_path = "interpolate_packed_fused", "fragments.interpolate_packed is the torch path for anything else"
     _fused_kernels("interpolate_packed")
-    _check_lists(name, frag, True)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
-    if vert_attrs.dim() != 2:
-        raise ValueError(f"{name}: vert_attrs must be [P,C], got {tuple(vert_attrs.shape)}")
-    if not 1 <= vert_attrs.shape[1] <= 256:
-        raise ValueError(f"{name}: C must be in 1..256, got {vert_attrs.shape[1]}")
-    rows = _check_packed(name, torch_path, frag, packed)
-    _check_tensors(name, torch_path, frag.pix_to_face, [("faces", faces), ("packed.row", packed.row), ("packed.n_used", packed.n_used)],
-                   [("frag.bary", frag.bary), ("vert_attrs", vert_attrs)])
+    rows = _check_interpolate(name, torch_path, frag, faces, vert_attrs, packed)
     if rows == 0:
         return vert_attrs.new_zeros((0, vert_attrs.shape[1]))
-    return _InterpolatePackedFn.apply(frag.pix_to_face, frag.bary, packed.row, packed.n_used, faces.to(th.int32), vert_attrs, rows)
+    return _InterpolateFn.apply(frag.pix_to_face, frag.bary, faces.to(th.int32), vert_attrs, packed.row, packed.n_used, rows)
 
 
 def composite_values_packed_fused(frag, packed: PackedSlots, faces_opacity: th.Tensor, values: th.Tensor,
@@ -760,17 +743,5 @@ def composite_values_packed_fused(frag, packed: PackedSlots, faces_opacity: th.T
     anything else is a TypeError -- composite_values_packed is the torch path for it; nothing falls back silently."""
     name, torch_path = "composite_values_packed_fused", "fragments.composite_values_packed is the torch path for anything else"
     _fused_kernels("composite_values_packed")
-    B, K, H, W = _check_lists(name, frag, False)
-    if faces_opacity.dim() != 1:
-        raise ValueError(f"{name}: faces_opacity must be [F], got {tuple(faces_opacity.shape)}")
-    F = faces_opacity.shape[0]
-    rows = _check_packed(name, torch_path, frag, packed)
-    if values.dim() != 2 or values.shape[0] != rows:
-        raise ValueError(f"{name}: values must be [packed.rows, C] = {(rows, 'C')}, got {tuple(values.shape)}")
-    if not 1 <= values.shape[1] <= 256:
-        raise ValueError(f"{name}: C must be in 1..256, got {values.shape[1]}")
-    if face_scale is not None and tuple(face_scale.shape) != (B, F):
-        raise ValueError(f"{name}: face_scale must be [B,F] = {(B, F)}, got {tuple(face_scale.shape)}")
-    floats = [("faces_opacity", faces_opacity), ("values", values)] + ([] if face_scale is None else [("face_scale", face_scale)])
-    _check_tensors(name, torch_path, frag.pix_to_face, [("packed.row", packed.row), ("packed.n_used", packed.n_used)], floats)
-    return _CompositeValuesPackedFn.apply(frag.pix_to_face, packed.row, packed.n_used, faces_opacity, values, face_scale)
+    _check_composite_values(name, torch_path, frag, faces_opacity, values, face_scale, packed)
+    return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale, packed.row, packed.n_used)

@@ -11,11 +11,15 @@ from shading_cases import EDGE_FRAMES, FRAME, MERGE_FRAME, NEW_FRAME, SIZES, KMA
 # The host dispatch of dmr_interp.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_deferred_cpu.py fails
 # when one of them is no longer in the file exactly once: then this follows the new dispatch.  (with_kmax and shade_vec are
 # dmr_shade_common.hpp's, restated in shading_cases.kmax_of / vec_of and pinned by tests/test_shading_coverage_cpu.py.)
+# COMMON_DISPATCH_LINES: the same for what this unit and the packed one (tests/packed_cases.py) take from COMMON_HEADER.
 # ---------------------------------------------------------------------------
 DEFER_MAX_C = 256
+COMMON_HEADER = "dmr_deferred_common.hpp"
+COMMON_DISPATCH_LINES = [
+    "p.vec = shade_vec(C, vert_attrs);",
+]
 DISPATCH_LINES = [
     "constexpr int DEFER_MAX_C = 256;",
-    "p.vec = shade_vec(C, vert_attrs);",
     "if (C <= 4) k_interpolate_fragments<4><<<rows, block, 0, st>>>(p, out);",
     "else k_interpolate_fragments<8><<<rows, block, 0, st>>>(p, out);",
     "if (C <= 4) k_interpolate_fragments_backward<4><<<groups, block, 0, st>>>(p, grad_out, dL_dvert_attrs, dL_dbary);",
@@ -30,17 +34,17 @@ DISPATCH_LINES = [
 
 
 def interp_ch(C):
-    """dmr_interpolate_fragments and its backward: if (C <= 4) <4> else <8>."""
+    """dmr_interpolate_fragments, dmr_interpolate_packed and their backwards: if (C <= 4) <4> else <8>."""
     return 4 if C <= 4 else 8
 
 
 def values_forward_ch(C):
-    """dmr_composite_values: if (C <= 4) k_composite_values<4> else k_composite_values<16>."""
+    """dmr_composite_values and dmr_composite_values_packed: if (C <= 4) <4> else <16>."""
     return 4 if C <= 4 else 16
 
 
 def values_backward_ch(C):
-    """launch_values_backward: if (p.C <= 4) <KMAX, 4> else <KMAX, 8>."""
+    """launch_values_backward and launch_packed_values_backward: if (p.C <= 4) <KMAX, 4> else <KMAX, 8>."""
     return 4 if C <= 4 else 8
 
 

@@ -6,12 +6,15 @@ shading_cases.py's frames and sizes.
 """
 from collections import namedtuple
 
+from deferred_cases import COMMON_DISPATCH_LINES, COMMON_HEADER, interp_ch, values_backward_ch, values_forward_ch  # noqa: F401
 from shading_cases import EDGE_FRAMES, FRAME, NEW_FRAME, SIZES, KMAXES, kmax_of, smallest_k, vec_of  # noqa: F401
 
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_packed.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_packed_cpu.py fails
 # when one of them is no longer in the file exactly once: then this follows the new dispatch.  (with_kmax and shade_vec are
 # dmr_shade_common.hpp's, restated in shading_cases.kmax_of / vec_of and pinned by tests/test_shading_coverage_cpu.py.)
+# The channel chunks (interp_ch, values_forward_ch, values_backward_ch) are the dense unit's, and so are deferred_cases' functions:
+# the lines below pin that this unit's dispatch has the same thresholds.  COMMON_DISPATCH_LINES: what both take from COMMON_HEADER.
 # ---------------------------------------------------------------------------
 PACKED_MAX_C = 256
 PACK_SLOTS = 2048    # slots of the flattened lists per workgroup of k_pack_count / k_pack_write
@@ -20,7 +23,6 @@ DISPATCH_LINES = [
     "constexpr int PACKED_MAX_C = 256;",
     "constexpr int PACK_PASSES = 8, PACK_SLOTS = 256 * PACK_PASSES, PACK_SCAN = 256;",
     "const int groups = (int)((slots + PACK_SLOTS - 1) / PACK_SLOTS);",
-    "p.vec = shade_vec(C, vert_attrs);",
     "p.rvec = shade_vec(C, values);",
     "if (C <= 4) k_interpolate_packed<4, false><<<rows, block, 0, st>>>(p, main_groups, out);",
     "constexpr int PLAIN_MAX_C = 8, STAGE_MAX_C = 32, STAGE_ROW = STAGE_MAX_C + 1;",
@@ -46,24 +48,9 @@ def pack_groups(slots):
 PLAIN_MAX_C, STAGE_MAX_C = 8, 32
 
 
-def interp_ch(C):
-    """dmr_interpolate_packed and its backward: if (C <= 4) <4> else <8>."""
-    return 4 if C <= 4 else 8
-
-
 def interp_via_lds(C):
     """dmr_interpolate_packed's store shape: rows transposed through LDS where a row is more than one chunk and fits the stage."""
     return PLAIN_MAX_C < C <= STAGE_MAX_C
-
-
-def values_forward_ch(C):
-    """dmr_composite_values_packed: if (C <= 4) <4> else <16>."""
-    return 4 if C <= 4 else 16
-
-
-def values_backward_ch(C):
-    """launch_packed_values_backward: if (p.C <= 4) <KMAX, 4> else <KMAX, 8>."""
-    return 4 if C <= 4 else 8
 
 
 # One forward + backward of BOTH pairs as the dispatch sees it.  aligned: the base of vert_attrs (interpolate: p.vec) and of

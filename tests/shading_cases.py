@@ -240,7 +240,10 @@ EDGES = {
 # ---------------------------------------------------------------------------
 def binding_refusals(unit, dev):
     """[(case, name of the call in _C, positional arguments)] for unit "shade" / "texture": every case through the forward
-    call and through the backward call (need: nothing, so that a call that were not refused would return before its memsets)."""
+    call and through the backward call (need: nothing, so that a call that were not refused would return before its memsets).
+    "visibility" / "deferred" / "packed": the tables of LIST_REFUSALS below."""
+    if unit in LIST_REFUSALS:
+        return LIST_REFUSALS[unit](dev)
     z = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype, device=dev)
     good = dict(face=z(1, 1, 1, 1, dtype=th.int32), bary=z(1, 1, 2, 1, 1), corners=th.tensor([[0, 1, 2]], dtype=th.int32, device=dev),
                 opacity=z(1) + 0.5, scale=None, grad_image=z(1, 3, 1, 1), grad_T=z(1, 1, 1, 1))
@@ -288,3 +291,206 @@ def binding_refusals(unit, dev):
                 tail = ([a["wrap"]] if unit == "texture" else []) + ([a["grad_image"], a["grad_T"], a["need"]] if call.endswith("_backward") else [])
                 out.append((case, call, lists + tail))
     return out
+
+
+# ---------------------------------------------------------------------------
+# The same for the units over the lists alone (face_visibility*), the deferred pair (interpolate_fragments*, composite_values*)
+# and its packed twin (pack_slots, interpolate_packed*, composite_values_packed*): F = 1, P = 3, C = 3, N = 1.  The expected
+# messages (tests/golden/shading_refusals.json, "binding") are a record of the binding on the GPU before the six argument
+# builders of these units were put together from shared checks.  A case's name starts with the family of calls it goes
+# through; "A with B" is two wrong arguments, and says which check comes first.
+# ---------------------------------------------------------------------------
+def _refusals(good, families):
+    """families: [(prefix, {call: argument names}, cases, backward_only)] -> [(case, call, positional arguments)]; a call whose
+    name ends in _backward is a backward call, and takes the cases of both tables."""
+    out = []
+    for prefix, calls, cases, backward_only in families:
+        for table, only_backward in ((cases, False), (backward_only, True)):
+            for case, changes in table.items():
+                a = dict(good)
+                a.update(changes)
+                for call, names in calls.items():
+                    if call.endswith("_backward") or not only_backward:
+                        out.append((prefix + ": " + case, call, [a[n] for n in names]))
+    return out
+
+
+def _visibility_refusals(dev):
+    z = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype, device=dev)
+    good = dict(face=z(1, 1, 1, 1, dtype=th.int32), opacity=z(1) + 0.5, weight=None, coverage=False, grad_vis=z(1, 1), need=(False, False))
+    calls = {"face_visibility": ("face", "opacity", "weight", "coverage"),
+             "face_visibility_backward": ("face", "opacity", "weight", "grad_vis", "need")}
+    k33 = dict(face=z(1, 33, 1, 1, dtype=th.int32))
+    cases = {
+        "pix_to_face on the CPU": dict(face=good["face"].cpu()),
+        "pix_to_face with three dimensions": dict(face=good["face"][0]),
+        "K = 33": k33,
+        "K = 0": dict(face=z(1, 0, 1, 1, dtype=th.int32)),
+        "empty fragment lists": dict(face=z(1, 1, 0, 1, dtype=th.int32)),
+        "faces_opacity with two dimensions": dict(opacity=z(1, 1)),
+        "pixel_weight of another shape": dict(weight=z(1, 1, 2)),
+        "faces_opacity on the CPU": dict(opacity=th.zeros(1)),
+        "pixel_weight on the CPU": dict(weight=th.zeros(1, 1, 1)),
+        "pix_to_face int64": dict(face=good["face"].long()),
+        "faces_opacity float64": dict(opacity=good["opacity"].double()),
+        "K = 33 with faces_opacity with two dimensions": dict(k33, opacity=z(1, 1)),
+        "empty fragment lists with faces_opacity with two dimensions": dict(face=z(1, 1, 0, 1, dtype=th.int32), opacity=z(1, 1)),
+        "pixel_weight of another shape with faces_opacity on the CPU": dict(weight=z(1, 1, 2), opacity=th.zeros(1)),
+    }
+    backward_only = {
+        "need pixel_weight without pixel_weight": dict(need=(False, True)),
+        "grad_vis of another shape": dict(grad_vis=z(1, 2)),
+        "grad_vis on the CPU": dict(grad_vis=th.zeros(1, 1)),
+    }
+    return _refusals(good, [("face_visibility", calls, cases, backward_only)])
+
+
+def _interp_cases(z, good, k):
+    """The cases both interpolate pairs share.  k(K): the lists of K slots as changes."""
+    return {
+        "pix_to_face on the CPU": dict(face=good["face"].cpu()),
+        "pix_to_face with three dimensions": dict(face=good["face"][0]),
+        "bary of another shape": dict(bary=z(1, 1, 3, 1, 1)),
+        "faces [F,2]": dict(faces=good["faces"][:, :2]),
+        "vert_attrs with one dimension": dict(attrs=z(3)),
+        "K = 33": k(33),
+        "K = 0": k(0),
+        "C = 257": dict(attrs=z(3, 257)),
+        "C = 0": dict(attrs=z(3, 0)),
+        "bary on the CPU": dict(bary=good["bary"].cpu()),
+        "faces on the CPU": dict(faces=good["faces"].cpu()),
+        "vert_attrs on the CPU": dict(attrs=th.zeros(3, 3)),
+        "bary float64": dict(bary=good["bary"].double()),
+        "pix_to_face int64": dict(face=good["face"].long()),
+        "K = 33 with C = 257": dict(k(33), attrs=z(3, 257)),
+        "C = 257 with vert_attrs on the CPU": dict(attrs=th.zeros(3, 257)),
+        "K = 0 with bary on the CPU": {n: (t.cpu() if n == "bary" else t) for n, t in k(0).items()},
+    }
+
+
+def _values_cases(z, good, k, values_of):
+    """The cases both composite_values pairs share.  values_of(C): values of C channels."""
+    return {
+        "pix_to_face on the CPU": dict(face=good["face"].cpu()),
+        "pix_to_face with three dimensions": dict(face=good["face"][0]),
+        "faces_opacity with two dimensions": dict(opacity=z(1, 1)),
+        "K = 33": k(33),
+        "K = 0": k(0),
+        "C = 257": dict(values=values_of(257)),
+        "C = 0": dict(values=values_of(0)),
+        "face_scale of another shape": dict(scale=z(1, 2)),
+        "faces_opacity on the CPU": dict(opacity=th.zeros(1)),
+        "values on the CPU": dict(values=good["values"].cpu()),
+        "face_scale on the CPU": dict(scale=th.zeros(1, 1)),
+        "values float64": dict(values=good["values"].double()),
+        "K = 33 with C = 257": dict(k(33), values=values_of(257) if good["values"].dim() == 2 else z(1, 33, 257, 1, 1)),
+        "C = 257 with faces_opacity on the CPU": dict(values=values_of(257), opacity=th.zeros(1)),
+    }
+
+
+def _values_backward_only(z):
+    """The cases of both composite_values backward calls alone."""
+    return {
+        "need face_scale without face_scale": dict(need3=(False, False, True)),
+        "grad_image of another shape": dict(grad_image=z(1, 4, 1, 1)),
+        "grad_T of another size": dict(grad_T=z(1, 1, 1, 2)),
+        "grad_image on the CPU": dict(grad_image=th.zeros(1, 3, 1, 1)),
+    }
+
+
+def _deferred_refusals(dev):
+    z = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype, device=dev)
+    iz = lambda *shape: z(*shape, dtype=th.int32)
+    good = dict(face=iz(1, 1, 1, 1), bary=z(1, 1, 2, 1, 1), faces=th.tensor([[0, 1, 2]], dtype=th.int32, device=dev), attrs=z(3, 3),
+                opacity=z(1) + 0.5, values=z(1, 1, 3, 1, 1), scale=None, grad_out=z(1, 1, 3, 1, 1), grad_image=z(1, 3, 1, 1),
+                grad_T=z(1, 1, 1, 1), need2=(False, False), need3=(False, False, False))
+    interp_calls = {"interpolate_fragments": ("face", "bary", "faces", "attrs"),
+                    "interpolate_fragments_backward": ("face", "bary", "faces", "attrs", "grad_out", "need2")}
+    values_calls = {"composite_values": ("face", "opacity", "values", "scale"),
+                    "composite_values_backward": ("face", "opacity", "values", "scale", "grad_image", "grad_T", "need3")}
+    interp = _interp_cases(z, good, lambda K: dict(face=iz(1, K, 1, 1), bary=z(1, K, 2, 1, 1)))
+    interp["empty fragment lists"] = dict(face=iz(1, 1, 0, 1), bary=z(1, 1, 2, 0, 1))
+    interp_backward = {"grad_out of another shape": dict(grad_out=z(1, 1, 4, 1, 1)), "grad_out on the CPU": dict(grad_out=th.zeros(1, 1, 3, 1, 1))}
+    values = _values_cases(z, good, lambda K: dict(face=iz(1, K, 1, 1), values=z(1, K, 3, 1, 1)), lambda C: z(1, 1, C, 1, 1))
+    values.update({
+        "values of another shape": dict(values=z(1, 1, 3, 1, 2)),
+        "values with four dimensions": dict(values=z(1, 3, 1, 1)),
+        "empty fragment lists": dict(face=iz(1, 1, 0, 1), values=z(1, 1, 3, 0, 1)),
+        "empty fragment lists with face_scale of another shape": dict(face=iz(1, 1, 0, 1), values=z(1, 1, 3, 0, 1), scale=z(1, 2)),
+    })
+    return _refusals(good, [("interpolate_fragments", interp_calls, interp, interp_backward),
+                            ("composite_values", values_calls, values, _values_backward_only(z))])
+
+
+def _packed_refusals(dev):
+    z = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype, device=dev)
+    iz = lambda *shape: z(*shape, dtype=th.int32)
+    good = dict(face=iz(1, 1, 1, 1), bary=z(1, 1, 2, 1, 1), row=iz(1, 1, 1, 1), n_used=iz(1) + 1, faces=th.tensor([[0, 1, 2]], dtype=th.int32, device=dev),
+                attrs=z(3, 3), opacity=z(1) + 0.5, values=z(1, 3), scale=None, F=1, capacity=1, N=1, grad_out=z(1, 3), grad_image=z(1, 3, 1, 1),
+                grad_T=z(1, 1, 1, 1), need2=(False, False), need3=(False, False, False))
+    # 2^31 slots in one element of memory: the size checks come before anything makes a tensor contiguous
+    huge = lambda t: t.expand(2 ** 16, 1, 2 ** 15, 1)
+    lists = {
+        "pix_to_face on the CPU": dict(face=good["face"].cpu()),
+        "pix_to_face with three dimensions": dict(face=good["face"][0]),
+        "pix_to_face int64": dict(face=good["face"].long()),
+    }
+    with_row = {
+        "row of another shape": dict(row=iz(1, 1, 1, 2)),
+        "row with three dimensions": dict(row=iz(1, 1, 1)),
+        "row on the CPU": dict(row=good["row"].cpu()),
+        "row int64": dict(row=good["row"].long()),
+        "row of another shape with K = 33": dict(face=iz(1, 33, 1, 1)),
+    }
+    n_used = {
+        "n_used with two elements": dict(n_used=iz(2)),
+        "n_used on the CPU": dict(n_used=good["n_used"].cpu()),
+        "n_used with two elements with K = 33": dict(face=iz(1, 33, 1, 1), row=iz(1, 33, 1, 1), n_used=iz(2)),
+    }
+    pack = dict(lists)
+    pack.update({
+        "K = 33": dict(face=iz(1, 33, 1, 1)),
+        "K = 0": dict(face=iz(1, 0, 1, 1)),
+        "empty fragment lists": dict(face=iz(1, 1, 0, 1)),
+        "B K H W = 2^31": dict(face=huge(good["face"])),
+        "F = -1": dict(F=-1),
+        "F = 2^31": dict(F=2 ** 31),
+        "capacity = -1": dict(capacity=-1),
+        "K = 33 with F = -1": dict(face=iz(1, 33, 1, 1), F=-1),
+        "F = -1 with capacity = -1": dict(F=-1, capacity=-1),
+    })
+    k_interp = lambda K: dict(face=iz(1, K, 1, 1), bary=z(1, K, 2, 1, 1), row=iz(1, K, 1, 1))
+    interp = _interp_cases(z, good, k_interp)
+    interp.update(with_row)
+    interp.update(n_used)
+    interp.update({
+        "empty fragment lists": dict(face=iz(1, 1, 0, 1), bary=z(1, 1, 2, 0, 1), row=iz(1, 1, 0, 1)),
+        "B K H W = 2^31": dict(face=huge(good["face"]), row=huge(good["row"])),
+        "rows = -1": dict(N=-1, grad_out=z(3)),  # (the backward call takes its rows from grad_out, and -1 when that is no [N,C])
+        "bary of another shape with row on the CPU": dict(bary=z(1, 1, 3, 1, 1), row=good["row"].cpu()),
+        "C = 257 with rows = -1": dict(attrs=z(3, 257), N=-1, grad_out=z(3)),
+    })
+    interp_backward = {"grad_out of another C": dict(grad_out=z(1, 4)), "grad_out on the CPU": dict(grad_out=th.zeros(1, 3))}
+    k_values = lambda K: dict(face=iz(1, K, 1, 1), row=iz(1, K, 1, 1))
+    values = _values_cases(z, good, k_values, lambda C: z(1, C))
+    values.update(with_row)
+    values.update({
+        "values with one dimension": dict(values=z(3)),
+        "empty fragment lists": dict(face=iz(1, 1, 0, 1), row=iz(1, 1, 0, 1)),
+        "2^31 rows": dict(values=z(1, 1).expand(2 ** 31, 3)),
+        "C = 257 with 2^31 rows": dict(values=z(1, 1).expand(2 ** 31, 257)),
+    })
+    values_backward = _values_backward_only(z)
+    values_backward.update(n_used)  # (the forward call takes no n_used)
+    return _refusals(good, [
+        ("pack_slots", {"pack_slots": ("face", "F", "capacity")}, pack, {}),
+        ("interpolate_packed", {"interpolate_packed": ("face", "bary", "row", "n_used", "faces", "attrs", "N"),
+                                "interpolate_packed_backward": ("face", "bary", "row", "n_used", "faces", "attrs", "grad_out", "need2")},
+         interp, interp_backward),
+        ("composite_values_packed", {"composite_values_packed": ("face", "row", "opacity", "values", "scale"),
+                                     "composite_values_packed_backward": ("face", "row", "n_used", "opacity", "values", "scale", "grad_image",
+                                                                          "grad_T", "need3")},
+         values, values_backward)])
+
+
+LIST_REFUSALS = {"visibility": _visibility_refusals, "deferred": _deferred_refusals, "packed": _packed_refusals}

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_deferred.h")
 UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_interp.hip")
 UNIT_TEXT = open(UNIT).read()   # (read at import: every test here is about this unit, and none means anything without it)
+COMMON_TEXT = open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", DC.COMMON_HEADER)).read()   # what it shares with the packed unit
 FUNCTIONS = ["dmr_composite_values", "dmr_composite_values_backward", "dmr_interpolate_fragments", "dmr_interpolate_fragments_backward"]
 
 
@@ -36,7 +37,7 @@ def test_library_exports_the_declared_symbols():
 
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
-    assert "dmr_interp.hip" in build.SOURCES
+    assert "dmr_interp.hip" in build.SOURCES and DC.COMMON_HEADER in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_deferred.h" for d in deps)
@@ -351,12 +352,15 @@ def _all_cases():
 def test_dispatch_restated_as_the_unit_has_it():
     unit = UNIT_TEXT
     for line in DC.DISPATCH_LINES:
-        assert unit.count(line) == 1, line
+        assert unit.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
+    for line in DC.COMMON_DISPATCH_LINES:
+        assert COMMON_TEXT.count(line) == 1 and unit.count(line) == 0, line
+    assert '#include "%s"' % DC.COMMON_HEADER in unit
     assert [DC.interp_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 8, 8]
     assert [DC.values_forward_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 16, 16]
     assert [DC.values_backward_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 8, 8]
     # the kernels the unit instantiates are the ones every_instantiation lists
-    named = set(re.findall(r"\b(k_[a-z_]+)<", unit)) - {"k_deferred_zero"}
+    named = set(re.findall(r"\b(k_[a-z_]+)<", unit))   # (k_deferred_zero is the common header's)
     assert named == {k for k, _, _ in DC.every_instantiation()}
 
 

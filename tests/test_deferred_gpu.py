@@ -514,3 +514,21 @@ def all_cases():
     yield "merge interpolate", dict(g_r, out=out_r)
     image_r, T_r, v_r = _values_model(d, True)
     yield "merge composite_values", dict(v_r, image=image_r, T=T_r)
+
+
+def test_binding_refusals(hip_device):
+    """The binding's own refusals, below fragments.py's: every case of shading_cases.binding_refusals("deferred") raises a
+    RuntimeError with the message the binding gave before its argument builders were put together from shared checks
+    (tests/golden/shading_refusals.json: a record of that binding on the GPU over the same cases).  One or two wrong arguments
+    per call, at one pixel: no call reaches a kernel."""
+    import json
+    import os
+    import shading_cases as SC
+    from dmesh_renderer_amd import _C
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shading_refusals.json")))["binding"]["deferred"]
+    cases = SC.binding_refusals("deferred", hip_device)
+    assert sorted({case for case, _, _ in cases}) == sorted(golden)
+    for case, call, args in cases:
+        with pytest.raises(RuntimeError) as e:
+            getattr(_C, call)(*args)
+        assert str(e.value) == golden[case], (case, call)

@@ -31,7 +31,7 @@ def test_library_exports_the_declared_symbols():
 
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
-    assert "dmr_visibility.hip" in build.SOURCES
+    assert "dmr_visibility.hip" in build.SOURCES and "dmr_deferred_common.hpp" in build.HEADERS   # (its zeroing kernel)
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_visibility.h" for d in deps)

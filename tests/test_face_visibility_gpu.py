@@ -316,3 +316,21 @@ def test_non_finite_opacity_and_huge_ids_stay_in_bounds(hip_device, poison):
     em = float(np.abs(mx.cpu().numpy()[:, others] - mx_r[:, others]).max())
     print(f"\nopacity {poison}: the other faces' vis {ev:.2e} max_weight {em:.2e}")
     assert ev <= FWD_TOL and em <= FWD_TOL and np.array_equal(px.cpu().numpy()[:, others], px_r[:, others])
+
+
+def test_binding_refusals(hip_device):
+    """The binding's own refusals, below fragments.py's: every case of shading_cases.binding_refusals("visibility") raises a
+    RuntimeError with the message the binding gave before its argument builders were put together from shared checks
+    (tests/golden/shading_refusals.json: a record of that binding on the GPU over the same cases).  One or two wrong arguments
+    per call, at one pixel: no call reaches a kernel."""
+    import json
+    import os
+    import shading_cases as SC
+    from dmesh_renderer_amd import _C
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shading_refusals.json")))["binding"]["visibility"]
+    cases = SC.binding_refusals("visibility", hip_device)
+    assert sorted({case for case, _, _ in cases}) == sorted(golden)
+    for case, call, args in cases:
+        with pytest.raises(RuntimeError) as e:
+            getattr(_C, call)(*args)
+        assert str(e.value) == golden[case], (case, call)

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_packed.h")
 UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_packed.hip")
 UNIT_TEXT = open(UNIT).read()   # (read at import: every test here is about this unit, and none means anything without it)
+COMMON_TEXT = open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", PC.COMMON_HEADER)).read()   # what it shares with the dense unit
 FUNCTIONS = ["dmr_composite_values_packed", "dmr_composite_values_packed_backward", "dmr_interpolate_packed",
              "dmr_interpolate_packed_backward", "dmr_pack_slots"]
 NAMES = ("PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused", "composite_values_packed",
@@ -39,7 +40,7 @@ def test_library_exports_the_declared_symbols():
 
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
-    assert "dmr_packed.hip" in build.SOURCES
+    assert "dmr_packed.hip" in build.SOURCES and PC.COMMON_HEADER in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_packed.h" for d in deps)
@@ -452,20 +453,25 @@ def _all_cases():
 def test_dispatch_restated_as_the_unit_has_it():
     unit = UNIT_TEXT
     for line in PC.DISPATCH_LINES:
-        assert unit.count(line) == 1, line
+        assert unit.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
+    for line in PC.COMMON_DISPATCH_LINES:
+        assert COMMON_TEXT.count(line) == 1 and unit.count(line) == 0, line
+    assert '#include "%s"' % PC.COMMON_HEADER in unit
     assert [PC.interp_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 8, 8]
     assert [PC.interp_via_lds(c) for c in (1, 4, 5, 8, 9, 32, 33, 256)] == [False, False, False, False, True, True, False, False]
     assert [PC.values_forward_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 16, 16]
     assert [PC.values_backward_ch(c) for c in (1, 4, 5, 256)] == [4, 4, 8, 8]
     assert PC.PACK_SLOTS == 256 * 8 and [PC.pack_groups(n) for n in (1, 2047, 2048, 2049)] == [1, 1, 1, 2]
     # the kernels the unit instantiates are the ones every_instantiation lists
-    named = set(re.findall(r"\b(k_[a-z_]+)<\w", unit)) - {"k_packed_zero", "k_pack_count", "k_pack_scan", "k_pack_write"}
+    named = set(re.findall(r"\b(k_[a-z_]+)<\w", unit)) - {"k_pack_count", "k_pack_scan", "k_pack_write"}   # (k_deferred_zero is the common header's)
     assert named == {k for k, _, _ in PC.every_instantiation()}
 
 
 def test_the_unit_leaves_the_other_shading_units_alone():
-    """No workgroup waits for another (the scan is three launches), and what is accumulated into is zeroed by the unit's own kernel."""
-    code = re.sub(r"//[^\n]*", "", UNIT_TEXT)
+    """No workgroup waits for another (the scan is three launches), and what is accumulated into is zeroed by a kernel of the
+    unit (the common header's k_deferred_zero: the header's text is read along with the unit's)."""
+    code = re.sub(r"//[^\n]*", "", COMMON_TEXT + UNIT_TEXT)
+    assert "k_deferred_zero<<<" in code
     assert "hipMemsetAsync" not in code and "hipMalloc" not in code and "Synchronize" not in code
     assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
     assert all(k in code for k in ("k_pack_count<<<", "k_pack_scan<<<dim3(1)", "k_pack_write<<<"))

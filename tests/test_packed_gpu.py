@@ -489,3 +489,21 @@ def test_graph_replay(hip_device):
         counts.append(same(captured, fresh, f"lists rewritten in place, {fraction:.0%} emptied"))
     print(f"used slots over the replays: {counts} of capacity {M}")
     assert counts[1] < counts[0] < counts[2] < M
+
+
+def test_binding_refusals(hip_device):
+    """The binding's own refusals, below fragments.py's: every case of shading_cases.binding_refusals("packed") raises a
+    RuntimeError with the message the binding gave before its argument builders were put together from shared checks
+    (tests/golden/shading_refusals.json: a record of that binding on the GPU over the same cases).  One or two wrong arguments
+    per call, at one pixel: no call reaches a kernel."""
+    import json
+    import os
+    import shading_cases as SC
+    from dmesh_renderer_amd import _C
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shading_refusals.json")))["binding"]["packed"]
+    cases = SC.binding_refusals("packed", hip_device)
+    assert sorted({case for case, _, _ in cases}) == sorted(golden)
+    for case, call, args in cases:
+        with pytest.raises(RuntimeError) as e:
+            getattr(_C, call)(*args)
+        assert str(e.value) == golden[case], (case, call)
