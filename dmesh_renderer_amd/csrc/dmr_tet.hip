@@ -510,19 +510,47 @@ struct TetAccum {
     }
 };
 
-// Arithmetic of k_tet_backward_seq that decides nothing (no index, no branch of the march depends on it): contracted to FMA,
-// 1-ulp reciprocals and the hardware exponential.  Gradients are checked to 1e-4; the forward and the re-marching kernel,
+// The hit (t, u, v) of a marched face for k_tet_backward_seq (cuda_renderer/auxiliary.h:265-296 without the hit test: the march
+// already decided): the products and sums of ray_tri_hit, NOT contracted.  A ray that grazes a face (|P . E1| a few 1e-4 of
+// |P||E1|: a fine mesh has such hits) gets its (u, v) from sums that cancel, and there another rounding of the same formula is
+// another (u, v) by 1e-4: with FMAs here the two backward kernels differed by 1.3e-5 / 2.1e-5 of the largest gradient on 20^3
+// lattices (tests/test_tet_paths_gpu.py, fpt2 / fpt4); with the forward's own sums they agree to 4e-7.  Cost at C3: the tet
+// backward 0.241 -> 0.244 ms.
+struct TetHit { V3 E1, E2, P; float inv_den, t, u, v; };  // (E1, E2, P, 1 / den: what the full gradients take up again)
+// IEEE_DIV: the forward's 1.0f / den too, so t, u, v are the march's own bits (the camera variant, see tet_cam_k); else 1 ulp
+template <bool IEEE_DIV>
+__device__ __forceinline__ TetHit tet_hit(V3 o, V3 d, V3 p0, V3 p1, V3 p2) {
+    TetHit h;
+    const V3 T = o - p0;
+    h.E1 = p1 - p0; h.E2 = p2 - p0;
+    h.P = cross(d, h.E2);
+    const V3 Q = cross(T, h.E1);
+    const float den = dot(h.P, h.E1);
+    h.inv_den = IEEE_DIV ? 1.0f / den : fast::rcp(den);
+    h.t = dot(Q, h.E2) * h.inv_den; h.u = dot(h.P, T) * h.inv_den; h.v = dot(Q, d) * h.inv_den;
+    return h;
+}
+
+// The camera variant's (kz, kw) = G d(ndc depth)/d(clip z, clip w) at the hit point (TetCamPix below), with the re-marching
+// kernel's arithmetic: hit point, clip z and w not contracted, IEEE 1 / w.  dL/dmv and dL/dproj are sums of these over every
+// pixel and step that cancel to 1e-2 of their terms, so every one-sided 1e-7 (a 1-ulp reciprocal, the hardware exponential, an
+// FMA) shows as 1e-5 of the result: with t, the weight and these two bit-identical to the re-march's, the two kernels' direct
+// matrix gradients are equal (tests/test_tet_camera_grads_gpu.py asks 1e-5; it was 9.9e-6).  Camera variant only: 0.502 -> 0.517 ms.
+__device__ __forceinline__ void tet_cam_k(V3 o, V3 d, float t, const float* __restrict__ mv, const float* __restrict__ pr, float G,
+                                          float& kz, float& kw) {
+    const V3 pt = o + (d * t);
+    const V4 pn = xform4x4(xform4x3(pt, mv), pr);
+    const float pw = 1.0f / clamp_w(pn.w);
+    kz = G * pw;
+    kw = clamp_w(pn.w) == pn.w ? -kz * (pn.z * pw) : 0.f;
+}
+
+// The other arithmetic of k_tet_backward_seq that decides nothing (no index, no branch of the march depends on it): contracted to
+// FMA, 1-ulp reciprocals and the hardware exponential.  Gradients are checked to 1e-4; the forward and the re-marching kernel,
 // whose tests pick faces, keep the exact forms.
 #pragma clang fp contract(fast)
 namespace tfast {  // fast's F3 (dmr_device.hpp) and what this renderer adds to it
 using namespace fast;
-// (t, u, v) of cuda_renderer/auxiliary.h:265-296 without the hit test (the march already decided)
-__device__ __forceinline__ void tuv(F3 o, F3 d, F3 p0, F3 p1, F3 p2, float& t, float& u, float& v) {
-    const F3 T = o - p0, E1 = p1 - p0, E2 = p2 - p0;
-    const F3 P = cross(d, E2), Q = cross(T, E1);
-    const float inv = rcp(dot(P, E1));
-    t = dot(Q, E2) * inv; u = dot(P, T) * inv; v = dot(Q, d) * inv;
-}
 // ndc depth of a world point: rows z and w of proj * (mv * (pt, 1)) (auxiliary.h:71-90), z / clamp_w(w)
 __device__ __forceinline__ float ndc_depth(F3 pt, const float* __restrict__ mv, const float* __restrict__ pr) {
     const float vx = mv[0] * pt.x + mv[4] * pt.y + mv[8] * pt.z + mv[12];
@@ -546,14 +574,6 @@ __device__ __forceinline__ float ndc_depth_dt(F3 pt, F3 d, const float* __restri
     const float dcw = pr[3] * dx + pr[7] * dy + pr[11] * dz;
     const float cwc = clamp_w(cw), inv = rcp(cwc);
     return cwc == cw ? (dcz - cz * inv * dcw) * inv : dcz * inv;
-}
-// (clip z, clip w) of a world point, with ndc_depth's arithmetic (the compiler computes them once for both)
-__device__ __forceinline__ void clip_zw(F3 pt, const float* __restrict__ mv, const float* __restrict__ pr, float& cz, float& cw) {
-    const float vx = mv[0] * pt.x + mv[4] * pt.y + mv[8] * pt.z + mv[12];
-    const float vy = mv[1] * pt.x + mv[5] * pt.y + mv[9] * pt.z + mv[13];
-    const float vz = mv[2] * pt.x + mv[6] * pt.y + mv[10] * pt.z + mv[14];
-    cz = pr[2] * vx + pr[6] * vy + pr[10] * vz + pr[14];
-    cw = pr[3] * vx + pr[7] * vy + pr[11] * vz + pr[15];
 }
 }  // namespace tfast
 
@@ -692,8 +712,8 @@ struct TetBwdPixel {
 #pragma clang fp contract(fast)
         using namespace tfast;
         const F3 o = {ro.x, ro.y, ro.z}, d = {rd.x, rd.y, rd.z};
-        float rt, iu, iv;
-        tuv(o, d, {f0.x, f0.y, f0.z}, {f0.w, f1.x, f1.y}, {f1.z, f1.w, f2.x}, rt, iu, iv);
+        const TetHit hit = tet_hit<CAM>(ro, rd, {f0.x, f0.y, f0.z}, {f0.w, f1.x, f1.y}, {f1.z, f1.w, f2.x});  // (its sums are not contracted)
+        const float rt = hit.t, iu = hit.u, iv = hit.v;
         const F3 c0 = {cq0.x, cq0.y, cq0.z}, c1 = {cq0.w, cq1.x, cq1.y}, c2 = {cq1.z, cq1.w, cq2.x};
         v0 = __float_as_int(cq2.y); v1 = __float_as_int(cq2.z); v2 = __float_as_int(cq2.w);
         const float i0 = 1.0f - iu - iv, i1 = iu, i2 = iv;
@@ -702,7 +722,8 @@ struct TetBwdPixel {
         const float pdepth = ndc_depth(o + (rt * d), mv, pr);
         if (!first_iter) prev_log_T = prev_log_T - cq3.y;  // logf(1 - opacity), per face (TetColRec)
         first_iter = false;
-        const float prev_T = __expf(prev_log_T);
+        // (CAM: the re-marching kernel's expf, see tet_cam_k)
+        const float prev_T = CAM ? expf(prev_log_T) : __expf(prev_log_T);
         float dop = 0.f;
         ar0 = last_alpha * lc0 + (1.f - last_alpha) * ar0; lc0 = col.x;
         ar1 = last_alpha * lc1 + (1.f - last_alpha) * ar1; lc1 = col.y;
@@ -720,19 +741,17 @@ struct TetBwdPixel {
         g[6] = i2 * dc0; g[7] = i2 * dc1; g[8] = i2 * dc2;
         g[9] = dop;
         if constexpr (FULL) {
-            const F3 p0 = {f0.x, f0.y, f0.z}, E1 = F3{f0.w, f1.x, f1.y} - p0, E2 = F3{f1.z, f1.w, f2.x} - p0;
-            const F3 P = cross(d, E2);
+            const F3 E1 = {hit.E1.x, hit.E1.y, hit.E1.z}, E2 = {hit.E2.x, hit.E2.y, hit.E2.z}, P = {hit.P.x, hit.P.y, hit.P.z};
             const F3 craw = (i0 * c0) + (i1 * c1) + (i2 * c2);
             const F3 dc = {dc0, dc1, dc2};  // dL/dcolour of the pixel * w * intensity
             const float w = opacity * prev_T;
-            [[maybe_unused]] const F3 lam = full_grads(d, E1, E2, P, rcp(dot(P, E1)), w * dpd * ndc_depth_dt(o + (rt * d), d, mv, pr),
+            [[maybe_unused]] const F3 lam = full_grads(d, E1, E2, P, hit.inv_den, w * dpd * ndc_depth_dt(o + (rt * d), d, mv, pr),
                                                        dot(dc, c1 - c0), dot(dc, c2 - c0), i0, i1, i2,
                                                        w * (dpc0 * craw.x + dpc1 * craw.y + dpc2 * craw.z), g + 10);
             if constexpr (CAM) {
-                float cz, cw;
-                clip_zw(o + (rt * d), mv, pr, cz, cw);
-                const float cwc = clamp_w(cw), inv = rcp(cwc), kz = w * dpd * inv;
-                cam->add(lam, rt, kz, cwc == cw ? -kz * cz * inv : 0.f, mv, pr);
+                float kz, kw;
+                tet_cam_k(ro, rd, rt, mv, pr, w * dpd, kz, kw);  // (not contracted)
+                cam->add(lam, rt, kz, kw, mv, pr);
             }
         }
     }
