@@ -1,6 +1,7 @@
 """Test-only helpers (a plain module, imported like util.py): the one launcher of child processes (two gloo ranks of
-tests/sharded_child.py; tests/fallback_child.py on the ablation build), the graph capture ritual, and the
-clone-call-backpropagate step of a Module."""
+tests/sharded_child.py; tests/fallback_child.py on the ablation build), the graph capture ritual, the
+clone-call-backpropagate step of a Module, and tri calls through the C ABI with a guarded allocator."""
+import ctypes as C
 import os
 import signal
 import socket
@@ -100,3 +101,73 @@ def module_step(renderer, t, grad_names, upstream):
     out = renderer(*(leaves[k] if k in leaves else t[k] for k in (TET_ARGS if "tets" in t else TRI_ARGS)))
     th.autograd.backward([o for o in out if o.requires_grad][:len(upstream)], list(upstream))
     return [o.detach() for o in out], {k: leaves[k].grad for k in grad_names}
+
+
+class GuardedTriCalls:
+    """dmr_tri_forward / dmr_tri_backward through the C ABI with an allocator of its own: every buffer the library asks for is
+    followed by GUARD bytes of 0xA5, checked after every call -- a store behind a scratch buffer fails the call's test.
+    `lib` is the library with the ABI's signatures bound (dmr_overflowed, dmr_redo_count, ...)."""
+    GUARD = 4096
+
+    def __init__(self, dev):
+        from dmesh_renderer_amd import _C
+        import capi_ctypes as capi
+        self.capi, self.dev = capi, dev
+        self.lib = C.CDLL(_C.library_path())
+        for name, (restype, argtypes) in capi.EXPORTS.items():
+            getattr(self.lib, name).restype = restype
+            getattr(self.lib, name).argtypes = argtypes
+        self.held = []      # (tensor with its guard, bytes asked for, which) of the call in hand
+        self.buffers = {}   # the last forward's scratch by DMR_BUF_*, without the guards
+
+        def alloc(_ctx, which, nbytes):
+            t = th.full((int(nbytes) + self.GUARD,), 0xA5, dtype=th.uint8, device=dev)
+            self.held.append((t, int(nbytes), int(which)))
+            return t.data_ptr()
+
+        self.alloc_fn = capi.ALLOC_FN(alloc)
+
+    def _scene(self, d, B, H, W, flags):
+        from util import c_args
+        a = [x.contiguous() for x in c_args(d, self.dev)]
+        a[2] = a[2].to(th.int32).contiguous()
+        sc = self.capi.Scene(B=B, P=a[1].shape[0], F=a[2].shape[0], T=0, W=W, H=H, background=a[0].data_ptr(), verts=a[1].data_ptr(),
+                             faces=a[2].data_ptr(), verts_color=a[3].data_ptr(), faces_opacity=a[4].data_ptr(), mv_mats=a[5].data_ptr(),
+                             proj_mats=a[6].data_ptr(), inv_mv_mats=a[7].data_ptr(), inv_proj_mats=a[8].data_ptr(),
+                             verts_depth=a[9].data_ptr(), faces_intense=a[10].data_ptr(), tets=None, face_tets=None, tet_faces=None,
+                             ray_random_seed=0, row_begin=0, row_end=0, mats_transposed=0, flags=flags)
+        return sc, a
+
+    def _guards_intact(self):
+        for t, nbytes, _ in self.held:
+            assert bool((t[nbytes:] == 0xA5).all()), "guard words behind a scratch buffer were overwritten"
+
+    def forward(self, d, B, H, W, flags):
+        """-> (the R the call returns, colour, depth, the call's tensor arguments); flags: DMR_FLAG_ASYNC = 1"""
+        sc, a = self._scene(d, B, H, W, flags)
+        color = th.empty(B, 3, H, W, device=self.dev)
+        depth = th.empty(B, 1, H, W, device=self.dev)
+        R = C.c_int(0)
+        del self.held[:]
+        rc = self.lib.dmr_tri_forward(C.byref(sc), color.data_ptr(), depth.data_ptr(), self.alloc_fn, None, None, C.byref(R))
+        th.cuda.synchronize()
+        assert rc == 0, self.lib.dmr_last_error()
+        self._guards_intact()
+        self.buffers = {which: t[:nbytes] for t, nbytes, which in self.held}
+        return R.value, color, depth, a
+
+    def backward(self, d, B, H, W, flags, R, gc, gd):
+        """The backward of the last forward (same scene): -> [dL_dverts, dL_dvcolor, dL_dfopacity, dL_dvdepth, dL_dfintense]"""
+        sc, a = self._scene(d, B, H, W, flags)
+        P, F = a[1].shape[0], a[2].shape[0]
+        gc, gd = gc.to(self.dev).contiguous(), gd.to(self.dev).contiguous()
+        out = [th.full(s, float("nan"), device=self.dev) for s in ((P, 3), (P, 3), (F,), (B, P), (B, F))]
+        capi = self.capi
+        buf = [self.buffers[w].data_ptr() for w in (capi.BUF_POINT, capi.BUF_FACE, capi.BUF_BINNING, capi.BUF_IMAGE)]
+        del self.held[:]
+        rc = self.lib.dmr_tri_backward(C.byref(sc), gc.data_ptr(), gd.data_ptr(), int(R), *buf, *[o.data_ptr() for o in out],
+                                       self.alloc_fn, None, None)
+        th.cuda.synchronize()
+        assert rc == 0, self.lib.dmr_last_error()
+        self._guards_intact()
+        return out

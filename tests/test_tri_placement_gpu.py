@@ -2,7 +2,6 @@
 after the first call of a key the front end is projection -> ONE binning kernel that emits straight into segments placed
 from the previous counts (+ 25 % + 32 entries per tile).  Every view configuration here is used by no other test: the
 placement, like the size estimates, is keyed by it."""
-import ctypes as C
 import os
 import sys
 import tempfile
@@ -12,7 +11,7 @@ import pytest
 import torch as th
 
 from dmesh_renderer_amd import scenes
-from harness import HERE, _run_child, capture_replay, replay
+from harness import HERE, GuardedTriCalls, _run_child, capture_replay, replay
 from util import c_args, rel_err, upstream_grads
 
 pytestmark = pytest.mark.gpu
@@ -114,42 +113,10 @@ def test_jump_into_empty_tiles_is_redone_once(hip_device, oracle):
 def test_async_jump_is_clamped_and_flagged(hip_device, oracle):
     """Through the C ABI with an allocator of its own: every buffer is followed by guard words.  The asynchronous call of
     the second mesh must raise the overflow word and leave the guards alone; the default call then repairs it."""
-    from dmesh_renderer_amd import _C
-    import capi_ctypes as capi
-    lib = C.CDLL(_C.library_path())
-    for name, (restype, argtypes) in capi.EXPORTS.items():
-        getattr(lib, name).restype = restype
-        getattr(lib, name).argtypes = argtypes
-    dev = hip_device
+    calls = GuardedTriCalls(hip_device)
+    lib = calls.lib
     B, H, W = 1, 280, 392
-    GUARD = 4096
-    held = []
-
-    def alloc(_ctx, _which, nbytes):
-        t = th.full((int(nbytes) + GUARD,), 0xA5, dtype=th.uint8, device=dev)
-        held.append((t, int(nbytes)))
-        return t.data_ptr()
-
-    alloc_fn = capi.ALLOC_FN(alloc)
-
-    def forward(d, flags):
-        a = [x.contiguous() for x in c_args(d, dev)]
-        a[2] = a[2].to(th.int32).contiguous()
-        sc = capi.Scene(B=B, P=a[1].shape[0], F=a[2].shape[0], T=0, W=W, H=H, background=a[0].data_ptr(), verts=a[1].data_ptr(),
-                        faces=a[2].data_ptr(), verts_color=a[3].data_ptr(), faces_opacity=a[4].data_ptr(), mv_mats=a[5].data_ptr(),
-                        proj_mats=a[6].data_ptr(), inv_mv_mats=a[7].data_ptr(), inv_proj_mats=a[8].data_ptr(),
-                        verts_depth=a[9].data_ptr(), faces_intense=a[10].data_ptr(), tets=None, face_tets=None, tet_faces=None,
-                        ray_random_seed=0, row_begin=0, row_end=0, mats_transposed=0, flags=flags)
-        color = th.empty(B, 3, H, W, device=dev)
-        depth = th.empty(B, 1, H, W, device=dev)
-        R = C.c_int(0)
-        del held[:]
-        rc = lib.dmr_tri_forward(C.byref(sc), color.data_ptr(), depth.data_ptr(), alloc_fn, None, None, C.byref(R))
-        th.cuda.synchronize()
-        assert rc == 0, lib.dmr_last_error()
-        for t, nbytes in held:
-            assert bool((t[nbytes:] == 0xA5).all()), "guard words behind a scratch buffer were overwritten"
-        return R.value, color, depth, a
+    forward = lambda d, flags: calls.forward(d, B, H, W, flags)
 
     left, right = _half(-1.0, B, H, W, 6), _half(1.0, B, H, W, 7)
     lib.dmr_overflowed(-1, 1)
