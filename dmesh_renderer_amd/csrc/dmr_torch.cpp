@@ -53,6 +53,9 @@
 //   grad_image, grad_T, need=(opacity, values, scale)): the packed, channel-last form of the four above
 //   (fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused), over
 //                            include/dmesh_renderer_amd_packed.h (SUPPORTS_FRAGMENT_PACKED)
+//   mlp_rows(x [N,Cin], weights, biases, act, oact, n_rows=None) -> y [N,Cout] and mlp_rows_backward(..., grad_out, need_x,
+//   need_w, need_b) -> (dL_dx | None, [dL_dW_l | None], [dL_db_l | None]): a 1- or 2-hidden-layer MLP over packed rows
+//   (fragments.mlp_rows_fused), over include/dmesh_renderer_amd_mlp.h (SUPPORTS_FRAGMENT_MLP)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -76,6 +79,7 @@
 #include "../../include/dmesh_renderer_amd_visibility.h"
 #include "../../include/dmesh_renderer_amd_deferred.h"
 #include "../../include/dmesh_renderer_amd_packed.h"
+#include "../../include/dmesh_renderer_amd_mlp.h"
 
 namespace {
 
@@ -121,6 +125,9 @@ struct Abi {
     decltype(&dmr_interpolate_packed_backward) interpolate_packed_backward = nullptr;
     decltype(&dmr_composite_values_packed) composite_values_packed = nullptr;
     decltype(&dmr_composite_values_packed_backward) composite_values_packed_backward = nullptr;
+    // dmesh_renderer_amd_mlp.h: optional too (SUPPORTS_FRAGMENT_MLP), both or none
+    decltype(&dmr_mlp_rows) mlp_rows = nullptr;
+    decltype(&dmr_mlp_rows_backward) mlp_rows_backward = nullptr;
 };
 
 Abi g_abi;
@@ -191,6 +198,9 @@ void load_abi() {
         !g_abi.composite_values_packed_backward)
         g_abi.pack_slots = nullptr, g_abi.interpolate_packed = nullptr, g_abi.interpolate_packed_backward = nullptr,
         g_abi.composite_values_packed = nullptr, g_abi.composite_values_packed_backward = nullptr;
+    g_abi.mlp_rows = reinterpret_cast<decltype(g_abi.mlp_rows)>(dlsym(g_abi.handle, "dmr_mlp_rows"));
+    g_abi.mlp_rows_backward = reinterpret_cast<decltype(g_abi.mlp_rows_backward)>(dlsym(g_abi.handle, "dmr_mlp_rows_backward"));
+    if (!g_abi.mlp_rows || !g_abi.mlp_rows_backward) g_abi.mlp_rows = nullptr, g_abi.mlp_rows_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -1152,6 +1162,111 @@ py::tuple composite_values_packed_backward(In face, In row, In n_used, In faces_
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
+// -- mlp_rows: a small MLP over [N,Cin] rows (dmesh_renderer_amd_mlp.h).  weights = (W_in [Hd,Cin], [W_mid [Hd,Hd],] W_out [Cout,Hd]),
+// biases = one per weight, each a tensor or None.  The checks come in fragments.mlp_rows_fused's order: shapes, sizes, one
+// device, dtypes.
+using OptTensors = std::vector<std::optional<at::Tensor>>;
+struct MlpArgs {
+    at::Tensor x, n_rows;
+    std::vector<at::Tensor> w, b;  // b[l] undefined: no bias
+    int64_t N = 0, Cin = 0, Hd = 0, Cout = 0;
+    int nh = 0, act = 0, oact = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return stream_on(dev); }
+    const float* wp(size_t l) const { return mptr<const float>(w[l]); }
+    const float* bp(size_t l) const { return b[l].defined() ? mptr<const float>(b[l]) : nullptr; }
+    const float* mid_w() const { return nh == 2 ? wp(1) : nullptr; }
+    const float* mid_b() const { return nh == 2 ? bp(1) : nullptr; }
+    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
+};
+
+MlpArgs mlp_args(In x, const std::vector<at::Tensor>& weights, const OptTensors& biases, int64_t act, int64_t oact,
+                 const std::optional<at::Tensor>& n_rows) {
+    built(g_abi.mlp_rows, "dmr_mlp_rows");
+    MlpArgs a;
+    a.dev = hip_device_of(x);
+    if (x.dim() != 2) err("x must have dimensions (rows, Cin)");
+    if (weights.size() != 2 && weights.size() != 3) err("mlp_rows: 2 or 3 weights (1 or 2 hidden layers), got " + std::to_string(weights.size()));
+    if (biases.size() != weights.size()) err("mlp_rows: one bias (or None) per weight");
+    a.nh = (int)weights.size() - 1;
+    a.N = x.size(0); a.Cin = x.size(1);
+    for (const at::Tensor& w : weights)
+        if (w.dim() != 2) err("mlp_rows: every weight must have dimensions (out, in)");
+    a.Hd = weights[0].size(0); a.Cout = weights.back().size(0);
+    if (a.Hd != 16 && a.Hd != 32 && a.Hd != 64) err("mlp_rows: the hidden width must be 16, 32 or 64, got " + std::to_string(a.Hd));
+    if (a.Cin < 1 || a.Cin > 64) err("mlp_rows: Cin must be in 1..64, got " + std::to_string(a.Cin));
+    if (a.Cout < 1 || a.Cout > 16) err("mlp_rows: Cout must be in 1..16, got " + std::to_string(a.Cout));
+    if (a.N >= ((int64_t)1 << 31)) err("mlp_rows: rows must be below 2^31");
+    int64_t in = a.Cin;
+    for (size_t l = 0; l < weights.size(); l++) {
+        const int64_t out = l + 1 == weights.size() ? a.Cout : a.Hd;
+        if (weights[l].size(0) != out || weights[l].size(1) != in) err("mlp_rows: weight " + std::to_string(l) + " must have dimensions (" + std::to_string(out) + ", " + std::to_string(in) + ")");
+        if (biases[l] && (biases[l]->dim() != 1 || biases[l]->size(0) != out)) err("mlp_rows: bias " + std::to_string(l) + " must have dimensions (" + std::to_string(out) + ",)");
+        in = out;
+    }
+    if (act < 0 || act > 1 || oact < 0 || oact > 1) err("mlp_rows: bad activation");
+    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
+    for (size_t l = 0; l < weights.size(); l++)
+        if (weights[l].device() != a.dev || (biases[l] && biases[l]->device() != a.dev)) err("mlp_rows: the weights and biases must be on the device of x");
+    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
+    a.x = f32(x, "x");
+    for (size_t l = 0; l < weights.size(); l++) {
+        a.w.push_back(f32(weights[l], "weight"));
+        a.b.push_back(biases[l] ? f32(*biases[l], "bias") : at::Tensor());
+    }
+    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    a.act = (int)act; a.oact = (int)oact;
+    return a;
+}
+
+// -> y [N,Cout]
+at::Tensor mlp_rows(In x, const std::vector<at::Tensor>& weights, const OptTensors& biases, int64_t act, int64_t oact,
+                    const std::optional<at::Tensor>& n_rows) {
+    const MlpArgs a = mlp_args(x, weights, biases, act, oact, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor y = at::empty({a.N, a.Cout}, f32_on(a.dev));
+    if (g_abi.mlp_rows((int)a.N, (int)a.Cin, (int)a.Hd, (int)a.Cout, a.nh, a.act, a.oact, mptr<const float>(a.x), a.wp(0), a.bp(0), a.mid_w(),
+                       a.mid_b(), a.wp(a.nh), a.bp(a.nh), a.rows_ptr(), mptr<float>(y), a.stream()))
+        raise_lib();
+    return y;
+}
+
+// need_x, need_w[l], need_b[l] -> (dL_dx, [dL_dW_l], [dL_db_l]), None where not asked for; grad_out [N,Cout].  The scratch of
+// the weight-gradient reduction comes from PyTorch's allocator (DMR_MLP_SCRATCH_FLOATS), only when such a gradient is wanted.
+py::tuple mlp_rows_backward(In x, const std::vector<at::Tensor>& weights, const OptTensors& biases, int64_t act, int64_t oact,
+                            const std::optional<at::Tensor>& n_rows, In grad_out, bool need_x, const std::vector<bool>& need_w,
+                            const std::vector<bool>& need_b) {
+    const MlpArgs a = mlp_args(x, weights, biases, act, oact, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.Cout || grad_out.device() != a.dev)
+        err("grad_out must have dimensions (rows, Cout) on the device of x");
+    if (need_w.size() != a.w.size() || need_b.size() != a.w.size()) err("mlp_rows_backward: one need flag per weight and per bias");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor dx = grad_if(need_x, {a.N, a.Cin}, a.dev);
+    std::vector<at::Tensor> dw(3), db(3);  // (in, mid, out)
+    bool any = false;
+    for (size_t l = 0; l < a.w.size(); l++) {
+        const size_t slot = l + 1 == a.w.size() ? 2 : l;
+        if (need_b[l] && !a.b[l].defined()) err("mlp_rows_backward: the gradient of a bias that was not given");
+        dw[slot] = grad_if(need_w[l], a.w[l].sizes(), a.dev);
+        db[slot] = grad_if(need_b[l], {a.w[l].size(0)}, a.dev);
+        any = any || need_w[l] || need_b[l];
+    }
+    const int64_t scratch_floats = any ? DMR_MLP_SCRATCH_FLOATS(a.Hd, a.nh) : 0;
+    at::Tensor scratch = any ? at::empty({scratch_floats}, f32_on(a.dev)) : at::Tensor();
+    if (g_abi.mlp_rows_backward((int)a.N, (int)a.Cin, (int)a.Hd, (int)a.Cout, a.nh, a.act, a.oact, mptr<const float>(a.x), a.wp(0), a.bp(0),
+                                a.mid_w(), a.mid_b(), a.wp(a.nh), a.bp(a.nh), a.rows_ptr(), mptr<const float>(go), out_ptr(dx), out_ptr(dw[0]),
+                                out_ptr(db[0]), out_ptr(dw[1]), out_ptr(db[1]), out_ptr(dw[2]), out_ptr(db[2]), out_ptr(scratch), scratch_floats,
+                                a.stream()))
+        raise_lib();
+    py::list gw, gb;
+    for (size_t l = 0; l < a.w.size(); l++) {
+        const size_t slot = l + 1 == a.w.size() ? 2 : l;
+        gw.append(or_none(dw[slot])); gb.append(or_none(db[slot]));
+    }
+    return py::make_tuple(or_none(dx), gw, gb);
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1228,6 +1343,9 @@ PYBIND11_MODULE(_C, m) {
     m.def("composite_values_packed_backward", &composite_values_packed_backward, py::arg("face"), py::arg("row"), py::arg("n_used"),
           py::arg("faces_opacity"), py::arg("values"), py::arg("face_scale"), py::arg("grad_image"), py::arg("grad_T"),
           py::arg("need") = std::array<bool, 3>{true, true, true});
+    m.def("mlp_rows", &mlp_rows, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("act"), py::arg("oact"), py::arg("n_rows") = py::none());
+    m.def("mlp_rows_backward", &mlp_rows_backward, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("act"), py::arg("oact"),
+          py::arg("n_rows"), py::arg("grad_out"), py::arg("need_x"), py::arg("need_w"), py::arg("need_b"));
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1261,6 +1379,8 @@ PYBIND11_MODULE(_C, m) {
     // fragments.pack_slots_fused / interpolate_packed_fused / composite_values_packed_fused; False: the loaded library predates
     // dmesh_renderer_amd_packed.h
     m.attr("SUPPORTS_FRAGMENT_PACKED") = g_abi.pack_slots != nullptr;
+    // fragments.mlp_rows_fused; False: the loaded library predates dmesh_renderer_amd_mlp.h
+    m.attr("SUPPORTS_FRAGMENT_MLP") = g_abi.mlp_rows != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

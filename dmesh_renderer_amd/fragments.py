@@ -17,10 +17,14 @@ pix_to_face.flatten(), interpolate_packed_fused writes one channel-last row per 
 composite_values_packed_fused blends the rows the shader returns -- no permute, and nothing computed for an empty slot:
     packed = pack_slots_fused(frag, F)                                  # or capacity=M: no host wait, capturable
     x = interpolate_packed_fused(frag, packed, faces, features)         # [N,C]
-    rgb = mlp(x)                                                        # [N,3], the caller's own torch code
+    rgb = mlp(x)                                                        # [N,3], the caller's own torch code -- or
+    rgb = mlp_rows_fused(x, weights, biases, n_rows=packed.n_used)      # a 1- or 2-hidden-layer MLP as one HIP kernel (RowMLP holds the parameters)
     image, T = composite_values_packed_fused(frag, packed, faces_opacity, rgb)
     color = image + T * bg.view(1, 3, 1, 1)
 (pack_slots, interpolate_packed, composite_values_packed are the torch models, unpack_values the way back to [B,K,C,H,W]).
+mlp_rows_fused (csrc/dmr_mlp.hip) is that MLP -- widths 16, 32 or 64, relu or tanh, an optional sigmoid on the output -- as one
+forward and one backward kernel: the hidden activations stay in registers and the backward recomputes them, so nothing of size
+[N,hidden] is written, read or kept for autograd; mlp_rows is its torch model, RowMLP the nn.Module that picks between them.
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -49,14 +53,14 @@ renderer's colour and alpha differ from the lines above by 1e-5 bg and 1e-5 ther
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch as th
 
 __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
            "composite_texture_fused", "face_coverage", "face_visibility_fused", "composite_values", "interpolate_fused",
            "composite_values_fused", "PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused",
-           "composite_values_packed", "composite_values_packed_fused", "unpack_values"]
+           "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -194,7 +198,8 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "composite_values": ("SUPPORTS_FRAGMENT_DEFERRED", "per-slot value"),
           "pack_slots": ("SUPPORTS_FRAGMENT_PACKED", "fragment", "slot packing"),
           "interpolate_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed fragment", "interpolation"),
-          "composite_values_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed per-slot value")}  # (a third entry: what stands for "compositing" in the message)
+          "composite_values_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed per-slot value"),
+          "mlp_rows": ("SUPPORTS_FRAGMENT_MLP", "row", "MLP")}  # (a third entry: what stands for "compositing" in the message)
 
 
 def _fused_kernels(torch_path: str):
@@ -745,3 +750,196 @@ def composite_values_packed_fused(frag, packed: PackedSlots, faces_opacity: th.T
     _fused_kernels("composite_values_packed")
     _check_composite_values(name, torch_path, frag, faces_opacity, values, face_scale, packed)
     return _CompositeValuesFn.apply(frag.pix_to_face, faces_opacity, values, face_scale, packed.row, packed.n_used)
+
+
+# ---------------------------------------------------------------------------
+# A small MLP over packed rows: the shader between interpolate_packed_fused and composite_values_packed_fused (csrc/dmr_mlp.hip)
+# ---------------------------------------------------------------------------
+ACTIVATIONS = ("relu", "tanh")        # the index into it is the C calls' `act`
+OUT_ACTIVATIONS = ("none", "sigmoid")  # ... and `oact`
+MLP_HIDDEN = (16, 32, 64)             # the fused kernels' hidden widths; 1 <= Cin <= 64, 1 <= Cout <= 16
+
+
+def _mlp_arguments(name: str, x, weights, biases, activation, out_activation, n_rows):
+    """What mlp_rows and mlp_rows_fused both refuse (ValueError), in this order: the number of weights and biases, the
+    activations' names, x [N,Cin], the weights' chain of shapes [out_l, in_l] with one hidden width, the biases' shapes, n_rows.
+    -> (weights, biases) as tuples."""
+    weights, biases = tuple(weights), tuple(biases)
+    if len(weights) not in (2, 3):
+        raise ValueError(f"{name}: weights must hold 2 or 3 tensors (1 or 2 hidden layers), got {len(weights)}")
+    if len(biases) != len(weights):
+        raise ValueError(f"{name}: biases must hold one entry (a tensor or None) per weight, got {len(biases)} for {len(weights)}")
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"{name}: activation must be one of {ACTIVATIONS}, got {activation!r}")
+    if out_activation not in OUT_ACTIVATIONS:
+        raise ValueError(f"{name}: out_activation must be one of {OUT_ACTIVATIONS}, got {out_activation!r}")
+    if x.dim() != 2:
+        raise ValueError(f"{name}: x must be [N,Cin], got {tuple(x.shape)}")
+    if any(w.dim() != 2 for w in weights):
+        raise ValueError(f"{name}: every weight must be [out,in], got {[tuple(w.shape) for w in weights]}")
+    hidden, c_out, c_in = weights[0].shape[0], weights[-1].shape[0], x.shape[1]
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        want = (c_out if l == len(weights) - 1 else hidden, c_in if l == 0 else hidden)
+        if tuple(w.shape) != want:
+            raise ValueError(f"{name}: weights[{l}] must be [out,in] = {want} (x is {tuple(x.shape)}, one hidden width), got {tuple(w.shape)}")
+        if b is not None and tuple(b.shape) != want[:1]:
+            raise ValueError(f"{name}: biases[{l}] must be [out] = {want[:1]} or None, got {tuple(b.shape)}")
+    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
+        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+    return weights, biases
+
+
+def mlp_rows(x: th.Tensor, weights: Sequence[th.Tensor], biases: Sequence[Optional[th.Tensor]], *, activation: str = "relu",
+             out_activation: str = "none", n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """A small MLP over rows x [N,Cin] -> [N,Cout]: y = oact(W_L act(... act(W_1 x + b_1)) + b_L), weights W_l [out_l, in_l] in
+    nn.Linear's layout (2 or 3 of them: 1 or 2 hidden layers of one width), biases [out_l] or None each; activation "relu" or
+    "tanh", out_activation "none" or "sigmoid".  n_rows (None, or an integer tensor of one element on x's device -- what
+    PackedSlots.n_used is): the rows r >= min(max(n_rows, 0), N) are NOT READ -- a NaN there reaches nothing --, give exact zeros
+    in y and in dL_dx and add nothing to the gradient of any weight or bias; y[:n] is the MLP of x[:n].  With capacity=M the tail
+    rows of interpolate_packed's result are zeros, which a bias turns into non-zero outputs: without n_rows they would enter
+    dL_db and dL_dW.  The count is used on the device (no host wait).  Plain torch, any device, any float dtype: the model
+    mlp_rows_fused is tested against."""
+    weights, biases = _mlp_arguments("mlp_rows", x, weights, biases, activation, out_activation, n_rows)
+    mask = None
+    h = x
+    if n_rows is not None:
+        mask = (th.arange(x.shape[0], device=x.device) < n_rows.reshape(1).clamp(min=0)).unsqueeze(1)
+        h = th.where(mask, x, th.zeros((), dtype=x.dtype, device=x.device))
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        h = h @ w.t()
+        if b is not None:
+            h = h + b
+        if l < len(weights) - 1:
+            h = th.relu(h) if activation == "relu" else th.tanh(h)
+    if out_activation == "sigmoid":
+        h = th.sigmoid(h)
+    return h if mask is None else th.where(mask, h, th.zeros((), dtype=h.dtype, device=h.device))
+
+
+class _MlpRowsFn(th.autograd.Function):
+    """mlp_rows_fused over _C.mlp_rows / _C.mlp_rows_backward.  Arguments: x, n_rows (a tensor or None), act, oact, the number of
+    weights L, then the L weights and the L biases (a tensor or None each).  Nothing but the inputs is saved."""
+
+    @staticmethod
+    def forward(ctx, x, n_rows, act, oact, L, *params):
+        weights, biases = params[:L], params[L:]
+        y = _fused_kernels("mlp_rows").mlp_rows(x, list(weights), list(biases), act, oact, n_rows)
+        ctx.has_bias, ctx.has_rows, ctx.meta = tuple(b is not None for b in biases), n_rows is not None, (act, oact, L)
+        ctx.save_for_backward(x, *weights, *(b for b in biases if b is not None), *((n_rows,) if ctx.has_rows else ()))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        act, oact, L = ctx.meta
+        need = ctx.needs_input_grad
+        need_x, need_w = need[0], list(need[5:5 + L])
+        need_b = [ctx.has_bias[l] and need[5 + L + l] for l in range(L)]
+        if grad_y is None or not (need_x or any(need_w) or any(need_b)):
+            return (None,) * (5 + 2 * L)
+        saved = list(ctx.saved_tensors)
+        x, weights, rest = saved[0], saved[1:1 + L], saved[1 + L:]
+        biases = [rest.pop(0) if has else None for has in ctx.has_bias]
+        n_rows = rest.pop(0) if ctx.has_rows else None
+        dx, gw, gb = _fused_kernels("mlp_rows").mlp_rows_backward(x, weights, biases, act, oact, n_rows, grad_y.contiguous(), need_x, need_w, need_b)
+        return (dx, None, None, None, None, *gw, *gb)
+
+
+def mlp_rows_fused(x: th.Tensor, weights: Sequence[th.Tensor], biases: Sequence[Optional[th.Tensor]], *, activation: str = "relu",
+                   out_activation: str = "none", n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """mlp_rows(...) as one HIP kernel, and one for its backward (plus a small one that sums the workgroups' weight-gradient
+    sums in f64): a lane owns a row, the hidden activations live in its registers and never reach memory, and the backward
+    recomputes them from x -- autograd keeps x, the weights and nothing of size [N,hidden].  The same y, the same n_rows rule
+    (read on the device: no host wait, capturable; a negative count is 0), gradients to x, every weight and every bias, each
+    computed only when autograd asks for it.  Hidden width 16, 32 or 64, 1 <= Cin <= 64, 1 <= Cout <= 16, N >= 0 (ValueError).  HIP
+    float32 tensors on one device only (n_rows int32 [1]), made contiguous if they are not: anything else is a TypeError --
+    mlp_rows is the torch path for it; nothing falls back silently."""
+    name, torch_path = "mlp_rows_fused", "fragments.mlp_rows is the torch path for anything else"
+    _fused_kernels("mlp_rows")
+    weights, biases = _mlp_arguments(name, x, weights, biases, activation, out_activation, n_rows)
+    hidden, c_in, c_out = weights[0].shape[0], x.shape[1], weights[-1].shape[0]
+    if hidden not in MLP_HIDDEN:
+        raise ValueError(f"{name}: the hidden width must be one of {MLP_HIDDEN}, got {hidden}; {torch_path}")
+    if not 1 <= c_in <= 64:
+        raise ValueError(f"{name}: Cin must be in 1..64, got {c_in}; {torch_path}")
+    if not 1 <= c_out <= 16:
+        raise ValueError(f"{name}: Cout must be in 1..16, got {c_out}; {torch_path}")
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
+    floats = [("x", x)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases) if b is not None]
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if n_rows is not None and n_rows.dtype != th.int32:
+        raise TypeError(f"{name}: n_rows must be int32, got {n_rows.dtype}; {torch_path}")
+    for n, t in floats + ([] if n_rows is None else [("n_rows", n_rows)]):
+        if not t.is_cuda or t.device != x.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    return _MlpRowsFn.apply(x, None if n_rows is None else n_rows.reshape(1), ACTIVATIONS.index(activation), OUT_ACTIVATIONS.index(out_activation),
+                            len(weights), *weights, *biases)
+
+
+class RowMLP(th.nn.Module):
+    """The parameters of mlp_rows / mlp_rows_fused as a Module, so that an optimizer can own them: c_in -> hidden (x n_hidden, 1 or
+    2) -> c_out, nn.Linear's layout and initialisation.  forward(x, n_rows=None) runs mlp_rows_fused on HIP float32 rows and
+    mlp_rows on anything else.  from_sequential(seq) takes over the Linear layers of an nn.Sequential (it shares their
+    Parameters); to_sequential() is the way back."""
+
+    def __init__(self, c_in: int, hidden: int, c_out: int, n_hidden: int = 1, activation: str = "relu", out_activation: str = "none",
+                 bias: bool = True):
+        super().__init__()
+        if n_hidden not in (1, 2):
+            raise ValueError(f"RowMLP: n_hidden must be 1 or 2, got {n_hidden!r}")
+        if activation not in ACTIVATIONS or out_activation not in OUT_ACTIVATIONS:
+            raise ValueError(f"RowMLP: activation must be one of {ACTIVATIONS} and out_activation one of {OUT_ACTIVATIONS}, "
+                             f"got {activation!r}, {out_activation!r}")
+        self.activation, self.out_activation = activation, out_activation
+        dims = [c_in] + [hidden] * n_hidden + [c_out]
+        layers = [th.nn.Linear(i, o, bias=bias) for i, o in zip(dims[:-1], dims[1:])]  # (for their initialisation)
+        self.weights = th.nn.ParameterList([l.weight for l in layers])
+        self.biases = th.nn.ParameterList([l.bias for l in layers]) if bias else None
+
+    def _biases(self):
+        return [None] * len(self.weights) if self.biases is None else list(self.biases)
+
+    def forward(self, x: th.Tensor, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+        f = mlp_rows_fused if (x.is_cuda and x.dtype == th.float32) else mlp_rows
+        return f(x, list(self.weights), self._biases(), activation=self.activation, out_activation=self.out_activation, n_rows=n_rows)
+
+    @classmethod
+    def from_sequential(cls, seq: th.nn.Sequential) -> "RowMLP":
+        """An nn.Sequential of Linear, ReLU / Tanh, [Linear, ReLU / Tanh,] Linear [, Sigmoid] -> a RowMLP on the same Parameters."""
+        mods = list(seq)
+        out_activation = "none"
+        if mods and isinstance(mods[-1], th.nn.Sigmoid):
+            out_activation, mods = "sigmoid", mods[:-1]
+        linears, acts = mods[0::2], mods[1::2]
+        names = {th.nn.ReLU: "relu", th.nn.Tanh: "tanh"}
+        if (len(mods) not in (3, 5) or not all(isinstance(m, th.nn.Linear) for m in linears) or not all(type(m) in names for m in acts)
+                or len({type(m) for m in acts}) != 1):
+            raise ValueError("RowMLP.from_sequential: expected Linear, ReLU|Tanh, [Linear, the same activation,] Linear [, Sigmoid], got "
+                             + ", ".join(type(m).__name__ for m in seq))
+        has = {l.bias is not None for l in linears}
+        if len(has) != 1 or len({l.out_features for l in linears[:-1]}) != 1:
+            raise ValueError("RowMLP.from_sequential: the Linear layers must all have a bias or all have none, and one hidden width")
+        m = cls(linears[0].in_features, linears[0].out_features, linears[-1].out_features, n_hidden=len(linears) - 1,
+                activation=names[type(acts[0])], out_activation=out_activation, bias=has.pop())
+        m.weights = th.nn.ParameterList([l.weight for l in linears])
+        if m.biases is not None:
+            m.biases = th.nn.ParameterList([l.bias for l in linears])
+        return m
+
+    def to_sequential(self) -> th.nn.Sequential:
+        """The same network as an nn.Sequential of Linear layers on the same Parameters."""
+        mods = []
+        for l, (w, b) in enumerate(zip(self.weights, self._biases())):
+            lin = th.nn.Linear(w.shape[1], w.shape[0], bias=b is not None, device="meta")
+            lin.weight = w
+            if b is not None:
+                lin.bias = b
+            mods.append(lin)
+            if l < len(self.weights) - 1:
+                mods.append(th.nn.ReLU() if self.activation == "relu" else th.nn.Tanh())
+        if self.out_activation == "sigmoid":
+            mods.append(th.nn.Sigmoid())
+        return th.nn.Sequential(*mods)
