@@ -56,6 +56,9 @@
 //   mlp_rows(x [N,Cin], weights, biases, act, oact, n_rows=None) -> y [N,Cout] and mlp_rows_backward(..., grad_out, need_x,
 //   need_w, need_b) -> (dL_dx | None, [dL_dW_l | None], [dL_db_l | None]): a 1- or 2-hidden-layer MLP over packed rows
 //   (fragments.mlp_rows_fused), over include/dmesh_renderer_amd_mlp.h (SUPPORTS_FRAGMENT_MLP)
+//   hashgrid_rows(x [N,3], table [rows,F], resolutions, log2_T, n_rows=None) -> y [N,L*F] and hashgrid_rows_backward(...,
+//   grad_out, need_x, need_table) -> (dL_dx | None, dL_dtable | None): a multiresolution hash-grid encoding of packed rows
+//   (fragments.hashgrid_rows_fused), over include/dmesh_renderer_amd_hashgrid.h (SUPPORTS_FRAGMENT_HASHGRID)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -80,6 +83,7 @@
 #include "../../include/dmesh_renderer_amd_deferred.h"
 #include "../../include/dmesh_renderer_amd_packed.h"
 #include "../../include/dmesh_renderer_amd_mlp.h"
+#include "../../include/dmesh_renderer_amd_hashgrid.h"
 
 namespace {
 
@@ -128,6 +132,10 @@ struct Abi {
     // dmesh_renderer_amd_mlp.h: optional too (SUPPORTS_FRAGMENT_MLP), both or none
     decltype(&dmr_mlp_rows) mlp_rows = nullptr;
     decltype(&dmr_mlp_rows_backward) mlp_rows_backward = nullptr;
+    // dmesh_renderer_amd_hashgrid.h: optional too (SUPPORTS_FRAGMENT_HASHGRID), all three or none
+    decltype(&dmr_hashgrid_layout) hashgrid_layout = nullptr;
+    decltype(&dmr_hashgrid_rows) hashgrid_rows = nullptr;
+    decltype(&dmr_hashgrid_rows_backward) hashgrid_rows_backward = nullptr;
 };
 
 Abi g_abi;
@@ -201,6 +209,11 @@ void load_abi() {
     g_abi.mlp_rows = reinterpret_cast<decltype(g_abi.mlp_rows)>(dlsym(g_abi.handle, "dmr_mlp_rows"));
     g_abi.mlp_rows_backward = reinterpret_cast<decltype(g_abi.mlp_rows_backward)>(dlsym(g_abi.handle, "dmr_mlp_rows_backward"));
     if (!g_abi.mlp_rows || !g_abi.mlp_rows_backward) g_abi.mlp_rows = nullptr, g_abi.mlp_rows_backward = nullptr;
+    g_abi.hashgrid_layout = reinterpret_cast<decltype(g_abi.hashgrid_layout)>(dlsym(g_abi.handle, "dmr_hashgrid_layout"));
+    g_abi.hashgrid_rows = reinterpret_cast<decltype(g_abi.hashgrid_rows)>(dlsym(g_abi.handle, "dmr_hashgrid_rows"));
+    g_abi.hashgrid_rows_backward = reinterpret_cast<decltype(g_abi.hashgrid_rows_backward)>(dlsym(g_abi.handle, "dmr_hashgrid_rows_backward"));
+    if (!g_abi.hashgrid_layout || !g_abi.hashgrid_rows || !g_abi.hashgrid_rows_backward)
+        g_abi.hashgrid_layout = nullptr, g_abi.hashgrid_rows = nullptr, g_abi.hashgrid_rows_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -1267,6 +1280,76 @@ py::tuple mlp_rows_backward(In x, const std::vector<at::Tensor>& weights, const 
     return py::make_tuple(or_none(dx), gw, gb);
 }
 
+// -- hashgrid_rows: a multiresolution hash-grid encoding of [N,3] rows (dmesh_renderer_amd_hashgrid.h).  resolutions: the L
+// levels' R_l (host integers); table [rows,F] with rows = what dmr_hashgrid_layout gives.  The checks come in
+// fragments.hashgrid_rows_fused's order: shapes, sizes, one device, dtypes.
+struct HashGridArgs {
+    at::Tensor x, table, n_rows;
+    std::vector<int32_t> res;
+    int64_t N = 0, L = 0, F = 0, rows = 0;
+    int log2_T = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return stream_on(dev); }
+    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
+};
+
+HashGridArgs hashgrid_args(In x, In table, const std::vector<int64_t>& resolutions, int64_t log2_T, const std::optional<at::Tensor>& n_rows) {
+    built(g_abi.hashgrid_rows, "dmr_hashgrid_rows");
+    HashGridArgs a;
+    a.dev = hip_device_of(x);
+    if (x.dim() != 2 || x.size(1) != 3) err("x must have dimensions (rows, 3)");
+    if (table.dim() != 2) err("table must have dimensions (rows, F)");
+    a.N = x.size(0); a.L = (int64_t)resolutions.size(); a.F = table.size(1);
+    if (a.L < 1 || a.L > DMR_HASHGRID_MAX_LEVELS) err("hashgrid_rows: 1 to 16 levels, got " + std::to_string(a.L));
+    if (a.F != 1 && a.F != 2 && a.F != 4 && a.F != 8) err("hashgrid_rows: F must be 1, 2, 4 or 8, got " + std::to_string(a.F));
+    if (a.L * a.F > DMR_HASHGRID_MAX_CHANNELS) err("hashgrid_rows: L * F must be at most 64, got " + std::to_string(a.L * a.F));
+    if (log2_T < 4 || log2_T > 24) err("hashgrid_rows: log2_T must be in 4..24, got " + std::to_string(log2_T));
+    for (int64_t r : resolutions) {
+        if (r < 1 || r > 65536) err("hashgrid_rows: a resolution must be in 1..65536, got " + std::to_string(r));
+        a.res.push_back((int32_t)r);
+    }
+    a.log2_T = (int)log2_T;
+    std::vector<int64_t> offsets((size_t)a.L + 1);
+    if (g_abi.hashgrid_layout((int)a.L, a.log2_T, a.res.data(), offsets.data())) raise_lib();
+    a.rows = offsets.back();
+    if (table.size(0) != a.rows) err("hashgrid_rows: table must have " + std::to_string(a.rows) + " rows, got " + std::to_string(table.size(0)));
+    if (a.N >= ((int64_t)1 << 31)) err("hashgrid_rows: rows must be below 2^31");
+    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
+    if (table.device() != a.dev) err("hashgrid_rows: table must be on the device of x");
+    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
+    a.x = f32(x, "x");
+    a.table = f32(table, "table");
+    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    return a;
+}
+
+// -> y [N, L*F]
+at::Tensor hashgrid_rows(In x, In table, const std::vector<int64_t>& resolutions, int64_t log2_T, const std::optional<at::Tensor>& n_rows) {
+    const HashGridArgs a = hashgrid_args(x, table, resolutions, log2_T, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor y = at::empty({a.N, a.L * a.F}, f32_on(a.dev));
+    if (g_abi.hashgrid_rows((int)a.N, (int)a.L, (int)a.F, a.log2_T, a.res.data(), mptr<const float>(a.x), reinterpret_cast<const float*>(a.table.data_ptr()),
+                            a.rows_ptr(), mptr<float>(y), a.stream()))
+        raise_lib();
+    return y;
+}
+
+// need_x, need_table -> (dL_dx [N,3], dL_dtable [rows,F]), None where not asked for; grad_out [N, L*F]
+py::tuple hashgrid_rows_backward(In x, In table, const std::vector<int64_t>& resolutions, int64_t log2_T, const std::optional<at::Tensor>& n_rows,
+                                 In grad_out, bool need_x, bool need_table) {
+    const HashGridArgs a = hashgrid_args(x, table, resolutions, log2_T, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.L * a.F || grad_out.device() != a.dev)
+        err("grad_out must have dimensions (rows, L * F) on the device of x");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor dx = grad_if(need_x, {a.N, 3}, a.dev), dt = grad_if(need_table, {a.rows, a.F}, a.dev);
+    if (g_abi.hashgrid_rows_backward((int)a.N, (int)a.L, (int)a.F, a.log2_T, a.res.data(), mptr<const float>(a.x),
+                                     reinterpret_cast<const float*>(a.table.data_ptr()), a.rows_ptr(), mptr<const float>(go), out_ptr(dx), out_ptr(dt),
+                                     a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(dx), or_none(dt));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1346,6 +1429,9 @@ PYBIND11_MODULE(_C, m) {
     m.def("mlp_rows", &mlp_rows, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("act"), py::arg("oact"), py::arg("n_rows") = py::none());
     m.def("mlp_rows_backward", &mlp_rows_backward, py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("act"), py::arg("oact"),
           py::arg("n_rows"), py::arg("grad_out"), py::arg("need_x"), py::arg("need_w"), py::arg("need_b"));
+    m.def("hashgrid_rows", &hashgrid_rows, py::arg("x"), py::arg("table"), py::arg("resolutions"), py::arg("log2_T"), py::arg("n_rows") = py::none());
+    m.def("hashgrid_rows_backward", &hashgrid_rows_backward, py::arg("x"), py::arg("table"), py::arg("resolutions"), py::arg("log2_T"),
+          py::arg("n_rows"), py::arg("grad_out"), py::arg("need_x"), py::arg("need_table"));
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1381,6 +1467,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_PACKED") = g_abi.pack_slots != nullptr;
     // fragments.mlp_rows_fused; False: the loaded library predates dmesh_renderer_amd_mlp.h
     m.attr("SUPPORTS_FRAGMENT_MLP") = g_abi.mlp_rows != nullptr;
+    // fragments.hashgrid_rows_fused; False: the loaded library predates dmesh_renderer_amd_hashgrid.h
+    m.attr("SUPPORTS_FRAGMENT_HASHGRID") = g_abi.hashgrid_rows != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

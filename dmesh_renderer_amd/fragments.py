@@ -25,6 +25,12 @@ composite_values_packed_fused blends the rows the shader returns -- no permute, 
 mlp_rows_fused (csrc/dmr_mlp.hip) is that MLP -- widths 16, 32 or 64, relu or tanh, an optional sigmoid on the output -- as one
 forward and one backward kernel: the hidden activations stay in registers and the backward recomputes them, so nothing of size
 [N,hidden] is written, read or kept for autograd; mlp_rows is its torch model, RowMLP the nn.Module that picks between them.
+A LEARNED FIELD for that MLP to read -- this renderer's meshes change connectivity, so a UV atlas does not survive a step -- is a
+multiresolution hash grid (Instant-NGP) sampled at every fragment's hit point, interpolate_packed_fused(frag, packed, faces, verts):
+hashgrid_spec lays the table out (a HashGridSpec), hashgrid_rows is the torch model of the encoding [N,3] -> [N, L*F], hashgrid_rows_fused
+(csrc/dmr_hashgrid.hip) the same as one forward and one backward kernel, HashGrid the nn.Module that owns the table:
+    hit = interpolate_packed_fused(frag, packed, faces, verts)          # [N,3]; differentiable with fragment_grads=True
+    rgb = mlp(grid(hit, n_rows=packed.n_used), n_rows=packed.n_used)    # grid = HashGrid(...), mlp = RowMLP(grid.out_features, 64, 3)
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -53,6 +59,7 @@ renderer's colour and alpha differ from the lines above by 1e-5 bg and 1e-5 ther
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch as th
@@ -60,7 +67,8 @@ import torch as th
 __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "composite_fused", "composite_texture",
            "composite_texture_fused", "face_coverage", "face_visibility_fused", "composite_values", "interpolate_fused",
            "composite_values_fused", "PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused",
-           "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP"]
+           "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP",
+           "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -199,7 +207,8 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "pack_slots": ("SUPPORTS_FRAGMENT_PACKED", "fragment", "slot packing"),
           "interpolate_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed fragment", "interpolation"),
           "composite_values_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed per-slot value"),
-          "mlp_rows": ("SUPPORTS_FRAGMENT_MLP", "row", "MLP")}  # (a third entry: what stands for "compositing" in the message)
+          "mlp_rows": ("SUPPORTS_FRAGMENT_MLP", "row", "MLP"),  # (a third entry: what stands for "compositing" in the message)
+          "hashgrid_rows": ("SUPPORTS_FRAGMENT_HASHGRID", "row", "hash-grid encoding")}
 
 
 def _fused_kernels(torch_path: str):
@@ -943,3 +952,183 @@ class RowMLP(th.nn.Module):
         if self.out_activation == "sigmoid":
             mods.append(th.nn.Sigmoid())
         return th.nn.Sequential(*mods)
+
+
+# ---------------------------------------------------------------------------
+# A multiresolution hash grid over packed rows of 3-D points: the learned field in front of the MLP (csrc/dmr_hashgrid.hip)
+# ---------------------------------------------------------------------------
+HASH_PRIMES = (1, 2654435761, 805459861)  # per axis; the products are taken modulo 2^32
+HASHGRID_FEATURES = (1, 2, 4, 8)          # F; 1 <= L <= 16, L * F <= 64 (RowMLP's Cin), 4 <= log2_T <= 24, 1 <= R_l <= 65536
+
+
+class HashGridSpec(NamedTuple):
+    """The layout of a hash grid's table (hashgrid_spec): per level its resolution and its number of rows, the running sums of
+    those (offsets[L] = the rows of the table), the features per row and log2 of the hashed levels' size."""
+    resolutions: Tuple[int, ...]
+    sizes: Tuple[int, ...]
+    offsets: Tuple[int, ...]
+    features: int
+    log2_table_size: int
+
+
+def hashgrid_spec(n_levels: int = 16, features: int = 2, log2_table_size: int = 19, base_resolution: int = 16,
+                  per_level_scale: float = 1.38) -> HashGridSpec:
+    """The layout of a multiresolution hash grid (Instant-NGP) of n_levels = L levels with F = features floats per grid vertex:
+    level l has resolution R_l = floor(base_resolution * per_level_scale**l) (float64) -- R_l cells and R_l + 1 vertices per axis
+    over the unit cube -- and, with T = 2**log2_table_size, is DENSE when (R_l + 1)^3 <= T: (R_l + 1)^3 rows, vertex (ix, iy, iz)
+    in row ix + (R_l + 1) (iy + (R_l + 1) iz); else HASHED: T rows, the vertex in row ((ix * 1) ^ (iy * 2654435761) ^
+    (iz * 805459861)) & (T - 1), the products modulo 2^32.  The table is one tensor [offsets[L], F], level l owns the rows
+    [offsets[l], offsets[l+1]).  ValueError, in this order, unless 1 <= L <= 16, F in {1, 2, 4, 8}, L * F <= 64,
+    4 <= log2_table_size <= 24 and 1 <= R_l <= 65536.  Computed on the host; the C library states the same rule
+    (dmr_hashgrid_layout) and a test holds the two equal."""
+    name = "hashgrid_spec"
+    L, F, log2_T = int(n_levels), int(features), int(log2_table_size)
+    if not 1 <= L <= 16:
+        raise ValueError(f"{name}: n_levels must be in 1..16, got {n_levels!r}")
+    if F not in HASHGRID_FEATURES:
+        raise ValueError(f"{name}: features must be one of {HASHGRID_FEATURES}, got {features!r}")
+    if L * F > 64:
+        raise ValueError(f"{name}: n_levels * features must be at most 64 (RowMLP's Cin), got {L * F}")
+    if not 4 <= log2_T <= 24:
+        raise ValueError(f"{name}: log2_table_size must be in 4..24, got {log2_table_size!r}")
+    resolutions = tuple(int(math.floor(float(base_resolution) * float(per_level_scale) ** l)) for l in range(L))
+    for l, r in enumerate(resolutions):
+        if not 1 <= r <= 65536:
+            raise ValueError(f"{name}: the resolution of level {l} must be in 1..65536, got {r}")
+    T = 1 << log2_T
+    sizes = tuple((r + 1) ** 3 if (r + 1) ** 3 <= T else T for r in resolutions)
+    offsets = [0]
+    for s in sizes:
+        offsets.append(offsets[-1] + s)
+    return HashGridSpec(resolutions, sizes, tuple(offsets), F, log2_T)
+
+
+def _hashgrid_arguments(name: str, x, table, spec, n_rows):
+    """What hashgrid_rows and hashgrid_rows_fused both refuse (ValueError), in this order: the spec's type, x [N,3], table
+    [offsets[L], F], n_rows."""
+    if not isinstance(spec, HashGridSpec):
+        raise ValueError(f"{name}: spec must be a HashGridSpec (hashgrid_spec(...)), got {type(spec).__name__}")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: x must be [N,3], got {tuple(x.shape)}")
+    want = (spec.offsets[-1], spec.features)
+    if tuple(table.shape) != want:
+        raise ValueError(f"{name}: table must be [offsets[L], F] = {want}, got {tuple(table.shape)}")
+    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
+        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+
+
+def hashgrid_rows(x: th.Tensor, table: th.Tensor, spec: HashGridSpec, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """The multiresolution hash-grid encoding of rows x [N,3] of points of the unit cube -> [N, L*F], level-major channels: per
+    level l and coordinate u, u_c = clamp(u, 0, 1) with NaN counting as 0, p = u_c R_l, i = min(floor(p), R_l - 1), t = p - i in
+    [0, 1] (a point on the upper face lands in the last cell with t = 1), and
+        y[r, l F + f] = sum over the 8 corners c of w_c table[offsets[l] + row_l(i + c), f]
+    with the trilinear w_c = (wx wy) wz from (t_x, t_y, t_z) and row_l of hashgrid_spec (index arithmetic in int64 with explicit
+    & 0xffffffff).  Differentiable in table (a scatter of w_c g) and in x (dL/dx_a = sum_l R_l sum_c dw_c/dt_a (table row . g_l);
+    exactly 0 for a coordinate that is NaN or outside [0, 1], passed at exactly 0 and 1 as th.clamp does); the cell and the hash
+    are constants.  n_rows follows mlp_rows' rule (None, or an integer tensor of one element on x's device -- what
+    PackedSlots.n_used is): rows r >= min(max(n_rows, 0), N) are NOT READ, give exact zeros in y and dL_dx and add nothing to
+    dL_dtable.  Plain torch, any device, any float dtype: the model hashgrid_rows_fused is tested against."""
+    _hashgrid_arguments("hashgrid_rows", x, table, spec, n_rows)
+    zero = th.zeros((), dtype=x.dtype, device=x.device)
+    mask = None
+    if n_rows is not None:
+        mask = (th.arange(x.shape[0], device=x.device) < n_rows.reshape(1).clamp(min=0)).unsqueeze(1)
+        x = th.where(mask, x, zero)
+    u = th.where(th.isnan(x), zero, x).clamp(0, 1)
+    F, T = spec.features, 1 << spec.log2_table_size
+    out = []
+    for l, R in enumerate(spec.resolutions):
+        p = u * R
+        i = p.detach().floor().clamp(max=R - 1).clamp(min=0)
+        t = p - i
+        i = i.long()
+        dense = spec.sizes[l] == (R + 1) ** 3 and (R + 1) ** 3 <= T
+        acc = 0
+        for c in range(8):
+            cx, cy, cz = c & 1, (c >> 1) & 1, (c >> 2) & 1
+            ix, iy, iz = i[:, 0] + cx, i[:, 1] + cy, i[:, 2] + cz
+            if dense:
+                row = (ix + (R + 1) * (iy + (R + 1) * iz)).clamp(max=spec.sizes[l] - 1)
+            else:
+                row = (((ix * HASH_PRIMES[0]) & 0xffffffff) ^ ((iy * HASH_PRIMES[1]) & 0xffffffff) ^ ((iz * HASH_PRIMES[2]) & 0xffffffff)) & (T - 1)
+            wx = t[:, 0] if cx else 1 - t[:, 0]
+            wy = t[:, 1] if cy else 1 - t[:, 1]
+            wz = t[:, 2] if cz else 1 - t[:, 2]
+            acc = acc + ((wx * wy) * wz).unsqueeze(1) * table[spec.offsets[l] + row].to(x.dtype)
+        out.append(acc)
+    y = th.cat(out, dim=1)
+    return y if mask is None else th.where(mask, y, zero)
+
+
+class _HashGridRowsFn(th.autograd.Function):
+    """hashgrid_rows_fused over _C.hashgrid_rows / _C.hashgrid_rows_backward.  Arguments: x, table, n_rows (a tensor or None),
+    the spec.  Only x, table and n_rows are saved."""
+
+    @staticmethod
+    def forward(ctx, x, table, n_rows, spec):
+        y = _fused_kernels("hashgrid_rows").hashgrid_rows(x, table, list(spec.resolutions), spec.log2_table_size, n_rows)
+        ctx.spec, ctx.has_rows = spec, n_rows is not None
+        ctx.save_for_backward(x, table, *((n_rows,) if ctx.has_rows else ()))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        need_x, need_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_y is None or not (need_x or need_table):
+            return None, None, None, None
+        x, table, *rest = ctx.saved_tensors
+        dx, dtable = _fused_kernels("hashgrid_rows").hashgrid_rows_backward(x, table, list(ctx.spec.resolutions), ctx.spec.log2_table_size,
+                                                                            rest[0] if ctx.has_rows else None, grad_y.contiguous(), need_x, need_table)
+        return dx, dtable, None, None
+
+
+def hashgrid_rows_fused(x: th.Tensor, table: th.Tensor, spec: HashGridSpec, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """hashgrid_rows(...) as one HIP kernel, and one for its backward (plus the one that zeroes dL_dtable): a lane owns a row and
+    walks the levels; the forward stores y through an LDS transpose; the backward's dL/dx recomputes the eight table rows of
+    every level (a plain store per row), and its dL/dtable sums on chip what shares a table row -- the lanes of a wave, then a
+    per-workgroup LDS table of f64 cells -- before float atomics leave (so dL_dtable depends on the order of summation in its
+    last bits).  The same y, the same n_rows rule (read on the device: no host wait, capturable), each gradient computed only
+    when autograd asks for it; autograd keeps x, table and n_rows, nothing else.  N < 2^31 (ValueError).  HIP float32 tensors on
+    one device only (n_rows int32 [1]), made contiguous if they are not: anything else is a TypeError -- hashgrid_rows is the
+    torch path for it; nothing falls back silently.  Refused in this order: an older binding, the shapes (as hashgrid_rows), N,
+    the dtypes, the devices."""
+    name, torch_path = "hashgrid_rows_fused", "fragments.hashgrid_rows is the torch path for anything else"
+    _fused_kernels("hashgrid_rows")
+    _hashgrid_arguments(name, x, table, spec, n_rows)
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
+    for n, t in (("x", x), ("table", table)):
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    if n_rows is not None and n_rows.dtype != th.int32:
+        raise TypeError(f"{name}: n_rows must be int32, got {n_rows.dtype}; {torch_path}")
+    for n, t in [("x", x), ("table", table)] + ([] if n_rows is None else [("n_rows", n_rows)]):
+        if not t.is_cuda or t.device != x.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    return _HashGridRowsFn.apply(x, table, None if n_rows is None else n_rows.reshape(1), spec)
+
+
+class HashGrid(th.nn.Module):
+    """A multiresolution hash grid as a Module that owns its `table` (a Parameter [spec.offsets[L], F], initialised uniform in
+    +-1e-4, tiny-cuda-nn's choice -- not derived here): the learned volumetric field in front of a RowMLP.  Takes hashgrid_spec's
+    five numbers and the box lo, hi (3 floats each; default the unit cube).  .spec is the layout, .out_features = L * F.
+    forward(x, n_rows=None) maps (x - lo) / (hi - lo) in torch and runs hashgrid_rows_fused on HIP float32 rows and hashgrid_rows
+    on anything else."""
+
+    def __init__(self, n_levels: int = 16, features: int = 2, log2_table_size: int = 19, base_resolution: int = 16,
+                 per_level_scale: float = 1.38, lo: Sequence[float] = (0.0, 0.0, 0.0), hi: Sequence[float] = (1.0, 1.0, 1.0)):
+        super().__init__()
+        self.spec = hashgrid_spec(n_levels, features, log2_table_size, base_resolution, per_level_scale)
+        self.out_features = len(self.spec.resolutions) * self.spec.features
+        lo, hi = th.as_tensor(lo, dtype=th.float32).reshape(-1), th.as_tensor(hi, dtype=th.float32).reshape(-1)
+        if lo.numel() != 3 or hi.numel() != 3 or not bool((hi > lo).all()):
+            raise ValueError(f"HashGrid: lo and hi must hold 3 floats each with lo < hi, got {lo.tolist()}, {hi.tolist()}")
+        self.register_buffer("lo", lo.clone())
+        self.register_buffer("hi", hi.clone())
+        self.table = th.nn.Parameter(th.empty(self.spec.offsets[-1], self.spec.features).uniform_(-1e-4, 1e-4))
+
+    def forward(self, x: th.Tensor, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+        u = (x - self.lo.to(x.dtype)) / (self.hi - self.lo).to(x.dtype)
+        fused = u.is_cuda and u.dtype == th.float32 and self.table.dtype == th.float32
+        return (hashgrid_rows_fused if fused else hashgrid_rows)(u, self.table, self.spec, n_rows)
