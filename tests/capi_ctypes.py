@@ -16,6 +16,46 @@ LIB_PATH = os.environ.get("DMR_LIBRARY") or os.path.join(HERE, "libdmesh_rendere
 ABI_VERSION = 4
 
 BUF_POINT, BUF_FACE, BUF_BINNING, BUF_IMAGE, BUF_WORK = range(5)
+# outputs the library requests through `alloc` and fully overwrites / fills for the rendered rows ...
+BUF_TET_GRADS, BUF_TRI_CAMERA_GRADS, BUF_TET_CAMERA_GRADS, BUF_TRI_FRAGMENTS = 5, 6, 7, 8
+# ... and inputs the caller has filled before the call (the fragment lists' faces and the gradient of their barycentrics)
+BUF_TRI_FRAGMENT_FACES, BUF_TRI_FRAGMENT_BARY_GRADS = 9, 10
+BUF_TET_FRAGMENTS = 11
+BUF_TET_FRAGMENT_FACES, BUF_TET_FRAGMENT_BARY_GRADS = 12, 13
+NUM_BUFFERS = 14
+BUF_NAMES = ("POINT", "FACE", "BINNING", "IMAGE", "WORK", "TET_GRADS", "TRI_CAMERA_GRADS", "TET_CAMERA_GRADS", "TRI_FRAGMENTS",
+             "TRI_FRAGMENT_FACES", "TRI_FRAGMENT_BARY_GRADS", "TET_FRAGMENTS", "TET_FRAGMENT_FACES", "TET_FRAGMENT_BARY_GRADS")
+OUTPUT_BUFFERS = (BUF_TET_GRADS, BUF_TRI_CAMERA_GRADS, BUF_TET_CAMERA_GRADS, BUF_TRI_FRAGMENTS, BUF_TET_FRAGMENTS)
+INPUT_BUFFERS = (BUF_TRI_FRAGMENT_FACES, BUF_TRI_FRAGMENT_BARY_GRADS, BUF_TET_FRAGMENT_FACES, BUF_TET_FRAGMENT_BARY_GRADS)
+
+FLAG_ASYNC = 1
+FLAG_TET_FULL_GRADS = 2
+FLAG_TRI_EXACT_GRADS = 4
+FLAG_TRI_CAMERA_GRADS = 8
+FLAG_TET_CAMERA_GRADS = 16
+FLAG_ALPHA = 32
+FLAG_TRI_FRAGMENTS = 64
+FLAG_TRI_FRAGMENT_GRADS = 128
+FLAG_TET_FRAGMENTS = 1 << 16
+FLAG_TET_FRAGMENT_GRADS = 1 << 17
+FRAG_MAX_K = 32
+
+
+def fragments_k(flags: int) -> int:
+    """DMR_FRAGMENTS_K(flags)"""
+    return (flags >> 8) & 255
+
+
+def fragments_flags(k: int) -> int:
+    """DMR_FRAGMENTS_FLAGS(k)"""
+    return FLAG_TRI_FRAGMENTS | ((k & 255) << 8)
+
+
+def tet_fragments_flags(k: int) -> int:
+    """DMR_TET_FRAGMENTS_FLAGS(k)"""
+    return FLAG_TET_FRAGMENTS | ((k & 255) << 8)
+
+
 NUM_STAGES = 12
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)

@@ -50,6 +50,72 @@ def test_scene_struct_layout_matches_header():
     assert _lib.Scene.background.offset == 24 and _lib.Scene.ray_random_seed.offset == 24 + 14 * 8
 
 
+def _c_int(expr, macros):
+    """The value of a header macro body: integer literals, names of macros already known, | & << >> + - and parentheses."""
+    expr = re.sub(r"\b([A-Z_][A-Z_0-9]*)\b", lambda m: str(macros[m.group(1)]), expr)
+    assert re.fullmatch(r"[\d\s()|&<>+\-]+", expr), expr
+    return int(eval(expr, {"__builtins__": {}}))
+
+
+def _header_constants():
+    """-> ({DMR_BUF_* name: id} of the first enum, {object-like DMR_* macro: value}, {function-like macro: (parameter, body)})"""
+    src = open(HEADER).read()
+    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    enum = re.search(r"enum\s*\{([^}]*DMR_BUF_POINT[^}]*)\}", code)
+    bufs, nxt = {}, 0
+    for item in (x.strip() for x in enum.group(1).split(",")):
+        if item:
+            name, _, val = (p.strip() for p in item.partition("="))
+            nxt = int(val, 0) if val else nxt
+            bufs[name] = nxt
+            nxt += 1
+    macros, fn_macros = {}, {}
+    for m in re.finditer(r"^#define[ \t]+(DMR_[A-Z_0-9]+)(\(([a-z]+)\))?[ \t]+(.+?)[ \t]*$", code, re.M):
+        name, par, body = m.group(1), m.group(3), m.group(4)
+        if par:
+            fn_macros[name] = (par, body)
+        else:
+            macros[name] = _c_int(body, macros)
+    return bufs, macros, fn_macros
+
+
+def test_buffer_ids_and_flags_match_header():
+    """capi_ctypes restates every DMR_BUF_* id, every DMR_FLAG_* bit and the two K helpers: each is read out of the header's
+    text and held equal, and nothing the header has is missing from the table."""
+    import capi_ctypes as capi
+    bufs, macros, fn_macros = _header_constants()
+    assert len(bufs) == capi.NUM_BUFFERS == len(capi.BUF_NAMES) and sorted(bufs.values()) == list(range(capi.NUM_BUFFERS))
+    for name, which in bufs.items():
+        assert getattr(capi, name[len("DMR_"):]) == which and capi.BUF_NAMES[which] == name[len("DMR_BUF_"):], name
+    flags = {n: v for n, v in macros.items() if n.startswith("DMR_FLAG_")}
+    assert len(flags) == 10
+    for name, v in flags.items():
+        assert getattr(capi, name[len("DMR_"):]) == v, name
+    assert sorted(n for n in dir(capi) if n.startswith("FLAG_")) == sorted(n[len("DMR_"):] for n in flags)
+    assert len(set(flags.values())) == len(flags) and all(v & (v - 1) == 0 for v in flags.values())   # one bit each ...
+    assert not any(v & (255 << 8) for v in flags.values())                                            # ... none in K's bits
+    assert macros["DMR_ABI_VERSION"] == capi.ABI_VERSION
+    assert sorted(fn_macros) == ["DMR_FRAGMENTS_FLAGS", "DMR_FRAGMENTS_K", "DMR_TET_FRAGMENTS_FLAGS"]
+    helpers = {"DMR_FRAGMENTS_FLAGS": capi.fragments_flags, "DMR_TET_FRAGMENTS_FLAGS": capi.tet_fragments_flags,
+               "DMR_FRAGMENTS_K": capi.fragments_k}
+    for name, (par, body) in fn_macros.items():
+        for arg in (0, 1, 4, 31, 32, 33, 255, 256 + 7, 0x12345, (1 << 16) | (4 << 8) | 64):
+            want = _c_int(re.sub(r"\b%s\b" % par, str(arg), body), macros)
+            assert helpers[name](arg) == want, (name, arg)
+    for k in range(1, capi.FRAG_MAX_K + 1):
+        assert capi.fragments_k(capi.fragments_flags(k)) == k == capi.fragments_k(capi.tet_fragments_flags(k))
+    # which ids are outputs and which inputs: the header's own words behind each id
+    src = open(HEADER).read()
+    for name, which in bufs.items():
+        m = re.search(r"%s = %d /\*[^*]*?\b(an OUTPUT|an INPUT)\b" % (name, which), src)
+        if which in capi.OUTPUT_BUFFERS:
+            assert m and m.group(1) == "an OUTPUT", name
+        elif which in capi.INPUT_BUFFERS:
+            assert m and m.group(1) == "an INPUT", name
+        else:
+            assert which <= capi.BUF_WORK and not m, name
+
+
 def test_compiled_binding_is_the_only_one():
     """`_C` is a compiled extension module over the C ABI (no ctypes / pure-Python binding left in the product) and
     it is bound to the in-tree HIP library."""
