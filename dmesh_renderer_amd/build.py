@@ -2,7 +2,8 @@
 
   * libdmesh_renderer_hip.so -- the C ABI (include/dmesh_renderer_amd.h, dmesh_renderer_amd_shade.h, dmesh_renderer_amd_texture.h,
                                 dmesh_renderer_amd_visibility.h, dmesh_renderer_amd_deferred.h, dmesh_renderer_amd_packed.h,
-                                dmesh_renderer_amd_mlp.h, dmesh_renderer_amd_hashgrid.h) and every gfx950 kernel, with hipcc;
+                                dmesh_renderer_amd_mlp.h, dmesh_renderer_amd_hashgrid.h, dmesh_renderer_amd_sh.h) and every gfx950 kernel,
+                                with hipcc;
   * _C.<python ext suffix>   -- `dmesh_renderer_amd._C`, the compiled PyTorch-ROCm binding over that C ABI
                                 (csrc/dmr_torch.cpp: pybind11 + ATen, no kernels), with g++.
 
@@ -31,7 +32,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdmesh_renderer_hip.so")
 LIB_ABLATION = os.path.join(HERE, "libdmesh_renderer_hip_ablation.so")
 SOURCES = ["dmr_api.hip", "dmr_binning.hip", "dmr_tri.hip", "dmr_tet.hip", "dmr_shade.hip", "dmr_texture.hip", "dmr_visibility.hip",
-           "dmr_interp.hip", "dmr_packed.hip", "dmr_mlp.hip", "dmr_hashgrid.hip"]
+           "dmr_interp.hip", "dmr_packed.hip", "dmr_mlp.hip", "dmr_hashgrid.hip", "dmr_sh.hip"]
 HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_deferred_common.hpp", "dmr_texture_wrap.hpp",
            os.path.join("..", "..", "include", "dmesh_renderer_amd.h"), os.path.join("..", "..", "include", "dmesh_renderer_amd_shade.h"),
            os.path.join("..", "..", "include", "dmesh_renderer_amd_texture.h"),
@@ -39,7 +40,8 @@ HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_ti
            os.path.join("..", "..", "include", "dmesh_renderer_amd_deferred.h"),
            os.path.join("..", "..", "include", "dmesh_renderer_amd_packed.h"),
            os.path.join("..", "..", "include", "dmesh_renderer_amd_mlp.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h")]
+           os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h"),
+           os.path.join("..", "..", "include", "dmesh_renderer_amd_sh.h")]
 ARCH = "gfx950"
 
 
@@ -62,7 +64,8 @@ GLUE_SOURCES = ["dmr_torch.cpp", os.path.join("..", "..", "include", "dmesh_rend
                 os.path.join("..", "..", "include", "dmesh_renderer_amd_deferred.h"),
                 os.path.join("..", "..", "include", "dmesh_renderer_amd_packed.h"),
                 os.path.join("..", "..", "include", "dmesh_renderer_amd_mlp.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h")]
+                os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h"),
+                os.path.join("..", "..", "include", "dmesh_renderer_amd_sh.h")]
 
 
 def glue_stale() -> bool:

@@ -59,6 +59,10 @@
 //   hashgrid_rows(x [N,3], table [rows,F], resolutions, log2_T, n_rows=None) -> y [N,L*F] and hashgrid_rows_backward(...,
 //   grad_out, need_x, need_table) -> (dL_dx | None, dL_dtable | None): a multiresolution hash-grid encoding of packed rows
 //   (fragments.hashgrid_rows_fused), over include/dmesh_renderer_amd_hashgrid.h (SUPPORTS_FRAGMENT_HASHGRID)
+//   packed_row_views(row [B,K,H,W], rows) -> view i32 [rows], sh_rows(x [N,3], degree, origin=None, row_view=None, n_rows=None)
+//   -> y [N,degree^2] and sh_rows_backward(..., grad_out, need_x, need_origin) -> (dL_dx | None, dL_dorigin | None): the view
+//   direction of packed rows as spherical harmonics (fragments.packed_row_views_fused, sh_rows_fused), over
+//   include/dmesh_renderer_amd_sh.h (SUPPORTS_FRAGMENT_SH)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -84,6 +88,7 @@
 #include "../../include/dmesh_renderer_amd_packed.h"
 #include "../../include/dmesh_renderer_amd_mlp.h"
 #include "../../include/dmesh_renderer_amd_hashgrid.h"
+#include "../../include/dmesh_renderer_amd_sh.h"
 
 namespace {
 
@@ -136,6 +141,10 @@ struct Abi {
     decltype(&dmr_hashgrid_layout) hashgrid_layout = nullptr;
     decltype(&dmr_hashgrid_rows) hashgrid_rows = nullptr;
     decltype(&dmr_hashgrid_rows_backward) hashgrid_rows_backward = nullptr;
+    // dmesh_renderer_amd_sh.h: optional too (SUPPORTS_FRAGMENT_SH), all three or none
+    decltype(&dmr_packed_row_views) packed_row_views = nullptr;
+    decltype(&dmr_sh_rows) sh_rows = nullptr;
+    decltype(&dmr_sh_rows_backward) sh_rows_backward = nullptr;
 };
 
 Abi g_abi;
@@ -214,6 +223,11 @@ void load_abi() {
     g_abi.hashgrid_rows_backward = reinterpret_cast<decltype(g_abi.hashgrid_rows_backward)>(dlsym(g_abi.handle, "dmr_hashgrid_rows_backward"));
     if (!g_abi.hashgrid_layout || !g_abi.hashgrid_rows || !g_abi.hashgrid_rows_backward)
         g_abi.hashgrid_layout = nullptr, g_abi.hashgrid_rows = nullptr, g_abi.hashgrid_rows_backward = nullptr;
+    g_abi.packed_row_views = reinterpret_cast<decltype(g_abi.packed_row_views)>(dlsym(g_abi.handle, "dmr_packed_row_views"));
+    g_abi.sh_rows = reinterpret_cast<decltype(g_abi.sh_rows)>(dlsym(g_abi.handle, "dmr_sh_rows"));
+    g_abi.sh_rows_backward = reinterpret_cast<decltype(g_abi.sh_rows_backward)>(dlsym(g_abi.handle, "dmr_sh_rows_backward"));
+    if (!g_abi.packed_row_views || !g_abi.sh_rows || !g_abi.sh_rows_backward)
+        g_abi.packed_row_views = nullptr, g_abi.sh_rows = nullptr, g_abi.sh_rows_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -1350,6 +1364,89 @@ py::tuple hashgrid_rows_backward(In x, In table, const std::vector<int64_t>& res
     return py::make_tuple(or_none(dx), or_none(dt));
 }
 
+// -- packed_row_views / sh_rows: the view direction of packed rows as spherical harmonics (dmesh_renderer_amd_sh.h).  The checks
+// come in fragments.sh_rows_fused's order: shapes, sizes, one device, dtypes.
+// -> view i32 [rows]: the view of the slot that owns each packed row, -1 where no slot does
+at::Tensor packed_row_views(In row, int64_t rows) {
+    built(g_abi.packed_row_views, "dmr_packed_row_views");
+    const c10::Device dev = hip_device_of(row);
+    if (row.dim() != 4) err("row must have dimensions (B, K, H, W)");
+    if (rows < 0 || rows >= ((int64_t)1 << 31)) err("packed_row_views: rows must be in 0..2^31 - 1");
+    const int64_t B = row.size(0), K = row.size(1), H = row.size(2), W = row.size(3);
+    if (B * K * H * W >= ((int64_t)1 << 31)) err("packed_row_views: B K H W must be below 2^31");
+    const at::Tensor r = i32(row, "row");
+    c10::DeviceGuard guard(dev);
+    if (B * H * W == 0) return at::full({rows}, -1, at::TensorOptions().dtype(at::kInt).device(dev));  // (the C call enqueues nothing)
+    at::Tensor view = at::empty({rows}, at::TensorOptions().dtype(at::kInt).device(dev));
+    if (g_abi.packed_row_views((int)B, (int)K, (int)H, (int)W, (int)rows, mptr<const int32_t>(r), mptr<int32_t>(view), stream_on(dev))) raise_lib();
+    return view;
+}
+
+struct ShArgs {
+    at::Tensor x, origin, row_view, n_rows;
+    int64_t N = 0, B = 0, degree = 0;
+    c10::Device dev{c10::kCPU};
+    void* stream() const { return stream_on(dev); }
+    const float* origin_ptr() const { return origin.defined() ? reinterpret_cast<const float*>(origin.data_ptr()) : nullptr; }
+    const int32_t* view_ptr() const { return row_view.defined() ? reinterpret_cast<const int32_t*>(row_view.data_ptr()) : nullptr; }
+    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
+};
+
+ShArgs sh_args(In x, int64_t degree, const std::optional<at::Tensor>& origin, const std::optional<at::Tensor>& row_view,
+               const std::optional<at::Tensor>& n_rows) {
+    built(g_abi.sh_rows, "dmr_sh_rows");
+    ShArgs a;
+    a.dev = hip_device_of(x);
+    if (x.dim() != 2 || x.size(1) != 3) err("x must have dimensions (rows, 3)");
+    a.N = x.size(0); a.degree = degree;
+    if (degree < 1 || degree > DMR_SH_MAX_DEGREE) err("sh_rows: degree must be in 1..4, got " + std::to_string(degree));
+    if (origin) {
+        if (origin->dim() != 2 || origin->size(1) != 3) err("origin must have dimensions (views, 3)");
+        a.B = origin->size(0);
+        if (a.B < 1 || a.B > DMR_SH_MAX_VIEWS) err("sh_rows: 1 to " + std::to_string(DMR_SH_MAX_VIEWS) + " views, got " + std::to_string(a.B));
+    }
+    if (row_view && !origin) err("sh_rows: row_view without origin");
+    if (row_view && (row_view->dim() != 1 || row_view->size(0) != a.N)) err("row_view must have dimensions (rows)");
+    if (a.N >= ((int64_t)1 << 31)) err("sh_rows: rows must be below 2^31");
+    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
+    if (origin && origin->device() != a.dev) err("sh_rows: origin must be on the device of x");
+    if (row_view && row_view->device() != a.dev) err("sh_rows: row_view must be on the device of x");
+    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
+    a.x = f32(x, "x");
+    if (origin) a.origin = f32(*origin, "origin");
+    if (row_view) a.row_view = i32(*row_view, "row_view");
+    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    return a;
+}
+
+// -> y [N, degree^2]
+at::Tensor sh_rows(In x, int64_t degree, const std::optional<at::Tensor>& origin, const std::optional<at::Tensor>& row_view,
+                   const std::optional<at::Tensor>& n_rows) {
+    const ShArgs a = sh_args(x, degree, origin, row_view, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor y = at::empty({a.N, a.degree * a.degree}, f32_on(a.dev));
+    if (g_abi.sh_rows((int)a.N, (int)a.degree, (int)a.B, mptr<const float>(a.x), a.origin_ptr(), a.N ? a.view_ptr() : nullptr, a.rows_ptr(),
+                      mptr<float>(y), a.stream()))
+        raise_lib();
+    return y;
+}
+
+// need_x, need_origin -> (dL_dx [N,3], dL_dorigin [B,3]), None where not asked for; grad_out [N, degree^2]
+py::tuple sh_rows_backward(In x, int64_t degree, const std::optional<at::Tensor>& origin, const std::optional<at::Tensor>& row_view,
+                           const std::optional<at::Tensor>& n_rows, In grad_out, bool need_x, bool need_origin) {
+    const ShArgs a = sh_args(x, degree, origin, row_view, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.degree * a.degree || grad_out.device() != a.dev)
+        err("grad_out must have dimensions (rows, degree^2) on the device of x");
+    if (need_origin && !origin) err("sh_rows_backward: need_origin without origin");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor dx = grad_if(need_x, {a.N, 3}, a.dev), dorg = grad_if(need_origin, {a.B, 3}, a.dev);
+    if (g_abi.sh_rows_backward((int)a.N, (int)a.degree, (int)a.B, mptr<const float>(a.x), a.origin_ptr(), a.N ? a.view_ptr() : nullptr, a.rows_ptr(),
+                               mptr<const float>(go), out_ptr(dx), out_ptr(dorg), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(dx), or_none(dorg));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1432,6 +1529,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("hashgrid_rows", &hashgrid_rows, py::arg("x"), py::arg("table"), py::arg("resolutions"), py::arg("log2_T"), py::arg("n_rows") = py::none());
     m.def("hashgrid_rows_backward", &hashgrid_rows_backward, py::arg("x"), py::arg("table"), py::arg("resolutions"), py::arg("log2_T"),
           py::arg("n_rows"), py::arg("grad_out"), py::arg("need_x"), py::arg("need_table"));
+    m.def("packed_row_views", &packed_row_views, py::arg("row"), py::arg("rows"));
+    m.def("sh_rows", &sh_rows, py::arg("x"), py::arg("degree"), py::arg("origin") = py::none(), py::arg("row_view") = py::none(),
+          py::arg("n_rows") = py::none());
+    m.def("sh_rows_backward", &sh_rows_backward, py::arg("x"), py::arg("degree"), py::arg("origin"), py::arg("row_view"), py::arg("n_rows"),
+          py::arg("grad_out"), py::arg("need_x"), py::arg("need_origin"));
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1469,6 +1571,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_MLP") = g_abi.mlp_rows != nullptr;
     // fragments.hashgrid_rows_fused; False: the loaded library predates dmesh_renderer_amd_hashgrid.h
     m.attr("SUPPORTS_FRAGMENT_HASHGRID") = g_abi.hashgrid_rows != nullptr;
+    // fragments.packed_row_views_fused / sh_rows_fused; False: the loaded library predates dmesh_renderer_amd_sh.h
+    m.attr("SUPPORTS_FRAGMENT_SH") = g_abi.sh_rows != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

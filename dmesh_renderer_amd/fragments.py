@@ -31,6 +31,16 @@ hashgrid_spec lays the table out (a HashGridSpec), hashgrid_rows is the torch mo
 (csrc/dmr_hashgrid.hip) the same as one forward and one backward kernel, HashGrid the nn.Module that owns the table:
     hit = interpolate_packed_fused(frag, packed, faces, verts)          # [N,3]; differentiable with fragment_grads=True
     rgb = mlp(grid(hit, n_rows=packed.n_used), n_rows=packed.n_used)    # grid = HashGrid(...), mlp = RowMLP(grid.out_features, 64, 3)
+THE VIEW DIRECTION is that appearance model's other input -- without it the chain learns view-independent colour only: no
+specular, no sheen.  A packed row does not know its view; packed_row_views_fused (packed_row_views is the torch model) tells, per
+row, the view b of the slot that owns it.  sh_rows is the torch model of the encoding: per row w = x - origin[row_view], d = w / |w|,
+and the degree^2 real spherical harmonics of d (tiny-cuda-nn's "SphericalHarmonics"); sh_rows_fused (csrc/dmr_sh.hip) the same as
+one forward and one backward kernel, ViewSH the nn.Module, camera_origins the camera centres of the Modules' mv_mats (plain
+torch through th.linalg.inv: dL/dorigin reaches mv_mats for pose refinement):
+    view = FG.packed_row_views_fused(frag, packed)
+    hit  = FG.interpolate_packed_fused(frag, packed, faces, verts)
+    enc  = th.cat([grid(hit, n_rows=n), FG.ViewSH(4)(hit, FG.camera_origins(mv_mats), view, n_rows=n)], 1)
+    image, T = FG.composite_values_packed_fused(frag, packed, faces_opacity, mlp(enc, n_rows=n))
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -68,7 +78,8 @@ __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "comp
            "composite_texture_fused", "face_coverage", "face_visibility_fused", "composite_values", "interpolate_fused",
            "composite_values_fused", "PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused",
            "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP",
-           "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid"]
+           "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid",
+           "packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -208,7 +219,9 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "interpolate_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed fragment", "interpolation"),
           "composite_values_packed": ("SUPPORTS_FRAGMENT_PACKED", "packed per-slot value"),
           "mlp_rows": ("SUPPORTS_FRAGMENT_MLP", "row", "MLP"),  # (a third entry: what stands for "compositing" in the message)
-          "hashgrid_rows": ("SUPPORTS_FRAGMENT_HASHGRID", "row", "hash-grid encoding")}
+          "hashgrid_rows": ("SUPPORTS_FRAGMENT_HASHGRID", "row", "hash-grid encoding"),
+          "packed_row_views": ("SUPPORTS_FRAGMENT_SH", "packed row", "view map"),
+          "sh_rows": ("SUPPORTS_FRAGMENT_SH", "row", "spherical-harmonics encoding")}
 
 
 def _fused_kernels(torch_path: str):
@@ -1132,3 +1145,219 @@ class HashGrid(th.nn.Module):
         u = (x - self.lo.to(x.dtype)) / (self.hi - self.lo).to(x.dtype)
         fused = u.is_cuda and u.dtype == th.float32 and self.table.dtype == th.float32
         return (hashgrid_rows_fused if fused else hashgrid_rows)(u, self.table, self.spec, n_rows)
+
+
+# ---------------------------------------------------------------------------
+# The view direction of packed rows as real spherical harmonics: the MLP's second input beside the hash grid (csrc/dmr_sh.hip)
+# ---------------------------------------------------------------------------
+SH_MAX_DEGREE = 4      # degree^2 = 1, 4, 9 or 16 channels
+SH_MAX_VIEWS = 1024    # DMR_SH_MAX_VIEWS: the rows of `origin`
+SH_MIN_LENGTH = 1e-8   # a shorter (or non-finite) |w| gives the zero direction
+
+
+def packed_row_views(frag, packed: PackedSlots) -> th.Tensor:
+    """int32 [N], N = packed.rows: entry r is the view index b of the slot that owns row r of a packed tensor -- a slot (b, k, y, x)
+    counts when 0 <= packed.row < N --, and -1 in every row no slot owns (the tail [min(n_used, N), N) under capacity=M).  If two
+    slots claim one row (a `packed` made for other lists) the entry is one of their views.  Nothing is differentiable; frag.bary
+    is not read.  Plain torch, any device: the model packed_row_views_fused is tested against."""
+    B, K, H, W = _check_lists("packed_row_views", frag, False)
+    rows = _check_packed("packed_row_views", "", frag, packed)
+    row = packed.row
+    live = (row >= 0) & (row < rows)
+    view = th.arange(B, dtype=th.int32, device=row.device).view(B, 1, 1, 1).expand(B, K, H, W)
+    out = th.full((rows,), -1, dtype=th.int32, device=row.device)
+    out[row[live].long()] = view[live]
+    return out
+
+
+def packed_row_views_fused(frag, packed: PackedSlots) -> th.Tensor:
+    """packed_row_views(...) as two stream-ordered HIP launches (a fill with -1, one walk of the slots on the packed unit's lanes
+    that writes 4 bytes per counting slot): the same int32 [N], exactly, for a `packed` whose rows have one owner each.  No host
+    wait, capturable.  N == 0 or an empty image launches nothing.  K <= 32, B K H W < 2^31 (ValueError).  HIP int32 lists only:
+    anything else is a TypeError -- packed_row_views is the torch path for it; nothing falls back silently."""
+    name, torch_path = "packed_row_views_fused", "fragments.packed_row_views is the torch path for anything else"
+    c = _fused_kernels("packed_row_views")
+    B, K, H, W = _check_lists(name, frag, False)
+    rows = _check_packed(name, torch_path, frag, packed)
+    if B * K * H * W >= 2 ** 31 or rows >= 2 ** 31:
+        raise ValueError(f"{name}: B K H W and packed.rows must be below 2^31, got {B * K * H * W} slots, {rows} rows")
+    _check_tensors(name, torch_path, frag.pix_to_face, [("packed.row", packed.row)], [])
+    return c.packed_row_views(packed.row, rows)
+
+
+def _sh_arguments(name: str, x, degree, origin, row_view, n_rows) -> int:
+    """What sh_rows and sh_rows_fused both refuse (ValueError), in this order: x [N,3], degree, origin [B,3] and B, row_view
+    without origin, row_view [N], origin of several views without row_view, n_rows.  -> B (0 without origin)"""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: x must be [N,3], got {tuple(x.shape)}")
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= SH_MAX_DEGREE:
+        raise ValueError(f"{name}: degree must be an int in 1..{SH_MAX_DEGREE}, got {degree!r}")
+    B = 0
+    if origin is not None:
+        if origin.dim() != 2 or origin.shape[1] != 3:
+            raise ValueError(f"{name}: origin must be [B,3], got {tuple(origin.shape)}")
+        B = origin.shape[0]
+        if not 1 <= B <= SH_MAX_VIEWS:
+            raise ValueError(f"{name}: origin must hold 1..{SH_MAX_VIEWS} views, got {B}")
+    if row_view is not None:
+        if origin is None:
+            raise ValueError(f"{name}: row_view needs origin (with origin=None x holds the directions themselves)")
+        if tuple(row_view.shape) != (x.shape[0],):
+            raise ValueError(f"{name}: row_view must be [N] = {(x.shape[0],)}, got {tuple(row_view.shape)}")
+    elif B > 1:
+        raise ValueError(f"{name}: origin holds {B} views: row_view must tell the view of every row (packed_row_views_fused)")
+    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
+        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+    return B
+
+
+def _sh_polynomials(d: th.Tensor, degree: int) -> th.Tensor:
+    """[N, degree^2]: channel l*l + l + m is the real spherical harmonic Y_lm of d [N,3] in the Condon-Shortley sign convention,
+    written as a homogeneous polynomial of d = (x, y, z) -- the table of include/dmesh_renderer_amd_sh.h."""
+    x, y, z = d[:, 0], d[:, 1], d[:, 2]
+    out = [x * 0 + 0.28209479177387814]   # (d is finite; the product keeps the constant in the graph: its gradient is an exact 0)
+    if degree >= 2:
+        out += [-0.4886025119029199 * y, 0.4886025119029199 * z, -0.4886025119029199 * x]
+    if degree >= 3:
+        xx, yy, zz = x * x, y * y, z * z
+        out += [1.0925484305920792 * (x * y), -1.0925484305920792 * (y * z), 0.31539156525252005 * (2 * zz - xx - yy),
+                -1.0925484305920792 * (x * z), 0.5462742152960396 * (xx - yy)]
+    if degree >= 4:
+        out += [-0.5900435899266435 * y * (3 * xx - yy), 2.890611442640554 * (x * y) * z, -0.4570457994644658 * y * (4 * zz - xx - yy),
+                0.3731763325901154 * z * (2 * zz - 3 * xx - 3 * yy), -0.4570457994644658 * x * (4 * zz - xx - yy),
+                1.445305721320277 * z * (xx - yy), -0.5900435899266435 * x * (xx - 3 * yy)]
+    return th.stack(out, dim=1)
+
+
+def _sh_directions(x, origin, row_view, n_rows):
+    """(d [N,3], live bool [N]) of sh_rows: the unit vectors (zeros where the length is not finite or below SH_MIN_LENGTH, and in
+    rows that are not read) and the rows that are read.  What is masked out is masked BEFORE it is used: a NaN there reaches
+    neither d nor a gradient."""
+    N = x.shape[0]
+    zero = th.zeros((), dtype=x.dtype, device=x.device)
+    live = th.ones(N, dtype=th.bool, device=x.device)
+    if n_rows is not None:
+        live = live & (th.arange(N, device=x.device) < n_rows.reshape(1).clamp(min=0))
+    w = x
+    if origin is not None:
+        if row_view is not None:
+            v = row_view.long()
+            live = live & (v >= 0) & (v < origin.shape[0])
+            o = origin.to(x.dtype)[v.clamp(0, origin.shape[0] - 1)]
+        else:
+            o = origin.to(x.dtype)[0].unsqueeze(0).expand(N, 3)
+        w = th.where(live.unsqueeze(1), x, zero) - th.where(live.unsqueeze(1), o, zero)
+    else:
+        w = th.where(live.unsqueeze(1), x, zero)
+    n = th.sqrt((w.detach() * w.detach()).sum(1))
+    ok = live & th.isfinite(n) & ~(n < SH_MIN_LENGTH)
+    unit = th.zeros(3, dtype=x.dtype, device=x.device)
+    unit[2] = 1
+    safe = th.where(ok.unsqueeze(1), w, unit)     # (the rows that are not ok leave here: their gradient is an exact 0)
+    d = safe / th.sqrt((safe * safe).sum(1, keepdim=True))
+    return th.where(ok.unsqueeze(1), d, zero), live
+
+
+def sh_rows(x: th.Tensor, degree: int, *, origin: Optional[th.Tensor] = None, row_view: Optional[th.Tensor] = None,
+            n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """The view direction of rows x [N,3] as real spherical harmonics -> [N, degree^2], degree 1..4.  Per row r:
+        v = row_view[r] (an integer tensor [N]; without it v = 0)
+        w = x[r] - origin[v] with origin [B,3], 1 <= B <= 1024 -- or w = x[r] with origin=None: the caller hands over directions
+            (row_view must then be None; an origin of B > 1 views needs row_view)
+        n = sqrt(w . w) in x's dtype, d = w / n -- d = (0, 0, 0) if n is not finite or n < 1e-8: dL/dx of the row is then an exact
+            0 and it adds nothing to dL/dorigin
+        y[r, l*l + l + m] = Y_lm(d), Condon-Shortley signs, homogeneous polynomials of d (tiny-cuda-nn's and the Gaussian-splatting
+            code's basis; the table is in include/dmesh_renderer_amd_sh.h)
+    NOT READ -- a NaN there reaches nothing; exact zeros in y and dL/dx, nothing added to dL/dorigin -- are a row whose v lies
+    outside [0, B) (-1 is what packed_row_views gives a row no slot owns) and a row at or past min(max(n_rows, 0), N), mlp_rows'
+    rule (n_rows: None, or an integer tensor of one element on x's device -- what PackedSlots.n_used is).  A row that is read and
+    has d = 0 gives (0.2820..., 0, ..., 0).  Differentiable in x and origin: dL/dw = (gd - d (d . gd)) / n with gd = sum_i g_i
+    dY_i/dd, dL/dx = dL/dw, dL/dorigin[v] = - the sum over the rows of v.  Plain torch, any device, any float dtype: the model
+    sh_rows_fused is tested against."""
+    _sh_arguments("sh_rows", x, degree, origin, row_view, n_rows)
+    d, live = _sh_directions(x, origin, row_view, n_rows)
+    y = _sh_polynomials(d, degree)
+    return th.where(live.unsqueeze(1), y, th.zeros((), dtype=y.dtype, device=y.device))
+
+
+class _ShRowsFn(th.autograd.Function):
+    """sh_rows_fused over _C.sh_rows / _C.sh_rows_backward.  Arguments: x, origin, row_view, n_rows (tensors or None), degree.
+    Only those tensors are saved: nothing of size [N, degree^2]; the backward recomputes d."""
+
+    @staticmethod
+    def forward(ctx, x, origin, row_view, n_rows, degree):
+        y = _fused_kernels("sh_rows").sh_rows(x, degree, origin, row_view, n_rows)
+        ctx.degree = degree
+        ctx.has = (origin is not None, row_view is not None, n_rows is not None)
+        ctx.save_for_backward(x, *(t for t in (origin, row_view, n_rows) if t is not None))
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        need_x, need_origin = ctx.needs_input_grad[0], ctx.has[0] and ctx.needs_input_grad[1]
+        if grad_y is None or not (need_x or need_origin):
+            return None, None, None, None, None
+        x, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        origin, row_view, n_rows = (next(rest) if h else None for h in ctx.has)
+        dx, dorigin = _fused_kernels("sh_rows").sh_rows_backward(x, ctx.degree, origin, row_view, n_rows, grad_y.contiguous(), need_x, need_origin)
+        return dx, dorigin, None, None, None
+
+
+def sh_rows_fused(x: th.Tensor, degree: int, *, origin: Optional[th.Tensor] = None, row_view: Optional[th.Tensor] = None,
+                  n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """sh_rows(...) as one HIP kernel, and one for its backward (plus the one that zeroes dL_dorigin): a lane owns a row, `degree`
+    is a template parameter, y leaves through an LDS transpose at degree 3 and 4 (row by row below; the upstream arrives row by row).
+    The same y, the same rows not read (n_rows and row_view are read on the device: no host wait, capturable), each gradient
+    computed only when autograd asks for it; autograd keeps x, origin, row_view and n_rows, nothing of size [N, degree^2].
+    dL_dorigin sums a wave's rows with DPP, then per workgroup in an LDS table of f64 cells, before one float atomic per cell
+    leaves -- so it depends on the order of summation in its last bits; y and dL_dx do not.  N < 2^31 (ValueError).  HIP float32
+    tensors on one device only (row_view int32 [N], n_rows int32 [1]), made contiguous if they are not: anything else is a
+    TypeError -- sh_rows is the torch path for it; nothing falls back silently.  Refused in this order: an older binding, the
+    arguments (as sh_rows), N, the dtypes, the devices."""
+    name, torch_path = "sh_rows_fused", "fragments.sh_rows is the torch path for anything else"
+    _fused_kernels("sh_rows")
+    _sh_arguments(name, x, degree, origin, row_view, n_rows)
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
+    floats = [("x", x)] + ([] if origin is None else [("origin", origin)])
+    ints = ([] if row_view is None else [("row_view", row_view)]) + ([] if n_rows is None else [("n_rows", n_rows)])
+    for n, t in floats:
+        if t.dtype != th.float32:
+            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
+    for n, t in ints:
+        if t.dtype != th.int32:
+            raise TypeError(f"{name}: {n} must be int32, got {t.dtype}; {torch_path}")
+    for n, t in floats + ints:
+        if not t.is_cuda or t.device != x.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    return _ShRowsFn.apply(x, origin, row_view, None if n_rows is None else n_rows.reshape(1), degree)
+
+
+def camera_origins(mv_mats: th.Tensor) -> th.Tensor:
+    """[B,3]: the camera centre of every view, from the Modules' mv_mats [B,4,4] (what TriRenderer / TetRenderer.forward take):
+    the translation column of the inverse, inv(mv_mats)[:, :3, 3] -- the Modules hand mv_mats.transpose(1, 2) and its inverse
+    down, and the kernels read a pixel ray's origin at inv_mv[12..14] of that storage, which is this column.  Plain torch through
+    th.linalg.inv, so it is differentiable: dL/dorigin reaches mv_mats (pose refinement)."""
+    if mv_mats.dim() != 3 or tuple(mv_mats.shape[1:]) != (4, 4):
+        raise ValueError(f"camera_origins: mv_mats must be [B,4,4], got {tuple(mv_mats.shape)}")
+    return th.linalg.inv(mv_mats)[:, :3, 3]
+
+
+class ViewSH(th.nn.Module):
+    """The spherical-harmonics encoding of the view direction as a Module without parameters: .degree, .out_features =
+    degree^2.  forward(x, origin=None, row_view=None, n_rows=None) runs sh_rows_fused on HIP float32 rows and sh_rows on
+    anything else, as HashGrid does."""
+
+    def __init__(self, degree: int = 4):
+        super().__init__()
+        if isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= SH_MAX_DEGREE:
+            raise ValueError(f"ViewSH: degree must be an int in 1..{SH_MAX_DEGREE}, got {degree!r}")
+        self.degree = degree
+        self.out_features = degree * degree
+
+    def forward(self, x: th.Tensor, origin: Optional[th.Tensor] = None, row_view: Optional[th.Tensor] = None,
+                n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+        fused = x.is_cuda and x.dtype == th.float32 and (origin is None or origin.dtype == th.float32)
+        return (sh_rows_fused if fused else sh_rows)(x, self.degree, origin=origin, row_view=row_view, n_rows=n_rows)
