@@ -32,16 +32,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdmesh_renderer_hip.so")
 LIB_ABLATION = os.path.join(HERE, "libdmesh_renderer_hip_ablation.so")
 SOURCES = ["dmr_api.hip", "dmr_binning.hip", "dmr_tri.hip", "dmr_tet.hip", "dmr_shade.hip", "dmr_texture.hip", "dmr_visibility.hip",
-           "dmr_interp.hip", "dmr_packed.hip", "dmr_mlp.hip", "dmr_hashgrid.hip", "dmr_sh.hip"]
-HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_deferred_common.hpp", "dmr_texture_wrap.hpp",
-           os.path.join("..", "..", "include", "dmesh_renderer_amd.h"), os.path.join("..", "..", "include", "dmesh_renderer_amd_shade.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_texture.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_visibility.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_deferred.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_packed.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_mlp.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h"),
-           os.path.join("..", "..", "include", "dmesh_renderer_amd_sh.h")]
+           "dmr_interp.hip", "dmr_packed.hip", "dmr_rows_common.hip", "dmr_mlp.hip", "dmr_hashgrid.hip", "dmr_sh.hip"]
+PUBLIC_HEADERS = [os.path.join("..", "..", "include", h + ".h") for h in (  # THE list of them (the docstring names them too)
+    "dmesh_renderer_amd", "dmesh_renderer_amd_shade", "dmesh_renderer_amd_texture", "dmesh_renderer_amd_visibility", "dmesh_renderer_amd_deferred",
+    "dmesh_renderer_amd_packed", "dmesh_renderer_amd_mlp", "dmesh_renderer_amd_hashgrid", "dmesh_renderer_amd_sh")]
+HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_deferred_common.hpp",
+           "dmr_rows_common.hpp", "dmr_texture_wrap.hpp"] + PUBLIC_HEADERS
 ARCH = "gfx950"
 
 
@@ -57,15 +53,7 @@ def _glue_path() -> str:
     return os.path.join(HERE, "_C" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 
-GLUE_SOURCES = ["dmr_torch.cpp", os.path.join("..", "..", "include", "dmesh_renderer_amd.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_shade.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_texture.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_visibility.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_deferred.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_packed.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_mlp.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_hashgrid.h"),
-                os.path.join("..", "..", "include", "dmesh_renderer_amd_sh.h")]
+GLUE_SOURCES = ["dmr_torch.cpp"] + PUBLIC_HEADERS
 
 
 def glue_stale() -> bool:

@@ -11,7 +11,7 @@
 //
 // Rows r >= min(max(n_rows[0], 0), N) are not read.  Every table row index is clamped (dense level) or masked (hashed level) into
 // its level's slice as the last step before the access.  Offsets into y, grad_out and table are int64_t.
-#include "dmr_shade_common.hpp"
+#include "dmr_rows_common.hpp"
 #include "../../include/dmesh_renderer_amd_hashgrid.h"
 
 namespace dmr {
@@ -43,16 +43,6 @@ struct HgParams {
     int dbg;
 #endif
 };
-
-__device__ __forceinline__ int hg_rows_used(const HgParams& p) {
-    if (!p.n_rows) return p.N;
-    const int u = p.n_rows[0];
-    return u < 0 ? 0 : (u > p.N ? p.N : u);
-}
-__device__ __forceinline__ void hg_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // a coordinate at a level of resolution R: the cell i in 0 .. R - 1 and t = p - i in [0, 1]
 struct HgAxis { int i; float t; };
@@ -103,7 +93,7 @@ k_hashgrid_rows(HgParams p, int tiles, float* __restrict__ y) {
     __shared__ float stage[HG_THREADS / 64][64 * HG_PITCH];
     const int tid = threadIdx.x, lane = tid & 63;
     float* st = stage[tid >> 6];
-    const int n = hg_rows_used(p);
+    const int n = rows_used(p);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (int64_t)tile * HG_THREADS + tid, row0 = row - lane;
         if (row0 >= p.N) continue;  // (wave-uniform)
@@ -137,14 +127,14 @@ k_hashgrid_rows(HgParams p, int tiles, float* __restrict__ y) {
                 }
             }
             if constexpr (VIA_LDS) {
-                hg_wave_sync();
+                rows_wave_sync();
                 const int c0 = l0 * F, cw = p.C - c0 < HG_CHUNK ? p.C - c0 : HG_CHUNK;
 #pragma unroll
                 for (int i = 0; i < HG_CHUNK; i++) {
                     const int e = i * 64 + lane, r = e / HG_CHUNK, c = e % HG_CHUNK;
                     if (c < cw && row0 + r < p.N) y[(row0 + r) * p.C + c0 + c] = st[r * HG_PITCH + c];
                 }
-                hg_wave_sync();
+                rows_wave_sync();
             }
         }
     }
@@ -222,10 +212,9 @@ k_hashgrid_rows_backward(HgParams p, int tiles, const float* __restrict__ gout, 
         }
         if (tid == 0) filled = 0;
     };
-    const int n = hg_rows_used(p);
-    const int per = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = (int)blockIdx.x * per, t1 = t0 + per < tiles ? t0 + per : tiles;
-    for (int tile = t0; tile < t1; tile++) {
+    const int n = rows_used(p);
+    const RowsTileRun run = rows_tile_run(tiles);
+    for (int tile = run.t0; tile < run.t1; tile++) {
         const int64_t row = (int64_t)tile * HG_THREADS + tid;
         const bool active = row < n;
         const unsigned long long live = __ballot(active);
@@ -309,21 +298,7 @@ k_hashgrid_rows_backward(HgParams p, int tiles, const float* __restrict__ gout, 
     if constexpr (WT) flush();
 }
 
-// dL_dtable before the backward adds into it (a kernel, not a memset node: README, "HIP graphs")
-__global__ void __launch_bounds__(256) k_hashgrid_zero(float* __restrict__ a, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] = 0.f;
-}
-
 #pragma clang fp contract(off)
-
-// f(F) as an integral constant: the 4 instantiations of the forward, the 12 of the backward
-template <class Fn>
-void hg_with_features(int F, Fn&& f) {
-    if (F == 1) f(std::integral_constant<int, 1>());
-    else if (F == 2) f(std::integral_constant<int, 2>());
-    else if (F == 4) f(std::integral_constant<int, 4>());
-    else f(std::integral_constant<int, 8>());
-}
 
 // THE layout rule (the header states it): the rows of level l, dense when (R + 1)^3 <= T
 int64_t hg_level_rows(int R, int log2_T, bool* dense) {
@@ -403,15 +378,15 @@ int dmr_hashgrid_rows(int N, int L, int F, int log2_T, const int32_t* resolution
     if (N == 0) return 0;
     if (!y) return api_fail("dmr_hashgrid_rows: null output");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int tiles = (int)(((int64_t)N + HG_THREADS - 1) / HG_THREADS);
-    dim3 groups((unsigned)(tiles < HG_MAX_GROUPS ? tiles : HG_MAX_GROUPS)), block(HG_THREADS);
-    hg_with_features(F, [&](auto f) {
+    const RowsGrid g = rows_grid(N, HG_THREADS, HG_MAX_GROUPS);
+    dim3 groups((unsigned)g.groups), block(HG_THREADS);
+    with_one_of<1, 2, 4, 8>(F, [&](auto f) {  // (the 4 instantiations of the forward)
         constexpr int FF = decltype(f)::value;
 #ifdef DMR_ABLATION
         if (p.dbg & HG_FWD_PER_CHUNK) groups.y = (unsigned)((L * FF + HG_CHUNK - 1) / HG_CHUNK);  // a (row block, chunk of levels) grid
-        if (p.dbg & HG_FWD_LANE_STORE) { k_hashgrid_rows<FF, false><<<groups, block, 0, st>>>(p, tiles, y); return; }
+        if (p.dbg & HG_FWD_LANE_STORE) { k_hashgrid_rows<FF, false><<<groups, block, 0, st>>>(p, g.tiles, y); return; }
 #endif
-        k_hashgrid_rows<FF, true><<<groups, block, 0, st>>>(p, tiles, y);
+        k_hashgrid_rows<FF, true><<<groups, block, 0, st>>>(p, g.tiles, y);
     });
     return launched(name);
 }
@@ -422,24 +397,20 @@ int dmr_hashgrid_rows_backward(int N, int L, int F, int log2_T, const int32_t* r
     const char* name = "dmr_hashgrid_rows_backward";
     HgParams p;
     if (hg_params(name, N, L, F, log2_T, resolutions, x, table, n_rows, p)) return 1;
-    if (N > 0 && !grad_out) return api_fail("dmr_hashgrid_rows_backward: null grad_out");
-    if (N == 0) dL_dx = nullptr;  // (no row to write)
-    if (!dL_dx && !dL_dtable) return 0;
+    const int go = rows_backward_prologue(name, N, grad_out, nullptr, dL_dx, dL_dtable != nullptr);
+    if (go != SHADE_LAUNCH) return go;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dL_dtable) {
-        const int64_t floats = (int64_t)p.off[HG_MAX_L] * F;
-        const int64_t blocks = (floats + 255) / 256;
-        k_hashgrid_zero<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st>>>(dL_dtable, floats);
+    if (dL_dtable) {  // zeroed before the backward adds into it
+        rows_fill_on(st, dL_dtable, (int64_t)p.off[HG_MAX_L] * F, 0u);
         if (launched(name)) return 1;
     }
     if (N == 0) return 0;
-    const int tiles = (int)(((int64_t)N + HG_THREADS - 1) / HG_THREADS);
-    const dim3 groups((unsigned)(tiles < HG_MAX_GROUPS ? tiles : HG_MAX_GROUPS)), block(HG_THREADS);
-    hg_with_features(F, [&](auto f) {
-        constexpr int FF = decltype(f)::value;
-        if (dL_dx && dL_dtable) k_hashgrid_rows_backward<FF, true, true><<<groups, block, 0, st>>>(p, tiles, grad_out, dL_dx, dL_dtable);
-        else if (dL_dx) k_hashgrid_rows_backward<FF, true, false><<<groups, block, 0, st>>>(p, tiles, grad_out, dL_dx, nullptr);
-        else k_hashgrid_rows_backward<FF, false, true><<<groups, block, 0, st>>>(p, tiles, grad_out, nullptr, dL_dtable);
+    const RowsGrid g = rows_grid(N, HG_THREADS, HG_MAX_GROUPS);
+    const dim3 groups((unsigned)g.groups), block(HG_THREADS);
+    with_one_of<1, 2, 4, 8>(F, [&](auto f) {  // (... the 12 of the backward)
+        with_wanted(dL_dx != nullptr, dL_dtable != nullptr, [&](auto wx, auto wt) {  // (an output that is not wanted is null)
+            k_hashgrid_rows_backward<decltype(f)::value, decltype(wx)::value, decltype(wt)::value><<<groups, block, 0, st>>>(p, g.tiles, grad_out, dL_dx, dL_dtable);
+        });
     });
     return launched(name);
 }

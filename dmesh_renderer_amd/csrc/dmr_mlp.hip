@@ -9,7 +9,7 @@
 //
 // Rows r >= min(max(n_rows[0], 0), N) are not read: y and dL_dx get exact zeros there, and their lanes stage zeros into the
 // weight-gradient sums.  Offsets into the [N,C] buffers are int64_t.
-#include "dmr_shade_common.hpp"
+#include "dmr_rows_common.hpp"
 #include "../../include/dmesh_renderer_amd_mlp.h"
 
 namespace dmr {
@@ -62,19 +62,9 @@ __device__ __forceinline__ void mlp_load_weights(const MlpParams& p, float* __re
     }
 }
 
-__device__ __forceinline__ int mlp_rows_used(const MlpParams& p) {
-    if (!p.n_rows) return p.N;
-    const int u = p.n_rows[0];
-    return u < 0 ? 0 : (u > p.N ? p.N : u);
-}
 __device__ __forceinline__ float mlp_act(float z, int act) { return act == DMR_MLP_TANH ? tanhf(z) : (z > 0.f ? z : 0.f); }
 // the activation's derivative from its VALUE (relu: a > 0 exactly where z > 0, so 0 at z = 0)
 __device__ __forceinline__ float mlp_dact(float a, int act) { return act == DMR_MLP_TANH ? 1.f - a * a : (a > 0.f ? 1.f : 0.f); }
-// a wave reads back what its lanes wrote to LDS (no workgroup barrier: the staging areas are per wave)
-__device__ __forceinline__ void mlp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // Between the steps of a fully unrolled loop over Hd whose every step reads its own weights: without it the scheduler hoists
 // all Hd steps' LDS reads to the front and the kernel spills (HD = 64: 1024 registers of weights).
@@ -162,7 +152,7 @@ k_mlp_rows(MlpParams p, int tiles, float* __restrict__ y) {
     __shared__ alignas(16) float w[L::TOTAL];
     mlp_load_weights<HD, NH, MLP_FWD_THREADS>(p, w);
     __syncthreads();
-    const int n = mlp_rows_used(p);
+    const int n = rows_used(p);
     const bool narrow = p.Cout <= 4;
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (int64_t)tile * MLP_FWD_THREADS + threadIdx.x;
@@ -284,7 +274,7 @@ k_mlp_rows_backward(MlpParams p, int tiles, const float* __restrict__ gout, floa
     if (want_w)
         for (int e = tid; e < L::TOTAL; e += THREADS) tbl[e] = 0.f;
     __syncthreads();
-    const int n = mlp_rows_used(p);
+    const int n = rows_used(p);
     const bool narrow = p.Cout <= 4;
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (int64_t)tile * THREADS + tid;
@@ -334,12 +324,12 @@ k_mlp_rows_backward(MlpParams p, int tiles, const float* __restrict__ gout, floa
 #pragma unroll
             for (int o = 0; o < MLP_OUT; o++) sg[lane * GP + o] = g[o];
         }
-        mlp_wave_sync();
+        rows_wave_sync();
         if (want_w) {  // dL/dW_out, dL/db_out
             if (narrow) mlp_outer<4, HD, GP, PITCH>(sg, sb, tbl + L::W3, 1, MLP_OUT, lane);
             else mlp_outer<MLP_OUT, HD, GP, PITCH>(sg, sb, tbl + L::W3, 1, MLP_OUT, lane);
             mlp_colsum<MLP_OUT, GP>(sg, tbl + L::B3, lane);
-            mlp_wave_sync();
+            rows_wave_sync();
         }
         float dz1[HD];
         if constexpr (NH == 2) {
@@ -356,14 +346,14 @@ k_mlp_rows_backward(MlpParams p, int tiles, const float* __restrict__ gout, floa
 #pragma unroll
                 for (int i = 0; i < HD; i++) da1[i] += wr[i] * dz2;
             }
-            mlp_wave_sync();
+            rows_wave_sync();
             if (want_w) {  // dL/dW_mid, dL/db_mid
                 mlp_outer<HD, HD, PITCH, PITCH>(sb, sa, tbl + L::W2, HD, 1, lane);
                 mlp_colsum<HD, PITCH>(sb, tbl + L::B2, lane);
             }
 #pragma unroll
             for (int i = 0; i < HD; i++) dz1[i] = da1[i] * mlp_dact(sa[lane * PITCH + i], p.act);
-            mlp_wave_sync();
+            rows_wave_sync();
         } else {
 #pragma unroll
             for (int j = 0; j < HD; j++) {
@@ -389,17 +379,17 @@ k_mlp_rows_backward(MlpParams p, int tiles, const float* __restrict__ gout, floa
         if (want_w) {  // dL/dW_in, dL/db_in: dz1 in sb, x through sg sixteen columns at a time
 #pragma unroll
             for (int j = 0; j < HD; j++) sb[lane * PITCH + j] = dz1[j];
-            mlp_wave_sync();
+            rows_wave_sync();
             mlp_colsum<HD, PITCH>(sb, tbl + L::B1, lane);
             for (int c0 = 0; c0 < p.Cin; c0 += MLP_OUT) {
 #pragma unroll
                 for (int i = 0; i < MLP_OUT; i++) sg[lane * GP + i] = (active && c0 + i < p.Cin) ? xr[c0 + i] : 0.f;
-                mlp_wave_sync();
+                rows_wave_sync();
                 mlp_outer<HD, MLP_OUT, PITCH, GP>(sb, sg, tbl + L::W1 + c0 * HD, 1, HD, lane);
-                mlp_wave_sync();
+                rows_wave_sync();
             }
         }
-        mlp_wave_sync();
+        rows_wave_sync();
     }
     if (want_w) {
         __syncthreads();
@@ -437,17 +427,12 @@ k_mlp_reduce(const float* __restrict__ scratch, int groups, int Cin, int Cout, f
 // f(Hd, hidden layers, float4 row loads) as integral constants: the 12 instantiations of each kernel
 template <class Fn>
 void mlp_with_shape(int Hd, int n_hidden, bool vec, Fn&& f) {
-    const auto layers = [&](auto hd) {
-        const auto loads = [&](auto nh) {
+    with_one_of<16, 32, 64>(Hd, [&](auto hd) {
+        with_one_of<1, 2>(n_hidden, [&](auto nh) {
             if (vec) f(hd, nh, std::true_type());
             else f(hd, nh, std::false_type());
-        };
-        if (n_hidden == 1) loads(std::integral_constant<int, 1>());
-        else loads(std::integral_constant<int, 2>());
-    };
-    if (Hd == 16) layers(std::integral_constant<int, 16>());
-    else if (Hd == 32) layers(std::integral_constant<int, 32>());
-    else layers(std::integral_constant<int, 64>());
+        });
+    });
 }
 
 // what both calls check first, in the header's order -> MlpParams
@@ -485,10 +470,10 @@ int dmr_mlp_rows(int N, int Cin, int Hd, int Cout, int n_hidden, int act, int oa
     if (!y) return api_fail("dmr_mlp_rows: null output");
     p.ovec = shade_vec(Cout, y);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int tiles = (int)(((int64_t)N + MLP_FWD_THREADS - 1) / MLP_FWD_THREADS);
-    const dim3 groups((unsigned)(tiles < MLP_FWD_MAX_GROUPS ? tiles : MLP_FWD_MAX_GROUPS)), block(MLP_FWD_THREADS);
+    const RowsGrid g = rows_grid(N, MLP_FWD_THREADS, MLP_FWD_MAX_GROUPS);
+    const dim3 groups((unsigned)g.groups), block(MLP_FWD_THREADS);
     mlp_with_shape(Hd, n_hidden, shade_vec(Cin, x) != 0, [&](auto hd, auto nh, auto vec) {
-        k_mlp_rows<decltype(hd)::value, decltype(nh)::value, decltype(vec)::value><<<groups, block, 0, st>>>(p, tiles, y);
+        k_mlp_rows<decltype(hd)::value, decltype(nh)::value, decltype(vec)::value><<<groups, block, 0, st>>>(p, g.tiles, y);
     });
     return launched(name);
 }
@@ -502,26 +487,24 @@ int dmr_mlp_rows_backward(int N, int Cin, int Hd, int Cout, int n_hidden, int ac
     const char* name = "dmr_mlp_rows_backward";
     MlpParams p;
     if (mlp_params(name, N, Cin, Hd, Cout, n_hidden, act, oact, x, W_in, b_in, W_mid, b_mid, W_out, b_out, n_rows, p)) return 1;
-    if (N > 0 && !grad_out) return api_fail("dmr_mlp_rows_backward: null grad_out");
-    if ((dL_dW_mid || dL_db_mid) && n_hidden != 2) return api_fail("dmr_mlp_rows_backward: a gradient of the second hidden layer without one");
-    if ((dL_db_in && !b_in) || (dL_db_mid && !b_mid) || (dL_db_out && !b_out)) return api_fail("dmr_mlp_rows_backward: the gradient of a bias without the bias");
+    const char* own = nullptr;
+    if ((dL_dW_mid || dL_db_mid) && n_hidden != 2) own = "a gradient of the second hidden layer without one";
+    else if ((dL_db_in && !b_in) || (dL_db_mid && !b_mid) || (dL_db_out && !b_out)) own = "the gradient of a bias without the bias";
     const bool want_w = dL_dW_in || dL_db_in || dL_dW_mid || dL_db_mid || dL_dW_out || dL_db_out;
-    if (N == 0) dL_dx = nullptr;  // (no row to write)
-    if (!want_w && !dL_dx) return 0;
+    const int go = rows_backward_prologue(name, N, grad_out, own, dL_dx, want_w);
+    if (go != SHADE_LAUNCH) return go;
     if (want_w && (!scratch || scratch_floats < DMR_MLP_SCRATCH_FLOATS(Hd, n_hidden))) return api_fail("dmr_mlp_rows_backward: scratch too small");
     p.ovec = shade_vec(Cout, grad_out);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int threads = mlp_bwd_threads(Hd, n_hidden);
-    const int tiles = (int)(((int64_t)N + threads - 1) / threads);
-    const int groups = tiles < MLP_BWD_MAX_GROUPS ? tiles : MLP_BWD_MAX_GROUPS;
+    const RowsGrid g = rows_grid(N, mlp_bwd_threads(Hd, n_hidden), MLP_BWD_MAX_GROUPS);
     const bool vec = shade_vec(Cin, x) && (!dL_dx || shade_vec(Cin, dL_dx));
     mlp_with_shape(Hd, n_hidden, vec, [&](auto hd, auto nh, auto v) {
         constexpr int HD = decltype(hd)::value, NH = decltype(nh)::value;
-        if (groups > 0)
-            k_mlp_rows_backward<HD, NH, decltype(v)::value><<<dim3((unsigned)groups), dim3(mlp_bwd_threads(HD, NH)), 0, st>>>(p, tiles, grad_out, dL_dx,
+        if (g.groups > 0)
+            k_mlp_rows_backward<HD, NH, decltype(v)::value><<<dim3((unsigned)g.groups), dim3(mlp_bwd_threads(HD, NH)), 0, st>>>(p, g.tiles, grad_out, dL_dx,
                                                                                                                          want_w ? 1 : 0, scratch);
         if (want_w)
-            k_mlp_reduce<HD, NH><<<dim3((unsigned)((MlpLayout<HD, NH>::TOTAL + 63) / 64)), dim3(256), 0, st>>>(scratch, groups, Cin, Cout, dL_dW_in, dL_db_in,
+            k_mlp_reduce<HD, NH><<<dim3((unsigned)((MlpLayout<HD, NH>::TOTAL + 63) / 64)), dim3(256), 0, st>>>(scratch, g.groups, Cin, Cout, dL_dW_in, dL_db_in,
                                                                                                             dL_dW_mid, dL_db_mid, dL_dW_out, dL_db_out);
     });
     return launched(name);

@@ -16,6 +16,7 @@
 #include <cfloat>
 
 #include "dmr_deferred_common.hpp"
+#include "dmr_rows_common.hpp"
 #include "../../include/dmesh_renderer_amd_sh.h"
 
 namespace dmr {
@@ -44,16 +45,6 @@ struct ShParams {
     const int32_t* __restrict__ row_view;   // [N] or null: view 0
     const int32_t* __restrict__ n_rows;     // [1] or null
 };
-
-__device__ __forceinline__ int sh_rows_used(const ShParams& p) {
-    if (!p.n_rows) return p.N;
-    const int u = p.n_rows[0];
-    return u < 0 ? 0 : (u > p.N ? p.N : u);
-}
-__device__ __forceinline__ void sh_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // a row as the kernels see it: whether it is read at all, its view, its direction and 1 / n (0 with a zero direction)
 struct ShRow {
@@ -131,7 +122,7 @@ k_sh_rows(ShParams p, int tiles, float* __restrict__ y) {
     constexpr int C = DEG * DEG, PITCH = sh_pitch(C);
     const int tid = threadIdx.x, lane = tid & 63;
     [[maybe_unused]] float* st = reinterpret_cast<float*>(sh_lds) + (tid >> 6) * (64 * PITCH);  // (VIA_LDS) the wave's staging area
-    const int n = sh_rows_used(p);
+    const int n = rows_used(p);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (int64_t)tile * SH_THREADS + tid, row0 = row - lane;
         if (row0 >= p.N) continue;  // (wave-uniform)
@@ -145,14 +136,14 @@ k_sh_rows(ShParams p, int tiles, float* __restrict__ y) {
         if constexpr (VIA_LDS) {
 #pragma unroll
             for (int c = 0; c < C; c++) st[lane * PITCH + c] = o[c];
-            sh_wave_sync();
+            rows_wave_sync();
             const int64_t left = ((int64_t)p.N - row0) * C;  // the floats of y from the wave's first row on
 #pragma unroll
             for (int i = 0; i < C; i++) {
                 const int e = i * 64 + lane;
                 if (e < left) y[row0 * C + e] = st[(e / C) * PITCH + e % C];
             }
-            sh_wave_sync();
+            rows_wave_sync();
         } else if (row < p.N) {
 #pragma unroll
             for (int c = 0; c < C; c++) y[row * C + c] = o[c];
@@ -193,10 +184,9 @@ k_sh_rows_backward(ShParams p, int tiles, int lds_table, const float* __restrict
         for (int i = tid; i < 3 * p.B; i += SH_THREADS) tab[i] = 0.0;
         __syncthreads();
     }
-    const int n = sh_rows_used(p);
-    const int per = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = (int)blockIdx.x * per, t1 = t0 + per < tiles ? t0 + per : tiles;
-    for (int tile = t0; tile < t1; tile++) {
+    const int n = rows_used(p);
+    const RowsTileRun run = rows_tile_run(tiles);
+    for (int tile = run.t0; tile < run.t1; tile++) {
         const int64_t row = (int64_t)tile * SH_THREADS + tid, row0 = row - lane;
         if (row0 >= p.N) continue;  // (wave-uniform)
         const ShRow r = sh_row(p, row, n);
@@ -211,10 +201,10 @@ k_sh_rows_backward(ShParams p, int tiles, int lds_table, const float* __restrict
                     const int e = i * 64 + lane;
                     st[(e / C) * PITCH + e % C] = e < left ? gout[row0 * C + e] : 0.f;
                 }
-                sh_wave_sync();
+                rows_wave_sync();
 #pragma unroll
                 for (int c = 0; c < C; c++) g[c] = st[lane * PITCH + c];
-                sh_wave_sync();
+                rows_wave_sync();
             } else {
 #pragma unroll
                 for (int c = 0; c < C; c++) g[c] = r.active ? gout[row * C + c] : 0.f;
@@ -251,12 +241,6 @@ k_sh_rows_backward(ShParams p, int tiles, int lds_table, const float* __restrict
     }
 }
 
-// n 4-byte words <- value: dL_dorigin before the backward adds into it (0), view_out before the walk writes the owned rows (-1).
-// A kernel, not a memset node (dmr_visibility.hip).
-__global__ void __launch_bounds__(256) k_sh_fill(uint32_t* __restrict__ a, int64_t n, uint32_t value) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] = value;
-}
-
 // ---------------------------------------------------------------------------
 // the view of every packed row: one walk of the slots on the packed unit's row-shaped lanes (RowPix: a wave on 64 pixels of an
 // image row), k by k -- 64 consecutive slots of the flattened lists per load.  A slot with 0 <= row < N writes its view.
@@ -272,20 +256,6 @@ k_sh_row_views(int B, int K, int H, int W, int N, int sx, int sy, const int32_t*
 }
 
 #pragma clang fp contract(off)
-
-void sh_fill_on(hipStream_t st, void* a, int64_t n, uint32_t value) {
-    const int64_t blocks = (n + 255) / 256;
-    k_sh_fill<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st>>>(static_cast<uint32_t*>(a), n, value);
-}
-
-// f(degree) as an integral constant: the 4 instantiations of the forward, the 12 of the backward
-template <class Fn>
-void sh_with_degree(int degree, Fn&& f) {
-    if (degree == 1) f(std::integral_constant<int, 1>());
-    else if (degree == 2) f(std::integral_constant<int, 2>());
-    else if (degree == 3) f(std::integral_constant<int, 3>());
-    else f(std::integral_constant<int, 4>());
-}
 
 // what both encoding calls check first, in the header's order -> ShParams
 int sh_params(const char* name, int N, int degree, int B, const float* x, const float* origin, const int32_t* row_view, const int32_t* n_rows,
@@ -319,7 +289,7 @@ int dmr_packed_row_views(int B, int K, int H, int W, int N, const int32_t* row, 
     if (N > 0 && !view_out) return api_fail((n + "null output").c_str());
     if (N == 0 || !slots) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    sh_fill_on(st, view_out, N, 0xffffffffu);
+    rows_fill_on(st, view_out, N, 0xffffffffu);
     if (launched(name)) return 1;
     k_sh_row_views<<<dim3((unsigned)(B * sx * sy)), dim3(256), 0, st>>>(B, K, H, W, N, (int)sx, (int)sy, row, view_out);
     return launched(name);
@@ -334,15 +304,15 @@ int dmr_sh_rows(int N, int degree, int B, const float* x, const float* origin, c
     if (N == 0) return 0;
     if (!y) return api_fail("dmr_sh_rows: null output");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int tiles = (int)(((int64_t)N + SH_THREADS - 1) / SH_THREADS);
-    const dim3 groups((unsigned)(tiles < SH_MAX_GROUPS ? tiles : SH_MAX_GROUPS)), block(SH_THREADS);
-    sh_with_degree(degree, [&](auto deg) {
+    const RowsGrid g = rows_grid(N, SH_THREADS, SH_MAX_GROUPS);
+    const dim3 groups((unsigned)g.groups), block(SH_THREADS);
+    with_one_of<1, 2, 3, 4>(degree, [&](auto deg) {  // (the 4 instantiations of the forward)
         constexpr int D = decltype(deg)::value;
         constexpr bool L = sh_via_lds(D);
 #ifdef DMR_ABLATION
-        if (ablate_bits() & SH_OTHER_SHAPE) { k_sh_rows<D, !L><<<groups, block, sh_stage_bytes(D, !L), st>>>(p, tiles, y); return; }
+        if (ablate_bits() & SH_OTHER_SHAPE) { k_sh_rows<D, !L><<<groups, block, sh_stage_bytes(D, !L), st>>>(p, g.tiles, y); return; }
 #endif
-        k_sh_rows<D, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, tiles, y);
+        k_sh_rows<D, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, g.tiles, y);
     });
     return launched(name);
 }
@@ -353,33 +323,28 @@ int dmr_sh_rows_backward(int N, int degree, int B, const float* x, const float* 
     const char* name = "dmr_sh_rows_backward";
     ShParams p;
     if (sh_params(name, N, degree, B, x, origin, row_view, n_rows, p)) return 1;
-    if (N > 0 && !grad_out) return api_fail("dmr_sh_rows_backward: null grad_out");
-    if (dL_dorigin && !origin) return api_fail("dmr_sh_rows_backward: dL_dorigin without origin");
-    if (N == 0) dL_dx = nullptr;  // (no row to write)
-    if (!dL_dx && !dL_dorigin) return 0;
+    const int go = rows_backward_prologue(name, N, grad_out, dL_dorigin && !origin ? "dL_dorigin without origin" : nullptr, dL_dx, dL_dorigin != nullptr);
+    if (go != SHADE_LAUNCH) return go;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dL_dorigin) {
-        sh_fill_on(st, dL_dorigin, (int64_t)3 * B, 0u);
+        rows_fill_on(st, dL_dorigin, (int64_t)3 * B, 0u);
         if (launched(name)) return 1;
     }
     if (N == 0) return 0;
-    const int tiles = (int)(((int64_t)N + SH_THREADS - 1) / SH_THREADS);
-    const dim3 groups((unsigned)(tiles < SH_MAX_GROUPS ? tiles : SH_MAX_GROUPS)), block(SH_THREADS);
+    const RowsGrid g = rows_grid(N, SH_THREADS, SH_MAX_GROUPS);
+    const dim3 groups((unsigned)g.groups), block(SH_THREADS);
     const size_t tab = sh_table_bytes(p.B);  // the workgroup's table of dL/dorigin
-    sh_with_degree(degree, [&](auto deg) {
+    with_one_of<1, 2, 3, 4>(degree, [&](auto deg) {  // (... the 12 of the backward)
         constexpr int D = decltype(deg)::value;
         constexpr bool L = sh_loads_via_lds(D);
+        with_wanted(dL_dx != nullptr, dL_dorigin != nullptr, [&](auto wx, auto wo) {  // (an output that is not wanted is null, and its kernel has no table)
+            constexpr bool WX = decltype(wx)::value, WO = decltype(wo)::value;
+            const size_t table = WO ? tab : 0;
 #ifdef DMR_ABLATION
-        if (ablate_bits() & SH_OTHER_SHAPE) {
-            if (dL_dx && dL_dorigin) k_sh_rows_backward<D, true, true, !L><<<groups, block, tab + sh_stage_bytes(D, !L), st>>>(p, tiles, (int)tab, grad_out, dL_dx, dL_dorigin);
-            else if (dL_dx) k_sh_rows_backward<D, true, false, !L><<<groups, block, sh_stage_bytes(D, !L), st>>>(p, tiles, 0, grad_out, dL_dx, nullptr);
-            else k_sh_rows_backward<D, false, true, !L><<<groups, block, tab + sh_stage_bytes(D, !L), st>>>(p, tiles, (int)tab, grad_out, nullptr, dL_dorigin);
-            return;
-        }
+            if (ablate_bits() & SH_OTHER_SHAPE) { k_sh_rows_backward<D, WX, WO, !L><<<groups, block, table + sh_stage_bytes(D, !L), st>>>(p, g.tiles, (int)table, grad_out, dL_dx, dL_dorigin); return; }
 #endif
-        if (dL_dx && dL_dorigin) k_sh_rows_backward<D, true, true, L><<<groups, block, tab + sh_stage_bytes(D, L), st>>>(p, tiles, (int)tab, grad_out, dL_dx, dL_dorigin);
-        else if (dL_dx) k_sh_rows_backward<D, true, false, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, tiles, 0, grad_out, dL_dx, nullptr);
-        else k_sh_rows_backward<D, false, true, L><<<groups, block, tab + sh_stage_bytes(D, L), st>>>(p, tiles, (int)tab, grad_out, nullptr, dL_dorigin);
+            k_sh_rows_backward<D, WX, WO, L><<<groups, block, table + sh_stage_bytes(D, L), st>>>(p, g.tiles, (int)table, grad_out, dL_dx, dL_dorigin);
+        });
     });
     return launched(name);
 }

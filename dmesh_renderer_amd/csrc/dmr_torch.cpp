@@ -1189,41 +1189,66 @@ py::tuple composite_values_packed_backward(In face, In row, In n_used, In faces_
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
-// -- mlp_rows: a small MLP over [N,Cin] rows (dmesh_renderer_amd_mlp.h).  weights = (W_in [Hd,Cin], [W_mid [Hd,Hd],] W_out [Cout,Hd]),
-// biases = one per weight, each a tensor or None.  The checks come in fragments.mlp_rows_fused's order: shapes, sizes, one
-// device, dtypes.
-using OptTensors = std::vector<std::optional<at::Tensor>>;
-struct MlpArgs {
-    at::Tensor x, n_rows;
-    std::vector<at::Tensor> w, b;  // b[l] undefined: no bias
-    int64_t N = 0, Cin = 0, Hd = 0, Cout = 0;
-    int nh = 0, act = 0, oact = 0;
+// -- The row units (mlp_rows, hashgrid_rows, sh_rows) start from x [N,C] on a HIP device and an optional count n_rows [1]: RowArgs.
+// A unit's argument block extends it, and its builder calls the named checks below in the unit's order, which is fragments.py's:
+// shapes, sizes, one device, dtypes.
+struct RowArgs {
+    at::Tensor x, n_rows;  // n_rows undefined: none
+    int64_t N = 0;
     c10::Device dev{c10::kCPU};
+    const char* call = "";  // what the unit's own messages start with: "mlp_rows", ...
     void* stream() const { return stream_on(dev); }
+    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
+};
+// fn: the unit's forward in g_abi, dmr_<call>; then the device, x [N, cols] (cols 0: any width; cols_name: what the message calls it) and N
+template <class Fn>
+void rows_begin(RowArgs& a, const char* call, Fn fn, In x, int64_t cols, const char* cols_name) {
+    built(fn, (std::string("dmr_") + call).c_str());
+    a.call = call; a.dev = hip_device_of(x);
+    if (x.dim() != 2 || (cols && x.size(1) != cols)) err(std::string("x must have dimensions (rows, ") + cols_name + ")");
+    a.N = x.size(0);
+}
+void check_row_count(const RowArgs& a) { if (a.N >= ((int64_t)1 << 31)) err(std::string(a.call) + ": rows must be below 2^31"); }
+void check_n_rows(const std::optional<at::Tensor>& n_rows) { if (n_rows && n_rows->numel() != 1) err("n_rows must have one element"); }
+void on_device_of_x(const RowArgs& a, In t, const std::string& what) { if (t.device() != a.dev) err(what + " must be on the device of x"); }
+void on_device_of_x(const RowArgs& a, const std::optional<at::Tensor>& t, const std::string& what) { if (t) on_device_of_x(a, *t, what); }
+// where the device checks end and the dtypes begin (n_rows is the last tensor of the one, x the first of the other), and where those end
+void rows_devices_end(RowArgs& a, In x, const std::optional<at::Tensor>& n_rows) { on_device_of_x(a, n_rows, "n_rows"); a.x = f32(x, "x"); }
+void rows_finish(RowArgs& a, const std::optional<at::Tensor>& n_rows) { if (n_rows) a.n_rows = i32(*n_rows, "n_rows"); }
+// a backward's upstream [N, cols]; cols_name: "Cout", "L * F", "degree^2"
+void check_grad_out(const RowArgs& a, In grad_out, int64_t cols, const char* cols_name) {
+    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != cols || grad_out.device() != a.dev)
+        err(std::string("grad_out must have dimensions (rows, ") + cols_name + ") on the device of x");
+}
+
+// -- mlp_rows: a small MLP over [N,Cin] rows (dmesh_renderer_amd_mlp.h).  weights = (W_in [Hd,Cin], [W_mid [Hd,Hd],] W_out [Cout,Hd]),
+// biases = one per weight, each a tensor or None.
+using OptTensors = std::vector<std::optional<at::Tensor>>;
+struct MlpArgs : RowArgs {
+    std::vector<at::Tensor> w, b;  // b[l] undefined: no bias
+    int64_t Cin = 0, Hd = 0, Cout = 0;
+    int nh = 0, act = 0, oact = 0;
     const float* wp(size_t l) const { return mptr<const float>(w[l]); }
     const float* bp(size_t l) const { return b[l].defined() ? mptr<const float>(b[l]) : nullptr; }
     const float* mid_w() const { return nh == 2 ? wp(1) : nullptr; }
     const float* mid_b() const { return nh == 2 ? bp(1) : nullptr; }
-    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
 };
 
 MlpArgs mlp_args(In x, const std::vector<at::Tensor>& weights, const OptTensors& biases, int64_t act, int64_t oact,
                  const std::optional<at::Tensor>& n_rows) {
-    built(g_abi.mlp_rows, "dmr_mlp_rows");
     MlpArgs a;
-    a.dev = hip_device_of(x);
-    if (x.dim() != 2) err("x must have dimensions (rows, Cin)");
+    rows_begin(a, "mlp_rows", g_abi.mlp_rows, x, 0, "Cin");
     if (weights.size() != 2 && weights.size() != 3) err("mlp_rows: 2 or 3 weights (1 or 2 hidden layers), got " + std::to_string(weights.size()));
     if (biases.size() != weights.size()) err("mlp_rows: one bias (or None) per weight");
     a.nh = (int)weights.size() - 1;
-    a.N = x.size(0); a.Cin = x.size(1);
+    a.Cin = x.size(1);
     for (const at::Tensor& w : weights)
         if (w.dim() != 2) err("mlp_rows: every weight must have dimensions (out, in)");
     a.Hd = weights[0].size(0); a.Cout = weights.back().size(0);
     if (a.Hd != 16 && a.Hd != 32 && a.Hd != 64) err("mlp_rows: the hidden width must be 16, 32 or 64, got " + std::to_string(a.Hd));
     if (a.Cin < 1 || a.Cin > 64) err("mlp_rows: Cin must be in 1..64, got " + std::to_string(a.Cin));
     if (a.Cout < 1 || a.Cout > 16) err("mlp_rows: Cout must be in 1..16, got " + std::to_string(a.Cout));
-    if (a.N >= ((int64_t)1 << 31)) err("mlp_rows: rows must be below 2^31");
+    check_row_count(a);
     int64_t in = a.Cin;
     for (size_t l = 0; l < weights.size(); l++) {
         const int64_t out = l + 1 == weights.size() ? a.Cout : a.Hd;
@@ -1232,16 +1257,15 @@ MlpArgs mlp_args(In x, const std::vector<at::Tensor>& weights, const OptTensors&
         in = out;
     }
     if (act < 0 || act > 1 || oact < 0 || oact > 1) err("mlp_rows: bad activation");
-    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
-    for (size_t l = 0; l < weights.size(); l++)
-        if (weights[l].device() != a.dev || (biases[l] && biases[l]->device() != a.dev)) err("mlp_rows: the weights and biases must be on the device of x");
-    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
-    a.x = f32(x, "x");
+    check_n_rows(n_rows);
+    const char* both = "mlp_rows: the weights and biases";
+    for (size_t l = 0; l < weights.size(); l++) { on_device_of_x(a, weights[l], both); on_device_of_x(a, biases[l], both); }
+    rows_devices_end(a, x, n_rows);
     for (size_t l = 0; l < weights.size(); l++) {
         a.w.push_back(f32(weights[l], "weight"));
         a.b.push_back(biases[l] ? f32(*biases[l], "bias") : at::Tensor());
     }
-    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    rows_finish(a, n_rows);
     a.act = (int)act; a.oact = (int)oact;
     return a;
 }
@@ -1265,8 +1289,7 @@ py::tuple mlp_rows_backward(In x, const std::vector<at::Tensor>& weights, const 
                             const std::vector<bool>& need_b) {
     const MlpArgs a = mlp_args(x, weights, biases, act, oact, n_rows);
     c10::DeviceGuard guard(a.dev);
-    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.Cout || grad_out.device() != a.dev)
-        err("grad_out must have dimensions (rows, Cout) on the device of x");
+    check_grad_out(a, grad_out, a.Cout, "Cout");
     if (need_w.size() != a.w.size() || need_b.size() != a.w.size()) err("mlp_rows_backward: one need flag per weight and per bias");
     const at::Tensor go = f32(grad_out, "grad_out");
     at::Tensor dx = grad_if(need_x, {a.N, a.Cin}, a.dev);
@@ -1295,25 +1318,19 @@ py::tuple mlp_rows_backward(In x, const std::vector<at::Tensor>& weights, const 
 }
 
 // -- hashgrid_rows: a multiresolution hash-grid encoding of [N,3] rows (dmesh_renderer_amd_hashgrid.h).  resolutions: the L
-// levels' R_l (host integers); table [rows,F] with rows = what dmr_hashgrid_layout gives.  The checks come in
-// fragments.hashgrid_rows_fused's order: shapes, sizes, one device, dtypes.
-struct HashGridArgs {
-    at::Tensor x, table, n_rows;
+// levels' R_l (host integers); table [rows,F] with rows = what dmr_hashgrid_layout gives.
+struct HashGridArgs : RowArgs {
+    at::Tensor table;
     std::vector<int32_t> res;
-    int64_t N = 0, L = 0, F = 0, rows = 0;
+    int64_t L = 0, F = 0, rows = 0;
     int log2_T = 0;
-    c10::Device dev{c10::kCPU};
-    void* stream() const { return stream_on(dev); }
-    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
 };
 
 HashGridArgs hashgrid_args(In x, In table, const std::vector<int64_t>& resolutions, int64_t log2_T, const std::optional<at::Tensor>& n_rows) {
-    built(g_abi.hashgrid_rows, "dmr_hashgrid_rows");
     HashGridArgs a;
-    a.dev = hip_device_of(x);
-    if (x.dim() != 2 || x.size(1) != 3) err("x must have dimensions (rows, 3)");
+    rows_begin(a, "hashgrid_rows", g_abi.hashgrid_rows, x, 3, "3");
     if (table.dim() != 2) err("table must have dimensions (rows, F)");
-    a.N = x.size(0); a.L = (int64_t)resolutions.size(); a.F = table.size(1);
+    a.L = (int64_t)resolutions.size(); a.F = table.size(1);
     if (a.L < 1 || a.L > DMR_HASHGRID_MAX_LEVELS) err("hashgrid_rows: 1 to 16 levels, got " + std::to_string(a.L));
     if (a.F != 1 && a.F != 2 && a.F != 4 && a.F != 8) err("hashgrid_rows: F must be 1, 2, 4 or 8, got " + std::to_string(a.F));
     if (a.L * a.F > DMR_HASHGRID_MAX_CHANNELS) err("hashgrid_rows: L * F must be at most 64, got " + std::to_string(a.L * a.F));
@@ -1327,13 +1344,12 @@ HashGridArgs hashgrid_args(In x, In table, const std::vector<int64_t>& resolutio
     if (g_abi.hashgrid_layout((int)a.L, a.log2_T, a.res.data(), offsets.data())) raise_lib();
     a.rows = offsets.back();
     if (table.size(0) != a.rows) err("hashgrid_rows: table must have " + std::to_string(a.rows) + " rows, got " + std::to_string(table.size(0)));
-    if (a.N >= ((int64_t)1 << 31)) err("hashgrid_rows: rows must be below 2^31");
-    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
-    if (table.device() != a.dev) err("hashgrid_rows: table must be on the device of x");
-    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
-    a.x = f32(x, "x");
+    check_row_count(a);
+    check_n_rows(n_rows);
+    on_device_of_x(a, table, "hashgrid_rows: table");
+    rows_devices_end(a, x, n_rows);
     a.table = f32(table, "table");
-    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    rows_finish(a, n_rows);
     return a;
 }
 
@@ -1353,8 +1369,7 @@ py::tuple hashgrid_rows_backward(In x, In table, const std::vector<int64_t>& res
                                  In grad_out, bool need_x, bool need_table) {
     const HashGridArgs a = hashgrid_args(x, table, resolutions, log2_T, n_rows);
     c10::DeviceGuard guard(a.dev);
-    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.L * a.F || grad_out.device() != a.dev)
-        err("grad_out must have dimensions (rows, L * F) on the device of x");
+    check_grad_out(a, grad_out, a.L * a.F, "L * F");
     const at::Tensor go = f32(grad_out, "grad_out");
     at::Tensor dx = grad_if(need_x, {a.N, 3}, a.dev), dt = grad_if(need_table, {a.rows, a.F}, a.dev);
     if (g_abi.hashgrid_rows_backward((int)a.N, (int)a.L, (int)a.F, a.log2_T, a.res.data(), mptr<const float>(a.x),
@@ -1364,8 +1379,7 @@ py::tuple hashgrid_rows_backward(In x, In table, const std::vector<int64_t>& res
     return py::make_tuple(or_none(dx), or_none(dt));
 }
 
-// -- packed_row_views / sh_rows: the view direction of packed rows as spherical harmonics (dmesh_renderer_amd_sh.h).  The checks
-// come in fragments.sh_rows_fused's order: shapes, sizes, one device, dtypes.
+// -- packed_row_views / sh_rows: the view direction of packed rows as spherical harmonics (dmesh_renderer_amd_sh.h).
 // -> view i32 [rows]: the view of the slot that owns each packed row, -1 where no slot does
 at::Tensor packed_row_views(In row, int64_t rows) {
     built(g_abi.packed_row_views, "dmr_packed_row_views");
@@ -1382,23 +1396,18 @@ at::Tensor packed_row_views(In row, int64_t rows) {
     return view;
 }
 
-struct ShArgs {
-    at::Tensor x, origin, row_view, n_rows;
-    int64_t N = 0, B = 0, degree = 0;
-    c10::Device dev{c10::kCPU};
-    void* stream() const { return stream_on(dev); }
+struct ShArgs : RowArgs {
+    at::Tensor origin, row_view;
+    int64_t B = 0, degree = 0;
     const float* origin_ptr() const { return origin.defined() ? reinterpret_cast<const float*>(origin.data_ptr()) : nullptr; }
     const int32_t* view_ptr() const { return row_view.defined() ? reinterpret_cast<const int32_t*>(row_view.data_ptr()) : nullptr; }
-    const int32_t* rows_ptr() const { return n_rows.defined() ? mptr<const int32_t>(n_rows) : nullptr; }
 };
 
 ShArgs sh_args(In x, int64_t degree, const std::optional<at::Tensor>& origin, const std::optional<at::Tensor>& row_view,
                const std::optional<at::Tensor>& n_rows) {
-    built(g_abi.sh_rows, "dmr_sh_rows");
     ShArgs a;
-    a.dev = hip_device_of(x);
-    if (x.dim() != 2 || x.size(1) != 3) err("x must have dimensions (rows, 3)");
-    a.N = x.size(0); a.degree = degree;
+    rows_begin(a, "sh_rows", g_abi.sh_rows, x, 3, "3");
+    a.degree = degree;
     if (degree < 1 || degree > DMR_SH_MAX_DEGREE) err("sh_rows: degree must be in 1..4, got " + std::to_string(degree));
     if (origin) {
         if (origin->dim() != 2 || origin->size(1) != 3) err("origin must have dimensions (views, 3)");
@@ -1407,15 +1416,14 @@ ShArgs sh_args(In x, int64_t degree, const std::optional<at::Tensor>& origin, co
     }
     if (row_view && !origin) err("sh_rows: row_view without origin");
     if (row_view && (row_view->dim() != 1 || row_view->size(0) != a.N)) err("row_view must have dimensions (rows)");
-    if (a.N >= ((int64_t)1 << 31)) err("sh_rows: rows must be below 2^31");
-    if (n_rows && n_rows->numel() != 1) err("n_rows must have one element");
-    if (origin && origin->device() != a.dev) err("sh_rows: origin must be on the device of x");
-    if (row_view && row_view->device() != a.dev) err("sh_rows: row_view must be on the device of x");
-    if (n_rows && n_rows->device() != a.dev) err("n_rows must be on the device of x");
-    a.x = f32(x, "x");
+    check_row_count(a);
+    check_n_rows(n_rows);
+    on_device_of_x(a, origin, "sh_rows: origin");
+    on_device_of_x(a, row_view, "sh_rows: row_view");
+    rows_devices_end(a, x, n_rows);
     if (origin) a.origin = f32(*origin, "origin");
     if (row_view) a.row_view = i32(*row_view, "row_view");
-    if (n_rows) a.n_rows = i32(*n_rows, "n_rows");
+    rows_finish(a, n_rows);
     return a;
 }
 
@@ -1436,8 +1444,7 @@ py::tuple sh_rows_backward(In x, int64_t degree, const std::optional<at::Tensor>
                            const std::optional<at::Tensor>& n_rows, In grad_out, bool need_x, bool need_origin) {
     const ShArgs a = sh_args(x, degree, origin, row_view, n_rows);
     c10::DeviceGuard guard(a.dev);
-    if (grad_out.dim() != 2 || grad_out.size(0) != a.N || grad_out.size(1) != a.degree * a.degree || grad_out.device() != a.dev)
-        err("grad_out must have dimensions (rows, degree^2) on the device of x");
+    check_grad_out(a, grad_out, a.degree * a.degree, "degree^2");
     if (need_origin && !origin) err("sh_rows_backward: need_origin without origin");
     const at::Tensor go = f32(grad_out, "grad_out");
     at::Tensor dx = grad_if(need_x, {a.N, 3}, a.dev), dorg = grad_if(need_origin, {a.B, 3}, a.dev);

@@ -782,6 +782,39 @@ OUT_ACTIVATIONS = ("none", "sigmoid")  # ... and `oact`
 MLP_HIDDEN = (16, 32, 64)             # the fused kernels' hidden widths; 1 <= Cin <= 64, 1 <= Cout <= 16
 
 
+def _check_n_rows(name: str, n_rows):
+    """The last of what the torch and the fused path of every row function (mlp_rows, hashgrid_rows, sh_rows) both refuse."""
+    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
+        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+
+
+def _check_row_tensors(name: str, torch_path: str, x, floats, ints):
+    """What the fused row functions refuse after their arguments' shapes, in this order: N (ValueError), then (TypeError) the
+    float32 tensors `floats`, the int32 tensors `ints`, one HIP device for all; both are lists of (name, tensor or None), x first."""
+    floats, ints = ([(n, t) for n, t in tensors if t is not None] for tensors in (floats, ints))
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
+    for tensors, dtype, word in ((floats, th.float32, "float32"), (ints, th.int32, "int32")):
+        for n, t in tensors:
+            if t.dtype != dtype:
+                raise TypeError(f"{name}: {n} must be {word}, got {t.dtype}; {torch_path}")
+    for n, t in floats + ints:
+        if not t.is_cuda or t.device != x.device:
+            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+
+
+def _save_optional(ctx, *tensors):
+    """save_for_backward for tensors of which some are None ..."""
+    ctx.saved_mask = tuple(t is not None for t in tensors)
+    ctx.save_for_backward(*(t for t in tensors if t is not None))
+
+
+def _saved_optional(ctx):
+    """... and the same tuple back, None where it was."""
+    saved = iter(ctx.saved_tensors)
+    return tuple(next(saved) if has else None for has in ctx.saved_mask)
+
+
 def _mlp_arguments(name: str, x, weights, biases, activation, out_activation, n_rows):
     """What mlp_rows and mlp_rows_fused both refuse (ValueError), in this order: the number of weights and biases, the
     activations' names, x [N,Cin], the weights' chain of shapes [out_l, in_l] with one hidden width, the biases' shapes, n_rows.
@@ -806,8 +839,7 @@ def _mlp_arguments(name: str, x, weights, biases, activation, out_activation, n_
             raise ValueError(f"{name}: weights[{l}] must be [out,in] = {want} (x is {tuple(x.shape)}, one hidden width), got {tuple(w.shape)}")
         if b is not None and tuple(b.shape) != want[:1]:
             raise ValueError(f"{name}: biases[{l}] must be [out] = {want[:1]} or None, got {tuple(b.shape)}")
-    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
-        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+    _check_n_rows(name, n_rows)
     return weights, biases
 
 
@@ -846,8 +878,8 @@ class _MlpRowsFn(th.autograd.Function):
     def forward(ctx, x, n_rows, act, oact, L, *params):
         weights, biases = params[:L], params[L:]
         y = _fused_kernels("mlp_rows").mlp_rows(x, list(weights), list(biases), act, oact, n_rows)
-        ctx.has_bias, ctx.has_rows, ctx.meta = tuple(b is not None for b in biases), n_rows is not None, (act, oact, L)
-        ctx.save_for_backward(x, *weights, *(b for b in biases if b is not None), *((n_rows,) if ctx.has_rows else ()))
+        ctx.meta = (act, oact, L)
+        _save_optional(ctx, x, *weights, *biases, n_rows)
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
         return y
 
@@ -856,13 +888,11 @@ class _MlpRowsFn(th.autograd.Function):
         act, oact, L = ctx.meta
         need = ctx.needs_input_grad
         need_x, need_w = need[0], list(need[5:5 + L])
-        need_b = [ctx.has_bias[l] and need[5 + L + l] for l in range(L)]
+        need_b = [ctx.saved_mask[1 + L + l] and need[5 + L + l] for l in range(L)]
         if grad_y is None or not (need_x or any(need_w) or any(need_b)):
             return (None,) * (5 + 2 * L)
-        saved = list(ctx.saved_tensors)
-        x, weights, rest = saved[0], saved[1:1 + L], saved[1 + L:]
-        biases = [rest.pop(0) if has else None for has in ctx.has_bias]
-        n_rows = rest.pop(0) if ctx.has_rows else None
+        x, *params, n_rows = _saved_optional(ctx)
+        weights, biases = params[:L], params[L:]
         dx, gw, gb = _fused_kernels("mlp_rows").mlp_rows_backward(x, weights, biases, act, oact, n_rows, grad_y.contiguous(), need_x, need_w, need_b)
         return (dx, None, None, None, None, *gw, *gb)
 
@@ -886,17 +916,8 @@ def mlp_rows_fused(x: th.Tensor, weights: Sequence[th.Tensor], biases: Sequence[
         raise ValueError(f"{name}: Cin must be in 1..64, got {c_in}; {torch_path}")
     if not 1 <= c_out <= 16:
         raise ValueError(f"{name}: Cout must be in 1..16, got {c_out}; {torch_path}")
-    if x.shape[0] >= 2 ** 31:
-        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
-    floats = [("x", x)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases) if b is not None]
-    for n, t in floats:
-        if t.dtype != th.float32:
-            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
-    if n_rows is not None and n_rows.dtype != th.int32:
-        raise TypeError(f"{name}: n_rows must be int32, got {n_rows.dtype}; {torch_path}")
-    for n, t in floats + ([] if n_rows is None else [("n_rows", n_rows)]):
-        if not t.is_cuda or t.device != x.device:
-            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    floats = [("x", x)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
+    _check_row_tensors(name, torch_path, x, floats, [("n_rows", n_rows)])
     return _MlpRowsFn.apply(x, None if n_rows is None else n_rows.reshape(1), ACTIVATIONS.index(activation), OUT_ACTIVATIONS.index(out_activation),
                             len(weights), *weights, *biases)
 
@@ -1026,8 +1047,7 @@ def _hashgrid_arguments(name: str, x, table, spec, n_rows):
     want = (spec.offsets[-1], spec.features)
     if tuple(table.shape) != want:
         raise ValueError(f"{name}: table must be [offsets[L], F] = {want}, got {tuple(table.shape)}")
-    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
-        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+    _check_n_rows(name, n_rows)
 
 
 def hashgrid_rows(x: th.Tensor, table: th.Tensor, spec: HashGridSpec, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
@@ -1080,8 +1100,8 @@ class _HashGridRowsFn(th.autograd.Function):
     @staticmethod
     def forward(ctx, x, table, n_rows, spec):
         y = _fused_kernels("hashgrid_rows").hashgrid_rows(x, table, list(spec.resolutions), spec.log2_table_size, n_rows)
-        ctx.spec, ctx.has_rows = spec, n_rows is not None
-        ctx.save_for_backward(x, table, *((n_rows,) if ctx.has_rows else ()))
+        ctx.spec = spec
+        _save_optional(ctx, x, table, n_rows)
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
         return y
 
@@ -1090,9 +1110,9 @@ class _HashGridRowsFn(th.autograd.Function):
         need_x, need_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if grad_y is None or not (need_x or need_table):
             return None, None, None, None
-        x, table, *rest = ctx.saved_tensors
+        x, table, n_rows = _saved_optional(ctx)
         dx, dtable = _fused_kernels("hashgrid_rows").hashgrid_rows_backward(x, table, list(ctx.spec.resolutions), ctx.spec.log2_table_size,
-                                                                            rest[0] if ctx.has_rows else None, grad_y.contiguous(), need_x, need_table)
+                                                                            n_rows, grad_y.contiguous(), need_x, need_table)
         return dx, dtable, None, None
 
 
@@ -1109,16 +1129,7 @@ def hashgrid_rows_fused(x: th.Tensor, table: th.Tensor, spec: HashGridSpec, n_ro
     name, torch_path = "hashgrid_rows_fused", "fragments.hashgrid_rows is the torch path for anything else"
     _fused_kernels("hashgrid_rows")
     _hashgrid_arguments(name, x, table, spec, n_rows)
-    if x.shape[0] >= 2 ** 31:
-        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
-    for n, t in (("x", x), ("table", table)):
-        if t.dtype != th.float32:
-            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
-    if n_rows is not None and n_rows.dtype != th.int32:
-        raise TypeError(f"{name}: n_rows must be int32, got {n_rows.dtype}; {torch_path}")
-    for n, t in [("x", x), ("table", table)] + ([] if n_rows is None else [("n_rows", n_rows)]):
-        if not t.is_cuda or t.device != x.device:
-            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    _check_row_tensors(name, torch_path, x, [("x", x), ("table", table)], [("n_rows", n_rows)])
     return _HashGridRowsFn.apply(x, table, None if n_rows is None else n_rows.reshape(1), spec)
 
 
@@ -1206,8 +1217,7 @@ def _sh_arguments(name: str, x, degree, origin, row_view, n_rows) -> int:
             raise ValueError(f"{name}: row_view must be [N] = {(x.shape[0],)}, got {tuple(row_view.shape)}")
     elif B > 1:
         raise ValueError(f"{name}: origin holds {B} views: row_view must tell the view of every row (packed_row_views_fused)")
-    if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
-        raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
+    _check_n_rows(name, n_rows)
     return B
 
 
@@ -1288,19 +1298,16 @@ class _ShRowsFn(th.autograd.Function):
     def forward(ctx, x, origin, row_view, n_rows, degree):
         y = _fused_kernels("sh_rows").sh_rows(x, degree, origin, row_view, n_rows)
         ctx.degree = degree
-        ctx.has = (origin is not None, row_view is not None, n_rows is not None)
-        ctx.save_for_backward(x, *(t for t in (origin, row_view, n_rows) if t is not None))
+        _save_optional(ctx, x, origin, row_view, n_rows)
         ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
-        need_x, need_origin = ctx.needs_input_grad[0], ctx.has[0] and ctx.needs_input_grad[1]
+        need_x, need_origin = ctx.needs_input_grad[0], ctx.saved_mask[1] and ctx.needs_input_grad[1]
         if grad_y is None or not (need_x or need_origin):
             return None, None, None, None, None
-        x, *rest = ctx.saved_tensors
-        rest = iter(rest)
-        origin, row_view, n_rows = (next(rest) if h else None for h in ctx.has)
+        x, origin, row_view, n_rows = _saved_optional(ctx)
         dx, dorigin = _fused_kernels("sh_rows").sh_rows_backward(x, ctx.degree, origin, row_view, n_rows, grad_y.contiguous(), need_x, need_origin)
         return dx, dorigin, None, None, None
 
@@ -1319,19 +1326,7 @@ def sh_rows_fused(x: th.Tensor, degree: int, *, origin: Optional[th.Tensor] = No
     name, torch_path = "sh_rows_fused", "fragments.sh_rows is the torch path for anything else"
     _fused_kernels("sh_rows")
     _sh_arguments(name, x, degree, origin, row_view, n_rows)
-    if x.shape[0] >= 2 ** 31:
-        raise ValueError(f"{name}: N must be below 2^31, got {x.shape[0]}; {torch_path}")
-    floats = [("x", x)] + ([] if origin is None else [("origin", origin)])
-    ints = ([] if row_view is None else [("row_view", row_view)]) + ([] if n_rows is None else [("n_rows", n_rows)])
-    for n, t in floats:
-        if t.dtype != th.float32:
-            raise TypeError(f"{name}: {n} must be float32, got {t.dtype}; {torch_path}")
-    for n, t in ints:
-        if t.dtype != th.int32:
-            raise TypeError(f"{name}: {n} must be int32, got {t.dtype}; {torch_path}")
-    for n, t in floats + ints:
-        if not t.is_cuda or t.device != x.device:
-            raise TypeError(f"{name}: {n} is on {t.device}: every tensor must be on one HIP device (there is no CPU path); {torch_path}")
+    _check_row_tensors(name, torch_path, x, [("x", x), ("origin", origin)], [("row_view", row_view), ("n_rows", n_rows)])
     return _ShRowsFn.apply(x, origin, row_view, None if n_rows is None else n_rows.reshape(1), degree)
 
 

@@ -7,25 +7,27 @@ from collections import namedtuple
 
 import numpy as np
 
+from mlp_cases import COMMON_DISPATCH_LINES, COMMON_HEADER, COMMON_SOURCE, FILL_KERNEL, FILL_LAUNCH_LINE  # noqa: F401
+
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_hashgrid.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_hashgrid_cpu.py
-# fails when one of them is no longer in the file exactly once: then this follows the new dispatch.
+# fails when one of them is no longer in the file exactly once: then this follows the new dispatch.  COMMON_DISPATCH_LINES: what
+# the row units take from COMMON_HEADER (the ladder behind with_one_of and with_wanted, the grid, the backward call's opening).
 # ---------------------------------------------------------------------------
 FEATURES = (1, 2, 4, 8)
 THREADS, MAX_GROUPS = 256, 1024
 DISPATCH_LINES = [
     "constexpr int HG_MAX_L = DMR_HASHGRID_MAX_LEVELS, HG_THREADS = 256, HG_MAX_GROUPS = DMR_HASHGRID_MAX_GROUPS;",
-    "if (F == 1) f(std::integral_constant<int, 1>());",
-    "else if (F == 2) f(std::integral_constant<int, 2>());",
-    "else if (F == 4) f(std::integral_constant<int, 4>());",
-    "else f(std::integral_constant<int, 8>());",
-    "k_hashgrid_rows<FF, true><<<groups, block, 0, st>>>(p, tiles, y);",
-    "if (dL_dx && dL_dtable) k_hashgrid_rows_backward<FF, true, true><<<groups, block, 0, st>>>(p, tiles, grad_out, dL_dx, dL_dtable);",
-    "else if (dL_dx) k_hashgrid_rows_backward<FF, true, false><<<groups, block, 0, st>>>(p, tiles, grad_out, dL_dx, nullptr);",
-    "else k_hashgrid_rows_backward<FF, false, true><<<groups, block, 0, st>>>(p, tiles, grad_out, nullptr, dL_dtable);",
-    "const dim3 groups((unsigned)(tiles < HG_MAX_GROUPS ? tiles : HG_MAX_GROUPS)), block(HG_THREADS);",
-    "if (N == 0) dL_dx = nullptr;  // (no row to write)",
+    "with_one_of<1, 2, 4, 8>(F, [&](auto f) {  // (the 4 instantiations of the forward)",
+    "with_one_of<1, 2, 4, 8>(F, [&](auto f) {  // (... the 12 of the backward)",
+    "k_hashgrid_rows<FF, true><<<groups, block, 0, st>>>(p, g.tiles, y);",
+    "with_wanted(dL_dx != nullptr, dL_dtable != nullptr, [&](auto wx, auto wt) {  // (an output that is not wanted is null)",
+    "k_hashgrid_rows_backward<decltype(f)::value, decltype(wx)::value, decltype(wt)::value><<<groups, block, 0, st>>>(p, g.tiles, grad_out, dL_dx, dL_dtable);",
+    "const dim3 groups((unsigned)g.groups), block(HG_THREADS);",
+    "const int go = rows_backward_prologue(name, N, grad_out, nullptr, dL_dx, dL_dtable != nullptr);",
+    "rows_fill_on(st, dL_dtable, (int64_t)p.off[HG_MAX_L] * F, 0u);",
 ]
+TWICE = ("const RowsGrid g = rows_grid(N, HG_THREADS, HG_MAX_GROUPS);", "dim3 groups((unsigned)g.groups), block(HG_THREADS);")   # (both calls)
 HEADER_LINES = ["#define DMR_HASHGRID_MAX_GROUPS 1024", "#define DMR_HASHGRID_MAX_LEVELS 16", "#define DMR_HASHGRID_MAX_CHANNELS 64"]
 
 # One forward + backward as the dispatch sees it.  (R0, s): the grid's base resolution and per-level scale; order: how the rows
@@ -48,14 +50,14 @@ def instantiations(cases):
             out.add(("k_hashgrid_rows", (c.F, True)))
             out.add(("k_hashgrid_rows_backward", (c.F, "x" in c.want, "t" in c.want)))
         if "t" in c.want:
-            out.add(("k_hashgrid_zero", ()))
+            out.add((FILL_KERNEL, ()))
     return out
 
 
 def every_instantiation():
     full = {("k_hashgrid_rows", (f, True)) for f in FEATURES}
     full |= {("k_hashgrid_rows_backward", (f, wx, wt)) for f in FEATURES for wx, wt in ((True, True), (True, False), (False, True))}
-    return full | {("k_hashgrid_zero", ())}
+    return full | {(FILL_KERNEL, ())}
 
 
 # The three grids of the issue: (R0, s, L), with the share of uniform rows the boundary band leaves out below 3 %.

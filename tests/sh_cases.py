@@ -7,31 +7,36 @@ from collections import namedtuple
 
 import numpy as np
 
+from mlp_cases import COMMON_DISPATCH_LINES, COMMON_HEADER, COMMON_SOURCE, FILL_KERNEL, FILL_LAUNCH_LINE  # noqa: F401
+
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_sh.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_sh_cpu.py fails when one of
-# them is no longer in the file exactly once: then this follows the new dispatch.
+# them is no longer in the file exactly once: then this follows the new dispatch.  COMMON_DISPATCH_LINES: what the row units take
+# from COMMON_HEADER (the ladder behind with_one_of and with_wanted, the grid, the backward call's opening).
 # ---------------------------------------------------------------------------
 DEGREES = (1, 2, 3, 4)
 THREADS, MAX_GROUPS, MAX_VIEWS = 256, 1024, 1024
 DISPATCH_LINES = [
     "constexpr int SH_THREADS = 256, SH_MAX_GROUPS = DMR_SH_MAX_GROUPS, SH_MAX_VIEWS = DMR_SH_MAX_VIEWS;",
     "constexpr bool sh_via_lds(int degree) { return degree >= 3; }",
-    "if (degree == 1) f(std::integral_constant<int, 1>());",
-    "else if (degree == 2) f(std::integral_constant<int, 2>());",
-    "else if (degree == 3) f(std::integral_constant<int, 3>());",
-    "else f(std::integral_constant<int, 4>());",
+    "with_one_of<1, 2, 3, 4>(degree, [&](auto deg) {  // (the 4 instantiations of the forward)",
+    "with_one_of<1, 2, 3, 4>(degree, [&](auto deg) {  // (... the 12 of the backward)",
     "constexpr bool sh_loads_via_lds(int) { return false; }",
     "constexpr bool L = sh_via_lds(D);",
     "constexpr bool L = sh_loads_via_lds(D);",
-    "k_sh_rows<D, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, tiles, y);",
-    "if (dL_dx && dL_dorigin) k_sh_rows_backward<D, true, true, L><<<groups, block, tab + sh_stage_bytes(D, L), st>>>(p, tiles, (int)tab, grad_out, dL_dx, dL_dorigin);",
-    "else if (dL_dx) k_sh_rows_backward<D, true, false, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, tiles, 0, grad_out, dL_dx, nullptr);",
-    "else k_sh_rows_backward<D, false, true, L><<<groups, block, tab + sh_stage_bytes(D, L), st>>>(p, tiles, (int)tab, grad_out, nullptr, dL_dorigin);",
-    "const dim3 groups((unsigned)(tiles < SH_MAX_GROUPS ? tiles : SH_MAX_GROUPS)), block(SH_THREADS);",
-    "if (N == 0) dL_dx = nullptr;  // (no row to write)",
+    "k_sh_rows<D, L><<<groups, block, sh_stage_bytes(D, L), st>>>(p, g.tiles, y);",
+    "with_wanted(dL_dx != nullptr, dL_dorigin != nullptr, [&](auto wx, auto wo) {  // (an output that is not wanted is null, and its kernel has no table)",
+    "constexpr bool WX = decltype(wx)::value, WO = decltype(wo)::value;",
+    "const size_t table = WO ? tab : 0;",
+    "k_sh_rows_backward<D, WX, WO, L><<<groups, block, table + sh_stage_bytes(D, L), st>>>(p, g.tiles, (int)table, grad_out, dL_dx, dL_dorigin);",
+    "const RowsGrid g = rows_grid(N, SH_THREADS, SH_MAX_GROUPS);",
+    "const dim3 groups((unsigned)g.groups), block(SH_THREADS);",
+    'const int go = rows_backward_prologue(name, N, grad_out, dL_dorigin && !origin ? "dL_dorigin without origin" : nullptr, dL_dx, dL_dorigin != nullptr);',
+    "rows_fill_on(st, dL_dorigin, (int64_t)3 * B, 0u);",
+    "rows_fill_on(st, view_out, N, 0xffffffffu);",
     "if (N == 0 || !slots) return 0;",
 ]
-TWICE = ("const dim3 groups((unsigned)(tiles < SH_MAX_GROUPS ? tiles : SH_MAX_GROUPS)), block(SH_THREADS);",)   # (both calls)
+TWICE = ("const RowsGrid g = rows_grid(N, SH_THREADS, SH_MAX_GROUPS);", "const dim3 groups((unsigned)g.groups), block(SH_THREADS);")   # (both calls)
 HEADER_LINES = ["#define DMR_SH_MAX_GROUPS 1024", "#define DMR_SH_MAX_VIEWS 1024", "#define DMR_SH_MAX_DEGREE 4"]
 
 
@@ -71,14 +76,14 @@ def instantiations(cases):
             out.add(("k_sh_rows", (c.degree, via_lds(c.degree))))
             out.add(("k_sh_rows_backward", (c.degree, "x" in c.want, "o" in c.want, loads_via_lds(c.degree))))
         if "o" in c.want:
-            out.add(("k_sh_fill", ()))
+            out.add((FILL_KERNEL, ()))
     return out
 
 
 def every_instantiation():
     full = {("k_sh_rows", (d, via_lds(d))) for d in DEGREES}
     full |= {("k_sh_rows_backward", (d, wx, wo, loads_via_lds(d))) for d in DEGREES for wx, wo in ((True, True), (True, False), (False, True))}
-    return full | {("k_sh_fill", ()), ("k_sh_row_views", ())}
+    return full | {(FILL_KERNEL, ()), ("k_sh_row_views", ())}
 
 
 def _table():

@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_hashgrid.h")
 UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_hashgrid.hip")
 UNIT_TEXT = open(UNIT).read()
+COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (HC.COMMON_HEADER, HC.COMMON_SOURCE))
 HEADER_TEXT = open(HEADER).read()
 FUNCTIONS = ["dmr_hashgrid_layout", "dmr_hashgrid_rows", "dmr_hashgrid_rows_backward"]
 TORCH_PATH = r"fragments\.hashgrid_rows is the torch path"
@@ -293,7 +294,7 @@ def test_library_exports_the_declared_symbols():
 
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
-    assert "dmr_hashgrid.hip" in build.SOURCES
+    assert "dmr_hashgrid.hip" in build.SOURCES and HC.COMMON_SOURCE in build.SOURCES and HC.COMMON_HEADER in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_hashgrid.h" for d in deps)
@@ -448,22 +449,28 @@ def test_c_abi_refusals():
 # ---------------------------------------------------------------------------
 def test_dispatch_restated_as_the_unit_has_it():
     for line in HC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == 1, line
-    assert UNIT_TEXT.count("dim3 groups((unsigned)(tiles < HG_MAX_GROUPS ? tiles : HG_MAX_GROUPS)), block(HG_THREADS);") == 2   # (both calls)
+        assert UNIT_TEXT.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
+    for line in HC.TWICE:
+        assert UNIT_TEXT.count(line) == 2, line
+    for line in HC.COMMON_DISPATCH_LINES:
+        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
+    assert FILL_TEXT.count(HC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % HC.COMMON_HEADER in UNIT_TEXT
     for line in HC.HEADER_LINES:
         assert HEADER_TEXT.count(line) == 1, line
     assert tuple(FG.HASHGRID_FEATURES) == HC.FEATURES
     # the kernels the unit launches are the ones every_instantiation lists; the product launches no <FF, false> forward
     product = re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S)
-    assert set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", product)) == {k for k, _ in HC.every_instantiation()}
+    launches = lambda text: set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", text))
+    assert launches(FILL_TEXT) == {HC.FILL_KERNEL} and "rows_fill_on(st, " in product   # (the shared code's launch for this unit)
+    assert launches(product) | launches(FILL_TEXT) == {k for k, _ in HC.every_instantiation()}
     assert "k_hashgrid_rows<FF, false>" not in product and "g_hg_stats" not in product and "p.dbg" not in product
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S))
+    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT, flags=re.S))
     assert "hipMemset" not in code and "hipMalloc" not in code and "Synchronize" not in code and "hipMemcpy" not in code
     assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert "k_hashgrid_zero<<<" in code and "asm" not in code
+    assert code.count("rows_fill_on(st, ") == 1 and HC.FILL_KERNEL + "<<<" in code and "asm" not in code
 
 
 def test_tables_reach_every_instantiation():

@@ -1,5 +1,5 @@
 """fragments.hashgrid_rows_fused and HashGrid on the GPU (csrc/dmr_hashgrid.hip: k_hashgrid_rows, k_hashgrid_rows_backward,
-k_hashgrid_zero) against fragments.hashgrid_rows evaluated in float64 on the CPU, on the same float32 inputs cast up: the case
+and csrc/dmr_rows_common.hip's k_rows_fill) against fragments.hashgrid_rows evaluated in float64 on the CPU, on the same float32 inputs cast up: the case
 table of tests/hashgrid_cases.py (every instantiation; N around a wave, a workgroup's tile and the capped grid; dense, hashed and
 mixed levels up to R = 4096; rows along a ramp, uniform, and all identical), y off a 16-byte boundary, special coordinates,
 n_rows on the device, single gradients, the chain pack -> hit points -> HashGrid -> RowMLP -> blend on rendered lists, and a

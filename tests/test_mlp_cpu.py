@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_mlp.h")
 UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_mlp.hip")
 UNIT_TEXT = open(UNIT).read()
+COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (MC.COMMON_HEADER, MC.COMMON_SOURCE))
 HEADER_TEXT = open(HEADER).read()
 FUNCTIONS = ["dmr_mlp_rows", "dmr_mlp_rows_backward"]
 TORCH_PATH = r"fragments\.mlp_rows is the torch path"
@@ -142,7 +143,7 @@ def test_library_exports_the_declared_symbols():
 
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
-    assert "dmr_mlp.hip" in build.SOURCES
+    assert "dmr_mlp.hip" in build.SOURCES and MC.COMMON_SOURCE in build.SOURCES and MC.COMMON_HEADER in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_mlp.h" for d in deps)
@@ -324,7 +325,10 @@ def _all_cases():
 
 def test_dispatch_restated_as_the_unit_has_it():
     for line in MC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == 1, line
+        assert UNIT_TEXT.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
+    for line in MC.COMMON_DISPATCH_LINES:
+        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
+    assert FILL_TEXT.count(MC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % MC.COMMON_HEADER in UNIT_TEXT
     assert UNIT_TEXT.count("const bool narrow = p.Cout <= 4;") == 2   # (both kernels: the output loops' two widths)
     for line in MC.HEADER_LINES:
         assert HEADER_TEXT.count(line) == 1, line
@@ -336,7 +340,7 @@ def test_dispatch_restated_as_the_unit_has_it():
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", UNIT_TEXT)
+    code = re.sub(r"//[^\n]*", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT)
     assert "hipMemsetAsync" not in code and "hipMalloc" not in code and "Synchronize" not in code
     assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
     assert "k_mlp_reduce<HD, NH><<<" in code and "asm" not in code

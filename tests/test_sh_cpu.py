@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_sh.h")
 UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_sh.hip")
 UNIT_TEXT = open(UNIT).read()
+COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (SC.COMMON_HEADER, SC.COMMON_SOURCE))
 HEADER_TEXT = open(HEADER).read()
 FUNCTIONS = ["dmr_packed_row_views", "dmr_sh_rows", "dmr_sh_rows_backward"]
 TORCH_PATH = r"fragments\.sh_rows is the torch path"
@@ -342,6 +343,7 @@ def test_library_exports_the_declared_symbols():
 def test_the_source_and_header_are_build_dependencies():
     from dmesh_renderer_amd import build
     assert "dmr_sh.hip" in build.SOURCES and "dmr_deferred_common.hpp" in build.HEADERS   # (RowPix, the packed unit's lanes)
+    assert SC.COMMON_SOURCE in build.SOURCES and SC.COMMON_HEADER in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
     for deps in (build.HEADERS, build.GLUE_SOURCES):
         assert any(os.path.basename(d) == "dmesh_renderer_amd_sh.h" for d in deps)
@@ -536,21 +538,26 @@ def test_c_abi_refusals():
 # ---------------------------------------------------------------------------
 def test_dispatch_restated_as_the_unit_has_it():
     for line in SC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == (2 if line in SC.TWICE else 1), line
+        assert UNIT_TEXT.count(line) == (2 if line in SC.TWICE else 1) and COMMON_TEXT.count(line) == 0, line
+    for line in SC.COMMON_DISPATCH_LINES:
+        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
+    assert FILL_TEXT.count(SC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % SC.COMMON_HEADER in UNIT_TEXT
     for line in SC.HEADER_LINES:
         assert HEADER_TEXT.count(line) == 1, line
     assert all(SC.via_lds(d) == (d >= 3) and not SC.loads_via_lds(d) for d in SC.DEGREES) and SC.DEGREES == tuple(range(1, FG.SH_MAX_DEGREE + 1))
     # the kernels the unit launches are the ones every_instantiation lists; the product launches no <D, !L> shape
     product = re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S)
-    assert set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", product)) == {k for k, _ in SC.every_instantiation()}
+    launches = lambda text: set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", text))
+    assert launches(FILL_TEXT) == {SC.FILL_KERNEL} and "rows_fill_on(st, " in product   # (the shared code's launch for this unit)
+    assert launches(product) | launches(FILL_TEXT) == {k for k, _ in SC.every_instantiation()}
     assert "!L>" not in product and "ablate_bits" not in product and "!L>" in UNIT_TEXT
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S))
+    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT, flags=re.S))
     assert "hipMemset" not in code and "hipMalloc" not in code and "Synchronize" not in code and "hipMemcpy" not in code
     assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert code.count("sh_fill_on(st, ") == 2 and "k_sh_fill<<<" in code and "asm" not in code
+    assert code.count("rows_fill_on(st, ") == 2 and SC.FILL_KERNEL + "<<<" in code and "asm" not in code
     assert "zero_on(" not in code   # (what this unit fills, its own kernel fills)
 
 

@@ -1,5 +1,5 @@
 """fragments.sh_rows_fused, packed_row_views_fused and ViewSH on the GPU (csrc/dmr_sh.hip: k_sh_rows, k_sh_rows_backward,
-k_sh_fill, k_sh_row_views) against fragments.sh_rows / packed_row_views evaluated in float64 on the CPU, on the same float32
+k_sh_row_views; csrc/dmr_rows_common.hip: k_rows_fill) against fragments.sh_rows / packed_row_views evaluated in float64 on the CPU, on the same float32
 inputs cast up: the case table of tests/sh_cases.py (every instantiation; N around a wave, a workgroup's tile and the capped
 grid; B = 1, 2, 5; rows of one view, views changing inside a wave, exactly at wave and workgroup edges, shuffled, with -1 and
 >= B scattered in; origin=None and origin [1,3]), x and y off a 16-byte boundary, special rows, n_rows on the device, single
