@@ -63,6 +63,9 @@
 //   -> y [N,degree^2] and sh_rows_backward(..., grad_out, need_x, need_origin) -> (dL_dx | None, dL_dorigin | None): the view
 //   direction of packed rows as spherical harmonics (fragments.packed_row_views_fused, sh_rows_fused), over
 //   include/dmesh_renderer_amd_sh.h (SUPPORTS_FRAGMENT_SH)
+//   envmap_rows(d [N,3], envmap [He,We,C], n_rows=None) -> y [N,C] and envmap_rows_backward(..., grad_out, need_d, need_envmap)
+//   -> (dL_dd | None, dL_denvmap | None): direction rows looked up in a lat-long environment map (fragments.envmap_rows_fused),
+//   over include/dmesh_renderer_amd_envmap.h (SUPPORTS_FRAGMENT_ENVMAP)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -89,6 +92,7 @@
 #include "../../include/dmesh_renderer_amd_mlp.h"
 #include "../../include/dmesh_renderer_amd_hashgrid.h"
 #include "../../include/dmesh_renderer_amd_sh.h"
+#include "../../include/dmesh_renderer_amd_envmap.h"
 
 namespace {
 
@@ -145,6 +149,9 @@ struct Abi {
     decltype(&dmr_packed_row_views) packed_row_views = nullptr;
     decltype(&dmr_sh_rows) sh_rows = nullptr;
     decltype(&dmr_sh_rows_backward) sh_rows_backward = nullptr;
+    // dmesh_renderer_amd_envmap.h: optional too (SUPPORTS_FRAGMENT_ENVMAP), both or none
+    decltype(&dmr_envmap_rows) envmap_rows = nullptr;
+    decltype(&dmr_envmap_rows_backward) envmap_rows_backward = nullptr;
 };
 
 Abi g_abi;
@@ -228,6 +235,9 @@ void load_abi() {
     g_abi.sh_rows_backward = reinterpret_cast<decltype(g_abi.sh_rows_backward)>(dlsym(g_abi.handle, "dmr_sh_rows_backward"));
     if (!g_abi.packed_row_views || !g_abi.sh_rows || !g_abi.sh_rows_backward)
         g_abi.packed_row_views = nullptr, g_abi.sh_rows = nullptr, g_abi.sh_rows_backward = nullptr;
+    g_abi.envmap_rows = reinterpret_cast<decltype(g_abi.envmap_rows)>(dlsym(g_abi.handle, "dmr_envmap_rows"));
+    g_abi.envmap_rows_backward = reinterpret_cast<decltype(g_abi.envmap_rows_backward)>(dlsym(g_abi.handle, "dmr_envmap_rows_backward"));
+    if (!g_abi.envmap_rows || !g_abi.envmap_rows_backward) g_abi.envmap_rows = nullptr, g_abi.envmap_rows_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -1189,7 +1199,7 @@ py::tuple composite_values_packed_backward(In face, In row, In n_used, In faces_
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
-// -- The row units (mlp_rows, hashgrid_rows, sh_rows) start from x [N,C] on a HIP device and an optional count n_rows [1]: RowArgs.
+// -- The row units (mlp_rows, hashgrid_rows, sh_rows, envmap_rows) start from x [N,C] on a HIP device and an optional count n_rows [1]: RowArgs.
 // A unit's argument block extends it, and its builder calls the named checks below in the unit's order, which is fragments.py's:
 // shapes, sizes, one device, dtypes.
 struct RowArgs {
@@ -1454,6 +1464,53 @@ py::tuple sh_rows_backward(In x, int64_t degree, const std::optional<at::Tensor>
     return py::make_tuple(or_none(dx), or_none(dorg));
 }
 
+// -- envmap_rows: direction rows looked up in a lat-long environment map (dmesh_renderer_amd_envmap.h).  envmap [He,We,C].
+struct EnvMapArgs : RowArgs {
+    at::Tensor envmap;
+    int64_t He = 0, We = 0, C = 0;
+};
+
+EnvMapArgs envmap_args(In d, In envmap, const std::optional<at::Tensor>& n_rows) {
+    EnvMapArgs a;
+    rows_begin(a, "envmap_rows", g_abi.envmap_rows, d, 3, "3");
+    if (envmap.dim() != 3) err("envmap must have dimensions (He, We, C)");
+    a.He = envmap.size(0); a.We = envmap.size(1); a.C = envmap.size(2);
+    if (a.C < 1 || a.C > DMR_ENVMAP_MAX_CHANNELS) err("envmap_rows: C must be in 1..16, got " + std::to_string(a.C));
+    if (a.He < 1 || a.We < 1) err("envmap_rows: the map must have at least one texel");
+    if (a.He * a.We * ((a.C + 3) / 4) >= ((int64_t)1 << 31)) err("envmap_rows: He * We * ceil(C / 4) must be below 2^31");
+    check_row_count(a);
+    check_n_rows(n_rows);
+    on_device_of_x(a, envmap, "envmap_rows: envmap");
+    rows_devices_end(a, d, n_rows);
+    a.envmap = f32(envmap, "envmap");
+    rows_finish(a, n_rows);
+    return a;
+}
+
+// -> y [N,C]
+at::Tensor envmap_rows(In d, In envmap, const std::optional<at::Tensor>& n_rows) {
+    const EnvMapArgs a = envmap_args(d, envmap, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor y = at::empty({a.N, a.C}, f32_on(a.dev));
+    if (g_abi.envmap_rows((int)a.N, (int)a.C, (int)a.He, (int)a.We, mptr<const float>(a.x), mptr<const float>(a.envmap), a.rows_ptr(), mptr<float>(y),
+                          a.stream()))
+        raise_lib();
+    return y;
+}
+
+// need_d, need_envmap -> (dL_dd [N,3], dL_denvmap [He,We,C]), None where not asked for; grad_out [N,C]
+py::tuple envmap_rows_backward(In d, In envmap, const std::optional<at::Tensor>& n_rows, In grad_out, bool need_d, bool need_envmap) {
+    const EnvMapArgs a = envmap_args(d, envmap, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    check_grad_out(a, grad_out, a.C, "C");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor dd = grad_if(need_d, {a.N, 3}, a.dev), de = grad_if(need_envmap, {a.He, a.We, a.C}, a.dev);
+    if (g_abi.envmap_rows_backward((int)a.N, (int)a.C, (int)a.He, (int)a.We, mptr<const float>(a.x), mptr<const float>(a.envmap), a.rows_ptr(),
+                                   mptr<const float>(go), out_ptr(dd), out_ptr(de), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(dd), or_none(de));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1541,6 +1598,9 @@ PYBIND11_MODULE(_C, m) {
           py::arg("n_rows") = py::none());
     m.def("sh_rows_backward", &sh_rows_backward, py::arg("x"), py::arg("degree"), py::arg("origin"), py::arg("row_view"), py::arg("n_rows"),
           py::arg("grad_out"), py::arg("need_x"), py::arg("need_origin"));
+    m.def("envmap_rows", &envmap_rows, py::arg("d"), py::arg("envmap"), py::arg("n_rows") = py::none());
+    m.def("envmap_rows_backward", &envmap_rows_backward, py::arg("d"), py::arg("envmap"), py::arg("n_rows"), py::arg("grad_out"), py::arg("need_d"),
+          py::arg("need_envmap"));
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1580,6 +1640,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_HASHGRID") = g_abi.hashgrid_rows != nullptr;
     // fragments.packed_row_views_fused / sh_rows_fused; False: the loaded library predates dmesh_renderer_amd_sh.h
     m.attr("SUPPORTS_FRAGMENT_SH") = g_abi.sh_rows != nullptr;
+    // fragments.envmap_rows_fused; False: the loaded library predates dmesh_renderer_amd_envmap.h
+    m.attr("SUPPORTS_FRAGMENT_ENVMAP") = g_abi.envmap_rows != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

@@ -41,6 +41,16 @@ torch through th.linalg.inv: dL/dorigin reaches mv_mats for pose refinement):
     hit  = FG.interpolate_packed_fused(frag, packed, faces, verts)
     enc  = th.cat([grid(hit, n_rows=n), FG.ViewSH(4)(hit, FG.camera_origins(mv_mats), view, n_rows=n)], 1)
     image, T = FG.composite_values_packed_fused(frag, packed, faces_opacity, mlp(enc, n_rows=n))
+THE BACKGROUND -- what shows between and through the faces wherever T > 0 -- is, without this, one constant RGB triple.  envmap_rows
+is the torch model of a lookup from direction rows d [N,3] into a learnable lat-long (equirectangular) map [He,We,C], bilinear,
+columns repeating and rows clamped, the pole axis z; envmap_rows_fused (csrc/dmr_envmap.hip) the same as one forward and one
+backward kernel, EnvMap the nn.Module that owns the map, pixel_directions the world-space ray of every pixel centre in the
+renderer's own convention (plain torch, differentiable to both matrices):
+    env  = FG.EnvMap(256, 512).to(dev)                                   # render with settings.bg = 0
+    dirs = FG.pixel_directions(mv_mats, proj_mats, H, W)                 # [B,H,W,3]
+    bg   = env(dirs.reshape(-1, 3)).view(B, H, W, 3).permute(0, 3, 1, 2)
+    color = image + T * bg                                               # image, T from any composite_* call (or 1 - alpha)
+Fed a reflected or view direction per packed row (env(d, n_rows=n)) the same lookup is the cheapest specular term.
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -79,7 +89,8 @@ __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "comp
            "composite_values_fused", "PackedSlots", "pack_slots", "pack_slots_fused", "interpolate_packed", "interpolate_packed_fused",
            "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP",
            "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid",
-           "packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH"]
+           "packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH",
+           "envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -221,7 +232,8 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "mlp_rows": ("SUPPORTS_FRAGMENT_MLP", "row", "MLP"),  # (a third entry: what stands for "compositing" in the message)
           "hashgrid_rows": ("SUPPORTS_FRAGMENT_HASHGRID", "row", "hash-grid encoding"),
           "packed_row_views": ("SUPPORTS_FRAGMENT_SH", "packed row", "view map"),
-          "sh_rows": ("SUPPORTS_FRAGMENT_SH", "row", "spherical-harmonics encoding")}
+          "sh_rows": ("SUPPORTS_FRAGMENT_SH", "row", "spherical-harmonics encoding"),
+          "envmap_rows": ("SUPPORTS_FRAGMENT_ENVMAP", "row", "environment-map lookup")}
 
 
 def _fused_kernels(torch_path: str):
@@ -783,7 +795,7 @@ MLP_HIDDEN = (16, 32, 64)             # the fused kernels' hidden widths; 1 <= C
 
 
 def _check_n_rows(name: str, n_rows):
-    """The last of what the torch and the fused path of every row function (mlp_rows, hashgrid_rows, sh_rows) both refuse."""
+    """The last of what the torch and the fused path of every row function (mlp_rows, hashgrid_rows, sh_rows, envmap_rows) both refuse."""
     if n_rows is not None and (not isinstance(n_rows, th.Tensor) or n_rows.numel() != 1):
         raise ValueError(f"{name}: n_rows must be None or a tensor of one element, got {tuple(n_rows.shape) if isinstance(n_rows, th.Tensor) else n_rows!r}")
 
@@ -1356,3 +1368,171 @@ class ViewSH(th.nn.Module):
                 n_rows: Optional[th.Tensor] = None) -> th.Tensor:
         fused = x.is_cuda and x.dtype == th.float32 and (origin is None or origin.dtype == th.float32)
         return (sh_rows_fused if fused else sh_rows)(x, self.degree, origin=origin, row_view=row_view, n_rows=n_rows)
+
+
+# ---------------------------------------------------------------------------
+# Direction rows looked up in a learnable lat-long environment map: the background, and a specular term (csrc/dmr_envmap.hip)
+# ---------------------------------------------------------------------------
+ENVMAP_MAX_CHANNELS = 16     # DMR_ENVMAP_MAX_CHANNELS
+ENVMAP_MIN_LENGTH = 1e-8     # a shorter (or non-finite) |d| is a skipped row
+ENVMAP_POLE_RHO2 = 1e-12     # ux^2 + uy^2 below it: phi = 0, and the row's dL/dd is an exact 0
+
+
+def _envmap_arguments(name: str, d, envmap, n_rows):
+    """What envmap_rows and envmap_rows_fused both refuse (ValueError), in this order: d [N,3], envmap [He,We,C], C, an empty map,
+    a map too large for the kernels' keys, n_rows."""
+    if d.dim() != 2 or d.shape[1] != 3:
+        raise ValueError(f"{name}: d must be [N,3], got {tuple(d.shape)}")
+    if envmap.dim() != 3:
+        raise ValueError(f"{name}: envmap must be [He,We,C], got {tuple(envmap.shape)}")
+    He, We, C = envmap.shape
+    if not 1 <= C <= ENVMAP_MAX_CHANNELS:
+        raise ValueError(f"{name}: C must be in 1..{ENVMAP_MAX_CHANNELS}, got {C}")
+    if He < 1 or We < 1:
+        raise ValueError(f"{name}: the map must have at least one texel, got {tuple(envmap.shape)}")
+    if He * We * ((C + 3) // 4) >= 2 ** 31:
+        raise ValueError(f"{name}: He * We * ceil(C / 4) must be below 2^31, got {tuple(envmap.shape)}")
+    _check_n_rows(name, n_rows)
+
+
+def envmap_rows(d: th.Tensor, envmap: th.Tensor, *, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """Direction rows d [N,3] looked up in a lat-long (equirectangular) map envmap [He,We,C], channel-last like composite_texture's
+    texture, 1 <= C <= 16 -> [N,C].  Per row r, in d's dtype:
+        n = sqrt(d . d); the row is SKIPPED when n is not finite or n < 1e-8, or when r >= min(max(n_rows, 0), N), mlp_rows' rule
+            (n_rows: None, or an integer tensor of one element on d's device -- what PackedSlots.n_used is): it is not read -- a
+            NaN there reaches nothing --, gives exact zeros in y and dL/dd and adds nothing to dL/denvmap
+        u = d / n, rho2 = ux^2 + uy^2; the pole axis is z, as in sh_rows' table: theta = acos(clamp(uz, -1, 1)), evaluated as
+            atan2(sqrt(rho2), uz) (the same angle, without acos' loss of digits next to the poles), phi = atan2(uy, ux) -- where
+            rho2 < 1e-12: phi = 0, and the row's dL/dd is an exact 0
+        s = phi / (2 pi) + 0.5, t = theta / pi: row 0 of the map is +z, +x the middle of a row
+        x = s We - 0.5, y = t He - 0.5 (texel centres at half-integers, composite_texture's rule); x0 = floor(x), fx = x - x0 from
+            the unwrapped coordinate, likewise y; columns repeat, rows clamp
+        y[r] = the bilinear mix of the four texels.
+    Differentiable in d and envmap: dL/denvmap is the four weights times the upstream, summed over the rows; dL/dd goes through
+    (x, y), (phi, theta) and the normalisation, the cell (the floors) held constant as in composite_texture.  In float32 the
+    coordinates carry the rounding of the two atan2 times the map's size: the deviation from float64 grows with He and We.
+    Not modelled: mip levels, cube maps, a map per view, a nearest filter.  Plain torch, any device, any float dtype: the model
+    envmap_rows_fused is tested against."""
+    _envmap_arguments("envmap_rows", d, envmap, n_rows)
+    N, (He, We, C) = d.shape[0], envmap.shape
+    zero = th.zeros((), dtype=d.dtype, device=d.device)
+    live = th.ones(N, dtype=th.bool, device=d.device)
+    if n_rows is not None:
+        live = live & (th.arange(N, device=d.device) < n_rows.reshape(1).clamp(min=0))
+    w = th.where(live.unsqueeze(1), d, zero)
+    n = th.sqrt((w.detach() * w.detach()).sum(1))
+    ok = live & th.isfinite(n) & ~(n < ENVMAP_MIN_LENGTH)
+    ex = th.zeros(3, dtype=d.dtype, device=d.device)
+    ex[0] = 1
+    safe = th.where(ok.unsqueeze(1), w, ex)        # (the rows that are not ok leave here: their gradient is an exact 0)
+    u = safe / th.sqrt((safe * safe).sum(1, keepdim=True))
+    pole = (u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]).detach() < ENVMAP_POLE_RHO2
+    us = th.where(pole.unsqueeze(1), ex, u)        # (... and the poles here)
+    rho = th.sqrt(us[:, 0] * us[:, 0] + us[:, 1] * us[:, 1])
+    phi = th.atan2(us[:, 1], us[:, 0])
+    theta = th.atan2(rho, us[:, 2])
+    theta = th.where(pole, th.where(u[:, 2].detach() > 0, zero, zero + math.pi), theta)
+    x = (phi / (2 * math.pi) + 0.5) * We - 0.5
+    y = (theta / math.pi) * He - 0.5
+    x0, y0 = x.detach().floor(), y.detach().floor()
+    fx, fy = (x - x0).unsqueeze(1), (y - y0).unsqueeze(1)
+    ix0, ix1 = _wrap_index(x0.long(), We, "repeat"), _wrap_index(x0.long() + 1, We, "repeat")
+    iy0, iy1 = _wrap_index(y0.long(), He, "clamp"), _wrap_index(y0.long() + 1, He, "clamp")
+    e = envmap.to(d.dtype)
+    out = (1 - fy) * ((1 - fx) * e[iy0, ix0] + fx * e[iy0, ix1]) + fy * ((1 - fx) * e[iy1, ix0] + fx * e[iy1, ix1])
+    return th.where(ok.unsqueeze(1), out, zero)
+
+
+class _EnvMapRowsFn(th.autograd.Function):
+    """envmap_rows_fused over _C.envmap_rows / _C.envmap_rows_backward.  Arguments: d, envmap, n_rows (a tensor or None).  Only
+    those are saved: nothing of size [N,C]; the backward re-reads the four texels."""
+
+    @staticmethod
+    def forward(ctx, d, envmap, n_rows):
+        y = _fused_kernels("envmap_rows").envmap_rows(d, envmap, n_rows)
+        _save_optional(ctx, d, envmap, n_rows)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        need_d, need_envmap = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_y is None or not (need_d or need_envmap):
+            return None, None, None
+        d, envmap, n_rows = _saved_optional(ctx)
+        dd, denvmap = _fused_kernels("envmap_rows").envmap_rows_backward(d, envmap, n_rows, grad_y.contiguous(), need_d, need_envmap)
+        return dd, denvmap, None
+
+
+def envmap_rows_fused(d: th.Tensor, envmap: th.Tensor, *, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """envmap_rows(...) as one HIP kernel, and one for its backward (plus the one that zeroes dL_denvmap): a lane owns a row, forms
+    its four texel addresses and weights once and takes the channels in chunks of four (float4 texel reads when C % 4 == 0); y
+    leaves row by row or through an LDS transpose, per C the shape that measured faster.  The backward's dL/dd re-reads the four
+    texels (a plain store per row, no atomics); its dL/denvmap sums on chip what shares a texel -- the lanes of a wave, then a
+    per-workgroup LDS table of f64 cells -- before float atomics leave (so dL_denvmap depends on the order of summation in its
+    last bits; y and dL_dd do not).  The same y, the same skipped rows (n_rows is read on the device: no host wait, capturable),
+    each gradient computed only when autograd asks for it; autograd keeps d, envmap and n_rows, nothing of size [N,C].  Whatever
+    the bits of d, every access is in bounds.  N < 2^31 (ValueError).  HIP float32 tensors on one device only (n_rows int32 [1]),
+    made contiguous if they are not: anything else is a TypeError -- envmap_rows is the torch path for it; nothing falls back
+    silently.  Refused in this order: an older binding, the arguments (as envmap_rows), N, the dtypes, the devices."""
+    name, torch_path = "envmap_rows_fused", "fragments.envmap_rows is the torch path for anything else"
+    _fused_kernels("envmap_rows")
+    _envmap_arguments(name, d, envmap, n_rows)
+    _check_row_tensors(name, torch_path, d, [("d", d), ("envmap", envmap)], [("n_rows", n_rows)])
+    return _EnvMapRowsFn.apply(d, envmap, None if n_rows is None else n_rows.reshape(1))
+
+
+class EnvMap(th.nn.Module):
+    """A lat-long environment map as a Module that owns its `envmap` (a Parameter [height, width, channels], initialised to 0.5:
+    mid-grey, not derived here): the learnable background behind the faces, or a specular term over packed rows.
+    frame (optional, [3,3]): d is rotated to frame @ d in torch before the lookup, for a pole axis other than z -- its rows are
+    the map's x, y and z axes in world coordinates; kept as a buffer.  .out_features = channels.
+    forward(d, n_rows=None) runs envmap_rows_fused on HIP float32 rows and envmap_rows on anything else, as HashGrid does."""
+
+    def __init__(self, height: int, width: int, channels: int = 3, frame: Optional[th.Tensor] = None):
+        super().__init__()
+        for what, v in (("height", height), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"EnvMap: {what} must be a positive int, got {v!r}")
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= ENVMAP_MAX_CHANNELS:
+            raise ValueError(f"EnvMap: channels must be an int in 1..{ENVMAP_MAX_CHANNELS}, got {channels!r}")
+        if frame is not None:
+            frame = th.as_tensor(frame, dtype=th.float32)
+            if tuple(frame.shape) != (3, 3):
+                raise ValueError(f"EnvMap: frame must be [3,3], got {tuple(frame.shape)}")
+            frame = frame.clone()
+        self.register_buffer("frame", frame)
+        self.out_features = channels
+        self.envmap = th.nn.Parameter(th.full((height, width, channels), 0.5))
+
+    def forward(self, d: th.Tensor, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+        if self.frame is not None:
+            d = d @ self.frame.to(d.dtype).T
+        fused = d.is_cuda and d.dtype == th.float32 and self.envmap.dtype == th.float32
+        return (envmap_rows_fused if fused else envmap_rows)(d, self.envmap, n_rows=n_rows)
+
+
+def pixel_directions(mv_mats: th.Tensor, proj_mats: th.Tensor, H: int, W: int) -> th.Tensor:
+    """[B,H,W,3]: the normalised world-space ray of every pixel centre, from the Modules' mv_mats and proj_mats [B,4,4] (what
+    TriRenderer / TetRenderer.forward take; camera_origins' matrix convention), by the arithmetic of the kernels' pixel ray: the
+    pixel (px, py) goes through ndc ((2 (px + 0.5) + 1) / W - 1, (2 (py + 0.5) + 1) / H - 1, -1), that point through inv(proj_mats)
+    and the affine part of inv(mv_mats) into world space, w = it - the camera centre, d = w / (|w| + 1e-7) -- the tri renderer's
+    length (the tet renderer divides by max(|w|, 1e-4): the same to 1e-7 of |w|).  The tet renderer's seeded jitter of the pixel
+    position (seed > 0) is NOT modelled: these are the rays of seed = 0.  Plain torch through th.linalg.inv, any device and float
+    dtype, differentiable to both matrices."""
+    for what, m in (("mv_mats", mv_mats), ("proj_mats", proj_mats)):
+        if m.dim() != 3 or tuple(m.shape[1:]) != (4, 4):
+            raise ValueError(f"pixel_directions: {what} must be [B,4,4], got {tuple(m.shape)}")
+    if proj_mats.shape[0] != mv_mats.shape[0]:
+        raise ValueError(f"pixel_directions: mv_mats and proj_mats must hold the same views, got {mv_mats.shape[0]} and {proj_mats.shape[0]}")
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
+        raise ValueError(f"pixel_directions: H and W must be positive ints, got {H!r}, {W!r}")
+    dt, dev = mv_mats.dtype, mv_mats.device
+    im, ip = th.linalg.inv(mv_mats), th.linalg.inv(proj_mats.to(dt))
+    nx = ((th.arange(W, dtype=dt, device=dev) + 0.5) * 2 + 1) / W - 1
+    ny = ((th.arange(H, dtype=dt, device=dev) + 0.5) * 2 + 1) / H - 1
+    ndc = th.stack([nx.view(1, W).expand(H, W), ny.view(H, 1).expand(H, W), -th.ones(H, W, dtype=dt, device=dev),
+                    th.ones(H, W, dtype=dt, device=dev)], -1)                       # [H,W,4]
+    pv = th.einsum("bij,hwj->bhwi", ip, ndc)                                        # [B,H,W,4]
+    w = th.einsum("bij,bhwj->bhwi", im[:, :3, :3], pv[..., :3])                     # (+ the centre, - the centre)
+    return w / (th.sqrt((w * w).sum(-1, keepdim=True)) + 1e-7)
