@@ -8,7 +8,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from mlp_cases import COMMON_DISPATCH_LINES, COMMON_HEADER, COMMON_SOURCE, FILL_KERNEL, FILL_LAUNCH_LINE  # noqa: F401
+from row_units import FILL_KERNEL
 
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_envmap.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_envmap_cpu.py fails when

@@ -7,12 +7,12 @@ from collections import namedtuple
 
 import numpy as np
 
-from mlp_cases import COMMON_DISPATCH_LINES, COMMON_HEADER, COMMON_SOURCE, FILL_KERNEL, FILL_LAUNCH_LINE  # noqa: F401
+from row_units import FILL_KERNEL
 
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_hashgrid.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_hashgrid_cpu.py
-# fails when one of them is no longer in the file exactly once: then this follows the new dispatch.  COMMON_DISPATCH_LINES: what
-# the row units take from COMMON_HEADER (the ladder behind with_one_of and with_wanted, the grid, the backward call's opening).
+# fails when one of them is no longer in the file exactly once: then this follows the new dispatch.  What the row units take
+# from the shared csrc/dmr_rows_common.* is restated once, in tests/row_units.py (COMMON_DISPATCH_LINES, FILL_KERNEL).
 # ---------------------------------------------------------------------------
 FEATURES = (1, 2, 4, 8)
 THREADS, MAX_GROUPS = 256, 1024

@@ -7,31 +7,9 @@ from collections import namedtuple
 
 # ---------------------------------------------------------------------------
 # The host dispatch of dmr_mlp.hip, restated.  DISPATCH_LINES holds the lines this mirrors; tests/test_mlp_cpu.py fails when
-# one of them is no longer in the file exactly once: then this follows the new dispatch.
-# COMMON_DISPATCH_LINES: the same for what this unit, the hash grid (tests/hashgrid_cases.py) and the SH unit (tests/sh_cases.py)
-# take from COMMON_HEADER -- the n_rows clamp, a backward workgroup's run of tiles, the grid, the two ladders and the backward
-# calls' opening --, each there exactly once and in no unit; COMMON_SOURCE defines the fill kernel FILL_KERNEL, launched by
-# FILL_LAUNCH_LINE for the units that call rows_fill_on.
+# one of them is no longer in the file exactly once: then this follows the new dispatch.  What the row units take from the
+# shared csrc/dmr_rows_common.* is restated once, in tests/row_units.py (COMMON_DISPATCH_LINES; this unit fills nothing).
 # ---------------------------------------------------------------------------
-COMMON_HEADER, COMMON_SOURCE, FILL_KERNEL = "dmr_rows_common.hpp", "dmr_rows_common.hip", "k_rows_fill"
-COMMON_DISPATCH_LINES = [
-    "return u < 0 ? 0 : (u > p.N ? p.N : u);",
-    '__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");',
-    "const int per = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;",
-    "return {t0, t0 + per < tiles ? t0 + per : tiles};",
-    "const int tiles = (int)(((int64_t)N + threads - 1) / threads);",
-    "return {tiles, tiles < max_groups ? tiles : max_groups};",
-    "if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>());",
-    "else if (v == V) f(std::integral_constant<int, V>());",
-    "else with_one_of<Rest...>(v, f);",
-    "if (first && second) f(std::true_type(), std::true_type());",
-    "else if (first) f(std::true_type(), std::false_type());",
-    "else f(std::false_type(), std::true_type());",
-    'if (N > 0 && !grad_out) return api_fail((std::string(name) + ": null grad_out").c_str());',
-    "if (N == 0) dL_dx = nullptr;  // (no row to write)",
-    "return (dL_dx || others) ? SHADE_LAUNCH : SHADE_DONE;",
-]
-FILL_LAUNCH_LINE = "k_rows_fill<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st>>>(static_cast<uint32_t*>(a), n, value);"
 HIDDEN = (16, 32, 64)
 MAX_CIN, MAX_COUT = 64, 16
 FWD_THREADS, FWD_MAX_GROUPS, BWD_MAX_GROUPS = 256, 1024, 512

@@ -4,7 +4,6 @@ breaks --, agreement across the seam, gradcheck, the sum identity of the bilinea
 tests/tri_grad_ref.py's pixel_rays, csrc/dmr_envmap_coords.hpp compiled with the host compiler and run over the bits that must
 not be tried on a GPU, the library's exports and the build lists, the refusals of the functional layer and of the C ABI in their
 documented order, and the case tables of the GPU tests (tests/envmap_cases.py) against the unit's dispatch."""
-import ctypes as C
 import math
 import os
 import re
@@ -17,17 +16,14 @@ import pytest
 import torch as th
 
 import envmap_cases as EC
+import row_units as RU
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
+from row_units import CSRC, D
 from tri_grad_ref import pixel_rays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dmesh_renderer_amd", "csrc")
-HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_envmap.h")
-UNIT_TEXT = open(os.path.join(CSRC, "dmr_envmap.hip")).read()
+UNIT_TEXT, HEADER_TEXT = RU.unit_texts("dmr_envmap.hip", "dmesh_renderer_amd_envmap.h")
 COORDS_TEXT = open(os.path.join(CSRC, EC.COORDS_HEADER)).read()
-COMMON_TEXT, FILL_TEXT = (open(os.path.join(CSRC, f)).read() for f in (EC.COMMON_HEADER, EC.COMMON_SOURCE))
-HEADER_TEXT = open(HEADER).read()
 FUNCTIONS = ["dmr_envmap_rows", "dmr_envmap_rows_backward"]
 TORCH_PATH = r"fragments\.envmap_rows is the torch path"
 NAMES = ("envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions")
@@ -357,34 +353,12 @@ def test_the_unit_takes_its_indices_from_that_header():
 # ---------------------------------------------------------------------------
 # Library, binding and build lists
 # ---------------------------------------------------------------------------
-def _library():
-    import capi_ctypes
-    lib = capi_ctypes.load()
-    lib.dmr_envmap_rows.restype = lib.dmr_envmap_rows_backward.restype = C.c_int
-    lib.dmr_envmap_rows.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5
-    lib.dmr_envmap_rows_backward.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
-    return lib
-
-
 def test_library_exports_the_declared_symbols():
-    from dmesh_renderer_amd import build
-    src = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-    assert sorted(set(re.findall(r"\b(dmr_[a-z_0-9]+)\s*\(", src))) == FUNCTIONS
-    lib = C.CDLL(build.build())
-    for n in FUNCTIONS:
-        assert hasattr(lib, n), f"{n} declared in the header but not exported"
-    assert not hasattr(lib, "dmr_envmap_stats")   # (the ablation build's counters are not in the product)
+    RU.exports_declared(HEADER_TEXT, FUNCTIONS, absent=["dmr_envmap_stats"])   # (the ablation build's counters are not in the product)
 
 
 def test_the_source_and_headers_are_build_dependencies():
-    from dmesh_renderer_amd import build
-    assert "dmr_envmap.hip" in build.SOURCES and EC.COORDS_HEADER in build.HEADERS and "dmr_texture_wrap.hpp" in build.HEADERS
-    assert EC.COMMON_SOURCE in build.SOURCES and EC.COMMON_HEADER in build.HEADERS
-    assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
-    for deps in (build.HEADERS, build.GLUE_SOURCES, build.PUBLIC_HEADERS):
-        assert any(os.path.basename(d) == "dmesh_renderer_amd_envmap.h" for d in deps)
-        assert all(os.path.exists(os.path.join(build.CSRC, d)) for d in deps)
-    assert "dmesh_renderer_amd_envmap.h" in build.__doc__
+    RU.are_build_dependencies("dmr_envmap.hip", "dmesh_renderer_amd_envmap.h", extra=[EC.COORDS_HEADER, "dmr_texture_wrap.hpp"])
 
 
 def test_binding_supports_it():
@@ -474,7 +448,6 @@ def test_refusals_in_their_documented_order():
 # Refusals of the C ABI, through ctypes with device pointers that are never dereferenced: every check runs before any HIP call.
 # No call here has wholly valid arguments and an output to write: none reaches a launch.
 # ---------------------------------------------------------------------------
-D = C.c_void_p(16)  # non-null, never dereferenced on these paths
 INTS = "N C He We"
 PTRS = {"dmr_envmap_rows": "d envmap n_rows y", "dmr_envmap_rows_backward": "d envmap n_rows grad_out dL_dd dL_denvmap"}
 SIZES = dict(N=1, C=3, He=4, We=8)
@@ -504,23 +477,8 @@ PER_CALL = {
 
 
 def test_c_abi_refusals():
-    lib = _library()
-    seen = set()
-    for call, ptrs in PTRS.items():
-        takes = INTS.split() + ptrs.split()
-        for case, (changes, text) in list(EVERY_CALL.items()) + list(PER_CALL[call].items()):
-            assert all(k in takes for k in changes), (call, case)
-            args = [changes.get(n, SIZES[n]) for n in INTS.split()]
-            args += [changes.get(n, None if n in NULL_BY_DEFAULT else D) for n in ptrs.split()]
-            args.append(None)   # stream
-            ret = getattr(lib, call)(*args)
-            got = lib.dmr_last_error().decode() if ret else ""
-            if text is None:
-                assert (ret, got) == (0, ""), (call, case, got)
-            else:
-                assert ret == 1 and got == f"{call}: {text}", (call, case, got)
-            seen.add((call, case))
-    assert len(seen) == 2 * len(EVERY_CALL) + sum(len(v) for v in PER_CALL.values())
+    import capi_ctypes
+    RU.run_refusals(RU.declare(capi_ctypes.load(), FUNCTIONS), INTS, PTRS, SIZES, NULL_BY_DEFAULT, EVERY_CALL, PER_CALL)
     # the order the header documents is the order tested above
     order = re.sub(r"\s*\n \* ", " ", HEADER_TEXT[HEADER_TEXT.index("The order, for both calls"):])
     at = [order.index(w) for w in ('"bad rows"', "C,", "at least one texel", '"map too large"', "null d", "null envmap", "a null output (dmr_envmap_rows,", "null grad_out")]
@@ -531,27 +489,14 @@ def test_c_abi_refusals():
 # The case tables of the GPU tests
 # ---------------------------------------------------------------------------
 def test_dispatch_restated_as_the_unit_has_it():
-    for line in EC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == (2 if line in EC.TWICE else 1) and COMMON_TEXT.count(line) == 0, line
-    for line in EC.COMMON_DISPATCH_LINES:
-        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
-    assert FILL_TEXT.count(EC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % EC.COMMON_HEADER in UNIT_TEXT
-    for line in EC.HEADER_LINES:
-        assert HEADER_TEXT.count(line) == 1, line
+    product = RU.dispatch_restated(EC, UNIT_TEXT, HEADER_TEXT, twice=EC.TWICE)
     assert [EC.via_lds(n) for n in EC.CHUNKS] == [False, True, True] and [EC.chunks_of(c) for c in (1, 4, 5, 8, 9, 12, 13, 16)] == [1, 1, 2, 2, 4, 4, 4, 4]
-    # the kernels the unit launches are the ones every_instantiation lists; the product launches no <NCH, !L> shape
-    product = re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S)
-    launches = lambda text: set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", text))
-    assert launches(FILL_TEXT) == {EC.FILL_KERNEL} and "rows_fill_on(st, " in product
-    assert launches(product) | launches(FILL_TEXT) == {k for k, _ in EC.every_instantiation()}
+    # the kernels the product launches are the ones every_instantiation lists: no <NCH, !L> shape
     assert "!L>" not in product and "ablate_bits" not in product and "g_env_stats" not in product and "p.dbg" not in product and "!L>" in UNIT_TEXT
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT + COORDS_TEXT, flags=re.S))
-    assert "hipMemset" not in code and "hipMalloc" not in code and "Synchronize" not in code and "hipMemcpy" not in code
-    assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert code.count("rows_fill_on(st, ") == 1 and EC.FILL_KERNEL + "<<<" in code and "asm" not in code   # (what this unit fills, the shared kernel fills)
+    code = RU.waits_for_nothing([UNIT_TEXT, COORDS_TEXT], fill_calls=1)
     # dL_dd is stored, never added: the only global atomics are the two into dL_denvmap
     assert code.count("unsafeAtomicAdd(&denv[") == 2 and code.count("unsafeAtomicAdd(") == 2 and "atomicAdd(&dd" not in code
 

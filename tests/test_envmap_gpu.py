@@ -5,7 +5,7 @@ C = 1 .. 16; maps from 1 x 1 to 64 x 128; directions uniform, in a 2-degree cone
 shuffled), special rows between sentinels, d, y and the map off a 16-byte boundary, n_rows on the device, single gradients, the
 sum identity, a replayed HIP graph, the pixel directions of rendered lists, and the two chains of the module docstring.
 
-Inputs: |d| in [0.5, 3], map and upstream ~ N(0,1).  Errors are max |got - ref| / max |ref| (_rel: relative to the largest entry).
+Inputs: |d| in [0.5, 3], map and upstream ~ N(0,1).  Errors are max |got - ref| / max |ref| (_rel, which is row_units.rel_to_largest).
 Bounds (the project's own): y within max(FWD_TOL = 1e-5, 4 x the yardstick), gradients within max(GRAD_TOL = 1e-4, 4 x the
 yardstick), the yardstick being fragments.envmap_rows in float32 on the CPU against float64 on the same case; never anything the
 kernels gave.  For the dL_dd comparison only, rows within 1e-3 texel of a cell line or with rho2 < 1e-4 carry no upstream
@@ -34,21 +34,12 @@ import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
 from dmesh_renderer_amd import scenes
 from harness import TRI_ARGS, capture_replay, replay
+from row_units import FWD_TOL, GRAD_TOL, check, counts_calls, declare, guarded, intact, models, n_rows_counts, within_floors
+from row_units import rel_to_largest as _rel
 from tri_grad_ref import pixel_rays
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
-
-FWD_TOL = 1e-5
-GRAD_TOL = 1e-4
-
-
-def _rel(got, ref):
-    """max |got - ref| / max |ref| (max |got| where the reference is all zeros: such an output must be zeros)."""
-    if ref.size == 0:
-        return 0.0
-    top = float(np.abs(ref).max())
-    return float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max()) / (top if top > 0 else 1.0)
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,23 +71,11 @@ def _run(f, c, t, device, dtype, n=None, want=None):
 @functools.lru_cache(maxsize=None)
 def _models(c, n=None):
     """fragments.envmap_rows on the CPU in float64 and in float32 -> (reference, {name: (the bound of the case, the yardstick)})."""
-    t = _inputs(c)
-    full = c._replace(want="de")
-    ref, f32 = _run(FG.envmap_rows, full, t, "cpu", th.float64, n), _run(FG.envmap_rows, full, t, "cpu", th.float32, n)
-    bounds = {}
-    for k in ref:
-        yard = _rel(f32[k], ref[k])
-        bounds[k] = (max(FWD_TOL if k == "y" else GRAD_TOL, 4 * yard), yard)
-    return ref, bounds
+    return models(_run, FG.envmap_rows, c._replace(want="de"), _inputs(c), n, _rel)
 
 
 def _check(what, c, got, n=None):
-    ref, bounds = _models(c, n)
-    for k in got:
-        e, (bound, yard) = _rel(got[k], ref[k]), bounds[k]
-        print(f"\n{what} {k}: {e:.2e} (float32 torch {yard:.2e}, bound {bound:.1e}, max |ref| {float(np.abs(ref[k]).max()) if ref[k].size else 0:.3g})")
-        assert got[k].shape == ref[k].shape and np.isfinite(got[k]).all() and e <= bound, (what, k, e)
-    return ref
+    return check(what, *_models(c, n), got, _rel)
 
 
 @pytest.mark.parametrize("i", range(len(EC.TABLE)))
@@ -125,27 +104,7 @@ def test_table(hip_device, i):
 # ---------------------------------------------------------------------------
 def _c_calls():
     from dmesh_renderer_amd import _C
-    lib = C.CDLL(_C.library_path())
-    lib.dmr_envmap_rows.restype = lib.dmr_envmap_rows_backward.restype = C.c_int
-    lib.dmr_envmap_rows.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5
-    lib.dmr_envmap_rows_backward.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
-    lib.dmr_last_error.restype = C.c_char_p
-    return lib
-
-
-SENTINEL, PAD = 0x7fc0beef, 64   # a NaN with a payload; words before and after every body
-
-
-def _guarded(dev, n, off=0):
-    """(buffer int32 [PAD + off + n + PAD] of sentinels, its body as float32 [n] starting `off` floats past a 256-byte boundary)"""
-    buf = th.full((PAD + off + n + PAD,), SENTINEL, dtype=th.int32, device=dev)
-    body = buf[PAD + off:PAD + off + n].view(th.float32)
-    assert body.data_ptr() % 16 == (4 * off) % 16
-    return buf, body
-
-
-def _intact(buf, n, off=0):
-    return bool((buf[:PAD + off] == SENTINEL).all()) and bool((buf[PAD + off + n:] == SENTINEL).all())
+    return declare(C.CDLL(_C.library_path()), ["dmr_envmap_rows", "dmr_envmap_rows_backward"])
 
 
 def _call_pair(lib, dev, N, Cn, He, We, d, env, up, off=0, n_rows=None):
@@ -153,7 +112,7 @@ def _call_pair(lib, dev, N, Cn, He, We, d, env, up, off=0, n_rows=None):
     -> (y [N,C], dL_dd [N,3], dL_denvmap [He,We,C]) as numpy; asserts that every sentinel is unchanged."""
     stream = th.cuda.current_stream(dev).cuda_stream
     sizes = dict(d=N * 3, env=He * We * Cn, y=N * Cn, up=N * Cn, dd=N * 3, de=He * We * Cn)
-    bufs = {k: _guarded(dev, n, off) for k, n in sizes.items()}
+    bufs = {k: guarded(dev, n, off) for k, n in sizes.items()}
     bufs["d"][1].copy_(d.to(dev).flatten())
     bufs["env"][1].copy_(env.to(dev).flatten())
     bufs["up"][1].copy_(up.to(dev).flatten())
@@ -164,7 +123,7 @@ def _call_pair(lib, dev, N, Cn, He, We, d, env, up, off=0, n_rows=None):
         assert lib.dmr_envmap_rows_backward(N, Cn, He, We, p["d"], p["env"], nr, p["up"], p["dd"], p["de"], stream) == 0, lib.dmr_last_error()
     th.cuda.synchronize()
     for k, n in sizes.items():
-        assert _intact(bufs[k][0], n, off), k
+        assert intact(bufs[k][0], n, off), k
     return (bufs["y"][1].cpu().numpy().reshape(N, Cn), bufs["dd"][1].cpu().numpy().reshape(N, 3), bufs["de"][1].cpu().numpy().reshape(He, We, Cn))
 
 
@@ -228,17 +187,14 @@ def test_n_rows_on_the_device(hip_device):
     y and dL_dd, dL_denvmap the model's (nothing from the tail)."""
     c = EC.N_ROWS
     base = _inputs(c)
-    for n in (0, 130, c.N, c.N + 50, -7):
+    for n in n_rows_counts(c.N):
         m = min(max(n, 0), c.N)
         t = dict(base, d=base["d"].clone(), up=base["up"].clone(), up_d=base["up_d"].clone())
         t["d"][m:], t["up"][m:], t["up_d"][m:] = float("nan"), float("nan"), float("nan")
         got = _run(FG.envmap_rows_fused, c, t, hip_device, th.float32, n)
         clean = {k: (th.nan_to_num(v) if v.dtype.is_floating_point else v) for k, v in t.items()}
         ref = _run(FG.envmap_rows, c, clean, "cpu", th.float64, n)
-        for k in ref:
-            e = _rel(got[k], ref[k])
-            print(f"\nn_rows {n} of {c.N}, {k}: {e:.2e}")
-            assert np.isfinite(got[k]).all() and e <= (FWD_TOL if k == "y" else GRAD_TOL), (n, k, e)
+        within_floors(f"n_rows {n} of {c.N},", ref, got, _rel)
         assert float(np.abs(got["y"][m:]).sum()) == 0.0 and float(np.abs(got["d"][m:]).sum()) == 0.0
         if m == 0:
             assert all(float(np.abs(got[k]).max()) == 0.0 for k in got)
@@ -277,9 +233,7 @@ def test_no_upstream_launches_nothing(hip_device, monkeypatch):
     d, env = t["d"].to(hip_device).requires_grad_(True), t["env"].to(hip_device).requires_grad_(True)
     y = FG.envmap_rows_fused(d, env)
     z = y * 1.0
-    calls = []
-    real = _C.envmap_rows_backward
-    monkeypatch.setattr(_C, "envmap_rows_backward", lambda *a, **k: calls.append(1) or real(*a, **k))
+    calls = counts_calls(monkeypatch, _C, "envmap_rows_backward")
     grads = th.autograd.grad((d * 3).sum(), [d, env], allow_unused=True)
     assert grads[1] is None and not calls
     assert FG._EnvMapRowsFn.backward(y.grad_fn, None) == (None, None, None) and not calls

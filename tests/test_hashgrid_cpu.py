@@ -9,7 +9,6 @@ their documented order -- and the case tables of the GPU tests (tests/hashgrid_c
 unit compiles, with at most 3 % of a case's rows in the boundary band."""
 import ctypes as C
 import math
-import os
 import re
 
 import numpy as np
@@ -17,15 +16,12 @@ import pytest
 import torch as th
 
 import hashgrid_cases as HC
+import row_units as RU
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
+from row_units import D
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_hashgrid.h")
-UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_hashgrid.hip")
-UNIT_TEXT = open(UNIT).read()
-COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (HC.COMMON_HEADER, HC.COMMON_SOURCE))
-HEADER_TEXT = open(HEADER).read()
+UNIT_TEXT, HEADER_TEXT = RU.unit_texts("dmr_hashgrid.hip", "dmesh_renderer_amd_hashgrid.h")
 FUNCTIONS = ["dmr_hashgrid_layout", "dmr_hashgrid_rows", "dmr_hashgrid_rows_backward"]
 TORCH_PATH = r"fragments\.hashgrid_rows is the torch path"
 
@@ -256,12 +252,7 @@ def test_module():
 # ---------------------------------------------------------------------------
 def _library():
     import capi_ctypes
-    lib = capi_ctypes.load()
-    lib.dmr_hashgrid_layout.restype = lib.dmr_hashgrid_rows.restype = lib.dmr_hashgrid_rows_backward.restype = C.c_int
-    lib.dmr_hashgrid_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.dmr_hashgrid_rows.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
-    lib.dmr_hashgrid_rows_backward.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
-    return lib
+    return RU.declare(capi_ctypes.load(), FUNCTIONS)
 
 
 def test_the_c_layout_is_the_spec():
@@ -278,28 +269,12 @@ def test_the_c_layout_is_the_spec():
     assert any(sz == 1 << T for L, F, T, R0, s in specs for sz in FG.hashgrid_spec(L, F, T, R0, s).sizes)
 
 
-def _declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-    return sorted(set(re.findall(r"\b(dmr_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_library_exports_the_declared_symbols():
-    from dmesh_renderer_amd import build
-    assert _declared_functions() == FUNCTIONS
-    lib = C.CDLL(build.build())
-    for n in FUNCTIONS:
-        assert hasattr(lib, n), f"{n} declared in the header but not exported"
-    assert not hasattr(lib, "dmr_hashgrid_stats")   # (the ablation build's counters are not in the product)
+    RU.exports_declared(HEADER_TEXT, FUNCTIONS, absent=["dmr_hashgrid_stats"])   # (the ablation build's counters are not in the product)
 
 
 def test_the_source_and_header_are_build_dependencies():
-    from dmesh_renderer_amd import build
-    assert "dmr_hashgrid.hip" in build.SOURCES and HC.COMMON_SOURCE in build.SOURCES and HC.COMMON_HEADER in build.HEADERS
-    assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
-    for deps in (build.HEADERS, build.GLUE_SOURCES):
-        assert any(os.path.basename(d) == "dmesh_renderer_amd_hashgrid.h" for d in deps)
-        assert all(os.path.exists(os.path.join(build.CSRC, d)) for d in deps)
-    assert "dmesh_renderer_amd_hashgrid.h" in build.__doc__
+    RU.are_build_dependencies("dmr_hashgrid.hip", "dmesh_renderer_amd_hashgrid.h")
 
 
 def test_binding_supports_it():
@@ -379,7 +354,6 @@ def test_refusals_in_their_documented_order():
 # Refusals of the C ABI, through ctypes with device pointers that are never dereferenced: every check runs before any HIP call.
 # `resolutions` is a host array and is read.  No call here has wholly valid arguments and an output to write: none reaches a launch.
 # ---------------------------------------------------------------------------
-D = C.c_void_p(16)  # non-null, never dereferenced on these paths
 INTS = "N L F log2_T"
 PTRS = {"dmr_hashgrid_rows": "resolutions x table n_rows y", "dmr_hashgrid_rows_backward": "resolutions x table n_rows grad_out dL_dx dL_dtable"}
 SIZES = dict(N=1, L=3, F=2, log2_T=6)
@@ -422,22 +396,7 @@ PER_CALL = {
 
 def test_c_abi_refusals():
     lib = _library()
-    seen = set()
-    for call, ptrs in PTRS.items():
-        takes = INTS.split() + ptrs.split()
-        for case, (changes, text) in list(EVERY_CALL.items()) + list(PER_CALL[call].items()):
-            assert all(k in takes for k in changes), (call, case)
-            args = [changes.get(n, SIZES[n]) for n in INTS.split()]
-            args += [changes.get(n, RES if n == "resolutions" else (None if n in NULL_BY_DEFAULT else D)) for n in ptrs.split()]
-            args.append(None)   # stream
-            ret = getattr(lib, call)(*args)
-            got = lib.dmr_last_error().decode() if ret else ""
-            if text is None:
-                assert (ret, got) == (0, ""), (call, case, got)
-            else:
-                assert ret == 1 and got == f"{call}: {text}", (call, case, got)
-            seen.add((call, case))
-    assert len(seen) == 2 * len(EVERY_CALL) + sum(len(v) for v in PER_CALL.values())
+    RU.run_refusals(lib, INTS, PTRS, SIZES, NULL_BY_DEFAULT, EVERY_CALL, PER_CALL, special=dict(resolutions=RES))
     out = (C.c_int64 * 4)()
     for args, text in (((0, 6, RES, out), "L must be in 1..16, got 0"), ((3, 3, RES, out), "log2_T must be in 4..24, got 3"), ((3, 6, None, out), "null resolutions"),
                        ((3, 6, _res(2, 4, 0), out), "resolutions[2] must be in 1..65536, got 0"), ((3, 6, RES, None), "null output"), ((0, 3, None, None), "L must be in 1..16, got 0")):
@@ -448,29 +407,14 @@ def test_c_abi_refusals():
 # The case tables of the GPU tests
 # ---------------------------------------------------------------------------
 def test_dispatch_restated_as_the_unit_has_it():
-    for line in HC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
-    for line in HC.TWICE:
-        assert UNIT_TEXT.count(line) == 2, line
-    for line in HC.COMMON_DISPATCH_LINES:
-        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
-    assert FILL_TEXT.count(HC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % HC.COMMON_HEADER in UNIT_TEXT
-    for line in HC.HEADER_LINES:
-        assert HEADER_TEXT.count(line) == 1, line
+    product = RU.dispatch_restated(HC, UNIT_TEXT, HEADER_TEXT, twice=HC.TWICE)
     assert tuple(FG.HASHGRID_FEATURES) == HC.FEATURES
-    # the kernels the unit launches are the ones every_instantiation lists; the product launches no <FF, false> forward
-    product = re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S)
-    launches = lambda text: set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", text))
-    assert launches(FILL_TEXT) == {HC.FILL_KERNEL} and "rows_fill_on(st, " in product   # (the shared code's launch for this unit)
-    assert launches(product) | launches(FILL_TEXT) == {k for k, _ in HC.every_instantiation()}
+    # the kernels the product launches are the ones every_instantiation lists: no <FF, false> forward
     assert "k_hashgrid_rows<FF, false>" not in product and "g_hg_stats" not in product and "p.dbg" not in product
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT, flags=re.S))
-    assert "hipMemset" not in code and "hipMalloc" not in code and "Synchronize" not in code and "hipMemcpy" not in code
-    assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert code.count("rows_fill_on(st, ") == 1 and HC.FILL_KERNEL + "<<<" in code and "asm" not in code
+    RU.waits_for_nothing([UNIT_TEXT], fill_calls=1)
 
 
 def test_tables_reach_every_instantiation():

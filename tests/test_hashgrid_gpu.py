@@ -38,12 +38,11 @@ import hashgrid_cases as HC
 from dmesh_renderer_amd import fragments as FG
 from dmesh_renderer_amd import scenes
 from harness import TET_ARGS, TRI_ARGS, capture_replay, replay
+from row_units import FWD_TOL, GRAD_TOL, check, counts_calls, declare, guarded, intact, models, n_rows_counts, within_floors
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
 
-FWD_TOL = 1e-5
-GRAD_TOL = 1e-4
 BAND_CAP = 0.03
 
 
@@ -89,22 +88,11 @@ def _run(f, c, d, device, dtype, n=None, want="xt"):
 @functools.lru_cache(maxsize=None)
 def _models(c, n=None):
     """fragments.hashgrid_rows on the CPU in float64 and in float32 -> (reference, {name: (the bound of the case, the yardstick)})."""
-    d = _inputs(c)
-    ref, f32 = _run(FG.hashgrid_rows, c, d, "cpu", th.float64, n), _run(FG.hashgrid_rows, c, d, "cpu", th.float32, n)
-    bounds = {}
-    for k in ref:
-        yard = rel_err(f32[k], ref[k])
-        bounds[k] = (max(FWD_TOL if k == "y" else GRAD_TOL, 4 * yard), yard)
-    return ref, bounds
+    return models(_run, FG.hashgrid_rows, c, _inputs(c), n, rel_err)
 
 
 def _check(what, c, got, n=None):
-    ref, bounds = _models(c, n)
-    for k in got:
-        e, (bound, yard) = rel_err(got[k], ref[k]), bounds[k]
-        print(f"\n{what} {k}: {e:.2e} (float32 torch {yard:.2e}, bound {bound:.1e}, max |ref| {float(np.abs(ref[k]).max()) if ref[k].size else 0:.3g})")
-        assert got[k].shape == ref[k].shape and np.isfinite(got[k]).all() and e <= bound, (what, k, e)
-    return ref
+    return check(what, *_models(c, n), got, rel_err)
 
 
 @pytest.mark.parametrize("i", range(len(HC.TABLE)))
@@ -124,17 +112,13 @@ def test_table(hip_device, i):
 # ---------------------------------------------------------------------------
 def _c_calls(dev):
     from dmesh_renderer_amd import _C
-    lib = C.CDLL(_C.library_path())
-    lib.dmr_hashgrid_rows.restype = lib.dmr_hashgrid_rows_backward.restype = C.c_int
-    lib.dmr_hashgrid_rows.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
-    lib.dmr_hashgrid_rows_backward.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
-    lib.dmr_last_error.restype = C.c_char_p
-    return lib
+    return declare(C.CDLL(_C.library_path()), ["dmr_hashgrid_rows", "dmr_hashgrid_rows_backward"])
 
 
 @pytest.mark.parametrize("i", range(len(HC.MISALIGNED)))
 def test_y_one_float_off_a_16_byte_boundary(hip_device, i):
-    """The same call with y, grad_out and dL_dx at base + 4 bytes: the forward bit-equal, the gradients within sum_order_tol."""
+    """The same call with y, grad_out and dL_dx at base + 4 bytes: the forward bit-equal, the gradients within sum_order_tol;
+    the words around the three buffers unchanged."""
     c, dev = HC.MISALIGNED[i], hip_device
     d, spec, lib = _inputs(c), _spec(c), _c_calls(hip_device)
     C_, stream = c.L * c.F, th.cuda.current_stream(dev).cuda_stream
@@ -142,9 +126,7 @@ def test_y_one_float_off_a_16_byte_boundary(hip_device, i):
     res = (C.c_int32 * c.L)(*spec.resolutions)
     outs = []
     for off in (0, 1):
-        ybuf, gbuf, dxbuf = (th.full((c.N * w + 1,), float("nan"), device=dev) for w in (C_, C_, 3))
-        y, g, dx = ybuf[off:off + c.N * C_], gbuf[off:off + c.N * C_], dxbuf[off:off + c.N * 3]
-        assert y.data_ptr() % 16 == 4 * off and g.data_ptr() % 16 == 4 * off
+        (ybuf, y), (gbuf, g), (dxbuf, dx) = (guarded(dev, c.N * w, off) for w in (C_, C_, 3))
         g.copy_(up.flatten())
         dt = th.full_like(table, float("nan"))
         with th.cuda.device(dev):
@@ -152,8 +134,7 @@ def test_y_one_float_off_a_16_byte_boundary(hip_device, i):
             assert lib.dmr_hashgrid_rows_backward(c.N, c.L, c.F, c.log2_T, res, x.data_ptr(), table.data_ptr(), None, g.data_ptr(), dx.data_ptr(),
                                                   dt.data_ptr(), stream) == 0, lib.dmr_last_error()
         th.cuda.synchronize()
-        spare = -1 if off == 0 else 0
-        assert bool(th.isnan(ybuf[spare])) and bool(th.isnan(dxbuf[spare]))   # the float beside the buffer is untouched
+        assert all(intact(buf, c.N * w, off) for buf, w in ((ybuf, C_), (gbuf, C_), (dxbuf, 3)))   # every sentinel word on both sides
         outs.append((y.cpu().numpy().reshape(c.N, C_), dx.cpu().numpy().reshape(c.N, 3), dt.cpu().numpy()))
     (y0, dx0, dt0), (y1, dx1, dt1) = outs
     e_x, e_t = rel_err(dx1, dx0), rel_err(dt1, dt0)
@@ -203,17 +184,14 @@ def test_n_rows_on_the_device(hip_device):
     and dL_dx, dL_dtable equal to the truncated call's."""
     c = HC.N_ROWS
     base = _inputs(c)
-    for n in (0, 130, c.N, c.N + 50, -7):
+    for n in n_rows_counts(c.N):
         m = min(max(n, 0), c.N)
         d = dict(base, x=base["x"].clone(), up=base["up"].clone(), up_x=base["up_x"].clone())
         d["x"][m:], d["up"][m:], d["up_x"][m:] = float("nan"), float("nan"), float("nan")
         got = _run(FG.hashgrid_rows_fused, c, d, hip_device, th.float32, n)
         clean = {k: (th.nan_to_num(v) if isinstance(v, th.Tensor) else v) for k, v in d.items()}
         ref = _run(FG.hashgrid_rows, c, clean, "cpu", th.float64, n)
-        for k in ref:
-            e = rel_err(got[k], ref[k])
-            print(f"\nn_rows {n} of {c.N}, {k}: {e:.2e}")
-            assert np.isfinite(got[k]).all() and e <= (FWD_TOL if k == "y" else GRAD_TOL), (n, k, e)
+        within_floors(f"n_rows {n} of {c.N},", ref, got, rel_err)
         assert float(np.abs(got["y"][m:]).sum()) == 0.0 and float(np.abs(got["x"][m:]).sum()) == 0.0
         assert m == 0 or (float(np.abs(got["y"][:m]).max()) > 0 and float(np.abs(got["x"][:m]).max()) > 0)
         if m == 0:
@@ -261,9 +239,7 @@ def test_no_upstream_launches_nothing(hip_device, monkeypatch):
     x, table = d["x"].to(hip_device).requires_grad_(True), d["table"].to(hip_device).requires_grad_(True)
     y = FG.hashgrid_rows_fused(x, table, spec)
     z = y * 1.0
-    calls = []
-    real = _C.hashgrid_rows_backward
-    monkeypatch.setattr(_C, "hashgrid_rows_backward", lambda *a, **k: calls.append(1) or real(*a, **k))
+    calls = counts_calls(monkeypatch, _C, "hashgrid_rows_backward")
     grads = th.autograd.grad((x * 3).sum(), [x, table], allow_unused=True)
     assert grads[1] is None and not calls
     assert FG._HashGridRowsFn.backward(y.grad_fn, None) == (None, None, None, None) and not calls

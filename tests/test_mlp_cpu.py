@@ -4,24 +4,18 @@ rows reaches nothing), RowMLP round-trips through nn.Sequential, the library exp
 declares and the build lists hold the new files, the functional layer and the C ABI refuse what the kernels do not take --
 before anything reaches a device, in their documented order -- and the case table of the GPU tests (tests/mlp_cases.py)
 reaches every kernel instantiation the unit compiles."""
-import ctypes as C
 import itertools
-import os
-import re
 
 import pytest
 import torch as th
 
 import mlp_cases as MC
+import row_units as RU
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
+from row_units import D
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_mlp.h")
-UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_mlp.hip")
-UNIT_TEXT = open(UNIT).read()
-COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (MC.COMMON_HEADER, MC.COMMON_SOURCE))
-HEADER_TEXT = open(HEADER).read()
+UNIT_TEXT, HEADER_TEXT = RU.unit_texts("dmr_mlp.hip", "dmesh_renderer_amd_mlp.h")
 FUNCTIONS = ["dmr_mlp_rows", "dmr_mlp_rows_backward"]
 TORCH_PATH = r"fragments\.mlp_rows is the torch path"
 
@@ -128,27 +122,12 @@ def test_row_mlp_round_trips():
 # ---------------------------------------------------------------------------
 # Library and build lists
 # ---------------------------------------------------------------------------
-def _declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-    return sorted(set(re.findall(r"\b(dmr_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_library_exports_the_declared_symbols():
-    from dmesh_renderer_amd import build
-    assert _declared_functions() == FUNCTIONS
-    lib = C.CDLL(build.build())
-    for n in FUNCTIONS:
-        assert hasattr(lib, n), f"{n} declared in the header but not exported"
+    RU.exports_declared(HEADER_TEXT, FUNCTIONS)
 
 
 def test_the_source_and_header_are_build_dependencies():
-    from dmesh_renderer_amd import build
-    assert "dmr_mlp.hip" in build.SOURCES and MC.COMMON_SOURCE in build.SOURCES and MC.COMMON_HEADER in build.HEADERS
-    assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
-    for deps in (build.HEADERS, build.GLUE_SOURCES):
-        assert any(os.path.basename(d) == "dmesh_renderer_amd_mlp.h" for d in deps)
-        assert all(os.path.exists(os.path.join(build.CSRC, d)) for d in deps)
-    assert "dmesh_renderer_amd_mlp.h" in build.__doc__
+    RU.are_build_dependencies("dmr_mlp.hip", "dmesh_renderer_amd_mlp.h")
 
 
 def test_binding_supports_it():
@@ -248,10 +227,9 @@ def test_refusals_in_their_documented_order():
 # Refusals of the C ABI, through ctypes with pointers that are never dereferenced (as tests/test_packed_cpu.py): every check
 # runs before any HIP call.  No call here has wholly valid arguments and an output to write: none reaches a launch.
 # ---------------------------------------------------------------------------
-D = C.c_void_p(16)  # non-null, never dereferenced on these paths
 INTS = "N Cin Hd Cout n_hidden act oact"
-PTRS = {"dmr_mlp_rows": "x W_in b_in W_mid b_mid W_out b_out n_rows y",
-        "dmr_mlp_rows_backward": "x W_in b_in W_mid b_mid W_out b_out n_rows grad_out dL_dx dL_dW_in dL_db_in dL_dW_mid dL_db_mid dL_dW_out dL_db_out scratch"}
+PTRS = {"dmr_mlp_rows": "x W_in b_in W_mid b_mid W_out b_out n_rows y",   # (scratch_floats: the int64 between scratch and the stream, 0 unless a case sets it)
+        "dmr_mlp_rows_backward": "x W_in b_in W_mid b_mid W_out b_out n_rows grad_out dL_dx dL_dW_in dL_db_in dL_dW_mid dL_db_mid dL_dW_out dL_db_out scratch scratch_floats"}
 SIZES = dict(N=1, Cin=3, Hd=16, Cout=3, n_hidden=2, act=0, oact=0)
 NULL_BY_DEFAULT = ("n_rows", "dL_dx", "dL_dW_in", "dL_db_in", "dL_dW_mid", "dL_db_mid", "dL_dW_out", "dL_db_out", "scratch")
 EVERY_CALL = {
@@ -284,36 +262,10 @@ PER_CALL = {
 }
 
 
-def _library():
-    import capi_ctypes
-    lib = capi_ctypes.load()
-    n = len(INTS.split())
-    lib.dmr_mlp_rows.restype = lib.dmr_mlp_rows_backward.restype = C.c_int
-    lib.dmr_mlp_rows.argtypes = [C.c_int] * n + [C.c_void_p] * (len(PTRS["dmr_mlp_rows"].split()) + 1)
-    lib.dmr_mlp_rows_backward.argtypes = [C.c_int] * n + [C.c_void_p] * len(PTRS["dmr_mlp_rows_backward"].split()) + [C.c_int64, C.c_void_p]
-    return lib
-
-
 def test_c_abi_refusals():
-    lib = _library()
+    import capi_ctypes
     assert "#define DMR_MLP_TABLE_FLOATS(Hd, n_hidden) (64 * (Hd) + (Hd) + ((n_hidden) == 2 ? (Hd) * (Hd) + (Hd) : 0) + 16 * (Hd) + 16)" in HEADER_TEXT
-    seen = set()
-    for call, ptrs in PTRS.items():
-        takes = INTS.split() + ptrs.split() + ["scratch_floats"]
-        for case, (changes, text) in list(EVERY_CALL.items()) + list(PER_CALL[call].items()):
-            assert all(k in takes for k in changes), (call, case)
-            args = [changes.get(n, SIZES[n]) for n in INTS.split()] + [changes.get(n, None if n in NULL_BY_DEFAULT else D) for n in ptrs.split()]
-            if call == "dmr_mlp_rows_backward":
-                args.append(changes.get("scratch_floats", 0))
-            args.append(None)   # stream
-            ret = getattr(lib, call)(*args)
-            got = lib.dmr_last_error().decode() if ret else ""
-            if text is None:
-                assert (ret, got) == (0, ""), (call, case, got)
-            else:
-                assert ret == 1 and got == f"{call}: {text}", (call, case, got)
-            seen.add((call, case))
-    assert len(seen) == 2 * len(EVERY_CALL) + sum(len(v) for v in PER_CALL.values())
+    RU.run_refusals(RU.declare(capi_ctypes.load(), FUNCTIONS), INTS, PTRS, SIZES, NULL_BY_DEFAULT, EVERY_CALL, PER_CALL, special=dict(scratch_floats=0))
 
 
 # ---------------------------------------------------------------------------
@@ -324,26 +276,15 @@ def _all_cases():
 
 
 def test_dispatch_restated_as_the_unit_has_it():
-    for line in MC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == 1 and COMMON_TEXT.count(line) == 0, line
-    for line in MC.COMMON_DISPATCH_LINES:
-        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
-    assert FILL_TEXT.count(MC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % MC.COMMON_HEADER in UNIT_TEXT
+    RU.dispatch_restated(MC, UNIT_TEXT, HEADER_TEXT, fills=False)   # (the kernels it launches are the ones every_instantiation lists)
     assert UNIT_TEXT.count("const bool narrow = p.Cout <= 4;") == 2   # (both kernels: the output loops' two widths)
-    for line in MC.HEADER_LINES:
-        assert HEADER_TEXT.count(line) == 1, line
     assert [MC.bwd_threads(hd, nh) for hd in MC.HIDDEN for nh in (1, 2)] == [256, 256, 256, 256, 256, 128]
     assert [MC.vec_of(c, a) for c, a in ((4, True), (4, False), (5, True), (64, True))] == [True, False, False, True]
     assert tuple(FG.MLP_HIDDEN) == MC.HIDDEN
-    # the kernels the unit launches are the ones every_instantiation lists
-    assert set(re.findall(r"\b(k_[a-z_]+)<[^<]*><<<", UNIT_TEXT)) == {k for k, _, _ in MC.every_instantiation()}
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT)
-    assert "hipMemsetAsync" not in code and "hipMalloc" not in code and "Synchronize" not in code
-    assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert "k_mlp_reduce<HD, NH><<<" in code and "asm" not in code
+    assert "k_mlp_reduce<HD, NH><<<" in RU.waits_for_nothing([UNIT_TEXT], fill_calls=0)   # (the partial sums' reduction is a kernel)
 
 
 def test_table_reaches_every_instantiation():

@@ -32,12 +32,11 @@ import mlp_cases as MC
 from dmesh_renderer_amd import fragments as FG
 from dmesh_renderer_amd import scenes
 from harness import TET_ARGS, TRI_ARGS, capture_replay, replay
+from row_units import FWD_TOL, GRAD_TOL, check, models, n_rows_counts, within_floors
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
 
-FWD_TOL = 1e-5
-GRAD_TOL = 1e-4
 KINK = 1e-5
 
 
@@ -84,23 +83,14 @@ def _run(f, c, d, device, dtype, n=None, x=None):
 
 @functools.lru_cache(maxsize=None)
 def _models(c, n=None):
-    """fragments.mlp_rows on the CPU in float64 and in float32 -> (reference, {name: the bound of the case})."""
-    d = _inputs(c)
-    ref, f32 = _run(FG.mlp_rows, c, d, "cpu", th.float64, n), _run(FG.mlp_rows, c, d, "cpu", th.float32, n)
-    bounds = {}
-    for k in ref:
-        yard = rel_err(f32[k], ref[k])
-        bounds[k] = (max(FWD_TOL if k == "y" else GRAD_TOL, 4 * yard), yard)
-    return ref, bounds
+    """fragments.mlp_rows on the CPU in float64 and in float32 -> (reference, {name: (the bound of the case, the yardstick)})."""
+    return models(_run, FG.mlp_rows, c, _inputs(c), n, rel_err)
 
 
 def _check(what, c, got, n=None):
     ref, bounds = _models(c, n)
-    for k in ref:
-        e, (bound, yard) = rel_err(got[k], ref[k]), bounds[k]
-        print(f"\n{what} {k}: {e:.2e} (float32 torch {yard:.2e}, bound {bound:.1e}, max |ref| {float(np.abs(ref[k]).max()) if ref[k].size else 0:.3g})")
-        assert got[k].shape == ref[k].shape and np.isfinite(got[k]).all() and e <= bound, (what, k, e)
-    return ref
+    assert set(got) == set(ref)
+    return check(what, ref, bounds, got, rel_err)
 
 
 @pytest.mark.parametrize("i", range(len(MC.TABLE)))
@@ -138,10 +128,7 @@ def test_a_dead_relu_unit(hip_device):
     d["bs"][0] = d["bs"][0].clone(); d["bs"][0][k] = 0
     got = _run(FG.mlp_rows_fused, c, d, hip_device, th.float32)
     ref = _run(FG.mlp_rows, c, d, "cpu", th.float64)
-    for name in ref:
-        e = rel_err(got[name], ref[name])
-        print(f"\ndead unit {name}: {e:.2e}")
-        assert e <= (FWD_TOL if name == "y" else GRAD_TOL)
+    within_floors("dead unit", ref, got, rel_err)
     assert float(np.abs(got["w0"][k]).max()) == 0.0 and float(got["b0"][k]) == 0.0 and float(np.abs(got["w1"][:, k]).max()) == 0.0
     assert float(np.abs(ref["w0"][k]).max()) == 0.0 and float(np.abs(got["w0"]).max()) > 0
 
@@ -152,16 +139,13 @@ def test_n_rows_on_the_device(hip_device, which):
     and dL_dx, weight and bias gradients equal to the model's on the first n rows -- and the same case without n_rows differs."""
     c = getattr(MC, which)
     base = _inputs(c)
-    for n in (0, 130, c.N, c.N + 50, -7):
+    for n in n_rows_counts(c.N):
         m = min(max(n, 0), c.N)
         d = dict(base, x=base["x"].clone(), up=base["up"].clone())
         d["x"][m:], d["up"][m:] = float("nan"), float("nan")
         got = _run(FG.mlp_rows_fused, c, d, hip_device, th.float32, n)
         ref = _run(FG.mlp_rows, c, dict(d, x=th.nan_to_num(d["x"]), up=th.nan_to_num(d["up"])), "cpu", th.float64, n)
-        for k in ref:
-            e = rel_err(got[k], ref[k])
-            print(f"\nn_rows {n} of {c.N}, {k}: {e:.2e}")
-            assert np.isfinite(got[k]).all() and e <= (FWD_TOL if k == "y" else GRAD_TOL), (n, k, e)
+        within_floors(f"n_rows {n} of {c.N},", ref, got, rel_err)
         assert float(np.abs(got["y"][m:]).sum()) == 0.0 and float(np.abs(got["x"][m:]).sum()) == 0.0
         assert m == 0 or (float(np.abs(got["y"][:m]).max()) > 0 and float(np.abs(got["x"][:m]).max()) > 0)
         if m == 0:

@@ -12,6 +12,7 @@ import pytest
 import torch as th
 
 import capi_ctypes
+from row_units import declare
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +23,7 @@ SIZES = [1, 255, 256, 257, CAP, CAP + 1, 2 * CAP + 54]
 
 
 def _library():
-    lib = capi_ctypes.load()
-    lib.dmr_packed_row_views.restype = lib.dmr_hashgrid_layout.restype = lib.dmr_hashgrid_rows_backward.restype = C.c_int
-    lib.dmr_packed_row_views.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3
-    lib.dmr_hashgrid_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.dmr_hashgrid_rows_backward.argtypes = [C.c_int] * 4 + [C.c_void_p] * 8
-    return lib
+    return declare(capi_ctypes.load(), ["dmr_packed_row_views", "dmr_hashgrid_layout", "dmr_hashgrid_rows_backward"])
 
 
 def _buffer(n):

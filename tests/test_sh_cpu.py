@@ -6,9 +6,7 @@ is a Python loop's result, camera_origins is a hand-built look-at camera's eye, 
 include/dmesh_renderer_amd_sh.h declares and the build lists hold the new files, the functional layer and the C ABI refuse what
 the kernels do not take -- before anything reaches a device, in their documented order -- and the case tables of the GPU tests
 (tests/sh_cases.py) reach every kernel instantiation the unit compiles."""
-import ctypes as C
 import math
-import os
 import re
 from types import SimpleNamespace
 
@@ -16,16 +14,13 @@ import numpy as np
 import pytest
 import torch as th
 
+import row_units as RU
 import sh_cases as SC
 import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
+from row_units import D
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dmesh_renderer_amd_sh.h")
-UNIT = os.path.join(ROOT, "dmesh_renderer_amd", "csrc", "dmr_sh.hip")
-UNIT_TEXT = open(UNIT).read()
-COMMON_TEXT, FILL_TEXT = (open(os.path.join(ROOT, "dmesh_renderer_amd", "csrc", f)).read() for f in (SC.COMMON_HEADER, SC.COMMON_SOURCE))
-HEADER_TEXT = open(HEADER).read()
+UNIT_TEXT, HEADER_TEXT = RU.unit_texts("dmr_sh.hip", "dmesh_renderer_amd_sh.h")
 FUNCTIONS = ["dmr_packed_row_views", "dmr_sh_rows", "dmr_sh_rows_backward"]
 TORCH_PATH = r"fragments\.sh_rows is the torch path"
 NAMES = ("packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH")
@@ -317,38 +312,12 @@ def test_module_on_cpu_rows():
 # ---------------------------------------------------------------------------
 # Library, binding and build lists
 # ---------------------------------------------------------------------------
-def _library():
-    import capi_ctypes
-    lib = capi_ctypes.load()
-    lib.dmr_packed_row_views.restype = lib.dmr_sh_rows.restype = lib.dmr_sh_rows_backward.restype = C.c_int
-    lib.dmr_packed_row_views.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3
-    lib.dmr_sh_rows.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6
-    lib.dmr_sh_rows_backward.argtypes = [C.c_int] * 3 + [C.c_void_p] * 8
-    return lib
-
-
-def _declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", HEADER_TEXT, flags=re.S)
-    return sorted(set(re.findall(r"\b(dmr_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_library_exports_the_declared_symbols():
-    from dmesh_renderer_amd import build
-    assert _declared_functions() == FUNCTIONS
-    lib = C.CDLL(build.build())
-    for n in FUNCTIONS:
-        assert hasattr(lib, n), f"{n} declared in the header but not exported"
+    RU.exports_declared(HEADER_TEXT, FUNCTIONS)
 
 
 def test_the_source_and_header_are_build_dependencies():
-    from dmesh_renderer_amd import build
-    assert "dmr_sh.hip" in build.SOURCES and "dmr_deferred_common.hpp" in build.HEADERS   # (RowPix, the packed unit's lanes)
-    assert SC.COMMON_SOURCE in build.SOURCES and SC.COMMON_HEADER in build.HEADERS
-    assert all(os.path.exists(os.path.join(build.CSRC, s)) for s in build.SOURCES)
-    for deps in (build.HEADERS, build.GLUE_SOURCES):
-        assert any(os.path.basename(d) == "dmesh_renderer_amd_sh.h" for d in deps)
-        assert all(os.path.exists(os.path.join(build.CSRC, d)) for d in deps)
-    assert "dmesh_renderer_amd_sh.h" in build.__doc__
+    RU.are_build_dependencies("dmr_sh.hip", "dmesh_renderer_amd_sh.h", extra=["dmr_deferred_common.hpp"])   # (RowPix, the packed unit's lanes)
 
 
 def test_binding_supports_it():
@@ -467,7 +436,6 @@ def test_refusals_in_their_documented_order():
 # Refusals of the C ABI, through ctypes with device pointers that are never dereferenced: every check runs before any HIP call.
 # No call here has wholly valid arguments and an output to write: none reaches a launch.
 # ---------------------------------------------------------------------------
-D = C.c_void_p(16)  # non-null, never dereferenced on these paths
 INTS = "N degree B"
 PTRS = {"dmr_sh_rows": "x origin row_view n_rows y", "dmr_sh_rows_backward": "x origin row_view n_rows grad_out dL_dx dL_dorigin"}
 SIZES = dict(N=1, degree=4, B=2)
@@ -505,23 +473,9 @@ VIEWS_CALL = [  # (B, K, H, W, N, row, view_out) -> text (None: returns 0 withou
 
 
 def test_c_abi_refusals():
-    lib = _library()
-    seen = set()
-    for call, ptrs in PTRS.items():
-        takes = INTS.split() + ptrs.split()
-        for case, (changes, text) in list(EVERY_CALL.items()) + list(PER_CALL[call].items()):
-            assert all(k in takes for k in changes), (call, case)
-            args = [changes.get(n, SIZES[n]) for n in INTS.split()]
-            args += [changes.get(n, None if n in NULL_BY_DEFAULT else D) for n in ptrs.split()]
-            args.append(None)   # stream
-            ret = getattr(lib, call)(*args)
-            got = lib.dmr_last_error().decode() if ret else ""
-            if text is None:
-                assert (ret, got) == (0, ""), (call, case, got)
-            else:
-                assert ret == 1 and got == f"{call}: {text}", (call, case, got)
-            seen.add((call, case))
-    assert len(seen) == 2 * len(EVERY_CALL) + sum(len(v) for v in PER_CALL.values())
+    import capi_ctypes
+    lib = RU.declare(capi_ctypes.load(), FUNCTIONS)
+    RU.run_refusals(lib, INTS, PTRS, SIZES, NULL_BY_DEFAULT, EVERY_CALL, PER_CALL)
     for args, text in VIEWS_CALL:
         ret = lib.dmr_packed_row_views(*args, None)
         got = lib.dmr_last_error().decode() if ret else ""
@@ -537,28 +491,14 @@ def test_c_abi_refusals():
 # The case tables of the GPU tests
 # ---------------------------------------------------------------------------
 def test_dispatch_restated_as_the_unit_has_it():
-    for line in SC.DISPATCH_LINES:
-        assert UNIT_TEXT.count(line) == (2 if line in SC.TWICE else 1) and COMMON_TEXT.count(line) == 0, line
-    for line in SC.COMMON_DISPATCH_LINES:
-        assert COMMON_TEXT.count(line) == 1 and UNIT_TEXT.count(line) == 0, line
-    assert FILL_TEXT.count(SC.FILL_LAUNCH_LINE) == 1 and '#include "%s"' % SC.COMMON_HEADER in UNIT_TEXT
-    for line in SC.HEADER_LINES:
-        assert HEADER_TEXT.count(line) == 1, line
+    product = RU.dispatch_restated(SC, UNIT_TEXT, HEADER_TEXT, twice=SC.TWICE)
     assert all(SC.via_lds(d) == (d >= 3) and not SC.loads_via_lds(d) for d in SC.DEGREES) and SC.DEGREES == tuple(range(1, FG.SH_MAX_DEGREE + 1))
-    # the kernels the unit launches are the ones every_instantiation lists; the product launches no <D, !L> shape
-    product = re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", UNIT_TEXT, flags=re.S)
-    launches = lambda text: set(re.findall(r"\b(k_[a-z_]+)(?:<[^<]*>)?<<<", text))
-    assert launches(FILL_TEXT) == {SC.FILL_KERNEL} and "rows_fill_on(st, " in product   # (the shared code's launch for this unit)
-    assert launches(product) | launches(FILL_TEXT) == {k for k, _ in SC.every_instantiation()}
+    # the kernels the product launches are the ones every_instantiation lists: no <D, !L> shape
     assert "!L>" not in product and "ablate_bits" not in product and "!L>" in UNIT_TEXT
 
 
 def test_the_unit_waits_for_nothing_and_zeroes_nothing_by_memset():
-    code = re.sub(r"//[^\n]*", "", re.sub(r"#ifdef DMR_ABLATION.*?#endif", "", COMMON_TEXT + FILL_TEXT + UNIT_TEXT, flags=re.S))
-    assert "hipMemset" not in code and "hipMalloc" not in code and "Synchronize" not in code and "hipMemcpy" not in code
-    assert "while (" not in code and "__builtin_amdgcn_s_sleep" not in code   # no spin on a flag
-    assert code.count("rows_fill_on(st, ") == 2 and SC.FILL_KERNEL + "<<<" in code and "asm" not in code
-    assert "zero_on(" not in code   # (what this unit fills, its own kernel fills)
+    RU.waits_for_nothing([UNIT_TEXT], fill_calls=2, extra_forbidden=["zero_on("])   # (dL_dorigin and view_out; nothing by the shading units' zero_on)
 
 
 def test_tables_reach_every_instantiation():

@@ -6,9 +6,9 @@ grid; B = 1, 2, 5; rows of one view, views changing inside a wave, exactly at wa
 gradients, the row-to-view map on the packed unit's shapes, the ray directions of rendered lists, the chain pack -> hit points
 -> HashGrid + ViewSH -> RowMLP -> blend on rendered lists, and a replayed HIP graph.
 
-Inputs: |x - origin[view]| in [0.5, 3], upstream ~ N(0,1).  Errors are max |got - ref| / max |ref| (_rel: relative to the
-largest entry).  Bounds (the project's own): y within max(FWD_TOL = 1e-5, 4 x the yardstick), gradients within max(GRAD_TOL =
-1e-4, 4 x the yardstick), the yardstick being fragments.sh_rows in float32 on the CPU against float64 on the same case; never
+Inputs: |x - origin[view]| in [0.5, 3], upstream ~ N(0,1).  Errors are max |got - ref| / max |ref| (_rel, which is
+row_units.rel_to_largest).  Bounds (the project's own): y within max(FWD_TOL = 1e-5, 4 x the yardstick), gradients within
+max(GRAD_TOL = 1e-4, 4 x the yardstick), the yardstick being fragments.sh_rows in float32 on the CPU against float64 on the same case; never
 anything the kernels gave.  Every case prints what it measured (pytest -s).
 
 MEASURED on the MI355X, the largest figure over the table's 32 cases (in brackets float32 torch on the CPU on the same cases, the
@@ -32,22 +32,14 @@ import dmesh_renderer_amd as dmr
 from dmesh_renderer_amd import fragments as FG
 from dmesh_renderer_amd import scenes
 from harness import TET_ARGS, TRI_ARGS, capture_replay, replay
+from row_units import FWD_TOL, GRAD_TOL, check, counts_calls, declare, guarded, intact, models, n_rows_counts, within_floors
+from row_units import rel_to_largest as _rel
 from tri_grad_ref import pixel_rays
 from util import rel_err, sum_order_tol
 
 pytestmark = pytest.mark.gpu
 
-FWD_TOL = 1e-5
-GRAD_TOL = 1e-4
 C0 = 0.28209479177387814
-
-
-def _rel(got, ref):
-    """max |got - ref| / max |ref| (max |got| where the reference is all zeros: such an output must be zeros)."""
-    if ref.size == 0:
-        return 0.0
-    top = float(np.abs(ref).max())
-    return float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max()) / (top if top > 0 else 1.0)
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,22 +69,11 @@ def _run(f, c, d, device, dtype, n=None, want=None):
 @functools.lru_cache(maxsize=None)
 def _models(c, n=None):
     """fragments.sh_rows on the CPU in float64 and in float32 -> (reference, {name: (the bound of the case, the yardstick)})."""
-    d = _inputs(c)
-    ref, f32 = _run(FG.sh_rows, c, d, "cpu", th.float64, n), _run(FG.sh_rows, c, d, "cpu", th.float32, n)
-    bounds = {}
-    for k in ref:
-        yard = _rel(f32[k], ref[k])
-        bounds[k] = (max(FWD_TOL if k == "y" else GRAD_TOL, 4 * yard), yard)
-    return ref, bounds
+    return models(_run, FG.sh_rows, c, _inputs(c), n, _rel)
 
 
 def _check(what, c, got, n=None):
-    ref, bounds = _models(c, n)
-    for k in got:
-        e, (bound, yard) = _rel(got[k], ref[k]), bounds[k]
-        print(f"\n{what} {k}: {e:.2e} (float32 torch {yard:.2e}, bound {bound:.1e}, max |ref| {float(np.abs(ref[k]).max()) if ref[k].size else 0:.3g})")
-        assert got[k].shape == ref[k].shape and np.isfinite(got[k]).all() and e <= bound, (what, k, e)
-    return ref
+    return check(what, *_models(c, n), got, _rel)
 
 
 @pytest.mark.parametrize("i", range(len(SC.TABLE)))
@@ -118,17 +99,13 @@ def test_table(hip_device, i):
 # ---------------------------------------------------------------------------
 def _c_calls():
     from dmesh_renderer_amd import _C
-    lib = C.CDLL(_C.library_path())
-    lib.dmr_sh_rows.restype = lib.dmr_sh_rows_backward.restype = C.c_int
-    lib.dmr_sh_rows.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6
-    lib.dmr_sh_rows_backward.argtypes = [C.c_int] * 3 + [C.c_void_p] * 8
-    lib.dmr_last_error.restype = C.c_char_p
-    return lib
+    return declare(C.CDLL(_C.library_path()), ["dmr_sh_rows", "dmr_sh_rows_backward"])
 
 
 @pytest.mark.parametrize("i", range(len(SC.MISALIGNED)))
 def test_one_float_off_a_16_byte_boundary(hip_device, i):
-    """The same call with x, y, grad_out and dL_dx at base + 4 bytes: y and dL_dx bit-equal, dL_dorigin within sum_order_tol."""
+    """The same call with x, y, grad_out and dL_dx at base + 4 bytes: y and dL_dx bit-equal, dL_dorigin within sum_order_tol;
+    the words around the four buffers unchanged."""
     c, dev = SC.MISALIGNED[i], hip_device
     d, lib = _inputs(c), _c_calls()
     C_, stream = c.degree ** 2, th.cuda.current_stream(dev).cuda_stream
@@ -136,9 +113,7 @@ def test_one_float_off_a_16_byte_boundary(hip_device, i):
     view = d["view"].to(dev) if c.form == "views" else None
     outs = []
     for off in (0, 1):
-        xbuf, ybuf, gbuf, dxbuf = (th.full((c.N * w + 1,), float("nan"), device=dev) for w in (3, C_, C_, 3))
-        x, y, g, dx = xbuf[off:off + c.N * 3], ybuf[off:off + c.N * C_], gbuf[off:off + c.N * C_], dxbuf[off:off + c.N * 3]
-        assert x.data_ptr() % 16 == 4 * off and y.data_ptr() % 16 == 4 * off and g.data_ptr() % 16 == 4 * off
+        (xbuf, x), (ybuf, y), (gbuf, g), (dxbuf, dx) = (guarded(dev, c.N * w, off) for w in (3, C_, C_, 3))
         x.copy_(d["x"].to(dev).flatten())
         g.copy_(up.flatten())
         do = th.full_like(origin, float("nan"))
@@ -148,8 +123,7 @@ def test_one_float_off_a_16_byte_boundary(hip_device, i):
             assert lib.dmr_sh_rows_backward(c.N, c.degree, c.B, x.data_ptr(), origin.data_ptr(), vp, None, g.data_ptr(), dx.data_ptr(),
                                             do.data_ptr(), stream) == 0, lib.dmr_last_error()
         th.cuda.synchronize()
-        spare = -1 if off == 0 else 0
-        assert bool(th.isnan(ybuf[spare])) and bool(th.isnan(dxbuf[spare]))   # the float beside the buffer is untouched
+        assert all(intact(buf, c.N * w, off) for buf, w in ((xbuf, 3), (ybuf, C_), (gbuf, C_), (dxbuf, 3)))   # every sentinel word on both sides
         outs.append((y.cpu().numpy().reshape(c.N, C_), dx.cpu().numpy().reshape(c.N, 3), do.cpu().numpy()))
     (y0, dx0, do0), (y1, dx1, do1) = outs
     e_o = _rel(do1, do0)
@@ -206,17 +180,14 @@ def test_n_rows_on_the_device(hip_device):
     and dL_dx, dL_dorigin the model's."""
     c = SC.N_ROWS
     base = _inputs(c)
-    for n in (0, 130, c.N, c.N + 50, -7):
+    for n in n_rows_counts(c.N):
         m = min(max(n, 0), c.N)
         d = dict(base, x=base["x"].clone(), up=base["up"].clone())
         d["x"][m:], d["up"][m:] = float("nan"), float("nan")
         got = _run(FG.sh_rows_fused, c, d, hip_device, th.float32, n)
         clean = {k: (th.nan_to_num(v) if v.dtype.is_floating_point else v) for k, v in d.items()}
         ref = _run(FG.sh_rows, c, clean, "cpu", th.float64, n)
-        for k in ref:
-            e = _rel(got[k], ref[k])
-            print(f"\nn_rows {n} of {c.N}, {k}: {e:.2e}")
-            assert np.isfinite(got[k]).all() and e <= (FWD_TOL if k == "y" else GRAD_TOL), (n, k, e)
+        within_floors(f"n_rows {n} of {c.N},", ref, got, _rel)
         assert float(np.abs(got["y"][m:]).sum()) == 0.0 and float(np.abs(got["x"][m:]).sum()) == 0.0
         if m == 0:
             assert all(float(np.abs(got[k]).max()) == 0.0 for k in got)
@@ -253,9 +224,7 @@ def test_no_upstream_launches_nothing(hip_device, monkeypatch):
     x, origin = d["x"].to(hip_device).requires_grad_(True), d["origin"].to(hip_device).requires_grad_(True)
     y = FG.sh_rows_fused(x, c.degree, origin=origin, row_view=d["view"].to(hip_device))
     z = y * 1.0
-    calls = []
-    real = _C.sh_rows_backward
-    monkeypatch.setattr(_C, "sh_rows_backward", lambda *a, **k: calls.append(1) or real(*a, **k))
+    calls = counts_calls(monkeypatch, _C, "sh_rows_backward")
     grads = th.autograd.grad((x * 3).sum(), [x, origin], allow_unused=True)
     assert grads[1] is None and not calls
     assert FG._ShRowsFn.backward(y.grad_fn, None) == (None, None, None, None, None) and not calls
