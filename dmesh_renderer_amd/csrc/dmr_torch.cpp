@@ -66,6 +66,10 @@
 //   envmap_rows(d [N,3], envmap [He,We,C], n_rows=None) -> y [N,C] and envmap_rows_backward(..., grad_out, need_d, need_envmap)
 //   -> (dL_dd | None, dL_denvmap | None): direction rows looked up in a lat-long environment map (fragments.envmap_rows_fused),
 //   over include/dmesh_renderer_amd_envmap.h (SUPPORTS_FRAGMENT_ENVMAP)
+//   surface_packed(face, bary, row, n_used, faces, verts [P,3], origin [B,3], N) -> (hit, normal, reflect) [N,3] and
+//   surface_packed_backward(..., grad_hit, grad_normal, grad_reflect (None = zero), need=(verts, bary, origin)) -> those three
+//   gradients or None: the surface frame of packed rows (fragments.surface_packed_fused), over
+//   include/dmesh_renderer_amd_surface.h (SUPPORTS_FRAGMENT_SURFACE)
 //   set_async(True)          calls never wait for the device (DMR_FLAG_ASYNC; automatic under stream capture):
 //                            `num_rendered` is then the capacity used, overflowed() reports a scene that outgrew it
 #include <torch/extension.h>
@@ -93,6 +97,7 @@
 #include "../../include/dmesh_renderer_amd_hashgrid.h"
 #include "../../include/dmesh_renderer_amd_sh.h"
 #include "../../include/dmesh_renderer_amd_envmap.h"
+#include "../../include/dmesh_renderer_amd_surface.h"
 
 namespace {
 
@@ -152,6 +157,9 @@ struct Abi {
     // dmesh_renderer_amd_envmap.h: optional too (SUPPORTS_FRAGMENT_ENVMAP), both or none
     decltype(&dmr_envmap_rows) envmap_rows = nullptr;
     decltype(&dmr_envmap_rows_backward) envmap_rows_backward = nullptr;
+    // dmesh_renderer_amd_surface.h: optional too (SUPPORTS_FRAGMENT_SURFACE), both or none
+    decltype(&dmr_surface_packed) surface_packed = nullptr;
+    decltype(&dmr_surface_packed_backward) surface_packed_backward = nullptr;
 };
 
 Abi g_abi;
@@ -238,6 +246,9 @@ void load_abi() {
     g_abi.envmap_rows = reinterpret_cast<decltype(g_abi.envmap_rows)>(dlsym(g_abi.handle, "dmr_envmap_rows"));
     g_abi.envmap_rows_backward = reinterpret_cast<decltype(g_abi.envmap_rows_backward)>(dlsym(g_abi.handle, "dmr_envmap_rows_backward"));
     if (!g_abi.envmap_rows || !g_abi.envmap_rows_backward) g_abi.envmap_rows = nullptr, g_abi.envmap_rows_backward = nullptr;
+    g_abi.surface_packed = reinterpret_cast<decltype(g_abi.surface_packed)>(dlsym(g_abi.handle, "dmr_surface_packed"));
+    g_abi.surface_packed_backward = reinterpret_cast<decltype(g_abi.surface_packed_backward)>(dlsym(g_abi.handle, "dmr_surface_packed_backward"));
+    if (!g_abi.surface_packed || !g_abi.surface_packed_backward) g_abi.surface_packed = nullptr, g_abi.surface_packed_backward = nullptr;
     if (g_abi.abi_version() != DMR_ABI_VERSION)
         throw std::runtime_error("ABI mismatch: " + path + " is version " + std::to_string(g_abi.abi_version()) +
                                  ", the binding expects " + std::to_string(DMR_ABI_VERSION));
@@ -1199,6 +1210,69 @@ py::tuple composite_values_packed_backward(In face, In row, In n_used, In faces_
     return py::make_tuple(or_none(d_op), or_none(d_values), or_none(d_scale));
 }
 
+// -- surface_packed: the surface frame of packed rows (dmesh_renderer_amd_surface.h).  The interpolate_packed argument block with
+// attrs = verts [P,3], and origin [B,3]: one camera centre per view of the lists; its own builder, so that every message names
+// this call and its tensors.
+struct SurfaceArgs : PackedInterpArgs { at::Tensor origin; };
+
+SurfaceArgs surface_args(In face, In bary, In row, In n_used, In faces, In verts, In origin, int64_t N) {
+    built(g_abi.surface_packed, "dmr_surface_packed");
+    SurfaceArgs a;
+    packed_lists(a, a, "surface_packed", face, &row, &n_used);
+    check_bary(a, bary);
+    a.F = check_corners(faces, "faces");
+    if (verts.dim() != 2 || verts.size(1) != 3) err("verts must have dimensions (num_points, 3)");
+    if (origin.dim() != 2 || origin.size(0) != a.B || origin.size(1) != 3) err("origin must have dimensions (B, 3) of pix_to_face's B");
+    a.P = verts.size(0); a.C = 3; a.N = N;
+    check_rows(a, N);
+    same_device(a, bary, "bary"); same_device(a, faces, "faces"); same_device(a, verts, "verts"); same_device(a, origin, "origin");
+    a.bary = f32(bary, "bary"); a.faces = i32(faces, "faces"); a.attrs = f32(verts, "verts"); a.origin = f32(origin, "origin");
+    return a;
+}
+
+// -> (hit, normal, reflect), each [N,3]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> surface_packed(In face, In bary, In row, In n_used, In faces, In verts, In origin, int64_t N) {
+    const SurfaceArgs a = surface_args(face, bary, row, n_used, faces, verts, origin, N);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor hit = at::empty({a.N, 3}, f32_on(a.dev)), normal = at::empty({a.N, 3}, f32_on(a.dev)), reflect = at::empty({a.N, 3}, f32_on(a.dev));
+    if (g_abi.surface_packed(a.B, a.K, a.H, a.W, a.P, a.F, a.N, mptr<const int32_t>(a.face), mptr<const float>(a.bary), mptr<const int32_t>(a.row),
+                             mptr<const int32_t>(a.n_used), mptr<const int32_t>(a.faces), mptr<const float>(a.attrs), mptr<const float>(a.origin),
+                             mptr<float>(hit), mptr<float>(normal), mptr<float>(reflect), a.stream()))
+        raise_lib();
+    return {hit, normal, reflect};
+}
+
+// need = (verts, bary, origin) -> those three gradients, None where not asked for; grad_hit / grad_normal / grad_reflect [N,3]:
+// None = zero (N: the rows of those that arrive, which must agree)
+py::tuple surface_packed_backward(In face, In bary, In row, In n_used, In faces, In verts, In origin, const std::optional<at::Tensor>& grad_hit,
+                                  const std::optional<at::Tensor>& grad_normal, const std::optional<at::Tensor>& grad_reflect,
+                                  const std::array<bool, 3>& need) {
+    int64_t N = -1;
+    for (const auto* g : {&grad_hit, &grad_normal, &grad_reflect}) {
+        if (!*g) continue;
+        if ((*g)->dim() != 2 || (*g)->size(1) != 3 || (N >= 0 && (*g)->size(0) != N)) err("the upstream gradients must have dimensions (rows, 3), the same rows");
+        N = (*g)->size(0);
+    }
+    if (N < 0) err("surface_packed_backward: no upstream gradient");
+    const SurfaceArgs a = surface_args(face, bary, row, n_used, faces, verts, origin, N);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor gs[3];
+    const std::optional<at::Tensor>* in[3] = {&grad_hit, &grad_normal, &grad_reflect};
+    for (int i = 0; i < 3; i++) {
+        if (!*in[i]) continue;
+        same_device(a, **in[i], "an upstream gradient");
+        gs[i] = f32(**in[i], "an upstream gradient");
+    }
+    at::Tensor d_verts = grad_if(need[0], {a.P, 3}, a.dev), d_bary = grad_if(need[1], {a.B, a.K, 2, a.H, a.W}, a.dev);
+    at::Tensor d_origin = grad_if(need[2], {a.B, 3}, a.dev);
+    if (g_abi.surface_packed_backward(a.B, a.K, a.H, a.W, a.P, a.F, a.N, mptr<const int32_t>(a.face), mptr<const float>(a.bary),
+                                      mptr<const int32_t>(a.row), mptr<const int32_t>(a.n_used), mptr<const int32_t>(a.faces),
+                                      mptr<const float>(a.attrs), mptr<const float>(a.origin), in_ptr(gs[0]), in_ptr(gs[1]), in_ptr(gs[2]),
+                                      out_ptr(d_verts), out_ptr(d_bary), out_ptr(d_origin), a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(d_verts), or_none(d_bary), or_none(d_origin));
+}
+
 // -- The row units (mlp_rows, hashgrid_rows, sh_rows, envmap_rows) start from x [N,C] on a HIP device and an optional count n_rows [1]: RowArgs.
 // A unit's argument block extends it, and its builder calls the named checks below in the unit's order, which is fragments.py's:
 // shapes, sizes, one device, dtypes.
@@ -1601,6 +1675,11 @@ PYBIND11_MODULE(_C, m) {
     m.def("envmap_rows", &envmap_rows, py::arg("d"), py::arg("envmap"), py::arg("n_rows") = py::none());
     m.def("envmap_rows_backward", &envmap_rows_backward, py::arg("d"), py::arg("envmap"), py::arg("n_rows"), py::arg("grad_out"), py::arg("need_d"),
           py::arg("need_envmap"));
+    m.def("surface_packed", &surface_packed, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"), py::arg("faces"), py::arg("verts"),
+          py::arg("origin"), py::arg("rows"));
+    m.def("surface_packed_backward", &surface_packed_backward, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"), py::arg("faces"),
+          py::arg("verts"), py::arg("origin"), py::arg("grad_hit"), py::arg("grad_normal"), py::arg("grad_reflect"),
+          py::arg("need") = std::array<bool, 3>{true, true, true});
     m.def("export", &export_item, py::arg("name"), py::arg("call_args"), py::arg("is_tet"), py::arg("num_rendered"), py::arg("buffers"),
           py::arg("H"), py::arg("W"), py::arg("dtype"));
     // asynchronous calls (include/dmesh_renderer_amd.h, "Sizes only the device knows")
@@ -1642,6 +1721,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_SH") = g_abi.sh_rows != nullptr;
     // fragments.envmap_rows_fused; False: the loaded library predates dmesh_renderer_amd_envmap.h
     m.attr("SUPPORTS_FRAGMENT_ENVMAP") = g_abi.envmap_rows != nullptr;
+    // fragments.surface_packed_fused; False: the loaded library predates dmesh_renderer_amd_surface.h
+    m.attr("SUPPORTS_FRAGMENT_SURFACE") = g_abi.surface_packed != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;
     m.attr("STAGE_SCAN") = (int)DMR_STAGE_SCAN; m.attr("STAGE_SCATTER") = (int)DMR_STAGE_SCATTER; m.attr("STAGE_SORT") = (int)DMR_STAGE_SORT;
     m.attr("STAGE_TRI_FORWARD") = (int)DMR_STAGE_TRI_FORWARD; m.attr("STAGE_TRI_BACKWARD") = (int)DMR_STAGE_TRI_BACKWARD;

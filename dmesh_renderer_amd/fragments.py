@@ -50,7 +50,15 @@ renderer's own convention (plain torch, differentiable to both matrices):
     dirs = FG.pixel_directions(mv_mats, proj_mats, H, W)                 # [B,H,W,3]
     bg   = env(dirs.reshape(-1, 3)).view(B, H, W, 3).permute(0, 3, 1, 2)
     color = image + T * bg                                               # image, T from any composite_* call (or 1 - alpha)
-Fed a reflected or view direction per packed row (env(d, n_rows=n)) the same lookup is the cheapest specular term.
+Fed a reflected or view direction per packed row (env(d, n_rows=n)) the same lookup is the cheapest specular term;
+surface_packed_fused makes that direction.
+THE SURFACE FRAME of every packed row -- the hit point, the unit geometric normal of its face turned towards the camera (these
+meshes have no consistent winding) and the view ray mirrored at it -- is what an n.l term, a specular lookup, a Ref-NeRF-style
+encoding or a normal loss start from.  surface_packed is the torch model, surface_packed_fused (csrc/dmr_surface.hip) the same as
+one forward and one backward kernel, differentiable in verts, frag.bary and the camera centres; a slot's view is its b:
+    s = FG.surface_packed_fused(frag, packed, faces, verts, FG.camera_origins(mv_mats))       # SurfaceRows(hit, normal, reflect), each [N,3]
+    enc = th.cat([grid(s.hit, n_rows=n), FG.sh_rows_fused(s.reflect, 4, n_rows=n), s.normal], 1)
+    rgb = mlp(enc, n_rows=n) + env(s.reflect, n_rows=n)                                       # diffuse + specular lookup
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -90,7 +98,7 @@ __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "comp
            "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP",
            "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid",
            "packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH",
-           "envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions"]
+           "envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions", "SurfaceRows", "surface_packed", "surface_packed_fused"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -233,7 +241,8 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "hashgrid_rows": ("SUPPORTS_FRAGMENT_HASHGRID", "row", "hash-grid encoding"),
           "packed_row_views": ("SUPPORTS_FRAGMENT_SH", "packed row", "view map"),
           "sh_rows": ("SUPPORTS_FRAGMENT_SH", "row", "spherical-harmonics encoding"),
-          "envmap_rows": ("SUPPORTS_FRAGMENT_ENVMAP", "row", "environment-map lookup")}
+          "envmap_rows": ("SUPPORTS_FRAGMENT_ENVMAP", "row", "environment-map lookup"),
+          "surface_packed": ("SUPPORTS_FRAGMENT_SURFACE", "packed row", "surface frame")}
 
 
 def _fused_kernels(torch_path: str):
@@ -1536,3 +1545,121 @@ def pixel_directions(mv_mats: th.Tensor, proj_mats: th.Tensor, H: int, W: int) -
     pv = th.einsum("bij,hwj->bhwi", ip, ndc)                                        # [B,H,W,4]
     w = th.einsum("bij,bhwj->bhwi", im[:, :3, :3], pv[..., :3])                     # (+ the centre, - the centre)
     return w / (th.sqrt((w * w).sum(-1, keepdim=True)) + 1e-7)
+
+
+# ---------------------------------------------------------------------------
+# The surface frame of packed rows: hit point, geometric normal towards the camera, mirrored view ray (csrc/dmr_surface.hip)
+# ---------------------------------------------------------------------------
+SURFACE_MIN_AREA = 1e-20    # a face whose |e1 x e2| is smaller (or not finite) is degenerate: normal 0
+SURFACE_MIN_LENGTH = 1e-8   # SH_MIN_LENGTH: a shorter (or non-finite) |hit - origin| gives the zero direction
+
+
+class SurfaceRows(NamedTuple):
+    """What surface_packed / surface_packed_fused return: three row tensors [N,3], N = packed.rows."""
+    hit: th.Tensor       # the point of the face the slot's ray meets: interpolate_packed(frag, packed, faces, verts)
+    normal: th.Tensor    # the unit geometric normal of the face, turned towards the camera; 0 on a degenerate face
+    reflect: th.Tensor   # the view direction mirrored at the face: unit length; the view direction itself on a degenerate face
+
+
+def _unit_or_zero(x: th.Tensor, least: float) -> Tuple[th.Tensor, th.Tensor]:
+    """(x / |x| along the last axis, ok) -- zeros, and an exact 0 gradient, where |x| is not finite or below `least`."""
+    n = th.sqrt((x.detach() * x.detach()).sum(-1))
+    ok = (th.isfinite(n) & ~(n < least)).unsqueeze(-1)
+    unit = th.zeros(3, dtype=x.dtype, device=x.device)
+    unit[2] = 1
+    safe = th.where(ok, x, unit)     # (what is not ok leaves here: its gradient is an exact 0)
+    return th.where(ok, safe / th.sqrt((safe * safe).sum(-1, keepdim=True)), th.zeros((), dtype=x.dtype, device=x.device)), ok
+
+
+def _check_surface(name: str, frag, packed, faces, verts, origin) -> int:
+    """The shapes surface_packed and surface_packed_fused both refuse (ValueError) -> packed.rows."""
+    B, K, H, W = _check_lists(name, frag, True)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{name}: faces must be [F,3], got {tuple(faces.shape)}")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"{name}: verts must be [P,3], got {tuple(verts.shape)}")
+    if tuple(origin.shape) != (B, 3):
+        raise ValueError(f"{name}: origin must be [B,3] = {(B, 3)}, one camera centre per view of the lists, got {tuple(origin.shape)}")
+    return _check_packed(name, "fragments.surface_packed is the torch path for anything else", frag, packed)
+
+
+def surface_packed(frag, packed: PackedSlots, faces: th.Tensor, verts: th.Tensor, origin: th.Tensor) -> SurfaceRows:
+    """The surface frame of every packed row -> SurfaceRows(hit, normal, reflect), each [N,3], N = packed.rows.  faces [F,3], verts
+    [P,3], origin [B,3]: one camera centre per view of the lists (camera_origins(mv_mats)).  For a slot (b, k, y, x) that counts
+    (0 <= row < N and a face id in [0, F)) with p0, p1, p2 the vertices of its face and (u, v) its barycentrics, in verts' dtype:
+        h = (1 - u - v) p0 + u p1 + v p2                      == interpolate_packed(frag, packed, faces, verts)
+        g = (p1 - p0) x (p2 - p0), a = |g|, m = g / a         m = 0 if a is not finite or a < 1e-20 (a degenerate face)
+        w = h - origin[b], d = w / |w|                        d = 0 if |w| is not finite or |w| < 1e-8 (sh_rows' rule)
+        s = m . d
+        normal = m if s <= 0 else -m                          towards the camera: normal . d <= 0, whatever the face's winding
+        reflect = d - 2 s m                                   unit length; d on a degenerate face, 0 where d = 0
+    at row[b, k, y, x]; every other row is 0 (and so are the three rows of a slot whose face holds a vertex index outside [0, P)).
+    The sign of the normal is a constant of every gradient.  Differentiable in verts (through the hit point and, unless the face is
+    degenerate, through the normal), in frag.bary when the renderer's fragment_grads made it differentiable, and in origin.
+    Plain torch, any device, any float dtype: the model surface_packed_fused is tested against."""
+    rows = _check_surface("surface_packed", frag, packed, faces, verts, origin)
+    F, P = faces.shape[0], verts.shape[0]
+    B = frag.pix_to_face.shape[0]
+    zero = th.zeros((), dtype=verts.dtype, device=verts.device)
+    live = _counting(frag, packed, F)
+    out = [verts.new_zeros(rows, 3) for _ in range(3)]
+    if F == 0 or P == 0:   # no slot counts, or no face has its vertices
+        return SurfaceRows(*out)
+    vid = faces.long()[frag.pix_to_face.clamp(0, F - 1).long()[live]]                    # [n,3]
+    inside = ((vid >= 0) & (vid < P)).all(1)
+    p = verts[vid.clamp(0, P - 1)]                                                       # [n,3,3]
+    bary = frag.bary.to(verts.dtype).permute(0, 1, 3, 4, 2)[live]                        # [n,2]
+    u, v = bary[:, :1], bary[:, 1:]
+    h = (1 - u - v) * p[:, 0] + u * p[:, 1] + v * p[:, 2]
+    m, _ = _unit_or_zero(th.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), SURFACE_MIN_AREA)
+    view = th.arange(B, device=live.device).view(B, 1, 1, 1).expand_as(live)[live]
+    d, _ = _unit_or_zero(h - origin.to(verts.dtype)[view], SURFACE_MIN_LENGTH)
+    s = (m * d).sum(1, keepdim=True)
+    normal = th.where(s.detach() <= 0, m, -m)
+    reflect = d - 2 * s * m
+    at = (packed.row[live].long(),)
+    return SurfaceRows(*(o.index_put(at, th.where(inside.unsqueeze(1), x, zero)) for o, x in zip(out, (h, normal, reflect))))
+
+
+class _SurfacePackedFn(th.autograd.Function):
+    """surface_packed_fused over _C.surface_packed / _C.surface_packed_backward.  Arguments: pix_to_face, bary, row, n_used, faces,
+    verts, origin, rows.  Only those tensors are saved: the backward recomputes the frame."""
+
+    @staticmethod
+    def forward(ctx, face, bary, row, n_used, faces, verts, origin, rows):
+        out = _fused_kernels("surface_packed").surface_packed(face, bary, row, n_used, faces, verts, origin, rows)
+        ctx.save_for_backward(face, bary, row, n_used, faces, verts, origin)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as a null pointer: no zeros
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_hit, grad_normal, grad_reflect):
+        need = (ctx.needs_input_grad[5], ctx.needs_input_grad[1], ctx.needs_input_grad[6])  # (verts, bary, origin)
+        ups = [None if g is None else g.contiguous() for g in (grad_hit, grad_normal, grad_reflect)]
+        if all(g is None for g in ups) or not any(need):
+            return (None,) * 8
+        d_verts, d_bary, d_origin = _fused_kernels("surface_packed").surface_packed_backward(*ctx.saved_tensors, *ups, need)
+        return None, d_bary, None, None, None, d_verts, d_origin, None
+
+
+def surface_packed_fused(frag, packed: PackedSlots, faces: th.Tensor, verts: th.Tensor, origin: th.Tensor) -> SurfaceRows:
+    """surface_packed(...) as one HIP kernel, and one for its backward (plus the one that zeroes dL_dverts and dL_dorigin): the same
+    SurfaceRows(hit, normal, reflect), each [N,3]; hit equals interpolate_packed_fused(frag, packed, faces, verts) bit for bit.  The
+    forward reads a face's three vertices once per counting slot and stores three 12-byte rows per lane; the backward merges the
+    nine vertex-gradient floats of a wave's lanes of equal face, sums them per tile in an LDS table of f64 cells keyed by vertex
+    and sums dL_dorigin per wave and per workgroup before at most three float atomics leave -- so dL_dverts and dL_dorigin depend
+    on the order of summation in their last bits; the three outputs and dL_dbary do not.  A slot counts only if 0 <= row < N and
+    its face id lies in [0, F): a `packed` made for another F or capacity stays in bounds; a face with a vertex index outside
+    [0, P) gives three rows of zeros; rows [min(n_used, N), N) are exact zeros (the count is read on the device: no host wait,
+    capturable).  Each gradient (verts, frag.bary, origin) is computed only when autograd asks for it, and an output the loss does
+    not use sends no upstream down; dL_dbary is an exact 0 in slots that do not count.  N == 0 gives three empty [0,3] tensors
+    without a launch.  K <= 32, origin [B,3] (ValueError).  HIP float32 / int32 tensors on one device only: anything else is a
+    TypeError -- surface_packed is the torch path for it; nothing falls back silently."""
+    name, torch_path = "surface_packed_fused", "fragments.surface_packed is the torch path for anything else"
+    _fused_kernels("surface_packed")
+    rows = _check_surface(name, frag, packed, faces, verts, origin)
+    ints = [("faces", faces), ("packed.row", packed.row), ("packed.n_used", packed.n_used)]
+    _check_tensors(name, torch_path, frag.pix_to_face, ints, [("frag.bary", frag.bary), ("verts", verts), ("origin", origin)])
+    if rows == 0:
+        return SurfaceRows(*(verts.new_zeros((0, 3)) for _ in range(3)))
+    return SurfaceRows(*_SurfacePackedFn.apply(frag.pix_to_face, frag.bary, packed.row, packed.n_used, faces.to(th.int32), verts, origin, rows))
