@@ -3,7 +3,8 @@
   * libdmesh_renderer_hip.so -- the C ABI (include/dmesh_renderer_amd.h, dmesh_renderer_amd_shade.h, dmesh_renderer_amd_texture.h,
                                 dmesh_renderer_amd_visibility.h, dmesh_renderer_amd_deferred.h, dmesh_renderer_amd_packed.h,
                                 dmesh_renderer_amd_mlp.h, dmesh_renderer_amd_hashgrid.h, dmesh_renderer_amd_sh.h,
-                                dmesh_renderer_amd_envmap.h, dmesh_renderer_amd_surface.h) and every gfx950 kernel, with hipcc;
+                                dmesh_renderer_amd_envmap.h, dmesh_renderer_amd_envmap_lod.h, dmesh_renderer_amd_surface.h) and every
+                                gfx950 kernel, with hipcc;
   * _C.<python ext suffix>   -- `dmesh_renderer_amd._C`, the compiled PyTorch-ROCm binding over that C ABI
                                 (csrc/dmr_torch.cpp: pybind11 + ATen, no kernels), with g++.
 
@@ -33,13 +34,13 @@ LIB = os.path.join(HERE, "libdmesh_renderer_hip.so")
 LIB_ABLATION = os.path.join(HERE, "libdmesh_renderer_hip_ablation.so")
 SOURCES = ["dmr_api.hip", "dmr_binning.hip", "dmr_tri.hip", "dmr_tet.hip", "dmr_shade.hip", "dmr_texture.hip", "dmr_visibility.hip",
            "dmr_interp.hip", "dmr_packed.hip", "dmr_rows_common.hip", "dmr_mlp.hip", "dmr_hashgrid.hip", "dmr_sh.hip", "dmr_envmap.hip",
-           "dmr_surface.hip"]
+           "dmr_envmap_lod.hip", "dmr_surface.hip"]
 PUBLIC_HEADERS = [os.path.join("..", "..", "include", h + ".h") for h in (  # THE list of them (the docstring names them too)
     "dmesh_renderer_amd", "dmesh_renderer_amd_shade", "dmesh_renderer_amd_texture", "dmesh_renderer_amd_visibility", "dmesh_renderer_amd_deferred",
     "dmesh_renderer_amd_packed", "dmesh_renderer_amd_mlp", "dmesh_renderer_amd_hashgrid", "dmesh_renderer_amd_sh", "dmesh_renderer_amd_envmap",
-    "dmesh_renderer_amd_surface")]
+    "dmesh_renderer_amd_envmap_lod", "dmesh_renderer_amd_surface")]
 HEADERS = ["dmr_device.hpp", "dmr_kernels.hpp", "dmr_placement_key.hpp", "dmr_tile_order.hpp", "dmr_sort.hpp", "dmr_shade_common.hpp", "dmr_deferred_common.hpp",
-           "dmr_rows_common.hpp", "dmr_texture_wrap.hpp", "dmr_envmap_coords.hpp"] + PUBLIC_HEADERS
+           "dmr_rows_common.hpp", "dmr_texture_wrap.hpp", "dmr_envmap_coords.hpp", "dmr_envmap_lod_coords.hpp"] + PUBLIC_HEADERS
 ARCH = "gfx950"
 
 

@@ -66,6 +66,11 @@
 //   envmap_rows(d [N,3], envmap [He,We,C], n_rows=None) -> y [N,C] and envmap_rows_backward(..., grad_out, need_d, need_envmap)
 //   -> (dL_dd | None, dL_denvmap | None): direction rows looked up in a lat-long environment map (fragments.envmap_rows_fused),
 //   over include/dmesh_renderer_amd_envmap.h (SUPPORTS_FRAGMENT_ENVMAP)
+//   envmap_pyramid(envmap [He,We,C], levels) -> pyramid [T,C] and envmap_pyramid_backward(grad_pyramid, He, We, levels) -> dL_denvmap:
+//   the mip pyramid of a lat-long map (fragments.envmap_pyramid_fused); envmap_lod_rows(d [N,3], lod [N] or [N,1] (any stride >= 1),
+//   pyramid [T,C], He, We, levels, n_rows=None) -> y [N,C] and envmap_lod_rows_backward(..., grad_out, need_d, need_lod, need_pyramid)
+//   -> (dL_dd | None, dL_dlod | None, dL_dpyramid | None): direction rows looked up in it at a per-row level of detail
+//   (fragments.envmap_lod_rows_fused), over include/dmesh_renderer_amd_envmap_lod.h (SUPPORTS_FRAGMENT_ENVMAP_LOD)
 //   surface_packed(face, bary, row, n_used, faces, verts [P,3], origin [B,3], N) -> (hit, normal, reflect) [N,3] and
 //   surface_packed_backward(..., grad_hit, grad_normal, grad_reflect (None = zero), need=(verts, bary, origin)) -> those three
 //   gradients or None: the surface frame of packed rows (fragments.surface_packed_fused), over
@@ -97,6 +102,7 @@
 #include "../../include/dmesh_renderer_amd_hashgrid.h"
 #include "../../include/dmesh_renderer_amd_sh.h"
 #include "../../include/dmesh_renderer_amd_envmap.h"
+#include "../../include/dmesh_renderer_amd_envmap_lod.h"
 #include "../../include/dmesh_renderer_amd_surface.h"
 
 namespace {
@@ -157,6 +163,11 @@ struct Abi {
     // dmesh_renderer_amd_envmap.h: optional too (SUPPORTS_FRAGMENT_ENVMAP), both or none
     decltype(&dmr_envmap_rows) envmap_rows = nullptr;
     decltype(&dmr_envmap_rows_backward) envmap_rows_backward = nullptr;
+    // dmesh_renderer_amd_envmap_lod.h: optional too (SUPPORTS_FRAGMENT_ENVMAP_LOD), all four or none
+    decltype(&dmr_envmap_pyramid) envmap_pyramid = nullptr;
+    decltype(&dmr_envmap_pyramid_backward) envmap_pyramid_backward = nullptr;
+    decltype(&dmr_envmap_lod_rows) envmap_lod_rows = nullptr;
+    decltype(&dmr_envmap_lod_rows_backward) envmap_lod_rows_backward = nullptr;
     // dmesh_renderer_amd_surface.h: optional too (SUPPORTS_FRAGMENT_SURFACE), both or none
     decltype(&dmr_surface_packed) surface_packed = nullptr;
     decltype(&dmr_surface_packed_backward) surface_packed_backward = nullptr;
@@ -246,6 +257,12 @@ void load_abi() {
     g_abi.envmap_rows = reinterpret_cast<decltype(g_abi.envmap_rows)>(dlsym(g_abi.handle, "dmr_envmap_rows"));
     g_abi.envmap_rows_backward = reinterpret_cast<decltype(g_abi.envmap_rows_backward)>(dlsym(g_abi.handle, "dmr_envmap_rows_backward"));
     if (!g_abi.envmap_rows || !g_abi.envmap_rows_backward) g_abi.envmap_rows = nullptr, g_abi.envmap_rows_backward = nullptr;
+    g_abi.envmap_pyramid = reinterpret_cast<decltype(g_abi.envmap_pyramid)>(dlsym(g_abi.handle, "dmr_envmap_pyramid"));
+    g_abi.envmap_pyramid_backward = reinterpret_cast<decltype(g_abi.envmap_pyramid_backward)>(dlsym(g_abi.handle, "dmr_envmap_pyramid_backward"));
+    g_abi.envmap_lod_rows = reinterpret_cast<decltype(g_abi.envmap_lod_rows)>(dlsym(g_abi.handle, "dmr_envmap_lod_rows"));
+    g_abi.envmap_lod_rows_backward = reinterpret_cast<decltype(g_abi.envmap_lod_rows_backward)>(dlsym(g_abi.handle, "dmr_envmap_lod_rows_backward"));
+    if (!g_abi.envmap_pyramid || !g_abi.envmap_pyramid_backward || !g_abi.envmap_lod_rows || !g_abi.envmap_lod_rows_backward)
+        g_abi.envmap_pyramid = nullptr, g_abi.envmap_pyramid_backward = nullptr, g_abi.envmap_lod_rows = nullptr, g_abi.envmap_lod_rows_backward = nullptr;
     g_abi.surface_packed = reinterpret_cast<decltype(g_abi.surface_packed)>(dlsym(g_abi.handle, "dmr_surface_packed"));
     g_abi.surface_packed_backward = reinterpret_cast<decltype(g_abi.surface_packed_backward)>(dlsym(g_abi.handle, "dmr_surface_packed_backward"));
     if (!g_abi.surface_packed || !g_abi.surface_packed_backward) g_abi.surface_packed = nullptr, g_abi.surface_packed_backward = nullptr;
@@ -1585,6 +1602,103 @@ py::tuple envmap_rows_backward(In d, In envmap, const std::optional<at::Tensor>&
     return py::make_tuple(or_none(dd), or_none(de));
 }
 
+// -- envmap_pyramid / envmap_lod_rows: a mip pyramid of a lat-long map and direction rows looked up in it at a per-row level of
+// detail (dmesh_renderer_amd_envmap_lod.h).  The spec (He, We, L) -> T, the pyramid's rows; `call` starts the messages.
+int64_t pyramid_rows(const char* call, int64_t C, int64_t He, int64_t We, int64_t L) {
+    const std::string n = std::string(call) + ": ";
+    if (C < 1 || C > DMR_ENVMAP_LOD_MAX_CHANNELS) err(n + "C must be in 1..16, got " + std::to_string(C));
+    if (L < 1 || L > DMR_ENVMAP_LOD_MAX_LEVELS) err(n + "levels must be in 1..12, got " + std::to_string(L));
+    if (He < 1 || We < 1) err(n + "the map must have at least one texel");
+    const int64_t mask = ((int64_t)1 << (L - 1)) - 1;
+    if ((He & mask) || (We & mask)) err(n + "He and We must be multiples of 2^(levels-1)");
+    int64_t T = 0;
+    for (int64_t l = 0; l < L; l++) T += (He >> l) * (We >> l);
+    if (T * ((C + 3) / 4) >= ((int64_t)1 << 31)) err(n + "T * ceil(C / 4) must be below 2^31");
+    return T;
+}
+
+// envmap [He,We,C] -> pyramid [T,C]
+at::Tensor envmap_pyramid(In envmap, int64_t levels) {
+    built(g_abi.envmap_pyramid, "dmr_envmap_pyramid");
+    const c10::Device dev = hip_device_of(envmap);
+    if (envmap.dim() != 3) err("envmap must have dimensions (He, We, C)");
+    const int64_t He = envmap.size(0), We = envmap.size(1), C = envmap.size(2);
+    const int64_t T = pyramid_rows("envmap_pyramid", C, He, We, levels);
+    const at::Tensor e = f32(envmap, "envmap");
+    c10::DeviceGuard guard(dev);
+    at::Tensor pyramid = at::empty({T, C}, f32_on(dev));
+    if (g_abi.envmap_pyramid((int)C, (int)He, (int)We, (int)levels, mptr<const float>(e), mptr<float>(pyramid), stream_on(dev))) raise_lib();
+    return pyramid;
+}
+
+// grad_pyramid [T,C] -> dL_denvmap [He,We,C]
+at::Tensor envmap_pyramid_backward(In grad_pyramid, int64_t He, int64_t We, int64_t levels) {
+    built(g_abi.envmap_pyramid_backward, "dmr_envmap_pyramid_backward");
+    const c10::Device dev = hip_device_of(grad_pyramid);
+    if (grad_pyramid.dim() != 2) err("grad_pyramid must have dimensions (T, C)");
+    const int64_t C = grad_pyramid.size(1);
+    if (pyramid_rows("envmap_pyramid_backward", C, He, We, levels) != grad_pyramid.size(0)) err("grad_pyramid must have dimensions (T, C) of the spec");
+    const at::Tensor g = f32(grad_pyramid, "grad_pyramid");
+    c10::DeviceGuard guard(dev);
+    at::Tensor de = at::empty({He, We, C}, f32_on(dev));
+    if (g_abi.envmap_pyramid_backward((int)C, (int)He, (int)We, (int)levels, mptr<const float>(g), mptr<float>(de), stream_on(dev))) raise_lib();
+    return de;
+}
+
+struct EnvLodArgs : RowArgs {
+    at::Tensor lod, pyramid;  // lod: a 1-D view, read in place at its own stride
+    int64_t He = 0, We = 0, L = 0, C = 0, T = 0, lod_stride = 1;
+    const float* lod_ptr() const { return N ? lod.data_ptr<float>() : nullptr; }
+};
+
+EnvLodArgs envmap_lod_args(In d, In lod, In pyramid, int64_t He, int64_t We, int64_t levels, const std::optional<at::Tensor>& n_rows) {
+    EnvLodArgs a;
+    rows_begin(a, "envmap_lod_rows", g_abi.envmap_lod_rows, d, 3, "3");
+    if (!(lod.dim() == 1 || (lod.dim() == 2 && lod.size(1) == 1)) || lod.size(0) != a.N) err("lod must have dimensions (rows,) or (rows, 1)");
+    if (pyramid.dim() != 2) err("pyramid must have dimensions (T, C)");
+    a.He = He; a.We = We; a.L = levels; a.C = pyramid.size(1);
+    a.T = pyramid_rows("envmap_lod_rows", a.C, He, We, levels);
+    if (pyramid.size(0) != a.T) err("envmap_lod_rows: pyramid must have the " + std::to_string(a.T) + " rows of the spec, got " + std::to_string(pyramid.size(0)));
+    check_row_count(a);
+    check_n_rows(n_rows);
+    on_device_of_x(a, lod, "envmap_lod_rows: lod");
+    on_device_of_x(a, pyramid, "envmap_lod_rows: pyramid");
+    rows_devices_end(a, d, n_rows);
+    if (lod.scalar_type() != at::kFloat) err("expected scalar type Float but found " + dtype_name(lod) + " (lod)");
+    a.lod = lod.dim() == 2 ? lod.select(1, 0) : lod;
+    if (a.N > 1 && (a.lod.stride(0) < 1 || a.lod.stride(0) > INT32_MAX)) a.lod = a.lod.contiguous();  // (an expanded or flipped view)
+    a.lod_stride = a.N > 1 ? a.lod.stride(0) : 1;
+    a.pyramid = f32(pyramid, "pyramid");
+    rows_finish(a, n_rows);
+    return a;
+}
+
+// -> y [N,C]
+at::Tensor envmap_lod_rows(In d, In lod, In pyramid, int64_t He, int64_t We, int64_t levels, const std::optional<at::Tensor>& n_rows) {
+    const EnvLodArgs a = envmap_lod_args(d, lod, pyramid, He, We, levels, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    at::Tensor y = at::empty({a.N, a.C}, f32_on(a.dev));
+    if (g_abi.envmap_lod_rows((int)a.N, (int)a.C, (int)a.He, (int)a.We, (int)a.L, (int)a.lod_stride, mptr<const float>(a.x), a.lod_ptr(),
+                              mptr<const float>(a.pyramid), a.rows_ptr(), mptr<float>(y), a.stream()))
+        raise_lib();
+    return y;
+}
+
+// need_d, need_lod, need_pyramid -> (dL_dd [N,3], dL_dlod [N], dL_dpyramid [T,C]), None where not asked for; grad_out [N,C]
+py::tuple envmap_lod_rows_backward(In d, In lod, In pyramid, int64_t He, int64_t We, int64_t levels, const std::optional<at::Tensor>& n_rows,
+                                   In grad_out, bool need_d, bool need_lod, bool need_pyramid) {
+    const EnvLodArgs a = envmap_lod_args(d, lod, pyramid, He, We, levels, n_rows);
+    c10::DeviceGuard guard(a.dev);
+    check_grad_out(a, grad_out, a.C, "C");
+    const at::Tensor go = f32(grad_out, "grad_out");
+    at::Tensor dd = grad_if(need_d, {a.N, 3}, a.dev), dl = grad_if(need_lod, {a.N}, a.dev), dp = grad_if(need_pyramid, {a.T, a.C}, a.dev);
+    if (g_abi.envmap_lod_rows_backward((int)a.N, (int)a.C, (int)a.He, (int)a.We, (int)a.L, (int)a.lod_stride, mptr<const float>(a.x), a.lod_ptr(),
+                                       mptr<const float>(a.pyramid), a.rows_ptr(), mptr<const float>(go), out_ptr(dd), out_ptr(dl), out_ptr(dp),
+                                       a.stream()))
+        raise_lib();
+    return py::make_tuple(or_none(dd), or_none(dl), or_none(dp));
+}
+
 py::tuple profile_collect() {
     std::vector<double> ms(DMR_NUM_STAGES, 0.0);
     std::vector<int64_t> cnt(DMR_NUM_STAGES, 0);
@@ -1675,6 +1789,12 @@ PYBIND11_MODULE(_C, m) {
     m.def("envmap_rows", &envmap_rows, py::arg("d"), py::arg("envmap"), py::arg("n_rows") = py::none());
     m.def("envmap_rows_backward", &envmap_rows_backward, py::arg("d"), py::arg("envmap"), py::arg("n_rows"), py::arg("grad_out"), py::arg("need_d"),
           py::arg("need_envmap"));
+    m.def("envmap_pyramid", &envmap_pyramid, py::arg("envmap"), py::arg("levels"));
+    m.def("envmap_pyramid_backward", &envmap_pyramid_backward, py::arg("grad_pyramid"), py::arg("He"), py::arg("We"), py::arg("levels"));
+    m.def("envmap_lod_rows", &envmap_lod_rows, py::arg("d"), py::arg("lod"), py::arg("pyramid"), py::arg("He"), py::arg("We"), py::arg("levels"),
+          py::arg("n_rows") = py::none());
+    m.def("envmap_lod_rows_backward", &envmap_lod_rows_backward, py::arg("d"), py::arg("lod"), py::arg("pyramid"), py::arg("He"), py::arg("We"),
+          py::arg("levels"), py::arg("n_rows"), py::arg("grad_out"), py::arg("need_d"), py::arg("need_lod"), py::arg("need_pyramid"));
     m.def("surface_packed", &surface_packed, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"), py::arg("faces"), py::arg("verts"),
           py::arg("origin"), py::arg("rows"));
     m.def("surface_packed_backward", &surface_packed_backward, py::arg("face"), py::arg("bary"), py::arg("row"), py::arg("n_used"), py::arg("faces"),
@@ -1721,6 +1841,8 @@ PYBIND11_MODULE(_C, m) {
     m.attr("SUPPORTS_FRAGMENT_SH") = g_abi.sh_rows != nullptr;
     // fragments.envmap_rows_fused; False: the loaded library predates dmesh_renderer_amd_envmap.h
     m.attr("SUPPORTS_FRAGMENT_ENVMAP") = g_abi.envmap_rows != nullptr;
+    // fragments.envmap_pyramid_fused / envmap_lod_rows_fused; False: the loaded library predates dmesh_renderer_amd_envmap_lod.h
+    m.attr("SUPPORTS_FRAGMENT_ENVMAP_LOD") = g_abi.envmap_lod_rows != nullptr;
     // fragments.surface_packed_fused; False: the loaded library predates dmesh_renderer_amd_surface.h
     m.attr("SUPPORTS_FRAGMENT_SURFACE") = g_abi.surface_packed != nullptr;
     m.attr("STAGE_PROJECT") = (int)DMR_STAGE_PROJECT; m.attr("STAGE_SETUP_FACES") = (int)DMR_STAGE_SETUP_FACES;

@@ -59,6 +59,16 @@ one forward and one backward kernel, differentiable in verts, frag.bary and the 
     s = FG.surface_packed_fused(frag, packed, faces, verts, FG.camera_origins(mv_mats))       # SurfaceRows(hit, normal, reflect), each [N,3]
     enc = th.cat([grid(s.hit, n_rows=n), FG.sh_rows_fused(s.reflect, 4, n_rows=n), s.normal], 1)
     rgb = mlp(enc, n_rows=n) + env(s.reflect, n_rows=n)                                       # diffuse + specular lookup
+A ROUGH SURFACE needs that lookup in a blurred copy of the map, chosen per row: a single tap makes every surface a perfect mirror.
+envmap_pyramid is the torch model of a mip pyramid [T,C] of the map (a 2 x 2 box chain in the map's own parameterisation, not a
+GGX prefilter), envmap_lod_rows that of the trilinear lookup -- bilinear in two adjacent levels, linear in a level of detail per
+row, differentiable in the direction, the level of detail and the pyramid; envmap_pyramid_fused and envmap_lod_rows_fused
+(csrc/dmr_envmap_lod.hip) the same on HIP, EnvMapPyramid the nn.Module that owns the base map and builds the pyramid per call:
+    s   = FG.surface_packed_fused(frag, packed, faces, verts, FG.camera_origins(mv_mats))
+    out = mlp(enc, n_rows=n)                                  # [M,4]: rgb + roughness
+    env = FG.EnvMapPyramid(256, 512).to(dev)
+    spec = env(s.reflect, out[:, 3].sigmoid() * (env.levels - 1), n_rows=n)   # lod from roughness, the caller's mapping
+    image, T = FG.composite_values_packed_fused(frag, packed, faces_opacity, out[:, :3] + spec)
 What is HELD CONSTANT by every
 function here -- it comes from the rasteriser as data, not as a function of the scene -- is
   * which faces a pixel blends (coverage, and where its walk stopped),
@@ -98,7 +108,8 @@ __all__ = ["blend_weights", "interpolate", "composite", "face_visibility", "comp
            "composite_values_packed", "composite_values_packed_fused", "unpack_values", "mlp_rows", "mlp_rows_fused", "RowMLP",
            "HashGridSpec", "hashgrid_spec", "hashgrid_rows", "hashgrid_rows_fused", "HashGrid",
            "packed_row_views", "packed_row_views_fused", "sh_rows", "sh_rows_fused", "camera_origins", "ViewSH",
-           "envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions", "SurfaceRows", "surface_packed", "surface_packed_fused"]
+           "envmap_rows", "envmap_rows_fused", "EnvMap", "pixel_directions", "SurfaceRows", "surface_packed", "surface_packed_fused",
+           "envmap_pyramid", "envmap_pyramid_fused", "envmap_lod_rows", "envmap_lod_rows_fused", "EnvMapPyramid"]
 
 WRAPS = ("clamp", "repeat")  # the index into it is the C calls' `wrap`
 
@@ -242,6 +253,8 @@ _FUSED = {"composite": ("SUPPORTS_FRAGMENT_COMPOSITE", "fragment"), "composite_t
           "packed_row_views": ("SUPPORTS_FRAGMENT_SH", "packed row", "view map"),
           "sh_rows": ("SUPPORTS_FRAGMENT_SH", "row", "spherical-harmonics encoding"),
           "envmap_rows": ("SUPPORTS_FRAGMENT_ENVMAP", "row", "environment-map lookup"),
+          "envmap_pyramid": ("SUPPORTS_FRAGMENT_ENVMAP_LOD", "row", "environment-map pyramid"),
+          "envmap_lod_rows": ("SUPPORTS_FRAGMENT_ENVMAP_LOD", "row", "environment-map lookup by level of detail"),
           "surface_packed": ("SUPPORTS_FRAGMENT_SURFACE", "packed row", "surface frame")}
 
 
@@ -1420,8 +1433,8 @@ def envmap_rows(d: th.Tensor, envmap: th.Tensor, *, n_rows: Optional[th.Tensor] 
     Differentiable in d and envmap: dL/denvmap is the four weights times the upstream, summed over the rows; dL/dd goes through
     (x, y), (phi, theta) and the normalisation, the cell (the floors) held constant as in composite_texture.  In float32 the
     coordinates carry the rounding of the two atan2 times the map's size: the deviation from float64 grows with He and We.
-    Not modelled: mip levels, cube maps, a map per view, a nearest filter.  Plain torch, any device, any float dtype: the model
-    envmap_rows_fused is tested against."""
+    Not modelled: mip levels (envmap_lod_rows looks up a pyramid of this map), cube maps, a map per view, a nearest filter.
+    Plain torch, any device, any float dtype: the model envmap_rows_fused is tested against."""
     _envmap_arguments("envmap_rows", d, envmap, n_rows)
     N, (He, We, C) = d.shape[0], envmap.shape
     zero = th.zeros((), dtype=d.dtype, device=d.device)
@@ -1519,6 +1532,259 @@ class EnvMap(th.nn.Module):
             d = d @ self.frame.to(d.dtype).T
         fused = d.is_cuda and d.dtype == th.float32 and self.envmap.dtype == th.float32
         return (envmap_rows_fused if fused else envmap_rows)(d, self.envmap, n_rows=n_rows)
+
+
+# ---------------------------------------------------------------------------
+# A mip pyramid of that map, looked up at a per-row level of detail: the specular term of a rough surface (csrc/dmr_envmap_lod.hip)
+# ---------------------------------------------------------------------------
+ENVMAP_LOD_MAX_LEVELS = 12   # DMR_ENVMAP_LOD_MAX_LEVELS
+
+
+def _pyramid_spec(name: str, He, We, L, C) -> Tuple[list, int]:
+    """THE LAYOUT of a pyramid (include/dmesh_renderer_amd_envmap_lod.h), restated: the spec is (He, We, L), 1 <= L <= 12; level l
+    has He >> l rows and We >> l columns, He and We multiples of 2^(L-1); pyramid [T,C] holds level l as the row-major
+    [He_l, We_l, C] block that starts at row off_l = sum_{j<l} He_j We_j; level 0 is the base map.  What every function here
+    refuses of a spec (ValueError), in this order: C, L, an empty map, the multiples, a pyramid too large for the kernels' keys.
+    -> ([off_0, ..., off_{L-1}], T)"""
+    if not 1 <= C <= ENVMAP_MAX_CHANNELS:
+        raise ValueError(f"{name}: C must be in 1..{ENVMAP_MAX_CHANNELS}, got {C}")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (He, We, L)) or not 1 <= L <= ENVMAP_LOD_MAX_LEVELS:
+        raise ValueError(f"{name}: levels must be an int in 1..{ENVMAP_LOD_MAX_LEVELS} (the spec: ints (He, We, L)), got {(He, We, L)!r}")
+    if He < 1 or We < 1:
+        raise ValueError(f"{name}: the map must have at least one texel, got {(He, We)}")
+    if He % (1 << (L - 1)) or We % (1 << (L - 1)):
+        raise ValueError(f"{name}: He and We must be multiples of 2^(levels-1) = {1 << (L - 1)}, got {(He, We)}")
+    offs, T = [], 0
+    for l in range(L):
+        offs.append(T)
+        T += (He >> l) * (We >> l)
+    if T * ((C + 3) // 4) >= 2 ** 31:
+        raise ValueError(f"{name}: T * ceil(C / 4) must be below 2^31, got T = {T}, C = {C}")
+    return offs, T
+
+
+def _pyramid_arguments(name: str, envmap, levels):
+    """What envmap_pyramid and envmap_pyramid_fused both refuse (ValueError): envmap [He,We,C], then the spec (_pyramid_spec)."""
+    if envmap.dim() != 3:
+        raise ValueError(f"{name}: envmap must be [He,We,C], got {tuple(envmap.shape)}")
+    He, We, C = envmap.shape
+    return _pyramid_spec(name, He, We, levels, C)
+
+
+def envmap_pyramid(envmap: th.Tensor, levels: int) -> th.Tensor:
+    """The mip pyramid of a lat-long map envmap [He,We,C] -> [T,C] in _pyramid_spec's layout, `levels` = L of them: level 0 is
+    the map itself, level l+1 at (i, j) is
+        ((a + b) + (c + d)) * 0.25,   a, b = level l at (2i, 2j), (2i, 2j+1);  c, d = the same columns of row 2i+1
+    -- this order of summation is part of the contract: envmap_pyramid_fused equals it bit for bit.  A BOX mip chain in the map's
+    own parameterisation, NOT a solid-angle or GGX prefilter; envmap_lod_rows accepts any [T,C] tensor in this layout, so a caller
+    may pass a pyramid prefiltered elsewhere.  Differentiable in envmap.  Plain torch, any device, any float dtype."""
+    _pyramid_arguments("envmap_pyramid", envmap, levels)
+    C = envmap.shape[2]
+    out, cur = [envmap.reshape(-1, C)], envmap
+    for _ in range(levels - 1):
+        cur = ((cur[0::2, 0::2] + cur[0::2, 1::2]) + (cur[1::2, 0::2] + cur[1::2, 1::2])) * 0.25
+        out.append(cur.reshape(-1, C))
+    return th.cat(out, 0)
+
+
+class _EnvMapPyramidFn(th.autograd.Function):
+    """envmap_pyramid_fused over _C.envmap_pyramid / _C.envmap_pyramid_backward.  Arguments: envmap, levels.  Nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, envmap, levels):
+        ctx.spec = (envmap.shape[0], envmap.shape[1], levels)
+        ctx.set_materialize_grads(False)
+        return _fused_kernels("envmap_pyramid").envmap_pyramid(envmap, levels)
+
+    @staticmethod
+    def backward(ctx, grad_pyramid):
+        if grad_pyramid is None or not ctx.needs_input_grad[0]:
+            return None, None
+        return _fused_kernels("envmap_pyramid").envmap_pyramid_backward(grad_pyramid.contiguous(), *ctx.spec), None
+
+
+def envmap_pyramid_fused(envmap: th.Tensor, levels: int) -> th.Tensor:
+    """envmap_pyramid(...) on HIP: one small launch per level, each reading the level below, and for the backward one gather
+    launch without atomics -- per base texel (y, x) Horner from the coarsest level down, acc = g_l[y >> l, x >> l] + 0.25 acc.
+    Multiplying by 0.25 is exact: both directions equal envmap_pyramid in float32 bit for bit on finite, normal values.  A HIP
+    float32 tensor only (made contiguous if it is not): anything else is a TypeError -- envmap_pyramid is the torch path for it;
+    nothing falls back silently.  Refused in this order: an older binding, the arguments (as envmap_pyramid), the dtype, the device."""
+    name, torch_path = "envmap_pyramid_fused", "fragments.envmap_pyramid is the torch path for anything else"
+    _fused_kernels("envmap_pyramid")
+    _pyramid_arguments(name, envmap, levels)
+    _check_row_tensors(name, torch_path, envmap, [("envmap", envmap)], [])
+    return _EnvMapPyramidFn.apply(envmap, levels)
+
+
+def _envmap_lod_angles(d, n_rows):
+    """(ok [N] bool, phi [N], theta [N]) of direction rows d [N,3], by envmap_rows' own lines (that function stays as it is, the
+    model of the single-level unit): ok is False in a skipped row (whose phi and theta are those of +x, with an exact 0 gradient);
+    at a pole phi = 0 and both angles are constants."""
+    N = d.shape[0]
+    zero = th.zeros((), dtype=d.dtype, device=d.device)
+    live = th.ones(N, dtype=th.bool, device=d.device)
+    if n_rows is not None:
+        live = live & (th.arange(N, device=d.device) < n_rows.reshape(1).clamp(min=0))
+    w = th.where(live.unsqueeze(1), d, zero)
+    n = th.sqrt((w.detach() * w.detach()).sum(1))
+    ok = live & th.isfinite(n) & ~(n < ENVMAP_MIN_LENGTH)
+    ex = th.zeros(3, dtype=d.dtype, device=d.device)
+    ex[0] = 1
+    safe = th.where(ok.unsqueeze(1), w, ex)        # (the rows that are not ok leave here: their gradient is an exact 0)
+    u = safe / th.sqrt((safe * safe).sum(1, keepdim=True))
+    pole = (u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]).detach() < ENVMAP_POLE_RHO2
+    us = th.where(pole.unsqueeze(1), ex, u)        # (... and the poles here)
+    rho = th.sqrt(us[:, 0] * us[:, 0] + us[:, 1] * us[:, 1])
+    phi = th.atan2(us[:, 1], us[:, 0])
+    theta = th.atan2(rho, us[:, 2])
+    theta = th.where(pole, th.where(u[:, 2].detach() > 0, zero, zero + math.pi), theta)
+    return ok, phi, theta
+
+
+def _envmap_lod_bilinear(table, off, He, We, phi, theta):
+    """[N,C]: envmap_rows' bilinear mix at (phi, theta) [N], per row in the row-major [He,We,C] block of table [T,C] that starts at
+    its row `off` -- texel centres at half-integers, the floors from the unwrapped coordinates and held constant, columns repeating
+    and rows clamped.  off, He, We: int64 tensors [N] on phi's device (a row's level of the pyramid)."""
+    x = (phi / (2 * math.pi) + 0.5) * We.to(phi.dtype) - 0.5
+    y = (theta / math.pi) * He.to(phi.dtype) - 0.5
+    x0, y0 = x.detach().floor(), y.detach().floor()
+    fx, fy = (x - x0).unsqueeze(1), (y - y0).unsqueeze(1)
+    ix0, ix1 = th.remainder(x0.long(), We), th.remainder(x0.long() + 1, We)
+    iy0, iy1 = th.minimum(y0.long().clamp(min=0), He - 1), th.minimum((y0.long() + 1).clamp(min=0), He - 1)
+    r0, r1 = off + iy0 * We, off + iy1 * We
+    return (1 - fy) * ((1 - fx) * table[r0 + ix0] + fx * table[r0 + ix1]) + fy * ((1 - fx) * table[r1 + ix0] + fx * table[r1 + ix1])
+
+
+def _envmap_lod_arguments(name: str, d, lod, pyramid, levels, n_rows):
+    """What envmap_lod_rows and envmap_lod_rows_fused both refuse (ValueError), in this order: d [N,3], lod [N] or [N,1], pyramid
+    [T,C], levels = (He, We, L), the spec (_pyramid_spec), the pyramid's T, n_rows.  -> ((He, We, L), [off_l])"""
+    if d.dim() != 2 or d.shape[1] != 3:
+        raise ValueError(f"{name}: d must be [N,3], got {tuple(d.shape)}")
+    if tuple(lod.shape) not in ((d.shape[0],), (d.shape[0], 1)):
+        raise ValueError(f"{name}: lod must be [N] or [N,1] = {(d.shape[0],)}, got {tuple(lod.shape)}")
+    if pyramid.dim() != 2:
+        raise ValueError(f"{name}: pyramid must be [T,C], got {tuple(pyramid.shape)}")
+    if not isinstance(levels, (tuple, list)) or len(levels) != 3:
+        raise ValueError(f"{name}: levels must be the spec (He, We, L), got {levels!r}")
+    He, We, L = levels
+    offs, T = _pyramid_spec(name, He, We, L, pyramid.shape[1])
+    if pyramid.shape[0] != T:
+        raise ValueError(f"{name}: pyramid must have the T = {T} rows of the spec {(He, We, L)}, got {tuple(pyramid.shape)}")
+    _check_n_rows(name, n_rows)
+    return (He, We, L), offs
+
+
+def envmap_lod_rows(d: th.Tensor, lod: th.Tensor, pyramid: th.Tensor, levels: Tuple[int, int, int], *,
+                    n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """Direction rows d [N,3] looked up in a mip pyramid [T,C] of a lat-long map (envmap_pyramid's layout, levels = (He, We, L))
+    at a level of detail per row, lod [N] or [N,1] -> [N,C]: bilinear in two adjacent levels, linear between them.  Per row r:
+        n, u, rho2, theta, phi, s, t, the pole rule and the SKIPPED row exactly as envmap_rows states them; a skipped row reads
+            neither lod nor the upstream, gives exact zeros in y, dL/dd and dL/dlod and adds nothing to dL/dpyramid
+        lam = lod >= 0 ? (lod <= L-1 ? lod : L-1) : 0 (a NaN compares false and becomes 0, +Inf becomes L-1)
+        inside = lod > 0 and lod < L-1;  l0 = min(floor(lam), L-2), l1 = l0 + 1, f = lam - l0 in [0, 1];  L == 1: l0 = l1 = 0, f = 0
+        B_l = envmap_rows' bilinear mix at level l: its own x = s We_l - 0.5, y = t He_l - 0.5, floors and fractions, columns
+            repeating and rows clamped on (We_l, He_l)
+        y[r] = (1-f) B_l0 + f B_l1.
+    Differentiable in d, lod and pyramid: dL/dlod = (B_l1 - B_l0) . g where inside holds and an exact 0 elsewhere (at an integer
+    lod the derivative to the right); dL/dd holds the cell constant at both levels and is an exact 0 at a pole; dL/dpyramid is the
+    eight weights times the upstream, summed over the rows.  The level of detail is the caller's mapping (from a roughness, say).
+    Not modelled: a GGX or solid-angle prefilter, cube maps, anisotropic footprints, a level from screen-space derivatives.  Plain
+    torch, any device, any float dtype: the model envmap_lod_rows_fused is tested against."""
+    (He, We, L), offs = _envmap_lod_arguments("envmap_lod_rows", d, lod, pyramid, levels, n_rows)
+    ok, phi, theta = _envmap_lod_angles(d, n_rows)
+    zero = th.zeros((), dtype=d.dtype, device=d.device)
+    lod = th.where(ok, lod.reshape(-1).to(d.dtype), zero)       # (a skipped row's lod leaves here)
+    top = float(L - 1)
+    lam = th.where(lod >= 0, th.where(lod <= top, lod, zero + top), zero).detach()
+    inside = ((lod > 0) & (lod < top)).detach()
+    lam = th.where(inside, lod, lam)                            # (the gradient passes where inside holds, and only there)
+    l0 = lam.detach().floor().long().clamp(max=L - 2).clamp(min=0)
+    l1 = (l0 + 1).clamp(max=L - 1)
+    f = (lam - l0.to(d.dtype)).unsqueeze(1)                     # (L == 1: lam = 0 = l0)
+    off, hs, ws = (th.tensor(v, dtype=th.int64, device=d.device) for v in (offs, [He >> l for l in range(L)], [We >> l for l in range(L)]))
+    table = pyramid.to(d.dtype)
+    b0, b1 = (_envmap_lod_bilinear(table, off[l], hs[l], ws[l], phi, theta) for l in (l0, l1))
+    return th.where(ok.unsqueeze(1), (1 - f) * b0 + f * b1, zero)
+
+
+class _EnvMapLodRowsFn(th.autograd.Function):
+    """envmap_lod_rows_fused over _C.envmap_lod_rows / _C.envmap_lod_rows_backward.  Arguments: d, lod (as given: [N] or [N,1] at its
+    own stride), pyramid, n_rows (a tensor or None), He, We, L.  Only the tensors are saved: nothing of size [N,C]."""
+
+    @staticmethod
+    def forward(ctx, d, lod, pyramid, n_rows, He, We, L):
+        y = _fused_kernels("envmap_lod_rows").envmap_lod_rows(d, lod, pyramid, He, We, L, n_rows)
+        _save_optional(ctx, d, lod, pyramid, n_rows)
+        ctx.spec = (He, We, L)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None, and goes down as None: no launch
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        need = ctx.needs_input_grad[:3]
+        if grad_y is None or not any(need):
+            return (None,) * 7
+        d, lod, pyramid, n_rows = _saved_optional(ctx)
+        dd, dlod, dpyr = _fused_kernels("envmap_lod_rows").envmap_lod_rows_backward(d, lod, pyramid, *ctx.spec, n_rows, grad_y.contiguous(), *need)
+        return dd, None if dlod is None else dlod.view(lod.shape), dpyr, None, None, None, None
+
+
+def envmap_lod_rows_fused(d: th.Tensor, lod: th.Tensor, pyramid: th.Tensor, levels: Tuple[int, int, int], *,
+                          n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+    """envmap_lod_rows(...) as one HIP kernel, and one for its backward (plus the one that zeroes dL_dpyramid): a lane owns a row,
+    evaluates the two atan2, the square root and the normalisation ONCE, forms the eight texel addresses and weights from (s, t) per
+    level and takes the channels in chunks of four (float4 texel reads when C % 4 == 0).  The forward does not read a level whose
+    weight is exactly 0.  The backward computes each gradient only when autograd asks for it: dL/dd and dL/dlod are plain stores
+    per row; dL/dpyramid sums on chip what shares a texel -- the lanes of a wave, then a per-workgroup LDS table of f64 cells --
+    before float atomics leave (so it depends on the order of summation in its last bits; y, dL_dd and dL_dlod do not).  lod is
+    read in place at its own stride: a column of a wider tensor (out[:, 3] of an MLP's output) needs no copy.  n_rows is read on
+    the device: no host wait, capturable.  Whatever the bits of d and lod, every access is in bounds.  N < 2^31 (ValueError).  HIP
+    float32 tensors on one device only (n_rows int32 [1]): anything else is a TypeError -- envmap_lod_rows is the torch path for
+    it; nothing falls back silently.  Refused in this order: an older binding, the arguments (as envmap_lod_rows), N, the dtypes,
+    the devices."""
+    name, torch_path = "envmap_lod_rows_fused", "fragments.envmap_lod_rows is the torch path for anything else"
+    _fused_kernels("envmap_lod_rows")
+    (He, We, L), _ = _envmap_lod_arguments(name, d, lod, pyramid, levels, n_rows)
+    _check_row_tensors(name, torch_path, d, [("d", d), ("lod", lod), ("pyramid", pyramid)], [("n_rows", n_rows)])
+    return _EnvMapLodRowsFn.apply(d, lod, pyramid, None if n_rows is None else n_rows.reshape(1), He, We, L)
+
+
+class EnvMapPyramid(th.nn.Module):
+    """A lat-long environment map looked up at a per-row level of detail, as a Module that owns the BASE map `envmap` (a Parameter
+    [height, width, channels], initialised to 0.5 like EnvMap's) and builds its mip pyramid in every forward: the specular term of
+    a rough surface.  levels: L of the pyramid; None: the largest the sizes allow (height and width multiples of 2^(L-1)), up to
+    12.  frame: EnvMap's.  .levels = L, .out_features = channels.
+    forward(d, lod, n_rows=None) runs envmap_pyramid_fused and envmap_lod_rows_fused on HIP float32 rows and the torch models on
+    anything else; the gradient reaches envmap through the pyramid.  lod is the caller's mapping, roughness * (levels - 1), say."""
+
+    def __init__(self, height: int, width: int, channels: int = 3, levels: Optional[int] = None, frame: Optional[th.Tensor] = None):
+        super().__init__()
+        for what, v in (("height", height), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"EnvMapPyramid: {what} must be a positive int, got {v!r}")
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= ENVMAP_MAX_CHANNELS:
+            raise ValueError(f"EnvMapPyramid: channels must be an int in 1..{ENVMAP_MAX_CHANNELS}, got {channels!r}")
+        if levels is None:
+            levels = 1
+            while levels < ENVMAP_LOD_MAX_LEVELS and height % (1 << levels) == 0 and width % (1 << levels) == 0:
+                levels += 1
+        _pyramid_spec("EnvMapPyramid", height, width, levels, channels)
+        if frame is not None:
+            frame = th.as_tensor(frame, dtype=th.float32)
+            if tuple(frame.shape) != (3, 3):
+                raise ValueError(f"EnvMapPyramid: frame must be [3,3], got {tuple(frame.shape)}")
+            frame = frame.clone()
+        self.register_buffer("frame", frame)
+        self.out_features, self.levels = channels, levels
+        self.envmap = th.nn.Parameter(th.full((height, width, channels), 0.5))
+
+    def forward(self, d: th.Tensor, lod: th.Tensor, n_rows: Optional[th.Tensor] = None) -> th.Tensor:
+        if self.frame is not None:
+            d = d @ self.frame.to(d.dtype).T
+        spec = (self.envmap.shape[0], self.envmap.shape[1], self.levels)
+        if d.is_cuda and d.dtype == th.float32 and lod.dtype == th.float32 and self.envmap.dtype == th.float32:
+            return envmap_lod_rows_fused(d, lod, envmap_pyramid_fused(self.envmap, self.levels), spec, n_rows=n_rows)
+        return envmap_lod_rows(d, lod, envmap_pyramid(self.envmap, self.levels), spec, n_rows=n_rows)
 
 
 def pixel_directions(mv_mats: th.Tensor, proj_mats: th.Tensor, H: int, W: int) -> th.Tensor:

@@ -34,7 +34,8 @@
  *       Gx = sum_c g_c dy_c/dx, Gy alike;  gu = (We Gx / (2 pi)) (-uy, ux, 0) / rho2 - (He Gy / pi) (0, 0, 1) / sqrt(rho2);
  *       dL_dd[r] = (gu - u (u . gu)) / n: one plain store per row, no atomics; y and dL_dd do not depend on any order.
  *
- * Out of scope: mip levels and prefiltered roughness, cube maps, a map per view, a nearest filter, HDR file reading.
+ * Out of scope: mip levels and prefiltered roughness (dmesh_renderer_amd_envmap_lod.h looks up a mip pyramid of such a map at a
+ * per-row level of detail), cube maps, a map per view, a nearest filter, HDR file reading.
  *
  * Limits: 0 <= N < 2^31, 1 <= C <= DMR_ENVMAP_MAX_CHANNELS, He, We >= 1, He * We * ceil(C / 4) < 2^31.
  *
